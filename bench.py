@@ -2,9 +2,16 @@
 """
 bench.py - MPC steps/s of the MI355X-native RDA ADMM inner solver (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W                # plain run: the headline loop and its line, nothing else
+    python bench.py --gpus 1 --steps K --warmup W --full         # + every other leg, check, size and roofline described below
+    python bench.py ... --dump-outputs DIR                        # + what the last timed step handed back, as DIR/<name>.npy (float64)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
-    python bench.py --only-headline --steps 200 --warmup 10       # the headline loop and nothing else (what tools/profile_round.sh profiles)
+    python bench.py --only-headline --steps 200 --warmup 10       # the headline loop + its timing pass (what tools/profile_round.sh profiles)
+
+A plain run sets up the workload, runs W warm-up and then EXACTLY K timed steps of the headline closed loop, writes the outputs of the last
+timed step when --dump-outputs is given, and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the
+K steps / K, ...).  Everything below that is not the headline figure itself - the recorded Python closed loops and the comparison with them,
+the second window, the other legs, `sizes`, rooflines, cpu_baseline, the obstacle-shard leg - runs with --full only.
 
 One "step" = one RDA_solver.iterative_solve (reference rda_solver.py:573-610): up to iter_num
 ADMM iterations with early stop.  Workload (north-star point of BASELINE.json / SURVEY.md 8d):
@@ -60,6 +67,10 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--n-obs", type=int, default=200)
     ap.add_argument("--horizon", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="every leg, check, size, roofline and baseline besides the headline loop (a plain run "
+                    "times the headline loop and prints its line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one handed back (applied "
+                    "control, robot state, residuals, solver duals) as DIR/<name>.npy, float64, <= 64 MB in all")
     ap.add_argument("--only-headline", action="store_true", help="the headline closed loop (+ its hipEvent timing pass) and nothing else: no recorded "
                     "traces, no comparison, no other leg - every kernel launch of the process belongs to the loop `value` comes from (profiles)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -81,7 +92,9 @@ def parse_args():
                          "with an RCCL all-gather per ADMM iteration (strong scaling, --n-obs = total obstacles)")
     args = ap.parse_args()
     if args.size_leg:                                   # one entry of `sizes`: the closed loops, the timed replay, one cpu_baseline sample
-        args.egos, args.no_ip_legs, args.no_sizes = 0, True, True
+        args.egos, args.no_ip_legs, args.no_sizes, args.full = 0, True, True, True
+    if args.dump_outputs and args.mode == "shard" and args.gpus > 1:
+        ap.error("--dump-outputs: the obstacle-shard mode has no headline closed loop to take the outputs from")
     return args
 
 
@@ -176,13 +189,58 @@ def base_line(ctx, value, ms_step, protocol):
     }
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, outputs):
+    """outputs of the last timed step -> d/<name>.npy (float64).  Should they pass DUMP_BYTES (huge scenes), every array is cut to the same
+    fixed, seeded sample of obstacle slots (its first axis)."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_BYTES:
+        per_slot = sum(a.nbytes // a.shape[0] for a in outputs.values() if a.ndim > 1)
+        n_slots = max(a.shape[0] for a in outputs.values() if a.ndim > 1)
+        keep = np.sort(np.random.default_rng(0).choice(n_slots, min(n_slots, (DUMP_BYTES - 4096) // max(per_slot, 1)), replace=False))
+        outputs = {k: (a[keep] if a.ndim > 1 and a.shape[0] == n_slots else a) for k, a in outputs.items()}
+        outputs["sampled_slots"] = keep.astype(np.float64)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
+def print_line(out):
+    """the one stdout line of a plain run (no detail file is written)"""
+    line = json.loads(compact.line(out))
+    line.pop("detail", None)
+    print(json.dumps(line, separators=(",", ":")), flush=True)
+
+
+def plain(ctx):
+    """a plain run: warm-up, the K timed steps of the headline loop, its outputs (--dump-outputs) and the line - no recorded Python closed loop,
+    no comparison, no second window, no timing pass, no other leg (--full)"""
+    args, K = ctx.args, ctx.K
+    hd = closed_loop.run(ctx, per_tick_scene=bool(args.moving), ordered=True, compare=False, second_window=False, outputs=bool(args.dump_outputs))
+    if ctx.rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hd.outputs)
+    out = base_line(ctx, K * ctx.world / hd.elapsed, hd.elapsed / K * 1e3, PROTOCOL_MOVING if args.moving else PROTOCOL_STATIC)
+    out["median_ms_per_step"] = round(float(np.median(hd.times) * 1e3), 5)
+    out["mean_admm_iters"] = round(float(np.mean(hd.iters)), 3)
+    out["residuals"] = closed_loop.residual_summary(hd.info, 0.2)
+    if hd.elapsed_per_rank:
+        out["per_rank_steps_per_s"] = [round(K / e, 3) for e in hd.elapsed_per_rank]
+    print_line(out)
+
+
 def headline_only(ctx):
     """--only-headline: the loop `value` comes from, its hipEvent timing pass, nothing else"""
     args, K = ctx.args, ctx.K
-    hd = closed_loop.run(ctx, per_tick_scene=bool(args.moving), ordered=True, compare=False)
+    hd = closed_loop.run(ctx, per_tick_scene=bool(args.moving), ordered=True, compare=False, outputs=bool(args.dump_outputs))
     tm = closed_loop.run(ctx, per_tick_scene=bool(args.moving), ordered=True, timing=True, compare=False)
     if ctx.rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hd.outputs)
     out = base_line(ctx, K * ctx.world / hd.elapsed, hd.elapsed / K * 1e3, PROTOCOL_MOVING if args.moving else PROTOCOL_STATIC)
     out["median_ms_per_step"] = round(float(np.median(hd.times) * 1e3), 5)
     out["mean_admm_iters"] = round(float(np.mean(hd.iters)), 3)
@@ -197,8 +255,8 @@ def main():
     args = parse_args()
     ctx = setup(args)
     rank, world, dist, shard, K, W, T, N, kw = ctx.rank, ctx.world, ctx.dist, ctx.shard, ctx.K, ctx.W, ctx.T, ctx.N, ctx.kw
-    if args.only_headline and not shard:
-        headline_only(ctx)
+    if (args.only_headline or not args.full) and not shard:
+        (headline_only if args.only_headline else plain)(ctx)
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -226,7 +284,9 @@ def main():
     head = fixed = follow = early = hard_off = pydrv = pcie = None
     if not shard:
         # HEADLINE = the reference's default semantics: obstacle_order=True, the scene re-sorted about the robot on every tick
-        head = closed_loop.run(ctx, per_tick_scene=moving, ordered=True)
+        head = closed_loop.run(ctx, per_tick_scene=moving, ordered=True, outputs=bool(args.dump_outputs))
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, head.outputs)
         if one:
             # the protocol of rounds 2-3: slots bound once (obstacle_order=False), no conversion kernel inside the timed region
             lp = closed_loop.run(ctx, per_tick_scene=moving)

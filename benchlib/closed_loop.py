@@ -19,6 +19,7 @@ class Loop:
     kernel_ms: Any = None        # timing pass: hipEvent times per launch, {"k_lammuz": [...], "k_su": [...]}
     lmz_kernel: str = ""
     elapsed_per_rank: Any = None # this loop's wall time on every rank (N > 1: the per-rank values of the driver line)
+    outputs: Any = None          # what the last timed step handed back (C driver, run(..., outputs=True)): {name: float64 array}
 
 
 def residual_summary(info, iter_threshold):
@@ -35,7 +36,17 @@ def residual_summary(info, iter_threshold):
             "su_interior_point_iters_per_step": round(float(ipm.mean()), 3)}
 
 
-def run(ctx, per_tick_scene, driver="c", car=None, compare=True, ordered=False, timing=False, **solver_kw):
+def last_step_outputs(sv, u, state, info, iters):
+    """what the caller of the timed loop holds after its last step: the control it applied, the robot state that control led to, the step's
+    residuals and iteration counts, and the solver's duals (rda_get_state) - read after the timed region"""
+    st = sv.get_state()
+    out = {"control": np.array(u, np.float64), "state": np.array(state, np.float64),
+           "info": np.array([info[0], info[1], info[2], iters], np.float64)}           # resi_dual, resi_pri, su interior-point iterations, ADMM iterations
+    out.update({k: np.asarray(st[k], np.float64) for k in ("lam", "mu", "z", "xi", "zeta")})
+    return out
+
+
+def run(ctx, per_tick_scene, driver="c", car=None, compare=True, ordered=False, timing=False, second_window=True, outputs=False, **solver_kw):
     """state in / control out per step; scene resident in HBM (per_tick_scene False) or handed over from host memory on every tick (True,
     BASELINE.md 2.4 'including H2D of obstacles').  driver "c": the loop is tools/closed_loop_host.c (C-ABI calls and the kinematic model in C,
     nothing of the interpreter between two steps); "python": the same loop written with ctypes / numpy.
@@ -43,7 +54,9 @@ def run(ctx, per_tick_scene, driver="c", car=None, compare=True, ordered=False, 
     max_obs_num are staged (mpc.py:205-206): per_tick_scene -> rda_upload_scene_async(order = 1), resident scene -> rda_scene_resort (the same
     conversion kernels on the resident raw scene, no copy); compared with the ordered Python closed loop.
     timing: hipEvents around every solver launch of the timed steps (switches the zero-copy hand-over off: a pass of its own, never the one
-    `value` comes from)."""
+    `value` comes from).
+    second_window: the extra window of steps behind the timed ones (C driver, one rank).  outputs: keep what the last timed step handed back
+    (Loop.outputs, C driver)."""
     from rda_planner_amd._capi import Info, dptr, iptr
     api, args, kw, T, K, W = ctx.api, ctx.args, ctx.kw, ctx.T, ctx.K, ctx.W
     path, obstacles = ctx.path, ctx.obstacles
@@ -79,7 +92,7 @@ def run(ctx, per_tick_scene, driver="c", car=None, compare=True, ordered=False, 
         # so this window has max(K, 50) steps where they fit
         fits = lambda n: 0.4 * (W + K + n) + 8.0 <= ctx.path_length
         K2 = max(K, 50) if fits(max(K, 50)) else (K if fits(K) else 0)
-        if ctx.world != 1 or timing:
+        if ctx.world != 1 or timing or not second_window:
             K2 = 0
         n_all = W + K + K2
         u_log, t_log, it_log, info_log = np.zeros((n_all, 2)), np.zeros(n_all), np.zeros(n_all, np.int32), np.zeros((n_all, 3))
@@ -103,6 +116,8 @@ def run(ctx, per_tick_scene, driver="c", car=None, compare=True, ordered=False, 
         res = Loop(el, t_log[W:W + K].copy(), 0.0, [int(v) for v in it_log[W:W + K]], info=info_log[W:W + K].copy())
         if ctx.world > 1:
             res.elapsed_per_rank = ctx.gather_over_ranks(el_local)
+        if outputs:
+            res.outputs = last_step_outputs(sv, u_log[W + K - 1], state, info_log[W + K - 1], it_log[W + K - 1])
         if timing:
             kt_ = {}
             for which, name in ((0, "k_lammuz"), (1, "k_su")):

@@ -48,7 +48,8 @@ def test_residual_summary_says_where_the_admm_ends():
 def test_bench_cli_keeps_the_flags_the_driver_and_the_profile_script_use():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--only-headline", "--n-obs", "--horizon", "--moving", "--no-sizes", "--no-cpu-baseline", "--mode"):
+    for flag in ("--gpus", "--steps", "--warmup", "--only-headline", "--n-obs", "--horizon", "--moving", "--no-sizes", "--no-cpu-baseline", "--mode",
+                 "--full", "--dump-outputs"):
         assert flag in out.stdout, flag
     text = open(os.path.join(ROOT, "tools", "profile_round.sh")).read()
     assert "bench.py --only-headline" in text

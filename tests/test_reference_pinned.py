@@ -1,7 +1,10 @@
-"""The UNMODIFIED reference in the loop (oracle/ref_harness.py) - CPU tests, skipped where /root/reference is absent.
+"""The UNMODIFIED reference in the loop (oracle/ref_harness.py) - CPU tests on what the reference computed.
 
-The reference (`RDA_planner/rda_solver.py`, `RDA_planner/mpc.py`) is imported from /root/reference and executed on top
-of the cvxpy / pathos stand-ins of oracle/refshim (the real packages are not installable here).  Two kinds of pins:
+The reference (`RDA_planner/rda_solver.py`, `RDA_planner/mpc.py`) is executed on top of the cvxpy / pathos stand-ins of
+oracle/refshim when the fixture is recorded: `RDA_RECORD_REF_PINNED=1 pytest tests/test_reference_pinned.py` with a reference
+checkout (oracle/ref_loader.py, RDA_REFERENCE_ROOT) runs every reference side below and writes what it computed - and the
+inputs it computed it from - to tests/golden/ref_pinned/<test>.pkl.xz.  Every other run reads those files: this side of each
+comparison runs as before, the other side is the reference's recorded answer.  Two kinds of pins:
 
 * mode "oracle" - `Problem.solve` of the reference's problem objects is answered by the oracle's two argmin functions,
   everything else (parameter staging, padding / truncation, the pool branch, the ADMM order, residuals, early stop,
@@ -13,27 +16,106 @@ of the cvxpy / pathos stand-ins of oracle/refshim (the real packages are not ins
   and be feasible for the reference's own constraint expressions.
 """
 import ctypes as C
+import glob
+import lzma
+import os
+import pickle
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import ref_loader
+from oracle import ref_harness as rh
 from rda_planner_amd import scenarios as sc
-from rda_planner_amd._capi import Info, dptr, f64
+from rda_planner_amd._capi import Cfg, Info, dptr, f64
 from rda_planner_amd.rda_solver import RDA_solver
 
 from helpers import random_polygon, su_solve
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="needs the reference checkout (/root/reference)")
-
 ADJ = ("ro1", "ro2", "slack_gain", "max_sd", "min_sd", "ws", "wu", "iter_threshold")
+PINNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_pinned")     # <first part of the key>.pkl.xz
+RECORD = os.environ.get("RDA_RECORD_REF_PINNED") == "1"
+
+
+def _plain(x):
+    """numbers, arrays, strings, bools, lists / tuples / dicts of them: nothing of the reference's classes goes into the fixture"""
+    if isinstance(x, dict):
+        return {k: _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return np.array(x)
+    if isinstance(x, (bool, np.bool_)):
+        return bool(x)
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if isinstance(x, (float, np.floating)):
+        return float(x)
+    if x is None or isinstance(x, str):
+        return x
+    raise TypeError(type(x))
+
+
+class Pinned:
+    """the reference's side of every comparison, by key: computed by `fn` (the live reference) and stored when recording, read back otherwise"""
+
+    def __init__(self):
+        self.recording = RECORD
+        self.data = {}
+        for path in sorted(glob.glob(os.path.join(PINNED, "*.pkl.xz"))):
+            with lzma.open(path, "rb") as f:
+                self.data.update(pickle.load(f))
+        if self.recording:
+            assert ref_loader.available(), f"recording needs the reference checkout ({ref_loader.REFERENCE_ROOT})"
+            self.rs, self.mp, self.backend = rh.load()
+        else:
+            assert self.data, f"{PINNED} is missing"
+
+    def get(self, key, fn):
+        if self.recording:
+            self.data[key] = _plain(fn())
+        assert key in self.data, f"{key} is not in {PINNED}: record it (RDA_RECORD_REF_PINNED=1)"
+        return self.data[key]
+
+    def save(self):
+        os.makedirs(PINNED, exist_ok=True)
+        for group in sorted({k.split(".")[0] for k in self.data}):
+            part = {k: v for k, v in self.data.items() if k.split(".")[0] == group}
+            with open(os.path.join(PINNED, group + ".pkl.xz"), "wb") as f:
+                f.write(lzma.compress(pickle.dumps(part, protocol=4), preset=9 | lzma.PRESET_EXTREME))
+
+
+QKEYS = ("lam", "mu", "z", "xi", "zeta", "dis", "a_lam", "b_lam", "s", "u")
+
+
+def _quantized(log, q):
+    """the per-iteration snapshots of a closed loop as integer multiples of q (the bulk of the fixture).  A value read back is within q / 2
+    of the reference's, so a comparison at tol - q / 2 against it is at least as strict as one at tol against the reference itself."""
+    return [{k: (np.round(np.asarray(v, np.float64) / q).astype(np.int64) if k in QKEYS else v) for k, v in snap.items()} for snap in log]
 
 
 @pytest.fixture(scope="module")
 def ref():
-    from oracle import ref_harness as rh
-    rs, mp, backend = rh.load()
-    return rh, rs, mp, backend
+    pin = Pinned()
+    yield pin
+    if pin.recording:
+        pin.save()
+
+
+def _obstacles(obs):
+    """recorded obstacle list -> the rdaobs tuples this repo's solver stages"""
+    from rda_planner_amd.mpc import rdaobs
+    return [rdaobs(*o) for o in obs]
+
+
+def _shim_on_path():
+    """the cvxpy stand-in of oracle/refshim, importable the way ref_loader.load puts it (only where the real cvxpy is absent)"""
+    try:
+        import cvxpy  # noqa: F401
+    except ImportError:
+        if ref_loader._SHIM not in sys.path:
+            sys.path.insert(0, ref_loader._SHIM)
 
 
 @pytest.fixture()
@@ -48,7 +130,8 @@ def cold_orc(orc):
 # ---------------------------------------------------------------------------------------------------------
 # the stand-in solver itself
 # ---------------------------------------------------------------------------------------------------------
-def test_shim_coneqp_known_answers(ref):
+def test_shim_coneqp_known_answers():
+    _shim_on_path()
     import cvxpy as cp
     if not cp.__version__.endswith("refshim"):
         pytest.skip("real cvxpy present")
@@ -83,38 +166,42 @@ def test_shim_coneqp_known_answers(ref):
 # ---------------------------------------------------------------------------------------------------------
 # mode "oracle": reference plumbing vs orc_admm_*
 # ---------------------------------------------------------------------------------------------------------
-def _compare_closed_loop(ref, orc, car_t, path, obstacles_of_step, steps, speed=4.0, process_num=1, tol=1e-9, hooks=None, **kw):
+def _compare_closed_loop(ref, orc, key, car_t, path, obstacles_of_step, steps, speed=4.0, process_num=1, tol=1e-9, hooks=None, **kw):
     """reference MPC (oracle-answered) in closed loop; after every ADMM iteration of every step compare every
     persistent parameter with the oracle library driven through the same pieces `orc_step` is made of"""
-    rh, rs, mp, _ = ref
     dt = kw.get("sample_time", 0.1)
-    rmpc = mp.MPC(car_t, [p.copy() for p in path], process_num=process_num, time_print=False, **kw)
-    rh.OracleAnswers(rmpc.rda, rs, orc)
-    log = rh.record_iterations(rmpc.rda)
+    rmpc, log, cap = None, [], {}
+    if ref.recording:
+        rmpc = ref.mp.MPC(car_t, [p.copy() for p in path], process_num=process_num, time_print=False, **kw)
+        rh.OracleAnswers(rmpc.rda, ref.rs, orc)
+        log = rh.record_iterations(rmpc.rda)
+        orig = rmpc.rda.iterative_solve
+
+        def spy(nom_s, nom_u, ref_states, ref_speed, obstacle_list, **k):
+            cap.update(nom_s=np.array(nom_s, float), nom_u=np.array(nom_u, float), ref=np.array(np.hstack(ref_states)[0:3, :], float),
+                       speed=float(ref_speed), obs=[tuple(o) for o in obstacle_list])
+            return orig(nom_s, nom_u, ref_states, ref_speed, obstacle_list, **k)
+        rmpc.rda.iterative_solve = spy
     from oracle.oracle_backend import oracle_backend
     T = kw["receding"]
     ours = RDA_solver(T, car_t, kw.get("max_edge_num", 5), kw.get("max_obs_num", 5), iter_num=kw.get("iter_num", 4), step_time=dt,
                       process_num=1, time_print=False, accelerated=kw.get("accelerated", True), _backend=oracle_backend,
                       **{k: v for k, v in kw.items() if k in ADJ})
     api, hd = ours._be.api, ours._be.handle
-    cap = {}
-    orig = rmpc.rda.iterative_solve
-
-    def spy(nom_s, nom_u, ref_states, ref_speed, obstacle_list, **k):
-        cap.update(nom_s=np.array(nom_s, float), nom_u=np.array(nom_u, float), ref=np.array(np.hstack(ref_states)[0:3, :], float),
-                   speed=float(ref_speed), obs=list(obstacle_list))
-        return orig(nom_s, nom_u, ref_states, ref_speed, obstacle_list, **k)
-    rmpc.rda.iterative_solve = spy
     state = path[0].copy().reshape(3, 1)
     worst, total_iters = {}, 0
+    q = 0.5 * tol                   # grid of the recorded snapshots: compared at 0.75 tol, never looser than tol against the reference
     for step in range(steps):
         if hooks and step in hooks:
-            hooks[step](rmpc.rda, ours)
-        del log[:]
-        obstacles = obstacles_of_step(step)
-        u, info = rmpc.control(state, speed, list(obstacles))
-        ours.upload_obstacles(cap["obs"])
-        api.admm_begin(hd, dptr(f64(cap["nom_s"])), dptr(f64(cap["nom_u"])), dptr(f64(cap["ref"])), cap["speed"])
+            hooks[step](rmpc.rda if rmpc is not None else None, ours)
+
+        def reference_step():
+            del log[:]
+            u, info = rmpc.control(state, speed, list(obstacles_of_step(step)))
+            return dict(u=u, resi_dual=info["resi_dual"], resi_pri=info["resi_pri"], q=q, log=_quantized(log, q), **cap)
+        rec = ref.get(f"{key}.{step}", reference_step)
+        ours.upload_obstacles(_obstacles(rec["obs"]))
+        api.admm_begin(hd, dptr(f64(rec["nom_s"])), dptr(f64(rec["nom_u"])), dptr(f64(rec["ref"])), rec["speed"])
         nit = 0
         for it in range(ours.iter_num):
             stopped = C.c_int(0)
@@ -126,20 +213,20 @@ def _compare_closed_loop(ref, orc, car_t, path, obstacles_of_step, steps, speed=
             api.admm_finish(hd, dptr(out_u), dptr(out_s), C.byref(inf))
             st = ours.get_state()
             st["s"], st["u"] = out_s, out_u
-            assert it < len(log), f"step {step}: the oracle runs iteration {it}, the reference stopped after {len(log)}"
+            assert it < len(rec["log"]), f"step {step}: the oracle runs iteration {it}, the reference stopped after {len(rec['log'])}"
             for k in ("lam", "mu", "z", "xi", "zeta", "dis", "a_lam", "b_lam", "s", "u"):
-                a, b = st[k], log[it][k]
+                a, b = st[k], rec["log"][it][k] * rec["q"]
                 if k in ("lam", "mu"):
                     a, b = a[:, 1:], b[:, 1:]         # column 0 is free in the reference problem (only cone-constrained)
                 worst[k] = max(worst.get(k, 0.0), float(np.max(np.abs(a - b))))
-            worst["resi_dual"] = max(worst.get("resi_dual", 0.0), abs(inf.resi_dual - log[it]["resi_dual"]) / max(1.0, abs(inf.resi_dual)))
-            worst["resi_pri"] = max(worst.get("resi_pri", 0.0), abs(inf.resi_pri - log[it]["resi_pri"]))
+            worst["resi_dual"] = max(worst.get("resi_dual", 0.0), abs(inf.resi_dual - rec["log"][it]["resi_dual"]) / max(1.0, abs(inf.resi_dual)))
+            worst["resi_pri"] = max(worst.get("resi_pri", 0.0), abs(inf.resi_pri - rec["log"][it]["resi_pri"]))
             nit += 1
-        assert nit == len(log), f"step {step}: {nit} oracle iterations, {len(log)} reference iterations (early stop differs)"
-        assert abs(info["resi_dual"] - inf.resi_dual) <= tol * max(1.0, abs(inf.resi_dual)) and abs(info["resi_pri"] - inf.resi_pri) <= tol
+        assert nit == len(rec["log"]), f"step {step}: {nit} oracle iterations, {len(rec['log'])} reference iterations (early stop differs)"
+        assert abs(rec["resi_dual"] - inf.resi_dual) <= tol * max(1.0, abs(inf.resi_dual)) and abs(rec["resi_pri"] - inf.resi_pri) <= tol
         total_iters += nit
-        state = sc.kinematic_step(state, u, car_t, dt)
-    bad = {k: v for k, v in worst.items() if v > tol}
+        state = sc.kinematic_step(state, np.array(rec["u"]), car_t, dt)
+    bad = {k: v for k, v in worst.items() if v > (tol - 0.5 * q if k in QKEYS else tol)}        # see _quantized
     assert not bad, bad
     return worst, total_iters
 
@@ -149,7 +236,7 @@ def test_plumbing_path_track_c1(ref, cold_orc):
     obstacles re-sorted by distance every step (Q5)"""
     car_t = sc.rectangle_robot(dynamics="diff", wheelbase=0)
     obs = sc.scene_path_track()
-    w, n = _compare_closed_loop(ref, cold_orc, car_t, sc.path_track_ref(), lambda k: obs, 15, receding=10, sample_time=0.1, iter_num=2,
+    w, n = _compare_closed_loop(ref, cold_orc, "c1", car_t, sc.path_track_ref(), lambda k: obs, 15, receding=10, sample_time=0.1, iter_num=2,
                                 max_edge_num=4, max_obs_num=11, ro1=300, obstacle_order=True)
     assert n >= 15
 
@@ -158,7 +245,7 @@ def test_plumbing_padding_and_spare_edge_rows(ref, cold_orc):
     """n_obs < max_obs_num (Q3: the last obstacle is duplicated, in the caller's list) and max_edge_num > edges (zero rows)"""
     car_t = sc.rectangle_robot(dynamics="diff", wheelbase=0)
     obs = sc.scene_path_track()[4:]
-    _compare_closed_loop(ref, cold_orc, car_t, sc.path_track_ref(), lambda k: obs, 6, receding=10, iter_num=3, max_edge_num=5,
+    _compare_closed_loop(ref, cold_orc, "padding", car_t, sc.path_track_ref(), lambda k: obs, 6, receding=10, iter_num=3, max_edge_num=5,
                          max_obs_num=11, ro1=300, obstacle_order=True)
 
 
@@ -166,7 +253,7 @@ def test_plumbing_truncation_through_the_pool_branch(ref, cold_orc):
     """n_obs > max_obs_num (nearest first), process_num > 1: `solve_parallel` and its 14-tuples (rda_solver.py:706-793)"""
     car_t = sc.rectangle_robot(dynamics="diff", wheelbase=0)
     obs = sc.scene_path_track()
-    _compare_closed_loop(ref, cold_orc, car_t, sc.path_track_ref(), lambda k: obs, 6, process_num=4, receding=10, iter_num=3,
+    _compare_closed_loop(ref, cold_orc, "truncation", car_t, sc.path_track_ref(), lambda k: obs, 6, process_num=4, receding=10, iter_num=3,
                          max_edge_num=4, max_obs_num=5, ro1=300, obstacle_order=True)
 
 
@@ -175,7 +262,7 @@ def test_plumbing_corridor_c2_acker(ref, cold_orc):
     car_t = sc.rectangle_robot(dynamics="acker")
     path = sc.line_path([0, 20, 0], [60, 20, 0], 0.1)
     obs = sc.scene_corridor()
-    _compare_closed_loop(ref, cold_orc, car_t, path, lambda k: obs, 8, receding=20, iter_num=3, max_edge_num=4, max_obs_num=20,
+    _compare_closed_loop(ref, cold_orc, "c2", car_t, path, lambda k: obs, 8, receding=20, iter_num=3, max_edge_num=4, max_obs_num=20,
                          obstacle_order=True, tol=1e-8)
 
 
@@ -188,7 +275,7 @@ def test_plumbing_moving_obstacles_omni_c4_shape(ref, cold_orc):
 
     def at(k):
         return [o._replace(vertex=o.vertex + o.velocity * (0.1 * k)) for o in base]
-    _compare_closed_loop(ref, cold_orc, car_t, path, at, 6, receding=12, iter_num=3, max_edge_num=4, max_obs_num=12, obstacle_order=True, tol=1e-8)
+    _compare_closed_loop(ref, cold_orc, "c4_omni", car_t, path, at, 6, receding=12, iter_num=3, max_edge_num=4, max_obs_num=12, obstacle_order=True, tol=1e-8)
 
 
 def test_plumbing_empty_list_reset_and_retune(ref, cold_orc):
@@ -202,40 +289,56 @@ def test_plumbing_empty_list_reset_and_retune(ref, cold_orc):
         return [] if k in (3, 4) else obs
 
     def do_reset(rref, ours):
-        rref.reset()
+        if rref is not None:
+            rref.reset()
         ours.reset()
 
     def retune(rref, ours):
-        rref.assign_adjust_parameter(ro1=120.0, slack_gain=5.0, max_sd=0.8)
+        if rref is not None:
+            rref.assign_adjust_parameter(ro1=120.0, slack_gain=5.0, max_sd=0.8)
         ours.assign_adjust_parameter(ro1=120.0, slack_gain=5.0, max_sd=0.8)
-    _compare_closed_loop(ref, cold_orc, car_t, path, at, 9, receding=10, iter_num=3, max_edge_num=4, max_obs_num=6,
+    _compare_closed_loop(ref, cold_orc, "empty_reset_retune", car_t, path, at, 9, receding=10, iter_num=3, max_edge_num=4, max_obs_num=6,
                          obstacle_order=False, hooks={2: do_reset, 6: retune}, tol=1e-8)
 
 
 def test_reference_mpc_on_top_of_our_solver_class(ref, cold_orc):
     """INTEGRATION.md option B: the reference's own `mpc.MPC` (pre_process, convert_rda_obstacle, arrive logic) drives this
     repo's `RDA_solver` class through the reference's constructor call (mpc.py:103-114) - same controls as the repo's MPC mirror"""
-    rh, rs, mp, _ = ref
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.mpc import MPC as OurMPC
-    import functools
     car_t = sc.rectangle_robot(dynamics="diff", wheelbase=0)
     obs = sc.scene_path_track()
     kw = dict(receding=10, sample_time=0.1, iter_num=2, max_edge_num=4, max_obs_num=11, ro1=300, obstacle_order=True)
+    a = _reference_mpc_on_our_solver(ref, car_t, sc.path_track_ref(), kw)
+    b = OurMPC(car_t, [p.copy() for p in sc.path_track_ref()], time_print=False, _backend=oracle_backend, **kw)
+    state = sc.path_track_ref()[0].copy().reshape(3, 1)
+    for k in range(25):
+        ra = ref.get(f"on_top_of_our_solver.{k}", lambda: _reference_control(a, state, 4.0, obs))
+        ua = np.array(ra["u"])
+        ub, ib = b.control(state.copy(), 4.0, list(obs))
+        assert np.array_equal(ua, ub) and ra["arrive"] == ib["arrive"]
+        assert all(np.array_equal(x, y) for x, y in zip(ra["ref_traj_list"], ib["ref_traj_list"]))
+        state = sc.kinematic_step(state, ua, car_t, 0.1)
+
+
+def _reference_mpc_on_our_solver(ref, car_t, path, kw):
+    """the reference's mpc.MPC on this repo's RDA_solver (oracle backend) - when recording; None otherwise"""
+    if not ref.recording:
+        return None
+    import functools
+    from oracle.oracle_backend import oracle_backend
+    mp = ref.mp
     saved = mp.RDA_solver
     mp.RDA_solver = functools.partial(RDA_solver, _backend=oracle_backend)
     try:
-        a = mp.MPC(car_t, [p.copy() for p in sc.path_track_ref()], time_print=False, **kw)
+        return mp.MPC(car_t, [q.copy() for q in path], time_print=False, **kw)
     finally:
         mp.RDA_solver = saved
-    b = OurMPC(car_t, [p.copy() for p in sc.path_track_ref()], time_print=False, _backend=oracle_backend, **kw)
-    state = sc.path_track_ref()[0].copy().reshape(3, 1)
-    for _ in range(25):
-        ua, ia = a.control(state.copy(), 4.0, list(obs))
-        ub, ib = b.control(state.copy(), 4.0, list(obs))
-        assert np.array_equal(ua, ub) and ia["arrive"] == ib["arrive"]
-        assert all(np.array_equal(x, y) for x, y in zip(ia["ref_traj_list"], ib["ref_traj_list"]))
-        state = sc.kinematic_step(state, ua, car_t, 0.1)
+
+
+def _reference_control(a, state, speed, obs):
+    ua, ia = a.control(state.copy(), speed, list(obs))
+    return dict(u=ua, arrive=ia["arrive"], ref_traj_list=ia["ref_traj_list"], cur_index=a.cur_index)
 
 
 def _mirror_scene(name):
@@ -279,27 +382,21 @@ def test_reference_mpc_equals_the_mirror_on_more_scenes(ref, cold_orc, name):
     arrive logic, convert_rda_obstacle + sort) is a mirror of the reference's `mpc.MPC`, and the device-side pipelines (f1, f3) are
     tested against THAT mirror - so the mirror itself is pinned on the reference: both MPC classes on the same solver backend must
     return bit-identical controls, reference trajectories and `arrive` flags, step for step."""
-    rh, rs, mp, _ = ref
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.mpc import MPC as OurMPC
-    import functools
     car_t, path, obs_at, kw, steps = _mirror_scene(name)
-    saved = mp.RDA_solver
-    mp.RDA_solver = functools.partial(RDA_solver, _backend=oracle_backend)
-    try:
-        a = mp.MPC(car_t, [q.copy() for q in path], sample_time=0.1, time_print=False, **kw)
-    finally:
-        mp.RDA_solver = saved
+    a = _reference_mpc_on_our_solver(ref, car_t, path, dict(kw, sample_time=0.1))
     b = OurMPC(car_t, [q.copy() for q in path], sample_time=0.1, time_print=False, _backend=oracle_backend, **kw)
     state = path[0][0:3].copy().reshape(3, 1)
     arrived, reversed_ = 0, False
     for k in range(steps):
-        ua, ia = a.control(state.copy(), 3.0, list(obs_at(k)))
+        ia = ref.get(f"mirror.{name}.{k}", lambda: _reference_control(a, state, 3.0, obs_at(k)))
+        ua = np.array(ia["u"])
         ub, ib = b.control(state.copy(), 3.0, list(obs_at(k)))
         assert np.array_equal(ua, ub), (name, k, float(np.abs(ua - ub).max()))
         assert ia["arrive"] == ib["arrive"], (name, k)
         assert len(ia["ref_traj_list"]) == len(ib["ref_traj_list"]) and all(np.array_equal(x, y) for x, y in zip(ia["ref_traj_list"], ib["ref_traj_list"])), (name, k)
-        assert a.cur_index == b.cur_index
+        assert ia["cur_index"] == b.cur_index
         arrived += int(ia["arrive"])
         reversed_ = reversed_ or float(ua[0, 0]) < -0.05
         state = sc.kinematic_step(state, ua, car_t, 0.1)
@@ -328,51 +425,78 @@ def test_reference_lammuz_problems_vs_oracle_argmin(ref, orc, accelerated):
     """reference-built LamMuZ problems (all T stages of an obstacle jointly, rda_solver.py:233-265,389-421) solved by the
     generic IPM vs. `orc_lammuz_one` per (obstacle, stage): optimal cost, min(Im, 0) and Hm agree (the oracle's
     clearance reward delta = 1e-6 bounds the difference), and the oracle's point satisfies the reference's own
-    constraint expressions"""
-    rh, rs, mp, _ = ref
-    rng = np.random.default_rng(7 + int(accelerated))
+    constraint expressions (evaluated when the fixture was recorded, for the point the oracle returns now)"""
     car_t = sc.rectangle_robot(dynamics="acker")
     T, N, E, R = 5, 6, 4, 4
-    r = rs.RDA_solver(T, car_t, max_edge_num=E, max_obs_num=N, iter_num=2, step_time=0.1, process_num=1, time_print=False,
-                      ro2=1.5, accelerated=accelerated)
     G, h = f64(car_t.G), f64(car_t.h).ravel()
-    worst = dict(cost=0.0, H=0.0, mneg=0.0, feas=0.0)
+
+    def oracle_point(p, nom_s, dis):
+        lam_o, mu_o, z_o, cmh_o = np.zeros((E, T + 1)), np.zeros((R, T + 1)), np.zeros((1, T)), np.zeros((T, 4))
+        for t in range(T):
+            lo, mo, zo, cmh = np.zeros(E), np.zeros(R), C.c_double(0), np.zeros(4)
+            orc.lib.orc_lammuz_one(E, R, dptr(f64(p["A"][t])), dptr(f64(p["b"][t])), int(p["cone"]), dptr(f64(nom_s[0:2, t + 1])), float(nom_s[2, t]),
+                                   dptr(G), dptr(h), dptr(f64(p["xi"][t + 1])), float(p["zeta"][0, t]), float(dis[0, t]),
+                                   1.5, 1e-6, int(accelerated), dptr(lo), dptr(mo), C.cast(C.byref(zo), C.POINTER(C.c_double)), dptr(cmh))
+            lam_o[:, t + 1], mu_o[:, t + 1], z_o[0, t], cmh_o[t] = lo, mo, zo.value, cmh
+        return lam_o, mu_o, z_o, cmh_o
+
+    def reference_problems():
+        rs, mp = ref.rs, ref.mp
+        rng = np.random.default_rng(7 + int(accelerated))
+        r = rs.RDA_solver(T, car_t, max_edge_num=E, max_obs_num=N, iter_num=2, step_time=0.1, process_num=1, time_print=False,
+                          ro2=1.5, accelerated=accelerated)
+        trials = []
+        for trial in range(3):
+            nom_s, nom_u = _random_nominal(rng, car_t, T)
+            dis = rng.uniform(0.1, 1.0, (1, T))
+            obs = []
+            for n in range(N):
+                dist, th = rng.choice([1.0, 2.5, 4.0, 8.0, 20.0]), rng.uniform(0, 2 * np.pi)
+                cen = nom_s[0:2, T // 2] + dist * np.array([np.cos(th), np.sin(th)])
+                if rng.random() < 0.3:
+                    obs.append(mp.rdaobs(np.array([[1, 0], [0, 1], [0, 0.0]]), np.array([[cen[0]], [cen[1]], [-rng.uniform(0.3, 1.5)]]), "norm2", None, None))
+                else:
+                    k = int(rng.integers(3, E + 1))
+                    A, b = random_polygon(rng, cen, k, rng.uniform(0.5, 2.0), k)
+                    obs.append(mp.rdaobs(A, b.reshape(-1, 1), "Rpositive", None, None))
+            r.assign_state_parameter(nom_s, nom_u, dis)
+            r.assign_obstacle_parameter(obs)
+            r.assign_combine_parameter_stateobs()
+            for n in range(N):
+                r.para_xi_list[n].value = np.vstack([np.zeros((1, 2)), rng.normal(0, rng.choice([0, 0.05, 0.5]), (T, 2))])
+                r.para_zeta_list[n].value = rng.normal(0, rng.choice([0, 0.3, 2.0]), (1, T))
+            probs = []
+            for n in range(N):
+                prob = r.prob_LamMuZ_list[n]
+                prob.solve()
+                p = dict(status=prob.status, value=prob.value, Im=r.indep_Im_array_LamMuZ[n].value.copy(), Hm=r.indep_Hm_array_LamMuZ[n].value.copy(),
+                         cone=int(r.para_obstacle_list[n]["cone_type"].value[1] > 0.5), xi=r.para_xi_list[n].value.copy(), zeta=r.para_zeta_list[n].value.copy(),
+                         A=[f64(r.para_obstacle_list[n]["A"][t + 1].value) for t in range(T)],
+                         b=[f64(r.para_obstacle_list[n]["b"][t + 1].value).ravel() for t in range(T)])
+                lam_o, mu_o, z_o, _ = oracle_point(p, nom_s, dis)
+                # the oracle's point in the reference's own expressions: feasible, and not worse than the IPM optimum
+                r.indep_lam_list[n]._value, r.indep_mu_list[n]._value, r.indep_z_list[n]._value = lam_o, mu_o, z_o
+                Im_expr = r.Im_LamMu(r.indep_lam_list[n], r.indep_mu_list[n], r.indep_z_list[n], r.para_s, r.para_dis, r.para_zeta_list[n],
+                                     r.para_obstacle_list[n], r.para_obsA_trans_list[n]).value
+                Hm_expr = r.Hm_LamMu(r.indep_lam_list[n], r.indep_mu_list[n], r.para_rot_list, r.para_xi_list[n], r.para_obstacle_list[n], T,
+                                     r.para_obsA_rot_list[n]).value
+                r.indep_Im_array_LamMuZ[n]._value, r.indep_Hm_array_LamMuZ[n]._value = Im_expr, Hm_expr
+                p.update(lam_o=lam_o, mu_o=mu_o, z_o=z_o, objective_at_oracle=prob.objective.value,
+                         violation_at_oracle=max(c.violation() for c in prob.constraints))
+                probs.append(_plain(p))                  # copies: the reference overwrites its parameter arrays in place
+            trials.append(dict(nom_s=nom_s, dis=dis, probs=probs))
+        return trials
+    worst = dict(cost=0.0, H=0.0, mneg=0.0, feas=0.0, point=0.0)
     n_active = n_slack = 0
-    for trial in range(3):
-        nom_s, nom_u = _random_nominal(rng, car_t, T)
-        dis = rng.uniform(0.1, 1.0, (1, T))
-        obs = []
-        for n in range(N):
-            dist, th = rng.choice([1.0, 2.5, 4.0, 8.0, 20.0]), rng.uniform(0, 2 * np.pi)
-            cen = nom_s[0:2, T // 2] + dist * np.array([np.cos(th), np.sin(th)])
-            if rng.random() < 0.3:
-                obs.append(mp.rdaobs(np.array([[1, 0], [0, 1], [0, 0.0]]), np.array([[cen[0]], [cen[1]], [-rng.uniform(0.3, 1.5)]]), "norm2", None, None))
-            else:
-                k = int(rng.integers(3, E + 1))
-                A, b = random_polygon(rng, cen, k, rng.uniform(0.5, 2.0), k)
-                obs.append(mp.rdaobs(A, b.reshape(-1, 1), "Rpositive", None, None))
-        r.assign_state_parameter(nom_s, nom_u, dis)
-        r.assign_obstacle_parameter(obs)
-        r.assign_combine_parameter_stateobs()
-        for n in range(N):
-            r.para_xi_list[n].value = np.vstack([np.zeros((1, 2)), rng.normal(0, rng.choice([0, 0.05, 0.5]), (T, 2))])
-            r.para_zeta_list[n].value = rng.normal(0, rng.choice([0, 0.3, 2.0]), (1, T))
-        for n in range(N):
-            prob = r.prob_LamMuZ_list[n]
-            prob.solve()
-            assert prob.status in ("optimal", "optimal_inaccurate")
-            Im, Hm = r.indep_Im_array_LamMuZ[n].value.copy(), r.indep_Hm_array_LamMuZ[n].value.copy()
-            cone = int(r.para_obstacle_list[n]["cone_type"].value[1] > 0.5)
-            lam_o, mu_o, z_o = np.zeros((E, T + 1)), np.zeros((R, T + 1)), np.zeros((1, T))
+    for tr in ref.get(f"lammuz.{int(accelerated)}", reference_problems):
+        nom_s, dis = np.array(tr["nom_s"]), np.array(tr["dis"])
+        for p in tr["probs"]:
+            assert p["status"] in ("optimal", "optimal_inaccurate")
+            Im, Hm = np.array(p["Im"]), np.array(p["Hm"])
+            lam_o, mu_o, z_o, cmh_o = oracle_point(p, nom_s, dis)
             for t in range(T):
-                A = f64(r.para_obstacle_list[n]["A"][t + 1].value)
-                b = f64(r.para_obstacle_list[n]["b"][t + 1].value).ravel()
-                lo, mo, zo, cmh = np.zeros(E), np.zeros(R), C.c_double(0), np.zeros(4)
-                orc.lib.orc_lammuz_one(E, R, dptr(A), dptr(b), cone, dptr(f64(nom_s[0:2, t + 1])), float(nom_s[2, t]), dptr(G), dptr(h),
-                                       dptr(f64(r.para_xi_list[n].value[t + 1])), float(r.para_zeta_list[n].value[0, t]), float(dis[0, t]),
-                                       1.5, 1e-6, int(accelerated), dptr(lo), dptr(mo), C.cast(C.byref(zo), C.POINTER(C.c_double)), dptr(cmh))
-                lam_o[:, t + 1], mu_o[:, t + 1], z_o[0, t] = lo, mo, zo.value
-                m_o = cmh[1] - zo.value
+                cmh = cmh_o[t]
+                m_o = cmh[1] - z_o[0, t]
                 hinge = (lambda v: min(v, 0.0)) if accelerated else (lambda v: v)
                 c_ref = 0.5 * hinge(Im[t]) ** 2 + 0.75 * np.sum(Hm[t] ** 2)
                 c_orc = 0.5 * hinge(m_o) ** 2 + 0.75 * (cmh[2] ** 2 + cmh[3] ** 2)
@@ -381,18 +505,11 @@ def test_reference_lammuz_problems_vs_oracle_argmin(ref, orc, accelerated):
                 worst["mneg"] = max(worst["mneg"], abs(hinge(Im[t]) - hinge(m_o)))
                 n_active += int(c_orc > 1e-6)
                 n_slack += int(c_orc <= 1e-6)
-            # the oracle's point in the reference's own expressions: feasible, and not worse than the IPM optimum
-            ipm_value = prob.value
-            r.indep_lam_list[n]._value, r.indep_mu_list[n]._value, r.indep_z_list[n]._value = lam_o, mu_o, z_o
-            cons = prob.constraints
-            Im_expr = r.Im_LamMu(r.indep_lam_list[n], r.indep_mu_list[n], r.indep_z_list[n], r.para_s, r.para_dis, r.para_zeta_list[n],
-                                 r.para_obstacle_list[n], r.para_obsA_trans_list[n]).value
-            Hm_expr = r.Hm_LamMu(r.indep_lam_list[n], r.indep_mu_list[n], r.para_rot_list, r.para_xi_list[n], r.para_obstacle_list[n], T,
-                                 r.para_obsA_rot_list[n]).value
-            r.indep_Im_array_LamMuZ[n]._value, r.indep_Hm_array_LamMuZ[n]._value = Im_expr, Hm_expr
-            worst["feas"] = max(worst["feas"], max(c.violation() for c in cons), float(np.max(np.maximum(-z_o, 0))))
-            assert prob.objective.value <= ipm_value + 2e-5 * T      # delta * |m| per stage at most
-    assert worst["cost"] < 1e-6 and worst["H"] < 2e-5 and worst["mneg"] < 2e-5 and worst["feas"] < 1e-9, worst
+            # the point the reference's expressions were evaluated at is the point the oracle returns now
+            worst["point"] = max(worst["point"], *(float(np.max(np.abs(x - np.array(p[k])))) for x, k in ((lam_o, "lam_o"), (mu_o, "mu_o"), (z_o, "z_o"))))
+            worst["feas"] = max(worst["feas"], p["violation_at_oracle"], float(np.max(np.maximum(-z_o, 0))))
+            assert p["objective_at_oracle"] <= p["value"] + 2e-5 * T      # delta * |m| per stage at most
+    assert worst["cost"] < 1e-6 and worst["H"] < 2e-5 and worst["mneg"] < 2e-5 and worst["feas"] < 1e-9 and worst["point"] < 1e-10, worst
     assert n_active >= 5 and n_slack >= 5, (n_active, n_slack)      # both regimes were exercised
 
 
@@ -401,35 +518,48 @@ def test_reference_lammuz_problems_vs_oracle_argmin(ref, orc, accelerated):
 def test_reference_su_problem_vs_oracle_argmin(ref, orc, dyn, accelerated):
     """the su-problem as `construct_su_prob` builds it (aux variables Im, Hm, rot included) solved by the generic IPM vs.
     `orc_su_solve` on the condensed data read from the same parameter objects: s, u, d agree (strictly convex problem)"""
-    rh, rs, mp, _ = ref
-    rng = np.random.default_rng(11)
     car_t = sc.rectangle_robot(dynamics=dyn, wheelbase=3.0 if dyn == "acker" else 0)
     T, N, E = 8, 5, 4
-    r = rs.RDA_solver(T, car_t, max_edge_num=E, max_obs_num=N, iter_num=2, step_time=0.1, process_num=1, time_print=False, ro1=200,
-                      accelerated=accelerated, ws=1.3, wu=0.7)
-    cfg = rh.make_cfg_from_reference(r)
+
+    def reference_problems():
+        rng = np.random.default_rng(11)
+        r = ref.rs.RDA_solver(T, car_t, max_edge_num=E, max_obs_num=N, iter_num=2, step_time=0.1, process_num=1, time_print=False, ro1=200,
+                              accelerated=accelerated, ws=1.3, wu=0.7)
+        cfg = rh.make_cfg_from_reference(r)
+        out = {"cfg": {name: (list(getattr(cfg, name)) if name in ("max_speed", "acce_bound") else getattr(cfg, name)) for name, _ in Cfg._fields_},
+               "trials": []}
+        for trial in range(3):
+            nom_s, nom_u = _random_nominal(rng, car_t, T)
+            ref_states = [nom_s[:, t:t + 1] + rng.normal(0, 0.3, (3, 1)) for t in range(T + 1)]
+            r.para_ref_s.value = np.hstack(ref_states)[0:3, :]
+            r.para_ref_speed.value = 4.0
+            r.assign_state_parameter(nom_s, nom_u, rng.uniform(0.1, 1.0, (1, T)))
+            for n in range(N):
+                a = rng.normal(0, 0.5, (T + 1, 2))
+                a /= np.maximum(1, np.linalg.norm(a, axis=1, keepdims=True))
+                r.para_obsA_lam_list[n].value = a
+                r.para_obsb_lam_list[n].value = (np.einsum("tk,kt->t", a, nom_s[0:2, :]) - rng.uniform(-0.5, 1.5, T + 1)).reshape(T + 1, 1)
+                r.para_mu_list[n].value = np.abs(rng.normal(0, 0.2, (4, T + 1)))
+                r.para_lam_list[n].value = np.abs(rng.normal(0, 0.2, (E, T + 1)))
+                r.para_z_list[n].value = np.abs(rng.normal(0, 0.2, (1, T)))
+                r.para_zeta_list[n].value = rng.normal(0, 0.3, (1, T))
+                r.para_xi_list[n].value = rng.normal(0, 0.3, (T + 1, 2))
+            s_ref, u_ref, d_ref = r.su_prob_solve()
+            out["trials"].append(_plain(dict(status=r.prob_su.status, inp=rh.su_inputs_from_reference(r), s=s_ref, u=u_ref, d=d_ref)))
+        return out
+    rec = ref.get(f"su.{dyn}.{int(accelerated)}", reference_problems)
+    cfg = Cfg()
+    for name, v in rec["cfg"].items():
+        if name in ("max_speed", "acce_bound"):
+            getattr(cfg, name)[0], getattr(cfg, name)[1] = v
+        else:
+            setattr(cfg, name, v)
     worst = 0.0
-    for trial in range(3):
-        nom_s, nom_u = _random_nominal(rng, car_t, T)
-        ref_states = [nom_s[:, t:t + 1] + rng.normal(0, 0.3, (3, 1)) for t in range(T + 1)]
-        r.para_ref_s.value = np.hstack(ref_states)[0:3, :]
-        r.para_ref_speed.value = 4.0
-        r.assign_state_parameter(nom_s, nom_u, rng.uniform(0.1, 1.0, (1, T)))
-        for n in range(N):
-            a = rng.normal(0, 0.5, (T + 1, 2))
-            a /= np.maximum(1, np.linalg.norm(a, axis=1, keepdims=True))
-            r.para_obsA_lam_list[n].value = a
-            r.para_obsb_lam_list[n].value = (np.einsum("tk,kt->t", a, nom_s[0:2, :]) - rng.uniform(-0.5, 1.5, T + 1)).reshape(T + 1, 1)
-            r.para_mu_list[n].value = np.abs(rng.normal(0, 0.2, (4, T + 1)))
-            r.para_lam_list[n].value = np.abs(rng.normal(0, 0.2, (E, T + 1)))
-            r.para_z_list[n].value = np.abs(rng.normal(0, 0.2, (1, T)))
-            r.para_zeta_list[n].value = rng.normal(0, 0.3, (1, T))
-            r.para_xi_list[n].value = rng.normal(0, 0.3, (T + 1, 2))
-        s_ref, u_ref, d_ref = r.su_prob_solve()
-        assert r.prob_su.status == "optimal"
-        st, s, u, d, it = su_solve(orc.lib.orc_su_solve, cfg, rh.su_inputs_from_reference(r))
+    for t in rec["trials"]:
+        assert t["status"] == "optimal"
+        st, s, u, d, it = su_solve(orc.lib.orc_su_solve, cfg, t["inp"])
         assert st == 0
-        worst = max(worst, np.max(np.abs(s - s_ref)), np.max(np.abs(u - u_ref)), np.max(np.abs(d - d_ref.ravel())))
+        worst = max(worst, np.max(np.abs(s - t["s"])), np.max(np.abs(u - t["u"])), np.max(np.abs(d - np.ravel(t["d"]))))
     assert worst < 2e-6, worst
 
 
@@ -455,10 +585,8 @@ def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, ro
     (Mehrotra predictor-corrector, NT scaling): optimal value, min(Im, 0) and Hm agree to solver tolerance for polygon and
     circle obstacles, rectangle AND circle (norm2, rda_solver.py:1034-1039) robots; the interior multipliers agree to a few
     per cent (the reference problem carries the free column 0 of lam, mu, which shares the step lengths - see DESIGN.md)."""
-    rh, rs, mp, _ = ref
     L = _ipm_api(orc)
     L.orc_set_lmz_ipm_mu(0.0)                     # stop by the gap test, like the stand-in and like ECOS
-    rng = np.random.default_rng(5)
     if robot == "rectangle":
         car_t = sc.rectangle_robot(dynamics="acker")
         rn2 = 0
@@ -467,36 +595,46 @@ def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, ro
         rn2 = 1
     G, h = f64(car_t.G), f64(car_t.h).ravel()
     R, E = G.shape[0], 4
-    r = rs.RDA_solver(1, car_t, max_edge_num=E, max_obs_num=1, iter_num=2, step_time=0.1, process_num=1, time_print=False, ro2=1.3)
+
+    def reference_problems():
+        rs, mp = ref.rs, ref.mp
+        rng = np.random.default_rng(5)
+        r = rs.RDA_solver(1, car_t, max_edge_num=E, max_obs_num=1, iter_num=2, step_time=0.1, process_num=1, time_print=False, ro2=1.3)
+        trials = []
+        for trial in range(30):
+            nom_s = np.zeros((3, 2))
+            nom_s[:, 0] = [rng.uniform(-2, 2), rng.uniform(-2, 2), rng.uniform(-3, 3)]
+            nom_u = np.array([[rng.uniform(1, 4)], [rng.uniform(-0.3, 0.3)]])
+            nom_s[:, 1] = sc.kinematic_step(nom_s[:, 0:1], nom_u, car_t, 0.1).ravel()
+            dis = rng.uniform(0.1, 1.0, (1, 1))
+            dist, th = rng.choice([1.0, 2.5, 4.0, 8.0, 20.0]), rng.uniform(0, 2 * np.pi)
+            cen = nom_s[0:2, 1] + dist * np.array([np.cos(th), np.sin(th)])
+            if rng.random() < 0.3:
+                ob, cone = mp.rdaobs(np.array([[1, 0], [0, 1], [0, 0.0]]), np.array([[cen[0]], [cen[1]], [-rng.uniform(0.3, 1.5)]]), "norm2", None, None), 1
+            else:
+                k = int(rng.integers(3, E + 1))
+                A_, b_ = random_polygon(rng, cen, k, rng.uniform(0.5, 2.0), k)
+                ob, cone = mp.rdaobs(A_, b_.reshape(-1, 1), "Rpositive", None, None), 0
+            r.assign_state_parameter(nom_s, nom_u, dis)
+            r.assign_obstacle_parameter([ob])
+            r.assign_combine_parameter_stateobs()
+            xi = np.vstack([np.zeros((1, 2)), rng.normal(0, rng.choice([0, 0.05, 0.5]), (1, 2))])
+            zeta = rng.normal(0, rng.choice([0, 0.3, 2.0]), (1, 1))
+            r.para_xi_list[0].value, r.para_zeta_list[0].value = xi, zeta
+            prob = r.prob_LamMuZ_list[0]
+            prob.solve()
+            trials.append(_plain(dict(status=prob.status, value=prob.value, lam=r.indep_lam_list[0].value[:, 1], mu=r.indep_mu_list[0].value[:, 1],
+                               Im=float(r.indep_Im_array_LamMuZ[0].value[0]), Hm=r.indep_Hm_array_LamMuZ[0].value[0],
+                               A=f64(r.para_obstacle_list[0]["A"][1].value), b=f64(r.para_obstacle_list[0]["b"][1].value).ravel(),
+                               cone=cone, nom_s=nom_s, dis=dis, xi=xi, zeta=zeta)))
+        return trials
     worst = dict(cost=0.0, H=0.0, mneg=0.0, rel=0.0)
     n_inacc = 0
-    for trial in range(30):
-        nom_s = np.zeros((3, 2))
-        nom_s[:, 0] = [rng.uniform(-2, 2), rng.uniform(-2, 2), rng.uniform(-3, 3)]
-        nom_u = np.array([[rng.uniform(1, 4)], [rng.uniform(-0.3, 0.3)]])
-        nom_s[:, 1] = sc.kinematic_step(nom_s[:, 0:1], nom_u, car_t, 0.1).ravel()
-        dis = rng.uniform(0.1, 1.0, (1, 1))
-        dist, th = rng.choice([1.0, 2.5, 4.0, 8.0, 20.0]), rng.uniform(0, 2 * np.pi)
-        cen = nom_s[0:2, 1] + dist * np.array([np.cos(th), np.sin(th)])
-        if rng.random() < 0.3:
-            ob, cone = mp.rdaobs(np.array([[1, 0], [0, 1], [0, 0.0]]), np.array([[cen[0]], [cen[1]], [-rng.uniform(0.3, 1.5)]]), "norm2", None, None), 1
-        else:
-            k = int(rng.integers(3, E + 1))
-            A_, b_ = random_polygon(rng, cen, k, rng.uniform(0.5, 2.0), k)
-            ob, cone = mp.rdaobs(A_, b_.reshape(-1, 1), "Rpositive", None, None), 0
-        r.assign_state_parameter(nom_s, nom_u, dis)
-        r.assign_obstacle_parameter([ob])
-        r.assign_combine_parameter_stateobs()
-        xi = np.vstack([np.zeros((1, 2)), rng.normal(0, rng.choice([0, 0.05, 0.5]), (1, 2))])
-        zeta = rng.normal(0, rng.choice([0, 0.3, 2.0]), (1, 1))
-        r.para_xi_list[0].value, r.para_zeta_list[0].value = xi, zeta
-        prob = r.prob_LamMuZ_list[0]
-        prob.solve()
-        assert prob.status == "optimal"
-        lam, mu = r.indep_lam_list[0].value[:, 1], r.indep_mu_list[0].value[:, 1]
-        Im, Hm = float(r.indep_Im_array_LamMuZ[0].value[0]), r.indep_Hm_array_LamMuZ[0].value[0]
-        A = f64(r.para_obstacle_list[0]["A"][1].value)
-        b = f64(r.para_obstacle_list[0]["b"][1].value).ravel()
+    for trial, tr in enumerate(ref.get(f"ipm_one_stage.{robot}", reference_problems)):
+        assert tr["status"] == "optimal"
+        lam, mu, Im, Hm = np.array(tr["lam"]), np.array(tr["mu"]), tr["Im"], np.array(tr["Hm"])
+        A, b, cone, nom_s, dis, xi, zeta = f64(tr["A"]), f64(tr["b"]), tr["cone"], np.array(tr["nom_s"]), np.array(tr["dis"]), np.array(tr["xi"]), np.array(tr["zeta"])
+        value = tr["value"]
         lo, mo, zo, cmh, it = np.zeros(E), np.zeros(R), C.c_double(0), np.zeros(4), C.c_int(0)
         st = L.orc_lammuz_ipm_one(E, R, dptr(A), dptr(b), cone, rn2, dptr(f64(nom_s[0:2, 1])), float(nom_s[2, 0]), dptr(G), dptr(h),
                                   dptr(f64(xi[1])), float(zeta[0, 0]), float(dis[0, 0]), 1.3, 1, dptr(lo), dptr(mo),
@@ -504,9 +642,9 @@ def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, ro
         assert st in (0, 1), (trial, st)          # 1 = the normal-equations solver stalled between 1e-8 and 1e-6 (rare)
         n_inacc += int(st == 1)
         if st == 1:
-            assert abs(prob.value - cmh[0]) < 1e-5
+            assert abs(value - cmh[0]) < 1e-5
             continue
-        worst["cost"] = max(worst["cost"], abs(prob.value - cmh[0]))
+        worst["cost"] = max(worst["cost"], abs(value - cmh[0]))
         worst["H"] = max(worst["H"], float(np.max(np.abs(Hm - cmh[2:4]))))
         worst["mneg"] = max(worst["mneg"], abs(min(Im, 0.0) - min(cmh[1], 0.0)))
         act = (np.abs(A).sum(axis=1) > 0) if cone == 0 else np.arange(E) < 3

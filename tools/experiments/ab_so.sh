@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of builds of librda_hip.so (tools/_bin/librda_hip_<tag>.so): headline (re-sorted), fixed binding, k_su us; two interleaved rounds
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-B="python bench.py --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos ${FLEET:-0} --steps ${STEPS:-40} --warmup 10 $EXTRA"
+B="python bench.py --full --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos ${FLEET:-0} --steps ${STEPS:-40} --warmup 10 $EXTRA"
 for ROUND in 1 2; do for TAG in "$@"; do
   RDA_HIP_SO=$PWD/tools/_bin/librda_hip_$TAG.so $B 2>/dev/null | python -c "
 import json,sys

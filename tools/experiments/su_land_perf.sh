@@ -2,7 +2,7 @@
 # what the landing of the su solve costs (round 6): headline (re-sorted) and fixed binding, default mode vs RDA_SU_LAND=1 at three stops of the interior point
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 run() {
-  env $1 python bench.py --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos 0 --steps 40 --warmup 10 > /dev/null 2>&1
+  env $1 python bench.py --full --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos 0 --steps 40 --warmup 10 > /dev/null 2>&1
   python - "$1" <<'PY'
 import json, sys
 j = json.load(open("gpurun_out/bench_detail.json")); r = j["roofline"]; f = j["fixed_slot_binding"]

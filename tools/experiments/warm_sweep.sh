@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the su start rules on the headline loop (re-sorted every tick): bench value + mean interior-point iterations per solve
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-B="python bench.py --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos 0 --steps 80 --warmup 10"
+B="python bench.py --full --no-sizes --no-cpu-baseline --no-ip-legs --egos 0 --fleet-egos 0 --steps 80 --warmup 10"
 run() { echo "== $*"; env "$@" $B 2>/dev/null | python -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=j['roofline']

@@ -90,14 +90,14 @@ PY
   done
 done
 
-timeout 400 python bench.py --egos 16 --fleet-egos 64 2> /dev/null | grep '^{' > "$OUT/bench_ns.json"                 # 200-step window, every leg, sizes
+timeout 400 python bench.py --full --egos 16 --fleet-egos 64 2> /dev/null | grep '^{' > "$OUT/bench_ns.json"                 # 200-step window, every leg, sizes
 S0=$SECONDS
-timeout 200 python bench.py --steps 20 --warmup 5 2> /dev/null | grep '^{' > "$OUT/bench_ns_driver_window.json"        # the driver's command
-echo "wall clock of the driver's command (python bench.py --steps 20 --warmup 5): $((SECONDS - S0)) s" > "$OUT/driver_window_wall.txt"
-for CFG in n20 n2000 c4; do timeout 300 python bench.py --no-sizes --egos 0 --fleet-egos 0 --no-ip-legs --cpu-threads 16 ${ARGS[$CFG]} 2> /dev/null | grep '^{' > "$OUT/bench_${CFG}.json"; done
-timeout 300 python bench.py --no-cpu-baseline --no-sizes --no-ip-legs --egos 0 --fleet-egos 64 --n-obs 100 --horizon 25 2> /dev/null | grep '^{' > "$OUT/bench_c5_fleet.json"
+timeout 200 python bench.py --full --steps 20 --warmup 5 2> /dev/null | grep '^{' > "$OUT/bench_ns_driver_window.json"        # the driver's window, every leg
+echo "wall clock of the driver's window with every leg (python bench.py --full --steps 20 --warmup 5): $((SECONDS - S0)) s" > "$OUT/driver_window_wall.txt"
+for CFG in n20 n2000 c4; do timeout 300 python bench.py --full --no-sizes --egos 0 --fleet-egos 0 --no-ip-legs --cpu-threads 16 ${ARGS[$CFG]} 2> /dev/null | grep '^{' > "$OUT/bench_${CFG}.json"; done
+timeout 300 python bench.py --full --no-cpu-baseline --no-sizes --no-ip-legs --egos 0 --fleet-egos 64 --n-obs 100 --horizon 25 2> /dev/null | grep '^{' > "$OUT/bench_c5_fleet.json"
 D="$SCR/stats_c5"; mkdir -p "$D"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o f -- python bench.py --no-cpu-baseline --no-sizes --no-ip-legs --egos 0 --fleet-egos 64 --n-obs 100 --horizon 25 --steps 100 > /dev/null 2>&1 || true
+rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o f -- python bench.py --full --no-cpu-baseline --no-sizes --no-ip-legs --egos 0 --fleet-egos 64 --n-obs 100 --horizon 25 --steps 100 > /dev/null 2>&1 || true
 find "$D" -name '*kernel_stats.csv' -exec cp {} "$OUT/c5_fleet_kernel_stats.csv" \;
 # (the phase counters live in the profiling builds: tools/_bin/librda_hip_prof.so = -DSU_PROF, librda_hip_fine.so = -DSU_FINE, same sources)
 RDA_HIP_SO=$PWD/tools/_bin/librda_hip_prof.so python tools/su_phase_profile.py > "$OUT/suprof_ns_fixed_binding.txt" 2>&1
