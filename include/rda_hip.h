@@ -160,8 +160,8 @@ typedef struct rda_opts {
                                 the central path the iteration stopped (the reason for the stated tolerance of rounds 3-5, 5e-4: a row that is only just
                                 active keeps the slack mu / lam*): kernel and cold oracle agree to 1e-9 with it (tests/test_gpu_land.py).
                                 Costs one factorisation + a verification pass per solve, saves the last interior-point iteration.  RDA_SU_LAND */
-    double  su_land_tol[3];  /* [1e-3, 1e-4, 1e-5] first stop of the interior point when it is landed; a refused landing is tried once more at 1e-2 x
-                                these values, then the iteration runs to su_tol                                                  RDA_SU_LAND_TOL */
+    double  su_land_tol[3];  /* [1e-3, 1e-4, 1e-5] first stop of the interior point when it is landed; a refused landing is tried again at 1e-2^k x
+                                these values (k = 1, 2, ... while they lie above su_tol), then the iteration stops at SU_LAND_FALLBACK x su_tol RDA_SU_LAND_TOL */
     double  su_land_rho;     /* [1e4] penalty of the landing's active rows, relative to the largest entry of the stage Hessians  RDA_SU_LAND_RHO */
     int32_t su_land_first;   /* [2] landing FIRST, for the warm-started su-problems (ADMM iterations >= 1: from the previous solution of the step and its multipliers; the first
                                 one of a tick: from the previous tick's solution, shifted by one stage).
@@ -403,7 +403,9 @@ int  rda_lammuz_batch(int B, int E, int R, const double *A, const double *b, con
                       int accelerated, double *lam, double *mu, double *z, double *cmh);
 
 /* su-problem with condensed obstacle terms a [N][T][2], cc [N][T], g [N][T][2];
- * d0 [T] initial guess; outputs s 3x(T+1), u 2xT, d [T].  Returns 0 ok, 1 not converged. */
+ * d0 [T] initial guess; outputs s 3x(T+1), u 2xT, d [T].  Returns 0 ok, 1 not converged.
+ * N = 0 (no obstacle terms) is refused here (RDA_ERR_UNSUPPORTED, like rda_create).  The su-problem itself is defined there: d keeps its
+ * cost -slack_gain sum(d) and its bounds, so d = max_sd (the oracle's orc_su_solve and tests/su_kkt.py solve it so). */
 int  rda_su_solve(const rda_cfg *cfg, const double *nom_s, const double *nom_u, const double *ref_s,
                   double ref_speed, const double *a, const double *cc, const double *g,
                   const double *d0, double *s, double *u, double *d, int32_t *ipm_iters);

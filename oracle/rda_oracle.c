@@ -695,7 +695,7 @@ static void chol_solve(const double *K, int n, double *rhs)
  * gradient at x+ (hinge terms re-evaluated) is stationary; otherwise move rows in / out of A by their signs (primal-dual active set) and try again, a few
  * rounds; no acceptance: the interior-point iterate is returned as before.  The model is solved by the method of multipliers on
  * K = H + rho C_A' C_A (one Cholesky factor, a few solves: converges like (|H| / rho)^k), so no row of C_A has to be independent of the others. */
-static int g_su_land = 1; static double g_su_land_tol[3] = {1e-3, 1e-4, 1e-5};   /* = rda_opts::su_land, su_land_tol (first stop; a refused landing is tried again at 1e-2 x, then never) */
+static int g_su_land = 1; static double g_su_land_tol[3] = {1e-3, 1e-4, 1e-5};   /* = rda_opts::su_land, su_land_tol (first stop; a refused landing is tried again at 1e-2^k x while above su_tol, then the stop is SU_LAND_FALLBACK x su_tol) */
 static __thread int t_su_landed = 0, t_su_land_rounds = 0;
 static long g_pol_stat[8];       /* calls, accepted, rounds summed, last verdict: chol failed, set still moving, not stationary; rows moved */
 void orc_get_su_land_stats(long *out8) { for (int i = 0; i < 8; ++i) { out8[i] = g_pol_stat[i]; g_pol_stat[i] = 0; } }
@@ -904,7 +904,7 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
         if (g_su_land && land_failed < 99) {
             /* Landing (round 6, see su_land): the interior point only has to get close enough for the active set to be read off - su_land_tol - and the
              * vertex is then computed exactly.  Refused (the active-set rounds can cycle while borderline rows are undecided): tried again at 1e-2 x
-             * su_land_tol, 1e-4 x ... down to su_tol itself, then the iterate at su_tol is returned as without the landing. */
+             * su_land_tol, 1e-4 x ... down to su_tol itself; once that one is refused the iteration stops at SU_LAND_FALLBACK x su_tol (below). */
             double lt[3], lsc = 1.0; int last = 1;
             for (int k = 0; k < land_failed && k < 8; ++k) lsc *= 1e-2;
             for (int k = 0; k < 3; ++k) { lt[k] = lsc * g_su_land_tol[k]; if (lt[k] <= g_su_tol[k]) lt[k] = g_su_tol[k]; else last = 0; }

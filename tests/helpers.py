@@ -19,6 +19,9 @@ from rda_planner_amd._capi import Cfg, dptr, iptr
 # interior point at su_tol - TOL_U_IP below is what holds for it.  Seen on 4 of 64 000 `--exotic` soak steps (0 of 230 000 others): 4.8e-6 .. 1.2e-4 in the steering angle
 # of an Ackermann robot at |v| <= 0.13 m/s, a direction the su-problem is nearly singular in; <= 3.9e-7 in what the robot does with the control (yaw rate).
 # Since the last commit of the round that fallback runs 1e-3 x tighter than su_tol (SU_LAND_FALLBACK, both sides): the same 64 000 steps again: max 4.6e-7, no step outside TOL_U.
+# Against the independent certified optimum (tests/su_kkt.py, tests/test_su_kkt_ref.py): the landed cold oracle is within 4e-10 of x* on a 240-problem grid and the
+# recorded hard problems - but 1.35e-7 on tests/golden/su_hard/diff_T20_N24_just_active_hinges.npz (m = 0.25, f - f* = 1.7e-13): hinge rows 1e-8 .. 1e-7 from their switch,
+# and a landing that is accepted at a stationarity residual of 100 x su_tol[0] relative.  Inside TOL_U, outside TOL_U_FIXED (pinned as a strict xfail there).
 TOL_U = 1e-6
 # ... and the bound asserted on the FIXED scenes of tests/test_gpu_baseline_sizes.py (BASELINE sizes) and the reference's dynamic_obs scene
 TOL_U_FIXED = 1e-7

@@ -4,43 +4,10 @@ import numpy as np
 import pytest
 
 import helpers as hp
+import su_kkt
 
 
-def _lin(dyn, s, u, dt, L):
-    phi, v, psi = s[2], u[0], u[1]
-    if dyn == 2:
-        phi = u[1]
-        A = np.eye(3)
-        B = np.array([[np.cos(phi) * dt, -v * np.sin(phi) * dt], [np.sin(phi) * dt, v * np.cos(phi) * dt], [0, 0]])
-        C = np.array([phi * v * np.sin(phi) * dt, -phi * v * np.cos(phi) * dt, 0])
-        return A, B, C
-    A = np.array([[1, 0, -v * dt * np.sin(phi)], [0, 1, v * dt * np.cos(phi)], [0, 0, 1]])
-    if dyn == 0:
-        B = np.array([[np.cos(phi) * dt, 0], [np.sin(phi) * dt, 0], [np.tan(psi) * dt / L, v * dt / (L * np.cos(psi) ** 2)]])
-        C = np.array([phi * v * np.sin(phi) * dt, -phi * v * np.cos(phi) * dt, -psi * v * dt / (L * np.cos(psi) ** 2)])
-    else:
-        B = np.array([[np.cos(phi) * dt, 0], [np.sin(phi) * dt, 0], [0, dt]])
-        C = np.array([phi * v * np.sin(phi) * dt, -phi * v * np.cos(phi) * dt, 0])
-    return A, B, C
-
-
-def _objective(cfg, si, S, U, D):
-    """the reference's su cost, literally (rda_solver.py:1011-1032, 846-851, 868, 376-383)"""
-    T, N, dyn = cfg.T, cfg.N, cfg.dynamics
-    w = np.array([1, 1, 0.0 if dyn == 2 else 1.0])[:, None]
-    J = cfg.ws * np.sum(w * (S - si["ref"]) ** 2) + cfg.wu * np.sum((U[0] - si["vref"]) ** 2) - cfg.slack_gain * np.sum(D)
-    J += 0.5 * cfg.eps_u * np.sum(U ** 2)
-    for t in range(T):
-        ph = si["nom_s"][2, t]
-        Rm = np.array([[np.cos(ph), -np.sin(ph)], [np.sin(ph), np.cos(ph)]])
-        dR = np.array([[-np.sin(ph), -np.cos(ph)], [np.cos(ph), -np.sin(ph)]])
-        rot = Rm + dR * (S[2, t + 1] - ph)
-        for n in range(N):
-            Im = si["a"][n, t] @ S[0:2, t + 1] - si["cc"][n, t] - D[t]
-            J += 0.5 * cfg.ro1 * (min(Im, 0) ** 2 if cfg.accelerated else Im ** 2)
-            Hm = si["g"][n, t] + si["a"][n, t] @ rot
-            J += 0.5 * cfg.ro2 * Hm @ Hm
-    return J
+_lin, _objective = su_kkt.lin, su_kkt.objective          # the reference's linearisation and cost (restated in tests/su_kkt.py)
 
 
 @pytest.fixture(autouse=True)

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import helpers as hp
+import su_kkt
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr, f64
 
@@ -116,6 +117,9 @@ def test_oracle_argmins_on_reference_built_problems(orc):
         cfg, si = _su_case(g, k)
         st, s, u, d, it = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
         assert st == 0 and max(np.abs(s - g[f"su.{k}.s"]).max(), np.abs(u - g[f"su.{k}.u"]).max(), np.abs(d - g[f"su.{k}.d"]).max()) < 2e-6
+        # ... and within TOL_U_FIXED of the certified optimum (tests/su_kkt.py, seeded by the reference's answer)
+        cert = su_kkt.certify(cfg, si, start=(g[f"su.{k}.s"], g[f"su.{k}.u"], g[f"su.{k}.d"]))
+        assert cert.distance(s, u, d) <= hp.TOL_U_FIXED, (k, cert.distance(s, u, d))
 
 
 def _check_lmz(g, z, cmh):
@@ -212,6 +216,8 @@ def test_hip_argmins_on_reference_built_problems(hip):
         cfg, si = _su_case(g, k)
         st, s, u, d, it = hp.su_solve(hip.lib.rda_su_solve, cfg, si)
         assert st == 0 and max(np.abs(s - g[f"su.{k}.s"]).max(), np.abs(u - g[f"su.{k}.u"]).max(), np.abs(d - g[f"su.{k}.d"]).max()) < 2e-6
+        cert = su_kkt.certify(cfg, si, start=(g[f"su.{k}.s"], g[f"su.{k}.u"], g[f"su.{k}.d"]))
+        assert cert.distance(s, u, d) <= hp.TOL_U_FIXED, (k, cert.distance(s, u, d))
 
 
 def test_cvxpy_fixtures_agree_with_the_shim_fixtures_where_the_answer_is_unique():
