@@ -187,7 +187,8 @@ const char *rda_strerror(int code);
 int  rda_device_count(void);
 int  rda_set_device(int dev);     /* device used by handles created afterwards (one process per GPU).  HIP's current device belongs to the calling HOST THREAD
                                    * (default 0): a thread that drives handles or fleets created on device `dev` calls this once first.  The library keeps
-                                   * no state outside its handles and fleets: distinct handles / fleets may be driven by distinct threads concurrently
+                                   * no state outside its handles and fleets but the two debug counters of rda_debug_alloc_fail (per thread) and
+                                   * rda_debug_alloc_stats (process-wide, atomic): distinct handles / fleets may be driven by distinct threads concurrently
                                    * (one thread at a time per handle or fleet) */
 
 /* One MPC step, host buffers: nom_s 3x(T+1), nom_u 2xT, ref_s 3x(T+1) row-major;
@@ -360,6 +361,11 @@ int  rda_debug_su_land_n(rda_handle *h, int32_t *out, int n);   /* ... the first
 int  rda_debug_flush_supports(rda_handle *h);             /* forget every remembered LamMuZ support (a cache: results must not depend on it) */
 int  rda_debug_slot_src(rda_handle *h, int32_t *src /*N*/, int32_t *used); /* slot -> entry of the caller's raw scene (device pipeline; used = 0: host-staged slots) */
 int  rda_debug_worklist(rda_handle *h, int *rows);        /* rows on the LamMuZ work list of the last executed iteration (split launch form) */
+/* debug: every call that fails changes nothing and leaks nothing (tests/test_gpu_lifecycle.py).  rda_debug_alloc_fail: in the calling thread, the
+ * device or pinned allocation with index n (0 = the next one) among those the library requests from now on is refused as if the HIP allocation
+ * had failed (n < 0 disarms); rda_debug_alloc_stats: the device and pinned allocations the library holds now (count, bytes), process-wide */
+int  rda_debug_alloc_fail(int n);
+int  rda_debug_alloc_stats(long long *live_allocs, long long *live_bytes);
 
 /* Obstacle sharding across the GPUs of one node (one process per GPU).  Rank r owns the obstacle slots
  * [r*ceil(N/world), (r+1)*ceil(N/world)): it solves their LamMuZ problems and keeps their duals.  What the su-problem needs of

@@ -89,6 +89,10 @@ class CApi:
                               c_double_p, c_double_p, c_int_p, C.c_int, c_double_p, c_double_p,
                               C.POINTER(Info)]
         f("step").restype = C.c_int
+        if hasattr(lib, f"{prefix}_debug_alloc_fail"):          # (HIP library only: the allocation rule's test hooks)
+            f("debug_alloc_fail").argtypes = [C.c_int]
+            f("debug_alloc_stats").argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+            f("debug_alloc_fail").restype = f("debug_alloc_stats").restype = C.c_int
         f("get_state").argtypes = [C.c_void_p] + [c_double_p] * 8
         f("get_state").restype = C.c_int
         f("set_state").argtypes = [C.c_void_p] + [c_double_p] * 8

@@ -22,8 +22,10 @@
 #include <cstring>
 #include <vector>
 #include <chrono>
+#include <memory>
 #include <dlfcn.h>
 #include "../../include/rda_hip.h"
+#include "host_buf.h"
 #include "lammuz_device.h"
 #include "lammuz_cp_device.h"
 #include "lammuz_ip_device.h"
@@ -1359,10 +1361,11 @@ __global__ __launch_bounds__(64) void k_follow_back(Dev d, const int *map, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// A handle owns its device / pinned buffers through the groups near the end (Dev and the members below hold views into them), its
+// events and its streams: deleting a handle releases everything, the streams first (each is synchronised before it is destroyed).
 struct rda_handle {
     Dev d;
     rda_opts opts;                                        // as handed to rda_create_opts (copied)
-    hipStream_t stream;
     size_t su_lds;
     // staging
     double *h_stage_A, *h_stage_b; int *h_stage_cone;    // pinned, N slots
@@ -1384,13 +1387,13 @@ struct rda_handle {
     int fuse_track; size_t su_trk_lds; unsigned long long trk_seq;
     int lmz_split;                        // dense LamMuZ grids as two launches: common path, then the deferred rows (RDA_LMZ_SPLIT=0: one fused kernel)
     int early_finish;                     // the su launch that detects the early stop writes the result slot (RDA_EARLY_FINISH=0: k_finish does)    // k_su_tracked (RDA_FUSE_TRACK=0: k_track and k_su as two launches)
-    hipStream_t stream2; hipEvent_t ev_tick, ev_scene; int scene_on_s2;   // in-tick scene staging runs beside the first su-problem
+    int scene_on_s2;                      // in-tick scene staging runs beside the first su-problem (stream2, ev_tick, ev_scene)
     // timing
-    int timing; std::vector<hipEvent_t> ev[3]; size_t ev_used[3];      // 0 LamMuZ launches, 1 su launches, 2 shard all-gathers
+    int timing; size_t ev_used[3];       // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers
     // device-side obstacle pipeline (rda_upload_scene): scene description and scratch, grown on demand
     int sc_cap; int *d_sc_sel; double *d_sc_blk, *d_sc_key;     // d_sc_blk mirrors the pinned block h_sc (ONE H2D copy per upload)
     scene::Args sc_args; int sc_n;                              // the resident raw scene as the conversion kernels were last given it (sc_n = 0: none)
-    void *h_sc; size_t h_sc_bytes;
+    char *h_sc; size_t h_sc_bytes;
     // device-side pre_process (rda_upload_path / rda_step_tracked)
     double *d_path; int path_len; track::Out *d_trk, *h_trk;
     int dense_from;          // grids above this many workgroups use the dense form of the LamMuZ launch (rda_opts::lmz_dense_from)
@@ -1399,9 +1402,14 @@ struct rda_handle {
     int stepped;             // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
     // rda_opts::duals_follow: slot -> raw-scene entry of the staging the dual state is arranged by (prev_used = -1: none yet)
     int follow; int *d_prev_sel, *d_follow_map; double *d_follow_tmp; int prev_used;
+    // owners
+    hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL), staging, result slot, follow tables
+    hbuf::Group terms;                    // Dev::coef, coefL (rda_shard_config replaces them)
+    hbuf::Group trace, path, scene, scene_host, verdict;    // d_tr_*; d_path; d_sc_*; h_sc; h_verdict
+    std::vector<hbuf::Event> ev[3];
+    hbuf::Event ev_tick, ev_scene;
+    hbuf::Stream stream, stream2;         // (last: destroyed first)
 };
-
-static void dev_free(void *p) { if (p) (void)hipFree(p); }
 
 extern "C" const char *rda_strerror(int code)
 {
@@ -1419,13 +1427,6 @@ extern "C" int rda_set_device(int dev) { HIPCHK(hipSetDevice(dev)); return RDA_O
 
 static size_t res_doubles(size_t T) { return 2 * T + 3 * (T + 1) + 8; }     // u | s | info (4) | track::Out (2) | non-convex count | sequence word
 static_assert(9 * su::NT >= track::LDS_DOUBLES, "TrackedRefWait runs track::run in the su solve's `part` scratch");
-
-template <typename Tp> static int dalloc(Tp **p, size_t n)
-{
-    HIPCHK(hipMalloc((void **)p, n * sizeof(Tp)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(Tp)));
-    return 0;
-}
 
 // Solver options: library defaults, then the RDA_* environment overrides (experiments and A/B runs; read HERE only)
 extern "C" void rda_opts_init(rda_opts *o)
@@ -1471,30 +1472,20 @@ static int robot_candidates(int R, const double *G, const double *h, unsigned ch
     return n;
 }
 
-static int create_impl(const rda_cfg *cfg, const rda_opts *opts, const double *G, const double *h, rda_handle **out, rda_handle **partial);
 static int terms_rebuild(rda_handle *H);
-extern "C" void rda_destroy(rda_handle *H);
 
 extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const double *G, const double *h, rda_handle **out)
 {
-    rda_handle *partial = nullptr;                      // a failure half-way releases what was built (rda_destroy takes partial handles)
     rda_opts def;
     if (!opts) { rda_opts_init(&def); opts = &def; }
-    const int rc = create_impl(cfg, opts, G, h, out, &partial);
-    if (rc != RDA_OK && partial) { rda_destroy(partial); if (out) *out = nullptr; }
-    return rc;
-}
-extern "C" int rda_create(const rda_cfg *cfg, const double *G, const double *h, rda_handle **out) { return rda_create_opts(cfg, nullptr, G, h, out); }
-
-static int create_impl(const rda_cfg *cfg, const rda_opts *opts, const double *G, const double *h, rda_handle **out, rda_handle **partial)
-{
     if (!cfg || !G || !h || !out) return RDA_ERR_ARG;
     if (cfg->robot_norm2 && cfg->R < 2) return RDA_ERR_UNSUPPORTED;
     if (cfg->E < 1 || cfg->E > RDA_EMAX || cfg->R < 1 || cfg->R > RDA_RMAX || cfg->T < 1 || cfg->T > RDA_TMAX || cfg->N < 1) return RDA_ERR_UNSUPPORTED;
     if (cfg->E + cfg->R + 1 > 64) return RDA_ERR_UNSUPPORTED;
     if (rda_device_count() < 1) return RDA_ERR_NODEVICE;
-    rda_handle *H = new rda_handle();
-    *partial = H;
+    *out = nullptr;
+    std::unique_ptr<rda_handle> owner(new rda_handle());     // a failure on the way drops the handle and with it what was built
+    rda_handle *H = owner.get();
     memset(&H->d, 0, sizeof(Dev));
     H->d.c = *cfg; H->d.nt = 1; H->d.obstacle_num = 0; H->K = 0; H->timing = 0;
     H->opts = *opts;
@@ -1516,48 +1507,52 @@ static int create_impl(const rda_cfg *cfg, const rda_opts *opts, const double *G
     H->d.su_land_blind_from = o.su_land_blind_from;
     H->d.su_land = o.su_land ? 1 : 0; H->d.su_land_rho = o.su_land_rho > 0 ? o.su_land_rho : 1e4;
     { const bool ok = o.su_land_tol[0] > 0 && o.su_land_tol[1] > 0 && o.su_land_tol[2] > 0; const double dflt[3] = {1e-3, 1e-4, 1e-5}; for (int i = 0; i < 3; ++i) H->d.su_land_tol[i] = ok ? o.su_land_tol[i] : dflt[i]; }
-    H->follow = o.duals_follow != 0; H->prev_used = -1; H->d_prev_sel = nullptr; H->d_follow_map = nullptr; H->d_follow_tmp = nullptr;
+    H->follow = o.duals_follow != 0; H->prev_used = -1;
     for (int i = 0; i < 3; ++i) H->d.su_tol[i] = o.su_tol[i] > 0 ? o.su_tol[i] : (i == 0 ? 1e-9 : (i == 1 ? 1e-10 : 1e-11));
     { const bool on = o.su_tol_early[0] > 0 && o.su_tol_early[1] > 0 && o.su_tol_early[2] > 0; for (int i = 0; i < 3; ++i) H->d.su_tol_early[i] = on ? o.su_tol_early[i] : 0.0; }
     H->nccl_lib = nullptr; H->comm = nullptr; H->p_allgather = nullptr; H->p_comm_destroy = nullptr; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = 0;
-    H->d_tr_s = H->d_tr_u = H->d_tr_ref = H->d_tr_speed = H->d_tr_out_u = H->d_tr_out_s = nullptr; H->d_tr_info = nullptr;
     const size_t T = cfg->T, N = cfg->N, E = cfg->E, R = cfg->R;
-    HIPCHK(hipStreamCreate(&H->stream));
-    HIPCHK(hipStreamCreate(&H->stream2));
-    HIPCHK(hipEventCreateWithFlags(&H->ev_tick, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&H->ev_scene, hipEventDisableTiming));
+    HIPCHK(hipStreamCreate(H->stream.out()));
+    HIPCHK(hipStreamCreate(H->stream2.out()));
+    HIPCHK(hipEventCreateWithFlags(H->ev_tick.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(H->ev_scene.out(), hipEventDisableTiming));
     Dev &d = H->d;
+    hbuf::Group &m = H->mem;
     int rc = 0;
-    rc |= dalloc(&d.G, 2 * R); rc |= dalloc(&d.h, R);
-    rc |= dalloc(&d.A, N * (T + 1) * E * 2); rc |= dalloc(&d.b, N * (T + 1) * E); rc |= dalloc(&d.cone, N);
-    rc |= dalloc(&d.wl, (N + GS) * T); d.wl_cap = (int)((N + GS) * T); d.src_cap = (int)(4 * N + 256); d.hint_stride = (int)N + d.src_cap; d.hint_len = d.hint_stride * (int)T; d.slot_src = nullptr; d.src_used = 0;
-    rc |= dalloc(&d.hint, 2 * (size_t)d.hint_len); d.oc_ls = (1 + (int)E + (int)E * ((int)E - 1) / 2 + 3) & ~3; d.oc_vs = (int)E * ((int)E - 1) > 2 ? (int)E * ((int)E - 1) : 2;
-    rc |= dalloc(&d.oc_lamc, N * (T + 1) * d.oc_ls); rc |= dalloc(&d.oc_vtx, N * (T + 1) * d.oc_vs); rc |= dalloc(&d.oc_cnt, N * (T + 1) * 2);
-    rc |= dalloc(&d.lam, N * (T + 1) * E); rc |= dalloc(&d.mu, N * (T + 1) * R); rc |= dalloc(&d.z, N * T);
-    rc |= dalloc(&d.xi, N * (T + 1) * 2); rc |= dalloc(&d.zeta, N * T); rc |= dalloc(&d.dis, T);
+    rc |= m.dev(&d.G, 2 * R); rc |= m.dev(&d.h, R);
+    rc |= m.dev(&d.A, N * (T + 1) * E * 2); rc |= m.dev(&d.b, N * (T + 1) * E); rc |= m.dev(&d.cone, N);
+    rc |= m.dev(&d.wl, (N + GS) * T); d.wl_cap = (int)((N + GS) * T); d.src_cap = (int)(4 * N + 256); d.hint_stride = (int)N + d.src_cap; d.hint_len = d.hint_stride * (int)T; d.slot_src = nullptr; d.src_used = 0;
+    rc |= m.dev(&d.hint, 2 * (size_t)d.hint_len); d.oc_ls = (1 + (int)E + (int)E * ((int)E - 1) / 2 + 3) & ~3; d.oc_vs = (int)E * ((int)E - 1) > 2 ? (int)E * ((int)E - 1) : 2;
+    rc |= m.dev(&d.oc_lamc, N * (T + 1) * d.oc_ls); rc |= m.dev(&d.oc_vtx, N * (T + 1) * d.oc_vs); rc |= m.dev(&d.oc_cnt, N * (T + 1) * 2);
+    rc |= m.dev(&d.lam, N * (T + 1) * E); rc |= m.dev(&d.mu, N * (T + 1) * R); rc |= m.dev(&d.z, N * T);
+    rc |= m.dev(&d.xi, N * (T + 1) * 2); rc |= m.dev(&d.zeta, N * T); rc |= m.dev(&d.dis, T);
     d.P = 1; d.rank = 0; d.Nloc = (int)N; d.Nlive = (int)N; d.J = (int)((N + GS - 1) / GS); d.chunk = chunk_doubles((int)T, (int)N); d.lchunk = lchunk_doubles((int)T, (int)N);
-    rc |= dalloc(&d.coef, d.chunk); rc |= dalloc(&d.coefL, d.lchunk);
-    rc |= dalloc(&d.s, 3 * (T + 1)); rc |= dalloc(&d.u, 2 * T); rc |= dalloc(&d.pose, 4 * T);
-    rc |= dalloc(&d.ctrl, 1);
-    rc |= dalloc(&d.su_lam_keep, 10 * T);
+    rc |= H->terms.dev(&d.coef, d.chunk); rc |= H->terms.dev(&d.coefL, d.lchunk);
+    rc |= m.dev(&d.s, 3 * (T + 1)); rc |= m.dev(&d.u, 2 * T); rc |= m.dev(&d.pose, 4 * T);
+    rc |= m.dev(&d.ctrl, 1);
+    rc |= m.dev(&d.su_lam_keep, 10 * T);
     if (H->follow) {
-        rc |= dalloc(&H->d_prev_sel, N); rc |= dalloc(&H->d_follow_map, N);
-        rc |= dalloc(&H->d_follow_tmp, N * (T + 1) * (E + R + 2) + 2 * N * T);
+        rc |= m.dev(&H->d_prev_sel, N); rc |= m.dev(&H->d_follow_map, N);
+        rc |= m.dev(&H->d_follow_tmp, N * (T + 1) * (E + R + 2) + 2 * N * T);
     }
 #if defined(SU_TRACE)
-    if (o.su_prof) rc |= dalloc(&d.su_prof, su::PROF_WORDS);                   // 16 + the per-wave event trace of the LAST su launch (tools/su_trace.py)
+    if (o.su_prof) rc |= m.dev(&d.su_prof, su::PROF_WORDS);                   // 16 + the per-wave event trace of the LAST su launch (tools/su_trace.py)
 #elif defined(SU_PROF) || defined(SU_FINE)
-    if (o.su_prof) rc |= dalloc(&d.su_prof, 16);
+    if (o.su_prof) rc |= m.dev(&d.su_prof, 16);
 #else
-    if (o.su_prof) { rda_destroy(H); *partial = nullptr; return RDA_ERR_UNSUPPORTED; }     // phase counters: profiling builds only (-DSU_PROF / -DSU_FINE, tools/su_phase_profile.py)
+    if (o.su_prof) return RDA_ERR_UNSUPPORTED;     // phase counters: profiling builds only (-DSU_PROF / -DSU_FINE, tools/su_phase_profile.py)
 #endif
     const size_t step_n = 3 * (T + 1) + 2 * T + 3 * (T + 1) + 1;
-    rc |= dalloc(&H->d_step, step_n);
+    rc |= m.dev(&H->d_step, step_n);
     // result block, identical on the device and in pinned memory: u [2T] | s [3(T+1)] | rda_info (4 doubles) | track::Out (4 doubles):
     // ONE copy back per step
-    rc |= dalloc(&H->d_out_u, res_doubles(T));
-    if (!rc) { H->d_out_s = H->d_out_u + 2 * T; H->d_info = (rda_info *)(H->d_out_s + 3 * (T + 1)); H->d_trk = (track::Out *)(H->d_out_s + 3 * (T + 1) + 4); }
-    if (rc) { rda_destroy(H); *partial = nullptr; return RDA_ERR_HIP; }
+    rc |= m.dev(&H->d_out_u, res_doubles(T));
+    rc |= m.pin(&H->h_stage_A, N * (T + 1) * E * 2); rc |= m.pin(&H->h_stage_b, N * (T + 1) * E); rc |= m.pin(&H->h_stage_cone, N);
+    rc |= m.pin(&H->h_step, step_n); rc |= m.pin(&H->h_out, res_doubles(T));
+    H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated);
+    if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
+    if (rc) return RDA_ERR_HIP;
+    H->d_out_s = H->d_out_u + 2 * T; H->d_info = (rda_info *)(H->d_out_s + 3 * (T + 1)); H->d_trk = (track::Out *)(H->d_out_s + 3 * (T + 1) + 4);
     { const int hard = 99; HIPCHK(hipMemcpy(&d.ctrl->su_last, &hard, sizeof(int), hipMemcpyHostToDevice)); }     // no su history yet
     HIPCHK(hipMemcpy(d.G, G, 2 * R * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.h, h, R * sizeof(double), hipMemcpyHostToDevice));
@@ -1565,12 +1560,7 @@ static int create_impl(const rda_cfg *cfg, const rda_opts *opts, const double *G
     HIPCHK(hipMemcpy(d.dis, ones.data(), T * sizeof(double), hipMemcpyHostToDevice));
     std::vector<int> cn(N, 1);                                              // para_cone init, rda_solver.py:158
     HIPCHK(hipMemcpy(d.cone, cn.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipHostMalloc((void **)&H->h_stage_A, N * (T + 1) * E * 2 * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&H->h_stage_b, N * (T + 1) * E * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&H->h_stage_cone, N * sizeof(int)));
-    HIPCHK(hipHostMalloc((void **)&H->h_step, step_n * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&H->h_out, res_doubles(T) * sizeof(double)));
-    memset(H->h_out, 0, res_doubles(T) * sizeof(double)); H->res_seq = 0; H->zero_copy = o.zero_copy;
+    H->res_seq = 0; H->zero_copy = o.zero_copy;
     H->h_info = (rda_info *)(H->h_out + 2 * T + 3 * (T + 1)); H->h_trk = (track::Out *)(H->h_out + 2 * T + 3 * (T + 1) + 4);
     H->su_lds = su::lds_bytes((int)T);
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_lds)));
@@ -1580,39 +1570,22 @@ static int create_impl(const rda_cfg *cfg, const rda_opts *opts, const double *G
     H->fuse_track = o.fuse_track; H->tick_stages = 0; H->tick_has_event = 0; H->trk_seq = 0;
     H->early_finish = o.early_finish;
     H->lmz_split = o.lmz_split;
-    H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated); H->admm_it = 0;
-    if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { if (dalloc(&H->d.ipw, N * T * 80) || dalloc(&H->d.ipf, N * T)) return RDA_ERR_HIP; }
+    H->admm_it = 0;
     // the terms of a fresh handle are all zero: their block partials (zero sums, every slot NEAR: a = 0 puts the hinge at -d < 0)
     int rcf = terms_rebuild(H);
     if (rcf != RDA_OK) return rcf;
     HIPCHK(hipStreamSynchronize(H->stream));
-    *out = H;
+    *out = owner.release();
     return RDA_OK;
 }
+extern "C" int rda_create(const rda_cfg *cfg, const double *G, const double *h, rda_handle **out) { return rda_create_opts(cfg, nullptr, G, h, out); }
 
 extern "C" void rda_destroy(rda_handle *H)
 {
     if (!H) return;
-    if (H->stream) (void)hipStreamSynchronize(H->stream);
+    (void)hipStreamSynchronize(H->stream);         // nothing is released while a launch or a collective may still use it
+    (void)hipStreamSynchronize(H->stream2);
     if (H->comm && H->p_comm_destroy) H->p_comm_destroy(H->comm);
-    Dev &d = H->d;
-    void *ptrs[] = { d.wl, d.hint, d.oc_lamc, d.oc_vtx, d.oc_cnt, d.G, d.h, d.A, d.b, d.cone, d.lam, d.mu, d.z, d.xi, d.zeta, d.dis, d.coef, d.coefL,
-                     d.s, d.u, d.pose, d.su_prof, d.ipw, d.ipf, d.ctrl, d.su_lam_keep, H->d_step, H->d_out_u,
-                     H->d_tr_s, H->d_tr_u, H->d_tr_ref, H->d_tr_speed, H->d_tr_out_u, H->d_tr_out_s, H->d_tr_info,
-                     H->d_sc_sel, H->d_sc_blk, H->d_sc_key, H->d_path, H->d_prev_sel, H->d_follow_map, H->d_follow_tmp };
-    for (void *p : ptrs) dev_free(p);
-    if (H->h_stage_A) (void)hipHostFree(H->h_stage_A);
-    if (H->h_stage_b) (void)hipHostFree(H->h_stage_b);
-    if (H->h_stage_cone) (void)hipHostFree(H->h_stage_cone);
-    if (H->h_step) (void)hipHostFree(H->h_step);
-    if (H->h_out) (void)hipHostFree(H->h_out);
-    if (H->h_sc) (void)hipHostFree(H->h_sc);
-    if (H->h_verdict) (void)hipHostFree(H->h_verdict);
-    for (int w = 0; w < 3; ++w) for (hipEvent_t e : H->ev[w]) (void)hipEventDestroy(e);
-    if (H->stream2) { (void)hipStreamSynchronize(H->stream2); (void)hipStreamDestroy(H->stream2); }
-    if (H->ev_tick) (void)hipEventDestroy(H->ev_tick);
-    if (H->ev_scene) (void)hipEventDestroy(H->ev_scene);
-    if (H->stream) (void)hipStreamDestroy(H->stream);
     delete H;
 }
 
@@ -1771,6 +1744,15 @@ extern "C" int rda_debug_worklist(rda_handle *H, int *rows)
     HIPCHK(hipMemcpy(rows, &H->d.ctrl->wl_count, sizeof(int), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
+// debug / test hooks of the rule that a failed call changes nothing and leaks nothing (host_buf.h): refuse the allocation with index n among
+// those this thread requests from now on (n < 0: none), and what the library holds now
+extern "C" int rda_debug_alloc_fail(int n) { hbuf::refuse_in = n; return RDA_OK; }
+extern "C" int rda_debug_alloc_stats(long long *live_allocs, long long *live_bytes)
+{
+    if (live_allocs) *live_allocs = hbuf::live_allocs;
+    if (live_bytes) *live_bytes = hbuf::live_bytes;
+    return RDA_OK;
+}
 
 // assign_obstacle_parameter (rda_solver.py:483-526): pad / truncate into N slots, then upload
 static int obstacles_stage(rda_handle *H, int n_obs, const double *A, const double *b, const int32_t *cone, int per_t, bool sync)
@@ -1817,23 +1799,17 @@ extern "C" int rda_upload_obstacles(rda_handle *H, int n_obs, const double *A, c
 static size_t scene_block_bytes(size_t n, size_t E) { return n * (E * 2 + 2) * sizeof(double) + 3 * sizeof(double) + 2 * n * sizeof(int); }
 static int scene_reserve(rda_handle *H, int n)
 {
-    const size_t E = H->d.c.E;
-    if (n > H->sc_cap) {
-        dev_free(H->d_sc_blk); dev_free(H->d_sc_sel); dev_free(H->d_sc_key);
-        H->d_sc_blk = nullptr; H->d_sc_sel = nullptr; H->d_sc_key = nullptr; H->sc_cap = 0; H->sc_n = 0;
-        int cap = n + n / 2 + 16, rc = 0;
-        rc |= dalloc(&H->d_sc_blk, scene_block_bytes((size_t)cap, E) / sizeof(double) + 1);
-        rc |= dalloc(&H->d_sc_sel, (size_t)cap); rc |= dalloc(&H->d_sc_key, (size_t)cap);
-        if (rc) return RDA_ERR_HIP;
-        H->sc_cap = cap;
-    }
-    const size_t need = scene_block_bytes((size_t)n, E);
-    if (need > H->h_sc_bytes) {
-        if (H->h_sc) (void)hipHostFree(H->h_sc);
-        H->h_sc = nullptr; H->h_sc_bytes = 0;
-        HIPCHK(hipHostMalloc(&H->h_sc, need * 2));
-        H->h_sc_bytes = need * 2;
-    }
+    const size_t E = H->d.c.E, need = scene_block_bytes((size_t)n, E);
+    const bool grow_dev = n > H->sc_cap, grow_host = need > H->h_sc_bytes;
+    const int cap = n + n / 2 + 16;
+    hbuf::Group dev, host;                  // the larger buffers replace the old ones only when all of them exist
+    double *blk = nullptr, *key = nullptr; int *sel = nullptr; char *hsc = nullptr;
+    int rc = 0;
+    if (grow_dev) { rc |= dev.dev(&blk, scene_block_bytes((size_t)cap, E) / sizeof(double) + 1); rc |= dev.dev(&sel, (size_t)cap); rc |= dev.dev(&key, (size_t)cap); }
+    if (grow_host) rc |= host.pin(&hsc, need * 2);
+    if (rc) return RDA_ERR_HIP;
+    if (grow_dev) { H->scene = std::move(dev); H->d_sc_blk = blk; H->d_sc_sel = sel; H->d_sc_key = key; H->sc_cap = cap; H->sc_n = 0; }
+    if (grow_host) { H->scene_host = std::move(host); H->h_sc = hsc; H->h_sc_bytes = need * 2; }
     return RDA_OK;
 }
 
@@ -1938,7 +1914,7 @@ extern "C" int rda_get_obstacles(rda_handle *H, double *A, double *b, int32_t *c
 
 static hipEvent_t next_event(rda_handle *H, int which)
 {
-    if (H->ev_used[which] == H->ev[which].size()) { hipEvent_t e; (void)hipEventCreate(&e); H->ev[which].push_back(e); }
+    if (H->ev_used[which] == H->ev[which].size()) { hbuf::Event e; (void)hipEventCreate(e.out()); H->ev[which].push_back(std::move(e)); }
     return H->ev[which][H->ev_used[which]++];
 }
 
@@ -2236,9 +2212,13 @@ extern "C" int rda_upload_path(rda_handle *H, int L, const double *path)
 {
     if (!H || L < 1 || !path) return RDA_ERR_ARG;
     HIPCHK(hipStreamSynchronize(H->stream));
-    if (L > H->path_len || !H->d_path) { dev_free(H->d_path); H->d_path = nullptr; if (dalloc(&H->d_path, (size_t)3 * L)) return RDA_ERR_HIP; }
+    hbuf::Group g;                                      // a longer path goes to a new buffer that replaces the old one once it holds the path
+    double *dst = H->d_path;
+    const bool grow = L > H->path_len || !H->d_path;
+    if (grow && g.dev(&dst, (size_t)3 * L)) return RDA_ERR_HIP;
+    HIPCHK(hipMemcpy(dst, path, (size_t)3 * L * sizeof(double), hipMemcpyHostToDevice));
+    if (grow) { H->path = std::move(g); H->d_path = dst; }
     H->path_len = L;
-    HIPCHK(hipMemcpy(H->d_path, path, (size_t)3 * L * sizeof(double), hipMemcpyHostToDevice));
     return RDA_OK;
 }
 
@@ -2367,16 +2347,18 @@ extern "C" int rda_upload_trace(rda_handle *H, int K, const double *nom_s, const
 {
     if (!H || K < 1 || !nom_s || !nom_u || !ref_s || !ref_speed) return RDA_ERR_ARG;
     const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
-    dev_free(H->d_tr_s); dev_free(H->d_tr_u); dev_free(H->d_tr_ref); dev_free(H->d_tr_speed);
-    dev_free(H->d_tr_out_u); dev_free(H->d_tr_out_s); dev_free(H->d_tr_info);
+    hbuf::Group g;                                      // the new trace replaces the old one once it is complete: a failed upload keeps the old
+    double *s, *u, *ref, *speed, *out_u, *out_s; rda_info *info;
     int rc = 0;
-    rc |= dalloc(&H->d_tr_s, K * ns); rc |= dalloc(&H->d_tr_u, K * nu); rc |= dalloc(&H->d_tr_ref, K * ns); rc |= dalloc(&H->d_tr_speed, (size_t)K);
-    rc |= dalloc(&H->d_tr_out_u, K * nu); rc |= dalloc(&H->d_tr_out_s, K * ns); rc |= dalloc(&H->d_tr_info, (size_t)K);
+    rc |= g.dev(&s, K * ns); rc |= g.dev(&u, K * nu); rc |= g.dev(&ref, K * ns); rc |= g.dev(&speed, (size_t)K);
+    rc |= g.dev(&out_u, K * nu); rc |= g.dev(&out_s, K * ns); rc |= g.dev(&info, (size_t)K);
     if (rc) return RDA_ERR_HIP;
-    HIPCHK(hipMemcpy(H->d_tr_s, nom_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(H->d_tr_u, nom_u, K * nu * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(H->d_tr_ref, ref_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(H->d_tr_speed, ref_speed, K * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s, nom_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(u, nom_u, K * nu * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ref, ref_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(speed, ref_speed, K * sizeof(double), hipMemcpyHostToDevice));
+    H->trace = std::move(g);
+    H->d_tr_s = s; H->d_tr_u = u; H->d_tr_ref = ref; H->d_tr_speed = speed; H->d_tr_out_u = out_u; H->d_tr_out_s = out_s; H->d_tr_info = info;
     H->K = K;
     return RDA_OK;
 }
@@ -2401,19 +2383,22 @@ extern "C" int rda_enqueue_range(rda_handle *H, int k0, int k1)
 extern "C" int rda_debug_lmz_clk(rda_handle *H, unsigned long long *out, int max_waves)     // out[max_waves][16]; reads and clears
 {
     static unsigned long long *buf = nullptr; static int cap = 0;
+    static hbuf::Group &keep = *new hbuf::Group;      // the armed buffers live as long as the process (the device globals point into them)
     HIPCHK(hipStreamSynchronize(H->stream));
     if (!buf) {
-        cap = max_waves;
-        HIPCHK(hipMalloc((void **)&buf, (size_t)cap * 16 * sizeof(unsigned long long)));
-        HIPCHK(hipMemset(buf, 0, (size_t)cap * 16 * sizeof(unsigned long long)));
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lmz_clk), &buf, sizeof(buf)));
+        hbuf::Group g; unsigned long long *b;
+        if (g.dev(&b, (size_t)max_waves * 16)) return RDA_ERR_HIP;
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lmz_clk), &b, sizeof(b)));
+        keep.d.push_back(std::move(g.d[0])); buf = b; cap = max_waves;
         return RDA_OK;
     }
     if (max_waves < 0) {          // the fail log instead: out = int[1 + 3 * 200000]; first call arms it
         static int *flog = nullptr;
         if (!flog) {
-            HIPCHK(hipMalloc((void **)&flog, (1 + 3 * 200000) * sizeof(int))); HIPCHK(hipMemset(flog, 0, (1 + 3 * 200000) * sizeof(int)));
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lmz_faillog), &flog, sizeof(flog)));
+            hbuf::Group g; int *f;
+            if (g.dev(&f, 1 + 3 * 200000)) return RDA_ERR_HIP;
+            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lmz_faillog), &f, sizeof(f)));
+            keep.d.push_back(std::move(g.d[0])); flog = f;
             return RDA_OK;
         }
         HIPCHK(hipMemcpy(out, flog, (1 + 3 * 200000) * sizeof(int), hipMemcpyDeviceToHost));
@@ -2497,6 +2482,9 @@ extern "C" int rda_get_state(rda_handle *H, double *lam, double *mu, double *z, 
 {
     if (!H) return RDA_ERR_ARG;
     Dev &d = H->d; const size_t T = d.c.T, N = d.c.N, E = d.c.E, R = d.c.R;
+    hbuf::Group g;                                      // the product temporaries, allocated before anything is written
+    double *ta = nullptr, *tb = nullptr;
+    if ((a_lam || b_lam) && (g.dev(&ta, N * (T + 1) * 2) || g.dev(&tb, N * (T + 1)))) return RDA_ERR_HIP;
     HIPCHK(hipStreamSynchronize(H->stream));
     std::vector<double> tmp;
     auto get = [&](const double *dev, double *host, size_t TT, size_t W) -> int {
@@ -2512,13 +2500,10 @@ extern "C" int rda_get_state(rda_handle *H, double *lam, double *mu, double *z, 
     if (zeta && get(d.zeta, zeta, T, 1)) return RDA_ERR_HIP;
     if (dis) HIPCHK(hipMemcpy(dis, d.dis, T * sizeof(double), hipMemcpyDeviceToHost));
     if (a_lam || b_lam) {
-        double *ta = nullptr, *tb = nullptr;
-        if (dalloc(&ta, N * (T + 1) * 2) || dalloc(&tb, N * (T + 1))) return RDA_ERR_HIP;
         hipLaunchKernelGGL(k_products_get, dim3(64), dim3(256), 0, H->stream, d, ta, tb);
         HIPCHK(hipStreamSynchronize(H->stream));
         if (a_lam) HIPCHK(hipMemcpy(a_lam, ta, N * (T + 1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
         if (b_lam) HIPCHK(hipMemcpy(b_lam, tb, N * (T + 1) * sizeof(double), hipMemcpyDeviceToHost));
-        dev_free(ta); dev_free(tb);
     }
     return RDA_OK;
 }
@@ -2530,6 +2515,9 @@ extern "C" int rda_set_state(rda_handle *H, const double *lam, const double *mu,
     if (!H) return RDA_ERR_ARG;
     if (shard_frozen(H)) return RDA_ERR_UNSUPPORTED;
     Dev &d = H->d; const size_t T = d.c.T, N = d.c.N, E = d.c.E, R = d.c.R;
+    hbuf::Group g;                                      // the product temporaries, allocated before anything is written
+    double *ta = nullptr, *tb = nullptr;
+    if ((a_lam && g.dev(&ta, N * (T + 1) * 2)) || (b_lam && g.dev(&tb, N * (T + 1)))) return RDA_ERR_HIP;
     HIPCHK(hipStreamSynchronize(H->stream));
     std::vector<double> tmp;
     auto put = [&](const double *host, double *dev, size_t TT, size_t W) -> int {
@@ -2544,13 +2532,11 @@ extern "C" int rda_set_state(rda_handle *H, const double *lam, const double *mu,
     if (xi && put(xi, d.xi, T + 1, 2)) return RDA_ERR_HIP;
     if (zeta && put(zeta, d.zeta, T, 1)) return RDA_ERR_HIP;
     if (dis) HIPCHK(hipMemcpy(d.dis, dis, T * sizeof(double), hipMemcpyHostToDevice));
-    double *ta = nullptr, *tb = nullptr;
-    if (a_lam) { if (dalloc(&ta, N * (T + 1) * 2)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(ta, a_lam, N * (T + 1) * 2 * sizeof(double), hipMemcpyHostToDevice)); }
-    if (b_lam) { if (dalloc(&tb, N * (T + 1))) return RDA_ERR_HIP; HIPCHK(hipMemcpy(tb, b_lam, N * (T + 1) * sizeof(double), hipMemcpyHostToDevice)); }
+    if (a_lam) HIPCHK(hipMemcpy(ta, a_lam, N * (T + 1) * 2 * sizeof(double), hipMemcpyHostToDevice));
+    if (b_lam) HIPCHK(hipMemcpy(tb, b_lam, N * (T + 1) * sizeof(double), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_products_set, dim3(64), dim3(256), 0, H->stream, d, ta, tb);
     int rc = terms_rebuild(H);                          // block sums / near masks of the rewritten terms
-    HIPCHK(hipStreamSynchronize(H->stream));
-    dev_free(ta); dev_free(tb);
+    HIPCHK(hipStreamSynchronize(H->stream));            // (before the temporaries go)
     return rc;
 }
 
@@ -2573,15 +2559,17 @@ extern "C" int rda_shard_config(rda_handle *H, int rank, int world)
     if (world > 1 && H->follow) return RDA_ERR_UNSUPPORTED;                          // duals_follow moves rows between slots = between ranks
     HIPCHK(hipStreamSynchronize(H->stream));
     Dev &d = H->d;
-    dev_free(d.coef); d.coef = nullptr; dev_free(d.coefL); d.coefL = nullptr;
+    const int Nloc = (d.c.N + world - 1) / world, first = rank * Nloc;
+    const size_t chunk = chunk_doubles(d.c.T, Nloc), lchunk = lchunk_doubles(d.c.T, Nloc);
+    hbuf::Group g;                                      // the new term arrays (zeroed) replace the old ones, and the geometry changes, only once both exist
+    double *coef, *coefL;
+    if (g.dev(&coef, chunk * world) || g.dev(&coefL, lchunk * world)) return RDA_ERR_HIP;
+    H->terms = std::move(g); d.coef = coef; d.coefL = coefL;
     // su_pre = 0 (the su set-up evaluates every term itself) reads g = G'mu + xi of every slot, which lives in the LOCAL chunk and is
     // never gathered: with more than one rank the reduced form (block sums / near masks, part of the gathered chunk) is the only one
     if (world > 1) d.su_pre = 1;
-    d.P = world; d.rank = rank; d.Nloc = (d.c.N + world - 1) / world; d.J = (d.Nloc + GS - 1) / GS; d.chunk = chunk_doubles(d.c.T, d.Nloc);
-    d.lchunk = lchunk_doubles(d.c.T, d.Nloc);
-    const int first = rank * d.Nloc;
-    d.Nlive = first >= d.c.N ? 0 : (d.c.N - first < d.Nloc ? d.c.N - first : d.Nloc);
-    if (dalloc(&d.coef, d.chunk * world) || dalloc(&d.coefL, d.lchunk * world)) return RDA_ERR_HIP;      // (dalloc zeroes)
+    d.P = world; d.rank = rank; d.Nloc = Nloc; d.J = (Nloc + GS - 1) / GS; d.chunk = chunk; d.lchunk = lchunk;
+    d.Nlive = first >= d.c.N ? 0 : (d.c.N - first < Nloc ? d.c.N - first : Nloc);
     if (d.Nloc * world != d.c.N) hipLaunchKernelGGL(k_dead_slots, dim3(64), dim3(256), 0, H->stream, d);
     int rc = terms_rebuild(H);                          // (the duals of a handle that is re-sharded are NOT re-condensed: shard before the first step)
     if (rc != RDA_OK) return rc;
@@ -2646,9 +2634,12 @@ extern "C" int rda_shard_comm_init(rda_handle *H, const void *uid128)
     H->p_allgather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t))rccl_sym(H, "ncclAllGather");
     H->p_comm_destroy = (int (*)(void *))rccl_sym(H, "ncclCommDestroy");
     if (!f || !H->p_allgather) return RDA_ERR_UNSUPPORTED;
+    hbuf::Group g;                                      // the verdict word (zero) exists before the communicator does
+    unsigned long long *verdict = H->h_verdict;
+    if (!verdict && g.pin(&verdict, 1)) return RDA_ERR_HIP;
     int rc = f(&H->comm, H->d.P, uid, H->d.rank);
     if (rc != 0) { fprintf(stderr, "librda_hip: ncclCommInitRank failed (%d)\n", rc); H->comm = nullptr; return RDA_ERR_HIP; }
-    if (!H->h_verdict) { HIPCHK(hipHostMalloc((void **)&H->h_verdict, sizeof(unsigned long long))); *H->h_verdict = 0; }
+    if (!H->h_verdict) { H->verdict = std::move(g); H->h_verdict = verdict; }
     return RDA_OK;
 }
 
@@ -2755,16 +2746,14 @@ __global__ __launch_bounds__(su::NT) void k_finish_fleet(const Dev *devs, const 
     finish_body(d, f);
 }
 
-struct rda_fleet {
+struct rda_fleet {                        // (owns its buffers, event and stream like rda_handle)
     int B;
     std::vector<rda_handle *> egos;
-    hipStream_t stream;
     Dev *h_devs, *d_devs;                 // pinned mirror / device array
     EgoIO *h_io, *d_io_step, *d_io_trace;
     double *h_in, *d_in;                  // step path, per ego: nom_s | nom_u | ref | speed
     double *h_out, *d_out;                // per ego: u | s
     rda_info *h_info, *d_info;
-    hipEvent_t ev;
     int T, iter_num, J, rows, lmz_split;
     size_t su_lds;
     // tracked stepping (device-side pre_process), allocated on first use
@@ -2772,18 +2761,15 @@ struct rda_fleet {
     double **h_paths, **d_paths; int *h_lens, *d_lens; EgoIO *h_io_track, *d_io_track;
     // rda_fleet_scene_resort (allocated on first use): the members' scene arguments, their robots' positions; rob_pending: a copy out of h_rob may be queued
     scene::Args *h_sc, *d_sc; double *h_rob, *d_rob; int rob_pending;
+    hbuf::Group mem, trk, resort;         // the tables above; those of tracked stepping; those of rda_fleet_scene_resort
+    hbuf::Event ev;
+    hbuf::Stream stream;                  // (last: destroyed first)
 };
 
 extern "C" void rda_fleet_destroy(rda_fleet *F)
 {
     if (!F) return;
     (void)hipStreamSynchronize(F->stream);
-    void *dp[] = { F->d_devs, F->d_io_step, F->d_io_trace, F->d_in, F->d_out, F->d_info, F->d_trk_in, F->d_trk_out, F->d_paths, F->d_lens, F->d_io_track, F->d_sc, F->d_rob };
-    for (void *q : dp) dev_free(q);
-    void *hp[] = { F->h_devs, F->h_io, F->h_in, F->h_out, F->h_info, F->h_trk_in, F->h_trk_out, F->h_paths, F->h_lens, F->h_io_track, F->h_sc, F->h_rob };
-    for (void *q : hp) if (q) (void)hipHostFree(q);
-    (void)hipEventDestroy(F->ev);
-    (void)hipStreamDestroy(F->stream);
     delete F;
 }
 
@@ -2798,25 +2784,20 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
         if (egos[i]->comm || egos[i]->d.P != 1) return RDA_ERR_UNSUPPORTED;        // egos are replicas, obstacle shards are not
         if (egos[i]->d.lmz_mode) return RDA_ERR_UNSUPPORTED;                       // the fused fleet launches run the enumeration kernels
     }
-    rda_fleet *F = new rda_fleet();
+    std::unique_ptr<rda_fleet> owner(new rda_fleet());     // a failure on the way drops the fleet and with it what was built
+    rda_fleet *F = owner.get();
     F->B = B; F->egos.assign(egos, egos + B);
-    F->d_devs = nullptr; F->d_io_step = F->d_io_trace = nullptr; F->d_in = F->d_out = nullptr; F->d_info = nullptr;
-    F->h_devs = nullptr; F->h_io = nullptr; F->h_in = F->h_out = nullptr; F->h_info = nullptr;
     const rda_cfg &c = egos[0]->d.c;
     F->T = c.T; F->iter_num = c.iter_num; F->J = (c.N + GS - 1) / GS; F->su_lds = egos[0]->su_lds;
-    HIPCHK(hipStreamCreate(&F->stream));
-    HIPCHK(hipEventCreateWithFlags(&F->ev, hipEventDisableTiming));
+    HIPCHK(hipStreamCreate(F->stream.out()));
+    HIPCHK(hipEventCreateWithFlags(F->ev.out(), hipEventDisableTiming));
     const size_t T = c.T, ns = 3 * (T + 1), nu = 2 * T, nin = 2 * ns + nu + 1, nout = nu + ns;
+    hbuf::Group &m = F->mem;
     int rc = 0;
-    rc |= dalloc(&F->d_devs, (size_t)B); rc |= dalloc(&F->d_io_step, (size_t)B); rc |= dalloc(&F->d_io_trace, (size_t)B);
-    rc |= dalloc(&F->d_in, B * nin); rc |= dalloc(&F->d_out, B * nout); rc |= dalloc(&F->d_info, (size_t)B);
-    if (rc) { rda_fleet_destroy(F); return RDA_ERR_HIP; }
-    HIPCHK(hipHostMalloc((void **)&F->h_devs, B * sizeof(Dev)));
-    HIPCHK(hipHostMalloc((void **)&F->h_io, B * sizeof(EgoIO)));
-    HIPCHK(hipHostMalloc((void **)&F->h_in, B * nin * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&F->h_out, B * nout * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&F->h_info, B * sizeof(rda_info)));
-    memset(F->h_devs, 0, B * sizeof(Dev));
+    rc |= m.dev(&F->d_devs, (size_t)B); rc |= m.dev(&F->d_io_step, (size_t)B); rc |= m.dev(&F->d_io_trace, (size_t)B);
+    rc |= m.dev(&F->d_in, B * nin); rc |= m.dev(&F->d_out, B * nout); rc |= m.dev(&F->d_info, (size_t)B);
+    rc |= m.pin(&F->h_devs, (size_t)B); rc |= m.pin(&F->h_io, (size_t)B); rc |= m.pin(&F->h_in, B * nin); rc |= m.pin(&F->h_out, B * nout); rc |= m.pin(&F->h_info, (size_t)B);
+    if (rc) return RDA_ERR_HIP;
     for (int i = 0; i < B; ++i) {
         EgoIO &e = F->h_io[i];
         e.s = F->d_in + i * nin; e.u = e.s + ns; e.ref = e.u + nu; e.speed = e.ref + ns;
@@ -2825,7 +2806,7 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
     HIPCHK(hipMemcpy(F->d_io_step, F->h_io, B * sizeof(EgoIO), hipMemcpyHostToDevice));
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su_fleet<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds)));
     HIPCHK(hipFuncSetAttribute((const void *)k_finish_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds));
-    *out = F;
+    *out = owner.release();
     return RDA_OK;
 }
 
@@ -2956,13 +2937,12 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
         if (H->sc_n <= 0 || H->d.obstacle_num == 0 || H->pending) return RDA_ERR_ARG;
         if (H->follow) return RDA_ERR_UNSUPPORTED;
     }
-    if (!F->d_sc) {
+    if (!F->d_sc) {                                     // first use: the tables (zeroed) take their place once all of them exist
+        hbuf::Group g; scene::Args *hsc, *dsc; double *hrob, *drob;
         int rc = 0;
-        rc |= dalloc(&F->d_sc, B); rc |= dalloc(&F->d_rob, 2 * B);
+        rc |= g.dev(&dsc, B); rc |= g.dev(&drob, 2 * B); rc |= g.pin(&hsc, B); rc |= g.pin(&hrob, 2 * B);
         if (rc) return RDA_ERR_HIP;
-        HIPCHK(hipHostMalloc((void **)&F->h_sc, B * sizeof(scene::Args)));
-        HIPCHK(hipHostMalloc((void **)&F->h_rob, 2 * B * sizeof(double)));
-        memset((void *)F->h_sc, 0, B * sizeof(scene::Args));
+        F->resort = std::move(g); F->d_sc = dsc; F->d_rob = drob; F->h_sc = hsc; F->h_rob = hrob;
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
@@ -2996,17 +2976,15 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
 {
     if (!F || !states || !ref_speed || !cur_index || !out_u || !out_s || ind_range < 1) return RDA_ERR_ARG;
     const size_t T = F->T, ns = 3 * (T + 1), nu = 2 * T, nin = 2 * ns + nu + 1, nout = nu + ns, B = F->B;
-    if (!F->d_trk_in) {
+    if (!F->d_trk_in) {                                 // first use: the tables (zeroed) take their place once all of them exist
+        hbuf::Group g; track::In *hti, *dti; track::Out *hto, *dto; double **hp, **dp; int *hl, *dl; EgoIO *hio, *dio;
         int rc = 0;
-        rc |= dalloc(&F->d_trk_in, B); rc |= dalloc(&F->d_trk_out, B); rc |= dalloc(&F->d_paths, B); rc |= dalloc(&F->d_lens, B);
-        rc |= dalloc(&F->d_io_track, B);
+        rc |= g.dev(&dti, B); rc |= g.dev(&dto, B); rc |= g.dev(&dp, B); rc |= g.dev(&dl, B); rc |= g.dev(&dio, B);
+        rc |= g.pin(&hti, B); rc |= g.pin(&hto, B); rc |= g.pin(&hp, B); rc |= g.pin(&hl, B); rc |= g.pin(&hio, B);
         if (rc) return RDA_ERR_HIP;
-        HIPCHK(hipHostMalloc((void **)&F->h_trk_in, B * sizeof(track::In)));
-        HIPCHK(hipHostMalloc((void **)&F->h_trk_out, B * sizeof(track::Out)));
-        HIPCHK(hipHostMalloc((void **)&F->h_paths, B * sizeof(double *)));
-        HIPCHK(hipHostMalloc((void **)&F->h_lens, B * sizeof(int)));
-        HIPCHK(hipHostMalloc((void **)&F->h_io_track, B * sizeof(EgoIO)));
-        memset(F->h_paths, 0, B * sizeof(double *)); memset(F->h_lens, 0, B * sizeof(int)); memset(F->h_io_track, 0, B * sizeof(EgoIO));
+        F->trk = std::move(g);
+        F->d_trk_in = dti; F->d_trk_out = dto; F->d_paths = dp; F->d_lens = dl; F->d_io_track = dio;
+        F->h_trk_in = hti; F->h_trk_out = hto; F->h_paths = hp; F->h_lens = hl; F->h_io_track = hio;
     }
     // the result of the tick is written where the host reads it (round 6): k_finish_fleet and k_track_fleet store straight into the pinned blocks (write-only,
     // fire-and-forget stores over the link, complete at the end of their kernels) instead of three device-to-host copies queued behind the last launch
@@ -3102,18 +3080,20 @@ extern "C" int rda_lammuz_batch(int B, int E, int R, const double *A, const doub
     if (B < 1 || E < 1 || E > RDA_EMAX || R < 1 || R > RDA_RMAX || E + R + 1 > 64) return RDA_ERR_UNSUPPORTED;
     if (rda_device_count() < 1) return RDA_ERR_NODEVICE;
     double *dA, *db, *dp, *dphi, *dG, *dh, *dxi, *dzeta, *ddbar, *dlam, *dmu, *dz, *dcmh; int *dcone;
-    struct Cp { void **dst; const void *src; size_t bytes; };
+    struct Cp { double **dst; const double *src; size_t n; };
     const size_t sB = (size_t)B;
-    Cp ins[] = { {(void **)&dA, A, sB * E * 2 * 8}, {(void **)&db, b, sB * E * 8}, {(void **)&dcone, cone, sB * 4}, {(void **)&dp, p, sB * 2 * 8},
-                 {(void **)&dphi, phi, sB * 8}, {(void **)&dG, G, (size_t)R * 2 * 8}, {(void **)&dh, h, (size_t)R * 8}, {(void **)&dxi, xi, sB * 2 * 8},
-                 {(void **)&dzeta, zeta, sB * 8}, {(void **)&ddbar, dbar, sB * 8} };
-    for (auto &c : ins) { HIPCHK(hipMalloc(c.dst, c.bytes)); HIPCHK(hipMemcpy(*c.dst, c.src, c.bytes, hipMemcpyHostToDevice)); }
-    HIPCHK(hipMalloc((void **)&dlam, sB * E * 8)); HIPCHK(hipMalloc((void **)&dmu, sB * R * 8)); HIPCHK(hipMalloc((void **)&dz, sB * 8)); HIPCHK(hipMalloc((void **)&dcmh, sB * 4 * 8));
+    Cp ins[] = { {&dA, A, sB * E * 2}, {&db, b, sB * E}, {&dp, p, sB * 2}, {&dphi, phi, sB}, {&dG, G, (size_t)R * 2}, {&dh, h, (size_t)R},
+                 {&dxi, xi, sB * 2}, {&dzeta, zeta, sB}, {&ddbar, dbar, sB} };
+    hbuf::Group g;                                      // every buffer of the call, released on every way out
+    for (auto &c : ins) { if (g.dev(c.dst, c.n)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(*c.dst, c.src, c.n * 8, hipMemcpyHostToDevice)); }
+    if (g.dev(&dcone, sB)) return RDA_ERR_HIP;
+    HIPCHK(hipMemcpy(dcone, cone, sB * 4, hipMemcpyHostToDevice));
+    if (g.dev(&dlam, sB * E) || g.dev(&dmu, sB * R) || g.dev(&dz, sB) || g.dev(&dcmh, sB * 4)) return RDA_ERR_HIP;
     rda_opts od; rda_opts_init(&od);                   // tie-break T1 of the defaults
     RobotCands rcands; rcands.nmv = robot_candidates(R, G, h, rcands.muc, rcands.rv, &rcands.nrv); rcands.centre = od.tie_centre ? 1 : 0;
     long long *dprof = nullptr;
 #ifdef RDA_LMZ_PROF     // debug build only: phase cycles of sub-problem 0 on stderr
-    HIPCHK(hipMalloc((void **)&dprof, 8 * sizeof(long long))); HIPCHK(hipMemset(dprof, 0, 8 * sizeof(long long)));
+    if (g.dev(&dprof, 8)) return RDA_ERR_HIP;
 #endif
     hipLaunchKernelGGL(k_lammuz_batch, dim3((B + 3) / 4), dim3(256), 0, 0, B, E, R, dA, db, dcone, dp, dphi, dG, dh, dxi, dzeta, ddbar,
                        ro2, delta, accelerated, dlam, dmu, dz, dcmh, dprof, rcands);
@@ -3123,13 +3103,10 @@ extern "C" int rda_lammuz_batch(int B, int E, int R, const double *A, const doub
         long long hp[8]; HIPCHK(hipMemcpy(hp, dprof, sizeof(hp), hipMemcpyDeviceToHost));
         fprintf(stderr, "lammuz prof (ticks, sub-problem 0): setup=%lld p1.it0=%lld p1.it1=%lld p2.it0=%lld p2.it1=%lld argmin1=%lld argmin2=%lld total=%lld\n",
                 hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
-        dev_free(dprof);
     }
     HIPCHK(hipMemcpy(lam, dlam, sB * E * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(mu, dmu, sB * R * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(z, dz, sB * 8, hipMemcpyDeviceToHost));
     if (cmh) HIPCHK(hipMemcpy(cmh, dcmh, sB * 4 * 8, hipMemcpyDeviceToHost));
-    for (auto &c : ins) dev_free(*c.dst);
-    dev_free(dlam); dev_free(dmu); dev_free(dz); dev_free(dcmh);
     return RDA_OK;
 }
 
@@ -3148,15 +3125,15 @@ extern "C" int rda_su_solve_opts(const rda_cfg *cfg, const rda_opts *opts, const
         soa[4 * T * N + k] = g[(n * T + t) * 2]; soa[5 * T * N + k] = g[(n * T + t) * 2 + 1];
     }
     double *dsoa, *dns, *dnu, *dref, *dspeed, *dd0, *dos, *dou, *dod; int *dst;
-    HIPCHK(hipMalloc((void **)&dsoa, soa.size() * 8)); HIPCHK(hipMemcpy(dsoa, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dns, ns * 8)); HIPCHK(hipMemcpy(dns, nom_s, ns * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dnu, nu * 8)); HIPCHK(hipMemcpy(dnu, nom_u, nu * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dref, ns * 8)); HIPCHK(hipMemcpy(dref, ref_s, ns * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dspeed, 8)); HIPCHK(hipMemcpy(dspeed, &ref_speed, 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dd0, T * 8));
+    hbuf::Group gb;                                     // every buffer of the call, released on every way out
+    if (gb.dev(&dsoa, soa.size())) return RDA_ERR_HIP; HIPCHK(hipMemcpy(dsoa, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
+    if (gb.dev(&dns, ns)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(dns, nom_s, ns * 8, hipMemcpyHostToDevice));
+    if (gb.dev(&dnu, nu)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(dnu, nom_u, nu * 8, hipMemcpyHostToDevice));
+    if (gb.dev(&dref, ns)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(dref, ref_s, ns * 8, hipMemcpyHostToDevice));
+    if (gb.dev(&dspeed, 1)) return RDA_ERR_HIP; HIPCHK(hipMemcpy(dspeed, &ref_speed, 8, hipMemcpyHostToDevice));
+    if (gb.dev(&dd0, T)) return RDA_ERR_HIP;
     if (d0) HIPCHK(hipMemcpy(dd0, d0, T * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&dos, ns * 8)); HIPCHK(hipMalloc((void **)&dou, nu * 8)); HIPCHK(hipMalloc((void **)&dod, T * 8));
-    HIPCHK(hipMalloc((void **)&dst, 2 * sizeof(int)));
+    if (gb.dev(&dos, ns) || gb.dev(&dou, nu) || gb.dev(&dod, T) || gb.dev(&dst, 2)) return RDA_ERR_HIP;
     su::Args ar;
     ar.c.T = cfg->T; ar.c.N = cfg->N; ar.c.dynamics = cfg->dynamics; ar.c.accelerated = cfg->accelerated;
     ar.c.dt = cfg->dt; ar.c.L = cfg->L; ar.c.umax0 = cfg->max_speed[0]; ar.c.umax1 = cfg->max_speed[1];
@@ -3173,10 +3150,10 @@ extern "C" int rda_su_solve_opts(const rda_cfg *cfg, const rda_opts *opts, const
     ar.P = 1; ar.Nloc = (int)N; ar.chunk = 0;
     ar.d_in = d0 ? dd0 : nullptr; ar.out_s = dos; ar.out_u = dou; ar.out_d = dod; ar.status = dst; ar.ipm_iters = dst + 1;
     long long *dprof = nullptr;
-    if (od.su_prof) { HIPCHK(hipMalloc((void **)&dprof, su::PROF_WORDS * sizeof(long long))); HIPCHK(hipMemset(dprof, 0, su::PROF_WORDS * sizeof(long long))); }
+    if (od.su_prof && gb.dev(&dprof, su::PROF_WORDS)) return RDA_ERR_HIP;
     ar.prof = dprof;
     double *ddbg = nullptr;
-    if (od.su_prof > 1) { HIPCHK(hipMalloc((void **)&ddbg, 400 * sizeof(double))); HIPCHK(hipMemset(ddbg, 0, 400 * sizeof(double))); }
+    if (od.su_prof > 1 && gb.dev(&ddbg, 400)) return RDA_ERR_HIP;
     ar.dbg = ddbg;
     const size_t lds = su::lds_bytes((int)T);
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su_hook<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
@@ -3189,17 +3166,13 @@ extern "C" int rda_su_solve_opts(const rda_cfg *cfg, const rda_opts *opts, const
         double hd[400]; HIPCHK(hipMemcpy(hd, ddbg, sizeof(hd), hipMemcpyDeviceToHost));
         for (int i = 0; i < 100 && (i == 0 || hd[4 * i + 3] != 0); ++i)
             fprintf(stderr, "it %d rdn %.3e rpn %.3e mu %.3e sc %.3e\n", i, hd[4 * i], hd[4 * i + 1], hd[4 * i + 2], hd[4 * i + 3]);
-        dev_free(ddbg);
     }
     if (dprof) {
         long long hp[16]; HIPCHK(hipMemcpy(hp, dprof, sizeof(hp), hipMemcpyDeviceToHost));
         fprintf(stderr, "su prof (cycles) iters=%d:", st[1]); for (int i = 0; i < 16; ++i) fprintf(stderr, " [%d]=%lld", i, hp[i]); fprintf(stderr, "\n");
-        dev_free(dprof);
     }
     HIPCHK(hipMemcpy(s, dos, ns * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(u, dou, nu * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(dd, dod, T * 8, hipMemcpyDeviceToHost));
     if (ipm_iters) *ipm_iters = st[1];
-    void *fr[] = { dsoa, dns, dnu, dref, dspeed, dd0, dos, dou, dod, dst };
-    for (void *p : fr) dev_free(p);
     return st[0] == 0 ? 0 : 1;
 }
 extern "C" int rda_su_solve(const rda_cfg *cfg, const double *nom_s, const double *nom_u, const double *ref_s,
