@@ -227,7 +227,7 @@ template <int BYTES> __device__ __forceinline__ void warm_kernargs()
 // `mirror` (pinned host memory): the same block written straight into the caller-visible host buffer and published with a
 // sequence number (system-scope release) - the host polls that word instead of queueing a device-to-host copy and waiting for
 // the stream (fetch_result).
-struct Fin { double *out_u, *out_s; rda_info *info; double *mirror; unsigned long long seq; int slot;   // slot: out_u is the handle's contiguous result slot
+struct Fin { double *out_u = nullptr, *out_s = nullptr; rda_info *info = nullptr; double *mirror = nullptr; unsigned long long seq = 0; int slot = 0;   // slot: out_u is the handle's contiguous result slot (Fin{}: no result hand-over)
              // obstacle shards: the su launch that takes the early-stop verdict itself publishes it (2 vseq + stop) in pinned host memory
              // BEFORE it starts its solve - the host polls that word and queues the next LamMuZ launch + all-gather (or stops queueing)
              // while the su-problem is still being solved: no stream synchronisation inside a step
@@ -992,11 +992,11 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
 // waves per SIMD with a few spilled registers (more sub-problems in flight: what a full chip wants)
 __global__ __launch_bounds__(64 * GS / 4) void k_lammuz_rows(Dev d, int it, Fin fin) { warm_kernargs<sizeof(Dev) + sizeof(int) + sizeof(Fin)>(); lammuz_body_rows<0, true>(d, blockIdx.x, gridDim.x, it, fin); }
 __global__ __launch_bounds__(64 * GS / 4, 2) void k_lammuz_rows_dense(Dev d, int it, Fin fin) { lammuz_body_rows<0>(d, blockIdx.x, gridDim.x, it, fin); }
-__global__ __launch_bounds__(64 * GS / 4, 3) void k_lammuz_rows_fast(Dev d, int it) { lammuz_body_rows<1>(d, blockIdx.x, gridDim.x, it, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0}); }
+__global__ __launch_bounds__(64 * GS / 4, 3) void k_lammuz_rows_fast(Dev d, int it) { lammuz_body_rows<1>(d, blockIdx.x, gridDim.x, it, Fin{}); }
 // (measured: the common path with four waves per SIMD and 31 spilled registers is 9 % slower.  Round 4, same-box A/B (tools/experiments/ab_so.sh): the common
 // path at TWO waves per SIMD - no scratch spills - is 9 % slower at N = 2000 and 20 % slower for the 64-ego C5 fleet than at three waves with its 53 spilled
 // registers, so it stays at three; the work list at ONE wave per SIMD (no spills; round 2-3: two waves, 91 spilled registers) is +1 % / +-0 %: kept)
-__global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_enum(Dev d, int it) { lammuz_body_rows<2>(d, blockIdx.x, gridDim.x, it, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0}); }
+__global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_enum(Dev d, int it) { lammuz_body_rows<2>(d, blockIdx.x, gridDim.x, it, Fin{}); }
 
 // Block partials from the STORED terms - the same row_term, the same row order as mode 0 of the packed kernel forms them in flight - and
 // the tail of the step.  Runs behind every LamMuZ form that leaves its rows to more than one workgroup or launch (split launch, one
@@ -1309,7 +1309,7 @@ __global__ void k_reset(Dev d)
 __global__ __launch_bounds__(256) void k_lmz_finalize_all(Dev d)
 {
     Dev q = d; q.rank = blockIdx.y; q.Nlive = d.c.N - q.rank * d.Nloc; if (q.Nlive > d.Nloc) q.Nlive = d.Nloc; if (q.Nlive < 0) q.Nlive = 0;
-    finalize_body(q, blockIdx.x, gridDim.x, -1, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0});
+    finalize_body(q, blockIdx.x, gridDim.x, -1, Fin{});
 }
 
 // ---- rda_opts::duals_follow: the dual state moves with its obstacle when the device pipeline re-binds the slots ----------------------
@@ -1369,9 +1369,9 @@ struct rda_handle {
     size_t su_lds;
     // staging
     double *h_stage_A, *h_stage_b; int *h_stage_cone;    // pinned, N slots
-    double *h_step;                                       // pinned: nom_s | nom_u | ref | speed
+    double *h_step;                                       // pinned: the step block (step_doubles)
     double *d_step;                                       // device copy of the above (slot 0 of the step path)
-    double *d_out_u, *d_out_s; rda_info *d_info;          // result slot of the step path
+    double *d_out_u, *d_out_s; rda_info *d_info;          // result block of the step path (res_doubles) and pointers into it
     double *h_out; rda_info *h_info;                      // pinned
     unsigned long long res_seq; int zero_copy;           // result mirror written by k_finish (see there); RDA_ZERO_COPY=0: D2H copy + stream sync
     unsigned long long *h_verdict = nullptr; unsigned long long vseq = 0;   // pinned early-stop verdict word of the su launches (sharded handles with a communicator)
@@ -1425,7 +1425,28 @@ extern "C" const char *rda_strerror(int code)
 extern "C" int rda_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 extern "C" int rda_set_device(int dev) { HIPCHK(hipSetDevice(dev)); return RDA_OK; }
 
-static size_t res_doubles(size_t T) { return 2 * T + 3 * (T + 1) + 8; }     // u | s | info (4) | track::Out (2) | non-convex count | sequence word
+// The two blocks every tick passes through: offsets and sizes in doubles, functions of the horizon T.  Host code takes them from here.
+// Three device places spell the same layouts out and keep their own text (the code of the su kernels follows how their source is
+// cut into functions): publish_result (result block), k_track and k_su_tracked (step block).  Whoever changes a block visits those three.
+constexpr size_t traj_s(size_t T) { return 3 * (T + 1); }      // a state trajectory [3][T+1]
+constexpr size_t traj_u(size_t T) { return 2 * T; }            // a control trajectory [2][T]
+// Step block  nom_s [3(T+1)] | nom_u [2T] | ref [3(T+1)] | speed [1]:  h_step / d_step, and one per member in the fleet's h_in / d_in
+constexpr size_t step_u(size_t T) { return traj_s(T); }
+constexpr size_t step_ref(size_t T) { return step_u(T) + traj_u(T); }
+constexpr size_t step_speed(size_t T) { return step_ref(T) + traj_s(T); }     // (= the block without its speed: what a tracked tick reads back)
+constexpr size_t step_doubles(size_t T) { return step_speed(T) + 1; }
+// Result block  u [2T] | s [3(T+1)] | rda_info | track::Out | non-convex count (long long) | sequence word:  d_out_u / h_out, identical on the
+// device and in pinned memory.  The zero-copy form publishes the sequence word behind the mirrored block; the D2H form copies the block without it.
+constexpr size_t res_s(size_t T) { return traj_u(T); }
+constexpr size_t res_info(size_t T) { return res_s(T) + traj_s(T); }          // (= u | s alone: a member's block of the fleet's h_out / d_out)
+constexpr size_t res_track(size_t T) { return res_info(T) + sizeof(rda_info) / sizeof(double); }
+constexpr size_t res_nonconvex(size_t T) { return res_track(T) + sizeof(track::Out) / sizeof(double); }
+constexpr size_t res_seq(size_t T) { return res_nonconvex(T) + 1; }
+constexpr size_t res_copied_doubles(size_t T) { return res_seq(T); }
+constexpr size_t res_doubles(size_t T) { return res_seq(T) + 1; }
+static_assert(sizeof(rda_info) % sizeof(double) == 0 && sizeof(track::Out) % sizeof(double) == 0, "info and track output are whole doubles of the result block");
+static_assert(res_doubles(1) == 2 * 1 + 3 * (1 + 1) + 8 && res_doubles(RDA_TMAX) == 2 * RDA_TMAX + 3 * (RDA_TMAX + 1) + 8, "the result block keeps its size (publish_result)");
+static_assert(step_doubles(1) == 2 * 3 * (1 + 1) + 2 * 1 + 1 && step_doubles(RDA_TMAX) == 2 * 3 * (RDA_TMAX + 1) + 2 * RDA_TMAX + 1, "the step block keeps its size (k_track, k_su_tracked)");
 static_assert(9 * su::NT >= track::LDS_DOUBLES, "TrackedRefWait runs track::run in the su solve's `part` scratch");
 
 // Solver options: library defaults, then the RDA_* environment overrides (experiments and A/B runs; read HERE only)
@@ -1446,7 +1467,24 @@ extern "C" void rda_opts_init(rda_opts *o)
     { const double ez[5] = {1e-12, 1e-12, 1e-12, 0.999999, 1e-7}; for (int i = 0; i < 5; ++i) o->su_easy[i] = ez[i]; }
     // (No environment overrides here since round 5: a library call has no process-global configuration.  The RDA_* switches of the A/B tools and
     // tests are applied by the Python host package - rda_planner_amd.rda_solver.hip_options - to the struct it hands to rda_create_opts.)
-    if (o->su_cold_probe < 1) o->su_cold_probe = 1;
+}
+// The options as the solver uses them (null: the defaults): entries outside their range clamped or replaced by the values of rda_opts_init.
+// su_tol falls back per entry, su_land_tol and su_tol_early (to 0 = off) all three together; su_hard_warm[0] <= 0 switches that rule off.
+static rda_opts opts_sanitised(const rda_opts *opts)
+{
+    rda_opts def; rda_opts_init(&def);
+    if (!opts) return def;
+    rda_opts o = *opts;
+    if (!(o.lmz_mu > 0)) o.lmz_mu = def.lmz_mu;
+    for (int i = 0; i < 3; ++i) if (!(o.su_tol[i] > 0)) o.su_tol[i] = def.su_tol[i];
+    if (!(o.su_tol_early[0] > 0 && o.su_tol_early[1] > 0 && o.su_tol_early[2] > 0)) for (int i = 0; i < 3; ++i) o.su_tol_early[i] = def.su_tol_early[i];
+    if (!(o.su_land_tol[0] > 0 && o.su_land_tol[1] > 0 && o.su_land_tol[2] > 0)) for (int i = 0; i < 3; ++i) o.su_land_tol[i] = def.su_land_tol[i];
+    if (!(o.su_land_rho > 0)) o.su_land_rho = def.su_land_rho;
+    if (!(o.su_hard_warm[0] > 0)) o.su_hard_warm[1] = 0.0;
+    if (o.su_cold_probe < 1) o.su_cold_probe = 1;
+    o.su_land_first = o.su_land_first < 0 ? 0 : (o.su_land_first > 2 ? 2 : o.su_land_first);
+    o.su_land = o.su_land ? 1 : 0;
+    return o;
 }
 
 // mu support candidates of a polygon robot: pairs whose intersection is a vertex of the robot, then the non-null rows, then
@@ -1476,8 +1514,6 @@ static int terms_rebuild(rda_handle *H);
 
 extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const double *G, const double *h, rda_handle **out)
 {
-    rda_opts def;
-    if (!opts) { rda_opts_init(&def); opts = &def; }
     if (!cfg || !G || !h || !out) return RDA_ERR_ARG;
     if (cfg->robot_norm2 && cfg->R < 2) return RDA_ERR_UNSUPPORTED;
     if (cfg->E < 1 || cfg->E > RDA_EMAX || cfg->R < 1 || cfg->R > RDA_RMAX || cfg->T < 1 || cfg->T > RDA_TMAX || cfg->N < 1) return RDA_ERR_UNSUPPORTED;
@@ -1488,28 +1524,25 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     rda_handle *H = owner.get();
     memset(&H->d, 0, sizeof(Dev));
     H->d.c = *cfg; H->d.nt = 1; H->d.obstacle_num = 0; H->K = 0; H->timing = 0;
-    H->opts = *opts;
-    const rda_opts &o = H->opts;
+    const rda_opts o = opts_sanitised(opts);
+    H->opts = opts ? *opts : o;
     H->d.warm = o.lmz_warm; H->dense_from = o.lmz_dense_from;
     H->d.rows = (cfg->E + cfg->R + 1 <= 16) && o.lmz_rows != 0;
     H->d.nmv = robot_candidates(cfg->R, G, h, H->d.muc, H->d.rv, &H->d.nrv);
     H->d.centre = o.tie_centre ? 1 : 0;
-    H->d.lmz_mode = (o.lmz_mode || cfg->robot_norm2) ? 1 : 0; H->d.lmz_mu = o.lmz_mu > 0 ? o.lmz_mu : 1e-6;      // the enumeration has no norm2-robot candidates
+    H->d.lmz_mode = (o.lmz_mode || cfg->robot_norm2) ? 1 : 0; H->d.lmz_mu = o.lmz_mu;      // the enumeration has no norm2-robot candidates
     H->d.su_warm_wfl = o.su_warm[0]; H->d.su_warm_mu0 = o.su_warm[1]; H->d.su_warm_cap = o.su_warm_cap; H->d.su_warm_first = o.su_warm_first;
-    H->d.su_hard_wfl = o.su_hard_warm[0]; H->d.su_hard_mu0 = o.su_hard_warm[0] > 0 ? o.su_hard_warm[1] : 0.0;
+    H->d.su_hard_wfl = o.su_hard_warm[0]; H->d.su_hard_mu0 = o.su_hard_warm[1];
     H->d.su_warm_tau = o.su_warm_endgame[0]; H->d.su_warm_sig = o.su_warm_endgame[1]; H->d.su_warm_clip = o.su_warm_clip;
     for (int i = 0; i < 5; ++i) H->d.su_easy[i] = o.su_easy[i];
     H->d.su_easy_max = o.su_easy_max; H->d.su_easy_nopred = o.su_easy_nopred;
     H->d.su_pre = o.su_pre;
-    H->d.su_cold_from = o.su_cold_from; H->d.su_cold_probe = o.su_cold_probe < 1 ? 1 : o.su_cold_probe;
+    H->d.su_cold_from = o.su_cold_from; H->d.su_cold_probe = o.su_cold_probe;
     H->d.su_light = o.su_light; H->d.su_split = o.su_split; H->d.su_accept = o.su_accept; H->d.su_first_attempt = o.su_first_attempt;
-    H->d.su_land_first = o.su_land_first < 0 ? 0 : (o.su_land_first > 2 ? 2 : o.su_land_first);
-    H->d.su_land_blind_from = o.su_land_blind_from;
-    H->d.su_land = o.su_land ? 1 : 0; H->d.su_land_rho = o.su_land_rho > 0 ? o.su_land_rho : 1e4;
-    { const bool ok = o.su_land_tol[0] > 0 && o.su_land_tol[1] > 0 && o.su_land_tol[2] > 0; const double dflt[3] = {1e-3, 1e-4, 1e-5}; for (int i = 0; i < 3; ++i) H->d.su_land_tol[i] = ok ? o.su_land_tol[i] : dflt[i]; }
+    H->d.su_land_first = o.su_land_first; H->d.su_land_blind_from = o.su_land_blind_from;
+    H->d.su_land = o.su_land; H->d.su_land_rho = o.su_land_rho;
+    for (int i = 0; i < 3; ++i) { H->d.su_tol[i] = o.su_tol[i]; H->d.su_tol_early[i] = o.su_tol_early[i]; H->d.su_land_tol[i] = o.su_land_tol[i]; }
     H->follow = o.duals_follow != 0; H->prev_used = -1;
-    for (int i = 0; i < 3; ++i) H->d.su_tol[i] = o.su_tol[i] > 0 ? o.su_tol[i] : (i == 0 ? 1e-9 : (i == 1 ? 1e-10 : 1e-11));
-    { const bool on = o.su_tol_early[0] > 0 && o.su_tol_early[1] > 0 && o.su_tol_early[2] > 0; for (int i = 0; i < 3; ++i) H->d.su_tol_early[i] = on ? o.su_tol_early[i] : 0.0; }
     H->nccl_lib = nullptr; H->comm = nullptr; H->p_allgather = nullptr; H->p_comm_destroy = nullptr; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = 0;
     const size_t T = cfg->T, N = cfg->N, E = cfg->E, R = cfg->R;
     HIPCHK(hipStreamCreate(H->stream.out()));
@@ -1528,7 +1561,7 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     rc |= m.dev(&d.xi, N * (T + 1) * 2); rc |= m.dev(&d.zeta, N * T); rc |= m.dev(&d.dis, T);
     d.P = 1; d.rank = 0; d.Nloc = (int)N; d.Nlive = (int)N; d.J = (int)((N + GS - 1) / GS); d.chunk = chunk_doubles((int)T, (int)N); d.lchunk = lchunk_doubles((int)T, (int)N);
     rc |= H->terms.dev(&d.coef, d.chunk); rc |= H->terms.dev(&d.coefL, d.lchunk);
-    rc |= m.dev(&d.s, 3 * (T + 1)); rc |= m.dev(&d.u, 2 * T); rc |= m.dev(&d.pose, 4 * T);
+    rc |= m.dev(&d.s, traj_s(T)); rc |= m.dev(&d.u, traj_u(T)); rc |= m.dev(&d.pose, 4 * T);
     rc |= m.dev(&d.ctrl, 1);
     rc |= m.dev(&d.su_lam_keep, 10 * T);
     if (H->follow) {
@@ -1542,17 +1575,14 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
 #else
     if (o.su_prof) return RDA_ERR_UNSUPPORTED;     // phase counters: profiling builds only (-DSU_PROF / -DSU_FINE, tools/su_phase_profile.py)
 #endif
-    const size_t step_n = 3 * (T + 1) + 2 * T + 3 * (T + 1) + 1;
-    rc |= m.dev(&H->d_step, step_n);
-    // result block, identical on the device and in pinned memory: u [2T] | s [3(T+1)] | rda_info (4 doubles) | track::Out (4 doubles):
-    // ONE copy back per step
+    rc |= m.dev(&H->d_step, step_doubles(T));
     rc |= m.dev(&H->d_out_u, res_doubles(T));
     rc |= m.pin(&H->h_stage_A, N * (T + 1) * E * 2); rc |= m.pin(&H->h_stage_b, N * (T + 1) * E); rc |= m.pin(&H->h_stage_cone, N);
-    rc |= m.pin(&H->h_step, step_n); rc |= m.pin(&H->h_out, res_doubles(T));
+    rc |= m.pin(&H->h_step, step_doubles(T)); rc |= m.pin(&H->h_out, res_doubles(T));
     H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated);
     if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
     if (rc) return RDA_ERR_HIP;
-    H->d_out_s = H->d_out_u + 2 * T; H->d_info = (rda_info *)(H->d_out_s + 3 * (T + 1)); H->d_trk = (track::Out *)(H->d_out_s + 3 * (T + 1) + 4);
+    H->d_out_s = H->d_out_u + res_s(T); H->d_info = (rda_info *)(H->d_out_u + res_info(T)); H->d_trk = (track::Out *)(H->d_out_u + res_track(T));
     { const int hard = 99; HIPCHK(hipMemcpy(&d.ctrl->su_last, &hard, sizeof(int), hipMemcpyHostToDevice)); }     // no su history yet
     HIPCHK(hipMemcpy(d.G, G, 2 * R * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.h, h, R * sizeof(double), hipMemcpyHostToDevice));
@@ -1561,7 +1591,7 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     std::vector<int> cn(N, 1);                                              // para_cone init, rda_solver.py:158
     HIPCHK(hipMemcpy(d.cone, cn.data(), N * sizeof(int), hipMemcpyHostToDevice));
     H->res_seq = 0; H->zero_copy = o.zero_copy;
-    H->h_info = (rda_info *)(H->h_out + 2 * T + 3 * (T + 1)); H->h_trk = (track::Out *)(H->h_out + 2 * T + 3 * (T + 1) + 4);
+    H->h_info = (rda_info *)(H->h_out + res_info(T)); H->h_trk = (track::Out *)(H->h_out + res_track(T));
     H->su_lds = su::lds_bytes((int)T);
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_lds)));
     HIPCHK(hipFuncSetAttribute((const void *)k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_lds));
@@ -1888,8 +1918,7 @@ static int scene_stage(rda_handle *H, int n, const int32_t *kind, const int32_t 
 extern "C" int rda_last_nonconvex(rda_handle *H)
 {
     if (!H) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T;
-    return (int)*(const long long *)(H->h_out + 2 * T + 3 * (T + 1) + 6);
+    return (int)*(const long long *)(H->h_out + res_nonconvex(H->d.c.T));
 }
 
 extern "C" int rda_upload_scene(rda_handle *H, int n, const int32_t *kind, const int32_t *nvert, const double *geom,
@@ -1921,69 +1950,63 @@ static hipEvent_t next_event(rda_handle *H, int which)
 // K1 launch of ADMM iteration `it`.  Packed rows when the shape allows: a small grid is ONE launch that also forms the block
 // partials; a dense grid is the common-path kernel + the work-list kernel, with k_lmz_finalize (partials) behind them.  One sub-problem per wave (big
 // shapes, the no-obstacle case of quirk Q9) and the per-thread interior-point kernel likewise end with k_lmz_finalize.
-static void launch_finalize(rda_handle *H, const Dev &d, int it, const Fin &fin)
+constexpr int LMZ_NTH = 64 * GS / 4;             // threads of a packed workgroup (2 waves)
+// The LamMuZ launch form of a handle's shape and staged obstacles, with its grids: decided here only.  launch_lammuz executes the plan,
+// rda_lammuz_kernel names it (bench.py labels its per-launch times with the name).
+enum LmzForm { LMZ_CP_SMALL, LMZ_CP_LARGE, LMZ_IP, LMZ_ROWS_SPLIT, LMZ_ROWS_DENSE, LMZ_ROWS, LMZ_WAVE };
+struct LmzPlan { LmzForm form; int nb, ne; };        // workgroups of the form's first launch; of the work-list launch (split form)
+static LmzPlan lammuz_plan(const rda_handle *H, const Dev &d)
 {
-    hipLaunchKernelGGL(k_lmz_finalize, dim3((d.c.T * d.J + FPB - 1) / FPB), dim3(256), 0, H->stream, d, it, fin);
+    const int units = d.c.T * GS * d.J;          // rows of the grid (a stage is padded to whole GS-slot blocks)
+    if (d.lmz_mode && !(H->ip_rows && d.obstacle_num)) {
+        const int nth = d.Nlive * d.c.T;
+        return { (d.c.E <= 4 && d.c.R <= 4) ? LMZ_CP_SMALL : LMZ_CP_LARGE, d.obstacle_num ? (nth + 63) / 64 : (d.c.T + 63) / 64, 0 };
+    }
+    if (d.lmz_mode) return { LMZ_IP, packed_grid(d.c.T, d.J), 0 };
+    if (d.rows && d.obstacle_num) {
+        const int nb = packed_grid(d.c.T, d.J), cus = (units / GS * LMZ_NTH + 255) / 256;      // launch indices (XCD-aware order, a few fillers); CUs the grid asks for at one wave per SIMD
+        // Grid size (in compute units at one wave per SIMD) from which the dense forms are used.  Scenes with per-stage obstacle data
+        // (moving obstacles) lose the remembered support of more rows per launch, so the work list of the split form is longer and the
+        // single launch stays ahead up to a larger grid: measured cross-over ~280 CUs for static scenes (N = 300, T = 20: 35.7 vs 38.7 us),
+        // ~560 for moving ones (T = 30: N = 200 40.9 vs 47.1 us for the single launch, N = 300 52.2 vs 50.1, N = 400 60.7 vs 51.1).
+        if (cus <= (d.nt > 1 ? H->dense_from * 7 / 4 : H->dense_from)) return { LMZ_ROWS, nb, 0 };
+        if (!H->lmz_split) return { LMZ_ROWS_DENSE, nb, 0 };
+        int ne = units / 32; if (ne < 64) ne = 64; if (ne > 2048) ne = 2048;
+        return { LMZ_ROWS_SPLIT, nb, ne };
+    }
+    return { LMZ_WAVE, d.obstacle_num ? (units + 3) / 4 : 1, 0 };
 }
-// (the row-parallel interior-point kernel: see k_lammuz_ip below)
-static void launch_lammuz_ip(rda_handle *H, const Dev &d, int it, const Fin &fin)
-{
-    hipLaunchKernelGGL(k_lammuz_ip, dim3(packed_grid(d.c.T, d.J)), dim3(64 * GS / 4), 0, H->stream, d, it, fin);
-}
-// the LamMuZ launch form launch_lammuz picks for the handle's shape and staged obstacles (bench.py labels its per-launch times with it)
 extern "C" const char *rda_lammuz_kernel(rda_handle *H)
 {
-    if (!H) return "";
-    const Dev &d = H->d;
-    if (d.lmz_mode && !(H->ip_rows && d.obstacle_num)) return (d.c.E <= 4 && d.c.R <= 4) ? "k_lammuz_cp_small+k_lmz_finalize" : "k_lammuz_cp_large+k_lmz_finalize";
-    if (d.lmz_mode) return "k_lammuz_ip";
-    if (d.rows && d.obstacle_num) {
-        const int cus = (d.c.T * d.J * (64 * GS / 4) + 255) / 256, dense_from = d.nt > 1 ? H->dense_from * 7 / 4 : H->dense_from;
-        if (cus > dense_from && H->lmz_split) return "k_lammuz_rows_fast+k_lammuz_enum+k_lmz_finalize";
-        return cus > dense_from ? "k_lammuz_rows_dense" : "k_lammuz_rows";
-    }
-    return "k_lammuz+k_lmz_finalize";
+    static const char *const names[] = { "k_lammuz_cp_small+k_lmz_finalize", "k_lammuz_cp_large+k_lmz_finalize", "k_lammuz_ip",
+                                         "k_lammuz_rows_fast+k_lammuz_enum+k_lmz_finalize", "k_lammuz_rows_dense", "k_lammuz_rows", "k_lammuz+k_lmz_finalize" };
+    return H ? names[lammuz_plan(H, H->d).form] : "";
 }
-// Grid size (in compute units at one wave per SIMD) from which the split form of the LamMuZ launch is used.  Scenes with per-stage
-// obstacle data (moving obstacles) lose the remembered support of more rows per launch, so the work list of the split form is longer and
-// the single launch stays ahead up to a larger grid: measured cross-over ~280 CUs for static scenes (N = 300, T = 20: 35.7 vs 38.7 us),
-// ~560 for moving ones (T = 30: N = 200 40.9 vs 47.1 us for the single launch, N = 300 52.2 vs 50.1, N = 400 60.7 vs 51.1).
-static inline int dense_threshold(const rda_handle *H, const Dev &d) { return d.nt > 1 ? H->dense_from * 7 / 4 : H->dense_from; }
 static void launch_lammuz(rda_handle *H, const Dev &d, int it, const Fin &fin)
 {
     if (d.Nlive == 0) return;                    // a shard without obstacles (N < P)
-    const int units = d.c.T * GS * d.J;          // rows of the grid (a stage is padded to whole GS-slot blocks)
-    if (d.lmz_mode && !(H->ip_rows && d.obstacle_num)) {
-        const int nth = d.Nlive * d.c.T, nb = d.obstacle_num ? (nth + 63) / 64 : (d.c.T + 63) / 64;
-        if (d.c.E <= 4 && d.c.R <= 4) hipLaunchKernelGGL(k_lammuz_cp_small, dim3(nb), dim3(64), 0, H->stream, d);
-        else hipLaunchKernelGGL(k_lammuz_cp_large, dim3(nb), dim3(64), 0, H->stream, d);
-        launch_finalize(H, d, it, fin);
-        return;
-    }
-    if (d.lmz_mode) { launch_lammuz_ip(H, d, it, fin); return; }
-    if (d.rows && d.obstacle_num) {
-        constexpr int NTH = 64 * GS / 4;             // threads of a packed workgroup (2 waves)
-        const int nb = packed_grid(d.c.T, d.J), cus = (units / GS * NTH + 255) / 256;      // launch indices (XCD-aware order, a few fillers); CUs the grid asks for at one wave per SIMD
-        const int dense_from = dense_threshold(H, d);
-        if (cus > dense_from && H->lmz_split) {
+    const LmzPlan p = lammuz_plan(H, d);
+    switch (p.form) {
+        case LMZ_CP_SMALL: hipLaunchKernelGGL(k_lammuz_cp_small, dim3(p.nb), dim3(64), 0, H->stream, d); break;
+        case LMZ_CP_LARGE: hipLaunchKernelGGL(k_lammuz_cp_large, dim3(p.nb), dim3(64), 0, H->stream, d); break;
+        case LMZ_IP: hipLaunchKernelGGL(k_lammuz_ip, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;      // (the row-parallel interior-point kernel)
+        case LMZ_ROWS: hipLaunchKernelGGL(k_lammuz_rows, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;
+        case LMZ_ROWS_DENSE: hipLaunchKernelGGL(k_lammuz_rows_dense, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;
+        case LMZ_ROWS_SPLIT:
             // dense grid: common path with three waves per SIMD, then the deferred rows one per wave (see lammuz_body_rows)
-            hipLaunchKernelGGL(k_lammuz_rows_fast, dim3(nb), dim3(NTH), 0, H->stream, d, it);
-            int ne = units / 32; if (ne < 64) ne = 64; if (ne > 2048) ne = 2048;
-            hipLaunchKernelGGL(k_lammuz_enum, dim3(ne), dim3(NTH), 0, H->stream, d, it);
-            launch_finalize(H, d, it, fin);
-        } else if (cus > dense_from) hipLaunchKernelGGL(k_lammuz_rows_dense, dim3(nb), dim3(NTH), 0, H->stream, d, it, fin);
-        else hipLaunchKernelGGL(k_lammuz_rows, dim3(nb), dim3(NTH), 0, H->stream, d, it, fin);
-    } else {
-        hipLaunchKernelGGL(k_lammuz, dim3(d.obstacle_num ? (units + 3) / 4 : 1), dim3(256), 0, H->stream, d, it);
-        launch_finalize(H, d, it, fin);
+            hipLaunchKernelGGL(k_lammuz_rows_fast, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it);
+            hipLaunchKernelGGL(k_lammuz_enum, dim3(p.ne), dim3(LMZ_NTH), 0, H->stream, d, it);
+            break;
+        case LMZ_WAVE: hipLaunchKernelGGL(k_lammuz, dim3(p.nb), dim3(256), 0, H->stream, d, it); break;
     }
+    hipLaunchKernelGGL(k_lmz_finalize, dim3((d.c.T * d.J + FPB - 1) / FPB), dim3(256), 0, H->stream, d, it, fin);      // block partials and the tail of the forms that do not make them
 }
 
 // queue the whole ADMM loop of one MPC step (rda_solver.py:588-596) - no host synchronisation
 // The ADMM loop of one MPC step in two parts.  The HEAD (the first su-problem, which also resets the step's control block) reads the nominal trajectory and the
 // condensed terms of the PREVIOUS step (quirk Q4) but nothing of the staged obstacles, so a caller may stage this tick's
 // obstacles on the stream between head and tail while the first su-problem is being solved (rda_tracked_begin/_finish).
-static void launch_su(rda_handle *H, const Dev &d, int it, const double *in_s, const double *in_u, const Fin &fin = Fin{nullptr, nullptr, nullptr, nullptr, 0, 0})
+static void launch_su(rda_handle *H, const Dev &d, int it, const double *in_s, const double *in_u, const Fin &fin = Fin{})
 {
     const int T = d.c.T;
     if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
@@ -2015,17 +2038,22 @@ static inline void cpu_relax()
     asm volatile("yield" ::: "memory");
 #endif
 }
+// spins on a pinned word that a kernel publishes until (word >> shift) == want (acquire), for at most `ms` milliseconds
+static bool poll_word(volatile unsigned long long *w, int shift, unsigned long long want, int ms)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spin = 0;; ++spin) {
+        if ((*w >> shift) == want) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return true; }
+        cpu_relax();
+        if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(ms)) return false;
+    }
+}
 static int fetch_result(rda_handle *H)
 {
     const size_t T = H->d.c.T;
     if (H->zero_copy && !H->timing) {
-        volatile unsigned long long *flag = (volatile unsigned long long *)(H->h_out + 2 * T + 3 * (T + 1) + 7);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spin = 0;; ++spin) {
-            if (*flag == H->res_seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return RDA_OK; }
-            cpu_relax();
-            if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-        }
+        volatile unsigned long long *flag = (volatile unsigned long long *)(H->h_out + res_seq(T));
+        if (poll_word(flag, 0, H->res_seq, 20)) return RDA_OK;
         // 20 ms without the word (a healthy step takes a fraction of a millisecond): synchronise the ordinary way.  A device fault -
         // in this step, or in the launches that were still queued behind the hand-over of the PREVIOUS step (the zero-copy hand-over
         // returns before they have drained) - never publishes the word and surfaces here as the stream's error.
@@ -2034,8 +2062,26 @@ static int fetch_result(rda_handle *H)
         return RDA_ERR_HIP;
     }
     // D2H form: the result block without the sequence word behind it (that word belongs to the zero-copy protocol)
-    HIPCHK(hipMemcpyAsync(H->h_out, H->d_out_u, (res_doubles(T) - 1) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
+    HIPCHK(hipMemcpyAsync(H->h_out, H->d_out_u, res_copied_doubles(T) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
     HIPCHK(hipStreamSynchronize(H->stream));
+    return RDA_OK;
+}
+// a finished step out of a pinned result block (blk: u | s) and its info; null = not wanted
+static void result_out(const double *blk, const rda_info *blk_info, size_t T, double *out_u, double *out_s, rda_info *info)
+{
+    if (out_u) memcpy(out_u, blk, traj_u(T) * sizeof(double));
+    if (out_s) memcpy(out_s, blk + res_s(T), traj_s(T) * sizeof(double));
+    if (info) *info = *blk_info;
+}
+// fills the pinned step block and queues its copy to the device
+static int step_block_upload(rda_handle *H, const double *nom_s, const double *nom_u, const double *ref_s, double ref_speed)
+{
+    const size_t T = H->d.c.T;
+    memcpy(H->h_step, nom_s, traj_s(T) * sizeof(double));
+    memcpy(H->h_step + step_u(T), nom_u, traj_u(T) * sizeof(double));
+    memcpy(H->h_step + step_ref(T), ref_s, traj_s(T) * sizeof(double));
+    H->h_step[step_speed(T)] = ref_speed;
+    HIPCHK(hipMemcpyAsync(H->d_step, H->h_step, step_doubles(T) * sizeof(double), hipMemcpyHostToDevice, H->stream));
     return RDA_OK;
 }
 static int enqueue_admm_head(rda_handle *H, const double *in_s, const double *in_u, const double *ref, const double *speed)
@@ -2055,7 +2101,7 @@ static int enqueue_admm_tail(rda_handle *H, const double *in_s, const double *in
     const Fin fin = make_fin(H, out_u, out_s, info);  // the su launch that detects the early stop hands the result over itself
     for (int it = 0; it < d.c.iter_num; ++it) {
         if (it > 0) {
-            Fin f = H->early_finish ? fin : Fin{nullptr, nullptr, nullptr, nullptr, 0, 0};
+            Fin f = H->early_finish ? fin : Fin{};
             if (H->comm) { f.verdict = H->h_verdict; f.vseq = ++H->vseq; }
             launch_su(H, d, it, in_s, in_u, f);
         }
@@ -2066,19 +2112,12 @@ static int enqueue_admm_tail(rda_handle *H, const double *in_s, const double *in
             // su-problems are bitwise identical); the host polls that word - no copy, no stream synchronisation - and goes on queueing
             // (or stops) while the su-problem is being solved.
             volatile unsigned long long *vw = H->h_verdict;
-            const auto t0 = std::chrono::steady_clock::now();
-            bool seen = false;
-            for (unsigned spin = 0; !seen; ++spin) {
-                if ((*vw >> 1) == H->vseq) { seen = true; break; }
-                cpu_relax();
-                if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
-            }
-            if (!seen) { HIPCHK(hipStreamSynchronize(H->stream)); if ((*vw >> 1) != H->vseq) return RDA_ERR_HIP; }
+            if (!poll_word(vw, 1, H->vseq, 50)) { HIPCHK(hipStreamSynchronize(H->stream)); if ((*vw >> 1) != H->vseq) return RDA_ERR_HIP; }
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             if (*vw & 1ull) break;
         }
         if (H->timing) (void)hipEventRecord(next_event(H, 0), H->stream);
-        launch_lammuz(H, d, it, H->early_finish ? fin : Fin{nullptr, nullptr, nullptr, nullptr, 0, 0});
+        launch_lammuz(H, d, it, H->early_finish ? fin : Fin{});
         if (H->timing) (void)hipEventRecord(next_event(H, 0), H->stream);
         if (H->comm) {      // one exchange per ADMM iteration: every rank's chunk to every rank (in place)
             if (H->timing) (void)hipEventRecord(next_event(H, 2), H->stream);
@@ -2108,19 +2147,13 @@ static int step_common(rda_handle *H, const double *nom_s, const double *nom_u, 
     int rc = stage();
     if (rc != RDA_OK) { (void)hipStreamSynchronize(H->stream); return rc; }
     const size_t T = H->d.c.T;
-    const size_t ns = 3 * (T + 1), nu = 2 * T;
-    memcpy(H->h_step, nom_s, ns * sizeof(double));
-    memcpy(H->h_step + ns, nom_u, nu * sizeof(double));
-    memcpy(H->h_step + ns + nu, ref_s, ns * sizeof(double));
-    H->h_step[ns + nu + ns] = ref_speed;
-    HIPCHK(hipMemcpyAsync(H->d_step, H->h_step, (2 * ns + nu + 1) * sizeof(double), hipMemcpyHostToDevice, H->stream));
-    rc = enqueue_admm(H, H->d_step, H->d_step + ns, H->d_step + ns + nu, H->d_step + ns + nu + ns, H->d_out_u, H->d_out_s, H->d_info);
+    rc = step_block_upload(H, nom_s, nom_u, ref_s, ref_speed);
+    if (rc != RDA_OK) return rc;
+    rc = enqueue_admm(H, H->d_step, H->d_step + step_u(T), H->d_step + step_ref(T), H->d_step + step_speed(T), H->d_out_u, H->d_out_s, H->d_info);
     if (rc != RDA_OK) return rc;
     rc = fetch_result(H);
     if (rc != RDA_OK) return rc;
-    memcpy(out_u, H->h_out, nu * sizeof(double));
-    memcpy(out_s, H->h_out + nu, ns * sizeof(double));
-    if (info) *info = *H->h_info;
+    result_out(H->h_out, H->h_info, T, out_u, out_s, info);
     return RDA_OK;
 }
 
@@ -2227,12 +2260,12 @@ extern "C" int rda_tracked_begin(rda_handle *H, const double *state, double ref_
 {
     if (!H || !state || H->pending) return RDA_ERR_ARG;
     if (!H->d_path || cur_index < 0 || cur_index >= H->path_len || ind_range < 1) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t T = H->d.c.T;
     const double *in_u = H->d.u;                       // the controls of the last solve are still resident
     if (nom_u) {
-        memcpy(H->h_step + ns, nom_u, nu * sizeof(double));
-        HIPCHK(hipMemcpyAsync(H->d_step + ns, H->h_step + ns, nu * sizeof(double), hipMemcpyHostToDevice, H->stream));
-        in_u = H->d_step + ns;
+        memcpy(H->h_step + step_u(T), nom_u, traj_u(T) * sizeof(double));
+        HIPCHK(hipMemcpyAsync(H->d_step + step_u(T), H->h_step + step_u(T), traj_u(T) * sizeof(double), hipMemcpyHostToDevice, H->stream));
+        in_u = H->d_step + step_u(T);
     }
     track::In in; in.sx = state[0]; in.sy = state[1]; in.sth = state[2]; in.speed = ref_speed; in.threshold = threshold;
     in.cur_index = cur_index; in.ind_range = ind_range;
@@ -2244,7 +2277,7 @@ extern "C" int rda_tracked_begin(rda_handle *H, const double *state, double ref_
     H->tick_stages = 0;
     if (H->fuse_track) {
         Dev d = H->d;
-        d.ref = H->d_step + ns + nu; d.ref_speed = H->d_step + 2 * ns + nu;
+        d.ref = H->d_step + step_ref(T); d.ref_speed = H->d_step + step_speed(T);
         if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
         H->trk_seq += 1;
         RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su_tracked<TT>, dim3(2), dim3(su::NT), H->su_trk_lds, H->stream, d, in, H->d_path, H->path_len,
@@ -2253,7 +2286,7 @@ extern "C" int rda_tracked_begin(rda_handle *H, const double *state, double ref_
         HIPCHK(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_track, dim3(1), dim3(64), 0, H->stream, H->d, in, H->d_path, H->path_len, in_u, H->d_step, H->d_trk);
-        int rc = enqueue_admm_head(H, H->d_step, in_u, H->d_step + ns + nu, H->d_step + 2 * ns + nu);
+        int rc = enqueue_admm_head(H, H->d_step, in_u, H->d_step + step_ref(T), H->d_step + step_speed(T));
         if (rc != RDA_OK) return rc;
     }
     H->pending = 1; H->pending_in_u = in_u;
@@ -2311,23 +2344,21 @@ extern "C" int rda_tracked_finish(rda_handle *H, double *out_u, double *out_s, r
                                   double *nom_s_out, double *ref_out, int32_t *min_index, double *end_heading)
 {
     if (!H || !H->pending) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t T = H->d.c.T;
     const double *in_u = H->pending_in_u;
     if (H->scene_on_s2) HIPCHK(hipStreamWaitEvent(H->stream, H->ev_scene, 0));
     H->pending = 0; H->pending_scene = 0; H->scene_on_s2 = 0;
-    int rc = enqueue_admm_tail(H, H->d_step, in_u, H->d_step + ns + nu, H->d_step + 2 * ns + nu, H->d_out_u, H->d_out_s, H->d_info);
+    int rc = enqueue_admm_tail(H, H->d_step, in_u, H->d_step + step_ref(T), H->d_step + step_speed(T), H->d_out_u, H->d_out_s, H->d_info);
     if (rc != RDA_OK) { (void)hipStreamSynchronize(H->stream); return rc; }
     if (nom_s_out || ref_out) {
-        HIPCHK(hipMemcpyAsync(H->h_step, H->d_step, (2 * ns + nu) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
+        HIPCHK(hipMemcpyAsync(H->h_step, H->d_step, step_speed(T) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
         HIPCHK(hipStreamSynchronize(H->stream));
     }
     rc = fetch_result(H);
     if (rc != RDA_OK) return rc;
-    if (out_u) memcpy(out_u, H->h_out, nu * sizeof(double));
-    if (out_s) memcpy(out_s, H->h_out + nu, ns * sizeof(double));
-    if (info) *info = *H->h_info;
-    if (nom_s_out) memcpy(nom_s_out, H->h_step, ns * sizeof(double));
-    if (ref_out) memcpy(ref_out, H->h_step + ns + nu, ns * sizeof(double));
+    result_out(H->h_out, H->h_info, T, out_u, out_s, info);
+    if (nom_s_out) memcpy(nom_s_out, H->h_step, traj_s(T) * sizeof(double));
+    if (ref_out) memcpy(ref_out, H->h_step + step_ref(T), traj_s(T) * sizeof(double));
     if (min_index) *min_index = H->h_trk->min_index;
     if (end_heading) *end_heading = H->h_trk->end_heading;
     return RDA_OK;
@@ -2346,7 +2377,7 @@ extern "C" int rda_step_tracked(rda_handle *H, const double *state, double ref_s
 extern "C" int rda_upload_trace(rda_handle *H, int K, const double *nom_s, const double *nom_u, const double *ref_s, const double *ref_speed)
 {
     if (!H || K < 1 || !nom_s || !nom_u || !ref_s || !ref_speed) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
     hbuf::Group g;                                      // the new trace replaces the old one once it is complete: a failed upload keeps the old
     double *s, *u, *ref, *speed, *out_u, *out_s; rda_info *info;
     int rc = 0;
@@ -2366,7 +2397,7 @@ extern "C" int rda_upload_trace(rda_handle *H, int K, const double *nom_s, const
 extern "C" int rda_enqueue_step(rda_handle *H, int k)
 {
     if (!H || k < 0 || k >= H->K) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
     return enqueue_admm(H, H->d_tr_s + k * ns, H->d_tr_u + k * nu, H->d_tr_ref + k * ns, H->d_tr_speed + k,
                         H->d_tr_out_u + k * nu, H->d_tr_out_s + k * ns, H->d_tr_info + k);
 }
@@ -2424,7 +2455,7 @@ extern "C" int rda_sync(rda_handle *H) { if (!H) return RDA_ERR_ARG; HIPCHK(hipS
 extern "C" int rda_fetch_result(rda_handle *H, int k, double *out_u, double *out_s, rda_info *info)
 {
     if (!H || k < 0 || k >= H->K) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
     HIPCHK(hipStreamSynchronize(H->stream));
     if (out_u) HIPCHK(hipMemcpy(out_u, H->d_tr_out_u + k * nu, nu * sizeof(double), hipMemcpyDeviceToHost));
     if (out_s) HIPCHK(hipMemcpy(out_s, H->d_tr_out_s + k * ns, ns * sizeof(double), hipMemcpyDeviceToHost));
@@ -2647,14 +2678,9 @@ extern "C" int rda_shard_comm_init(rda_handle *H, const void *uid128)
 extern "C" int rda_admm_begin(rda_handle *H, const double *nom_s, const double *nom_u, const double *ref_s, double ref_speed)
 {
     if (!H || !nom_s || !nom_u || !ref_s) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
     H->stepped = 1;
     HIPCHK(hipStreamSynchronize(H->stream));
-    memcpy(H->h_step, nom_s, ns * sizeof(double));
-    memcpy(H->h_step + ns, nom_u, nu * sizeof(double));
-    memcpy(H->h_step + ns + nu, ref_s, ns * sizeof(double));
-    H->h_step[ns + nu + ns] = ref_speed;
-    HIPCHK(hipMemcpyAsync(H->d_step, H->h_step, (2 * ns + nu + 1) * sizeof(double), hipMemcpyHostToDevice, H->stream));
+    { int rc = step_block_upload(H, nom_s, nom_u, ref_s, ref_speed); if (rc != RDA_OK) return rc; }
     hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, H->stream, H->d);
     HIPCHK(hipGetLastError());
     return RDA_OK;
@@ -2662,11 +2688,11 @@ extern "C" int rda_admm_begin(rda_handle *H, const double *nom_s, const double *
 extern "C" int rda_admm_su(rda_handle *H, int it, int *stopped)
 {
     if (!H || it < 0) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t T = H->d.c.T;
     H->admm_it = it;
     Dev d = H->d;
-    d.ref = H->d_step + ns + nu; d.ref_speed = H->d_step + ns + nu + ns;
-    RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su<TT>, dim3(1), dim3(su::NT), H->su_lds, H->stream, d, it, H->d_step, H->d_step + ns, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0}));
+    d.ref = H->d_step + step_ref(T); d.ref_speed = H->d_step + step_speed(T);
+    RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su<TT>, dim3(1), dim3(su::NT), H->su_lds, H->stream, d, it, H->d_step, H->d_step + step_u(T), Fin{}));
     HIPCHK(hipGetLastError());
     if (stopped) {
         Ctrl c;
@@ -2680,20 +2706,17 @@ extern "C" int rda_admm_lammuz(rda_handle *H)
 {
     if (!H) return RDA_ERR_ARG;
     Dev d = H->d;
-    launch_lammuz(H, d, H->admm_it, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0});
+    launch_lammuz(H, d, H->admm_it, Fin{});
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
 extern "C" int rda_admm_finish(rda_handle *H, double *out_u, double *out_s, rda_info *info)
 {
     if (!H || !out_u || !out_s) return RDA_ERR_ARG;
-    const size_t T = H->d.c.T, ns = 3 * (T + 1), nu = 2 * T;
     Dev d = H->d;
     { int rc = launch_finish(H, d, make_fin(H, H->d_out_u, H->d_out_s, H->d_info)); if (rc != RDA_OK) return rc; }
     { int rc = fetch_result(H); if (rc != RDA_OK) return rc; }
-    memcpy(out_u, H->h_out, nu * sizeof(double));
-    memcpy(out_s, H->h_out + nu, ns * sizeof(double));
-    if (info) *info = *H->h_info;
+    result_out(H->h_out, H->h_info, H->d.c.T, out_u, out_s, info);
     return RDA_OK;
 }
 
@@ -2730,8 +2753,8 @@ __global__ __launch_bounds__(64 * GS / 4, 2) void k_lammuz_fleet_rows(const Dev 
 #ifndef LMZ_FLEET_FAST_OCC
 #define LMZ_FLEET_FAST_OCC 3
 #endif
-__global__ __launch_bounds__(64 * GS / 4, LMZ_FLEET_FAST_OCC) void k_lammuz_fleet_rows_fast(const Dev *devs, int it) { lammuz_body_rows<1>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0}); }
-__global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_fleet_enum(const Dev *devs, int it) { lammuz_body_rows<2>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{nullptr, nullptr, nullptr, nullptr, 0, 0}); }
+__global__ __launch_bounds__(64 * GS / 4, LMZ_FLEET_FAST_OCC) void k_lammuz_fleet_rows_fast(const Dev *devs, int it) { lammuz_body_rows<1>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
+__global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_fleet_enum(const Dev *devs, int it) { lammuz_body_rows<2>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
 __global__ __launch_bounds__(256) void k_lmz_finalize_fleet(const Dev *devs, const EgoIO *io, int it, int k)
 {
     finalize_body(devs[blockIdx.y], blockIdx.x, gridDim.x, it, fleet_fin(devs[blockIdx.y], io[blockIdx.y], k));
@@ -2751,8 +2774,8 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     std::vector<rda_handle *> egos;
     Dev *h_devs, *d_devs;                 // pinned mirror / device array
     EgoIO *h_io, *d_io_step, *d_io_trace;
-    double *h_in, *d_in;                  // step path, per ego: nom_s | nom_u | ref | speed
-    double *h_out, *d_out;                // per ego: u | s
+    double *h_in, *d_in;                  // step path, per ego: a step block (step_doubles)
+    double *h_out, *d_out;                // per ego: u | s, the head of a result block (res_info doubles)
     rda_info *h_info, *d_info;
     int T, iter_num, J, rows, lmz_split;
     size_t su_lds;
@@ -2765,6 +2788,23 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
+
+// Member i's locations on the step path: its step block in d_in (in_u: nominal controls that live elsewhere, else null), its u | s block
+// under out_base, its info under info_base
+static EgoIO fleet_member_io(const rda_fleet *F, size_t i, const double *in_u, double *out_base, rda_info *info_base)
+{
+    const size_t T = F->T;
+    EgoIO e;
+    e.s = F->d_in + i * step_doubles(T); e.u = in_u ? in_u : e.s + step_u(T); e.ref = e.s + step_ref(T); e.speed = e.s + step_speed(T);
+    e.out_u = out_base + i * res_info(T); e.out_s = e.out_u + res_s(T); e.info = info_base + i;
+    return e;
+}
+// member i's finished step out of the fleet's pinned blocks, into the per-ego arrays of rda_step, concatenated
+static void fleet_result_out(const rda_fleet *F, size_t i, double *out_u, double *out_s, rda_info *info)
+{
+    const size_t T = F->T;
+    result_out(F->h_out + i * res_info(T), F->h_info + i, T, out_u + i * traj_u(T), out_s + i * traj_s(T), info ? info + i : nullptr);
+}
 
 extern "C" void rda_fleet_destroy(rda_fleet *F)
 {
@@ -2791,18 +2831,14 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
     F->T = c.T; F->iter_num = c.iter_num; F->J = (c.N + GS - 1) / GS; F->su_lds = egos[0]->su_lds;
     HIPCHK(hipStreamCreate(F->stream.out()));
     HIPCHK(hipEventCreateWithFlags(F->ev.out(), hipEventDisableTiming));
-    const size_t T = c.T, ns = 3 * (T + 1), nu = 2 * T, nin = 2 * ns + nu + 1, nout = nu + ns;
+    const size_t T = c.T, nin = step_doubles(T), nout = res_info(T);
     hbuf::Group &m = F->mem;
     int rc = 0;
     rc |= m.dev(&F->d_devs, (size_t)B); rc |= m.dev(&F->d_io_step, (size_t)B); rc |= m.dev(&F->d_io_trace, (size_t)B);
     rc |= m.dev(&F->d_in, B * nin); rc |= m.dev(&F->d_out, B * nout); rc |= m.dev(&F->d_info, (size_t)B);
     rc |= m.pin(&F->h_devs, (size_t)B); rc |= m.pin(&F->h_io, (size_t)B); rc |= m.pin(&F->h_in, B * nin); rc |= m.pin(&F->h_out, B * nout); rc |= m.pin(&F->h_info, (size_t)B);
     if (rc) return RDA_ERR_HIP;
-    for (int i = 0; i < B; ++i) {
-        EgoIO &e = F->h_io[i];
-        e.s = F->d_in + i * nin; e.u = e.s + ns; e.ref = e.u + nu; e.speed = e.ref + ns;
-        e.out_u = F->d_out + i * nout; e.out_s = e.out_u + nu; e.info = F->d_info + i;
-    }
+    for (int i = 0; i < B; ++i) F->h_io[i] = fleet_member_io(F, i, nullptr, F->d_out, F->d_info);
     HIPCHK(hipMemcpy(F->d_io_step, F->h_io, B * sizeof(EgoIO), hipMemcpyHostToDevice));
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su_fleet<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds)));
     HIPCHK(hipFuncSetAttribute((const void *)k_finish_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds));
@@ -2844,7 +2880,9 @@ static int fleet_enqueue(rda_fleet *F, const EgoIO *io, int k)
     const int B = F->B;
     for (int it = 0; it < F->iter_num; ++it) {          // iteration 0 resets every member's control block (su_body)
         RDA_SU_DISPATCH(F->T, hipLaunchKernelGGL(k_su_fleet<TT>, dim3(B), dim3(su::NT), F->su_lds, F->stream, F->d_devs, io, it, k));
-        constexpr int NTH = 64 * GS / 4;
+        // (The fleet's own selection of the LamMuZ form, not lammuz_plan: no dense threshold, and other clamps of the work-list grid -
+        // a shared plan would branch on its caller.)
+        constexpr int NTH = LMZ_NTH;
         const int nbr = F->T * F->J, nfin = (nbr + FPB - 1) / FPB, nbp = packed_grid(F->T, F->J);       // one workgroup per (stage, GS-slot block), XCD-aware order
         if (F->rows && F->lmz_split) {
             hipLaunchKernelGGL(k_lammuz_fleet_rows_fast, dim3(nbp, B), dim3(NTH), 0, F->stream, F->d_devs, it);
@@ -2867,11 +2905,11 @@ extern "C" int rda_fleet_step(rda_fleet *F, const double *nom_s, const double *n
                               double *out_u, double *out_s, rda_info *info)
 {
     if (!F || !nom_s || !nom_u || !ref_s || !ref_speed || !out_u || !out_s) return RDA_ERR_ARG;
-    const size_t T = F->T, ns = 3 * (T + 1), nu = 2 * T, nin = 2 * ns + nu + 1, nout = nu + ns, B = F->B;
+    const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), nout = res_info(T), B = F->B;
     for (size_t i = 0; i < B; ++i) {
         double *q = F->h_in + i * nin;
-        memcpy(q, nom_s + i * ns, ns * sizeof(double)); memcpy(q + ns, nom_u + i * nu, nu * sizeof(double));
-        memcpy(q + ns + nu, ref_s + i * ns, ns * sizeof(double)); q[2 * ns + nu] = ref_speed[i];
+        memcpy(q, nom_s + i * ns, ns * sizeof(double)); memcpy(q + step_u(T), nom_u + i * nu, nu * sizeof(double));
+        memcpy(q + step_ref(T), ref_s + i * ns, ns * sizeof(double)); q[step_speed(T)] = ref_speed[i];
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
@@ -2883,11 +2921,7 @@ extern "C" int rda_fleet_step(rda_fleet *F, const double *nom_s, const double *n
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
-    for (size_t i = 0; i < B; ++i) {
-        memcpy(out_u + i * nu, F->h_out + i * nout, nu * sizeof(double));
-        memcpy(out_s + i * ns, F->h_out + i * nout + nu, ns * sizeof(double));
-        if (info) info[i] = F->h_info[i];
-    }
+    for (size_t i = 0; i < B; ++i) fleet_result_out(F, i, out_u, out_s, info);
     return RDA_OK;
 }
 
@@ -2929,6 +2963,7 @@ extern "C" int rda_fleet_upload_scenes(rda_fleet *F, const int32_t *counts, cons
 // rda_scene_resort for every member in ONE launch set (round 6): the members' resident raw scenes (rda_upload_scene*, static obstacles) re-ranked about
 // states[i * stride + 0..1] and their slots rebuilt on the fleet's stream; the next fleet step runs behind it.  Same device code per member as
 // rda_scene_resort: bit-identical slots.  Members with rda_opts::duals_follow, without a resident scene, or inside a tick: RDA_ERR_UNSUPPORTED / _ARG.
+static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from d_rob)
 extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
 {
     if (!F || !states || stride < 2) return RDA_ERR_ARG;
@@ -2949,14 +2984,13 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
     bool changed = false;
     int nmax = 0, wmax = 0;
     for (size_t i = 0; i < B; ++i) {
-        scene::Args a = F->egos[i]->sc_args;
-        a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0;
+        const scene::Args a = fleet_resort_args(F->egos[i]);
         if (memcmp(&a, &F->h_sc[i], sizeof(scene::Args)) != 0) changed = true;
         nmax = a.n > nmax ? a.n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
     if (changed || F->rob_pending) { HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; }
     if (changed) {
-        for (size_t i = 0; i < B; ++i) { scene::Args a = F->egos[i]->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; memcpy((void *)&F->h_sc[i], &a, sizeof(a)); }
+        for (size_t i = 0; i < B; ++i) { const scene::Args a = fleet_resort_args(F->egos[i]); memcpy((void *)&F->h_sc[i], &a, sizeof(a)); }
         HIPCHK(hipMemcpyAsync(F->d_sc, F->h_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
     }
     for (size_t i = 0; i < B; ++i) { F->h_rob[2 * i] = states[i * stride]; F->h_rob[2 * i + 1] = states[i * stride + 1]; }
@@ -2975,7 +3009,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
                                       double *out_u, double *out_s, rda_info *info, double *ref_out, int32_t *min_index, double *end_heading)
 {
     if (!F || !states || !ref_speed || !cur_index || !out_u || !out_s || ind_range < 1) return RDA_ERR_ARG;
-    const size_t T = F->T, ns = 3 * (T + 1), nu = 2 * T, nin = 2 * ns + nu + 1, nout = nu + ns, B = F->B;
+    const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), nout = res_info(T), B = F->B;
     if (!F->d_trk_in) {                                 // first use: the tables (zeroed) take their place once all of them exist
         hbuf::Group g; track::In *hti, *dti; track::Out *hto, *dto; double **hp, **dp; int *hl, *dl; EgoIO *hio, *dio;
         int rc = 0;
@@ -3000,9 +3034,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
         track::In &in = F->h_trk_in[i];
         in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
         in.cur_index = cur_index[i]; in.ind_range = ind_range;
-        EgoIO e;
-        e.s = F->d_in + i * nin; e.u = nom_u ? e.s + ns : H->d.u; e.ref = e.s + ns + nu; e.speed = e.ref + ns;
-        e.out_u = out_base + i * nout; e.out_s = e.out_u + nu; e.info = info_base + i;
+        const EgoIO e = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, out_base, info_base);
         if (memcmp(&e, &F->h_io_track[i], sizeof(EgoIO)) != 0 || F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
     }
     int rc = fleet_refresh(F);
@@ -3011,9 +3043,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
         HIPCHK(hipStreamSynchronize(F->stream));
         for (size_t i = 0; i < B; ++i) {
             rda_handle *H = F->egos[i];
-            EgoIO &e = F->h_io_track[i];
-            e.s = F->d_in + i * nin; e.u = nom_u ? e.s + ns : H->d.u; e.ref = e.s + ns + nu; e.speed = e.ref + ns;
-            e.out_u = out_base + i * nout; e.out_s = e.out_u + nu; e.info = info_base + i;
+            F->h_io_track[i] = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, out_base, info_base);
             F->h_paths[i] = H->d_path; F->h_lens[i] = H->path_len;
         }
         HIPCHK(hipMemcpyAsync(F->d_io_track, F->h_io_track, B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
@@ -3021,8 +3051,8 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
         HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
     }
     if (nom_u) {
-        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + ns, nom_u + i * nu, nu * sizeof(double));
-        HIPCHK(hipMemcpy2DAsync(F->d_in + ns, nin * sizeof(double), F->h_in + ns, nin * sizeof(double), nu * sizeof(double), B,
+        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
+        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
                                 hipMemcpyHostToDevice, F->stream));
     }
     HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
@@ -3039,10 +3069,8 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
     HIPCHK(hipStreamSynchronize(F->stream));
     for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
     for (size_t i = 0; i < B; ++i) {
-        memcpy(out_u + i * nu, F->h_out + i * nout, nu * sizeof(double));
-        memcpy(out_s + i * ns, F->h_out + i * nout + nu, ns * sizeof(double));
-        if (info) info[i] = F->h_info[i];
-        if (ref_out) memcpy(ref_out + i * ns, F->h_in + i * nin + ns + nu, ns * sizeof(double));
+        fleet_result_out(F, i, out_u, out_s, info);
+        if (ref_out) memcpy(ref_out + i * ns, F->h_in + i * nin + step_ref(T), ns * sizeof(double));
         if (min_index) min_index[i] = F->h_trk_out[i].min_index;
         if (end_heading) end_heading[i] = F->h_trk_out[i].end_heading;
     }
@@ -3116,7 +3144,7 @@ extern "C" int rda_su_solve_opts(const rda_cfg *cfg, const rda_opts *opts, const
 {
     if (!cfg || cfg->T < 1 || cfg->T > RDA_TMAX || cfg->N < 1) return RDA_ERR_UNSUPPORTED;
     if (rda_device_count() < 1) return RDA_ERR_NODEVICE;
-    const size_t T = cfg->T, N = cfg->N, ns = 3 * (T + 1), nu = 2 * T;
+    const size_t T = cfg->T, N = cfg->N, ns = traj_s(T), nu = traj_u(T);
     std::vector<double> soa(6 * T * N, 0.0);
     for (size_t n = 0; n < N; ++n) for (size_t t = 0; t < T; ++t) {
         size_t k = t * N + n;
@@ -3139,12 +3167,11 @@ extern "C" int rda_su_solve_opts(const rda_cfg *cfg, const rda_opts *opts, const
     ar.c.dt = cfg->dt; ar.c.L = cfg->L; ar.c.umax0 = cfg->max_speed[0]; ar.c.umax1 = cfg->max_speed[1];
     ar.c.ab0 = cfg->acce_bound[0]; ar.c.ab1 = cfg->acce_bound[1]; ar.c.ws = cfg->ws; ar.c.wu = cfg->wu;
     ar.c.slack_gain = cfg->slack_gain; ar.c.max_sd = cfg->max_sd; ar.c.min_sd = cfg->min_sd; ar.c.ro1 = cfg->ro1; ar.c.ro2 = cfg->ro2;
-    rda_opts od; rda_opts_init(&od);                   // the stop tolerances / switches: the caller's, else the defaults
-    if (opts) od = *opts;
-    ar.c.eps_u = cfg->eps_u; ar.c.tol_rd = od.su_tol[0] > 0 ? od.su_tol[0] : 1e-9; ar.c.tol_rp = od.su_tol[1] > 0 ? od.su_tol[1] : 1e-10; ar.c.tol_mu = od.su_tol[2] > 0 ? od.su_tol[2] : 1e-11;    // (same fallback as rda_create_opts)
+    const rda_opts od = opts_sanitised(opts);          // the stop tolerances / switches: the caller's, else the defaults
+    ar.c.eps_u = cfg->eps_u; ar.c.tol_rd = od.su_tol[0]; ar.c.tol_rp = od.su_tol[1]; ar.c.tol_mu = od.su_tol[2];
     ar.split = od.su_split; ar.accept = od.su_accept; ar.first_attempt = od.su_first_attempt;
-    ar.land = od.su_land ? 1 : 0; if (od.su_land_rho > 0) ar.land_rho = od.su_land_rho;
-    if (od.su_land_tol[0] > 0 && od.su_land_tol[1] > 0 && od.su_land_tol[2] > 0) { ar.land_tol[0] = od.su_land_tol[0]; ar.land_tol[1] = od.su_land_tol[1]; ar.land_tol[2] = od.su_land_tol[2]; }
+    ar.land = od.su_land; ar.land_rho = od.su_land_rho;
+    for (int i = 0; i < 3; ++i) ar.land_tol[i] = od.su_land_tol[i];
     ar.in_s = dns; ar.in_u = dnu; ar.ref = dref; ar.ref_speed = dspeed;
     ar.ax = dsoa; ar.ay = dsoa + T * N; ar.cb = dsoa + 2 * T * N; ar.gx = dsoa + 4 * T * N; ar.gy = dsoa + 5 * T * N;
     ar.P = 1; ar.Nloc = (int)N; ar.chunk = 0;

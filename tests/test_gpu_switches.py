@@ -22,14 +22,16 @@ SWITCHES = [{"RDA_LMZ_DENSE_FROM": "0"}, {"RDA_LMZ_DENSE_FROM": "0", "RDA_LMZ_SP
             {"RDA_ZERO_COPY": "0", "RDA_EARLY_FINISH": "0", "RDA_FUSE_TRACK": "0", "RDA_SU_PRE": "0", "RDA_LMZ_DENSE_FROM": "0"}]
 
 
-def _loop(dyn, moving, steps=45):
+def _loop(dyn, moving, steps=45, **opts):
     from rda_planner_amd.mpc import MPC
+    from rda_planner_amd.rda_solver import hip_options
     car_t = sc.rectangle_robot(dynamics=dyn, wheelbase=3.0 if dyn == "acker" else 0)
     path = sc.line_path([4, 25, 0], [40, 25, 0], 0.1)
     clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])
     scene = sc.scene_polygons(30, lo=(8, 14), hi=(40, 36), seed=5, keep_clear=clear, clear_radius=3.0, moving=moving)
     scene.append(sc.circle(20.0, 29.5, 0.9, (0.0, -0.1)))
-    mpc = MPC(car_t, [p.copy() for p in path], receding=12, iter_num=4, max_edge_num=4, max_obs_num=32, time_print=False)
+    mpc = MPC(car_t, [p.copy() for p in path], receding=12, iter_num=4, max_edge_num=4, max_obs_num=32, time_print=False,
+              **({"hip_opts": hip_options(**opts)} if opts else {}))
     st = path[0].copy().reshape(3, 1)
     if dyn == "omni":
         st[2, 0] = 0.0
@@ -67,6 +69,41 @@ def test_switch_reproduces_the_default_closed_loop(defaults, monkeypatch, env, c
             continue
         assert np.array_equal(g[0], w[0]) and np.array_equal(g[1], w[1]), (k, float(np.abs(g[0] - w[0]).max()))
         assert g[2] == w[2] and g[3] == w[3], (k, g[2:4], w[2:4])
+
+
+# rda_opts entries outside their range, and the documented fallback each one stands for (include/rda_hip.h, rda_opts_init): su_tol falls back per
+# entry; su_land_tol and su_tol_early all three together (su_tol_early to "off"); su_hard_warm[0] <= 0 switches that rule off; su_cold_probe < 1 is 1;
+# su_land_first is clamped to 0..2; su_land_rho <= 0 is 1e4; lmz_mu <= 0 is 1e-6.
+ODD_OPTS = [(dict(su_land=0, su_tol=(1e-5, -1.0, 1e-5)), dict(su_land=0, su_tol=(1e-5, 1e-10, 1e-5))),      # (landing off: the interior point runs to su_tol)
+            (dict(su_land_tol=(1e-2, 0.0, 1e-4)), dict(su_land_tol=(1e-3, 1e-4, 1e-5))),
+            (dict(su_land=0, su_tol_early=(1e-6, 0.0, 1e-8)), dict(su_land=0, su_tol_early=(0.0, 0.0, 0.0))),
+            (dict(su_hard_warm=(0.0, 1e-3)), dict(su_hard_warm=(0.0, 0.0))),
+            (dict(su_land=0, su_cold_from=1, su_cold_probe=0), dict(su_land=0, su_cold_from=1, su_cold_probe=1)),
+            (dict(su_land_first=5), dict(su_land_first=2)), (dict(su_land_first=-1), dict(su_land_first=0)),
+            (dict(su_land_rho=0.0), dict(su_land_rho=1e4)),
+            (dict(lmz_mode=1, lmz_mu=0.0), dict(lmz_mode=1, lmz_mu=1e-6))]
+
+
+@pytest.mark.parametrize("odd,plain", ODD_OPTS, ids=lambda o: ",".join(f"{k}={v}" for k, v in o.items()).replace(" ", ""))
+def test_out_of_range_option_is_its_documented_fallback(hip, odd, plain):
+    """A handle created with an out-of-range rda_opts entry is the handle created with the fallback written out: a short closed loop (moving scene:
+    cold starts, hard starts and landings all occur) returns the same bits - controls, states, residuals, ADMM and interior-point iteration counts -
+    and so does the su hook rda_su_solve_opts, which reads the tolerances and landing entries of the same struct."""
+    import ctypes as C
+    import helpers as hp
+    from rda_planner_amd.rda_solver import hip_options
+    got, want = _loop("diff", True, steps=30, **odd), _loop("diff", True, steps=30, **plain)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g[4] == w[4] and g[5] == w[5], (k, g[4:], w[4:])
+        assert np.array_equal(g[0], w[0]) and np.array_equal(g[1], w[1]), (k, float(np.abs(g[0] - w[0]).max()))
+        assert g[2] == w[2] and g[3] == w[3], (k, g[2:4], w[2:4])
+    cfg = hp.make_cfg(T=20, N=60)
+    si = hp.su_inputs(np.random.default_rng(17), cfg)
+    oo, op = hip_options(**odd), hip_options(**plain)
+    ro = hp.su_solve(lambda *a: hip.lib.rda_su_solve_opts(a[0], C.byref(oo), *a[1:]), cfg, si)
+    rp = hp.su_solve(lambda *a: hip.lib.rda_su_solve_opts(a[0], C.byref(op), *a[1:]), cfg, si)
+    assert ro[0] == rp[0] and ro[4] == rp[4], (ro[0], rp[0], ro[4], rp[4])
+    assert all(np.array_equal(ro[k], rp[k]) for k in (1, 2, 3))
 
 
 def _circle_heavy_loop(steps=30):
