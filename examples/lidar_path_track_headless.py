@@ -2,7 +2,10 @@
 (with its ray-cast lidar) replaces `irsim`, `rda_planner_amd.lidar.scan_box` replaces the script's DBSCAN + cv2 `scan_box`,
 `rda_planner_amd.MPC` replaces `RDA_planner.mpc.MPC` (GPU backend).
 
-    python examples/lidar_path_track_headless.py [world.yaml]
+    python examples/lidar_path_track_headless.py [world.yaml] [--device-scan]
+
+--device-scan: the scan goes to `MPC.control(..., scan=scan_data)` - clustering, boxes and staging run on the GPU (rda_upload_scan);
+the default is the host front end, as in the reference.
 """
 import os
 import sys
@@ -19,7 +22,9 @@ from rda_planner_amd.mpc import MPC                        # instead of: from RD
 
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
-    world = sys.argv[1] if len(sys.argv) > 1 else os.path.join(here, "..", "tests", "golden", "world_lidar_track.yaml")
+    device_scan = "--device-scan" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--device-scan"]
+    world = args[0] if args else os.path.join(here, "..", "tests", "golden", "world_lidar_track.yaml")
     env = irsim.make(world, save_ani=False, display=False)
     car = namedtuple("car", "G h cone_type wheelbase max_speed max_acce dynamics")
     robot_info = env.get_robot_info()
@@ -30,11 +35,14 @@ def main():
     t0, steps, min_clear, seen = time.perf_counter(), 0, float("inf"), 0
     for i in range(500):
         scan_data = env.get_lidar_scan()
-        obs_list = scan_box(env.robot.state, scan_data)
-        seen = max(seen, len(obs_list))
-        for o in obs_list:
-            env.draw_box(o.vertex, refresh=True)
-        opt_vel, info = mpc_opt.control(env.robot.state, 4, obs_list)
+        if device_scan:
+            opt_vel, info = mpc_opt.control(env.robot.state, 4, scan=scan_data)
+        else:
+            obs_list = scan_box(env.robot.state, scan_data)
+            seen = max(seen, len(obs_list))
+            for o in obs_list:
+                env.draw_box(o.vertex, refresh=True)
+            opt_vel, info = mpc_opt.control(env.robot.state, 4, obs_list)
         env.step(opt_vel)
         env.render(show_traj=True, show_trail=True)
         steps += 1

@@ -287,6 +287,35 @@ int  rda_tracked_finish(rda_handle *h, double *out_u, double *out_s, rda_info *i
  * the horizon starts from the uploaded geometry).  RDA_ERR_ARG without a resident raw scene. */
 int  rda_scene_resort(rda_handle *h, const double *robot_xy /*2*/);
 
+/* ---- lidar front end on the device -----------------------------------------------------------------
+ * What the reference's lidar example does per tick in host Python before MPC.control (`scan_box`,
+ * example/lidar_nav/lidar_path_track.py:20-60): range scan -> hit points in the sensor frame -> DBSCAN(eps, min_samples) ->
+ * one minimum-area rectangle per cluster -> 4-vertex 'Rpositive' obstacles in the world frame.  One kernel of one workgroup,
+ * the points in LDS; the semantics are those of rda_planner_amd/lidar.py stage by stage:
+ *   beam i has the angle angle_min + i (angle_max - angle_min) / (n_beams - 1), the last one exactly angle_max; it is a hit
+ *   iff range < range_max - 0.01 (a NaN range is a miss); hits keep the beam order;
+ *   DBSCAN labels as scikit-learn gives them (core: >= min_samples points within eps, itself included; clusters numbered by
+ *   their smallest core point; a border point joins the lowest-numbered cluster in reach; noise -1);
+ *   the rectangle has a side on an edge of the cluster's convex hull (least area, the first such edge among equals), an
+ *   extent below 1 cm is widened to it; corners counter-clockwise; state = sensor pose (x, y, heading) in the world frame.
+ * Fewer than 4 hits give no box.  n_beams <= 4096 and a handle with E >= 4, else RDA_ERR_UNSUPPORTED; eps <= 0,
+ * min_samples < 1, n_beams < 0 or a missing array: RDA_ERR_ARG.
+ * scan -> boxes, returned to the host (the drop-in for the reference's scan_box; also the test hook).
+ * boxes [cap][4][2] world frame, CCW; labels [n_beams]: -2 miss, -1 noise, >= 0 cluster (either may be NULL).
+ * *n_boxes = clusters found (may exceed cap: the first cap are written). */
+int  rda_scan_boxes(rda_handle *h, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
+                    const double *state /*3*/, double eps, int min_samples,
+                    int32_t *n_boxes, double *boxes, int cap, int32_t *labels);
+/* the same scan staged as the handle's obstacles: equivalent to rda_upload_scene(order) of those boxes with robot_xy = state[0..1],
+ * but the boxes go device to device into the resident raw scene (rda_scene_resort works on it afterwards); only the 4-byte box
+ * count is read back (it sizes the scene launches and decides the n == 0 rule: slots untouched, dual side skipped).  The scan
+ * kernel runs on the handle's second stream: between rda_tracked_begin and rda_tracked_finish the wait for the count is not a
+ * wait for the first su-problem, and the conversion kernels run beside it like those of rda_upload_scene_async.  Outside a
+ * tick the staging is asynchronous like rda_upload_scene_async.  With rda_timing_reset(h, 1) the scan kernels are timed as
+ * launches `which` = 3 of rda_timing_read / rda_timing_launches. */
+int  rda_upload_scan(rda_handle *h, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
+                     const double *state /*3*/, double eps, int min_samples, int order, int32_t *n_boxes /* may be NULL */);
+
 /* ---- Fleet: B independent egos advanced together (BASELINE config C5, "batched multi-ego") -------------------
  * The reference plans one robot per RDA_solver object (rda_solver.py:54-109) and a multi-robot user loops over
  * objects.  Here the members stay ordinary handles (own state, obstacles, trace, accessors); the fleet launches

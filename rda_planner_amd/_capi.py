@@ -122,6 +122,15 @@ class CApi:
             f("get_obstacles").argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p]
             f("get_obstacles").restype = C.c_int
 
+        # lidar front end on the device (HIP library only)
+        self.has_scan = hasattr(lib, f"{prefix}_upload_scan")
+        if self.has_scan:
+            f("scan_boxes").argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_double, C.c_double, c_double_p, C.c_double, C.c_int,
+                                        c_int_p, c_double_p, C.c_int, c_int_p]
+            f("upload_scan").argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_double, C.c_double, c_double_p, C.c_double, C.c_int,
+                                         C.c_int, c_int_p]
+            f("scan_boxes").restype = f("upload_scan").restype = C.c_int
+
         # caller-side pre_process on the device (HIP library only)
         self.has_track = hasattr(lib, f"{prefix}_step_tracked")
         self.has_pipeline = False

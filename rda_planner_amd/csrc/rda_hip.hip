@@ -31,6 +31,7 @@
 #include "lammuz_ip_device.h"
 #include "su_device.h"
 #include "scene_device.h"
+#include "lidar_device.h"
 #include "track_device.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -1389,11 +1390,14 @@ struct rda_handle {
     int early_finish;                     // the su launch that detects the early stop writes the result slot (RDA_EARLY_FINISH=0: k_finish does)    // k_su_tracked (RDA_FUSE_TRACK=0: k_track and k_su as two launches)
     int scene_on_s2;                      // in-tick scene staging runs beside the first su-problem (stream2, ev_tick, ev_scene)
     // timing
-    int timing; size_t ev_used[3];       // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers
+    int timing; size_t ev_used[4];       // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers, 3 lidar scans (second stream)
     // device-side obstacle pipeline (rda_upload_scene): scene description and scratch, grown on demand
     int sc_cap; int *d_sc_sel; double *d_sc_blk, *d_sc_key;     // d_sc_blk mirrors the pinned block h_sc (ONE H2D copy per upload)
     scene::Args sc_args; int sc_n;                              // the resident raw scene as the conversion kernels were last given it (sc_n = 0: none)
     char *h_sc; size_t h_sc_bytes;
+    // device-side lidar front end (rda_scan_boxes / rda_upload_scan), allocated by the first scan: the boxes of the last scan on the device; pinned,
+    // read / written by the kernel itself: the ranges, the two counters, and the host's copy of labels and boxes
+    double *d_li_boxes, *h_li_ranges, *h_li_boxes; int *h_li_count, *h_li_labels;
     // device-side pre_process (rda_upload_path / rda_step_tracked)
     double *d_path; int path_len; track::Out *d_trk, *h_trk;
     int dense_from;          // grids above this many workgroups use the dense form of the LamMuZ launch (rda_opts::lmz_dense_from)
@@ -1405,8 +1409,8 @@ struct rda_handle {
     // owners
     hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL), staging, result slot, follow tables
     hbuf::Group terms;                    // Dev::coef, coefL (rda_shard_config replaces them)
-    hbuf::Group trace, path, scene, scene_host, verdict;    // d_tr_*; d_path; d_sc_*; h_sc; h_verdict
-    std::vector<hbuf::Event> ev[3];
+    hbuf::Group trace, path, scene, scene_host, verdict, lidar;    // d_tr_*; d_path; d_sc_*; h_sc; h_verdict; d_li_*, h_li_*
+    std::vector<hbuf::Event> ev[4];
     hbuf::Event ev_tick, ev_scene;
     hbuf::Stream stream, stream2;         // (last: destroyed first)
 };
@@ -1543,7 +1547,7 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     H->d.su_land = o.su_land; H->d.su_land_rho = o.su_land_rho;
     for (int i = 0; i < 3; ++i) { H->d.su_tol[i] = o.su_tol[i]; H->d.su_tol_early[i] = o.su_tol_early[i]; H->d.su_land_tol[i] = o.su_land_tol[i]; }
     H->follow = o.duals_follow != 0; H->prev_used = -1;
-    H->nccl_lib = nullptr; H->comm = nullptr; H->p_allgather = nullptr; H->p_comm_destroy = nullptr; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = 0;
+    H->nccl_lib = nullptr; H->comm = nullptr; H->p_allgather = nullptr; H->p_comm_destroy = nullptr; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = H->ev_used[3] = 0;
     const size_t T = cfg->T, N = cfg->N, E = cfg->E, R = cfg->R;
     HIPCHK(hipStreamCreate(H->stream.out()));
     HIPCHK(hipStreamCreate(H->stream2.out()));
@@ -2340,6 +2344,106 @@ extern "C" int rda_scene_resort(rda_handle *H, const double *robot_xy)
     });
 }
 
+// ---- lidar front end on the device (lidar_device.h) ------------------------------------------------------------------------------
+static int lidar_reserve(rda_handle *H)
+{
+    if (H->d_li_boxes) return RDA_OK;
+    hbuf::Group g;
+    double *db = nullptr, *hr = nullptr, *hb = nullptr; int *hc = nullptr, *hl = nullptr;
+    int rc = 0;
+    rc |= g.dev(&db, (size_t)lidar::MAXB * 8);
+    rc |= g.pin(&hr, (size_t)lidar::MAXB); rc |= g.pin(&hc, 2); rc |= g.pin(&hl, (size_t)lidar::MAXB); rc |= g.pin(&hb, (size_t)lidar::MAXB * 8);
+    if (rc) return RDA_ERR_HIP;
+    HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
+    H->lidar = std::move(g);
+    H->d_li_boxes = db; H->h_li_ranges = hr; H->h_li_count = hc; H->h_li_labels = hl; H->h_li_boxes = hb;
+    return RDA_OK;
+}
+static void lidar_release(rda_handle *H)
+{
+    H->lidar = hbuf::Group();
+    H->d_li_boxes = nullptr; H->h_li_ranges = nullptr; H->h_li_count = nullptr; H->h_li_labels = nullptr; H->h_li_boxes = nullptr;
+}
+
+// One scan through lidar::k_scan, and the wait for it.  The kernel runs on the SECOND stream and touches nothing but the lidar buffers, so inside a
+// tick the wait is for this kernel alone, not for the first su-problem.  The boxes stay in d_li_boxes; to_host: labels and boxes also in h_li_*.
+static int scan_run(rda_handle *H, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
+                    const double *state, double eps, int min_samples, bool to_host, int *n_boxes)
+{
+    if (!H || n_beams < 0 || !ranges || !state || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
+    if (n_beams > lidar::MAXB || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;
+    // a staging that is still queued may be reading the boxes of the previous scan
+    if (H->pending_scene) { HIPCHK(hipStreamSynchronize(H->stream)); HIPCHK(hipStreamSynchronize(H->stream2)); }
+    int rc = lidar_reserve(H);
+    if (rc != RDA_OK) return rc;
+    memcpy(H->h_li_ranges, ranges, (size_t)n_beams * sizeof(double));
+    H->h_li_count[0] = 0; H->h_li_count[1] = 0;
+    lidar::Args a;
+    a.n_beams = n_beams; a.ranges = H->h_li_ranges; a.angle_min = angle_min; a.angle_max = angle_max; a.range_max = range_max;
+    a.sx = state[0]; a.sy = state[1]; a.sth = state[2]; a.eps = eps; a.min_samples = min_samples;
+    a.boxes = H->d_li_boxes; a.count = H->h_li_count;
+    a.labels_h = to_host ? H->h_li_labels : nullptr; a.boxes_h = to_host ? H->h_li_boxes : nullptr;
+    if (H->timing) (void)hipEventRecord(next_event(H, 3), H->stream2);
+    hipLaunchKernelGGL(lidar::k_scan, dim3(1), dim3(lidar::NT), lidar::LDS_BYTES, H->stream2, a);
+    if (H->timing) (void)hipEventRecord(next_event(H, 3), H->stream2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(H->stream2));
+    *n_boxes = H->h_li_count[0];
+    return RDA_OK;
+}
+
+extern "C" int rda_scan_boxes(rda_handle *H, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
+                              const double *state, double eps, int min_samples, int32_t *n_boxes, double *boxes, int cap, int32_t *labels)
+{
+    if (!n_boxes || cap < 0 || (cap > 0 && !boxes)) return RDA_ERR_ARG;
+    int n = 0;
+    int rc = scan_run(H, n_beams, ranges, angle_min, angle_max, range_max, state, eps, min_samples, true, &n);
+    if (rc != RDA_OK) return rc;
+    *n_boxes = n;
+    if (boxes) memcpy(boxes, H->h_li_boxes, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
+    if (labels) memcpy(labels, H->h_li_labels, (size_t)n_beams * sizeof(int32_t));
+    return RDA_OK;
+}
+
+// the boxes of the last scan as the handle's raw scene (what scene_stage does with a host scene, from device memory) and the conversion kernels
+static int scan_stage(rda_handle *H, int n, const double *state, int order, hipStream_t st)
+{
+    Dev &d = H->d;
+    if (n <= 0) { d.obstacle_num = 0; return RDA_OK; }           // nothing written: stale A, b stay (rda_solver.py:485)
+    int rc = scene_reserve(H, n);
+    if (rc != RDA_OK) return rc;
+    const int E = d.c.E, T = d.c.T, N = d.c.N;
+    const size_t o_vel = (size_t)n * E * 2, o_rob = o_vel + (size_t)n * 2, o_bad = o_rob + 2, o_int = o_bad + 1;   // in doubles (scene_stage)
+    double *db = H->d_sc_blk;
+    int *const d_bad = (int *)(db + o_bad);
+    scene::Args a;
+    a.n = n; a.N = N; a.E = E; a.T = T; a.nt = 1; a.order = order; a.dt = d.c.dt;
+    a.kind = (int *)(db + o_int); a.nvert = (int *)(db + o_int) + n; a.geom = db; a.vel = db + o_vel; a.robot = db + o_rob;
+    a.key = H->d_sc_key; a.sel = H->d_sc_sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = d_bad;
+    a.rx = 0; a.ry = 0; a.robot_val = 0;
+    hipLaunchKernelGGL(lidar::k_scene_fill, dim3((n + 255) / 256), dim3(256), 0, st, (const double *)H->d_li_boxes, n, E, db, db + o_vel, db + o_rob, d_bad,
+                       (int *)(db + o_int), (int *)(db + o_int) + n, state[0], state[1]);
+    d.sc_bad = d_bad;
+    H->sc_args = a; H->sc_n = n;
+    scene_kernels(H, a, st);
+    HIPCHK(hipGetLastError());
+    return RDA_OK;
+}
+
+extern "C" int rda_upload_scan(rda_handle *H, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
+                               const double *state, double eps, int min_samples, int order, int32_t *n_boxes)
+{
+    if (!H) return RDA_ERR_ARG;
+    const bool fresh = !H->d_li_boxes;
+    int n = 0;
+    int rc = scan_run(H, n_beams, ranges, angle_min, angle_max, range_max, state, eps, min_samples, false, &n);
+    if (rc != RDA_OK) return rc;
+    rc = scene_async(H, n > 0, [&](hipStream_t st) -> int { return scan_stage(H, n, state, order, st); });
+    if (rc != RDA_OK) { if (fresh) lidar_release(H); return rc; }       // a failed call leaves what the handle holds as it was
+    if (n_boxes) *n_boxes = n;
+    return RDA_OK;
+}
+
 extern "C" int rda_tracked_finish(rda_handle *H, double *out_u, double *out_s, rda_info *info,
                                   double *nom_s_out, double *ref_out, int32_t *min_index, double *end_heading)
 {
@@ -2467,13 +2571,14 @@ extern "C" int rda_timing_reset(rda_handle *H, int enable)
 {
     if (!H) return RDA_ERR_ARG;
     HIPCHK(hipStreamSynchronize(H->stream));
-    H->timing = enable; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = 0;
+    HIPCHK(hipStreamSynchronize(H->stream2));
+    H->timing = enable; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = H->ev_used[3] = 0;
     return RDA_OK;
 }
 extern "C" int rda_timing_read(rda_handle *H, int which, double *total_ms, int *launches)
 {
-    if (!H || which < 0 || which > 2) return RDA_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(H->stream));
+    if (!H || which < 0 || which > 3) return RDA_ERR_ARG;
+    HIPCHK(hipStreamSynchronize(which == 3 ? H->stream2 : H->stream));
     double tot = 0; int n = 0;
     for (size_t i = 0; i + 1 < H->ev_used[which]; i += 2) {
         float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev[which][i], H->ev[which][i + 1]));
@@ -2486,8 +2591,8 @@ extern "C" int rda_timing_read(rda_handle *H, int which, double *total_ms, int *
 
 extern "C" int rda_timing_launches(rda_handle *H, int which, double *ms_out, int cap, int *launches)
 {
-    if (!H || which < 0 || which > 2 || (cap > 0 && !ms_out)) return RDA_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(H->stream));
+    if (!H || which < 0 || which > 3 || (cap > 0 && !ms_out)) return RDA_ERR_ARG;
+    HIPCHK(hipStreamSynchronize(which == 3 ? H->stream2 : H->stream));
     int n = 0;
     for (size_t i = 0; i + 1 < H->ev_used[which]; i += 2, ++n) {
         if (n >= cap) continue;

@@ -11,7 +11,9 @@ is not available here, so both steps are restated in numpy:
     and may return the corners in another order / starting corner - `MPC` re-orders vertices anyway, mpc.py:476-490).
     A cluster of collinear points gives a zero-width rectangle in OpenCV, which the reference's half-space conversion
     turns into an infinite line; here such a rectangle is given `min_width` (1 cm) so that it stays a bounded obstacle.
-This is host code, like in the reference (a few hundred points per scan); the solver behind `MPC.control` is the GPU path.
+This is host code, like in the reference, and the SPECIFICATION of the device front end (csrc/lidar_device.h: rda_scan_boxes /
+rda_upload_scan), which computes the same boxes in one kernel: `scan_box_device` below is the one-line replacement of `scan_box`,
+`MPC.control(state, speed, scan=scan_data)` stages the boxes without returning them to the host at all.
 """
 from collections import namedtuple
 
@@ -120,3 +122,11 @@ def scan_box(state, scan_data, eps=2.0, min_samples=6):
         box = min_area_rect(pts[labels == label])
         out.append(Obstacle(None, None, state[0:2] + R @ box.T, "Rpositive", np.zeros((2, 1))))
     return out
+
+
+def scan_box_device(solver, state, scan_data, eps=2.0, min_samples=6):
+    """`scan_box` computed on the device by `solver` (an `RDA_solver`, or anything that has one as `.rda`: an `MPC`):
+    the same list of obstacles, corners within rounding of the host function's"""
+    solver = getattr(solver, "rda", solver)
+    boxes = solver.scan_boxes(state, scan_data, eps, min_samples)
+    return [Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]

@@ -47,7 +47,9 @@ class MPC:
             self.curve_index = 0
 
     # ------------------------------------------------------------------ control (mpc.py:127-187)
-    def control(self, state, ref_speed=5, obstacle_list=[], **kwargs):
+    def control(self, state, ref_speed=5, obstacle_list=[], scan=None, scan_eps=2.0, scan_min_samples=6, **kwargs):
+        if scan is not None:                             # extension: the lidar scan itself instead of an obstacle list (see _control_scan)
+            return self._control_scan(state, ref_speed, obstacle_list, scan, scan_eps, scan_min_samples, **kwargs)
         if self._tracks(kwargs):
             return self._control_tracked(state, ref_speed, obstacle_list, **kwargs)
         cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
@@ -145,6 +147,36 @@ class MPC:
             u_opt_array, info, min_index, end_heading = self.rda.iterative_solve_tracked(
                 self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
         return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
+
+    # ---- extension: the lidar front end on the device (rda_upload_scan) ---------------------------------------------------
+    def _control_scan(self, state, ref_speed, obstacle_list, scan, eps, min_samples, **kwargs):
+        """`control` fed with a range scan (the dict of ir-sim's `get_lidar_scan`) taken from `state`: what `lidar.scan_box` makes of
+        it - DBSCAN clusters, one minimum-area box each - is computed AND staged on the device; no geometry crosses the host.
+        Same tick otherwise: the tracked path keeps its two halves (the scan is staged beside the first su-problem)."""
+        if len(obstacle_list):
+            raise ValueError("MPC.control: pass either an obstacle_list or scan=, not both")
+        if self.rda_obstacle or not self.rda.has_scan:
+            raise RuntimeError("MPC.control(scan=...) needs the device-side lidar front end (rda_upload_scan); there is no host fallback")
+        if self._tracks(kwargs):
+            cur_ref_path, gear_flag = self._piece(state)
+            self._sync_path(cur_ref_path)
+            if self.rda.has_pipeline:
+                self.rda.tracked_begin(self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
+                try:
+                    self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+                except BaseException:
+                    self.rda.tracked_finish(discard=True)           # close the tick before reporting the error
+                    raise
+                u_opt_array, info, min_index, end_heading = self.rda.tracked_finish()
+            else:
+                self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+                u_opt_array, info, min_index, end_heading = self.rda.iterative_solve_tracked(
+                    self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
+            return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
+        cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
+        self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+        u_opt_array, info = self.rda.iterative_solve_staged(state_pre_array, self.cur_vel_array, ref_traj_list, speed)
+        return self._end(cur_ref_path, u_opt_array, info)
 
     def _begin(self, state, ref_speed, **kwargs):
         """first half of `control` (mpc.py:127-147): the piece of the path in force, the signed reference speed, the

@@ -461,6 +461,59 @@ class RDA_solver:
         if rc < 0:
             raise RuntimeError(f"{self._be.api.prefix}_scene_resort failed with code {rc}")
 
+    # ---- lidar front end on the device (rda_scan_boxes / rda_upload_scan; host specification: lidar.py) ---------------------
+    @property
+    def has_scan(self):
+        return bool(getattr(self._be.api, "has_scan", False))
+
+    def _scan_args(self, state, scan_data, eps, min_samples):
+        ranges = f64(np.asarray(scan_data["ranges"], float).ravel())
+        st = f64(np.asarray(state, float).ravel()[0:3])
+        head = (self._be.handle, int(ranges.size), dptr(ranges), float(scan_data["angle_min"]), float(scan_data["angle_max"]),
+                float(scan_data["range_max"]), dptr(st), float(eps), int(min_samples))
+        return head, (ranges, st)                        # (the arrays stay referenced until the call has returned)
+
+    def scan_boxes(self, state, scan_data, eps=2.0, min_samples=6, with_labels=False):
+        """`lidar.scan_box` on the device: the (n, 4, 2) corners (world frame, counter-clockwise) of one minimum-area rectangle per
+        DBSCAN cluster of the scan taken from `state`; with_labels: also the per-beam labels (-2 miss, -1 noise, >= 0 cluster)"""
+        head, keep = self._scan_args(state, scan_data, eps, min_samples)
+        cap = max(1, keep[0].size)
+        boxes, n, labels = np.zeros((cap, 4, 2)), np.zeros(1, np.int32), np.zeros(cap, np.int32)
+        rc = self._be.api.scan_boxes(*head, iptr(n), dptr(boxes), cap, iptr(labels))
+        if rc < 0:
+            raise RuntimeError(f"{self._be.api.prefix}_scan_boxes failed with code {rc}")
+        return (boxes[:n[0]], labels[:keep[0].size]) if with_labels else boxes[:n[0]]
+
+    def upload_scan(self, state, scan_data, eps=2.0, min_samples=6, order=True):
+        """the boxes of `scan_boxes` staged as this solver's obstacles without leaving the device (`upload_scene` of them, robot at
+        state[0:2]); usable inside an open tick like `upload_scene_async`.  Returns the number of boxes."""
+        head, keep = self._scan_args(state, scan_data, eps, min_samples)
+        n = np.zeros(1, np.int32)
+        rc = self._be.api.upload_scan(*head, int(bool(order)), iptr(n))
+        if rc < 0:
+            raise RuntimeError(f"{self._be.api.prefix}_upload_scan failed with code {rc}")
+        return int(n[0])
+
+    def iterative_solve_staged(self, nom_s, nom_u, ref_states, ref_speed):
+        """`iterative_solve` on the obstacles that are staged on the device already (`upload_scan`), with the host's nominal
+        trajectory and reference: the device-resident step (a trace of one step: rda_upload_trace / rda_enqueue_step, which
+        tests/test_gpu_parity.py pins to rda_step)"""
+        T, lib, h = self.T, self._be.api.lib, self._be.handle
+        start = time.time()
+        ref = f64(np.hstack(ref_states)[0:3, :], (3, T + 1))
+        nom_s, nom_u, speed = f64(nom_s, (3, T + 1)), f64(nom_u, (2, T)), f64([float(ref_speed)])
+        out_u, out_s, info_c = np.zeros((2, T)), np.zeros((3, T + 1)), Info()
+        self._timing_begin()
+        rc = lib.rda_upload_trace(h, 1, dptr(nom_s), dptr(nom_u), dptr(ref), dptr(speed))
+        rc = rc or lib.rda_enqueue_step(h, 0) or lib.rda_sync(h)
+        rc = rc or lib.rda_fetch_result(h, 0, dptr(out_u), dptr(out_s), C.byref(info_c))
+        if rc < 0:
+            raise RuntimeError(f"{self._be.api.prefix}: the step on the staged obstacles failed with code {rc}")
+        if info_c.su_status and self.time_print:
+            print("No update of state and control vector")        # reference :699
+        self._timing_report(info_c, start)
+        return out_u, self.pack_info(ref_states, out_s, info_c, start)
+
     def tracked_finish(self, discard=False):
         """queue the rest of the ADMM loop, wait, return what `iterative_solve_tracked` returns"""
         T = self.T
