@@ -347,6 +347,27 @@ int  rda_fleet_step_tracked(rda_fleet *f, const double *states /*B*3*/, const do
  * behind it.  Replaces one MPC.convert_rda_obstacle + distance sort per robot and tick (mpc.py:189-218, obstacle_order=True).  Slots bit-identical to
  * rda_scene_resort on each member.  Until the next fleet step has returned the members must not be used on their own. */
 int  rda_fleet_scene_resort(rda_fleet *f, const double *states, int stride);
+/* Fleet lidar: rda_scan_boxes / rda_upload_scan for every member in ONE scan launch (a workgroup, and so a compute unit, per member; the reference's
+ * scan_box runs once per robot and tick, example/lidar_nav/lidar_path_track.py:20-60).  Per-member arrays are member-major; `ranges` is the
+ * concatenation of the members' scans (member i owns n_beams[i] consecutive entries, counts may differ, 0 = no scan: no box); states [B][3] are the
+ * sensor poses.  Same device code per member as the solo calls: counts, boxes, labels and staged slots are bit-identical to theirs.  Argument rules
+ * of the solo calls, for every member: a missing array, eps <= 0, min_samples < 1 or a negative beam count: RDA_ERR_ARG; a member with more than
+ * 4096 beams, E < 4, or (upload) a member with rda_opts::duals_follow: RDA_ERR_UNSUPPORTED - nothing is staged for any member then.  A refused
+ * allocation: RDA_ERR_HIP, fleet and members as they were.
+ * scans -> boxes, returned to the host: n_boxes [B] = clusters found per member (may exceed cap: the first cap are written), boxes [B][cap][4][2]
+ * world frame, CCW; labels at the member's offset in `ranges`: -2 miss, -1 noise, >= 0 cluster (boxes with cap = 0, and labels, may be NULL). */
+int  rda_fleet_scan_boxes(rda_fleet *f, const int32_t *n_beams /*B*/, const double *ranges, const double *angle_min /*B*/,
+                          const double *angle_max /*B*/, const double *range_max /*B*/, const double *states /*B*3*/,
+                          double eps, int min_samples, int32_t *n_boxes /*B*/, double *boxes /*B*cap*4*2 or NULL*/, int cap,
+                          int32_t *labels /*sum of n_beams, or NULL*/);
+/* the same scans staged as every member's obstacles, each exactly as rda_upload_scan(order[i]) stages it on the member (resident raw scene for a later
+ * rda_fleet_scene_resort / rda_scene_resort; zero boxes: obstacle count 0, slots untouched, dual side skipped): one pinned copy of all ranges, one scan
+ * launch, ONE wait for the B box counts, then boxes -> raw scenes -> slots -> candidate lists of all members by five launches whatever B is.  Everything
+ * runs on the fleet's stream, behind whatever the members still have queued; the next fleet step runs behind it.  As with rda_fleet_scene_resort: until
+ * rda_fleet_sync or the next fleet step has returned the members must not be used on their own (a member inside rda_tracked_begin: RDA_ERR_ARG). */
+int  rda_fleet_upload_scans(rda_fleet *f, const int32_t *n_beams, const double *ranges, const double *angle_min,
+                            const double *angle_max, const double *range_max, const double *states /*B*3*/,
+                            double eps, int min_samples, const int32_t *order /*B*/, int32_t *n_boxes /*B or NULL*/);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */
 int  rda_fleet_enqueue_range(rda_fleet *f, int k0, int k1);
 int  rda_fleet_sync(rda_fleet *f);

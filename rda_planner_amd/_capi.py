@@ -175,6 +175,14 @@ class CApi:
             if self.has_fleet_scenes:
                 f("fleet_upload_scenes").argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
                 f("fleet_upload_scenes").restype = C.c_int
+            # fleet lidar: every member's scan in one launch
+            self.has_fleet_scans = hasattr(lib, f"{prefix}_fleet_upload_scans")
+            if self.has_fleet_scans:
+                f("fleet_scan_boxes").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
+                                                  c_int_p, c_double_p, C.c_int, c_int_p]
+                f("fleet_upload_scans").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
+                                                    c_int_p, c_int_p]
+                f("fleet_scan_boxes").restype = f("fleet_upload_scans").restype = C.c_int
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

@@ -87,7 +87,8 @@ __device__ __forceinline__ Extent edge_extent(const double *px, const double *py
     return x;
 }
 
-__global__ __launch_bounds__(NT) void k_scan(const Args a)
+// one scan by one workgroup of NT threads with LDS_BYTES of dynamic LDS (every return below is taken by the whole workgroup)
+__device__ __forceinline__ void scan_body(const Args &a)
 {
 #pragma clang fp contract(off)        // numpy does not fuse: keep every product and sum separately rounded
     double *px = smem_lidar, *py = px + MAXB;
@@ -304,6 +305,17 @@ __global__ __launch_bounds__(NT) void k_scan(const Args a)
     }
 }
 
+__global__ __launch_bounds__(NT) void k_scan(const Args a) { scan_body(a); }
+
+// The same for a FLEET (rda_fleet_scan_boxes / rda_fleet_upload_scans): blockIdx.x = the member, its Args (own beams, field of view, pose, box buffer,
+// count words) in a device array.  Same device code per member, one workgroup each: boxes, labels and counts are bit-identical to k_scan's.
+__global__ __launch_bounds__(NT) void k_scan_fleet(const Args *as)
+{
+    const Args a = as[blockIdx.x];
+    if (a.n_beams <= 0) { if (threadIdx.x == 0) { a.count[0] = 0; a.count[1] = 0; } return; }
+    scan_body(a);
+}
+
 // the boxes as a raw scene in the layout scene_stage uploads (rda_hip.hip): polygons of 4 vertices, no velocity, the robot position for the ordering
 __global__ void k_scene_fill(const double *boxes, const int n, const int E, double *geom, double *vel, double *robot, int *nonconvex, int *kind, int *nvert,
                              const double rx, const double ry)
@@ -315,6 +327,26 @@ __global__ void k_scene_fill(const double *boxes, const int n, const int E, doub
     for (int e = 0; e < E; ++e) { g[2 * e] = e < 4 ? boxes[(size_t)i * 8 + 2 * e] : 0.0; g[2 * e + 1] = e < 4 ? boxes[(size_t)i * 8 + 2 * e + 1] : 0.0; }
     vel[2 * i] = 0.0; vel[2 * i + 1] = 0.0;
     kind[i] = 0; nvert[i] = 4;
+}
+
+
+// k_scene_fill for every member of a fleet in one launch (blockIdx.y = the member; n = 0: a member without boxes, nothing is written)
+struct Fill {
+    const double *boxes; int n, E;
+    double *geom, *vel, *robot; int *nonconvex, *kind, *nvert;
+    double rx, ry;
+};
+__global__ void k_scene_fill_fleet(const Fill *fs)
+{
+    const Fill f = fs[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f.n <= 0) return;
+    if (i == 0) { f.robot[0] = f.rx; f.robot[1] = f.ry; *f.nonconvex = 0; }
+    if (i >= f.n) return;
+    double *g = f.geom + (size_t)i * f.E * 2;
+    for (int e = 0; e < f.E; ++e) { g[2 * e] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e] : 0.0; g[2 * e + 1] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e + 1] : 0.0; }
+    f.vel[2 * i] = 0.0; f.vel[2 * i + 1] = 0.0;
+    f.kind[i] = 0; f.nvert[i] = 4;
 }
 
 }  // namespace lidar

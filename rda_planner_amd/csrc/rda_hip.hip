@@ -460,7 +460,12 @@ __device__ __forceinline__ void prepare_body(const Dev &d, lmz::WaveLDS *wl)
     if (lane == 0) { d.oc_cnt[2 * w] = W.npv; d.oc_cnt[2 * w + 1] = W.nlv; }
 }
 __global__ __launch_bounds__(256) void k_prepare(Dev d) { __shared__ lmz::WaveLDS wl[4]; prepare_body(d, wl); }
-__global__ __launch_bounds__(256) void k_prepare_fleet(const Dev *devs) { __shared__ lmz::WaveLDS wl[4]; prepare_body(devs[blockIdx.y], wl); }
+__global__ __launch_bounds__(256) void k_prepare_fleet(const Dev *devs)
+{
+    __shared__ lmz::WaveLDS wl[4];
+    if (!devs[blockIdx.y].obstacle_num) return;      // (uniform) a member without staged obstacles has no slots to list (rda_fleet_upload_scans: zero boxes)
+    prepare_body(devs[blockIdx.y], wl);
+}
 
 // Unit w of a rank's LamMuZ grid -> (stage t, local slot nl): the SLOT runs fastest and a stage is padded to GS J units, so a
 // workgroup of the packed kernels (GS = 8 rows: 2 waves x 4 rows) owns the slots GS j .. GS j + GS-1 of ONE stage: with the stage-major
@@ -1831,19 +1836,34 @@ extern "C" int rda_upload_obstacles(rda_handle *H, int n_obs, const double *A, c
 // raw scene block, identical on the host (pinned) and on the device: geom [n][E][2] | vel [n][2] | robot [2] | nonconvex
 // counter (int, padded to 8 bytes) | kind [n] | nvert [n]
 static size_t scene_block_bytes(size_t n, size_t E) { return n * (E * 2 + 2) * sizeof(double) + 3 * sizeof(double) + 2 * n * sizeof(int); }
+// the larger buffers a scene of n obstacles needs, built beside the old ones (alloc) and moved in (commit) only when all of them exist - rda_fleet_upload_scans
+// allocates for every member before it commits for any
+struct SceneGrow {
+    bool grow_dev = false, grow_host = false; int cap = 0; size_t need = 0;
+    hbuf::Group dev, host;
+    double *blk = nullptr, *key = nullptr; int *sel = nullptr; char *hsc = nullptr;
+};
+static int scene_grow_alloc(const rda_handle *H, int n, SceneGrow &g)
+{
+    const size_t E = H->d.c.E;
+    g.need = scene_block_bytes((size_t)n, E);
+    g.grow_dev = n > H->sc_cap; g.grow_host = g.need > H->h_sc_bytes;
+    g.cap = n + n / 2 + 16;
+    int rc = 0;
+    if (g.grow_dev) { rc |= g.dev.dev(&g.blk, scene_block_bytes((size_t)g.cap, E) / sizeof(double) + 1); rc |= g.dev.dev(&g.sel, (size_t)g.cap); rc |= g.dev.dev(&g.key, (size_t)g.cap); }
+    if (g.grow_host) rc |= g.host.pin(&g.hsc, g.need * 2);
+    return rc ? RDA_ERR_HIP : RDA_OK;
+}
+static void scene_grow_commit(rda_handle *H, SceneGrow &g)
+{
+    if (g.grow_dev) { H->scene = std::move(g.dev); H->d_sc_blk = g.blk; H->d_sc_sel = g.sel; H->d_sc_key = g.key; H->sc_cap = g.cap; H->sc_n = 0; }
+    if (g.grow_host) { H->scene_host = std::move(g.host); H->h_sc = g.hsc; H->h_sc_bytes = g.need * 2; }
+}
 static int scene_reserve(rda_handle *H, int n)
 {
-    const size_t E = H->d.c.E, need = scene_block_bytes((size_t)n, E);
-    const bool grow_dev = n > H->sc_cap, grow_host = need > H->h_sc_bytes;
-    const int cap = n + n / 2 + 16;
-    hbuf::Group dev, host;                  // the larger buffers replace the old ones only when all of them exist
-    double *blk = nullptr, *key = nullptr; int *sel = nullptr; char *hsc = nullptr;
-    int rc = 0;
-    if (grow_dev) { rc |= dev.dev(&blk, scene_block_bytes((size_t)cap, E) / sizeof(double) + 1); rc |= dev.dev(&sel, (size_t)cap); rc |= dev.dev(&key, (size_t)cap); }
-    if (grow_host) rc |= host.pin(&hsc, need * 2);
-    if (rc) return RDA_ERR_HIP;
-    if (grow_dev) { H->scene = std::move(dev); H->d_sc_blk = blk; H->d_sc_sel = sel; H->d_sc_key = key; H->sc_cap = cap; H->sc_n = 0; }
-    if (grow_host) { H->scene_host = std::move(host); H->h_sc = hsc; H->h_sc_bytes = need * 2; }
+    SceneGrow g;
+    if (scene_grow_alloc(H, n, g) != RDA_OK) return RDA_ERR_HIP;
+    scene_grow_commit(H, g);
     return RDA_OK;
 }
 
@@ -2405,6 +2425,21 @@ extern "C" int rda_scan_boxes(rda_handle *H, int n_beams, const double *ranges, 
     return RDA_OK;
 }
 
+// the conversion kernels' arguments for n boxes laid out as a raw scene in the handle's (reserved) scene block: 4-vertex polygons without velocity
+static scene::Args scan_scene_args(const rda_handle *H, int n, int order)
+{
+    const Dev &d = H->d;
+    const int E = d.c.E, T = d.c.T, N = d.c.N;
+    const size_t o_vel = (size_t)n * E * 2, o_rob = o_vel + (size_t)n * 2, o_bad = o_rob + 2, o_int = o_bad + 1;   // in doubles (scene_stage)
+    double *db = H->d_sc_blk;
+    scene::Args a;
+    a.n = n; a.N = N; a.E = E; a.T = T; a.nt = 1; a.order = order; a.dt = d.c.dt;
+    a.kind = (int *)(db + o_int); a.nvert = (int *)(db + o_int) + n; a.geom = db; a.vel = db + o_vel; a.robot = db + o_rob;
+    a.key = H->d_sc_key; a.sel = H->d_sc_sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = (int *)(db + o_bad);
+    a.rx = 0; a.ry = 0; a.robot_val = 0;
+    return a;
+}
+
 // the boxes of the last scan as the handle's raw scene (what scene_stage does with a host scene, from device memory) and the conversion kernels
 static int scan_stage(rda_handle *H, int n, const double *state, int order, hipStream_t st)
 {
@@ -2412,18 +2447,10 @@ static int scan_stage(rda_handle *H, int n, const double *state, int order, hipS
     if (n <= 0) { d.obstacle_num = 0; return RDA_OK; }           // nothing written: stale A, b stay (rda_solver.py:485)
     int rc = scene_reserve(H, n);
     if (rc != RDA_OK) return rc;
-    const int E = d.c.E, T = d.c.T, N = d.c.N;
-    const size_t o_vel = (size_t)n * E * 2, o_rob = o_vel + (size_t)n * 2, o_bad = o_rob + 2, o_int = o_bad + 1;   // in doubles (scene_stage)
-    double *db = H->d_sc_blk;
-    int *const d_bad = (int *)(db + o_bad);
-    scene::Args a;
-    a.n = n; a.N = N; a.E = E; a.T = T; a.nt = 1; a.order = order; a.dt = d.c.dt;
-    a.kind = (int *)(db + o_int); a.nvert = (int *)(db + o_int) + n; a.geom = db; a.vel = db + o_vel; a.robot = db + o_rob;
-    a.key = H->d_sc_key; a.sel = H->d_sc_sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = d_bad;
-    a.rx = 0; a.ry = 0; a.robot_val = 0;
-    hipLaunchKernelGGL(lidar::k_scene_fill, dim3((n + 255) / 256), dim3(256), 0, st, (const double *)H->d_li_boxes, n, E, db, db + o_vel, db + o_rob, d_bad,
-                       (int *)(db + o_int), (int *)(db + o_int) + n, state[0], state[1]);
-    d.sc_bad = d_bad;
+    const scene::Args a = scan_scene_args(H, n, order);
+    hipLaunchKernelGGL(lidar::k_scene_fill, dim3((n + 255) / 256), dim3(256), 0, st, (const double *)H->d_li_boxes, n, a.E, const_cast<double *>(a.geom),
+                       const_cast<double *>(a.vel), const_cast<double *>(a.robot), a.nonconvex, const_cast<int *>(a.kind), const_cast<int *>(a.nvert), state[0], state[1]);
+    d.sc_bad = a.nonconvex;
     H->sc_args = a; H->sc_n = n;
     scene_kernels(H, a, st);
     HIPCHK(hipGetLastError());
@@ -2889,7 +2916,12 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     double **h_paths, **d_paths; int *h_lens, *d_lens; EgoIO *h_io_track, *d_io_track;
     // rda_fleet_scene_resort (allocated on first use): the members' scene arguments, their robots' positions; rob_pending: a copy out of h_rob may be queued
     scene::Args *h_sc, *d_sc; double *h_rob, *d_rob; int rob_pending;
-    hbuf::Group mem, trk, resort;         // the tables above; those of tracked stepping; those of rda_fleet_scene_resort
+    // fleet lidar (rda_fleet_scan_boxes / rda_fleet_upload_scans), allocated on first use: per member the scan kernel's arguments, the fill kernel's and the
+    // conversion kernels' (pinned mirror / device array); the boxes of the last scans [B][MAXB][4][2] on the device; pinned, read / written by the kernel
+    // itself: the concatenated ranges [B * MAXB], the counters [B][2] - and, for rda_fleet_scan_boxes alone, the host's copy of labels and boxes
+    lidar::Args *h_li_args, *d_li_args; lidar::Fill *h_li_fill, *d_li_fill; scene::Args *h_li_sc, *d_li_sc;
+    double *d_li_boxes, *h_li_ranges, *h_li_boxes; int *h_li_count, *h_li_labels;
+    hbuf::Group mem, trk, resort, lidar, lidar_host;      // the tables above; those of tracked stepping; of rda_fleet_scene_resort; of the fleet lidar (scan, staging | host copies)
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -2951,6 +2983,15 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
     return RDA_OK;
 }
 
+// which form of the LamMuZ launch the members allow together
+static void fleet_refresh_flags(rda_fleet *F)
+{
+    F->rows = 1;
+    F->lmz_split = 1;
+    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->lmz_split) F->lmz_split = 0;
+    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->d.rows || !F->egos[i]->d.obstacle_num) F->rows = 0;
+}
+
 // members' records (obstacle count, staged pointers, weights may have changed since the last call) -> device; the fleet
 // stream then waits for whatever the members still have in flight on their own streams (obstacle uploads)
 static int fleet_refresh(rda_fleet *F)
@@ -2968,10 +3009,7 @@ static int fleet_refresh(rda_fleet *F)
         HIPCHK(hipEventRecord(F->ev, F->egos[i]->stream));
         HIPCHK(hipStreamWaitEvent(F->stream, F->ev, 0));
     }
-    F->rows = 1;
-    F->lmz_split = 1;
-    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->lmz_split) F->lmz_split = 0;
-    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->d.rows || !F->egos[i]->d.obstacle_num) F->rows = 0;
+    fleet_refresh_flags(F);
     if (changed) {
         HIPCHK(hipStreamSynchronize(F->stream));            // an earlier copy out of the pinned mirror may still be queued
         for (int i = 0; i < F->B; ++i) memcpy(&F->h_devs[i], &F->egos[i]->d, sizeof(Dev));
@@ -3106,6 +3144,156 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
     hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
     hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), (unsigned)B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
     HIPCHK(hipGetLastError());
+    return RDA_OK;
+}
+
+// ---- fleet lidar (lidar::k_scan_fleet): every member's range scan in one launch --------------------------------------------------------------------
+static int fleet_lidar_reserve(rda_fleet *F, bool host_copy)
+{
+    const size_t B = F->B;
+    if (!F->d_li_boxes) {
+        hbuf::Group g; lidar::Args *ha, *da; lidar::Fill *hf, *df; scene::Args *hs, *ds; double *db, *hr; int *hc;
+        int rc = 0;
+        rc |= g.dev(&da, B); rc |= g.dev(&df, B); rc |= g.dev(&ds, B); rc |= g.dev(&db, B * lidar::MAXB * 8);
+        rc |= g.pin(&ha, B); rc |= g.pin(&hf, B); rc |= g.pin(&hs, B); rc |= g.pin(&hr, B * lidar::MAXB); rc |= g.pin(&hc, 2 * B);
+        if (rc) return RDA_ERR_HIP;
+        HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
+        F->lidar = std::move(g);
+        F->h_li_args = ha; F->d_li_args = da; F->h_li_fill = hf; F->d_li_fill = df; F->h_li_sc = hs; F->d_li_sc = ds;
+        F->d_li_boxes = db; F->h_li_ranges = hr; F->h_li_count = hc;
+    }
+    if (host_copy && !F->h_li_boxes) {
+        hbuf::Group g; double *hb; int *hl;
+        int rc = 0;
+        rc |= g.pin(&hb, B * lidar::MAXB * 8); rc |= g.pin(&hl, B * lidar::MAXB);
+        if (rc) return RDA_ERR_HIP;
+        F->lidar_host = std::move(g); F->h_li_boxes = hb; F->h_li_labels = hl;
+    }
+    return RDA_OK;
+}
+static void fleet_lidar_release(rda_fleet *F)
+{
+    F->lidar = hbuf::Group();
+    F->h_li_args = F->d_li_args = nullptr; F->h_li_fill = F->d_li_fill = nullptr; F->h_li_sc = F->d_li_sc = nullptr;
+    F->d_li_boxes = F->h_li_ranges = nullptr; F->h_li_count = nullptr;
+}
+
+// the argument rules of scan_run, for every member
+static int fleet_scan_check(const rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                            const double *range_max, const double *states, double eps, int min_samples)
+{
+    if (!F || !n_beams || !ranges || !angle_min || !angle_max || !range_max || !states || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
+    for (int i = 0; i < F->B; ++i) if (n_beams[i] < 0) return RDA_ERR_ARG;
+    for (int i = 0; i < F->B; ++i) if (n_beams[i] > lidar::MAXB || F->egos[i]->d.c.E < 4) return RDA_ERR_UNSUPPORTED;
+    return RDA_OK;
+}
+
+// All members' scans through ONE lidar::k_scan_fleet launch on the fleet's stream (a workgroup and so a compute unit per member), and the ONE wait for
+// it: the counters are then in h_li_count [B][2], the boxes in d_li_boxes; to_host: labels (at the member's beam offset) and boxes also in h_li_*.
+static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                          const double *range_max, const double *states, double eps, int min_samples, bool to_host)
+{
+    const size_t B = F->B;
+    size_t off = 0;
+    for (size_t i = 0; i < B; ++i) {
+        lidar::Args &a = F->h_li_args[i];
+        a.n_beams = n_beams[i]; a.ranges = F->h_li_ranges + off; a.angle_min = angle_min[i]; a.angle_max = angle_max[i]; a.range_max = range_max[i];
+        a.sx = states[3 * i]; a.sy = states[3 * i + 1]; a.sth = states[3 * i + 2]; a.eps = eps; a.min_samples = min_samples;
+        a.boxes = F->d_li_boxes + i * lidar::MAXB * 8; a.count = F->h_li_count + 2 * i;
+        a.labels_h = to_host ? F->h_li_labels + off : nullptr; a.boxes_h = to_host ? F->h_li_boxes + i * lidar::MAXB * 8 : nullptr;
+        F->h_li_count[2 * i] = 0; F->h_li_count[2 * i + 1] = 0;
+        off += (size_t)n_beams[i];
+    }
+    memcpy(F->h_li_ranges, ranges, off * sizeof(double));               // one pinned copy of all ranges (off <= B * MAXB)
+    HIPCHK(hipMemcpyAsync(F->d_li_args, F->h_li_args, B * sizeof(lidar::Args), hipMemcpyHostToDevice, F->stream));
+    hipLaunchKernelGGL(lidar::k_scan_fleet, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)F->d_li_args);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    return RDA_OK;
+}
+
+extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                                    const double *range_max, const double *states, double eps, int min_samples, int32_t *n_boxes, double *boxes, int cap,
+                                    int32_t *labels)
+{
+    if (!n_boxes || cap < 0 || (cap > 0 && !boxes)) return RDA_ERR_ARG;
+    int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
+    if (rc != RDA_OK) return rc;
+    rc = fleet_lidar_reserve(F, true);
+    if (rc != RDA_OK) return rc;
+    rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, true);
+    if (rc != RDA_OK) return rc;
+    size_t off = 0;
+    for (size_t i = 0; i < (size_t)F->B; ++i) {
+        const int n = F->h_li_count[2 * i];
+        n_boxes[i] = n;
+        if (boxes) memcpy(boxes + i * (size_t)cap * 8, F->h_li_boxes + i * lidar::MAXB * 8, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
+        if (labels) memcpy(labels + off, F->h_li_labels + off, (size_t)n_beams[i] * sizeof(int32_t));
+        off += (size_t)n_beams[i];
+    }
+    return RDA_OK;
+}
+
+// rda_upload_scan for every member: one scan launch, one wait for the B counts, then every member's boxes -> raw scene -> slots -> candidate lists by
+// FIVE launches whatever B is (blockIdx.y = the member), all on the fleet's stream.  Host-side member state ends as scan_stage / scene_kernels leave it.
+extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                                      const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes)
+{
+    if (!order) return RDA_ERR_ARG;
+    int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
+    if (rc != RDA_OK) return rc;
+    const size_t B = F->B;
+    for (rda_handle *H : F->egos) if (H->pending) return RDA_ERR_ARG;                     // a member inside a tick of its own
+    for (rda_handle *H : F->egos) if (H->follow) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member)
+    const bool fresh = !F->d_li_boxes;
+    rc = fleet_lidar_reserve(F, false);
+    if (rc != RDA_OK) return rc;
+    rc = fleet_refresh(F);                              // behind whatever the members still have queued
+    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false);
+    // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
+    std::vector<SceneGrow> grow(B);
+    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->h_li_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->h_li_count[2 * i], grow[i]);
+    if (rc != RDA_OK) { if (fresh) fleet_lidar_release(F); return rc; }      // a failed call leaves what the fleet and the members hold as it was
+    int nmax = 0, wmax = 0;
+    for (size_t i = 0; i < B; ++i) {
+        rda_handle *H = F->egos[i];
+        Dev &d = H->d;
+        const int n = F->h_li_count[2 * i];
+        lidar::Fill &f = F->h_li_fill[i];
+        if (n <= 0) {                                   // nothing written: stale A, b stay (rda_solver.py:485)
+            d.obstacle_num = 0;
+            memset((void *)&F->h_li_sc[i], 0, sizeof(scene::Args)); memset((void *)&f, 0, sizeof(f));
+            continue;
+        }
+        scene_grow_commit(H, grow[i]);
+        const scene::Args a = scan_scene_args(H, n, order[i] ? 1 : 0);
+        f.boxes = F->d_li_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
+        f.geom = const_cast<double *>(a.geom); f.vel = const_cast<double *>(a.vel); f.robot = const_cast<double *>(a.robot);
+        f.nonconvex = a.nonconvex; f.kind = const_cast<int *>(a.kind); f.nvert = const_cast<int *>(a.nvert);
+        f.rx = states[3 * i]; f.ry = states[3 * i + 1];
+        memcpy((void *)&F->h_li_sc[i], &a, sizeof(a));
+        H->sc_args = a; H->sc_n = n;
+        d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;                        // (scene_kernels)
+        d.slot_src = H->d_sc_sel; d.src_used = n < a.N ? n : a.N;
+        nmax = n > nmax ? n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
+    }
+    // the members' records as they are now (the stream is idle: nothing reads the pinned mirrors)
+    for (size_t i = 0; i < B; ++i) memcpy(&F->h_devs[i], &F->egos[i]->d, sizeof(Dev));
+    HIPCHK(hipMemcpyAsync(F->d_devs, F->h_devs, B * sizeof(Dev), hipMemcpyHostToDevice, F->stream));
+    fleet_refresh_flags(F);
+    if (nmax > 0) {
+        HIPCHK(hipMemcpyAsync(F->d_li_fill, F->h_li_fill, B * sizeof(lidar::Fill), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(hipMemcpyAsync(F->d_li_sc, F->h_li_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
+        const scene::Args *as = F->d_li_sc; const double *own = nullptr;                  // every member's own order and robot position
+        hipLaunchKernelGGL(lidar::k_scene_fill_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const lidar::Fill *)F->d_li_fill);
+        hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, as, own);
+        hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, (unsigned)B), dim3(256), 0, F->stream, as, own);
+        hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, as, own);
+        hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), (unsigned)B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
+        HIPCHK(hipGetLastError());
+    }
+    if (n_boxes) for (size_t i = 0; i < B; ++i) n_boxes[i] = F->h_li_count[2 * i];
     return RDA_OK;
 }
 

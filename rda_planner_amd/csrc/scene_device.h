@@ -119,19 +119,27 @@ __global__ void k_build(Args a) { build_body(a, blockIdx.x * blockDim.x + thread
 // The same three kernels for a FLEET (rda_fleet_scene_resort, round 6): blockIdx.y = the member, its Args in a device array, its robot position in
 // rob [B][2] - one launch set re-sorts the resident scenes of all members about their robots (64 members x 4 launches on 64 streams cost the host
 // 4 ms per fleet tick; this is 4 launches).  Same device code per member: the slots come out bit-identical to rda_scene_resort on the member.
+// rob == null (rda_fleet_upload_scans: scenes staged for the first time): every member's Args are taken as they stand - its own `order`, the robot
+// position its raw scene holds.  A member with n = 0 has no scene: nothing of it is read or written (build_body would index sel[used - 1]).
 __device__ __forceinline__ Args fleet_args(const Args *as, const double *rob)
 {
     Args a = as[blockIdx.y];
-    a.order = 1; a.robot_val = 1; a.rx = rob[2 * blockIdx.y]; a.ry = rob[2 * blockIdx.y + 1];
+    if (rob) { a.order = 1; a.robot_val = 1; a.rx = rob[2 * blockIdx.y]; a.ry = rob[2 * blockIdx.y + 1]; }
     return a;
 }
 __global__ void k_keys_fleet(const Args *as, const double *rob)
 {
     const Args a = fleet_args(as, rob);
+    if (a.n <= 0) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.nonconvex = 0;        // (k_build, later in the stream, counts into it)
     keys_body(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
-__global__ void k_rank_fleet(const Args *as, const double *rob) { const Args a = fleet_args(as, rob); rank_body(a, blockIdx.x); }
-__global__ void k_build_fleet(const Args *as, const double *rob) { const Args a = fleet_args(as, rob); build_body(a, blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ void k_rank_fleet(const Args *as, const double *rob) { const Args a = fleet_args(as, rob); if (a.n <= 0) return; rank_body(a, blockIdx.x); }
+__global__ void k_build_fleet(const Args *as, const double *rob)
+{
+    const Args a = fleet_args(as, rob);
+    if (a.n <= 0) return;
+    build_body(a, blockIdx.x * blockDim.x + threadIdx.x);
+}
 
 }  // namespace scene

@@ -53,14 +53,29 @@ class Fleet:
         except Exception:
             pass
 
-    def control(self, states, ref_speeds, obstacle_lists, **kwargs):
+    def control(self, states, ref_speeds, obstacle_lists=None, scans=None, scan_eps=2.0, scan_min_samples=6, **kwargs):
         """one MPC step of every member: `states[i]`, `ref_speeds[i]` (a scalar is shared) and `obstacle_lists[i]` are
-        what `members[i].control` takes; returns the list of its `(u, info)` results."""
+        what `members[i].control` takes; returns the list of its `(u, info)` results.
+        scans: instead of obstacle lists, `scans[i]` is the range scan (the dict `MPC.control(scan=)` takes) member i took from
+        `states[i]` - all members' scans are clustered, boxed and staged on the device by one library call
+        (rda_fleet_upload_scans); result i is what `members[i].control(states[i], ref_speeds[i], scan=scans[i])` returns."""
         B, start = len(self.members), time.time()
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
+        if scans is not None:
+            if obstacle_lists is not None and any(len(ol) for ol in obstacle_lists):
+                raise ValueError("Fleet.control: pass either obstacle_lists or scans=, not both")
+            if len(scans) != B:
+                raise ValueError("Fleet.control: one scan per member")
+            if not getattr(self.api, "has_fleet_scans", False) or any(m.rda_obstacle for m in self.members):
+                raise RuntimeError("Fleet.control(scans=...) needs the fleet lidar front end (rda_fleet_upload_scans); there is no host fallback")
+            stage = lambda st: self.upload_scans(st, scans, scan_eps, scan_min_samples)      # noqa: E731
+        else:
+            if obstacle_lists is None:
+                obstacle_lists = [[] for _ in range(B)]
+            stage = None
         if hasattr(self.api.lib, "rda_fleet_step_tracked") and all(m._tracks(kwargs) for m in self.members):
-            return self._control_tracked(states, ref_speeds, obstacle_lists, start, **kwargs)
+            return self._control_tracked(states, ref_speeds, obstacle_lists, start, stage=stage, **kwargs)
         begun = []
         for i, m in enumerate(self.members):
             cur_ref_path, speed, nom_s, ref_list = m._begin(states[i], ref_speeds[i], **kwargs)
@@ -69,6 +84,9 @@ class Fleet:
             self._in_u[i] = f64(m.cur_vel_array, (2, T))
             self._ref[i] = np.hstack(ref_list)[0:3, :]
             self._speed[i] = speed
+            begun.append((cur_ref_path, ref_list))
+            if stage is not None:
+                continue
             obstacles = obstacle_lists[i]
             scene = None
             if not m.rda_obstacle and m.device_obstacles and m.rda.has_scene:
@@ -78,7 +96,8 @@ class Fleet:
             else:
                 rda_obs = obstacles if m.rda_obstacle else m.convert_rda_obstacle(obstacles, m.state, m.obstacle_order)
                 m.rda.upload_obstacles(rda_obs)
-            begun.append((cur_ref_path, ref_list))
+        if stage is not None:
+            stage(np.array([np.asarray(m.state, float).ravel()[0:3] for m in self.members]))
         rc = self.api.fleet_step(self._handle, dptr(self._in_s), dptr(self._in_u), dptr(self._ref), dptr(self._speed),
                                  dptr(self._out_u), dptr(self._out_s), self._info)
         if rc < 0:
@@ -117,7 +136,52 @@ class Fleet:
         self.batched_ticks += 1
         return True
 
-    def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10):
+    def _scan_arrays(self, states, scans):
+        """the member-major arrays of rda_fleet_scan_boxes / rda_fleet_upload_scans"""
+        B = len(self.members)
+        if len(scans) != B or len(states) != B:
+            raise ValueError("one state and one scan per member")
+        ranges = [f64(np.asarray(s["ranges"], float).ravel()) for s in scans]
+        n_beams = np.fromiter((r.size for r in ranges), np.int32, B)
+        allr = np.concatenate(ranges) if n_beams.sum() else np.zeros(1)
+        lo, hi, rmax = (f64([float(s[k]) for s in scans]) for k in ("angle_min", "angle_max", "range_max"))
+        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+        return n_beams, allr, lo, hi, rmax, st
+
+    def scan_boxes(self, states, scans, eps=2.0, min_samples=6):
+        """`RDA_solver.scan_boxes` for every member in one kernel launch: the list of (n_i, 4, 2) corner arrays"""
+        if not getattr(self.api, "has_fleet_scans", False):
+            raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_scan_boxes)")
+        n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
+        B, cap = len(self.members), max(1, int(n_beams.max()))
+        boxes, n = np.zeros((B, cap, 4, 2)), np.zeros(B, np.int32)
+        rc = self.api.fleet_scan_boxes(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
+                                       iptr(n), dptr(boxes), cap, None)
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_scan_boxes failed with code {rc}")
+        return [boxes[i, :n[i]].copy() for i in range(B)]
+
+    def upload_scans(self, states, scans, eps=2.0, min_samples=6):
+        """`RDA_solver.upload_scan` for every member (its own `obstacle_order`) in one library call; returns the box counts.
+        Until `sync` or the next `control` the members are not used on their own."""
+        if not getattr(self.api, "has_fleet_scans", False):
+            raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_upload_scans)")
+        n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
+        B = len(self.members)
+        order = np.fromiter((bool(m.obstacle_order) for m in self.members), np.int32, B)
+        n = np.zeros(B, np.int32)
+        rc = self.api.fleet_upload_scans(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
+                                         iptr(order), iptr(n))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_upload_scans failed with code {rc}")
+        return n
+
+    def sync(self):
+        rc = self.api.fleet_sync(self._handle)
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_sync failed with code {rc}")
+
+    def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
         """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the
         signed speed and the path index travel"""
         B, T = len(self.members), self.members[0].receding
@@ -131,7 +195,9 @@ class Fleet:
             cur[i] = m.cur_index
             resident = resident and m._nominal_u() is None
             pieces.append(cur_ref_path)
-        if not self._stage_all(obstacle_lists, st):
+        if stage is not None:
+            stage(st)
+        elif not self._stage_all(obstacle_lists, st):
             for i, m in enumerate(self.members):
                 m._stage_obstacles(obstacle_lists[i])
         nom_u = None

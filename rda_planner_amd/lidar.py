@@ -130,3 +130,10 @@ def scan_box_device(solver, state, scan_data, eps=2.0, min_samples=6):
     solver = getattr(solver, "rda", solver)
     boxes = solver.scan_boxes(state, scan_data, eps, min_samples)
     return [Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]
+
+
+def scan_box_device_fleet(fleet, states, scans, eps=2.0, min_samples=6):
+    """`scan_box_device` for every member of a `Fleet` in one kernel launch (rda_fleet_scan_boxes): `scans[i]` taken from
+    `states[i]`; the list of the members' obstacle lists"""
+    return [[Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]
+            for boxes in fleet.scan_boxes(states, scans, eps, min_samples)]

@@ -7,7 +7,13 @@
   2. the closed loop of examples/lidar_path_track_headless.py (tests/golden/world_lidar_track.yaml) driven three ways: host front end,
      `scan_box_device` + obstacle list, `MPC.control(scan=)`; at the world's own 100 beams and at --loop-beams.
 
+  3. --fleet B: a fleet of B planners that each carry a lidar.  Per tick, on the same members, in the same process, with the same scans:
+     (a) the loop of B `rda_upload_scan` calls followed by `rda_fleet_sync`, (b) ONE `rda_fleet_upload_scans` followed by `rda_fleet_sync`
+     (wall clock of the C calls, median over the ticks after a warm-up pass, --repeats times), at --fleet-beams; then a short
+     `Fleet.control(scans=)` closed loop in ego-steps/s.  With --fleet only this part runs.
+
     python tools/lidar_loop.py [--scans 50] [--repeats 3] [--steps 150] [--beams 100,360,1080,2048] [--loop-beams 1080]
+    python tools/lidar_loop.py --fleet 16,64 [--fleet-beams 360,1080] [--fleet-ticks 30] [--fleet-steps 40]
 """
 import argparse
 import os
@@ -147,6 +153,90 @@ def loops(args):
             print("%6d %-18s %6d %12.0f %28.3f" % (beams or 100, mode, n, rate, ms))
 
 
+def fleet_world(k, beams):
+    """member k's world: the robot near the head of the line path (0, 20) -> (60, 20), circles and boxes on both sides of the path ahead"""
+    rng = np.random.default_rng(7000 + k)
+    state = [1.0 + 0.05 * (k % 16), 20.0 + 0.05 * (k // 16), 0.01 * (k % 5)]
+    obstacles = []
+    for j in range(8):
+        pos = [7.0 + 4.0 * j + float(rng.uniform(-1, 1)), 20.0 + (4.5 if j % 2 else -4.5) + float(rng.uniform(-0.5, 0.5)), float(rng.uniform(-np.pi, np.pi))]
+        shape = {"name": "circle", "radius": 1.0} if j % 3 == 0 else {"name": "rectangle", "length": 2.5, "width": 1.2}
+        obstacles.append({"number": 1, "distribution": {"name": "manual"}, "state": [pos], "shape": [shape]})
+    cfg = {"world": {"step_time": 0.1},
+           "robot": [{"kinematics": {"name": "acker"}, "shape": {"name": "rectangle", "length": 4.6, "width": 1.6, "wheelbase": 3}, "state": state,
+                      "sensors": [{"type": "lidar2d", "range_max": 15.0, "angle_range": np.pi, "number": beams}]}],
+           "obstacle": obstacles}
+    return irsim.World(cfg)
+
+
+def fleet_part(args):
+    from rda_planner_amd.fleet import Fleet
+    fmt = lambda v: " ".join("%8.4f" % x for x in v)            # noqa: E731
+    print("fleet lidar: ms per fleet tick (all B scans staged and the fleet synchronised), median over %d ticks, %d repeats" % (args.fleet_ticks, args.repeats))
+    print("%4s %6s %6s | %-30s | %-30s | %s" % ("B", "beams", "boxes", "(a) B x rda_upload_scan + sync", "(b) rda_fleet_upload_scans + sync", "(a) / (b)"))
+    verdicts, cache = [], {}
+    for B in args.fleet:
+        memb = [MPC(sc.rectangle_robot(), sc.line_path([0, 20, 0], [60, 20, 0]), receding=10, max_edge_num=4, max_obs_num=5, iter_num=2) for _ in range(B)]
+        fleet = Fleet(memb)
+        api, fh = fleet.api, fleet._handle
+        handles = [m.rda._be.handle for m in memb]
+        for beams in args.fleet_beams:
+            if beams not in cache:                                  # per tick: 16 (state, scan) from random poses in random scenes
+                cache[beams] = [[random_scan(20000 + 97 * t + k, beams) for k in range(16)] for t in range(args.fleet_ticks)]
+            ticks = cache[beams]
+            packed = []
+            for items in ticks:
+                items = [items[i % len(items)] for i in range(B)]   # (B > 16: the scans repeat, the work per scan does not change)
+                rs = [np.ascontiguousarray(np.asarray(s["ranges"], float)) for _, s in items]
+                nb = np.full(B, beams, np.int32)
+                allr = np.ascontiguousarray(np.concatenate(rs))
+                lo, hi, rmax = (np.array([float(s[k]) for _, s in items]) for k in ("angle_min", "angle_max", "range_max"))
+                st = np.ascontiguousarray(np.array([x.ravel()[0:3] for x, _ in items]))
+                packed.append((rs, nb, allr, lo, hi, rmax, st))
+            order, n1, nB = np.ones(B, np.int32), np.zeros(1, np.int32), np.zeros(B, np.int32)
+
+            def looped(p):
+                rs, nb, allr, lo, hi, rmax, st = p
+                for i in range(B):
+                    rc = api.upload_scan(handles[i], beams, dptr(rs[i]), lo[i], hi[i], rmax[i], dptr(st[i]), 2.0, 6, 1, iptr(n1))
+                    assert rc == 0, rc
+                assert api.fleet_sync(fh) == 0                      # (a member's staging still queued on its own stream is waited for by its next scan)
+
+            def batched(p):
+                rs, nb, allr, lo, hi, rmax, st = p
+                rc = api.fleet_upload_scans(fh, iptr(nb), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), 2.0, 6, iptr(order), iptr(nB))
+                assert rc == 0, rc
+                assert api.fleet_sync(fh) == 0
+            t_a = median_ms(looped, packed, args.repeats)
+            t_b = median_ms(batched, packed, args.repeats)
+            print("%4d %6d %6.1f | %-30s | %-30s | %.1fx" % (B, beams, float(nB.mean()), fmt(t_a), fmt(t_b), np.median(t_a) / np.median(t_b)))
+            verdicts.append((B, beams, max(t_b) < min(t_a), min(t_a) / max(t_b)))
+        fleet.close()
+    for B, beams, faster, ratio in verdicts:
+        print("  B = %2d, %4d beams: one fleet call %s than the loop of solo calls in every repeat (fastest loop median vs slowest fleet median: %.1fx)"
+              % (B, beams, "FASTER" if faster else "NOT faster", ratio))
+    print("closed loop Fleet.control(scans=): every member in a world of its own (the ray casting and the plants run on the host and are not counted)")
+    print("%4s %6s %6s %14s %22s" % ("B", "beams", "ticks", "ego-steps/s", "Fleet.control ms/tick"))
+    for B in args.fleet:
+        for beams in args.fleet_beams:
+            envs = [fleet_world(k, beams) for k in range(B)]
+            memb = [MPC(sc.rectangle_robot(), sc.line_path([0, 20, 0], [60, 20, 0]), receding=10, max_edge_num=4, max_obs_num=5, iter_num=2) for _ in range(B)]
+            fleet = Fleet(memb)
+            per = []
+            for t in range(args.fleet_steps + 5):
+                states = [e.robot.state.copy() for e in envs]
+                scans = [e.get_lidar_scan() for e in envs]
+                t0 = time.perf_counter()
+                res = fleet.control(states, 4.0, scans=scans)
+                if t >= 5:                                          # (warm-up: first launches, allocations)
+                    per.append(time.perf_counter() - t0)
+                for e, (u, _) in zip(envs, res):
+                    e.step(u)
+            ms = 1e3 * float(np.median(per))
+            print("%4d %6d %6d %14.0f %22.3f" % (B, beams, len(per), B / (1e-3 * ms), ms))
+            fleet.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=50)
@@ -155,7 +245,15 @@ def main():
     ap.add_argument("--beams", type=lambda s: [int(x) for x in s.split(",")], default=[100, 360, 1080, 2048])
     ap.add_argument("--loop-beams", type=int, default=1080)
     ap.add_argument("--skip-loops", action="store_true")
+    ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
+    ap.add_argument("--fleet", type=ints, default=[], help="fleet sizes, e.g. 16,64: time the fleet lidar instead of parts 1 and 2")
+    ap.add_argument("--fleet-beams", type=ints, default=[360, 1080])
+    ap.add_argument("--fleet-ticks", type=int, default=30)
+    ap.add_argument("--fleet-steps", type=int, default=40)
     args = ap.parse_args()
+    if args.fleet:
+        assert args.fleet_ticks >= 8 and args.repeats >= 3
+        return fleet_part(args)
     assert args.scans >= 8
     front_end(args)
     if not args.skip_loops:
