@@ -368,6 +368,30 @@ int  rda_fleet_scan_boxes(rda_fleet *f, const int32_t *n_beams /*B*/, const doub
 int  rda_fleet_upload_scans(rda_fleet *f, const int32_t *n_beams, const double *ranges, const double *angle_min,
                             const double *angle_max, const double *range_max, const double *states /*B*3*/,
                             double eps, int min_samples, const int32_t *order /*B*/, int32_t *n_boxes /*B or NULL*/);
+/* Fleet rollout: K closed-loop ticks of every member queued back to back on the fleet's stream, ONE host wait - the loop a caller otherwise runs around
+ * rda_fleet_scene_resort + rda_fleet_step_tracked (tools/closed_loop_host.c closed_loop_fleet_run), with the host's part between two ticks done by a
+ * kernel: the member's first control is applied to its kinematic model (its own dynamics, dt, wheelbase; the expressions of that C loop, separately
+ * rounded), the new state and min_index become the next tick's tracker input and (resort != 0) re-sort position.  Arrival as in MPC.control
+ * (mpc.py:166-187): on the first tick k with min_index >= path length - goal_margin, arrived_at[i] = k and the applied control is zero on that tick and on
+ * every later one (the member keeps being stepped from its standing state: its solver state is then only good for rda_reset).
+ * states [B][3], ref_speed [B] (signed), cur_index [B], threshold, ind_range, nom_u: tick 0's inputs as in rda_fleet_step_tracked (nom_u NULL = the resident
+ * controls; later ticks always use them).  Logs, member-major per tick: states_log [K+1][B][3] (row 0 = states, row k+1 = after tick k), u_log [K][B][2] the
+ * applied controls, index_log [K][B] min_index, info_log [K][B] (may be NULL), arrived_at [B] (-1 = not arrived).  During a rollout the results stay in device
+ * memory whatever rda_opts::zero_copy says; given a state, a tick computes bit for bit what rda_fleet_scene_resort + rda_fleet_step_tracked compute.
+ * RDA_ERR_ARG: K < 1, K > 4096, a missing array, ind_range < 1, goal_margin < 1, a member without an uploaded path, with cur_index out of range, inside
+ * rda_tracked_begin, or (resort != 0) without a resident raw scene / with no staged obstacle.  RDA_ERR_UNSUPPORTED: a member with rda_opts::duals_follow or
+ * whose staged obstacles move (per-stage slots: such a scene has to be uploaded again every tick, as with rda_scene_resort).  A refused call queues nothing;
+ * a refused allocation: RDA_ERR_HIP, fleet and members as they were.  Afterwards the fleet and the members are as K host-driven ticks leave them: an
+ * ordinary rda_fleet_step_tracked from states_log[K] continues the loop. */
+int  rda_fleet_rollout(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                       const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin, int resort,
+                       const double *nom_u /*B*2*T or NULL = resident*/,
+                       double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                       rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/);
+/* of the last tick of the last rda_fleet_rollout, what rda_fleet_step_tracked returns besides the logged values: every member's full controls out_u (the
+ * resident nominal controls of its next tick) and end_heading (the heading of the last waypoint of the member's device path, quirk Q12) - for a caller that
+ * mirrors the members on the host, like Fleet.rollout.  No device work.  RDA_ERR_ARG before the first rollout. */
+int  rda_fleet_rollout_last(rda_fleet *f, double *out_u /*B*2*T or NULL*/, double *end_heading /*B or NULL*/);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */
 int  rda_fleet_enqueue_range(rda_fleet *f, int k0, int k1);
 int  rda_fleet_sync(rda_fleet *f);

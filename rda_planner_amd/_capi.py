@@ -183,6 +183,13 @@ class CApi:
                 f("fleet_upload_scans").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
                                                     c_int_p, c_int_p]
                 f("fleet_scan_boxes").restype = f("fleet_upload_scans").restype = C.c_int
+            # fleet rollout: K closed-loop ticks on the device, one host wait
+            self.has_fleet_rollout = hasattr(lib, f"{prefix}_fleet_rollout")
+            if self.has_fleet_rollout:
+                f("fleet_rollout").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, C.c_int, c_double_p,
+                                               c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p]
+                f("fleet_rollout_last").argtypes = [C.c_void_p, c_double_p, c_double_p]
+                f("fleet_rollout").restype = f("fleet_rollout_last").restype = C.c_int
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

@@ -33,6 +33,7 @@
 #include "scene_device.h"
 #include "lidar_device.h"
 #include "track_device.h"
+#include "rollout_device.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
     fprintf(stderr, "librda_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return RDA_ERR_HIP; } } while (0)
@@ -2921,9 +2922,42 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     // itself: the concatenated ranges [B * MAXB], the counters [B][2] - and, for rda_fleet_scan_boxes alone, the host's copy of labels and boxes
     lidar::Args *h_li_args, *d_li_args; lidar::Fill *h_li_fill, *d_li_fill; scene::Args *h_li_sc, *d_li_sc;
     double *d_li_boxes, *h_li_ranges, *h_li_boxes; int *h_li_count, *h_li_labels;
+    // rda_fleet_rollout (allocated on first use): the advance kernel's member table, the io tables of tick 0 | of the later ticks [2][B] (results in d_out
+    // whatever the members' zero_copy says); the log block of roll_cap ticks (roll_layout) on the device and in pinned memory, regrown for a longer rollout
+    rollout::Member *h_ro_m, *d_ro_m; EgoIO *h_io_roll, *d_io_roll; char *h_ro_log, *d_ro_log; int roll_cap, roll_K;
     hbuf::Group mem, trk, resort, lidar, lidar_host;      // the tables above; those of tracked stepping; of rda_fleet_scene_resort; of the fleet lidar (scan, staging | host copies)
+    hbuf::Group roll, roll_log;                           // of rda_fleet_rollout: tables | logs
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
+};
+
+// The tables a fleet makes on first use: built beside the fleet (alloc: zeroed, all or RDA_ERR_HIP) and moved in only when the call that needs them can no
+// longer be refused (commit) - a refused allocation leaves the fleet as it was.
+struct FleetTrackTables {                 // rda_fleet_step_tracked, rda_fleet_rollout
+    hbuf::Group g; track::In *hti, *dti; track::Out *hto, *dto; double **hp, **dp; int *hl, *dl; EgoIO *hio, *dio;
+    int alloc(size_t B)
+    {
+        int rc = 0;
+        rc |= g.dev(&dti, B); rc |= g.dev(&dto, B); rc |= g.dev(&dp, B); rc |= g.dev(&dl, B); rc |= g.dev(&dio, B);
+        rc |= g.pin(&hti, B); rc |= g.pin(&hto, B); rc |= g.pin(&hp, B); rc |= g.pin(&hl, B); rc |= g.pin(&hio, B);
+        return rc ? RDA_ERR_HIP : RDA_OK;
+    }
+    void commit(rda_fleet *F)
+    {
+        F->trk = std::move(g);
+        F->d_trk_in = dti; F->d_trk_out = dto; F->d_paths = dp; F->d_lens = dl; F->d_io_track = dio;
+        F->h_trk_in = hti; F->h_trk_out = hto; F->h_paths = hp; F->h_lens = hl; F->h_io_track = hio;
+    }
+};
+struct FleetResortTables {                // rda_fleet_scene_resort, rda_fleet_rollout
+    hbuf::Group g; scene::Args *hsc, *dsc; double *hrob, *drob;
+    int alloc(size_t B)
+    {
+        int rc = 0;
+        rc |= g.dev(&dsc, B); rc |= g.dev(&drob, 2 * B); rc |= g.pin(&hsc, B); rc |= g.pin(&hrob, 2 * B);
+        return rc ? RDA_ERR_HIP : RDA_OK;
+    }
+    void commit(rda_fleet *F) { F->resort = std::move(g); F->d_sc = dsc; F->d_rob = drob; F->h_sc = hsc; F->h_rob = hrob; }
 };
 
 // Member i's locations on the step path: its step block in d_in (in_u: nominal controls that live elsewhere, else null), its u | s block
@@ -3107,25 +3141,11 @@ extern "C" int rda_fleet_upload_scenes(rda_fleet *F, const int32_t *counts, cons
 // states[i * stride + 0..1] and their slots rebuilt on the fleet's stream; the next fleet step runs behind it.  Same device code per member as
 // rda_scene_resort: bit-identical slots.  Members with rda_opts::duals_follow, without a resident scene, or inside a tick: RDA_ERR_UNSUPPORTED / _ARG.
 static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from d_rob)
-extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
+// the members' scene arguments (uploaded when they changed) and their robots' positions -> d_sc, d_rob; nmax, wmax: what sizes the launches
+static int fleet_resort_positions(rda_fleet *F, const double *states, int stride, int &nmax, int &wmax)
 {
-    if (!F || !states || stride < 2) return RDA_ERR_ARG;
     const size_t B = F->B;
-    for (rda_handle *H : F->egos) {
-        if (H->sc_n <= 0 || H->d.obstacle_num == 0 || H->pending) return RDA_ERR_ARG;
-        if (H->follow) return RDA_ERR_UNSUPPORTED;
-    }
-    if (!F->d_sc) {                                     // first use: the tables (zeroed) take their place once all of them exist
-        hbuf::Group g; scene::Args *hsc, *dsc; double *hrob, *drob;
-        int rc = 0;
-        rc |= g.dev(&dsc, B); rc |= g.dev(&drob, 2 * B); rc |= g.pin(&hsc, B); rc |= g.pin(&hrob, 2 * B);
-        if (rc) return RDA_ERR_HIP;
-        F->resort = std::move(g); F->d_sc = dsc; F->d_rob = drob; F->h_sc = hsc; F->h_rob = hrob;
-    }
-    int rc = fleet_refresh(F);
-    if (rc != RDA_OK) return rc;
     bool changed = false;
-    int nmax = 0, wmax = 0;
     for (size_t i = 0; i < B; ++i) {
         const scene::Args a = fleet_resort_args(F->egos[i]);
         if (memcmp(&a, &F->h_sc[i], sizeof(scene::Args)) != 0) changed = true;
@@ -3139,10 +3159,36 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
     for (size_t i = 0; i < B; ++i) { F->h_rob[2 * i] = states[i * stride]; F->h_rob[2 * i + 1] = states[i * stride + 1]; }
     HIPCHK(hipMemcpyAsync(F->d_rob, F->h_rob, 2 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
     F->rob_pending = 1;
-    hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
-    hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, (unsigned)B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
-    hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
-    hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), (unsigned)B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
+    return RDA_OK;
+}
+// the four launches of a re-sort about the positions in d_rob
+static void fleet_resort_launch(rda_fleet *F, int nmax, int wmax)
+{
+    const unsigned B = (unsigned)F->B;
+    hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
+    hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
+    hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
+    hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
+}
+extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
+{
+    if (!F || !states || stride < 2) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    for (rda_handle *H : F->egos) {
+        if (H->sc_n <= 0 || H->d.obstacle_num == 0 || H->pending) return RDA_ERR_ARG;
+        if (H->follow) return RDA_ERR_UNSUPPORTED;
+    }
+    if (!F->d_sc) {                                     // first use: the tables (zeroed) take their place once all of them exist
+        FleetResortTables t;
+        if (t.alloc(B)) return RDA_ERR_HIP;
+        t.commit(F);
+    }
+    int rc = fleet_refresh(F);
+    if (rc != RDA_OK) return rc;
+    int nmax = 0, wmax = 0;
+    rc = fleet_resort_positions(F, states, stride, nmax, wmax);
+    if (rc != RDA_OK) return rc;
+    fleet_resort_launch(F, nmax, wmax);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
@@ -3304,14 +3350,9 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
     if (!F || !states || !ref_speed || !cur_index || !out_u || !out_s || ind_range < 1) return RDA_ERR_ARG;
     const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), nout = res_info(T), B = F->B;
     if (!F->d_trk_in) {                                 // first use: the tables (zeroed) take their place once all of them exist
-        hbuf::Group g; track::In *hti, *dti; track::Out *hto, *dto; double **hp, **dp; int *hl, *dl; EgoIO *hio, *dio;
-        int rc = 0;
-        rc |= g.dev(&dti, B); rc |= g.dev(&dto, B); rc |= g.dev(&dp, B); rc |= g.dev(&dl, B); rc |= g.dev(&dio, B);
-        rc |= g.pin(&hti, B); rc |= g.pin(&hto, B); rc |= g.pin(&hp, B); rc |= g.pin(&hl, B); rc |= g.pin(&hio, B);
-        if (rc) return RDA_ERR_HIP;
-        F->trk = std::move(g);
-        F->d_trk_in = dti; F->d_trk_out = dto; F->d_paths = dp; F->d_lens = dl; F->d_io_track = dio;
-        F->h_trk_in = hti; F->h_trk_out = hto; F->h_paths = hp; F->h_lens = hl; F->h_io_track = hio;
+        FleetTrackTables t;
+        if (t.alloc(B)) return RDA_ERR_HIP;
+        t.commit(F);
     }
     // the result of the tick is written where the host reads it (round 6): k_finish_fleet and k_track_fleet store straight into the pinned blocks (write-only,
     // fire-and-forget stores over the link, complete at the end of their kernels) instead of three device-to-host copies queued behind the last launch
@@ -3367,6 +3408,131 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
         if (min_index) min_index[i] = F->h_trk_out[i].min_index;
         if (end_heading) end_heading[i] = F->h_trk_out[i].end_heading;
     }
+    return RDA_OK;
+}
+
+// ---- rda_fleet_rollout: K closed-loop ticks queued back to back, ONE host wait ---------------------------------------------------------------------
+// Per tick the launches of the host loop (closed_loop_fleet_run: re-sort, k_track_fleet, the ADMM launches) and rollout::k_rollout_advance, which does on
+// the device what that loop's host does between two ticks and writes the next tick's inputs where these kernels read them.
+struct RollLayout { size_t states, u, endh, lastu, info, index, arrived, bytes; };     // byte offsets of the log block's parts (rollout::Logs; lastu [B][2][T]: the last tick's controls)
+static RollLayout roll_layout(size_t K, size_t B, size_t T)
+{
+    RollLayout l;
+    l.states = 0; l.u = l.states + (K + 1) * B * 3 * sizeof(double); l.endh = l.u + K * B * 2 * sizeof(double); l.lastu = l.endh + B * sizeof(double);
+    l.info = l.lastu + B * traj_u(T) * sizeof(double);
+    l.index = l.info + K * B * sizeof(rda_info); l.arrived = l.index + K * B * sizeof(int); l.bytes = l.arrived + B * sizeof(int);
+    return l;
+}
+extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                 int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
+                                 rda_info *info_log, int32_t *arrived_at)
+{
+    if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
+    if (ind_range < 1 || goal_margin < 1) return RDA_ERR_ARG;
+    const size_t T = F->T, nu = traj_u(T), nin = step_doubles(T), B = F->B;
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
+        if (resort && (H->sc_n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
+    }
+    for (const rda_handle *H : F->egos) {
+        if (H->follow) return RDA_ERR_UNSUPPORTED;                              // (k_follow_* are per member)
+        if (H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
+    }
+    // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
+    FleetTrackTables ttrk; FleetResortTables tres;
+    hbuf::Group gtab, glog; rollout::Member *hm = nullptr, *dm = nullptr; EgoIO *hio = nullptr, *dio = nullptr; char *hlog = nullptr, *dlog = nullptr;
+    const bool need_trk = !F->d_trk_in, need_res = resort && !F->d_sc, need_tab = !F->d_ro_m, need_log = !F->d_ro_log || K > F->roll_cap;
+    {
+        int rc = 0;
+        if (need_trk) rc |= ttrk.alloc(B);
+        if (need_res) rc |= tres.alloc(B);
+        if (need_tab) { rc |= gtab.dev(&dm, B); rc |= gtab.dev(&dio, 2 * B); rc |= gtab.pin(&hm, B); rc |= gtab.pin(&hio, 2 * B); }
+        if (need_log) { const size_t nb = roll_layout((size_t)K, B, T).bytes; rc |= glog.dev(&dlog, nb); rc |= glog.pin(&hlog, nb); }
+        if (rc) return RDA_ERR_HIP;
+    }
+    if (need_log) HIPCHK(hipStreamSynchronize(F->stream));                      // (a shorter block is freed below)
+    if (need_trk) ttrk.commit(F);
+    if (need_res) tres.commit(F);
+    if (need_tab) { F->roll = std::move(gtab); F->d_ro_m = dm; F->d_io_roll = dio; F->h_ro_m = hm; F->h_io_roll = hio; }
+    if (need_log) { F->roll_log = std::move(glog); F->d_ro_log = dlog; F->h_ro_log = hlog; F->roll_cap = K; }
+    F->roll_K = 0;                                                              // (until this rollout's logs are on the host)
+    int rc = fleet_refresh(F);
+    if (rc != RDA_OK) return rc;
+    // one-time table refreshes (the only other waits of a rollout): the tables are compared with what the device holds and uploaded when they differ
+    bool tables = false;
+    std::vector<rollout::Member> wm(B); std::vector<EgoIO> wio(2 * B);
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        wio[i] = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, F->d_out, F->d_info);          // tick 0
+        wio[B + i] = fleet_member_io(F, i, H->d.u, F->d_out, F->d_info);                         // later ticks: the resident controls
+        rollout::Member &m = wm[i];
+        memset((void *)&m, 0, sizeof(m));
+        m.out_u = wio[i].out_u; m.info = wio[i].info; m.T = (int)T; m.L = H->path_len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
+        if (F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
+    }
+    if (memcmp(wm.data(), F->h_ro_m, B * sizeof(rollout::Member)) != 0 || memcmp(wio.data(), F->h_io_roll, 2 * B * sizeof(EgoIO)) != 0) tables = true;
+    if (tables) {
+        HIPCHK(hipStreamSynchronize(F->stream));
+        memcpy((void *)F->h_ro_m, wm.data(), B * sizeof(rollout::Member)); memcpy((void *)F->h_io_roll, wio.data(), 2 * B * sizeof(EgoIO));
+        for (size_t i = 0; i < B; ++i) { F->h_paths[i] = F->egos[i]->d_path; F->h_lens[i] = F->egos[i]->path_len; }
+        HIPCHK(hipMemcpyAsync(F->d_ro_m, F->h_ro_m, B * sizeof(rollout::Member), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(hipMemcpyAsync(F->d_io_roll, F->h_io_roll, 2 * B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(hipMemcpyAsync(F->d_paths, F->h_paths, B * sizeof(double *), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
+    }
+    // tick 0's inputs, as rda_fleet_scene_resort and rda_fleet_step_tracked upload them
+    int nmax = 0, wmax = 0;
+    if (resort) { rc = fleet_resort_positions(F, states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
+    if (nom_u) {
+        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
+        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
+                                hipMemcpyHostToDevice, F->stream));
+    }
+    for (size_t i = 0; i < B; ++i) {
+        track::In &in = F->h_trk_in[i];
+        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
+        in.cur_index = cur_index[i]; in.ind_range = ind_range;
+    }
+    HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
+    const RollLayout lay = roll_layout((size_t)K, B, T);
+    rollout::Logs lg;
+    lg.states = (double *)(F->d_ro_log + lay.states); lg.u = (double *)(F->d_ro_log + lay.u); lg.end_heading = (double *)(F->d_ro_log + lay.endh);
+    lg.info = (rda_info *)(F->d_ro_log + lay.info); lg.index = (int *)(F->d_ro_log + lay.index); lg.arrived_at = (int *)(F->d_ro_log + lay.arrived);
+    HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, B * sizeof(int), F->stream));    // -1: not arrived
+    for (int k = 0; k < K; ++k) {
+        if (resort) fleet_resort_launch(F, nmax, wmax);                          // about d_rob: the caller's positions (tick 0), then the advance kernel's
+        const EgoIO *io = F->d_io_roll + (k == 0 ? 0 : B);
+        hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, io, F->d_trk_in, F->d_paths, F->d_lens, F->d_trk_out, (int)B);
+        rc = fleet_enqueue(F, io, 0);
+        if (rc != RDA_OK) return rc;
+        hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->d_ro_m,
+                           (const track::Out *)F->d_trk_out, F->d_trk_in, resort ? F->d_rob : nullptr, lg, k, goal_margin, (int)B);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy2DAsync(F->d_ro_log + lay.lastu, nu * sizeof(double), F->d_out, res_info(T) * sizeof(double), nu * sizeof(double), B,
+                            hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
+    HIPCHK(hipMemcpyAsync(F->h_ro_log, F->d_ro_log, lay.bytes, hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));                                    // the rollout's one wait
+    F->rob_pending = 0;
+    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;                       // their staged scenes have been consumed
+    F->roll_K = K;
+    memcpy(states_log, states, B * 3 * sizeof(double));                         // row 0: the input
+    memcpy(states_log + B * 3, F->h_ro_log + lay.states + B * 3 * sizeof(double), (size_t)K * B * 3 * sizeof(double));
+    memcpy(u_log, F->h_ro_log + lay.u, (size_t)K * B * 2 * sizeof(double));
+    memcpy(index_log, F->h_ro_log + lay.index, (size_t)K * B * sizeof(int32_t));
+    if (info_log) memcpy(info_log, F->h_ro_log + lay.info, (size_t)K * B * sizeof(rda_info));
+    memcpy(arrived_at, F->h_ro_log + lay.arrived, B * sizeof(int32_t));
+    return RDA_OK;
+}
+// What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls
+// of its next tick) and track::Out::end_heading (quirk Q12: what the heading of its path's last waypoint is now).  Either may be null.
+extern "C" int rda_fleet_rollout_last(rda_fleet *F, double *out_u, double *end_heading)
+{
+    if (!F || F->roll_K < 1) return RDA_ERR_ARG;
+    const RollLayout lay = roll_layout((size_t)F->roll_K, (size_t)F->B, (size_t)F->T);
+    if (out_u) memcpy(out_u, F->h_ro_log + lay.lastu, (size_t)F->B * traj_u(F->T) * sizeof(double));
+    if (end_heading) memcpy(end_heading, F->h_ro_log + lay.endh, (size_t)F->B * sizeof(double));
     return RDA_OK;
 }
 

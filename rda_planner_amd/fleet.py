@@ -181,6 +181,64 @@ class Fleet:
         if rc < 0:
             raise RuntimeError(f"rda_fleet_sync failed with code {rc}")
 
+    def rollout(self, states, ref_speeds, steps, resort=True, **kwargs):
+        """`steps` closed-loop ticks of every member on the device with ONE host wait (rda_fleet_rollout): per tick what `control` does with the
+        obstacles the members have staged (scenes that do not move; resort: re-sorted about every robot on every tick like `obstacle_order=True`),
+        then every member's first control applied to its kinematic model and `MPC.control`'s arrival rule (`goal_index_threshold`; zero control from
+        the arrival tick on).  kwargs: `threshold`, `ind_range` of `closest_point`.  Returns a dict: `states` (steps+1, B, 3) with row 0 the input,
+        `controls` (steps, B, 2) as applied, `index` and `iters` (steps, B), `arrived_at` (B,) the arrival tick or -1.  Afterwards every member's
+        `state`, `cur_index` and nominal controls are those of the last tick, so `control` continues the loop; the solver state of a member that has
+        arrived (it keeps being stepped where it stands) is only good for `reset`."""
+        ms = self.members
+        if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
+            raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
+        if not getattr(self.api, "has_fleet_rollout", False):
+            raise RuntimeError("the loaded solver library has no fleet rollout entry point (rda_fleet_rollout)")
+        margins = {int(m.goal_index_threshold) for m in ms}
+        if len(margins) != 1:
+            raise ValueError("Fleet.rollout: the members must share one goal_index_threshold")
+        B, T, K = len(ms), ms[0].receding, int(steps)
+        if np.isscalar(ref_speeds):
+            ref_speeds = [ref_speeds] * B
+        st, cur, speed = np.zeros((B, 3)), np.zeros(B, np.int32), np.zeros(B)
+        resident = True
+        for i, m in enumerate(ms):
+            cur_ref_path, gear = m._piece(states[i])
+            m._sync_path(cur_ref_path)
+            st[i] = np.asarray(m.state, float).ravel()[0:3]
+            speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
+            resident = resident and m._nominal_u() is None
+        nom_u = None
+        if not resident:            # some member's cur_vel_array was replaced since its last solve: send them all
+            for i, m in enumerate(ms):
+                self._in_u[i] = f64(m.cur_vel_array, (2, T))
+            nom_u = self._in_u
+        s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
+        i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
+        infos = (Info * (max(K, 1) * B))()
+        rc = self.api.fleet_rollout(self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)),
+                                    margins.pop(), 1 if resort else 0, dptr(nom_u), dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_rollout failed with code {rc}")
+        eh = np.zeros(B)
+        rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_rollout_last failed with code {rc}")
+        for i, m in enumerate(ms):
+            path = m.ref_path
+            m.state = s_log[K, i].reshape(3, 1).copy()
+            m.cur_index = int(i_log[K - 1, i])
+            path[-1][2, 0] = eh[i]                         # quirk Q12: the device rewrote the last waypoint's heading in its copy
+            if m._dev_path_key is not None and m._dev_path_key[0] is path:
+                m._dev_path_key[1][-1] = path[-1].tobytes()
+            if arrived[i] >= 0:                            # like _end: the robot stands, the next solve starts from zero controls
+                m.cur_vel_array = np.zeros((2, T))
+                m._dev_u = None
+            else:                                          # the device holds the controls of the last solve
+                m.cur_vel_array = m._dev_u = self._out_u[i].copy()
+        iters = np.array([infos[j].iters for j in range(K * B)], np.int32).reshape(K, B)
+        return {"states": s_log, "controls": u_log, "index": i_log, "iters": iters, "arrived_at": arrived}
+
     def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
         """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the
         signed speed and the path index travel"""

@@ -1,0 +1,155 @@
+"""Fleet closed loop: the host-driven loop against the device rollout, in ego-steps/s.
+
+  (a) host loop  tools/closed_loop_host.c closed_loop_fleet_run, resort = 2: per fleet tick rda_fleet_scene_resort + ONE rda_fleet_step_tracked + one host
+                 wait + every member's kinematics on the host
+  (b) rollout    ONE rda_fleet_rollout of K ticks: the same launches per tick plus rollout::k_rollout_advance, one host wait after the K ticks
+
+on the same members: BASELINE config C5 (T = 25, N = 100 polygons per ego, every ego its own seeded scene, re-sorted about its robot on every tick, the
+members of bench.py's `c_abi_closed_loop` leg), B = 16 and 64.  A measurement: --warm host-driven ticks, then TWO windows of K = 100 ticks by the leg's own
+method - the first one warms what the method uses (the rollout's tables and log block are made on first use), the second one is the figure.  Every
+measurement runs in a process of its own (fresh handles); the legs are interleaved (a b a b a b), medians over --repeats.  --baseline-so: another build of librda_hip.so for leg (a) - the
+parent commit's, so that the host loop is timed on the code it had before the rollout existed.
+
+    python tools/fleet_rollout.py [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6] [--baseline-so PATH]
+
+One measurement alone (what a kernel trace is taken of: the launches per tick are those of the host loop plus k_rollout_advance):
+    python tools/fleet_rollout.py --leg rollout --B 16        (or --leg host)
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+T, N = 25, 100
+
+
+def members(api, B, n_steps):
+    """B fresh solvers of the C5 shape with their paths and raw scenes resident, and their fleet"""
+    from benchlib.workload import build_workload
+    from rda_planner_amd._capi import dptr, iptr
+    from rda_planner_amd.rda_solver import RDA_solver
+    svs, states, plen = [], np.zeros((B, 3)), np.zeros(B, np.int32)
+    for e in range(B):
+        car_t, path, obstacles, kw = build_workload(seed_offset=e, n_obs=N, T=T, n_steps=n_steps + 10)
+        sv = RDA_solver(T, car_t, kw["max_edge_num"], N, iter_num=kw["iter_num"], step_time=0.1, time_print=False, ro1=kw["ro1"])
+        n_sc, kind, nvert, geom, vel = sv.flatten_scene(list(obstacles))
+        kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
+        geom, vel = np.ascontiguousarray(geom, float), np.ascontiguousarray(vel, float)
+        P = np.ascontiguousarray(np.hstack(path)[0:3, :].T, dtype=float)
+        states[e] = np.ascontiguousarray(path[0], float).ravel()[0:3]
+        plen[e] = P.shape[0]
+        assert api.upload_path(sv._be.handle, int(P.shape[0]), dptr(P)) == 0
+        assert api.upload_scene(sv._be.handle, int(n_sc), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(states[e]), 1, None) == 0
+        svs.append(sv)
+    arr = (C.c_void_p * B)(*[sv._be.handle for sv in svs])
+    F = C.c_void_p()
+    assert api.fleet_create(arr, B, C.byref(F)) == 0
+    return svs, arr, F, np.ascontiguousarray(states), plen, car_t
+
+
+def leg(name, B, K, warm):
+    """one measurement in this process: `warm` host-driven ticks, then K timed ticks by the host loop or by the rollout -> dict"""
+    from rda_planner_amd._capi import Info, dptr, iptr
+    from rda_planner_amd._lib import hip_api
+    import closed_loop_host as clh
+    api = hip_api()
+    host = clh.Host(api.lib)
+    n_all = warm + 2 * K
+    svs, arr, F, states, plen, car_t = members(api, B, n_all)
+    cur, nom0 = np.zeros(B, np.int32), np.zeros((B, 2, T))
+    u_log, t_log = np.zeros((n_all, B, 2)), np.zeros(n_all)
+    it_log, ipm_log = np.zeros((n_all, B), np.int32), np.zeros((n_all, B), np.int32)
+
+    def host_ticks(k0, n):
+        rc = host.fleet_run(C.byref(host.fleet_api), F, arr, B, T, 0, float(car_t.wheelbase), 0.1, 4.0, 0.1, 10, iptr(plen), 2, k0, n, dptr(nom0), dptr(states),
+                            iptr(cur), dptr(u_log[k0:]), dptr(t_log[k0:]), iptr(it_log[k0:]), iptr(ipm_log[k0:]))
+        assert rc == 0, rc
+    host_ticks(0, warm)
+    els = []
+    for win in range(2):
+        k0 = warm + win * K
+        t0 = time.perf_counter()
+        if name == "host":
+            host_ticks(k0, K)
+            els.append(time.perf_counter() - t0)
+            u, iters = u_log[k0:k0 + K], it_log[k0:k0 + K]
+        else:
+            s_log, u, i_log = np.zeros((K + 1, B, 3)), np.zeros((K, B, 2)), np.zeros((K, B), np.int32)
+            infos, arrived = (Info * (K * B))(), np.zeros(B, np.int32)
+            rc = api.fleet_rollout(F, K, dptr(states), dptr(np.full(B, 4.0)), iptr(cur), 0.1, 10, 1, 1, None, dptr(s_log), dptr(u), iptr(i_log), infos,
+                                   iptr(arrived))
+            els.append(time.perf_counter() - t0)
+            assert rc == 0, rc
+            assert np.all(arrived == -1)
+            states, cur = np.ascontiguousarray(s_log[K]), np.ascontiguousarray(i_log[K - 1])
+            iters = np.array([i.iters for i in infos]).reshape(K, B)
+    el = els[1]
+    out = {"leg": name, "B": B, "K": K, "ego_steps_per_s": B * K / el, "ms_per_tick": 1e3 * el / K, "first_window_ego_steps_per_s": B * K / els[0],
+           "mean_admm_iters": float(iters.mean()), "u_last": [float(x) for x in u[-1, 0]]}
+    api.fleet_destroy(F)
+    return out
+
+
+def child(name, B, args):
+    env = dict(os.environ)
+    if name == "host" and args.baseline_so:
+        env["RDA_HIP_SO"] = os.path.abspath(args.baseline_so)
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--B", str(B), "--K", str(args.K), "--warm", str(args.warm)]
+    res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.leg_timeout)
+    if res.returncode != 0:
+        raise RuntimeError(f"leg {name} B={B} ended with {res.returncode}: {res.stderr[-400:]}")
+    return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
+    ap.add_argument("--fleets", type=ints, default=[16, 64])
+    ap.add_argument("--K", type=int, default=100)
+    ap.add_argument("--warm", type=int, default=6)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--baseline-so", default=None)
+    ap.add_argument("--leg-timeout", type=float, default=300.0)
+    ap.add_argument("--leg", choices=["host", "rollout"], default=None, help="(internal) run one measurement in this process and print it as JSON")
+    ap.add_argument("--B", type=int, default=16)
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    if args.leg:
+        print(json.dumps(leg(args.leg, args.B, args.K, args.warm)))
+        return
+    assert args.repeats >= 3
+    print("fleet closed loop, C5 shape (T = %d, N = %d, own seeded scene per ego, re-sorted every tick): %d host-driven ticks, a first window of K = %d ticks, then the "
+          "timed window of K ticks; %d interleaved repeats" % (T, N, args.warm, args.K, args.repeats))
+    print("host loop: closed_loop_fleet_run (resort = 2) on %s" % ("the baseline library (the parent commit's build)" if args.baseline_so else "this library"))
+    print("%4s | %-40s | %-40s | %s" % ("B", "(a) host loop ego-steps/s", "(b) rda_fleet_rollout ego-steps/s", "median (b) / (a)"))
+    verdicts = []
+    for B in args.fleets:
+        a, b = [], []
+        for _ in range(args.repeats):
+            a.append(child("host", B, args))
+            b.append(child("rollout", B, args))
+        ra, rb = [x["ego_steps_per_s"] for x in a], [x["ego_steps_per_s"] for x in b]
+        fmt = lambda v: " ".join("%9.0f" % x for x in v)        # noqa: E731
+        print("%4d | %-40s | %-40s | %.2fx" % (B, fmt(ra), fmt(rb), np.median(rb) / np.median(ra)))
+        print("       ms per fleet tick (medians): host %.3f, rollout %.3f; mean ADMM iterations per ego-step: host %.3f, rollout %.3f"
+              % (np.median([x["ms_per_tick"] for x in a]), np.median([x["ms_per_tick"] for x in b]), a[0]["mean_admm_iters"], b[0]["mean_admm_iters"]))
+        print("       first window (one-time set-up included), medians: host %.0f, rollout %.0f ego-steps/s"
+              % (np.median([x["first_window_ego_steps_per_s"] for x in a]), np.median([x["first_window_ego_steps_per_s"] for x in b])))
+        print("       last applied control of ego 0: host %s, rollout %s (the two loops differ in the last bits of sin / cos / tan of the plant step)"
+              % (a[0]["u_last"], b[0]["u_last"]))
+        spread = max(ra) - min(ra)
+        verdicts.append((B, np.median(rb) >= np.median(ra) - spread, np.median(ra), np.median(rb), spread))
+    for B, ok, ma, mb, spread in verdicts:
+        print("  B = %2d: rollout median %.0f vs host-loop median %.0f ego-steps/s (host loop's own spread over the repeats: %.0f) - %s"
+              % (B, mb, ma, spread, "not slower than the host loop" if ok else "SLOWER than the host loop by more than its spread"))
+
+
+if __name__ == "__main__":
+    main()
