@@ -221,6 +221,8 @@ int  rda_step_scene(rda_handle *h, const double *nom_s, const double *nom_u, con
                     const double *robot_xy, int order, double *out_u, double *out_s, rda_info *info);
 /* test hook: staged slots A [N][nt][E][2], b [N][nt][E], cone [N]; *nt = 1 or T+1 (buffers sized for T+1) */
 int  rda_get_obstacles(rda_handle *h, double *A, double *b, int32_t *cone, int32_t *nt);
+/* test hook: the resident raw geometry [n][E][2] of the device pipeline as it stands (rda_fleet_rollout_moving advances it on the device); *n = 0: none */
+int  rda_debug_scene_geom(rda_handle *h, double *geom /*n*E*2*/, int32_t *n);
 
 /* Device-resident pipeline (what bench.py times): obstacles and a trace of K step inputs are
  * uploaded once; rda_enqueue_step queues the whole ADMM loop of step k on the handle's stream
@@ -392,6 +394,29 @@ int  rda_fleet_rollout(rda_fleet *f, int K, const double *states /*B*3*/, const 
  * resident nominal controls of its next tick) and end_heading (the heading of the last waypoint of the member's device path, quirk Q12) - for a caller that
  * mirrors the members on the host, like Fleet.rollout.  No device work.  RDA_ERR_ARG before the first rollout. */
 int  rda_fleet_rollout_last(rda_fleet *f, double *out_u /*B*2*T or NULL*/, double *end_heading /*B or NULL*/);
+/* The rollout for scenes that MOVE between ticks (BASELINE config C4, the reference's dynamic_obs loop): rda_fleet_rollout's arguments, logs, arrival rule
+ * and refusals, but members whose staged obstacles move (per-stage slots) are taken, and members with static scenes may be mixed in.  `base` is every
+ * member's resident raw geometry as the call finds it (snapshot on the device); at tick k of the call the resident geometry is base + vel * (dt * k) - one
+ * product dt * k, one product, one sum, each rounded separately; polygons: their nvert vertices; circles: the centre, never the radius - and the tick's
+ * per-stage slots are rebuilt from it by the launches of rda_fleet_scene_resort.  Every obstacle with a velocity moves, also below the 0.01 m/s under which
+ * motion is not PREDICTED (tools/closed_loop_host.c:60-66).  No world-border reflection.  After the call the resident geometry is where the obstacles are
+ * when tick K would start: rda_fleet_scene_resort + rda_fleet_step_tracked continue the loop, a second rollout takes it as its base.
+ * resort != 0: re-ranked about the advancing robot on every tick; resort = 0: rebuilt in the staged order (members staged with order = 0 only).
+ * Given a state, tick k computes bit for bit what rda_fleet_upload_scenes (the geometry of tick k, robot_xy = the state, the same order) +
+ * rda_fleet_step_tracked compute.  clearance_log [K][B] (may be NULL): member i's clearance after tick k - state k+1 against ALL obstacles of its raw scene
+ * at tick k+1 (scenarios.clearance for a polygon robot: separating axes against polygons, centre-to-edge distance minus the radius against circles;
+ * negative = overlap; +inf without a raw scene).  Additional refusals: RDA_ERR_ARG for resort = 0 with a member staged with order != 0; RDA_ERR_UNSUPPORTED
+ * for moving slots staged by the host (rda_upload_obstacles per_t: nothing to move) and, with a clearance log, for a norm2 (circle) robot.  A refused call
+ * queues nothing and leaves the resident geometry untouched.  rda_fleet_rollout_last serves this entry too. */
+int  rda_fleet_rollout_moving(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                              const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin, int resort,
+                              const double *nom_u /*B*2*T or NULL = resident*/,
+                              double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                              rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                              double *clearance_log /*K*B, or NULL*/);
+/* every member's clearance (as in clearance_log above) at states [B][3] against its resident raw scene as it stands: one launch, one wait.
+ * RDA_ERR_UNSUPPORTED: a norm2 robot; RDA_ERR_ARG: a member inside rda_tracked_begin. */
+int  rda_fleet_clearance(rda_fleet *f, const double *states /*B*3*/, double *clearance /*B*/);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */
 int  rda_fleet_enqueue_range(rda_fleet *f, int k0, int k1);
 int  rda_fleet_sync(rda_fleet *f);

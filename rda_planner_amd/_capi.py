@@ -190,6 +190,14 @@ class CApi:
                                                c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p]
                 f("fleet_rollout_last").argtypes = [C.c_void_p, c_double_p, c_double_p]
                 f("fleet_rollout").restype = f("fleet_rollout_last").restype = C.c_int
+            # ... for scenes that move (obstacle motion and the clearance log on the device), the clearance on its own, the raw-geometry test hook
+            self.has_fleet_rollout_moving = hasattr(lib, f"{prefix}_fleet_rollout_moving")
+            if self.has_fleet_rollout_moving:
+                f("fleet_rollout_moving").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, C.c_int, c_double_p,
+                                                      c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p, c_double_p]
+                f("fleet_clearance").argtypes = [C.c_void_p, c_double_p, c_double_p]
+                f("debug_scene_geom").argtypes = [C.c_void_p, c_double_p, c_int_p]
+                f("fleet_rollout_moving").restype = f("fleet_clearance").restype = f("debug_scene_geom").restype = C.c_int
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

@@ -1412,6 +1412,7 @@ struct rda_handle {
     int stepped;             // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
     // rda_opts::duals_follow: slot -> raw-scene entry of the staging the dual state is arranged by (prev_used = -1: none yet)
     int follow; int *d_prev_sel, *d_follow_map; double *d_follow_tmp; int prev_used;
+    std::vector<double> rob_G, rob_h;     // the robot's G x <= h as handed to rda_create (host copy: the clearance's robot vertices are solved from it)
     // owners
     hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL), staging, result slot, follow tables
     hbuf::Group terms;                    // Dev::coef, coefL (rda_shard_config replaces them)
@@ -1539,6 +1540,7 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     H->d.warm = o.lmz_warm; H->dense_from = o.lmz_dense_from;
     H->d.rows = (cfg->E + cfg->R + 1 <= 16) && o.lmz_rows != 0;
     H->d.nmv = robot_candidates(cfg->R, G, h, H->d.muc, H->d.rv, &H->d.nrv);
+    H->rob_G.assign(G, G + 2 * cfg->R); H->rob_h.assign(h, h + cfg->R);
     H->d.centre = o.tie_centre ? 1 : 0;
     H->d.lmz_mode = (o.lmz_mode || cfg->robot_norm2) ? 1 : 0; H->d.lmz_mu = o.lmz_mu;      // the enumeration has no norm2-robot candidates
     H->d.su_warm_wfl = o.su_warm[0]; H->d.su_warm_mu0 = o.su_warm[1]; H->d.su_warm_cap = o.su_warm_cap; H->d.su_warm_first = o.su_warm_first;
@@ -1963,6 +1965,16 @@ extern "C" int rda_get_obstacles(rda_handle *H, double *A, double *b, int32_t *c
     HIPCHK(hipMemcpy(b, d.b, N * d.nt * E * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cone, d.cone, N * sizeof(int), hipMemcpyDeviceToHost));
     *nt = d.nt;
+    return RDA_OK;
+}
+// test hook: the resident raw geometry [n][E][2] as it stands (rda_fleet_rollout_moving advances it on the device); *n = 0: no resident raw scene
+extern "C" int rda_debug_scene_geom(rda_handle *H, double *geom, int32_t *n)
+{
+    if (!H || !geom || !n) return RDA_ERR_ARG;
+    HIPCHK(hipStreamSynchronize(H->stream));
+    if (H->scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
+    *n = H->sc_n > 0 ? H->sc_n : 0;
+    if (*n > 0) HIPCHK(hipMemcpy(geom, H->sc_args.geom, (size_t)*n * H->d.c.E * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
 
@@ -2926,7 +2938,13 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     // whatever the members' zero_copy says); the log block of roll_cap ticks (roll_layout) on the device and in pinned memory, regrown for a longer rollout
     rollout::Member *h_ro_m, *d_ro_m; EgoIO *h_io_roll, *d_io_roll; char *h_ro_log, *d_ro_log; int roll_cap, roll_K;
     hbuf::Group mem, trk, resort, lidar, lidar_host;      // the tables above; those of tracked stepping; of rda_fleet_scene_resort; of the fleet lidar (scan, staging | host copies)
+    // rda_fleet_rollout_moving, rda_fleet_clearance (allocated on their first use): per member the move kernel's and the clearance kernel's arguments, the
+    // members' scene arguments as they stand (resort = 0: slots rebuilt in the staged order), the states of rda_fleet_clearance [B][3]; the snapshot of all
+    // members' raw geometry (mv_cap doubles) and the clearance log [cl_cap] on the device and in pinned memory, both regrown when a call needs more
+    scene::Move *h_mv, *d_mv; rollout::Clear *h_cl, *d_cl; scene::Args *h_mv_sc, *d_mv_sc; double *h_cl_st, *d_cl_st;
+    double *d_mv_base, *h_cl_log, *d_cl_log; size_t mv_cap, cl_cap;
     hbuf::Group roll, roll_log;                           // of rda_fleet_rollout: tables | logs
+    hbuf::Group mov, mov_base, clr_log;                   // of rda_fleet_rollout_moving / rda_fleet_clearance: tables | snapshot | clearance log
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -2958,6 +2976,26 @@ struct FleetResortTables {                // rda_fleet_scene_resort, rda_fleet_r
         return rc ? RDA_ERR_HIP : RDA_OK;
     }
     void commit(rda_fleet *F) { F->resort = std::move(g); F->d_sc = dsc; F->d_rob = drob; F->h_sc = hsc; F->h_rob = hrob; }
+};
+struct FleetMoveTables {                  // rda_fleet_rollout_moving, rda_fleet_clearance
+    hbuf::Group g; scene::Move *hmv, *dmv; rollout::Clear *hcl, *dcl; scene::Args *hsc, *dsc; double *hst, *dst;
+    int alloc(size_t B)
+    {
+        int rc = 0;
+        rc |= g.dev(&dmv, B); rc |= g.dev(&dcl, B); rc |= g.dev(&dsc, B); rc |= g.dev(&dst, 3 * B);
+        rc |= g.pin(&hmv, B); rc |= g.pin(&hcl, B); rc |= g.pin(&hsc, B); rc |= g.pin(&hst, 3 * B);
+        return rc ? RDA_ERR_HIP : RDA_OK;
+    }
+    void commit(rda_fleet *F)
+    {
+        F->mov = std::move(g);
+        F->d_mv = dmv; F->d_cl = dcl; F->d_mv_sc = dsc; F->d_cl_st = dst; F->h_mv = hmv; F->h_cl = hcl; F->h_mv_sc = hsc; F->h_cl_st = hst;
+    }
+};
+struct FleetClearLog {                    // the clearance log, regrown for a longer rollout
+    hbuf::Group g; double *h, *d; size_t cap;
+    int alloc(size_t n) { int rc = 0; cap = n; rc |= g.dev(&d, n); rc |= g.pin(&h, n); return rc ? RDA_ERR_HIP : RDA_OK; }
+    void commit(rda_fleet *F) { F->clr_log = std::move(g); F->d_cl_log = d; F->h_cl_log = h; F->cl_cap = cap; }
 };
 
 // Member i's locations on the step path: its step block in d_in (in_u: nominal controls that live elsewhere, else null), its u | s block
@@ -3161,13 +3199,13 @@ static int fleet_resort_positions(rda_fleet *F, const double *states, int stride
     F->rob_pending = 1;
     return RDA_OK;
 }
-// the four launches of a re-sort about the positions in d_rob
-static void fleet_resort_launch(rda_fleet *F, int nmax, int wmax)
+// the four launches of a re-sort: the members' scene arguments `sc` re-ranked about the positions `rob` (null: every member's arguments as they stand)
+static void fleet_resort_launch(rda_fleet *F, const scene::Args *sc, const double *rob, int nmax, int wmax)
 {
     const unsigned B = (unsigned)F->B;
-    hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
-    hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
-    hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, (const scene::Args *)F->d_sc, (const double *)F->d_rob);
+    hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
+    hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, B), dim3(256), 0, F->stream, sc, rob);
+    hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
     hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
 }
 extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
@@ -3188,7 +3226,7 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
     int nmax = 0, wmax = 0;
     rc = fleet_resort_positions(F, states, stride, nmax, wmax);
     if (rc != RDA_OK) return rc;
-    fleet_resort_launch(F, nmax, wmax);
+    fleet_resort_launch(F, F->d_sc, F->d_rob, nmax, wmax);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
@@ -3423,9 +3461,51 @@ static RollLayout roll_layout(size_t K, size_t B, size_t T)
     l.index = l.info + K * B * sizeof(rda_info); l.arrived = l.index + K * B * sizeof(int); l.bytes = l.arrived + B * sizeof(int);
     return l;
 }
-extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
-                                 int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
-                                 rda_info *info_log, int32_t *arrived_at)
+// The moving entry's per-member tables as the members stand now.  Robot vertices of the clearance: body-frame intersections of consecutive rows of
+// G x <= h (scenarios.robot_vertices: vertex i from rows i - 1 and i).  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
+struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
+static bool member_raw_scene(const rda_handle *H) { return H->sc_n > 0 && H->d.obstacle_num != 0; }
+static void fleet_move_view(const rda_fleet *F, MoveView &v)
+{
+    const size_t B = F->B;
+    v.mv.resize(B); v.cl.resize(B); v.sc.resize(B); v.off.assign(B, 0);
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        scene::Move &m = v.mv[i]; rollout::Clear &c = v.cl[i]; scene::Args &a = v.sc[i];
+        memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c)); memset((void *)&a, 0, sizeof(a));
+        const int R = H->d.c.R;
+        c.R = H->d.c.robot_norm2 ? 0 : R; c.E = H->d.c.E;
+        for (int k = 0; k < c.R; ++k) {
+            const int j = (k + R - 1) % R;
+            const double *G = H->rob_G.data(), *h = H->rob_h.data();
+            const double det = G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k];
+            c.rv[k][0] = (h[j] * G[2 * k + 1] - G[2 * j + 1] * h[k]) / det;
+            c.rv[k][1] = (G[2 * j] * h[k] - h[j] * G[2 * k]) / det;
+        }
+        if (!member_raw_scene(H)) continue;
+        a = H->sc_args;
+        m.geom = const_cast<double *>(a.geom); m.vel = a.vel; m.kind = a.kind; m.nvert = a.nvert; m.n = a.n; m.E = a.E; m.dt = H->d.c.dt;
+        v.off[i] = v.mv_total;                                                    // (its place in the snapshot buffer: Move::base is set by the rollout)
+        c.geom = a.geom; c.kind = a.kind; c.nvert = a.nvert; c.n = a.n;
+        v.mv_total += (size_t)a.n * a.E * 2;
+        v.gmax = a.n * a.E > v.gmax ? a.n * a.E : v.gmax;
+        v.nmax = a.n > v.nmax ? a.n : v.nmax; v.wmax = a.N * a.nt > v.wmax ? a.N * a.nt : v.wmax;
+    }
+}
+// a polygon robot whose consecutive rows intersect: what the clearance kernel takes
+static bool member_clearance_ok(const rda_handle *H)
+{
+    if (H->d.c.robot_norm2) return false;
+    const int R = H->d.c.R;
+    const double *G = H->rob_G.data();
+    for (int k = 0; k < R; ++k) { const int j = (k + R - 1) % R; if (G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k] == 0) return false; }
+    return true;
+}
+
+// rda_fleet_rollout (moving = false: exactly the static entry) and rda_fleet_rollout_moving share this body
+static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                              int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
+                              rda_info *info_log, int32_t *arrived_at, bool moving, double *clearance_log)
 {
     if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
     if (ind_range < 1 || goal_margin < 1) return RDA_ERR_ARG;
@@ -3437,10 +3517,20 @@ extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, cons
     }
     for (const rda_handle *H : F->egos) {
         if (H->follow) return RDA_ERR_UNSUPPORTED;                              // (k_follow_* are per member)
-        if (H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
+        if (!moving && H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
+    }
+    MoveView mvw;
+    if (moving) {
+        for (const rda_handle *H : F->egos) {
+            if (!resort && member_raw_scene(H) && H->sc_args.order != 0) return RDA_ERR_ARG;          // slots rebuilt in the staged order: only meaningful for order = 0
+            if (H->d.obstacle_num != 0 && H->d.nt > 1 && H->sc_n <= 0) return RDA_ERR_UNSUPPORTED;    // host-staged per-stage slots: no raw scene to move
+            if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+        }
+        fleet_move_view(F, mvw);
     }
     // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    FleetTrackTables ttrk; FleetResortTables tres;
+    FleetTrackTables ttrk; FleetResortTables tres; FleetMoveTables tmov; FleetClearLog tclr; hbuf::Group gbase; double *dbase = nullptr;
+    const bool need_mov = moving && !F->d_mv, need_base = moving && mvw.mv_total > F->mv_cap, need_clr = clearance_log && (size_t)K * F->B > F->cl_cap;
     hbuf::Group gtab, glog; rollout::Member *hm = nullptr, *dm = nullptr; EgoIO *hio = nullptr, *dio = nullptr; char *hlog = nullptr, *dlog = nullptr;
     const bool need_trk = !F->d_trk_in, need_res = resort && !F->d_sc, need_tab = !F->d_ro_m, need_log = !F->d_ro_log || K > F->roll_cap;
     {
@@ -3449,9 +3539,15 @@ extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, cons
         if (need_res) rc |= tres.alloc(B);
         if (need_tab) { rc |= gtab.dev(&dm, B); rc |= gtab.dev(&dio, 2 * B); rc |= gtab.pin(&hm, B); rc |= gtab.pin(&hio, 2 * B); }
         if (need_log) { const size_t nb = roll_layout((size_t)K, B, T).bytes; rc |= glog.dev(&dlog, nb); rc |= glog.pin(&hlog, nb); }
+        if (need_mov) rc |= tmov.alloc(B);
+        if (need_base) rc |= gbase.dev(&dbase, mvw.mv_total);
+        if (need_clr) rc |= tclr.alloc((size_t)K * B);
         if (rc) return RDA_ERR_HIP;
     }
-    if (need_log) HIPCHK(hipStreamSynchronize(F->stream));                      // (a shorter block is freed below)
+    if (need_log || need_base || need_clr) HIPCHK(hipStreamSynchronize(F->stream));      // (a shorter block is freed below)
+    if (need_mov) tmov.commit(F);
+    if (need_base) { F->mov_base = std::move(gbase); F->d_mv_base = dbase; F->mv_cap = mvw.mv_total; }
+    if (need_clr) tclr.commit(F);
     if (need_trk) ttrk.commit(F);
     if (need_res) tres.commit(F);
     if (need_tab) { F->roll = std::move(gtab); F->d_ro_m = dm; F->d_io_roll = dio; F->h_ro_m = hm; F->h_io_roll = hio; }
@@ -3472,8 +3568,20 @@ extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, cons
         if (F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
     }
     if (memcmp(wm.data(), F->h_ro_m, B * sizeof(rollout::Member)) != 0 || memcmp(wio.data(), F->h_io_roll, 2 * B * sizeof(EgoIO)) != 0) tables = true;
+    if (moving) {
+        for (size_t i = 0; i < B; ++i) if (mvw.mv[i].n > 0) mvw.mv[i].base = F->d_mv_base + mvw.off[i];
+        if (memcmp(mvw.mv.data(), F->h_mv, B * sizeof(scene::Move)) != 0 || memcmp(mvw.cl.data(), F->h_cl, B * sizeof(rollout::Clear)) != 0 ||
+            memcmp(mvw.sc.data(), F->h_mv_sc, B * sizeof(scene::Args)) != 0) tables = true;
+    }
     if (tables) {
         HIPCHK(hipStreamSynchronize(F->stream));
+        if (moving) {
+            memcpy((void *)F->h_mv, mvw.mv.data(), B * sizeof(scene::Move)); memcpy((void *)F->h_cl, mvw.cl.data(), B * sizeof(rollout::Clear));
+            memcpy((void *)F->h_mv_sc, mvw.sc.data(), B * sizeof(scene::Args));
+            HIPCHK(hipMemcpyAsync(F->d_mv, F->h_mv, B * sizeof(scene::Move), hipMemcpyHostToDevice, F->stream));
+            HIPCHK(hipMemcpyAsync(F->d_cl, F->h_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
+            HIPCHK(hipMemcpyAsync(F->d_mv_sc, F->h_mv_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
+        }
         memcpy((void *)F->h_ro_m, wm.data(), B * sizeof(rollout::Member)); memcpy((void *)F->h_io_roll, wio.data(), 2 * B * sizeof(EgoIO));
         for (size_t i = 0; i < B; ++i) { F->h_paths[i] = F->egos[i]->d_path; F->h_lens[i] = F->egos[i]->path_len; }
         HIPCHK(hipMemcpyAsync(F->d_ro_m, F->h_ro_m, B * sizeof(rollout::Member), hipMemcpyHostToDevice, F->stream));
@@ -3500,16 +3608,25 @@ extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, cons
     lg.states = (double *)(F->d_ro_log + lay.states); lg.u = (double *)(F->d_ro_log + lay.u); lg.end_heading = (double *)(F->d_ro_log + lay.endh);
     lg.info = (rda_info *)(F->d_ro_log + lay.info); lg.index = (int *)(F->d_ro_log + lay.index); lg.arrived_at = (int *)(F->d_ro_log + lay.arrived);
     HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, B * sizeof(int), F->stream));    // -1: not arrived
+    const bool moves = moving && mvw.gmax > 0;
+    const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
+    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_mv);      // `base`: the geometry as the call finds it
     for (int k = 0; k < K; ++k) {
-        if (resort) fleet_resort_launch(F, nmax, wmax);                          // about d_rob: the caller's positions (tick 0), then the advance kernel's
+        if (resort) fleet_resort_launch(F, F->d_sc, F->d_rob, nmax, wmax);       // about d_rob: the caller's positions (tick 0), then the advance kernel's
+        else if (moves) fleet_resort_launch(F, F->d_mv_sc, nullptr, mvw.nmax, mvw.wmax);      // a scene that moved: its slots rebuilt in the staged order
         const EgoIO *io = F->d_io_roll + (k == 0 ? 0 : B);
         hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, io, F->d_trk_in, F->d_paths, F->d_lens, F->d_trk_out, (int)B);
         rc = fleet_enqueue(F, io, 0);
         if (rc != RDA_OK) return rc;
         hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->d_ro_m,
                            (const track::Out *)F->d_trk_out, F->d_trk_in, resort ? F->d_rob : nullptr, lg, k, goal_margin, (int)B);
+        if (moves) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_mv, k + 1);     // where tick k + 1 finds them
+        if (clearance_log)                                                       // state k + 1 against the geometry of tick k + 1
+            hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_cl,
+                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->d_cl_log + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
+    if (clearance_log) HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
     HIPCHK(hipMemcpy2DAsync(F->d_ro_log + lay.lastu, nu * sizeof(double), F->d_out, res_info(T) * sizeof(double), nu * sizeof(double), B,
                             hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
     HIPCHK(hipMemcpyAsync(F->h_ro_log, F->d_ro_log, lay.bytes, hipMemcpyDeviceToHost, F->stream));
@@ -3523,6 +3640,64 @@ extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, cons
     memcpy(index_log, F->h_ro_log + lay.index, (size_t)K * B * sizeof(int32_t));
     if (info_log) memcpy(info_log, F->h_ro_log + lay.info, (size_t)K * B * sizeof(rda_info));
     memcpy(arrived_at, F->h_ro_log + lay.arrived, B * sizeof(int32_t));
+    if (clearance_log) memcpy(clearance_log, F->h_cl_log, (size_t)K * B * sizeof(double));
+    return RDA_OK;
+}
+extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                 int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
+                                 rda_info *info_log, int32_t *arrived_at)
+{
+    return fleet_rollout_body(F, K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, resort, nom_u, states_log, u_log, index_log, info_log,
+                              arrived_at, false, nullptr);
+}
+// The rollout for scenes that move: behind every tick's advance kernel scene::k_move_fleet puts every member's raw geometry where the next tick finds it
+// (base + vel * (dt * k), base = the geometry the call found), the tick's re-sort launches rebuild the per-stage slots from it, and (clearance_log)
+// rollout::k_clearance_fleet logs every member's clearance after the tick.
+extern "C" int rda_fleet_rollout_moving(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                        int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log,
+                                        int32_t *index_log, rda_info *info_log, int32_t *arrived_at, double *clearance_log)
+{
+    return fleet_rollout_body(F, K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, resort, nom_u, states_log, u_log, index_log, info_log,
+                              arrived_at, true, clearance_log);
+}
+// every member's clearance at states [B][3] against its resident raw scene as it stands: the rollout's kernel, one launch, one wait
+extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *clearance)
+{
+    if (!F || !states || !clearance) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    for (const rda_handle *H : F->egos) {
+        if (H->pending) return RDA_ERR_ARG;
+        if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+    }
+    FleetMoveTables tmov; FleetClearLog tclr;
+    const bool need_mov = !F->d_mv, need_clr = B > F->cl_cap;
+    {
+        int rc = 0;
+        if (need_mov) rc |= tmov.alloc(B);
+        if (need_clr) rc |= tclr.alloc(B);
+        if (rc) return RDA_ERR_HIP;
+    }
+    if (need_clr) HIPCHK(hipStreamSynchronize(F->stream));
+    if (need_mov) tmov.commit(F);
+    if (need_clr) tclr.commit(F);
+    int rc = fleet_refresh(F);                          // behind whatever the members still have queued
+    if (rc != RDA_OK) return rc;
+    MoveView v;
+    fleet_move_view(F, v);
+    if (memcmp(v.cl.data(), F->h_cl, B * sizeof(rollout::Clear)) != 0) {
+        HIPCHK(hipStreamSynchronize(F->stream));
+        memcpy((void *)F->h_cl, v.cl.data(), B * sizeof(rollout::Clear));
+        HIPCHK(hipMemcpyAsync(F->d_cl, F->h_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
+    }
+    memcpy(F->h_cl_st, states, 3 * B * sizeof(double));
+    HIPCHK(hipMemcpyAsync(F->d_cl_st, F->h_cl_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_cl,
+                       (const double *)F->d_cl_st, F->d_cl_log, (int)B);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    memcpy(clearance, F->h_cl_log, B * sizeof(double));
     return RDA_OK;
 }
 // What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls

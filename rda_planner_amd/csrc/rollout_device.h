@@ -62,4 +62,90 @@ __global__ void k_rollout_advance(const Member *ms, const track::Out *trk_out, t
     lg.end_heading[i] = o.end_heading;
 }
 
+// Robot / obstacle clearance of every member on the device (rda_fleet_rollout_moving's clearance log, rda_fleet_clearance): scenarios.clearance for a polygon
+// robot (scenarios.py:205-220) against ALL n obstacles of the member's resident raw scene as it stands, not only the N staged ones.  One workgroup per
+// member; its threads stride over the obstacles, the minimum is reduced by shuffles and LDS (a minimum is exact: its order is free).
+//   robot vertices    body-frame intersections of consecutive rows of G x <= h (solved once on the host: Clear::rv), rotated and shifted by the state
+//   polygon obstacle  _poly_sep: the edge normals of both polygons, normalised with the 1e-300 floor; the larger gap wins; no winding fix-up
+//   circle obstacle   point-segment distance of the centre to the robot's edges, minus the radius
+// A member without a raw scene (n = 0): +inf.
+struct Clear {                // per member
+    const double *geom;       // [n][E][2] resident raw geometry (scene::Args::geom)
+    const int *kind, *nvert;  // [n]
+    int n, E, R, pad;         // R: robot vertices
+    double rv[RDA_RMAX][2];   // body frame
+};
+constexpr int CLEAR_NT = 256;
+
+// gap of polygon W [kw] along the outward edge normals of polygon V [kv] (one half of _poly_sep)
+__device__ __forceinline__ double sep_half(const double *vx, const double *vy, int kv, const double *wx, const double *wy, int kw, double best)
+{
+#pragma clang fp contract(off)
+    for (int i = 0; i < kv; ++i) {
+        const int i1 = i + 1 < kv ? i + 1 : 0;
+        const double ex = vx[i1] - vx[i], ey = vy[i1] - vy[i];
+        double len = sqrt(ey * ey + ex * ex);
+        if (!(len > 1e-300)) len = 1e-300;
+        const double nx = ey / len, ny = -ex / len;
+        double lo = INFINITY;
+        for (int j = 0; j < kw; ++j) { const double p = nx * wx[j] + ny * wy[j]; if (p < lo) lo = p; }
+        const double gap = lo - (nx * vx[i] + ny * vy[i]);
+        if (gap > best) best = gap;
+    }
+    return best;
+}
+
+// states: [B][3] the members' states; out [B]
+__global__ __launch_bounds__(CLEAR_NT) void k_clearance_fleet(const Clear *cs, const double *states, double *out, int B)
+{
+#pragma clang fp contract(off)
+    __shared__ double rx[RDA_RMAX], ry[RDA_RMAX], part[CLEAR_NT / 64];
+    const int b = blockIdx.x;
+    if (b >= B) return;                                   // (uniform)
+    const Clear &c = cs[b];
+    const int R = c.R, E = c.E;
+    if ((int)threadIdx.x < R) {
+        const double x = states[3 * b], y = states[3 * b + 1], th = states[3 * b + 2];
+        const double co = cos(th), si = sin(th);
+        rx[threadIdx.x] = (co * c.rv[threadIdx.x][0] - si * c.rv[threadIdx.x][1]) + x;
+        ry[threadIdx.x] = (si * c.rv[threadIdx.x][0] + co * c.rv[threadIdx.x][1]) + y;
+    }
+    __syncthreads();
+    double best = INFINITY;
+    for (int i = threadIdx.x; i < c.n; i += CLEAR_NT) {
+        const double *g = c.geom + (size_t)i * E * 2;
+        double d;
+        if (c.kind[i] == 1) {
+            const double cx = g[0], cy = g[1];
+            d = INFINITY;
+            for (int j = 0; j < R; ++j) {
+                const int j1 = j + 1 < R ? j + 1 : 0;
+                const double ax = rx[j], ay = ry[j], abx = rx[j1] - ax, aby = ry[j1] - ay;
+                double s = ((cx - ax) * abx + (cy - ay) * aby) / (abx * abx + aby * aby);
+                s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
+                const double px = (ax + s * abx) - cx, py = (ay + s * aby) - cy;
+                const double e = sqrt(px * px + py * py);
+                if (e < d) d = e;
+            }
+            d = d - g[2];
+        } else {
+            int k = c.nvert[i];
+            if (k > RDA_EMAX) k = RDA_EMAX;
+            double qx[RDA_EMAX], qy[RDA_EMAX];
+            for (int j = 0; j < k; ++j) { qx[j] = g[2 * j]; qy[j] = g[2 * j + 1]; }
+            d = sep_half(rx, ry, R, qx, qy, k, -INFINITY);
+            d = sep_half(qx, qy, k, rx, ry, R, d);
+        }
+        if (d < best) best = d;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) best = fmin(best, __shfl_xor(best, off, 64));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < CLEAR_NT / 64; ++w) best = fmin(best, part[w]);
+        out[b] = best;
+    }
+}
+
 }  // namespace rollout

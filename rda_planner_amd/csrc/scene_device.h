@@ -142,4 +142,37 @@ __global__ void k_build_fleet(const Args *as, const double *rob)
     build_body(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+// Obstacle motion between two ticks of a rollout (rda_fleet_rollout_moving): what World.step and tools/closed_loop_host.c:60-66 do on the host, for the
+// whole fleet in one launch - blockIdx.y = the member, one thread per (obstacle, vertex entry).  The position is always computed from `base`, the snapshot
+// of the member's raw geometry taken when the call started (k_snapshot_fleet), never incrementally: geometry at tick k = base + vel * (dt * k), every product
+// and the sum separately rounded.  Polygon: entries v < nvert, both coordinates; circle: entry 0 (the centre) - the radius entry and the padding never change.
+// Every obstacle moves, also those below the 0.01 m/s under which k_build does not PREDICT motion.
+struct Move {
+    double *geom;           // [n][E][2] the member's resident raw geometry (Args::geom)
+    double *base;           // [n][E][2] its snapshot
+    const double *vel;      // [n][2]
+    const int *kind, *nvert;
+    int n, E;
+    double dt;
+};
+__global__ void k_snapshot_fleet(const Move *ms)
+{
+    const Move m = ms[blockIdx.y];
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= m.n * m.E) return;
+    m.base[2 * w] = m.geom[2 * w]; m.base[2 * w + 1] = m.geom[2 * w + 1];
+}
+__global__ void k_move_fleet(const Move *ms, int k)
+{
+#pragma clang fp contract(off)
+    const Move m = ms[blockIdx.y];
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= m.n * m.E) return;
+    const int i = w / m.E, v = w - i * m.E;
+    if (m.kind[i] == 1 ? v != 0 : v >= m.nvert[i]) return;
+    const double tk = m.dt * (double)k;
+    m.geom[2 * w] = m.base[2 * w] + m.vel[2 * i] * tk;
+    m.geom[2 * w + 1] = m.base[2 * w + 1] + m.vel[2 * i + 1] * tk;
+}
+
 }  // namespace scene

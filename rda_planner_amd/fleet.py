@@ -188,12 +188,29 @@ class Fleet:
         the arrival tick on).  kwargs: `threshold`, `ind_range` of `closest_point`.  Returns a dict: `states` (steps+1, B, 3) with row 0 the input,
         `controls` (steps, B, 2) as applied, `index` and `iters` (steps, B), `arrived_at` (B,) the arrival tick or -1.  Afterwards every member's
         `state`, `cur_index` and nominal controls are those of the last tick, so `control` continues the loop; the solver state of a member that has
-        arrived (it keeps being stepped where it stands) is only good for `reset`."""
+        arrived (it keeps being stepped where it stands) is only good for `reset`.
+        Further kwargs: `obstacle_lists=` stages every member's scene first as `control` does (the positions of tick 0; not needed when the scenes are
+        already staged).  `moving=True` (rda_fleet_rollout_moving): scenes whose obstacles move are taken - between two ticks every obstacle is put
+        forward by its velocity on the device, position at tick k = position at tick 0 + velocity * (dt * k), and the per-stage slots are rebuilt
+        (`resort=False`: in the staged order, for members with `obstacle_order=False`).  The caller's obstacle objects are NOT modified: to go on with
+        `control` afterwards the caller advances them by `steps * dt`.  `clearance=True` (with `moving=True`, polygon robots) adds `"clearance"`
+        (steps, B): every member's clearance after each tick against all obstacles of its scene, `scenarios.clearance` evaluated on the device.
+        Without `moving` a scene that moves is refused as before."""
         ms = self.members
+        kwargs = dict(kwargs)
+        obstacle_lists, moving, clearance = kwargs.pop("obstacle_lists", None), bool(kwargs.pop("moving", False)), bool(kwargs.pop("clearance", False))
         if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
             raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
         if not getattr(self.api, "has_fleet_rollout", False):
             raise RuntimeError("the loaded solver library has no fleet rollout entry point (rda_fleet_rollout)")
+        if moving and not getattr(self.api, "has_fleet_rollout_moving", False):
+            raise RuntimeError("the loaded solver library has no rollout for moving scenes (rda_fleet_rollout_moving)")
+        if clearance and not moving:
+            raise ValueError("Fleet.rollout: clearance=True needs moving=True (the clearance log belongs to rda_fleet_rollout_moving)")
+        if clearance and any(m.car_tuple.cone_type == "norm2" for m in ms):
+            raise RuntimeError("Fleet.rollout: the clearance log is for polygon robots; a circle (norm2) robot is not supported")
+        if obstacle_lists is not None and len(obstacle_lists) != len(ms):
+            raise ValueError("Fleet.rollout: one obstacle list per member")
         margins = {int(m.goal_index_threshold) for m in ms}
         if len(margins) != 1:
             raise ValueError("Fleet.rollout: the members must share one goal_index_threshold")
@@ -208,6 +225,9 @@ class Fleet:
             st[i] = np.asarray(m.state, float).ravel()[0:3]
             speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
             resident = resident and m._nominal_u() is None
+        if obstacle_lists is not None and not self._stage_all(obstacle_lists, st):
+            for i, m in enumerate(ms):
+                m._stage_obstacles(obstacle_lists[i])
         nom_u = None
         if not resident:            # some member's cur_vel_array was replaced since its last solve: send them all
             for i, m in enumerate(ms):
@@ -216,10 +236,12 @@ class Fleet:
         s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
         i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
         infos = (Info * (max(K, 1) * B))()
-        rc = self.api.fleet_rollout(self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)),
-                                    margins.pop(), 1 if resort else 0, dptr(nom_u), dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
+        args = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)),
+                margins.pop(), 1 if resort else 0, dptr(nom_u), dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
+        c_log = np.zeros((max(K, 0), B)) if clearance else None
+        rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_rollout failed with code {rc}")
+            raise RuntimeError(f"{'rda_fleet_rollout_moving' if moving else 'rda_fleet_rollout'} failed with code {rc}")
         eh = np.zeros(B)
         rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
         if rc < 0:
@@ -237,7 +259,25 @@ class Fleet:
             else:                                          # the device holds the controls of the last solve
                 m.cur_vel_array = m._dev_u = self._out_u[i].copy()
         iters = np.array([infos[j].iters for j in range(K * B)], np.int32).reshape(K, B)
-        return {"states": s_log, "controls": u_log, "index": i_log, "iters": iters, "arrived_at": arrived}
+        out = {"states": s_log, "controls": u_log, "index": i_log, "iters": iters, "arrived_at": arrived}
+        if clearance:
+            out["clearance"] = c_log
+        return out
+
+    def clearance(self, states):
+        """(B,) every member's clearance at `states[i]` against ALL obstacles of the scene it has staged, as they stand on the device
+        (rda_fleet_clearance: `scenarios.clearance` for polygon robots, one launch; negative = overlap, +inf without a staged scene)"""
+        if not getattr(self.api, "has_fleet_rollout_moving", False):
+            raise RuntimeError("the loaded solver library has no clearance entry point (rda_fleet_clearance)")
+        if any(m.car_tuple.cone_type == "norm2" for m in self.members):
+            raise RuntimeError("Fleet.clearance is for polygon robots; a circle (norm2) robot is not supported")
+        B = len(self.members)
+        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+        out = np.zeros(B)
+        rc = self.api.fleet_clearance(self._handle, dptr(st), dptr(out))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_clearance failed with code {rc}")
+        return out
 
     def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
         """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the

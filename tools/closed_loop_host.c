@@ -143,3 +143,63 @@ int closed_loop_fleet_run(const struct closed_loop_fleet_api *api, rda_fleet *f,
     free(out_u); free(out_s); free(speed); free(eh); free(inf); free(mi);
     return rc;
 }
+
+/* ---- the fleet loop for scenes that MOVE (BASELINE config C4 members in a fleet; the reference's dynamic_obs loop per robot): what
+ * rda_fleet_rollout_moving replaces.  Per tick: every member's geometry is put where its obstacles are at tick k - geom = geom0 + vel * (dt * k), computed
+ * from geom0, every product and the sum separately rounded; polygons (kind 0): their nvert vertices; circles (kind 1): entry 0, the centre, never the radius
+ * entry - then ONE rda_fleet_upload_scenes (robot_xy = the members' positions), ONE rda_fleet_step_tracked, and the plant on the host.  Member i owns
+ * counts[i] consecutive obstacles of kind / nvert / geom / geom0 [.][maxv][2] / vel [.][2]; order [B].  k counts from the tick whose geometry is geom0.
+ * The other arguments and the logs are those of closed_loop_fleet_run. */
+typedef int (*fleet_upload_scenes_fn)(rda_fleet *, const int32_t *, const int32_t *, const int32_t *, const double *, const double *, const double *,
+                                      const int32_t *);
+struct closed_loop_fleet_moving_api { fleet_step_tracked_fn fleet_step_tracked; fleet_upload_scenes_fn fleet_upload_scenes; };
+
+int closed_loop_fleet_run_moving(const struct closed_loop_fleet_moving_api *api, rda_fleet *f, int B, int T, int dynamics, double wheelbase, double dt,
+                                 double ref_speed, double threshold, int ind_range, const int32_t *path_len, const int32_t *counts, int maxv,
+                                 const int32_t *kind, const int32_t *nvert, double *geom, const double *geom0, const double *vel, const int32_t *order,
+                                 int k0, int n_steps, const double *nom_u_first, double *states, int32_t *cur_index, double *u_log, double *t_log,
+                                 int32_t *iters_log, int32_t *ipm_log)
+{
+    if (T > RDA_TMAX || B < 1 || maxv < 2) return -1;
+    const size_t nu = 2 * (size_t)T, ns = 3 * ((size_t)T + 1);
+    double *out_u = (double *)malloc(sizeof(double) * B * nu), *out_s = (double *)malloc(sizeof(double) * B * ns);
+    double *speed = (double *)malloc(sizeof(double) * B), *eh = (double *)malloc(sizeof(double) * B), *rob = (double *)malloc(sizeof(double) * B * 2);
+    rda_info *inf = (rda_info *)malloc(sizeof(rda_info) * B);
+    int32_t *mi = (int32_t *)malloc(sizeof(int32_t) * B);
+    int rc = 0;
+    size_t n_all = 0;
+    if (!out_u || !out_s || !speed || !eh || !rob || !inf || !mi) rc = -1;
+    for (int i = 0; i < B && rc == 0; ++i) { speed[i] = ref_speed; n_all += (size_t)counts[i]; }
+    for (int k = k0; k < k0 + n_steps && rc == 0; ++k) {
+        const double t0 = now_s();
+        for (size_t i = 0; i < n_all; ++i) {
+            const int nv = kind[i] == 1 ? 1 : (nvert[i] < maxv ? nvert[i] : maxv);
+            for (int v = 0; v < nv; ++v) {
+                const size_t o = (i * (size_t)maxv + v) * 2;
+                geom[o] = geom0[o] + vel[2 * i] * (dt * k);
+                geom[o + 1] = geom0[o + 1] + vel[2 * i + 1] * (dt * k);
+            }
+        }
+        for (int i = 0; i < B; ++i) { rob[2 * i] = states[3 * i]; rob[2 * i + 1] = states[3 * i + 1]; }
+        rc = api->fleet_upload_scenes(f, counts, kind, nvert, geom, vel, rob, order);
+        if (rc >= 0)
+            rc = api->fleet_step_tracked(f, states, speed, cur_index, threshold, ind_range, k == 0 ? nom_u_first : 0, out_u, out_s, inf, 0, mi, eh);
+        if (rc < 0) break;
+        rc = 0;
+        for (int i = 0; i < B; ++i) {
+            double *st = states + 3 * i;
+            const double v = out_u[i * nu], w = out_u[i * nu + T], phi = st[2];
+            cur_index[i] = mi[i];
+            if (mi[i] >= path_len[i] - 1) rc = 1;
+            if (dynamics == 0) { st[0] += dt * (v * cos(phi)); st[1] += dt * (v * sin(phi)); st[2] += dt * (v * tan(w) / wheelbase); }
+            else if (dynamics == 1) { st[0] += dt * (v * cos(phi)); st[1] += dt * (v * sin(phi)); st[2] += dt * w; }
+            else { st[0] += dt * (v * cos(w)); st[1] += dt * (v * sin(w)); }
+            u_log[((size_t)(k - k0) * B + i) * 2] = v; u_log[((size_t)(k - k0) * B + i) * 2 + 1] = w;
+            iters_log[(size_t)(k - k0) * B + i] = inf[i].iters;
+            if (ipm_log) ipm_log[(size_t)(k - k0) * B + i] = inf[i].su_ipm_iters;
+        }
+        t_log[k - k0] = now_s() - t0;
+    }
+    free(out_u); free(out_s); free(speed); free(eh); free(rob); free(inf); free(mi);
+    return rc;
+}

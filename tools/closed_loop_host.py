@@ -26,6 +26,10 @@ class FleetApi(C.Structure):   # struct closed_loop_fleet_api
     _fields_ = [(n_, C.c_void_p) for n_ in ("fleet_step_tracked", "scene_resort", "fleet_scene_resort")]
 
 
+class FleetMovingApi(C.Structure):   # struct closed_loop_fleet_moving_api
+    _fields_ = [(n_, C.c_void_p) for n_ in ("fleet_step_tracked", "fleet_upload_scenes")]
+
+
 class Host:
     """`run` = closed_loop_run; `api` = the four entry points of librda_hip.so it calls, as function pointers"""
 
@@ -48,3 +52,11 @@ class Host:
                                               C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         self.fleet_run = lib.closed_loop_fleet_run
+        self.fleet_moving_api = FleetMovingApi(*[C.cast(getattr(rda_lib, "rda_" + n_), C.c_void_p).value if hasattr(rda_lib, "rda_" + n_) else None
+                                                 for n_, _ in FleetMovingApi._fields_])
+        i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        lib.closed_loop_fleet_run_moving.restype = C.c_int
+        lib.closed_loop_fleet_run_moving.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                     i32p, i32p, C.c_int, i32p, i32p, f64p, f64p, f64p, i32p, C.c_int, C.c_int, f64p, f64p, i32p, f64p, f64p,
+                                                     i32p, i32p]
+        self.fleet_run_moving = lib.closed_loop_fleet_run_moving

@@ -12,6 +12,14 @@ parent commit's, so that the host loop is timed on the code it had before the ro
 
     python tools/fleet_rollout.py [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6] [--baseline-so PATH]
 
+--moving: the same comparison for scenes that MOVE (C5 shape with `scene_polygons(moving=True)` members: BASELINE C4's obstacles in a fleet).
+  (a) host loop  closed_loop_fleet_run_moving: per tick every member's geometry put forward on the host, ONE rda_fleet_upload_scenes, ONE
+                 rda_fleet_step_tracked + one host wait, the plants on the host
+  (b) rollout    ONE rda_fleet_rollout_moving of K ticks (no clearance log): the motion by scene::k_move_fleet, one host wait after the K ticks
+Both legs exist only from the commit that added the moving rollout on, so both run on this build (--baseline-so is not used).
+
+    python tools/fleet_rollout.py --moving [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6]         (output: profiles/fleet_rollout_moving.txt)
+
 One measurement alone (what a kernel trace is taken of: the launches per tick are those of the host loop plus k_rollout_advance):
     python tools/fleet_rollout.py --leg rollout --B 16        (or --leg host)
 """
@@ -30,14 +38,14 @@ sys.path.insert(0, ROOT)
 T, N = 25, 100
 
 
-def members(api, B, n_steps):
-    """B fresh solvers of the C5 shape with their paths and raw scenes resident, and their fleet"""
+def members(api, B, n_steps, moving=False):
+    """B fresh solvers of the C5 shape with their paths and raw scenes resident, and their fleet (+ the members' raw scenes, concatenated)"""
     from benchlib.workload import build_workload
     from rda_planner_amd._capi import dptr, iptr
     from rda_planner_amd.rda_solver import RDA_solver
-    svs, states, plen = [], np.zeros((B, 3)), np.zeros(B, np.int32)
+    svs, states, plen, raw = [], np.zeros((B, 3)), np.zeros(B, np.int32), []
     for e in range(B):
-        car_t, path, obstacles, kw = build_workload(seed_offset=e, n_obs=N, T=T, n_steps=n_steps + 10)
+        car_t, path, obstacles, kw = build_workload(seed_offset=e, n_obs=N, T=T, n_steps=n_steps + 10, moving=moving)
         sv = RDA_solver(T, car_t, kw["max_edge_num"], N, iter_num=kw["iter_num"], step_time=0.1, time_print=False, ro1=kw["ro1"])
         n_sc, kind, nvert, geom, vel = sv.flatten_scene(list(obstacles))
         kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
@@ -48,13 +56,17 @@ def members(api, B, n_steps):
         assert api.upload_path(sv._be.handle, int(P.shape[0]), dptr(P)) == 0
         assert api.upload_scene(sv._be.handle, int(n_sc), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(states[e]), 1, None) == 0
         svs.append(sv)
+        raw.append((kind, nvert, geom, vel))
+    scene = dict(counts=np.array([len(r[0]) for r in raw], np.int32), maxv=int(raw[0][2].shape[1]))
+    scene.update({key: np.ascontiguousarray(np.concatenate([r[j] for r in raw])) for j, key in enumerate(("kind", "nvert", "geom0", "vel"))})
+    scene["geom"], scene["order"] = scene["geom0"].copy(), np.ones(B, np.int32)
     arr = (C.c_void_p * B)(*[sv._be.handle for sv in svs])
     F = C.c_void_p()
     assert api.fleet_create(arr, B, C.byref(F)) == 0
-    return svs, arr, F, np.ascontiguousarray(states), plen, car_t
+    return svs, arr, F, np.ascontiguousarray(states), plen, car_t, scene
 
 
-def leg(name, B, K, warm):
+def leg(name, B, K, warm, moving=False):
     """one measurement in this process: `warm` host-driven ticks, then K timed ticks by the host loop or by the rollout -> dict"""
     from rda_planner_amd._capi import Info, dptr, iptr
     from rda_planner_amd._lib import hip_api
@@ -62,12 +74,18 @@ def leg(name, B, K, warm):
     api = hip_api()
     host = clh.Host(api.lib)
     n_all = warm + 2 * K
-    svs, arr, F, states, plen, car_t = members(api, B, n_all)
+    svs, arr, F, states, plen, car_t, sc = members(api, B, n_all, moving)
     cur, nom0 = np.zeros(B, np.int32), np.zeros((B, 2, T))
     u_log, t_log = np.zeros((n_all, B, 2)), np.zeros(n_all)
     it_log, ipm_log = np.zeros((n_all, B), np.int32), np.zeros((n_all, B), np.int32)
 
     def host_ticks(k0, n):
+        if moving:
+            rc = host.fleet_run_moving(C.byref(host.fleet_moving_api), F, B, T, 0, float(car_t.wheelbase), 0.1, 4.0, 0.1, 10, iptr(plen), iptr(sc["counts"]),
+                                       sc["maxv"], iptr(sc["kind"]), iptr(sc["nvert"]), dptr(sc["geom"]), dptr(sc["geom0"]), dptr(sc["vel"]), iptr(sc["order"]),
+                                       k0, n, dptr(nom0), dptr(states), iptr(cur), dptr(u_log[k0:]), dptr(t_log[k0:]), iptr(it_log[k0:]), iptr(ipm_log[k0:]))
+            assert rc == 0, rc
+            return
         rc = host.fleet_run(C.byref(host.fleet_api), F, arr, B, T, 0, float(car_t.wheelbase), 0.1, 4.0, 0.1, 10, iptr(plen), 2, k0, n, dptr(nom0), dptr(states),
                             iptr(cur), dptr(u_log[k0:]), dptr(t_log[k0:]), iptr(it_log[k0:]), iptr(ipm_log[k0:]))
         assert rc == 0, rc
@@ -83,8 +101,19 @@ def leg(name, B, K, warm):
         else:
             s_log, u, i_log = np.zeros((K + 1, B, 3)), np.zeros((K, B, 2)), np.zeros((K, B), np.int32)
             infos, arrived = (Info * (K * B))(), np.zeros(B, np.int32)
-            rc = api.fleet_rollout(F, K, dptr(states), dptr(np.full(B, 4.0)), iptr(cur), 0.1, 10, 1, 1, None, dptr(s_log), dptr(u), iptr(i_log), infos,
-                                   iptr(arrived))
+            if moving:
+                if win == 0:        # the host-driven ticks left the geometry of tick warm - 1 on the device: stage tick `warm`; from then on it is resident
+                    full = sc["geom0"] + sc["vel"][:, None, :] * (0.1 * k0)
+                    live = np.arange(sc["maxv"])[None, :] < sc["nvert"][:, None]
+                    sc["geom"][live] = full[live]
+                    rob = np.ascontiguousarray(states[:, 0:2])
+                    assert api.fleet_upload_scenes(F, iptr(sc["counts"]), iptr(sc["kind"]), iptr(sc["nvert"]), dptr(sc["geom"]), dptr(sc["vel"]), dptr(rob),
+                                                   iptr(sc["order"])) == 0
+                rc = api.fleet_rollout_moving(F, K, dptr(states), dptr(np.full(B, 4.0)), iptr(cur), 0.1, 10, 1, 1, None, dptr(s_log), dptr(u), iptr(i_log),
+                                              infos, iptr(arrived), None)
+            else:
+                rc = api.fleet_rollout(F, K, dptr(states), dptr(np.full(B, 4.0)), iptr(cur), 0.1, 10, 1, 1, None, dptr(s_log), dptr(u), iptr(i_log), infos,
+                                       iptr(arrived))
             els.append(time.perf_counter() - t0)
             assert rc == 0, rc
             assert np.all(arrived == -1)
@@ -99,13 +128,19 @@ def leg(name, B, K, warm):
 
 def child(name, B, args):
     env = dict(os.environ)
-    if name == "host" and args.baseline_so:
+    if name == "host" and args.baseline_so and not args.moving:
         env["RDA_HIP_SO"] = os.path.abspath(args.baseline_so)
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--B", str(B), "--K", str(args.K), "--warm", str(args.warm)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--B", str(B), "--K", str(args.K), "--warm", str(args.warm)] + (["--moving"] if args.moving else [])
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.leg_timeout)
     if res.returncode != 0:
         raise RuntimeError(f"leg {name} B={B} ended with {res.returncode}: {res.stderr[-400:]}")
     return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def print_static_head(args):
+    print("fleet closed loop, C5 shape (T = %d, N = %d, own seeded scene per ego, re-sorted every tick): %d host-driven ticks, a first window of K = %d ticks, then the "
+          "timed window of K ticks; %d interleaved repeats" % (T, N, args.warm, args.K, args.repeats))
+    print("host loop: closed_loop_fleet_run (resort = 2) on %s" % ("the baseline library (the parent commit's build)" if args.baseline_so else "this library"))
 
 
 def main():
@@ -116,19 +151,24 @@ def main():
     ap.add_argument("--warm", type=int, default=6)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-so", default=None)
+    ap.add_argument("--moving", action="store_true", help="scenes that move: closed_loop_fleet_run_moving against rda_fleet_rollout_moving, both on this build")
     ap.add_argument("--leg-timeout", type=float, default=300.0)
     ap.add_argument("--leg", choices=["host", "rollout"], default=None, help="(internal) run one measurement in this process and print it as JSON")
     ap.add_argument("--B", type=int, default=16)
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     if args.leg:
-        print(json.dumps(leg(args.leg, args.B, args.K, args.warm)))
+        print(json.dumps(leg(args.leg, args.B, args.K, args.warm, args.moving)))
         return
     assert args.repeats >= 3
-    print("fleet closed loop, C5 shape (T = %d, N = %d, own seeded scene per ego, re-sorted every tick): %d host-driven ticks, a first window of K = %d ticks, then the "
-          "timed window of K ticks; %d interleaved repeats" % (T, N, args.warm, args.K, args.repeats))
-    print("host loop: closed_loop_fleet_run (resort = 2) on %s" % ("the baseline library (the parent commit's build)" if args.baseline_so else "this library"))
-    print("%4s | %-40s | %-40s | %s" % ("B", "(a) host loop ego-steps/s", "(b) rda_fleet_rollout ego-steps/s", "median (b) / (a)"))
+    if args.moving:
+        print("fleet closed loop with MOVING scenes, C5 shape (T = %d, N = %d moving polygons per ego, velocities U[-1,1]^2 m/s, own seeded scene per ego, re-sorted every "
+              "tick): %d host-driven ticks, a first window of K = %d ticks, then the timed window of K ticks; %d interleaved repeats" % (T, N, args.warm, args.K, args.repeats))
+        print("host loop: closed_loop_fleet_run_moving (geometry forward on the host, rda_fleet_upload_scenes, rda_fleet_step_tracked per tick) on this library; "
+              "(b) = rda_fleet_rollout_moving without a clearance log")
+    else:
+        print_static_head(args)
+    print("%4s | %-40s | %-40s | %s" % ("B", "(a) host loop ego-steps/s", "(b) rda_fleet_rollout_moving ego-steps/s" if args.moving else "(b) rda_fleet_rollout ego-steps/s", "median (b) / (a)"))
     verdicts = []
     for B in args.fleets:
         a, b = [], []
