@@ -417,6 +417,49 @@ int  rda_fleet_rollout_moving(rda_fleet *f, int K, const double *states /*B*3*/,
 /* every member's clearance (as in clearance_log above) at states [B][3] against its resident raw scene as it stands: one launch, one wait.
  * RDA_ERR_UNSUPPORTED: a norm2 robot; RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_clearance(rda_fleet *f, const double *states /*B*3*/, double *clearance /*B*/);
+/* A resident WORLD per member: the true obstacles a simulated lidar sees (rda_fleet_raycast, rda_fleet_rollout_lidar), kept apart from the member's raw
+ * scene, which a lidar tick overwrites with boxes.  The layout of rda_fleet_upload_scenes with a vertex stride of its own: member i owns counts[i]
+ * consecutive entries (0 = an empty world), kind 0 polygon / 1 circle, geom[j] = `we` vertex pairs | centre, (radius, -), 3 <= we <= RDA_EMAX; vel NULL =
+ * a world that stands.  Owned by the fleet; a new upload replaces the old world.  RDA_ERR_ARG: a negative count, a missing array with a positive total,
+ * nvert outside 3..we for a polygon, a kind other than 0 / 1, we out of range; a refused allocation: RDA_ERR_HIP, the old world intact. */
+int  rda_fleet_upload_worlds(rda_fleet *f, const int32_t *counts /*B*/, int we, const int32_t *kind, const int32_t *nvert,
+                             const double *geom /*sum(counts)*we*2*/, const double *vel /*sum(counts)*2, or NULL = standing*/);
+/* The simulated sensor (World.get_lidar_scan of rda_planner_amd/world.py is the specification): every member's beams ray-cast against its resident world as
+ * it stands, from states [B][3], by ONE launch of lidar::k_raycast_fleet (the member in the grid, a thread per beam) and one wait.  Beam i of a member:
+ * angle_min + i * (angle_max - angle_min) / (n_beams - 1), the last one exactly angle_max, a single beam angle_min; direction (cos, sin) of heading +
+ * angle.  Circle: f = o - c, b = d.f, disc = b*b - (f.f - r*r), a hit needs disc >= 0 and t = -b - sqrt(disc) >= 0 (an origin inside a circle does not see
+ * it).  Polygon edge p -> q: e = q - p, w = p - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, s = (w.x d.y - w.y d.x) / den, a hit needs
+ * |den| > 1e-12, t >= 0, 0 <= s <= 1.  range = clip(min(range_max, all hits), range_min, range_max); an empty world: range_max everywhere.  `ranges` is
+ * the concatenation of the members' scans (n_beams[i] = 0: no scan).  RDA_ERR_UNSUPPORTED: more than 4096 beams; RDA_ERR_ARG: no uploaded world, a negative
+ * beam count, a missing array. */
+int  rda_fleet_raycast(rda_fleet *f, const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,
+                       const double *range_min, const double *range_max /*B each*/, const double *states /*B*3*/,
+                       double *ranges /*sum(n_beams)*/);
+/* The rollout of a fleet whose robots each carry a lidar: the loop a caller otherwise runs as World.get_lidar_scan -> rda_fleet_upload_scans ->
+ * rda_fleet_step_tracked -> the plant.  rda_fleet_rollout's arguments, logs, arrival rule and refusals without `resort` (a lidar tick always stages about the
+ * robot), the sensor arrays of rda_fleet_raycast, and eps, min_samples, order [B] of rda_fleet_upload_scans.  Per tick k, on the fleet's stream: the ray
+ * cast from the pose the advance kernel left on the device (tick 0: the caller's) into a device ranges buffer, the scan kernel on those ranges at that
+ * pose, ONE wait for the B box counts (4 * B bytes: they choose the LamMuZ launch form, apply the zero-box rule and size the staging launches), the staging
+ * of rda_fleet_upload_scans with the robot position taken from the device, the tracker, the ADMM launches and the advance kernel.  moving != 0: behind
+ * every tick the WORLD is put forward by the rule of rda_fleet_rollout_moving - `base` = the world as the call finds it, at tick k base + vel * (dt * k) -
+ * and after the call it stands where tick K would find it.  nbox_log [K][B] (may be NULL): the boxes every member saw; clearance_log [K][B] (may be NULL):
+ * state k+1 against the WORLD of tick k+1 (the true obstacles, not the boxes; +inf for an empty world; a norm2 robot: RDA_ERR_UNSUPPORTED).  Every
+ * member's raw scene is grown to n_beams[i] boxes and every buffer allocated before tick 0; a refused call queues nothing and leaves world and members as
+ * they were.  Given a state and the world of tick k, a tick computes bit for bit what rda_fleet_raycast, rda_fleet_upload_scans of those ranges at that
+ * state and rda_fleet_step_tracked compute; afterwards fleet and members are as K such host-driven ticks leave them.  Additional refusals: RDA_ERR_ARG
+ * without an uploaded world, for a negative beam count, eps <= 0, min_samples < 1 or a missing array; RDA_ERR_UNSUPPORTED for more than 4096 beams or
+ * E < 4.  rda_fleet_rollout_last serves this entry too. */
+int  rda_fleet_rollout_lidar(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                             const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                             const double *nom_u /*B*2*T or NULL = resident*/,
+                             const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,
+                             const double *range_min, const double *range_max /*B each*/,
+                             double eps, int min_samples, const int32_t *order /*B*/, int moving,
+                             double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                             rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                             int32_t *nbox_log /*K*B, may be NULL*/, double *clearance_log /*K*B, may be NULL*/);
+/* test hook: the geometry of the resident worlds as it stands, member-major [*n_total][*we][2] (geom and we may be NULL; *n_total = 0: no world) */
+int  rda_debug_fleet_world(rda_fleet *f, double *geom, int32_t *n_total, int32_t *we);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */
 int  rda_fleet_enqueue_range(rda_fleet *f, int k0, int k1);
 int  rda_fleet_sync(rda_fleet *f);

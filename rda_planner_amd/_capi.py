@@ -198,6 +198,17 @@ class CApi:
                 f("fleet_clearance").argtypes = [C.c_void_p, c_double_p, c_double_p]
                 f("debug_scene_geom").argtypes = [C.c_void_p, c_double_p, c_int_p]
                 f("fleet_rollout_moving").restype = f("fleet_clearance").restype = f("debug_scene_geom").restype = C.c_int
+            # the simulated sensor: a resident world per member, the fleet ray caster, the rollout around it, the world test hook
+            self.has_fleet_rollout_lidar = hasattr(lib, f"{prefix}_fleet_rollout_lidar")
+            if self.has_fleet_rollout_lidar:
+                f("fleet_upload_worlds").argtypes = [C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p]
+                f("fleet_raycast").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
+                f("fleet_rollout_lidar").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, c_double_p,
+                                                     c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int, c_int_p, C.c_int,
+                                                     c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p, c_int_p, c_double_p]
+                f("debug_fleet_world").argtypes = [C.c_void_p, c_double_p, c_int_p, c_int_p]
+                for name in ("fleet_upload_worlds", "fleet_raycast", "fleet_rollout_lidar", "debug_fleet_world"):
+                    f(name).restype = C.c_int
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "../../include/rda_hip.h"
 
 namespace lidar {
 
@@ -316,6 +317,89 @@ __global__ __launch_bounds__(NT) void k_scan_fleet(const Args *as)
     scan_body(a);
 }
 
+// ... with the sensor pose read from device memory, poses [B][3] (rda_fleet_rollout_lidar: the pose is where rollout::k_rollout_advance left it, the host
+// does not know it when it queues the launch; Args::ranges then points at what k_raycast_fleet wrote).  Same body: bit-identical to k_scan_fleet at that pose.
+__global__ __launch_bounds__(NT) void k_scan_fleet_at(const Args *as, const double *poses)
+{
+    Args a = as[blockIdx.x];
+    if (a.n_beams <= 0) { if (threadIdx.x == 0) { a.count[0] = 0; a.count[1] = 0; } return; }
+    a.sx = poses[3 * blockIdx.x]; a.sy = poses[3 * blockIdx.x + 1]; a.sth = poses[3 * blockIdx.x + 2];
+    scan_body(a);
+}
+
+// The sensor itself (rda_fleet_raycast, rda_fleet_rollout_lidar): exact ray casting of every member's beams against its resident WORLD - the true
+// obstacles, kept apart from the raw scene that a lidar tick overwrites with boxes.  The specification is World.get_lidar_scan (rda_planner_amd/world.py),
+// expression by expression (FMA contraction off):
+//   beam i     angle_min + i * (angle_max - angle_min) / (n_beams - 1), the last one exactly angle_max, a single beam angle_min (scan_body's rule =
+//              np.linspace); direction (cos, sin) of heading + angle, origin the pose's x, y
+//   circle     f = o - c, b = d.f, disc = b * b - (f.f - r * r); a hit: disc >= 0 and t = -b - sqrt(disc) >= 0 (an origin inside the circle: no hit)
+//   edge p->q  e = q - p, w = p - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, s = (w.x d.y - w.y d.x) / den;
+//              a hit: |den| > 1e-12, t >= 0, 0 <= s <= 1; only the polygon's nvert vertices
+//   range      clip(min(range_max, all hits), range_min, range_max); an empty world: range_max everywhere
+// One launch for the fleet: blockIdx.y = the member, a thread per beam, RAY_NT beams (one wave) per workgroup, so B * ceil(n_beams / 64) workgroups - 1088
+// at 64 members x 1080 beams.  The member's world goes through LDS in tiles of RAY_TILE obstacles; every lane reads the same obstacle at the same time
+// (broadcast reads, no bank conflict).  The minimum over obstacles is exact, its order free.  The obstacles are not split over workgroups: at the sizes
+// this is for (B >= 16, >= 360 beams) the beams alone give 96 .. 1088 waves, and a split would cost an initialising launch and atomics on the ranges.
+struct Ray {                  // per member
+    const double *geom;       // [n][E][2] the member's world: polygon vertices | circle: centre, (radius, -)
+    const int *kind, *nvert;  // [n] 0 polygon, 1 circle | polygon vertex count (3 .. E)
+    int n, E;
+    int n_beams, pad;
+    double angle_min, angle_max, range_min, range_max;
+    double *ranges;           // [n_beams] device memory
+};
+constexpr int RAY_NT = 64, RAY_TILE = 32;
+
+__global__ __launch_bounds__(RAY_NT) void k_raycast_fleet(const Ray *rs, const double *poses)
+{
+#pragma clang fp contract(off)        // numpy does not fuse: keep every product and sum separately rounded
+    __shared__ double tg[RAY_TILE * RDA_EMAX * 2];
+    __shared__ int tk[RAY_TILE], tv[RAY_TILE];
+    const Ray r = rs[blockIdx.y];
+    const int nb = r.n_beams, E = r.E < RDA_EMAX ? r.E : RDA_EMAX;
+    if ((int)(blockIdx.x * RAY_NT) >= nb) return;                                        // (the whole workgroup: the grid is sized by the longest scan)
+    const int b = blockIdx.x * RAY_NT + threadIdx.x;
+    const bool live = b < nb;
+    const double ox = poses[3 * blockIdx.y], oy = poses[3 * blockIdx.y + 1];
+    double dx = 1.0, dy = 0.0;
+    if (live) {
+        const double step = nb > 1 ? (r.angle_max - r.angle_min) / (double)(nb - 1) : 0.0;
+        const double ang = (nb > 1 && b == nb - 1) ? r.angle_max : (double)b * step + r.angle_min;
+        const double th = poses[3 * blockIdx.y + 2] + ang;
+        dx = cos(th); dy = sin(th);
+    }
+    double rng = r.range_max;
+    for (int o0 = 0; o0 < r.n; o0 += RAY_TILE) {
+        const int m = r.n - o0 < RAY_TILE ? r.n - o0 : RAY_TILE;
+        __syncthreads();                                                                 // (the tile before this one has been read)
+        for (int w = threadIdx.x; w < m * E * 2; w += RAY_NT) tg[w] = r.geom[(size_t)o0 * E * 2 + w];
+        for (int w = threadIdx.x; w < m; w += RAY_NT) { tk[w] = r.kind[o0 + w]; tv[w] = r.nvert[o0 + w]; }
+        __syncthreads();
+        if (!live) continue;
+        for (int j = 0; j < m; ++j) {
+            const double *g = tg + j * E * 2;
+            if (tk[j] == 1) {
+                const double fx = ox - g[0], fy = oy - g[1];
+                const double bq = dx * fx + dy * fy;
+                const double disc = bq * bq - ((fx * fx + fy * fy) - g[2] * g[2]);
+                if (disc >= 0) { const double t = -bq - sqrt(disc); if (t >= 0 && t < rng) rng = t; }
+                continue;
+            }
+            const int nv = tv[j] < E ? tv[j] : E;
+            for (int k = 0; k < nv; ++k) {
+                const int k1 = k + 1 < nv ? k + 1 : 0;
+                const double px = g[2 * k], py = g[2 * k + 1];
+                const double ex = g[2 * k1] - px, ey = g[2 * k1 + 1] - py;
+                const double den = dx * ey - dy * ex;
+                const double wx = px - ox, wy = py - oy;
+                const double t = (wx * ey - wy * ex) / den, s = (wx * dy - wy * dx) / den;
+                if (fabs(den) > 1e-12 && t >= 0 && s >= 0 && s <= 1 && t < rng) rng = t;
+            }
+        }
+    }
+    if (live) r.ranges[b] = fmin(fmax(rng, r.range_min), r.range_max);                   // np.clip
+}
+
 // the boxes as a raw scene in the layout scene_stage uploads (rda_hip.hip): polygons of 4 vertices, no velocity, the robot position for the ordering
 __global__ void k_scene_fill(const double *boxes, const int n, const int E, double *geom, double *vel, double *robot, int *nonconvex, int *kind, int *nvert,
                              const double rx, const double ry)
@@ -335,13 +419,14 @@ struct Fill {
     const double *boxes; int n, E;
     double *geom, *vel, *robot; int *nonconvex, *kind, *nvert;
     double rx, ry;
+    const double *rob;        // (may be null) the robot position [2] in device memory, taken instead of rx, ry (rda_fleet_rollout_lidar: where the advance kernel wrote it)
 };
 __global__ void k_scene_fill_fleet(const Fill *fs)
 {
     const Fill f = fs[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (f.n <= 0) return;
-    if (i == 0) { f.robot[0] = f.rx; f.robot[1] = f.ry; *f.nonconvex = 0; }
+    if (i == 0) { f.robot[0] = f.rob ? f.rob[0] : f.rx; f.robot[1] = f.rob ? f.rob[1] : f.ry; *f.nonconvex = 0; }
     if (i >= f.n) return;
     double *g = f.geom + (size_t)i * f.E * 2;
     for (int e = 0; e < f.E; ++e) { g[2 * e] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e] : 0.0; g[2 * e + 1] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e + 1] : 0.0; }

@@ -2945,6 +2945,15 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     double *d_mv_base, *h_cl_log, *d_cl_log; size_t mv_cap, cl_cap;
     hbuf::Group roll, roll_log;                           // of rda_fleet_rollout: tables | logs
     hbuf::Group mov, mov_base, clr_log;                   // of rda_fleet_rollout_moving / rda_fleet_clearance: tables | snapshot | clearance log
+    // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
+    // tick overwrites with boxes.  Member-major geometry [w_total][w_e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
+    // vertex counts; w_off[i]: member i's first obstacle.  Per member the ray caster's, the move kernel's and the clearance kernel's arguments (pinned mirror /
+    // device array) and the poses of rda_fleet_raycast [B][3].  The ranges of the last ray cast [w_rcap] on the device and in pinned memory, regrown on demand.
+    double *d_w_geom, *d_w_base, *d_w_vel; int *d_w_kind, *d_w_nvert; int w_e, w_have; size_t w_total;
+    std::vector<int> w_counts; std::vector<size_t> w_off;
+    lidar::Ray *h_w_ray, *d_w_ray; scene::Move *h_w_mv, *d_w_mv; rollout::Clear *h_w_cl, *d_w_cl; double *h_w_st, *d_w_st;
+    double *d_w_ranges, *h_w_ranges; size_t w_rcap;
+    hbuf::Group world, world_rng;
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -3242,6 +3251,7 @@ static int fleet_lidar_reserve(rda_fleet *F, bool host_copy)
         rc |= g.pin(&ha, B); rc |= g.pin(&hf, B); rc |= g.pin(&hs, B); rc |= g.pin(&hr, B * lidar::MAXB); rc |= g.pin(&hc, 2 * B);
         if (rc) return RDA_ERR_HIP;
         HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
+        HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet_at, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
         F->lidar = std::move(g);
         F->h_li_args = ha; F->d_li_args = da; F->h_li_fill = hf; F->d_li_fill = df; F->h_li_sc = hs; F->d_li_sc = ds;
         F->d_li_boxes = db; F->h_li_ranges = hr; F->h_li_count = hc;
@@ -3319,26 +3329,14 @@ extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const 
     return RDA_OK;
 }
 
-// rda_upload_scan for every member: one scan launch, one wait for the B counts, then every member's boxes -> raw scene -> slots -> candidate lists by
-// FIVE launches whatever B is (blockIdx.y = the member), all on the fleet's stream.  Host-side member state ends as scan_stage / scene_kernels leave it.
-extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
-                                      const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes)
+// The staging half of rda_fleet_upload_scans, shared with rda_fleet_rollout_lidar: the B box counts are in h_li_count, the boxes in d_li_boxes and the
+// fleet's stream is idle.  Every member's boxes -> raw scene -> slots -> candidate lists by FIVE launches whatever B is (blockIdx.y = the member); the
+// zero-box rule, the members' records and the LamMuZ launch form follow the counts.  grow: every member's larger raw scene where it needs one, allocated
+// by the caller (nothing of any member has changed when an allocation is refused).  The robot positions: states [B][3] on the host, or (pose_dev) [B][3]
+// in device memory - rda_fleet_rollout_lidar, where only the device knows them.  Host-side member state ends as scan_stage / scene_kernels leave it.
+static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const double *states, const double *pose_dev, const int32_t *order)
 {
-    if (!order) return RDA_ERR_ARG;
-    int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
-    if (rc != RDA_OK) return rc;
     const size_t B = F->B;
-    for (rda_handle *H : F->egos) if (H->pending) return RDA_ERR_ARG;                     // a member inside a tick of its own
-    for (rda_handle *H : F->egos) if (H->follow) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member)
-    const bool fresh = !F->d_li_boxes;
-    rc = fleet_lidar_reserve(F, false);
-    if (rc != RDA_OK) return rc;
-    rc = fleet_refresh(F);                              // behind whatever the members still have queued
-    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false);
-    // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
-    std::vector<SceneGrow> grow(B);
-    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->h_li_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->h_li_count[2 * i], grow[i]);
-    if (rc != RDA_OK) { if (fresh) fleet_lidar_release(F); return rc; }      // a failed call leaves what the fleet and the members hold as it was
     int nmax = 0, wmax = 0;
     for (size_t i = 0; i < B; ++i) {
         rda_handle *H = F->egos[i];
@@ -3355,7 +3353,7 @@ extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, cons
         f.boxes = F->d_li_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
         f.geom = const_cast<double *>(a.geom); f.vel = const_cast<double *>(a.vel); f.robot = const_cast<double *>(a.robot);
         f.nonconvex = a.nonconvex; f.kind = const_cast<int *>(a.kind); f.nvert = const_cast<int *>(a.nvert);
-        f.rx = states[3 * i]; f.ry = states[3 * i + 1];
+        f.rx = states ? states[3 * i] : 0.0; f.ry = states ? states[3 * i + 1] : 0.0; f.rob = pose_dev ? pose_dev + 3 * i : nullptr;
         memcpy((void *)&F->h_li_sc[i], &a, sizeof(a));
         H->sc_args = a; H->sc_n = n;
         d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;                        // (scene_kernels)
@@ -3377,6 +3375,30 @@ extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, cons
         hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), (unsigned)B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
         HIPCHK(hipGetLastError());
     }
+    return RDA_OK;
+}
+
+// rda_upload_scan for every member: one scan launch, one wait for the B counts, then the staging above, all on the fleet's stream.
+extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                                      const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes)
+{
+    if (!order) return RDA_ERR_ARG;
+    int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
+    if (rc != RDA_OK) return rc;
+    const size_t B = F->B;
+    for (rda_handle *H : F->egos) if (H->pending) return RDA_ERR_ARG;                     // a member inside a tick of its own
+    for (rda_handle *H : F->egos) if (H->follow) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member)
+    const bool fresh = !F->d_li_boxes;
+    rc = fleet_lidar_reserve(F, false);
+    if (rc != RDA_OK) return rc;
+    rc = fleet_refresh(F);                              // behind whatever the members still have queued
+    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false);
+    // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
+    std::vector<SceneGrow> grow(B);
+    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->h_li_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->h_li_count[2 * i], grow[i]);
+    if (rc != RDA_OK) { if (fresh) fleet_lidar_release(F); return rc; }      // a failed call leaves what the fleet and the members hold as it was
+    rc = fleet_scan_stage(F, grow, states, nullptr, order);
+    if (rc != RDA_OK) return rc;
     if (n_boxes) for (size_t i = 0; i < B; ++i) n_boxes[i] = F->h_li_count[2 * i];
     return RDA_OK;
 }
@@ -3465,6 +3487,18 @@ static RollLayout roll_layout(size_t K, size_t B, size_t T)
 // G x <= h (scenarios.robot_vertices: vertex i from rows i - 1 and i).  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
 struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
 static bool member_raw_scene(const rda_handle *H) { return H->sc_n > 0 && H->d.obstacle_num != 0; }
+static void clear_robot(const rda_handle *H, rollout::Clear &c)      // R, rv of the member's robot (0 vertices for a norm2 robot)
+{
+    const int R = H->d.c.R;
+    c.R = H->d.c.robot_norm2 ? 0 : R;
+    for (int k = 0; k < c.R; ++k) {
+        const int j = (k + R - 1) % R;
+        const double *G = H->rob_G.data(), *h = H->rob_h.data();
+        const double det = G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k];
+        c.rv[k][0] = (h[j] * G[2 * k + 1] - G[2 * j + 1] * h[k]) / det;
+        c.rv[k][1] = (G[2 * j] * h[k] - h[j] * G[2 * k]) / det;
+    }
+}
 static void fleet_move_view(const rda_fleet *F, MoveView &v)
 {
     const size_t B = F->B;
@@ -3473,15 +3507,8 @@ static void fleet_move_view(const rda_fleet *F, MoveView &v)
         const rda_handle *H = F->egos[i];
         scene::Move &m = v.mv[i]; rollout::Clear &c = v.cl[i]; scene::Args &a = v.sc[i];
         memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c)); memset((void *)&a, 0, sizeof(a));
-        const int R = H->d.c.R;
-        c.R = H->d.c.robot_norm2 ? 0 : R; c.E = H->d.c.E;
-        for (int k = 0; k < c.R; ++k) {
-            const int j = (k + R - 1) % R;
-            const double *G = H->rob_G.data(), *h = H->rob_h.data();
-            const double det = G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k];
-            c.rv[k][0] = (h[j] * G[2 * k + 1] - G[2 * j + 1] * h[k]) / det;
-            c.rv[k][1] = (G[2 * j] * h[k] - h[j] * G[2 * k]) / det;
-        }
+        clear_robot(H, c);
+        c.E = H->d.c.E;
         if (!member_raw_scene(H)) continue;
         a = H->sc_args;
         m.geom = const_cast<double *>(a.geom); m.vel = a.vel; m.kind = a.kind; m.nvert = a.nvert; m.n = a.n; m.E = a.E; m.dt = H->d.c.dt;
@@ -3502,6 +3529,83 @@ static bool member_clearance_ok(const rda_handle *H)
     return true;
 }
 
+// What every rollout entry does around its ticks (rda_fleet_rollout, _moving, _lidar).
+// The advance kernel's member table and the io tables of tick 0 | of the later ticks as the members stand now; true: they, or the members' paths, differ
+// from what the device holds.
+struct RollView { std::vector<rollout::Member> wm; std::vector<EgoIO> wio; };
+static bool fleet_roll_view(const rda_fleet *F, bool have_nom_u, RollView &v)
+{
+    const size_t B = F->B, T = F->T;
+    bool tables = false;
+    v.wm.resize(B); v.wio.resize(2 * B);
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        v.wio[i] = fleet_member_io(F, i, have_nom_u ? nullptr : H->d.u, F->d_out, F->d_info);      // tick 0
+        v.wio[B + i] = fleet_member_io(F, i, H->d.u, F->d_out, F->d_info);                         // later ticks: the resident controls
+        rollout::Member &m = v.wm[i];
+        memset((void *)&m, 0, sizeof(m));
+        m.out_u = v.wio[i].out_u; m.info = v.wio[i].info; m.T = (int)T; m.L = H->path_len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
+        if (F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
+    }
+    if (memcmp(v.wm.data(), F->h_ro_m, B * sizeof(rollout::Member)) != 0 || memcmp(v.wio.data(), F->h_io_roll, 2 * B * sizeof(EgoIO)) != 0) tables = true;
+    return tables;
+}
+// ... uploaded (the fleet's stream is idle: nothing reads the pinned mirrors)
+static int fleet_roll_upload(rda_fleet *F, const RollView &v)
+{
+    const size_t B = F->B;
+    memcpy((void *)F->h_ro_m, v.wm.data(), B * sizeof(rollout::Member)); memcpy((void *)F->h_io_roll, v.wio.data(), 2 * B * sizeof(EgoIO));
+    for (size_t i = 0; i < B; ++i) { F->h_paths[i] = F->egos[i]->d_path; F->h_lens[i] = F->egos[i]->path_len; }
+    HIPCHK(hipMemcpyAsync(F->d_ro_m, F->h_ro_m, B * sizeof(rollout::Member), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(F->d_io_roll, F->h_io_roll, 2 * B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(F->d_paths, F->h_paths, B * sizeof(double *), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
+    return RDA_OK;
+}
+// tick 0's nominal controls and tracker inputs, as rda_fleet_step_tracked uploads them; lg: the device logs of this rollout, arrived_at reset to -1
+static int fleet_roll_inputs(rda_fleet *F, const RollLayout &lay, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                             int ind_range, const double *nom_u, rollout::Logs &lg)
+{
+    const size_t T = F->T, nu = traj_u(T), nin = step_doubles(T), B = F->B;
+    if (nom_u) {
+        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
+        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
+                                hipMemcpyHostToDevice, F->stream));
+    }
+    for (size_t i = 0; i < B; ++i) {
+        track::In &in = F->h_trk_in[i];
+        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
+        in.cur_index = cur_index[i]; in.ind_range = ind_range;
+    }
+    HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
+    lg.states = (double *)(F->d_ro_log + lay.states); lg.u = (double *)(F->d_ro_log + lay.u); lg.end_heading = (double *)(F->d_ro_log + lay.endh);
+    lg.info = (rda_info *)(F->d_ro_log + lay.info); lg.index = (int *)(F->d_ro_log + lay.index); lg.arrived_at = (int *)(F->d_ro_log + lay.arrived);
+    HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, B * sizeof(int), F->stream));    // -1: not arrived
+    return RDA_OK;
+}
+// the logs to the host behind the last tick, the wait for them, and out to the caller's arrays
+static int fleet_roll_fetch(rda_fleet *F, int K, const RollLayout &lay, const double *states, double *states_log, double *u_log, int32_t *index_log,
+                            rda_info *info_log, int32_t *arrived_at, double *clearance_log)
+{
+    const size_t T = F->T, nu = traj_u(T), B = F->B;
+    if (clearance_log) HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipMemcpy2DAsync(F->d_ro_log + lay.lastu, nu * sizeof(double), F->d_out, res_info(T) * sizeof(double), nu * sizeof(double), B,
+                            hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
+    HIPCHK(hipMemcpyAsync(F->h_ro_log, F->d_ro_log, lay.bytes, hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;                       // their staged scenes have been consumed
+    F->roll_K = K;
+    memcpy(states_log, states, B * 3 * sizeof(double));                         // row 0: the input
+    memcpy(states_log + B * 3, F->h_ro_log + lay.states + B * 3 * sizeof(double), (size_t)K * B * 3 * sizeof(double));
+    memcpy(u_log, F->h_ro_log + lay.u, (size_t)K * B * 2 * sizeof(double));
+    memcpy(index_log, F->h_ro_log + lay.index, (size_t)K * B * sizeof(int32_t));
+    if (info_log) memcpy(info_log, F->h_ro_log + lay.info, (size_t)K * B * sizeof(rda_info));
+    memcpy(arrived_at, F->h_ro_log + lay.arrived, B * sizeof(int32_t));
+    if (clearance_log) memcpy(clearance_log, F->h_cl_log, (size_t)K * B * sizeof(double));
+    return RDA_OK;
+}
+
 // rda_fleet_rollout (moving = false: exactly the static entry) and rda_fleet_rollout_moving share this body
 static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
                               int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
@@ -3509,7 +3613,7 @@ static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const d
 {
     if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
     if (ind_range < 1 || goal_margin < 1) return RDA_ERR_ARG;
-    const size_t T = F->T, nu = traj_u(T), nin = step_doubles(T), B = F->B;
+    const size_t T = F->T, B = F->B;
     for (size_t i = 0; i < B; ++i) {
         const rda_handle *H = F->egos[i];
         if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
@@ -3556,18 +3660,8 @@ static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const d
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     // one-time table refreshes (the only other waits of a rollout): the tables are compared with what the device holds and uploaded when they differ
-    bool tables = false;
-    std::vector<rollout::Member> wm(B); std::vector<EgoIO> wio(2 * B);
-    for (size_t i = 0; i < B; ++i) {
-        const rda_handle *H = F->egos[i];
-        wio[i] = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, F->d_out, F->d_info);          // tick 0
-        wio[B + i] = fleet_member_io(F, i, H->d.u, F->d_out, F->d_info);                         // later ticks: the resident controls
-        rollout::Member &m = wm[i];
-        memset((void *)&m, 0, sizeof(m));
-        m.out_u = wio[i].out_u; m.info = wio[i].info; m.T = (int)T; m.L = H->path_len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
-        if (F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
-    }
-    if (memcmp(wm.data(), F->h_ro_m, B * sizeof(rollout::Member)) != 0 || memcmp(wio.data(), F->h_io_roll, 2 * B * sizeof(EgoIO)) != 0) tables = true;
+    RollView rv;
+    bool tables = fleet_roll_view(F, nom_u != nullptr, rv);
     if (moving) {
         for (size_t i = 0; i < B; ++i) if (mvw.mv[i].n > 0) mvw.mv[i].base = F->d_mv_base + mvw.off[i];
         if (memcmp(mvw.mv.data(), F->h_mv, B * sizeof(scene::Move)) != 0 || memcmp(mvw.cl.data(), F->h_cl, B * sizeof(rollout::Clear)) != 0 ||
@@ -3582,32 +3676,16 @@ static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const d
             HIPCHK(hipMemcpyAsync(F->d_cl, F->h_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
             HIPCHK(hipMemcpyAsync(F->d_mv_sc, F->h_mv_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
         }
-        memcpy((void *)F->h_ro_m, wm.data(), B * sizeof(rollout::Member)); memcpy((void *)F->h_io_roll, wio.data(), 2 * B * sizeof(EgoIO));
-        for (size_t i = 0; i < B; ++i) { F->h_paths[i] = F->egos[i]->d_path; F->h_lens[i] = F->egos[i]->path_len; }
-        HIPCHK(hipMemcpyAsync(F->d_ro_m, F->h_ro_m, B * sizeof(rollout::Member), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_io_roll, F->h_io_roll, 2 * B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_paths, F->h_paths, B * sizeof(double *), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
+        rc = fleet_roll_upload(F, rv);
+        if (rc != RDA_OK) return rc;
     }
     // tick 0's inputs, as rda_fleet_scene_resort and rda_fleet_step_tracked upload them
     int nmax = 0, wmax = 0;
     if (resort) { rc = fleet_resort_positions(F, states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
-    if (nom_u) {
-        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
-        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
-                                hipMemcpyHostToDevice, F->stream));
-    }
-    for (size_t i = 0; i < B; ++i) {
-        track::In &in = F->h_trk_in[i];
-        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
-        in.cur_index = cur_index[i]; in.ind_range = ind_range;
-    }
-    HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
     const RollLayout lay = roll_layout((size_t)K, B, T);
     rollout::Logs lg;
-    lg.states = (double *)(F->d_ro_log + lay.states); lg.u = (double *)(F->d_ro_log + lay.u); lg.end_heading = (double *)(F->d_ro_log + lay.endh);
-    lg.info = (rda_info *)(F->d_ro_log + lay.info); lg.index = (int *)(F->d_ro_log + lay.index); lg.arrived_at = (int *)(F->d_ro_log + lay.arrived);
-    HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, B * sizeof(int), F->stream));    // -1: not arrived
+    rc = fleet_roll_inputs(F, lay, states, ref_speed, cur_index, threshold, ind_range, nom_u, lg);
+    if (rc != RDA_OK) return rc;
     const bool moves = moving && mvw.gmax > 0;
     const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
     if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_mv);      // `base`: the geometry as the call finds it
@@ -3626,22 +3704,7 @@ static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const d
                                (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->d_cl_log + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
-    if (clearance_log) HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
-    HIPCHK(hipMemcpy2DAsync(F->d_ro_log + lay.lastu, nu * sizeof(double), F->d_out, res_info(T) * sizeof(double), nu * sizeof(double), B,
-                            hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
-    HIPCHK(hipMemcpyAsync(F->h_ro_log, F->d_ro_log, lay.bytes, hipMemcpyDeviceToHost, F->stream));
-    HIPCHK(hipStreamSynchronize(F->stream));                                    // the rollout's one wait
-    F->rob_pending = 0;
-    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;                       // their staged scenes have been consumed
-    F->roll_K = K;
-    memcpy(states_log, states, B * 3 * sizeof(double));                         // row 0: the input
-    memcpy(states_log + B * 3, F->h_ro_log + lay.states + B * 3 * sizeof(double), (size_t)K * B * 3 * sizeof(double));
-    memcpy(u_log, F->h_ro_log + lay.u, (size_t)K * B * 2 * sizeof(double));
-    memcpy(index_log, F->h_ro_log + lay.index, (size_t)K * B * sizeof(int32_t));
-    if (info_log) memcpy(info_log, F->h_ro_log + lay.info, (size_t)K * B * sizeof(rda_info));
-    memcpy(arrived_at, F->h_ro_log + lay.arrived, B * sizeof(int32_t));
-    if (clearance_log) memcpy(clearance_log, F->h_cl_log, (size_t)K * B * sizeof(double));
-    return RDA_OK;
+    return fleet_roll_fetch(F, K, lay, states, states_log, u_log, index_log, info_log, arrived_at, clearance_log);      // the rollout's one wait
 }
 extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
                                  int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
@@ -3700,6 +3763,243 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
     memcpy(clearance, F->h_cl_log, B * sizeof(double));
     return RDA_OK;
 }
+// ---- the members' worlds and the simulated sensor (lidar::k_raycast_fleet) -----------------------------------------------------------------------------
+// Every member's world in one call, in the layout of rda_fleet_upload_scenes with its own vertex stride `we`.  Built beside the old world and moved in
+// once everything is on the device: a refused call leaves the old world as it was.
+extern "C" int rda_fleet_upload_worlds(rda_fleet *F, const int32_t *counts, int we, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                       const double *vel)
+{
+    if (!F || !counts || we < 3 || we > RDA_EMAX) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    size_t total = 0;
+    for (size_t i = 0; i < B; ++i) { if (counts[i] < 0) return RDA_ERR_ARG; total += (size_t)counts[i]; }
+    if (total > 0 && (!kind || !nvert || !geom)) return RDA_ERR_ARG;
+    for (size_t j = 0; j < total; ++j) {
+        if (kind[j] == 0) { if (nvert[j] < 3 || nvert[j] > we) return RDA_ERR_ARG; }
+        else if (kind[j] != 1) return RDA_ERR_ARG;
+    }
+    hbuf::Group g;
+    double *dg, *db, *dv, *dst, *hst; int *dk, *dn; lidar::Ray *hray, *dray; scene::Move *hmv, *dmv; rollout::Clear *hcl, *dcl;
+    const size_t nt = total ? total : 1;                  // (an all-empty fleet still gets buffers to point at)
+    int rc = 0;
+    rc |= g.dev(&dg, nt * we * 2); rc |= g.dev(&db, nt * we * 2); rc |= g.dev(&dv, nt * 2); rc |= g.dev(&dk, nt); rc |= g.dev(&dn, nt);
+    rc |= g.dev(&dray, B); rc |= g.dev(&dmv, B); rc |= g.dev(&dcl, B); rc |= g.dev(&dst, 3 * B);
+    rc |= g.pin(&hray, B); rc |= g.pin(&hmv, B); rc |= g.pin(&hcl, B); rc |= g.pin(&hst, 3 * B);
+    if (rc) return RDA_ERR_HIP;
+    if (total > 0) {
+        HIPCHK(hipMemcpy(dg, geom, total * we * 2 * sizeof(double), hipMemcpyHostToDevice));
+        if (vel) HIPCHK(hipMemcpy(dv, vel, total * 2 * sizeof(double), hipMemcpyHostToDevice));      // (NULL: the zeros of the allocation - a standing world)
+        HIPCHK(hipMemcpy(dk, kind, total * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dn, nvert, total * sizeof(int), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipStreamSynchronize(F->stream));              // a ray cast of the old world may still be queued
+    F->world = std::move(g);
+    F->d_w_geom = dg; F->d_w_base = db; F->d_w_vel = dv; F->d_w_kind = dk; F->d_w_nvert = dn;
+    F->h_w_ray = hray; F->d_w_ray = dray; F->h_w_mv = hmv; F->d_w_mv = dmv; F->h_w_cl = hcl; F->d_w_cl = dcl; F->h_w_st = hst; F->d_w_st = dst;
+    F->w_e = we; F->w_total = total; F->w_have = 1;
+    F->w_counts.assign(counts, counts + B); F->w_off.assign(B, 0);
+    for (size_t i = 1; i < B; ++i) F->w_off[i] = F->w_off[i - 1] + (size_t)counts[i - 1];
+    return RDA_OK;
+}
+
+// test hook: the resident worlds' geometry as it stands, member-major [total][we][2]
+extern "C" int rda_debug_fleet_world(rda_fleet *F, double *geom, int32_t *n_total, int32_t *we)
+{
+    if (!F || !n_total) return RDA_ERR_ARG;
+    *n_total = F->w_have ? (int32_t)F->w_total : 0;
+    if (we) *we = F->w_have ? F->w_e : 0;
+    if (!F->w_have || F->w_total == 0 || !geom) return RDA_OK;
+    HIPCHK(hipStreamSynchronize(F->stream));
+    HIPCHK(hipMemcpy(geom, F->d_w_geom, F->w_total * F->w_e * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return RDA_OK;
+}
+
+// the argument rules of the sensor arrays (rda_fleet_raycast, rda_fleet_rollout_lidar); total: the beams of all members
+static int fleet_ray_check(const rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                           const double *range_max, size_t &total)
+{
+    if (!F || !n_beams || !angle_min || !angle_max || !range_min || !range_max || !F->w_have) return RDA_ERR_ARG;
+    total = 0;
+    for (int i = 0; i < F->B; ++i) { if (n_beams[i] < 0) return RDA_ERR_ARG; total += (size_t)n_beams[i]; }
+    for (int i = 0; i < F->B; ++i) if (n_beams[i] > lidar::MAXB) return RDA_ERR_UNSUPPORTED;
+    return RDA_OK;
+}
+struct FleetRayBuf {                      // the ranges of a ray cast, regrown for more beams
+    hbuf::Group g; double *h, *d; size_t cap;
+    int alloc(size_t n) { int rc = 0; cap = n; rc |= g.dev(&d, n); rc |= g.pin(&h, n); return rc ? RDA_ERR_HIP : RDA_OK; }
+    void commit(rda_fleet *F) { F->world_rng = std::move(g); F->d_w_ranges = d; F->h_w_ranges = h; F->w_rcap = cap; }
+};
+// the ray caster's member table for these sensors (member i's ranges at its beam offset in d_w_ranges) -> device; returns the longest scan
+static int fleet_ray_table(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                           const double *range_max, int &maxb)
+{
+    const size_t B = F->B;
+    size_t off = 0;
+    maxb = 0;
+    for (size_t i = 0; i < B; ++i) {
+        lidar::Ray &r = F->h_w_ray[i];
+        memset((void *)&r, 0, sizeof(r));
+        r.geom = F->d_w_geom + F->w_off[i] * F->w_e * 2; r.kind = F->d_w_kind + F->w_off[i]; r.nvert = F->d_w_nvert + F->w_off[i];
+        r.n = F->w_counts[i]; r.E = F->w_e; r.n_beams = n_beams[i];
+        r.angle_min = angle_min[i]; r.angle_max = angle_max[i]; r.range_min = range_min[i]; r.range_max = range_max[i];
+        r.ranges = F->d_w_ranges + off;
+        off += (size_t)n_beams[i];
+        maxb = n_beams[i] > maxb ? n_beams[i] : maxb;
+    }
+    HIPCHK(hipMemcpyAsync(F->d_w_ray, F->h_w_ray, B * sizeof(lidar::Ray), hipMemcpyHostToDevice, F->stream));
+    return RDA_OK;
+}
+static void fleet_ray_launch(rda_fleet *F, const double *poses, int maxb)
+{
+    if (maxb <= 0) return;
+    hipLaunchKernelGGL(lidar::k_raycast_fleet, dim3((unsigned)((maxb + lidar::RAY_NT - 1) / lidar::RAY_NT), (unsigned)F->B), dim3(lidar::RAY_NT), 0, F->stream,
+                       (const lidar::Ray *)F->d_w_ray, poses);
+}
+
+// the resident worlds as they stand, ray-cast from states [B][3]: one launch, one wait
+extern "C" int rda_fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                                 const double *range_max, const double *states, double *ranges)
+{
+    size_t total = 0;
+    int rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
+    if (rc != RDA_OK) return rc;
+    if (!states || (total > 0 && !ranges)) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    if (total > F->w_rcap) {
+        FleetRayBuf t;
+        if (t.alloc(total)) return RDA_ERR_HIP;
+        HIPCHK(hipStreamSynchronize(F->stream));
+        t.commit(F);
+    }
+    int maxb = 0;
+    rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
+    if (rc != RDA_OK) return rc;
+    memcpy(F->h_w_st, states, 3 * B * sizeof(double));
+    HIPCHK(hipMemcpyAsync(F->d_w_st, F->h_w_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    fleet_ray_launch(F, F->d_w_st, maxb);
+    HIPCHK(hipGetLastError());
+    if (total > 0) HIPCHK(hipMemcpyAsync(F->h_w_ranges, F->d_w_ranges, total * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    if (total > 0) memcpy(ranges, F->h_w_ranges, total * sizeof(double));
+    return RDA_OK;
+}
+
+// ---- rda_fleet_rollout_lidar: the closed loop around the simulated sensor -------------------------------------------------------------------------------
+// Per tick, on the fleet's stream: k_raycast_fleet from the pose the advance kernel left (row k of the device state log; row 0: the caller's) into
+// d_w_ranges, k_scan_fleet_at on those ranges at that pose, the ONE wait for the B box counts (they choose the LamMuZ launch form, apply the zero-box rule
+// and size the staging launches - fleet_scan_stage), then k_track_fleet, the ADMM launches and k_rollout_advance as in fleet_rollout_body, and behind them
+// (moving) scene::k_move_fleet on the WORLD and (clearance_log) k_clearance_fleet against the world.  Everything is allocated before tick 0.
+extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                       int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
+                                       const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
+                                       const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
+                                       int32_t *arrived_at, int32_t *nbox_log, double *clearance_log)
+{
+    if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
+    if (ind_range < 1 || goal_margin < 1 || !order || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
+    size_t total = 0;
+    int rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
+    if (rc != RDA_OK) return rc;
+    const size_t T = F->T, B = F->B;
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
+    }
+    for (const rda_handle *H : F->egos) {
+        if (H->follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member; a box has four vertices)
+        if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+    }
+    // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
+    FleetTrackTables ttrk; FleetClearLog tclr; FleetRayBuf tray;
+    hbuf::Group gtab, glog; rollout::Member *hm = nullptr, *dm = nullptr; EgoIO *hio = nullptr, *dio = nullptr; char *hlog = nullptr, *dlog = nullptr;
+    const bool need_trk = !F->d_trk_in, need_tab = !F->d_ro_m, need_log = !F->d_ro_log || K > F->roll_cap;
+    const bool need_clr = clearance_log && (size_t)K * B > F->cl_cap, need_ray = total > F->w_rcap;
+    std::vector<SceneGrow> grow(B), none(B);                                    // a raw scene for the most boxes a member's beams can give | per tick: nothing to grow
+    {
+        int bad = 0;
+        if (need_trk) bad |= ttrk.alloc(B);
+        if (need_tab) { bad |= gtab.dev(&dm, B); bad |= gtab.dev(&dio, 2 * B); bad |= gtab.pin(&hm, B); bad |= gtab.pin(&hio, 2 * B); }
+        if (need_log) { const size_t nb = roll_layout((size_t)K, B, T).bytes; bad |= glog.dev(&dlog, nb); bad |= glog.pin(&hlog, nb); }
+        if (need_clr) bad |= tclr.alloc((size_t)K * B);
+        if (need_ray) bad |= tray.alloc(total);
+        for (size_t i = 0; i < B && !bad; ++i) if (n_beams[i] > 0) bad |= scene_grow_alloc(F->egos[i], n_beams[i], grow[i]);
+        if (!bad) bad |= fleet_lidar_reserve(F, false);                         // (last: what it makes stays with the fleet)
+        if (bad) return RDA_ERR_HIP;
+    }
+    rc = fleet_refresh(F);                                                      // behind whatever the members still have queued
+    if (rc != RDA_OK) return rc;
+    HIPCHK(hipStreamSynchronize(F->stream));                                    // shorter blocks are freed below; the pinned tables are rewritten
+    if (need_trk) ttrk.commit(F);
+    if (need_tab) { F->roll = std::move(gtab); F->d_ro_m = dm; F->d_io_roll = dio; F->h_ro_m = hm; F->h_io_roll = hio; }
+    if (need_log) { F->roll_log = std::move(glog); F->d_ro_log = dlog; F->h_ro_log = hlog; F->roll_cap = K; }
+    if (need_clr) tclr.commit(F);
+    if (need_ray) tray.commit(F);
+    for (size_t i = 0; i < B; ++i) scene_grow_commit(F->egos[i], grow[i]);
+    F->roll_K = 0;                                                              // (until this rollout's logs are on the host)
+    RollView rv;
+    if (fleet_roll_view(F, nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
+    const RollLayout lay = roll_layout((size_t)K, B, T);
+    rollout::Logs lg;
+    rc = fleet_roll_inputs(F, lay, states, ref_speed, cur_index, threshold, ind_range, nom_u, lg);
+    if (rc != RDA_OK) return rc;
+    // the sensor, scan, move and clearance tables; tick 0's poses into row 0 of the device state log
+    int maxb = 0, gmax = 0;
+    rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
+    if (rc != RDA_OK) return rc;
+    memcpy(F->h_w_st, states, 3 * B * sizeof(double));
+    HIPCHK(hipMemcpyAsync(lg.states, F->h_w_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    {
+        size_t off = 0;
+        for (size_t i = 0; i < B; ++i) {
+            const rda_handle *H = F->egos[i];
+            lidar::Args &a = F->h_li_args[i];
+            memset((void *)&a, 0, sizeof(a));
+            a.n_beams = n_beams[i]; a.ranges = F->d_w_ranges + off; a.angle_min = angle_min[i]; a.angle_max = angle_max[i]; a.range_max = range_max[i];
+            a.eps = eps; a.min_samples = min_samples;                            // (the pose: k_scan_fleet_at's second argument)
+            a.boxes = F->d_li_boxes + i * lidar::MAXB * 8; a.count = F->h_li_count + 2 * i;
+            off += (size_t)n_beams[i];
+            scene::Move &m = F->h_w_mv[i]; rollout::Clear &c = F->h_w_cl[i];
+            memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c));
+            const size_t at = F->w_off[i];
+            m.geom = F->d_w_geom + at * F->w_e * 2; m.base = F->d_w_base + at * F->w_e * 2; m.vel = F->d_w_vel + at * 2;
+            m.kind = F->d_w_kind + at; m.nvert = F->d_w_nvert + at; m.n = F->w_counts[i]; m.E = F->w_e; m.dt = H->d.c.dt;
+            clear_robot(H, c);
+            c.geom = m.geom; c.kind = m.kind; c.nvert = m.nvert; c.n = m.n; c.E = F->w_e;
+            gmax = m.n * m.E > gmax ? m.n * m.E : gmax;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(F->d_li_args, F->h_li_args, B * sizeof(lidar::Args), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(F->d_w_mv, F->h_w_mv, B * sizeof(scene::Move), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(F->d_w_cl, F->h_w_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
+    const bool moves = moving && gmax > 0;
+    const dim3 gmove((unsigned)((gmax + 255) / 256), (unsigned)B);
+    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_w_mv);    // `base`: the world as the call finds it
+    for (int k = 0; k < K; ++k) {
+        const double *pose = lg.states + (size_t)k * B * 3;                     // where the advance kernel of tick k - 1 wrote the states
+        for (size_t i = 0; i < B; ++i) { F->h_li_count[2 * i] = 0; F->h_li_count[2 * i + 1] = 0; }
+        fleet_ray_launch(F, pose, maxb);
+        hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)F->d_li_args, pose);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(F->stream));                                // the tick's one wait: the B box counts
+        if (nbox_log) for (size_t i = 0; i < B; ++i) nbox_log[(size_t)k * B + i] = F->h_li_count[2 * i];
+        rc = fleet_scan_stage(F, none, nullptr, pose, order);
+        if (rc != RDA_OK) return rc;
+        const EgoIO *io = F->d_io_roll + (k == 0 ? 0 : B);
+        hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, io, F->d_trk_in, F->d_paths, F->d_lens, F->d_trk_out, (int)B);
+        rc = fleet_enqueue(F, io, 0);
+        if (rc != RDA_OK) return rc;
+        hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->d_ro_m,
+                           (const track::Out *)F->d_trk_out, F->d_trk_in, (double *)nullptr, lg, k, goal_margin, (int)B);
+        if (moves) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_w_mv, k + 1);     // where tick k + 1 finds it
+        if (clearance_log)                                                       // state k + 1 against the world of tick k + 1
+            hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_w_cl,
+                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->d_cl_log + (size_t)k * B, (int)B);
+    }
+    HIPCHK(hipGetLastError());
+    return fleet_roll_fetch(F, K, lay, states, states_log, u_log, index_log, info_log, arrived_at, clearance_log);
+}
+
 // What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls
 // of its next tick) and track::Out::end_heading (quirk Q12: what the heading of its path's last waypoint is now).  Either may be null.
 extern "C" int rda_fleet_rollout_last(rda_fleet *F, double *out_u, double *end_heading)

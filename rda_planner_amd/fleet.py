@@ -10,10 +10,35 @@ what `member.control(...)` would have returned.
 """
 import ctypes as C
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
 from ._capi import Info, dptr, iptr, f64
+
+SENSOR_FIELDS = ("number", "angle_min", "angle_max", "range_min", "range_max")
+WORLD_EMAX = 8              # RDA_EMAX of include/rda_hip.h: the most vertices a world polygon may have
+
+
+def sensor_arrays(sensors, B):
+    """B lidar sensors - mappings or objects (`World.lidar`) with `number`, `angle_min`, `angle_max`, `range_min`, `range_max` - as the member-major
+    arrays of rda_fleet_raycast: (n_beams, angle_min, angle_max, range_min, range_max)"""
+    if sensors is None or len(sensors) != B:
+        raise ValueError("one sensor per member")
+    rows = []
+    for s in sensors:
+        try:
+            row = [s[k] if hasattr(s, "keys") else getattr(s, k) for k in SENSOR_FIELDS]
+        except (KeyError, AttributeError, TypeError) as e:
+            raise ValueError(f"a sensor needs {', '.join(SENSOR_FIELDS)}: {e!r}") from None
+        n, lo, hi, rmin, rmax = int(row[0]), *(float(x) for x in row[1:])
+        if n != row[0] or n < 0:
+            raise ValueError(f"sensor: number = {row[0]!r} is not a beam count")
+        if not all(np.isfinite([lo, hi, rmin, rmax])) or hi < lo or rmin < 0 or rmax < rmin:
+            raise ValueError(f"sensor: need finite angle_min <= angle_max and 0 <= range_min <= range_max, got {row[1:]}")
+        rows.append((n, lo, hi, rmin, rmax))
+    cols = list(zip(*rows))
+    return (np.array(cols[0], np.int32),) + tuple(f64(c) for c in cols[1:])
 
 
 class Fleet:
@@ -176,6 +201,52 @@ class Fleet:
             raise RuntimeError(f"rda_fleet_upload_scans failed with code {rc}")
         return n
 
+    def upload_worlds(self, obstacle_lists):
+        """every member's WORLD - the true obstacles its simulated lidar sees (`raycast`, `rollout(lidar=)`), apart from the obstacles the planner
+        stages - resident on the device (rda_fleet_upload_worlds).  `obstacle_lists[i]`: the objects `control` takes (circles and polygons of up to 8
+        vertices, with their velocities); an empty list is an empty world.  A new upload replaces the old worlds."""
+        from .rda_solver import RDA_solver
+        if not getattr(self.api, "has_fleet_rollout_lidar", False):
+            raise RuntimeError("the loaded solver library has no world entry points (rda_fleet_upload_worlds)")
+        B = len(self.members)
+        if obstacle_lists is None or len(obstacle_lists) != B:
+            raise ValueError("Fleet.upload_worlds: one obstacle list per member")
+        every = [o for ol in obstacle_lists for o in ol]
+        if any(o.cone_type not in ("norm2", "Rpositive") for o in every):
+            raise ValueError("Fleet.upload_worlds: a world holds circles (norm2) and polygons (Rpositive)")
+        we = max([3] + [np.asarray(o.vertex).shape[1] for o in every if o.cone_type == "Rpositive"])
+        if we > WORLD_EMAX:
+            raise ValueError(f"Fleet.upload_worlds: a world polygon may have at most {WORLD_EMAX} vertices")
+        scene = RDA_solver._flatten_scene_numpy(SimpleNamespace(max_edge_num=we), every)
+        if scene is None or scene[0] != len(every):
+            raise ValueError("Fleet.upload_worlds: an obstacle cannot be expressed as a circle or a polygon with a velocity")
+        _, kind, nvert, geom, vel = scene
+        counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, B)
+        kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
+        rc = self.api.fleet_upload_worlds(self._handle, iptr(counts), int(we), iptr(kind), iptr(nvert), dptr(f64(geom)), dptr(f64(vel)))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_upload_worlds failed with code {rc}")
+
+    def raycast(self, states, sensors):
+        """every member's lidar scan of its resident world (`upload_worlds`) from `states[i]`, ray-cast on the device by one launch
+        (rda_fleet_raycast; `World.get_lidar_scan` is the specification).  `sensors[i]`: a mapping or object with `number`, `angle_min`, `angle_max`,
+        `range_min`, `range_max` (`World.lidar` has them).  Returns one scan dict per member in the ir-sim layout of `World.get_lidar_scan`, which
+        `control(scans=)` takes as it is."""
+        if not getattr(self.api, "has_fleet_rollout_lidar", False):
+            raise RuntimeError("the loaded solver library has no ray caster (rda_fleet_raycast)")
+        B = len(self.members)
+        nb, lo, hi, rmin, rmax = sensor_arrays(sensors, B)
+        if len(states) != B:
+            raise ValueError("Fleet.raycast: one state per member")
+        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+        ranges = np.zeros(max(int(nb.sum()), 1))
+        rc = self.api.fleet_raycast(self._handle, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges))
+        if rc < 0:
+            raise RuntimeError(f"rda_fleet_raycast failed with code {rc} (worlds are uploaded with Fleet.upload_worlds)")
+        cut = np.concatenate([[0], np.cumsum(nb)])
+        return [{"ranges": ranges[cut[i]:cut[i + 1]].copy(), "angle_min": lo[i], "angle_max": hi[i], "range_min": rmin[i], "range_max": rmax[i],
+                 "angle_increment": (hi[i] - lo[i]) / max(int(nb[i]) - 1, 1)} for i in range(B)]
+
     def sync(self):
         rc = self.api.fleet_sync(self._handle)
         if rc < 0:
@@ -195,17 +266,36 @@ class Fleet:
         (`resort=False`: in the staged order, for members with `obstacle_order=False`).  The caller's obstacle objects are NOT modified: to go on with
         `control` afterwards the caller advances them by `steps * dt`.  `clearance=True` (with `moving=True`, polygon robots) adds `"clearance"`
         (steps, B): every member's clearance after each tick against all obstacles of its scene, `scenarios.clearance` evaluated on the device.
-        Without `moving` a scene that moves is refused as before."""
+        Without `moving` a scene that moves is refused as before.
+        `lidar=sensors` (rda_fleet_rollout_lidar): the members plan against what a simulated lidar sees instead of resident scenes.  `sensors[i]` is
+        the sensor of `raycast`; `world=obstacle_lists` uploads the members' worlds first (`upload_worlds`; not needed when they are resident).  Per tick
+        every member's world is ray-cast from its pose on the device, the scan is clustered, boxed and staged as `control(scans=)` does (`scan_eps`,
+        `scan_min_samples`, the member's `obstacle_order`) with one short wait for the B box counts, then the tick runs as above.  `moving=True` puts
+        the WORLD forward between ticks by the rule above, `clearance=True` logs the clearance against the world (the true obstacles, not the boxes;
+        no `moving` needed).  The result has `"boxes"` (steps, B) as well: the boxes every member saw.  `resort` and `obstacle_lists` do not apply."""
         ms = self.members
         kwargs = dict(kwargs)
         obstacle_lists, moving, clearance = kwargs.pop("obstacle_lists", None), bool(kwargs.pop("moving", False)), bool(kwargs.pop("clearance", False))
+        lidar, world = kwargs.pop("lidar", None), kwargs.pop("world", None)
+        scan_eps, scan_min_samples = float(kwargs.pop("scan_eps", 2.0)), int(kwargs.pop("scan_min_samples", 6))
+        sensors = None
+        if lidar is None and world is not None:
+            raise ValueError("Fleet.rollout: world= belongs to lidar=")
+        if lidar is not None:
+            if obstacle_lists is not None:
+                raise ValueError("Fleet.rollout: pass either obstacle_lists= or lidar= (with world=), not both")
+            sensors = sensor_arrays(lidar, len(ms))
+            if not (scan_eps > 0) or scan_min_samples < 1:
+                raise ValueError("Fleet.rollout: scan_eps > 0 and scan_min_samples >= 1")
+            if not getattr(self.api, "has_fleet_rollout_lidar", False) or any(m.rda_obstacle for m in ms):
+                raise RuntimeError("Fleet.rollout(lidar=...) needs the lidar rollout (rda_fleet_rollout_lidar); there is no host fallback")
         if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
             raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
         if not getattr(self.api, "has_fleet_rollout", False):
             raise RuntimeError("the loaded solver library has no fleet rollout entry point (rda_fleet_rollout)")
         if moving and not getattr(self.api, "has_fleet_rollout_moving", False):
             raise RuntimeError("the loaded solver library has no rollout for moving scenes (rda_fleet_rollout_moving)")
-        if clearance and not moving:
+        if clearance and not moving and lidar is None:
             raise ValueError("Fleet.rollout: clearance=True needs moving=True (the clearance log belongs to rda_fleet_rollout_moving)")
         if clearance and any(m.car_tuple.cone_type == "norm2" for m in ms):
             raise RuntimeError("Fleet.rollout: the clearance log is for polygon robots; a circle (norm2) robot is not supported")
@@ -225,6 +315,8 @@ class Fleet:
             st[i] = np.asarray(m.state, float).ravel()[0:3]
             speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
             resident = resident and m._nominal_u() is None
+        if world is not None:
+            self.upload_worlds(world)
         if obstacle_lists is not None and not self._stage_all(obstacle_lists, st):
             for i, m in enumerate(ms):
                 m._stage_obstacles(obstacle_lists[i])
@@ -236,12 +328,20 @@ class Fleet:
         s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
         i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
         infos = (Info * (max(K, 1) * B))()
-        args = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)),
-                margins.pop(), 1 if resort else 0, dptr(nom_u), dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
+        head = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)), margins.pop())
+        logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
         c_log = np.zeros((max(K, 0), B)) if clearance else None
-        rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
+        if sensors is not None:
+            order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
+            b_log = np.zeros((max(K, 0), B), np.int32)
+            rc, name = self.api.fleet_rollout_lidar(*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples,
+                                                    iptr(order), 1 if moving else 0, *logs, iptr(b_log), dptr(c_log)), "rda_fleet_rollout_lidar"
+        else:
+            args = head + (1 if resort else 0, dptr(nom_u)) + logs
+            rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
+            name = "rda_fleet_rollout_moving" if moving else "rda_fleet_rollout"
         if rc < 0:
-            raise RuntimeError(f"{'rda_fleet_rollout_moving' if moving else 'rda_fleet_rollout'} failed with code {rc}")
+            raise RuntimeError(f"{name} failed with code {rc}")
         eh = np.zeros(B)
         rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
         if rc < 0:
@@ -262,6 +362,8 @@ class Fleet:
         out = {"states": s_log, "controls": u_log, "index": i_log, "iters": iters, "arrived_at": arrived}
         if clearance:
             out["clearance"] = c_log
+        if sensors is not None:
+            out["boxes"] = b_log
         return out
 
     def clearance(self, states):

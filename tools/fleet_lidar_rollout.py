@@ -1,0 +1,114 @@
+"""The simulated lidar of a fleet on the device, against the host code it replaces.  Two tables (output: profiles/fleet_lidar_rollout.txt):
+
+  (a) the sensor alone, per scan: Fleet.raycast (rda_fleet_raycast: lidar::k_raycast_fleet, one launch for the fleet, one wait) against the loop of
+      World.get_lidar_scan over the members, at B = 16 / 64, 360 / 1080 beams and 50 / 200 world obstacles per member (circles and rectangles);
+  (b) the closed loop, in ego-steps/s: Fleet.rollout(lidar=, world=) (rda_fleet_rollout_lidar: K ticks, one wait for the B box counts per tick) against the
+      host loop World.get_lidar_scan -> Fleet.control(scans=) -> World.step on the same members, K = 100 ticks.
+
+Every member has a world of its own (obstacles on both sides of its straight path, none on it) and a full-turn lidar of 15 m.  The baseline is the host loop
+on the same box; medians over --repeats.
+
+    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+T, N = 10, 10
+
+
+def world(k, beams, n_obs):
+    """member k's world: a robot at the head of the line (0, 20) -> (60, 20), n_obs circles and rectangles 4 .. 12 m to both sides of it"""
+    from rda_planner_amd import world as irsim
+    rng = np.random.default_rng(71000 + k)
+    obstacles = []
+    for j in range(n_obs):
+        side = 1.0 if j % 2 else -1.0
+        pos = [float(rng.uniform(2.0, 70.0)), 20.0 + side * float(rng.uniform(4.0, 12.0)), float(rng.uniform(-np.pi, np.pi))]
+        shape = {"name": "circle", "radius": float(rng.uniform(0.3, 0.8))} if j % 3 == 0 else \
+                {"name": "rectangle", "length": float(rng.uniform(0.5, 2.0)), "width": float(rng.uniform(0.3, 1.2))}
+        obstacles.append({"number": 1, "distribution": {"name": "manual"}, "state": [pos], "shape": [shape]})
+    cfg = {"world": {"step_time": 0.1, "width": 100, "height": 100},
+           "robot": [{"kinematics": {"name": "acker"}, "shape": {"name": "rectangle", "length": 4.6, "width": 1.6, "wheelbase": 3}, "state": [1.0, 20.0, 0.0],
+                      "sensors": [{"type": "lidar2d", "range_max": 15.0, "angle_range": 2 * np.pi - 0.01, "number": beams}]}],
+           "obstacle": obstacles}
+    return irsim.World(cfg)
+
+
+def fleet(B, beams, n_obs):
+    from rda_planner_amd import scenarios as sc
+    from rda_planner_amd.fleet import Fleet
+    from rda_planner_amd.mpc import MPC
+    envs = [world(k, beams, n_obs) for k in range(B)]
+    ms = [MPC(sc.rectangle_robot(), sc.line_path([0, 20, 0], [90, 20, 0]), receding=T, max_edge_num=4, max_obs_num=N, iter_num=2) for _ in envs]
+    return Fleet(ms), envs
+
+
+def sensor_table(args):
+    print("(a) one scan of every member, ms per fleet scan (medians of %d): World.get_lidar_scan in a loop | Fleet.raycast" % args.repeats)
+    print("%4s %6s %9s | %12s | %12s | %s" % ("B", "beams", "obstacles", "host loop", "Fleet.raycast", "host / device"))
+    for B in args.fleets:
+        for beams in args.beams:
+            for n_obs in args.obstacles:
+                f, envs = fleet(B, beams, n_obs)
+                f.upload_worlds([e.obstacles for e in envs])
+                states, sensors = [e.robot.state for e in envs], [e.lidar for e in envs]
+                dev = f.raycast(states, sensors)                                   # first use: the ranges buffer
+                host = [e.get_lidar_scan() for e in envs]
+                worst = max(float(np.abs(d["ranges"] - h["ranges"]).max()) for d, h in zip(dev, host))
+                th, td = [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter(); [e.get_lidar_scan() for e in envs]; th.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter(); f.raycast(states, sensors); td.append(time.perf_counter() - t0)
+                print("%4d %6d %9d | %12.3f | %12.3f | %7.1fx   (largest |device - host| %.1e m)"
+                      % (B, beams, n_obs, 1e3 * np.median(th), 1e3 * np.median(td), np.median(th) / np.median(td), worst))
+                f.close()
+
+
+def loop_table(args):
+    beams, n_obs, K = args.beams[0], args.obstacles[0], args.K
+    print("(b) closed loop of K = %d ticks, %d beams, %d world obstacles per member, ego-steps/s (medians of %d): get_lidar_scan -> Fleet.control(scans=) -> "
+          "World.step | Fleet.rollout(lidar=, world=)" % (K, beams, n_obs, args.repeats))
+    print("%4s | %12s | %12s | %s" % ("B", "host loop", "rollout", "rollout / host loop"))
+    for B in args.fleets:
+        ra, rb = [], []
+        for _ in range(args.repeats):
+            f, envs = fleet(B, beams, n_obs)
+            t0 = time.perf_counter()
+            for _k in range(K):
+                res = f.control([e.robot.state.copy() for e in envs], 4.0, scans=[e.get_lidar_scan() for e in envs])
+                for e, (u, _info) in zip(envs, res):
+                    e.step(u)
+            ra.append(B * K / (time.perf_counter() - t0))
+            f.close()
+            f, envs = fleet(B, beams, n_obs)
+            kw = dict(lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs])
+            out = f.rollout([e.robot.state.copy() for e in envs], 4.0, 2, **kw)    # first use: tables, logs and the members' raw scenes
+            t0 = time.perf_counter()
+            out = f.rollout([out["states"][-1, i].reshape(3, 1) for i in range(B)], 4.0, K, lidar=kw["lidar"])
+            rb.append(B * K / (time.perf_counter() - t0))
+            f.close()
+        print("%4d | %12.0f | %12.0f | %.1fx   (boxes seen per tick and member: %.1f)" % (B, np.median(ra), np.median(rb), np.median(rb) / np.median(ra), out["boxes"].mean()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
+    ap.add_argument("--fleets", type=ints, default=[16, 64])
+    ap.add_argument("--beams", type=ints, default=[360, 1080])
+    ap.add_argument("--obstacles", type=ints, default=[50, 200])
+    ap.add_argument("--K", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=3)
+    args = ap.parse_args()
+    sensor_table(args)
+    print()
+    loop_table(args)
+
+
+if __name__ == "__main__":
+    main()
