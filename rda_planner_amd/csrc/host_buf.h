@@ -55,6 +55,13 @@ private:
     }
 };
 
+template <typename T> struct Pair {          // n T on the device and their pinned mirror: views into the Group that owns both
+    T *h = nullptr, *d = nullptr; size_t n = 0;
+    int alloc(Group &g, size_t count) { const int rc = g.dev(&d, count) | g.pin(&h, count); n = rc ? 0 : count; return rc; }     // (refused: n stays 0)
+    hipError_t push(hipStream_t s) const { return hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s); }                        // all of the mirror
+    hipError_t pull(hipStream_t s, size_t count) const { return hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s); }      // the first count
+};
+
 template <typename Hd, hipError_t (*Destroy)(Hd)> class Res {     // a stream or an event, move-only
 public:
     Res() = default;

@@ -2914,106 +2914,140 @@ __global__ __launch_bounds__(su::NT) void k_finish_fleet(const Dev *devs, const 
     finish_body(d, f);
 }
 
+// The table sets a fleet makes on first use.  Each owns its allocations (g: zeroed, counted) beside the views into them - a device array with its pinned
+// mirror (hbuf::Pair) or a plain pointer where only one side exists - and is built beside the fleet (alloc: all or RDA_ERR_HIP).  The call that needs a set
+// moves it in (F->set = std::move(t)) only when it can no longer be refused: a refused allocation leaves the fleet as it was.  have(): allocated.
+struct FleetTrack {                       // tracked stepping (device-side pre_process): rda_fleet_step_tracked, the rollouts
+    hbuf::Group g; hbuf::Pair<track::In> in; hbuf::Pair<track::Out> out; hbuf::Pair<double *> paths; hbuf::Pair<int> lens; hbuf::Pair<EgoIO> io;
+    int alloc(size_t B) { return (in.alloc(g, B) | out.alloc(g, B) | paths.alloc(g, B) | lens.alloc(g, B) | io.alloc(g, B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return in.d != nullptr; }
+};
+struct FleetResort {                      // rda_fleet_scene_resort, the rollouts: the members' scene arguments, their robots' positions [B][2]
+    hbuf::Group g; hbuf::Pair<scene::Args> sc; hbuf::Pair<double> rob;
+    int alloc(size_t B) { return (sc.alloc(g, B) | rob.alloc(g, 2 * B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return sc.d != nullptr; }
+};
+// fleet lidar (rda_fleet_scan_boxes / rda_fleet_upload_scans): per member the scan kernel's arguments, the fill kernel's and the conversion kernels'; the
+// boxes of the last scans [B][MAXB][4][2] on the device; pinned, read / written by the kernel itself: the concatenated ranges [B * MAXB], the counters [B][2]
+struct FleetLidar {
+    hbuf::Group g; hbuf::Pair<lidar::Args> args; hbuf::Pair<lidar::Fill> fill; hbuf::Pair<scene::Args> sc;
+    double *d_boxes = nullptr, *h_ranges = nullptr; int *h_count = nullptr;
+    int alloc(size_t B)
+    {
+        return (args.alloc(g, B) | fill.alloc(g, B) | sc.alloc(g, B) | g.dev(&d_boxes, B * lidar::MAXB * 8) | g.pin(&h_ranges, B * lidar::MAXB) |
+                g.pin(&h_count, 2 * B)) ? RDA_ERR_HIP : RDA_OK;
+    }
+    bool have() const { return d_boxes != nullptr; }
+};
+struct FleetLidarHost {                   // for rda_fleet_scan_boxes alone: the host's copy of labels and boxes (pinned, written by the kernel)
+    hbuf::Group g; double *h_boxes = nullptr; int *h_labels = nullptr;
+    int alloc(size_t B) { return (g.pin(&h_boxes, B * lidar::MAXB * 8) | g.pin(&h_labels, B * lidar::MAXB)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return h_boxes != nullptr; }
+};
+// the rollouts: the advance kernel's member table, the io tables of tick 0 | of the later ticks [2][B] (results in the fleet's `out` whatever the members'
+// zero_copy says)
+struct FleetRollTables {
+    hbuf::Group g; hbuf::Pair<rollout::Member> m; hbuf::Pair<EgoIO> io;
+    int alloc(size_t B) { return (m.alloc(g, B) | io.alloc(g, 2 * B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return m.d != nullptr; }
+};
+struct RollLayout { size_t states, u, endh, lastu, info, index, arrived, bytes; };     // byte offsets of the log block's parts (rollout::Logs; lastu [B][2][T]: the last tick's controls)
+static RollLayout roll_layout(size_t K, size_t B, size_t T)
+{
+    RollLayout l;
+    l.states = 0; l.u = l.states + (K + 1) * B * 3 * sizeof(double); l.endh = l.u + K * B * 2 * sizeof(double); l.lastu = l.endh + B * sizeof(double);
+    l.info = l.lastu + B * traj_u(T) * sizeof(double);
+    l.index = l.info + K * B * sizeof(rda_info); l.arrived = l.index + K * B * sizeof(int); l.bytes = l.arrived + B * sizeof(int);
+    return l;
+}
+struct FleetRollLog {                     // the rollouts' log block of `cap` ticks (roll_layout), regrown for a longer rollout
+    hbuf::Group g; hbuf::Pair<char> log; int cap = 0;
+    int alloc(int K, size_t B, size_t T) { cap = K; return log.alloc(g, roll_layout((size_t)K, B, T).bytes) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return log.d != nullptr; }
+};
+// rda_fleet_rollout_moving, rda_fleet_clearance: per member the move kernel's and the clearance kernel's arguments, the members' scene arguments as they
+// stand (resort = 0: slots rebuilt in the staged order), the states of rda_fleet_clearance [B][3]
+struct FleetMove {
+    hbuf::Group g; hbuf::Pair<scene::Move> mv; hbuf::Pair<rollout::Clear> cl; hbuf::Pair<scene::Args> sc; hbuf::Pair<double> st;
+    int alloc(size_t B) { return (mv.alloc(g, B) | cl.alloc(g, B) | sc.alloc(g, B) | st.alloc(g, 3 * B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return mv.d != nullptr; }
+};
+struct FleetSnapshot {                    // rda_fleet_rollout_moving: the snapshot of all members' raw geometry (cap doubles), regrown when a call needs more
+    hbuf::Group g; double *d = nullptr; size_t cap = 0;
+    int alloc(size_t n) { cap = n; return g.dev(&d, n) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return d != nullptr; }
+};
+struct FleetDoubles {                     // v.n doubles, regrown when a call needs more: the clearance log [K][B] | the ranges of the last ray cast
+    hbuf::Group g; hbuf::Pair<double> v;
+    int alloc(size_t n) { return v.alloc(g, n) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return v.d != nullptr; }
+};
+// The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
+// tick overwrites with boxes.  Member-major geometry [total][e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
+// vertex counts; off[i]: member i's first obstacle.  Per member the ray caster's, the move kernel's and the clearance kernel's arguments and the poses of
+// rda_fleet_raycast [B][3].
+struct FleetWorld {
+    hbuf::Group g; double *geom = nullptr, *base = nullptr, *vel = nullptr; int *kind = nullptr, *nvert = nullptr; int e = 0; size_t total = 0;
+    std::vector<int> counts; std::vector<size_t> off;
+    hbuf::Pair<lidar::Ray> ray; hbuf::Pair<scene::Move> mv; hbuf::Pair<rollout::Clear> cl; hbuf::Pair<double> st;
+    int alloc(size_t B, const int32_t *member_counts, int we)
+    {
+        e = we; counts.assign(member_counts, member_counts + B); off.assign(B, 0);
+        for (size_t i = 1; i < B; ++i) off[i] = off[i - 1] + (size_t)counts[i - 1];
+        total = off[B - 1] + (size_t)counts[B - 1];
+        const size_t nt = total ? total : 1;              // (an all-empty fleet still gets buffers to point at)
+        return (g.dev(&geom, nt * e * 2) | g.dev(&base, nt * e * 2) | g.dev(&vel, nt * 2) | g.dev(&kind, nt) | g.dev(&nvert, nt) |
+                ray.alloc(g, B) | mv.alloc(g, B) | cl.alloc(g, B) | st.alloc(g, 3 * B)) ? RDA_ERR_HIP : RDA_OK;
+    }
+    bool have() const { return geom != nullptr; }
+};
+
 struct rda_fleet {                        // (owns its buffers, event and stream like rda_handle)
     int B;
     std::vector<rda_handle *> egos;
-    Dev *h_devs, *d_devs;                 // pinned mirror / device array
+    hbuf::Group mem;                      // what rda_fleet_create makes:
+    hbuf::Pair<Dev> devs;                 // the members' records
     EgoIO *h_io, *d_io_step, *d_io_trace;
-    double *h_in, *d_in;                  // step path, per ego: a step block (step_doubles)
-    double *h_out, *d_out;                // per ego: u | s, the head of a result block (res_info doubles)
-    rda_info *h_info, *d_info;
+    hbuf::Pair<double> in;                // step path, per ego: a step block (step_doubles)
+    hbuf::Pair<double> out;               // per ego: u | s, the head of a result block (res_info doubles)
+    hbuf::Pair<rda_info> info;
     int T, iter_num, J, rows, lmz_split;
     size_t su_lds;
-    // tracked stepping (device-side pre_process), allocated on first use
-    track::In *h_trk_in, *d_trk_in; track::Out *h_trk_out, *d_trk_out;
-    double **h_paths, **d_paths; int *h_lens, *d_lens; EgoIO *h_io_track, *d_io_track;
-    // rda_fleet_scene_resort (allocated on first use): the members' scene arguments, their robots' positions; rob_pending: a copy out of h_rob may be queued
-    scene::Args *h_sc, *d_sc; double *h_rob, *d_rob; int rob_pending;
-    // fleet lidar (rda_fleet_scan_boxes / rda_fleet_upload_scans), allocated on first use: per member the scan kernel's arguments, the fill kernel's and the
-    // conversion kernels' (pinned mirror / device array); the boxes of the last scans [B][MAXB][4][2] on the device; pinned, read / written by the kernel
-    // itself: the concatenated ranges [B * MAXB], the counters [B][2] - and, for rda_fleet_scan_boxes alone, the host's copy of labels and boxes
-    lidar::Args *h_li_args, *d_li_args; lidar::Fill *h_li_fill, *d_li_fill; scene::Args *h_li_sc, *d_li_sc;
-    double *d_li_boxes, *h_li_ranges, *h_li_boxes; int *h_li_count, *h_li_labels;
-    // rda_fleet_rollout (allocated on first use): the advance kernel's member table, the io tables of tick 0 | of the later ticks [2][B] (results in d_out
-    // whatever the members' zero_copy says); the log block of roll_cap ticks (roll_layout) on the device and in pinned memory, regrown for a longer rollout
-    rollout::Member *h_ro_m, *d_ro_m; EgoIO *h_io_roll, *d_io_roll; char *h_ro_log, *d_ro_log; int roll_cap, roll_K;
-    hbuf::Group mem, trk, resort, lidar, lidar_host;      // the tables above; those of tracked stepping; of rda_fleet_scene_resort; of the fleet lidar (scan, staging | host copies)
-    // rda_fleet_rollout_moving, rda_fleet_clearance (allocated on their first use): per member the move kernel's and the clearance kernel's arguments, the
-    // members' scene arguments as they stand (resort = 0: slots rebuilt in the staged order), the states of rda_fleet_clearance [B][3]; the snapshot of all
-    // members' raw geometry (mv_cap doubles) and the clearance log [cl_cap] on the device and in pinned memory, both regrown when a call needs more
-    scene::Move *h_mv, *d_mv; rollout::Clear *h_cl, *d_cl; scene::Args *h_mv_sc, *d_mv_sc; double *h_cl_st, *d_cl_st;
-    double *d_mv_base, *h_cl_log, *d_cl_log; size_t mv_cap, cl_cap;
-    hbuf::Group roll, roll_log;                           // of rda_fleet_rollout: tables | logs
-    hbuf::Group mov, mov_base, clr_log;                   // of rda_fleet_rollout_moving / rda_fleet_clearance: tables | snapshot | clearance log
-    // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
-    // tick overwrites with boxes.  Member-major geometry [w_total][w_e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
-    // vertex counts; w_off[i]: member i's first obstacle.  Per member the ray caster's, the move kernel's and the clearance kernel's arguments (pinned mirror /
-    // device array) and the poses of rda_fleet_raycast [B][3].  The ranges of the last ray cast [w_rcap] on the device and in pinned memory, regrown on demand.
-    double *d_w_geom, *d_w_base, *d_w_vel; int *d_w_kind, *d_w_nvert; int w_e, w_have; size_t w_total;
-    std::vector<int> w_counts; std::vector<size_t> w_off;
-    lidar::Ray *h_w_ray, *d_w_ray; scene::Move *h_w_mv, *d_w_mv; rollout::Clear *h_w_cl, *d_w_cl; double *h_w_st, *d_w_st;
-    double *d_w_ranges, *h_w_ranges; size_t w_rcap;
-    hbuf::Group world, world_rng;
+    FleetTrack trk;
+    FleetResort res; int rob_pending;     // rob_pending: a copy out of res.rob.h may be queued
+    FleetLidar li; FleetLidarHost li_host;
+    FleetRollTables ro; FleetRollLog ro_log; int roll_K;      // roll_K: the ticks of the rollout whose logs are on the host
+    FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
+    FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
 
-// The tables a fleet makes on first use: built beside the fleet (alloc: zeroed, all or RDA_ERR_HIP) and moved in only when the call that needs them can no
-// longer be refused (commit) - a refused allocation leaves the fleet as it was.
-struct FleetTrackTables {                 // rda_fleet_step_tracked, rda_fleet_rollout
-    hbuf::Group g; track::In *hti, *dti; track::Out *hto, *dto; double **hp, **dp; int *hl, *dl; EgoIO *hio, *dio;
-    int alloc(size_t B)
-    {
-        int rc = 0;
-        rc |= g.dev(&dti, B); rc |= g.dev(&dto, B); rc |= g.dev(&dp, B); rc |= g.dev(&dl, B); rc |= g.dev(&dio, B);
-        rc |= g.pin(&hti, B); rc |= g.pin(&hto, B); rc |= g.pin(&hp, B); rc |= g.pin(&hl, B); rc |= g.pin(&hio, B);
-        return rc ? RDA_ERR_HIP : RDA_OK;
-    }
-    void commit(rda_fleet *F)
-    {
-        F->trk = std::move(g);
-        F->d_trk_in = dti; F->d_trk_out = dto; F->d_paths = dp; F->d_lens = dl; F->d_io_track = dio;
-        F->h_trk_in = hti; F->h_trk_out = hto; F->h_paths = hp; F->h_lens = hl; F->h_io_track = hio;
-    }
-};
-struct FleetResortTables {                // rda_fleet_scene_resort, rda_fleet_rollout
-    hbuf::Group g; scene::Args *hsc, *dsc; double *hrob, *drob;
-    int alloc(size_t B)
-    {
-        int rc = 0;
-        rc |= g.dev(&dsc, B); rc |= g.dev(&drob, 2 * B); rc |= g.pin(&hsc, B); rc |= g.pin(&hrob, 2 * B);
-        return rc ? RDA_ERR_HIP : RDA_OK;
-    }
-    void commit(rda_fleet *F) { F->resort = std::move(g); F->d_sc = dsc; F->d_rob = drob; F->h_sc = hsc; F->h_rob = hrob; }
-};
-struct FleetMoveTables {                  // rda_fleet_rollout_moving, rda_fleet_clearance
-    hbuf::Group g; scene::Move *hmv, *dmv; rollout::Clear *hcl, *dcl; scene::Args *hsc, *dsc; double *hst, *dst;
-    int alloc(size_t B)
-    {
-        int rc = 0;
-        rc |= g.dev(&dmv, B); rc |= g.dev(&dcl, B); rc |= g.dev(&dsc, B); rc |= g.dev(&dst, 3 * B);
-        rc |= g.pin(&hmv, B); rc |= g.pin(&hcl, B); rc |= g.pin(&hsc, B); rc |= g.pin(&hst, 3 * B);
-        return rc ? RDA_ERR_HIP : RDA_OK;
-    }
-    void commit(rda_fleet *F)
-    {
-        F->mov = std::move(g);
-        F->d_mv = dmv; F->d_cl = dcl; F->d_mv_sc = dsc; F->d_cl_st = dst; F->h_mv = hmv; F->h_cl = hcl; F->h_mv_sc = hsc; F->h_cl_st = hst;
-    }
-};
-struct FleetClearLog {                    // the clearance log, regrown for a longer rollout
-    hbuf::Group g; double *h, *d; size_t cap;
-    int alloc(size_t n) { int rc = 0; cap = n; rc |= g.dev(&d, n); rc |= g.pin(&h, n); return rc ? RDA_ERR_HIP : RDA_OK; }
-    void commit(rda_fleet *F) { F->clr_log = std::move(g); F->d_cl_log = d; F->h_cl_log = h; F->cl_cap = cap; }
-};
+// The refresh of a pinned mirror, in its two halves; get(i): record i as it should be now.  mirror_differs: does any record differ from the mirror?
+// mirror_upload: the mirror rewritten and pushed.  Between the two the caller waits for the fleet's stream (an earlier copy out of the mirror may still be
+// queued): the wait is the caller's, because where one wait covers several tables the caller asks about all of them first.
+template <typename T, typename Get> static bool mirror_differs(const hbuf::Pair<T> &p, Get get)
+{
+    for (size_t i = 0; i < p.n; ++i) { const T &r = get(i); if (memcmp(&r, &p.h[i], sizeof(T)) != 0) return true; }
+    return false;
+}
+template <typename T, typename Get> static hipError_t mirror_upload(const hbuf::Pair<T> &p, Get get, hipStream_t stream)
+{
+    for (size_t i = 0; i < p.n; ++i) { const T &r = get(i); memcpy((void *)&p.h[i], &r, sizeof(T)); }
+    return p.push(stream);
+}
+template <typename T> static auto records(const std::vector<T> &v) { return [&v](size_t i) -> const T & { return v[i]; }; }
+static auto member_devs(const rda_fleet *F) { return [F](size_t i) -> const Dev & { return F->egos[i]->d; }; }
+static auto member_paths(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->d_path; }; }
+static auto member_lens(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path_len; }; }
 
-// Member i's locations on the step path: its step block in d_in (in_u: nominal controls that live elsewhere, else null), its u | s block
+// Member i's locations on the step path: its step block in `in` (in_u: nominal controls that live elsewhere, else null), its u | s block
 // under out_base, its info under info_base
 static EgoIO fleet_member_io(const rda_fleet *F, size_t i, const double *in_u, double *out_base, rda_info *info_base)
 {
     const size_t T = F->T;
     EgoIO e;
-    e.s = F->d_in + i * step_doubles(T); e.u = in_u ? in_u : e.s + step_u(T); e.ref = e.s + step_ref(T); e.speed = e.s + step_speed(T);
+    e.s = F->in.d + i * step_doubles(T); e.u = in_u ? in_u : e.s + step_u(T); e.ref = e.s + step_ref(T); e.speed = e.s + step_speed(T);
     e.out_u = out_base + i * res_info(T); e.out_s = e.out_u + res_s(T); e.info = info_base + i;
     return e;
 }
@@ -3021,7 +3055,7 @@ static EgoIO fleet_member_io(const rda_fleet *F, size_t i, const double *in_u, d
 static void fleet_result_out(const rda_fleet *F, size_t i, double *out_u, double *out_s, rda_info *info)
 {
     const size_t T = F->T;
-    result_out(F->h_out + i * res_info(T), F->h_info + i, T, out_u + i * traj_u(T), out_s + i * traj_s(T), info ? info + i : nullptr);
+    result_out(F->out.h + i * res_info(T), F->info.h + i, T, out_u + i * traj_u(T), out_s + i * traj_s(T), info ? info + i : nullptr);
 }
 
 extern "C" void rda_fleet_destroy(rda_fleet *F)
@@ -3051,12 +3085,9 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
     HIPCHK(hipEventCreateWithFlags(F->ev.out(), hipEventDisableTiming));
     const size_t T = c.T, nin = step_doubles(T), nout = res_info(T);
     hbuf::Group &m = F->mem;
-    int rc = 0;
-    rc |= m.dev(&F->d_devs, (size_t)B); rc |= m.dev(&F->d_io_step, (size_t)B); rc |= m.dev(&F->d_io_trace, (size_t)B);
-    rc |= m.dev(&F->d_in, B * nin); rc |= m.dev(&F->d_out, B * nout); rc |= m.dev(&F->d_info, (size_t)B);
-    rc |= m.pin(&F->h_devs, (size_t)B); rc |= m.pin(&F->h_io, (size_t)B); rc |= m.pin(&F->h_in, B * nin); rc |= m.pin(&F->h_out, B * nout); rc |= m.pin(&F->h_info, (size_t)B);
-    if (rc) return RDA_ERR_HIP;
-    for (int i = 0; i < B; ++i) F->h_io[i] = fleet_member_io(F, i, nullptr, F->d_out, F->d_info);
+    if (F->devs.alloc(m, (size_t)B) | F->in.alloc(m, B * nin) | F->out.alloc(m, B * nout) | F->info.alloc(m, (size_t)B) |
+        m.dev(&F->d_io_step, (size_t)B) | m.dev(&F->d_io_trace, (size_t)B) | m.pin(&F->h_io, (size_t)B)) return RDA_ERR_HIP;
+    for (int i = 0; i < B; ++i) F->h_io[i] = fleet_member_io(F, i, nullptr, F->out.d, F->info.d);
     HIPCHK(hipMemcpy(F->d_io_step, F->h_io, B * sizeof(EgoIO), hipMemcpyHostToDevice));
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su_fleet<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds)));
     HIPCHK(hipFuncSetAttribute((const void *)k_finish_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F->su_lds));
@@ -3077,9 +3108,7 @@ static void fleet_refresh_flags(rda_fleet *F)
 // stream then waits for whatever the members still have in flight on their own streams (obstacle uploads)
 static int fleet_refresh(rda_fleet *F)
 {
-    bool changed = false;
     for (int i = 0; i < F->B; ++i) {
-        if (memcmp(&F->h_devs[i], &F->egos[i]->d, sizeof(Dev)) != 0) changed = true;
         // the fleet's stream must run behind whatever a member still has queued on its OWN stream (an upload, a solo step).  An idle member stream needs no
         // edge: the event record + wait pair per member cost ~8 us of host time each, twice per fleet tick (re-sort + step) = 1 ms of a 4.2 ms tick of the
         // 64-ego closed loop with the GPU idle meanwhile (rocprofv3 kernel trace cut into ticks, tools/experiments/fleet_tick_trace.sh, round 6)
@@ -3091,10 +3120,9 @@ static int fleet_refresh(rda_fleet *F)
         HIPCHK(hipStreamWaitEvent(F->stream, F->ev, 0));
     }
     fleet_refresh_flags(F);
-    if (changed) {
+    if (mirror_differs(F->devs, member_devs(F))) {
         HIPCHK(hipStreamSynchronize(F->stream));            // an earlier copy out of the pinned mirror may still be queued
-        for (int i = 0; i < F->B; ++i) memcpy(&F->h_devs[i], &F->egos[i]->d, sizeof(Dev));
-        HIPCHK(hipMemcpyAsync(F->d_devs, F->h_devs, F->B * sizeof(Dev), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
     }
     return RDA_OK;
 }
@@ -3102,24 +3130,25 @@ static int fleet_refresh(rda_fleet *F)
 static int fleet_enqueue(rda_fleet *F, const EgoIO *io, int k)
 {
     const int B = F->B;
+    const Dev *devs = F->devs.d;
     for (int it = 0; it < F->iter_num; ++it) {          // iteration 0 resets every member's control block (su_body)
-        RDA_SU_DISPATCH(F->T, hipLaunchKernelGGL(k_su_fleet<TT>, dim3(B), dim3(su::NT), F->su_lds, F->stream, F->d_devs, io, it, k));
+        RDA_SU_DISPATCH(F->T, hipLaunchKernelGGL(k_su_fleet<TT>, dim3(B), dim3(su::NT), F->su_lds, F->stream, devs, io, it, k));
         // (The fleet's own selection of the LamMuZ form, not lammuz_plan: no dense threshold, and other clamps of the work-list grid -
         // a shared plan would branch on its caller.)
         constexpr int NTH = LMZ_NTH;
         const int nbr = F->T * F->J, nfin = (nbr + FPB - 1) / FPB, nbp = packed_grid(F->T, F->J);       // one workgroup per (stage, GS-slot block), XCD-aware order
         if (F->rows && F->lmz_split) {
-            hipLaunchKernelGGL(k_lammuz_fleet_rows_fast, dim3(nbp, B), dim3(NTH), 0, F->stream, F->d_devs, it);
+            hipLaunchKernelGGL(k_lammuz_fleet_rows_fast, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, it);
             int ne = nbr / 8; if (ne < 8) ne = 8; if (ne > 128) ne = 128;
-            hipLaunchKernelGGL(k_lammuz_fleet_enum, dim3(ne, B), dim3(NTH), 0, F->stream, F->d_devs, it);
-            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, F->d_devs, io, it, k);
-        } else if (F->rows) hipLaunchKernelGGL(k_lammuz_fleet_rows, dim3(nbp, B), dim3(NTH), 0, F->stream, F->d_devs, io, it, k);
+            hipLaunchKernelGGL(k_lammuz_fleet_enum, dim3(ne, B), dim3(NTH), 0, F->stream, devs, it);
+            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
+        } else if (F->rows) hipLaunchKernelGGL(k_lammuz_fleet_rows, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, io, it, k);
         else {
-            hipLaunchKernelGGL(k_lammuz_fleet, dim3(nbr * GS / 4, B), dim3(256), 0, F->stream, F->d_devs, it);
-            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, F->d_devs, io, it, k);
+            hipLaunchKernelGGL(k_lammuz_fleet, dim3(nbr * GS / 4, B), dim3(256), 0, F->stream, devs, it);
+            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
         }
     }
-    hipLaunchKernelGGL(k_finish_fleet, dim3(B), dim3(su::NT), F->su_lds, F->stream, F->d_devs, io, k);
+    hipLaunchKernelGGL(k_finish_fleet, dim3(B), dim3(su::NT), F->su_lds, F->stream, devs, io, k);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
@@ -3129,19 +3158,19 @@ extern "C" int rda_fleet_step(rda_fleet *F, const double *nom_s, const double *n
                               double *out_u, double *out_s, rda_info *info)
 {
     if (!F || !nom_s || !nom_u || !ref_s || !ref_speed || !out_u || !out_s) return RDA_ERR_ARG;
-    const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), nout = res_info(T), B = F->B;
+    const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), B = F->B;
     for (size_t i = 0; i < B; ++i) {
-        double *q = F->h_in + i * nin;
+        double *q = F->in.h + i * nin;
         memcpy(q, nom_s + i * ns, ns * sizeof(double)); memcpy(q + step_u(T), nom_u + i * nu, nu * sizeof(double));
         memcpy(q + step_ref(T), ref_s + i * ns, ns * sizeof(double)); q[step_speed(T)] = ref_speed[i];
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
-    HIPCHK(hipMemcpyAsync(F->d_in, F->h_in, B * nin * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(F->in.push(F->stream));
     rc = fleet_enqueue(F, F->d_io_step, 0);
     if (rc != RDA_OK) return rc;
-    HIPCHK(hipMemcpyAsync(F->h_out, F->d_out, B * nout * sizeof(double), hipMemcpyDeviceToHost, F->stream));
-    HIPCHK(hipMemcpyAsync(F->h_info, F->d_info, B * sizeof(rda_info), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(F->out.pull(F->stream, F->out.n));
+    HIPCHK(F->info.pull(F->stream, B));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
@@ -3187,24 +3216,21 @@ extern "C" int rda_fleet_upload_scenes(rda_fleet *F, const int32_t *counts, cons
 // rda_scene_resort for every member in ONE launch set (round 6): the members' resident raw scenes (rda_upload_scene*, static obstacles) re-ranked about
 // states[i * stride + 0..1] and their slots rebuilt on the fleet's stream; the next fleet step runs behind it.  Same device code per member as
 // rda_scene_resort: bit-identical slots.  Members with rda_opts::duals_follow, without a resident scene, or inside a tick: RDA_ERR_UNSUPPORTED / _ARG.
-static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from d_rob)
-// the members' scene arguments (uploaded when they changed) and their robots' positions -> d_sc, d_rob; nmax, wmax: what sizes the launches
+static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from res.rob)
+// the members' scene arguments (uploaded when they changed) and their robots' positions -> res.sc, res.rob; nmax, wmax: what sizes the launches
 static int fleet_resort_positions(rda_fleet *F, const double *states, int stride, int &nmax, int &wmax)
 {
     const size_t B = F->B;
-    bool changed = false;
+    const auto args = [F](size_t i) { return fleet_resort_args(F->egos[i]); };
     for (size_t i = 0; i < B; ++i) {
-        const scene::Args a = fleet_resort_args(F->egos[i]);
-        if (memcmp(&a, &F->h_sc[i], sizeof(scene::Args)) != 0) changed = true;
+        const scene::Args &a = F->egos[i]->sc_args;
         nmax = a.n > nmax ? a.n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
+    const bool changed = mirror_differs(F->res.sc, args);
     if (changed || F->rob_pending) { HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; }
-    if (changed) {
-        for (size_t i = 0; i < B; ++i) { const scene::Args a = fleet_resort_args(F->egos[i]); memcpy((void *)&F->h_sc[i], &a, sizeof(a)); }
-        HIPCHK(hipMemcpyAsync(F->d_sc, F->h_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
-    }
-    for (size_t i = 0; i < B; ++i) { F->h_rob[2 * i] = states[i * stride]; F->h_rob[2 * i + 1] = states[i * stride + 1]; }
-    HIPCHK(hipMemcpyAsync(F->d_rob, F->h_rob, 2 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    if (changed) HIPCHK(mirror_upload(F->res.sc, args, F->stream));
+    for (size_t i = 0; i < B; ++i) { F->res.rob.h[2 * i] = states[i * stride]; F->res.rob.h[2 * i + 1] = states[i * stride + 1]; }
+    HIPCHK(F->res.rob.push(F->stream));
     F->rob_pending = 1;
     return RDA_OK;
 }
@@ -3215,27 +3241,26 @@ static void fleet_resort_launch(rda_fleet *F, const scene::Args *sc, const doubl
     hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
     hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, B), dim3(256), 0, F->stream, sc, rob);
     hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
-    hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
+    hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), B), dim3(256), 0, F->stream, (const Dev *)F->devs.d);
 }
 extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
 {
     if (!F || !states || stride < 2) return RDA_ERR_ARG;
-    const size_t B = F->B;
     for (rda_handle *H : F->egos) {
         if (H->sc_n <= 0 || H->d.obstacle_num == 0 || H->pending) return RDA_ERR_ARG;
         if (H->follow) return RDA_ERR_UNSUPPORTED;
     }
-    if (!F->d_sc) {                                     // first use: the tables (zeroed) take their place once all of them exist
-        FleetResortTables t;
-        if (t.alloc(B)) return RDA_ERR_HIP;
-        t.commit(F);
+    if (!F->res.have()) {                               // first use: the tables (zeroed) take their place once all of them exist
+        FleetResort t;
+        if (t.alloc((size_t)F->B)) return RDA_ERR_HIP;
+        F->res = std::move(t);
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     int nmax = 0, wmax = 0;
     rc = fleet_resort_positions(F, states, stride, nmax, wmax);
     if (rc != RDA_OK) return rc;
-    fleet_resort_launch(F, F->d_sc, F->d_rob, nmax, wmax);
+    fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
@@ -3244,32 +3269,19 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
 static int fleet_lidar_reserve(rda_fleet *F, bool host_copy)
 {
     const size_t B = F->B;
-    if (!F->d_li_boxes) {
-        hbuf::Group g; lidar::Args *ha, *da; lidar::Fill *hf, *df; scene::Args *hs, *ds; double *db, *hr; int *hc;
-        int rc = 0;
-        rc |= g.dev(&da, B); rc |= g.dev(&df, B); rc |= g.dev(&ds, B); rc |= g.dev(&db, B * lidar::MAXB * 8);
-        rc |= g.pin(&ha, B); rc |= g.pin(&hf, B); rc |= g.pin(&hs, B); rc |= g.pin(&hr, B * lidar::MAXB); rc |= g.pin(&hc, 2 * B);
-        if (rc) return RDA_ERR_HIP;
+    if (!F->li.have()) {
+        FleetLidar t;
+        if (t.alloc(B)) return RDA_ERR_HIP;
         HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
         HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet_at, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
-        F->lidar = std::move(g);
-        F->h_li_args = ha; F->d_li_args = da; F->h_li_fill = hf; F->d_li_fill = df; F->h_li_sc = hs; F->d_li_sc = ds;
-        F->d_li_boxes = db; F->h_li_ranges = hr; F->h_li_count = hc;
+        F->li = std::move(t);
     }
-    if (host_copy && !F->h_li_boxes) {
-        hbuf::Group g; double *hb; int *hl;
-        int rc = 0;
-        rc |= g.pin(&hb, B * lidar::MAXB * 8); rc |= g.pin(&hl, B * lidar::MAXB);
-        if (rc) return RDA_ERR_HIP;
-        F->lidar_host = std::move(g); F->h_li_boxes = hb; F->h_li_labels = hl;
+    if (host_copy && !F->li_host.have()) {
+        FleetLidarHost t;
+        if (t.alloc(B)) return RDA_ERR_HIP;
+        F->li_host = std::move(t);
     }
     return RDA_OK;
-}
-static void fleet_lidar_release(rda_fleet *F)
-{
-    F->lidar = hbuf::Group();
-    F->h_li_args = F->d_li_args = nullptr; F->h_li_fill = F->d_li_fill = nullptr; F->h_li_sc = F->d_li_sc = nullptr;
-    F->d_li_boxes = F->h_li_ranges = nullptr; F->h_li_count = nullptr;
 }
 
 // the argument rules of scan_run, for every member
@@ -3283,24 +3295,25 @@ static int fleet_scan_check(const rda_fleet *F, const int32_t *n_beams, const do
 }
 
 // All members' scans through ONE lidar::k_scan_fleet launch on the fleet's stream (a workgroup and so a compute unit per member), and the ONE wait for
-// it: the counters are then in h_li_count [B][2], the boxes in d_li_boxes; to_host: labels (at the member's beam offset) and boxes also in h_li_*.
+// it: the counters are then in li.h_count [B][2], the boxes in li.d_boxes; to_host: labels (at the member's beam offset) and boxes also in li_host.
 static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
                           const double *range_max, const double *states, double eps, int min_samples, bool to_host)
 {
     const size_t B = F->B;
+    FleetLidar &li = F->li;
     size_t off = 0;
     for (size_t i = 0; i < B; ++i) {
-        lidar::Args &a = F->h_li_args[i];
-        a.n_beams = n_beams[i]; a.ranges = F->h_li_ranges + off; a.angle_min = angle_min[i]; a.angle_max = angle_max[i]; a.range_max = range_max[i];
+        lidar::Args &a = li.args.h[i];
+        a.n_beams = n_beams[i]; a.ranges = li.h_ranges + off; a.angle_min = angle_min[i]; a.angle_max = angle_max[i]; a.range_max = range_max[i];
         a.sx = states[3 * i]; a.sy = states[3 * i + 1]; a.sth = states[3 * i + 2]; a.eps = eps; a.min_samples = min_samples;
-        a.boxes = F->d_li_boxes + i * lidar::MAXB * 8; a.count = F->h_li_count + 2 * i;
-        a.labels_h = to_host ? F->h_li_labels + off : nullptr; a.boxes_h = to_host ? F->h_li_boxes + i * lidar::MAXB * 8 : nullptr;
-        F->h_li_count[2 * i] = 0; F->h_li_count[2 * i + 1] = 0;
+        a.boxes = li.d_boxes + i * lidar::MAXB * 8; a.count = li.h_count + 2 * i;
+        a.labels_h = to_host ? F->li_host.h_labels + off : nullptr; a.boxes_h = to_host ? F->li_host.h_boxes + i * lidar::MAXB * 8 : nullptr;
+        li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0;
         off += (size_t)n_beams[i];
     }
-    memcpy(F->h_li_ranges, ranges, off * sizeof(double));               // one pinned copy of all ranges (off <= B * MAXB)
-    HIPCHK(hipMemcpyAsync(F->d_li_args, F->h_li_args, B * sizeof(lidar::Args), hipMemcpyHostToDevice, F->stream));
-    hipLaunchKernelGGL(lidar::k_scan_fleet, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)F->d_li_args);
+    memcpy(li.h_ranges, ranges, off * sizeof(double));                  // one pinned copy of all ranges (off <= B * MAXB)
+    HIPCHK(li.args.push(F->stream));
+    hipLaunchKernelGGL(lidar::k_scan_fleet, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
@@ -3320,16 +3333,16 @@ extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const 
     if (rc != RDA_OK) return rc;
     size_t off = 0;
     for (size_t i = 0; i < (size_t)F->B; ++i) {
-        const int n = F->h_li_count[2 * i];
+        const int n = F->li.h_count[2 * i];
         n_boxes[i] = n;
-        if (boxes) memcpy(boxes + i * (size_t)cap * 8, F->h_li_boxes + i * lidar::MAXB * 8, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
-        if (labels) memcpy(labels + off, F->h_li_labels + off, (size_t)n_beams[i] * sizeof(int32_t));
+        if (boxes) memcpy(boxes + i * (size_t)cap * 8, F->li_host.h_boxes + i * lidar::MAXB * 8, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
+        if (labels) memcpy(labels + off, F->li_host.h_labels + off, (size_t)n_beams[i] * sizeof(int32_t));
         off += (size_t)n_beams[i];
     }
     return RDA_OK;
 }
 
-// The staging half of rda_fleet_upload_scans, shared with rda_fleet_rollout_lidar: the B box counts are in h_li_count, the boxes in d_li_boxes and the
+// The staging half of rda_fleet_upload_scans, shared with rda_fleet_rollout_lidar: the B box counts are in li.h_count, the boxes in li.d_boxes and the
 // fleet's stream is idle.  Every member's boxes -> raw scene -> slots -> candidate lists by FIVE launches whatever B is (blockIdx.y = the member); the
 // zero-box rule, the members' records and the LamMuZ launch form follow the counts.  grow: every member's larger raw scene where it needs one, allocated
 // by the caller (nothing of any member has changed when an allocation is refused).  The robot positions: states [B][3] on the host, or (pose_dev) [B][3]
@@ -3337,42 +3350,38 @@ extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const 
 static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const double *states, const double *pose_dev, const int32_t *order)
 {
     const size_t B = F->B;
+    FleetLidar &li = F->li;
     int nmax = 0, wmax = 0;
     for (size_t i = 0; i < B; ++i) {
         rda_handle *H = F->egos[i];
         Dev &d = H->d;
-        const int n = F->h_li_count[2 * i];
-        lidar::Fill &f = F->h_li_fill[i];
+        const int n = li.h_count[2 * i];
+        lidar::Fill &f = li.fill.h[i];
         if (n <= 0) {                                   // nothing written: stale A, b stay (rda_solver.py:485)
             d.obstacle_num = 0;
-            memset((void *)&F->h_li_sc[i], 0, sizeof(scene::Args)); memset((void *)&f, 0, sizeof(f));
+            memset((void *)&li.sc.h[i], 0, sizeof(scene::Args)); memset((void *)&f, 0, sizeof(f));
             continue;
         }
         scene_grow_commit(H, grow[i]);
         const scene::Args a = scan_scene_args(H, n, order[i] ? 1 : 0);
-        f.boxes = F->d_li_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
+        f.boxes = li.d_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
         f.geom = const_cast<double *>(a.geom); f.vel = const_cast<double *>(a.vel); f.robot = const_cast<double *>(a.robot);
         f.nonconvex = a.nonconvex; f.kind = const_cast<int *>(a.kind); f.nvert = const_cast<int *>(a.nvert);
         f.rx = states ? states[3 * i] : 0.0; f.ry = states ? states[3 * i + 1] : 0.0; f.rob = pose_dev ? pose_dev + 3 * i : nullptr;
-        memcpy((void *)&F->h_li_sc[i], &a, sizeof(a));
+        memcpy((void *)&li.sc.h[i], &a, sizeof(a));
         H->sc_args = a; H->sc_n = n;
         d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;                        // (scene_kernels)
         d.slot_src = H->d_sc_sel; d.src_used = n < a.N ? n : a.N;
         nmax = n > nmax ? n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
     // the members' records as they are now (the stream is idle: nothing reads the pinned mirrors)
-    for (size_t i = 0; i < B; ++i) memcpy(&F->h_devs[i], &F->egos[i]->d, sizeof(Dev));
-    HIPCHK(hipMemcpyAsync(F->d_devs, F->h_devs, B * sizeof(Dev), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
     fleet_refresh_flags(F);
     if (nmax > 0) {
-        HIPCHK(hipMemcpyAsync(F->d_li_fill, F->h_li_fill, B * sizeof(lidar::Fill), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_li_sc, F->h_li_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
-        const scene::Args *as = F->d_li_sc; const double *own = nullptr;                  // every member's own order and robot position
-        hipLaunchKernelGGL(lidar::k_scene_fill_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const lidar::Fill *)F->d_li_fill);
-        hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, as, own);
-        hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, (unsigned)B), dim3(256), 0, F->stream, as, own);
-        hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, as, own);
-        hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), (unsigned)B), dim3(256), 0, F->stream, (const Dev *)F->d_devs);
+        HIPCHK(li.fill.push(F->stream));
+        HIPCHK(li.sc.push(F->stream));
+        hipLaunchKernelGGL(lidar::k_scene_fill_fleet, dim3((nmax + 255) / 256, (unsigned)B), dim3(256), 0, F->stream, (const lidar::Fill *)li.fill.d);
+        fleet_resort_launch(F, li.sc.d, nullptr, nmax, wmax);                             // every member's own order and robot position
         HIPCHK(hipGetLastError());
     }
     return RDA_OK;
@@ -3388,18 +3397,38 @@ extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, cons
     const size_t B = F->B;
     for (rda_handle *H : F->egos) if (H->pending) return RDA_ERR_ARG;                     // a member inside a tick of its own
     for (rda_handle *H : F->egos) if (H->follow) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member)
-    const bool fresh = !F->d_li_boxes;
+    const bool fresh = !F->li.have();
     rc = fleet_lidar_reserve(F, false);
     if (rc != RDA_OK) return rc;
     rc = fleet_refresh(F);                              // behind whatever the members still have queued
     if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false);
     // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
     std::vector<SceneGrow> grow(B);
-    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->h_li_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->h_li_count[2 * i], grow[i]);
-    if (rc != RDA_OK) { if (fresh) fleet_lidar_release(F); return rc; }      // a failed call leaves what the fleet and the members hold as it was
+    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->li.h_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->li.h_count[2 * i], grow[i]);
+    if (rc != RDA_OK) { if (fresh) F->li = FleetLidar(); return rc; }        // a failed call leaves what the fleet and the members hold as it was
     rc = fleet_scan_stage(F, grow, states, nullptr, order);
     if (rc != RDA_OK) return rc;
-    if (n_boxes) for (size_t i = 0; i < B; ++i) n_boxes[i] = F->h_li_count[2 * i];
+    if (n_boxes) for (size_t i = 0; i < B; ++i) n_boxes[i] = F->li.h_count[2 * i];
+    return RDA_OK;
+}
+
+// One tick's tracker inputs, for rda_fleet_step_tracked and the rollouts' tick 0: the nominal controls (null: they are resident) into the members' step
+// blocks, every member's track::In -> device
+static int fleet_track_inputs(rda_fleet *F, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold, int ind_range,
+                              const double *nom_u)
+{
+    const size_t T = F->T, nu = traj_u(T), nin = step_doubles(T), B = F->B;
+    if (nom_u) {
+        for (size_t i = 0; i < B; ++i) memcpy(F->in.h + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
+        HIPCHK(hipMemcpy2DAsync(F->in.d + step_u(T), nin * sizeof(double), F->in.h + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
+                                hipMemcpyHostToDevice, F->stream));
+    }
+    for (size_t i = 0; i < B; ++i) {
+        track::In &in = F->trk.in.h[i];
+        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
+        in.cur_index = cur_index[i]; in.ind_range = ind_range;
+    }
+    HIPCHK(F->trk.in.push(F->stream));
     return RDA_OK;
 }
 
@@ -3408,65 +3437,53 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
                                       double *out_u, double *out_s, rda_info *info, double *ref_out, int32_t *min_index, double *end_heading)
 {
     if (!F || !states || !ref_speed || !cur_index || !out_u || !out_s || ind_range < 1) return RDA_ERR_ARG;
-    const size_t T = F->T, ns = traj_s(T), nu = traj_u(T), nin = step_doubles(T), nout = res_info(T), B = F->B;
-    if (!F->d_trk_in) {                                 // first use: the tables (zeroed) take their place once all of them exist
-        FleetTrackTables t;
+    const size_t T = F->T, ns = traj_s(T), nin = step_doubles(T), B = F->B;
+    if (!F->trk.have()) {                               // first use: the tables (zeroed) take their place once all of them exist
+        FleetTrack t;
         if (t.alloc(B)) return RDA_ERR_HIP;
-        t.commit(F);
+        F->trk = std::move(t);
     }
     // the result of the tick is written where the host reads it (round 6): k_finish_fleet and k_track_fleet store straight into the pinned blocks (write-only,
     // fire-and-forget stores over the link, complete at the end of their kernels) instead of three device-to-host copies queued behind the last launch
     // (~10 us each on the tick's critical path).  rda_opts::zero_copy = 0 on any member keeps the copies.
     bool zc = true;
     for (size_t i = 0; i < B; ++i) if (!F->egos[i]->zero_copy) zc = false;
-    double *const out_base = zc ? F->h_out : F->d_out;
-    rda_info *const info_base = zc ? F->h_info : F->d_info;
-    bool tables = false;
+    double *const out_base = zc ? F->out.h : F->out.d;
+    rda_info *const info_base = zc ? F->info.h : F->info.d;
+    FleetTrack &trk = F->trk;
     for (size_t i = 0; i < B; ++i) {
-        rda_handle *H = F->egos[i];
+        const rda_handle *H = F->egos[i];
         if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len) return RDA_ERR_ARG;
-        track::In &in = F->h_trk_in[i];
-        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
-        in.cur_index = cur_index[i]; in.ind_range = ind_range;
-        const EgoIO e = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, out_base, info_base);
-        if (memcmp(&e, &F->h_io_track[i], sizeof(EgoIO)) != 0 || F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
     }
+    const auto io = [&](size_t i) { return fleet_member_io(F, i, nom_u ? nullptr : F->egos[i]->d.u, out_base, info_base); };
+    const bool tables = mirror_differs(trk.io, io) || mirror_differs(trk.paths, member_paths(F)) || mirror_differs(trk.lens, member_lens(F));
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     if (tables) {
         HIPCHK(hipStreamSynchronize(F->stream));
-        for (size_t i = 0; i < B; ++i) {
-            rda_handle *H = F->egos[i];
-            F->h_io_track[i] = fleet_member_io(F, i, nom_u ? nullptr : H->d.u, out_base, info_base);
-            F->h_paths[i] = H->d_path; F->h_lens[i] = H->path_len;
-        }
-        HIPCHK(hipMemcpyAsync(F->d_io_track, F->h_io_track, B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_paths, F->h_paths, B * sizeof(double *), hipMemcpyHostToDevice, F->stream));
-        HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(mirror_upload(trk.io, io, F->stream));
+        HIPCHK(mirror_upload(trk.paths, member_paths(F), F->stream));
+        HIPCHK(mirror_upload(trk.lens, member_lens(F), F->stream));
     }
-    if (nom_u) {
-        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
-        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
-                                hipMemcpyHostToDevice, F->stream));
-    }
-    HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
-    hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, F->d_io_track, F->d_trk_in,
-                       F->d_paths, F->d_lens, zc ? F->h_trk_out : F->d_trk_out, (int)B);
-    rc = fleet_enqueue(F, F->d_io_track, 0);
+    rc = fleet_track_inputs(F, states, ref_speed, cur_index, threshold, ind_range, nom_u);
+    if (rc != RDA_OK) return rc;
+    hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->devs.d, trk.io.d, trk.in.d, trk.paths.d, trk.lens.d,
+                       zc ? trk.out.h : trk.out.d, (int)B);
+    rc = fleet_enqueue(F, trk.io.d, 0);
     if (rc != RDA_OK) return rc;
     if (!zc) {
-        HIPCHK(hipMemcpyAsync(F->h_out, F->d_out, B * nout * sizeof(double), hipMemcpyDeviceToHost, F->stream));
-        HIPCHK(hipMemcpyAsync(F->h_info, F->d_info, B * sizeof(rda_info), hipMemcpyDeviceToHost, F->stream));
-        HIPCHK(hipMemcpyAsync(F->h_trk_out, F->d_trk_out, B * sizeof(track::Out), hipMemcpyDeviceToHost, F->stream));
+        HIPCHK(F->out.pull(F->stream, F->out.n));
+        HIPCHK(F->info.pull(F->stream, B));
+        HIPCHK(trk.out.pull(F->stream, B));
     }
-    if (ref_out) HIPCHK(hipMemcpyAsync(F->h_in, F->d_in, B * nin * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    if (ref_out) HIPCHK(F->in.pull(F->stream, F->in.n));
     HIPCHK(hipStreamSynchronize(F->stream));
     for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
     for (size_t i = 0; i < B; ++i) {
         fleet_result_out(F, i, out_u, out_s, info);
-        if (ref_out) memcpy(ref_out + i * ns, F->h_in + i * nin + step_ref(T), ns * sizeof(double));
-        if (min_index) min_index[i] = F->h_trk_out[i].min_index;
-        if (end_heading) end_heading[i] = F->h_trk_out[i].end_heading;
+        if (ref_out) memcpy(ref_out + i * ns, F->in.h + i * nin + step_ref(T), ns * sizeof(double));
+        if (min_index) min_index[i] = trk.out.h[i].min_index;
+        if (end_heading) end_heading[i] = trk.out.h[i].end_heading;
     }
     return RDA_OK;
 }
@@ -3474,21 +3491,33 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
 // ---- rda_fleet_rollout: K closed-loop ticks queued back to back, ONE host wait ---------------------------------------------------------------------
 // Per tick the launches of the host loop (closed_loop_fleet_run: re-sort, k_track_fleet, the ADMM launches) and rollout::k_rollout_advance, which does on
 // the device what that loop's host does between two ticks and writes the next tick's inputs where these kernels read them.
-struct RollLayout { size_t states, u, endh, lastu, info, index, arrived, bytes; };     // byte offsets of the log block's parts (rollout::Logs; lastu [B][2][T]: the last tick's controls)
-static RollLayout roll_layout(size_t K, size_t B, size_t T)
+// What the three entries (rda_fleet_rollout, _moving, _lidar) take alike; clearance_log: null for the static entry
+struct RollArgs {
+    int K; const double *states, *ref_speed; const int32_t *cur_index; double threshold; int ind_range, goal_margin; const double *nom_u;
+    double *states_log, *u_log; int32_t *index_log; rda_info *info_log; int32_t *arrived_at; double *clearance_log;
+};
+// the argument rules every entry has: of the arrays and counts, and (roll_check_members) of the members' paths
+static int roll_check_args(const rda_fleet *F, const RollArgs &a)
 {
-    RollLayout l;
-    l.states = 0; l.u = l.states + (K + 1) * B * 3 * sizeof(double); l.endh = l.u + K * B * 2 * sizeof(double); l.lastu = l.endh + B * sizeof(double);
-    l.info = l.lastu + B * traj_u(T) * sizeof(double);
-    l.index = l.info + K * B * sizeof(rda_info); l.arrived = l.index + K * B * sizeof(int); l.bytes = l.arrived + B * sizeof(int);
-    return l;
+    if (!F || a.K < 1 || a.K > 4096 || !a.states || !a.ref_speed || !a.cur_index || !a.states_log || !a.u_log || !a.index_log || !a.arrived_at) return RDA_ERR_ARG;
+    return a.ind_range < 1 || a.goal_margin < 1 ? RDA_ERR_ARG : RDA_OK;
 }
-// The moving entry's per-member tables as the members stand now.  Robot vertices of the clearance: body-frame intersections of consecutive rows of
-// G x <= h (scenarios.robot_vertices: vertex i from rows i - 1 and i).  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
-struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
-static bool member_raw_scene(const rda_handle *H) { return H->sc_n > 0 && H->d.obstacle_num != 0; }
-static void clear_robot(const rda_handle *H, rollout::Clear &c)      // R, rv of the member's robot (0 vertices for a norm2 robot)
+static int roll_check_members(const rda_fleet *F, const int32_t *cur_index)
 {
+    for (int i = 0; i < F->B; ++i) {
+        const rda_handle *H = F->egos[i];
+        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
+    }
+    return RDA_OK;
+}
+
+// One member's move and clearance records for the geometry [n][E][2] it is given - its resident raw scene, or its world (geom null: none; base: the
+// geometry's snapshot).  Robot vertices of the clearance: body-frame intersections of consecutive rows of G x <= h (scenarios.robot_vertices: vertex i
+// from rows i - 1 and i); 0 vertices for a norm2 robot.
+static void member_move_clear(const rda_handle *H, double *geom, double *base, const double *vel, const int *kind, const int *nvert, int n, int E,
+                              scene::Move &m, rollout::Clear &c)
+{
+    memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c));
     const int R = H->d.c.R;
     c.R = H->d.c.robot_norm2 ? 0 : R;
     for (int k = 0; k < c.R; ++k) {
@@ -3498,22 +3527,27 @@ static void clear_robot(const rda_handle *H, rollout::Clear &c)      // R, rv of
         c.rv[k][0] = (h[j] * G[2 * k + 1] - G[2 * j + 1] * h[k]) / det;
         c.rv[k][1] = (G[2 * j] * h[k] - h[j] * G[2 * k]) / det;
     }
+    c.E = E;
+    if (!geom) return;
+    m.geom = geom; m.base = base; m.vel = vel; m.kind = kind; m.nvert = nvert; m.n = n; m.E = E; m.dt = H->d.c.dt;
+    c.geom = geom; c.kind = kind; c.nvert = nvert; c.n = n;
 }
+// The moving entry's per-member tables as the members' raw scenes stand now.  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
+struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
+static bool member_raw_scene(const rda_handle *H) { return H->sc_n > 0 && H->d.obstacle_num != 0; }
 static void fleet_move_view(const rda_fleet *F, MoveView &v)
 {
     const size_t B = F->B;
     v.mv.resize(B); v.cl.resize(B); v.sc.resize(B); v.off.assign(B, 0);
     for (size_t i = 0; i < B; ++i) {
         const rda_handle *H = F->egos[i];
-        scene::Move &m = v.mv[i]; rollout::Clear &c = v.cl[i]; scene::Args &a = v.sc[i];
-        memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c)); memset((void *)&a, 0, sizeof(a));
-        clear_robot(H, c);
-        c.E = H->d.c.E;
-        if (!member_raw_scene(H)) continue;
-        a = H->sc_args;
-        m.geom = const_cast<double *>(a.geom); m.vel = a.vel; m.kind = a.kind; m.nvert = a.nvert; m.n = a.n; m.E = a.E; m.dt = H->d.c.dt;
-        v.off[i] = v.mv_total;                                                    // (its place in the snapshot buffer: Move::base is set by the rollout)
-        c.geom = a.geom; c.kind = a.kind; c.nvert = a.nvert; c.n = a.n;
+        const bool raw = member_raw_scene(H);
+        scene::Args &a = v.sc[i];
+        memset((void *)&a, 0, sizeof(a));
+        if (raw) a = H->sc_args;
+        member_move_clear(H, raw ? const_cast<double *>(a.geom) : nullptr, nullptr, a.vel, a.kind, a.nvert, a.n, H->d.c.E, v.mv[i], v.cl[i]);      // (Move::base is set by the rollout)
+        if (!raw) continue;
+        v.off[i] = v.mv_total;                                                    // (its place in the snapshot buffer)
         v.mv_total += (size_t)a.n * a.E * 2;
         v.gmax = a.n * a.E > v.gmax ? a.n * a.E : v.gmax;
         v.nmax = a.n > v.nmax ? a.n : v.nmax; v.wmax = a.N * a.nt > v.wmax ? a.N * a.nt : v.wmax;
@@ -3529,96 +3563,123 @@ static bool member_clearance_ok(const rda_handle *H)
     return true;
 }
 
-// What every rollout entry does around its ticks (rda_fleet_rollout, _moving, _lidar).
+// What every rollout reserves before its first tick - the tracker's tables, the rollout tables, a log block of K ticks and (clearance) a clearance log of
+// K * B.  alloc: whatever of it the fleet lacks, beside the fleet, so that a refusal changes nothing; the entry allocates its own sets next to it and, when
+// all of it exists, calls move_in and moves its own.  wait: the entry replaces or rewrites more than these (a block that is replaced waits by itself).
+struct RollReserve {
+    FleetTrack trk; FleetRollTables tab; FleetRollLog log; FleetDoubles clr;
+    int alloc(const rda_fleet *F, int K, bool clearance)
+    {
+        const size_t B = F->B;
+        int rc = 0;
+        if (!F->trk.have()) rc |= trk.alloc(B);
+        if (!F->ro.have()) rc |= tab.alloc(B);
+        if (K > F->ro_log.cap) rc |= log.alloc(K, B, (size_t)F->T);
+        if (clearance && (size_t)K * B > F->cl_log.v.n) rc |= clr.alloc((size_t)K * B);
+        return rc ? RDA_ERR_HIP : RDA_OK;
+    }
+    int move_in(rda_fleet *F, bool wait)
+    {
+        if (wait || log.have() || clr.have()) HIPCHK(hipStreamSynchronize(F->stream));       // (a shorter block is freed below)
+        if (trk.have()) F->trk = std::move(trk);
+        if (tab.have()) F->ro = std::move(tab);
+        if (log.have()) F->ro_log = std::move(log);
+        if (clr.have()) F->cl_log = std::move(clr);
+        F->roll_K = 0;                                                          // (until this rollout's logs are on the host)
+        return RDA_OK;
+    }
+};
+
+// What every rollout entry does around its ticks.
 // The advance kernel's member table and the io tables of tick 0 | of the later ticks as the members stand now; true: they, or the members' paths, differ
 // from what the device holds.
 struct RollView { std::vector<rollout::Member> wm; std::vector<EgoIO> wio; };
 static bool fleet_roll_view(const rda_fleet *F, bool have_nom_u, RollView &v)
 {
     const size_t B = F->B, T = F->T;
-    bool tables = false;
     v.wm.resize(B); v.wio.resize(2 * B);
     for (size_t i = 0; i < B; ++i) {
         const rda_handle *H = F->egos[i];
-        v.wio[i] = fleet_member_io(F, i, have_nom_u ? nullptr : H->d.u, F->d_out, F->d_info);      // tick 0
-        v.wio[B + i] = fleet_member_io(F, i, H->d.u, F->d_out, F->d_info);                         // later ticks: the resident controls
+        v.wio[i] = fleet_member_io(F, i, have_nom_u ? nullptr : H->d.u, F->out.d, F->info.d);      // tick 0
+        v.wio[B + i] = fleet_member_io(F, i, H->d.u, F->out.d, F->info.d);                         // later ticks: the resident controls
         rollout::Member &m = v.wm[i];
         memset((void *)&m, 0, sizeof(m));
         m.out_u = v.wio[i].out_u; m.info = v.wio[i].info; m.T = (int)T; m.L = H->path_len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
-        if (F->h_paths[i] != H->d_path || F->h_lens[i] != H->path_len) tables = true;
     }
-    if (memcmp(v.wm.data(), F->h_ro_m, B * sizeof(rollout::Member)) != 0 || memcmp(v.wio.data(), F->h_io_roll, 2 * B * sizeof(EgoIO)) != 0) tables = true;
-    return tables;
+    return mirror_differs(F->trk.paths, member_paths(F)) || mirror_differs(F->trk.lens, member_lens(F)) || mirror_differs(F->ro.m, records(v.wm)) ||
+           mirror_differs(F->ro.io, records(v.wio));
 }
 // ... uploaded (the fleet's stream is idle: nothing reads the pinned mirrors)
 static int fleet_roll_upload(rda_fleet *F, const RollView &v)
 {
-    const size_t B = F->B;
-    memcpy((void *)F->h_ro_m, v.wm.data(), B * sizeof(rollout::Member)); memcpy((void *)F->h_io_roll, v.wio.data(), 2 * B * sizeof(EgoIO));
-    for (size_t i = 0; i < B; ++i) { F->h_paths[i] = F->egos[i]->d_path; F->h_lens[i] = F->egos[i]->path_len; }
-    HIPCHK(hipMemcpyAsync(F->d_ro_m, F->h_ro_m, B * sizeof(rollout::Member), hipMemcpyHostToDevice, F->stream));
-    HIPCHK(hipMemcpyAsync(F->d_io_roll, F->h_io_roll, 2 * B * sizeof(EgoIO), hipMemcpyHostToDevice, F->stream));
-    HIPCHK(hipMemcpyAsync(F->d_paths, F->h_paths, B * sizeof(double *), hipMemcpyHostToDevice, F->stream));
-    HIPCHK(hipMemcpyAsync(F->d_lens, F->h_lens, B * sizeof(int), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(mirror_upload(F->ro.m, records(v.wm), F->stream));
+    HIPCHK(mirror_upload(F->ro.io, records(v.wio), F->stream));
+    HIPCHK(mirror_upload(F->trk.paths, member_paths(F), F->stream));
+    HIPCHK(mirror_upload(F->trk.lens, member_lens(F), F->stream));
     return RDA_OK;
 }
 // tick 0's nominal controls and tracker inputs, as rda_fleet_step_tracked uploads them; lg: the device logs of this rollout, arrived_at reset to -1
-static int fleet_roll_inputs(rda_fleet *F, const RollLayout &lay, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
-                             int ind_range, const double *nom_u, rollout::Logs &lg)
+static int fleet_roll_inputs(rda_fleet *F, const RollLayout &lay, const RollArgs &a, rollout::Logs &lg)
 {
-    const size_t T = F->T, nu = traj_u(T), nin = step_doubles(T), B = F->B;
-    if (nom_u) {
-        for (size_t i = 0; i < B; ++i) memcpy(F->h_in + i * nin + step_u(T), nom_u + i * nu, nu * sizeof(double));
-        HIPCHK(hipMemcpy2DAsync(F->d_in + step_u(T), nin * sizeof(double), F->h_in + step_u(T), nin * sizeof(double), nu * sizeof(double), B,
-                                hipMemcpyHostToDevice, F->stream));
-    }
-    for (size_t i = 0; i < B; ++i) {
-        track::In &in = F->h_trk_in[i];
-        in.sx = states[3 * i]; in.sy = states[3 * i + 1]; in.sth = states[3 * i + 2]; in.speed = ref_speed[i]; in.threshold = threshold;
-        in.cur_index = cur_index[i]; in.ind_range = ind_range;
-    }
-    HIPCHK(hipMemcpyAsync(F->d_trk_in, F->h_trk_in, B * sizeof(track::In), hipMemcpyHostToDevice, F->stream));
-    lg.states = (double *)(F->d_ro_log + lay.states); lg.u = (double *)(F->d_ro_log + lay.u); lg.end_heading = (double *)(F->d_ro_log + lay.endh);
-    lg.info = (rda_info *)(F->d_ro_log + lay.info); lg.index = (int *)(F->d_ro_log + lay.index); lg.arrived_at = (int *)(F->d_ro_log + lay.arrived);
-    HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, B * sizeof(int), F->stream));    // -1: not arrived
+    int rc = fleet_track_inputs(F, a.states, a.ref_speed, a.cur_index, a.threshold, a.ind_range, a.nom_u);
+    if (rc != RDA_OK) return rc;
+    char *log = F->ro_log.log.d;
+    lg.states = (double *)(log + lay.states); lg.u = (double *)(log + lay.u); lg.end_heading = (double *)(log + lay.endh);
+    lg.info = (rda_info *)(log + lay.info); lg.index = (int *)(log + lay.index); lg.arrived_at = (int *)(log + lay.arrived);
+    HIPCHK(hipMemsetAsync(lg.arrived_at, 0xff, F->B * sizeof(int), F->stream));  // -1: not arrived
+    return RDA_OK;
+}
+// The tail of tick k, behind whatever the entry's head did to the members' slots: k_track_fleet, the ADMM launches, k_rollout_advance (rob: where it leaves
+// the robots' positions for the next re-sort, or null), then (mv: the raw scenes' or the world's move table, null: nothing moves) scene::k_move_fleet over
+// `gmove` and (cl: their clearance table, null: no clearance log) k_clearance_fleet of state k + 1 against the geometry of tick k + 1.
+static int fleet_roll_tail(rda_fleet *F, int k, const rollout::Logs &lg, int goal_margin, double *rob, const scene::Move *mv, dim3 gmove,
+                           const rollout::Clear *cl)
+{
+    const size_t B = F->B;
+    FleetTrack &trk = F->trk;
+    const EgoIO *io = F->ro.io.d + (k == 0 ? 0 : B);
+    hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->devs.d, io, trk.in.d, trk.paths.d, trk.lens.d, trk.out.d, (int)B);
+    int rc = fleet_enqueue(F, io, 0);
+    if (rc != RDA_OK) return rc;
+    hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->ro.m.d,
+                       (const track::Out *)trk.out.d, trk.in.d, rob, lg, k, goal_margin, (int)B);
+    if (mv) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, mv, k + 1);      // where tick k + 1 finds them
+    if (cl)
+        hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, cl,
+                           (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->cl_log.v.d + (size_t)k * B, (int)B);
     return RDA_OK;
 }
 // the logs to the host behind the last tick, the wait for them, and out to the caller's arrays
-static int fleet_roll_fetch(rda_fleet *F, int K, const RollLayout &lay, const double *states, double *states_log, double *u_log, int32_t *index_log,
-                            rda_info *info_log, int32_t *arrived_at, double *clearance_log)
+static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs &a)
 {
-    const size_t T = F->T, nu = traj_u(T), B = F->B;
-    if (clearance_log) HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
-    HIPCHK(hipMemcpy2DAsync(F->d_ro_log + lay.lastu, nu * sizeof(double), F->d_out, res_info(T) * sizeof(double), nu * sizeof(double), B,
+    const size_t T = F->T, nu = traj_u(T), B = F->B, K = a.K;
+    const char *log = F->ro_log.log.h;
+    if (a.clearance_log) HIPCHK(F->cl_log.v.pull(F->stream, K * B));
+    HIPCHK(hipMemcpy2DAsync(F->ro_log.log.d + lay.lastu, nu * sizeof(double), F->out.d, res_info(T) * sizeof(double), nu * sizeof(double), B,
                             hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
-    HIPCHK(hipMemcpyAsync(F->h_ro_log, F->d_ro_log, lay.bytes, hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;                       // their staged scenes have been consumed
-    F->roll_K = K;
-    memcpy(states_log, states, B * 3 * sizeof(double));                         // row 0: the input
-    memcpy(states_log + B * 3, F->h_ro_log + lay.states + B * 3 * sizeof(double), (size_t)K * B * 3 * sizeof(double));
-    memcpy(u_log, F->h_ro_log + lay.u, (size_t)K * B * 2 * sizeof(double));
-    memcpy(index_log, F->h_ro_log + lay.index, (size_t)K * B * sizeof(int32_t));
-    if (info_log) memcpy(info_log, F->h_ro_log + lay.info, (size_t)K * B * sizeof(rda_info));
-    memcpy(arrived_at, F->h_ro_log + lay.arrived, B * sizeof(int32_t));
-    if (clearance_log) memcpy(clearance_log, F->h_cl_log, (size_t)K * B * sizeof(double));
+    F->roll_K = a.K;
+    memcpy(a.states_log, a.states, B * 3 * sizeof(double));                     // row 0: the input
+    memcpy(a.states_log + B * 3, log + lay.states + B * 3 * sizeof(double), K * B * 3 * sizeof(double));
+    memcpy(a.u_log, log + lay.u, K * B * 2 * sizeof(double));
+    memcpy(a.index_log, log + lay.index, K * B * sizeof(int32_t));
+    if (a.info_log) memcpy(a.info_log, log + lay.info, K * B * sizeof(rda_info));
+    memcpy(a.arrived_at, log + lay.arrived, B * sizeof(int32_t));
+    if (a.clearance_log) memcpy(a.clearance_log, F->cl_log.v.h, K * B * sizeof(double));
     return RDA_OK;
 }
 
 // rda_fleet_rollout (moving = false: exactly the static entry) and rda_fleet_rollout_moving share this body
-static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
-                              int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
-                              rda_info *info_log, int32_t *arrived_at, bool moving, double *clearance_log)
+static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, bool moving)
 {
-    if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
-    if (ind_range < 1 || goal_margin < 1) return RDA_ERR_ARG;
+    int rc = roll_check_args(F, a);
+    if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
+    if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
-    for (size_t i = 0; i < B; ++i) {
-        const rda_handle *H = F->egos[i];
-        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
-        if (resort && (H->sc_n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
-    }
+    for (const rda_handle *H : F->egos) if (resort && (H->sc_n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
     for (const rda_handle *H : F->egos) {
         if (H->follow) return RDA_ERR_UNSUPPORTED;                              // (k_follow_* are per member)
         if (!moving && H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
@@ -3628,90 +3689,69 @@ static int fleet_rollout_body(rda_fleet *F, int K, const double *states, const d
         for (const rda_handle *H : F->egos) {
             if (!resort && member_raw_scene(H) && H->sc_args.order != 0) return RDA_ERR_ARG;          // slots rebuilt in the staged order: only meaningful for order = 0
             if (H->d.obstacle_num != 0 && H->d.nt > 1 && H->sc_n <= 0) return RDA_ERR_UNSUPPORTED;    // host-staged per-stage slots: no raw scene to move
-            if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+            if (a.clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
         }
         fleet_move_view(F, mvw);
     }
     // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    FleetTrackTables ttrk; FleetResortTables tres; FleetMoveTables tmov; FleetClearLog tclr; hbuf::Group gbase; double *dbase = nullptr;
-    const bool need_mov = moving && !F->d_mv, need_base = moving && mvw.mv_total > F->mv_cap, need_clr = clearance_log && (size_t)K * F->B > F->cl_cap;
-    hbuf::Group gtab, glog; rollout::Member *hm = nullptr, *dm = nullptr; EgoIO *hio = nullptr, *dio = nullptr; char *hlog = nullptr, *dlog = nullptr;
-    const bool need_trk = !F->d_trk_in, need_res = resort && !F->d_sc, need_tab = !F->d_ro_m, need_log = !F->d_ro_log || K > F->roll_cap;
+    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap;
     {
-        int rc = 0;
-        if (need_trk) rc |= ttrk.alloc(B);
-        if (need_res) rc |= tres.alloc(B);
-        if (need_tab) { rc |= gtab.dev(&dm, B); rc |= gtab.dev(&dio, 2 * B); rc |= gtab.pin(&hm, B); rc |= gtab.pin(&hio, 2 * B); }
-        if (need_log) { const size_t nb = roll_layout((size_t)K, B, T).bytes; rc |= glog.dev(&dlog, nb); rc |= glog.pin(&hlog, nb); }
-        if (need_mov) rc |= tmov.alloc(B);
-        if (need_base) rc |= gbase.dev(&dbase, mvw.mv_total);
-        if (need_clr) rc |= tclr.alloc((size_t)K * B);
-        if (rc) return RDA_ERR_HIP;
+        int bad = rsv.alloc(F, a.K, a.clearance_log != nullptr);
+        if (resort && !F->res.have()) bad |= tres.alloc(B);
+        if (moving && !F->mov.have()) bad |= tmov.alloc(B);
+        if (moving && mvw.mv_total > F->snap.cap) bad |= tsnap.alloc(mvw.mv_total);
+        if (bad) return RDA_ERR_HIP;
     }
-    if (need_log || need_base || need_clr) HIPCHK(hipStreamSynchronize(F->stream));      // (a shorter block is freed below)
-    if (need_mov) tmov.commit(F);
-    if (need_base) { F->mov_base = std::move(gbase); F->d_mv_base = dbase; F->mv_cap = mvw.mv_total; }
-    if (need_clr) tclr.commit(F);
-    if (need_trk) ttrk.commit(F);
-    if (need_res) tres.commit(F);
-    if (need_tab) { F->roll = std::move(gtab); F->d_ro_m = dm; F->d_io_roll = dio; F->h_ro_m = hm; F->h_io_roll = hio; }
-    if (need_log) { F->roll_log = std::move(glog); F->d_ro_log = dlog; F->h_ro_log = hlog; F->roll_cap = K; }
-    F->roll_K = 0;                                                              // (until this rollout's logs are on the host)
-    int rc = fleet_refresh(F);
+    rc = rsv.move_in(F, tsnap.have());
+    if (rc != RDA_OK) return rc;
+    if (tres.have()) F->res = std::move(tres);
+    if (tmov.have()) F->mov = std::move(tmov);
+    if (tsnap.have()) F->snap = std::move(tsnap);
+    rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     // one-time table refreshes (the only other waits of a rollout): the tables are compared with what the device holds and uploaded when they differ
     RollView rv;
-    bool tables = fleet_roll_view(F, nom_u != nullptr, rv);
+    bool tables = fleet_roll_view(F, a.nom_u != nullptr, rv);
     if (moving) {
-        for (size_t i = 0; i < B; ++i) if (mvw.mv[i].n > 0) mvw.mv[i].base = F->d_mv_base + mvw.off[i];
-        if (memcmp(mvw.mv.data(), F->h_mv, B * sizeof(scene::Move)) != 0 || memcmp(mvw.cl.data(), F->h_cl, B * sizeof(rollout::Clear)) != 0 ||
-            memcmp(mvw.sc.data(), F->h_mv_sc, B * sizeof(scene::Args)) != 0) tables = true;
+        for (size_t i = 0; i < B; ++i) if (mvw.mv[i].n > 0) mvw.mv[i].base = F->snap.d + mvw.off[i];
+        if (mirror_differs(F->mov.mv, records(mvw.mv)) || mirror_differs(F->mov.cl, records(mvw.cl)) || mirror_differs(F->mov.sc, records(mvw.sc))) tables = true;
     }
     if (tables) {
         HIPCHK(hipStreamSynchronize(F->stream));
         if (moving) {
-            memcpy((void *)F->h_mv, mvw.mv.data(), B * sizeof(scene::Move)); memcpy((void *)F->h_cl, mvw.cl.data(), B * sizeof(rollout::Clear));
-            memcpy((void *)F->h_mv_sc, mvw.sc.data(), B * sizeof(scene::Args));
-            HIPCHK(hipMemcpyAsync(F->d_mv, F->h_mv, B * sizeof(scene::Move), hipMemcpyHostToDevice, F->stream));
-            HIPCHK(hipMemcpyAsync(F->d_cl, F->h_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
-            HIPCHK(hipMemcpyAsync(F->d_mv_sc, F->h_mv_sc, B * sizeof(scene::Args), hipMemcpyHostToDevice, F->stream));
+            HIPCHK(mirror_upload(F->mov.mv, records(mvw.mv), F->stream));
+            HIPCHK(mirror_upload(F->mov.cl, records(mvw.cl), F->stream));
+            HIPCHK(mirror_upload(F->mov.sc, records(mvw.sc), F->stream));
         }
         rc = fleet_roll_upload(F, rv);
         if (rc != RDA_OK) return rc;
     }
     // tick 0's inputs, as rda_fleet_scene_resort and rda_fleet_step_tracked upload them
     int nmax = 0, wmax = 0;
-    if (resort) { rc = fleet_resort_positions(F, states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
-    const RollLayout lay = roll_layout((size_t)K, B, T);
+    if (resort) { rc = fleet_resort_positions(F, a.states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
+    const RollLayout lay = roll_layout((size_t)a.K, B, T);
     rollout::Logs lg;
-    rc = fleet_roll_inputs(F, lay, states, ref_speed, cur_index, threshold, ind_range, nom_u, lg);
+    rc = fleet_roll_inputs(F, lay, a, lg);
     if (rc != RDA_OK) return rc;
     const bool moves = moving && mvw.gmax > 0;
     const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
-    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_mv);      // `base`: the geometry as the call finds it
-    for (int k = 0; k < K; ++k) {
-        if (resort) fleet_resort_launch(F, F->d_sc, F->d_rob, nmax, wmax);       // about d_rob: the caller's positions (tick 0), then the advance kernel's
-        else if (moves) fleet_resort_launch(F, F->d_mv_sc, nullptr, mvw.nmax, mvw.wmax);      // a scene that moved: its slots rebuilt in the staged order
-        const EgoIO *io = F->d_io_roll + (k == 0 ? 0 : B);
-        hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, io, F->d_trk_in, F->d_paths, F->d_lens, F->d_trk_out, (int)B);
-        rc = fleet_enqueue(F, io, 0);
+    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->mov.mv.d);      // `base`: the geometry as the call finds it
+    for (int k = 0; k < a.K; ++k) {
+        if (resort) fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);            // about res.rob: the caller's positions (tick 0), then the advance kernel's
+        else if (moves) fleet_resort_launch(F, F->mov.sc.d, nullptr, mvw.nmax, mvw.wmax);     // a scene that moved: its slots rebuilt in the staged order
+        rc = fleet_roll_tail(F, k, lg, a.goal_margin, resort ? F->res.rob.d : nullptr, moves ? F->mov.mv.d : nullptr, gmove,
+                             a.clearance_log ? F->mov.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
-        hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->d_ro_m,
-                           (const track::Out *)F->d_trk_out, F->d_trk_in, resort ? F->d_rob : nullptr, lg, k, goal_margin, (int)B);
-        if (moves) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_mv, k + 1);     // where tick k + 1 finds them
-        if (clearance_log)                                                       // state k + 1 against the geometry of tick k + 1
-            hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_cl,
-                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->d_cl_log + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
-    return fleet_roll_fetch(F, K, lay, states, states_log, u_log, index_log, info_log, arrived_at, clearance_log);      // the rollout's one wait
+    return fleet_roll_fetch(F, lay, a);                                         // the rollout's one wait
 }
 extern "C" int rda_fleet_rollout(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
                                  int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log, int32_t *index_log,
                                  rda_info *info_log, int32_t *arrived_at)
 {
-    return fleet_rollout_body(F, K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, resort, nom_u, states_log, u_log, index_log, info_log,
-                              arrived_at, false, nullptr);
+    return fleet_rollout_scenes(F, RollArgs{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log,
+                                             arrived_at, nullptr }, resort, false);
 }
 // The rollout for scenes that move: behind every tick's advance kernel scene::k_move_fleet puts every member's raw geometry where the next tick finds it
 // (base + vel * (dt * k), base = the geometry the call found), the tick's re-sort launches rebuild the per-stage slots from it, and (clearance_log)
@@ -3720,8 +3760,8 @@ extern "C" int rda_fleet_rollout_moving(rda_fleet *F, int K, const double *state
                                         int ind_range, int goal_margin, int resort, const double *nom_u, double *states_log, double *u_log,
                                         int32_t *index_log, rda_info *info_log, int32_t *arrived_at, double *clearance_log)
 {
-    return fleet_rollout_body(F, K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, resort, nom_u, states_log, u_log, index_log, info_log,
-                              arrived_at, true, clearance_log);
+    return fleet_rollout_scenes(F, RollArgs{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log,
+                                             arrived_at, clearance_log }, resort, true);
 }
 // every member's clearance at states [B][3] against its resident raw scene as it stands: the rollout's kernel, one launch, one wait
 extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *clearance)
@@ -3732,35 +3772,33 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
         if (H->pending) return RDA_ERR_ARG;
         if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
     }
-    FleetMoveTables tmov; FleetClearLog tclr;
-    const bool need_mov = !F->d_mv, need_clr = B > F->cl_cap;
+    FleetMove tmov; FleetDoubles tclr;
     {
-        int rc = 0;
-        if (need_mov) rc |= tmov.alloc(B);
-        if (need_clr) rc |= tclr.alloc(B);
-        if (rc) return RDA_ERR_HIP;
+        int bad = 0;
+        if (!F->mov.have()) bad |= tmov.alloc(B);
+        if (B > F->cl_log.v.n) bad |= tclr.alloc(B);
+        if (bad) return RDA_ERR_HIP;
     }
-    if (need_clr) HIPCHK(hipStreamSynchronize(F->stream));
-    if (need_mov) tmov.commit(F);
-    if (need_clr) tclr.commit(F);
+    if (tclr.have()) HIPCHK(hipStreamSynchronize(F->stream));
+    if (tmov.have()) F->mov = std::move(tmov);
+    if (tclr.have()) F->cl_log = std::move(tclr);
     int rc = fleet_refresh(F);                          // behind whatever the members still have queued
     if (rc != RDA_OK) return rc;
     MoveView v;
     fleet_move_view(F, v);
-    if (memcmp(v.cl.data(), F->h_cl, B * sizeof(rollout::Clear)) != 0) {
+    if (mirror_differs(F->mov.cl, records(v.cl))) {
         HIPCHK(hipStreamSynchronize(F->stream));
-        memcpy((void *)F->h_cl, v.cl.data(), B * sizeof(rollout::Clear));
-        HIPCHK(hipMemcpyAsync(F->d_cl, F->h_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
+        HIPCHK(mirror_upload(F->mov.cl, records(v.cl), F->stream));
     }
-    memcpy(F->h_cl_st, states, 3 * B * sizeof(double));
-    HIPCHK(hipMemcpyAsync(F->d_cl_st, F->h_cl_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
-    hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_cl,
-                       (const double *)F->d_cl_st, F->d_cl_log, (int)B);
+    memcpy(F->mov.st.h, states, 3 * B * sizeof(double));
+    HIPCHK(F->mov.st.push(F->stream));
+    hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->mov.cl.d,
+                       (const double *)F->mov.st.d, F->cl_log.v.d, (int)B);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(F->h_cl_log, F->d_cl_log, B * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(F->cl_log.v.pull(F->stream, B));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
-    memcpy(clearance, F->h_cl_log, B * sizeof(double));
+    memcpy(clearance, F->cl_log.v.h, B * sizeof(double));
     return RDA_OK;
 }
 // ---- the members' worlds and the simulated sensor (lidar::k_raycast_fleet) -----------------------------------------------------------------------------
@@ -3778,27 +3816,16 @@ extern "C" int rda_fleet_upload_worlds(rda_fleet *F, const int32_t *counts, int 
         if (kind[j] == 0) { if (nvert[j] < 3 || nvert[j] > we) return RDA_ERR_ARG; }
         else if (kind[j] != 1) return RDA_ERR_ARG;
     }
-    hbuf::Group g;
-    double *dg, *db, *dv, *dst, *hst; int *dk, *dn; lidar::Ray *hray, *dray; scene::Move *hmv, *dmv; rollout::Clear *hcl, *dcl;
-    const size_t nt = total ? total : 1;                  // (an all-empty fleet still gets buffers to point at)
-    int rc = 0;
-    rc |= g.dev(&dg, nt * we * 2); rc |= g.dev(&db, nt * we * 2); rc |= g.dev(&dv, nt * 2); rc |= g.dev(&dk, nt); rc |= g.dev(&dn, nt);
-    rc |= g.dev(&dray, B); rc |= g.dev(&dmv, B); rc |= g.dev(&dcl, B); rc |= g.dev(&dst, 3 * B);
-    rc |= g.pin(&hray, B); rc |= g.pin(&hmv, B); rc |= g.pin(&hcl, B); rc |= g.pin(&hst, 3 * B);
-    if (rc) return RDA_ERR_HIP;
+    FleetWorld w;
+    if (w.alloc(B, counts, we)) return RDA_ERR_HIP;
     if (total > 0) {
-        HIPCHK(hipMemcpy(dg, geom, total * we * 2 * sizeof(double), hipMemcpyHostToDevice));
-        if (vel) HIPCHK(hipMemcpy(dv, vel, total * 2 * sizeof(double), hipMemcpyHostToDevice));      // (NULL: the zeros of the allocation - a standing world)
-        HIPCHK(hipMemcpy(dk, kind, total * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dn, nvert, total * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(w.geom, geom, total * we * 2 * sizeof(double), hipMemcpyHostToDevice));
+        if (vel) HIPCHK(hipMemcpy(w.vel, vel, total * 2 * sizeof(double), hipMemcpyHostToDevice));   // (NULL: the zeros of the allocation - a standing world)
+        HIPCHK(hipMemcpy(w.kind, kind, total * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(w.nvert, nvert, total * sizeof(int), hipMemcpyHostToDevice));
     }
     HIPCHK(hipStreamSynchronize(F->stream));              // a ray cast of the old world may still be queued
-    F->world = std::move(g);
-    F->d_w_geom = dg; F->d_w_base = db; F->d_w_vel = dv; F->d_w_kind = dk; F->d_w_nvert = dn;
-    F->h_w_ray = hray; F->d_w_ray = dray; F->h_w_mv = hmv; F->d_w_mv = dmv; F->h_w_cl = hcl; F->d_w_cl = dcl; F->h_w_st = hst; F->d_w_st = dst;
-    F->w_e = we; F->w_total = total; F->w_have = 1;
-    F->w_counts.assign(counts, counts + B); F->w_off.assign(B, 0);
-    for (size_t i = 1; i < B; ++i) F->w_off[i] = F->w_off[i - 1] + (size_t)counts[i - 1];
+    F->world = std::move(w);
     return RDA_OK;
 }
 
@@ -3806,11 +3833,12 @@ extern "C" int rda_fleet_upload_worlds(rda_fleet *F, const int32_t *counts, int 
 extern "C" int rda_debug_fleet_world(rda_fleet *F, double *geom, int32_t *n_total, int32_t *we)
 {
     if (!F || !n_total) return RDA_ERR_ARG;
-    *n_total = F->w_have ? (int32_t)F->w_total : 0;
-    if (we) *we = F->w_have ? F->w_e : 0;
-    if (!F->w_have || F->w_total == 0 || !geom) return RDA_OK;
+    const FleetWorld &w = F->world;
+    *n_total = (int32_t)w.total;
+    if (we) *we = w.e;
+    if (w.total == 0 || !geom) return RDA_OK;
     HIPCHK(hipStreamSynchronize(F->stream));
-    HIPCHK(hipMemcpy(geom, F->d_w_geom, F->w_total * F->w_e * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(geom, w.geom, w.total * w.e * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
 
@@ -3818,42 +3846,38 @@ extern "C" int rda_debug_fleet_world(rda_fleet *F, double *geom, int32_t *n_tota
 static int fleet_ray_check(const rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
                            const double *range_max, size_t &total)
 {
-    if (!F || !n_beams || !angle_min || !angle_max || !range_min || !range_max || !F->w_have) return RDA_ERR_ARG;
+    if (!F || !n_beams || !angle_min || !angle_max || !range_min || !range_max || !F->world.have()) return RDA_ERR_ARG;
     total = 0;
     for (int i = 0; i < F->B; ++i) { if (n_beams[i] < 0) return RDA_ERR_ARG; total += (size_t)n_beams[i]; }
     for (int i = 0; i < F->B; ++i) if (n_beams[i] > lidar::MAXB) return RDA_ERR_UNSUPPORTED;
     return RDA_OK;
 }
-struct FleetRayBuf {                      // the ranges of a ray cast, regrown for more beams
-    hbuf::Group g; double *h, *d; size_t cap;
-    int alloc(size_t n) { int rc = 0; cap = n; rc |= g.dev(&d, n); rc |= g.pin(&h, n); return rc ? RDA_ERR_HIP : RDA_OK; }
-    void commit(rda_fleet *F) { F->world_rng = std::move(g); F->d_w_ranges = d; F->h_w_ranges = h; F->w_rcap = cap; }
-};
-// the ray caster's member table for these sensors (member i's ranges at its beam offset in d_w_ranges) -> device; returns the longest scan
+// the ray caster's member table for these sensors (member i's ranges at its beam offset in rays.v.d) -> device; returns the longest scan
 static int fleet_ray_table(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
                            const double *range_max, int &maxb)
 {
     const size_t B = F->B;
+    FleetWorld &w = F->world;
     size_t off = 0;
     maxb = 0;
     for (size_t i = 0; i < B; ++i) {
-        lidar::Ray &r = F->h_w_ray[i];
+        lidar::Ray &r = w.ray.h[i];
         memset((void *)&r, 0, sizeof(r));
-        r.geom = F->d_w_geom + F->w_off[i] * F->w_e * 2; r.kind = F->d_w_kind + F->w_off[i]; r.nvert = F->d_w_nvert + F->w_off[i];
-        r.n = F->w_counts[i]; r.E = F->w_e; r.n_beams = n_beams[i];
+        r.geom = w.geom + w.off[i] * w.e * 2; r.kind = w.kind + w.off[i]; r.nvert = w.nvert + w.off[i];
+        r.n = w.counts[i]; r.E = w.e; r.n_beams = n_beams[i];
         r.angle_min = angle_min[i]; r.angle_max = angle_max[i]; r.range_min = range_min[i]; r.range_max = range_max[i];
-        r.ranges = F->d_w_ranges + off;
+        r.ranges = F->rays.v.d + off;
         off += (size_t)n_beams[i];
         maxb = n_beams[i] > maxb ? n_beams[i] : maxb;
     }
-    HIPCHK(hipMemcpyAsync(F->d_w_ray, F->h_w_ray, B * sizeof(lidar::Ray), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(w.ray.push(F->stream));
     return RDA_OK;
 }
 static void fleet_ray_launch(rda_fleet *F, const double *poses, int maxb)
 {
     if (maxb <= 0) return;
     hipLaunchKernelGGL(lidar::k_raycast_fleet, dim3((unsigned)((maxb + lidar::RAY_NT - 1) / lidar::RAY_NT), (unsigned)F->B), dim3(lidar::RAY_NT), 0, F->stream,
-                       (const lidar::Ray *)F->d_w_ray, poses);
+                       (const lidar::Ray *)F->world.ray.d, poses);
 }
 
 // the resident worlds as they stand, ray-cast from states [B][3]: one launch, one wait
@@ -3865,139 +3889,116 @@ extern "C" int rda_fleet_raycast(rda_fleet *F, const int32_t *n_beams, const dou
     if (rc != RDA_OK) return rc;
     if (!states || (total > 0 && !ranges)) return RDA_ERR_ARG;
     const size_t B = F->B;
-    if (total > F->w_rcap) {
-        FleetRayBuf t;
+    if (total > F->rays.v.n) {
+        FleetDoubles t;
         if (t.alloc(total)) return RDA_ERR_HIP;
         HIPCHK(hipStreamSynchronize(F->stream));
-        t.commit(F);
+        F->rays = std::move(t);
     }
     int maxb = 0;
     rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
     if (rc != RDA_OK) return rc;
-    memcpy(F->h_w_st, states, 3 * B * sizeof(double));
-    HIPCHK(hipMemcpyAsync(F->d_w_st, F->h_w_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
-    fleet_ray_launch(F, F->d_w_st, maxb);
+    memcpy(F->world.st.h, states, 3 * B * sizeof(double));
+    HIPCHK(F->world.st.push(F->stream));
+    fleet_ray_launch(F, F->world.st.d, maxb);
     HIPCHK(hipGetLastError());
-    if (total > 0) HIPCHK(hipMemcpyAsync(F->h_w_ranges, F->d_w_ranges, total * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    if (total > 0) HIPCHK(F->rays.v.pull(F->stream, total));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
-    if (total > 0) memcpy(ranges, F->h_w_ranges, total * sizeof(double));
+    if (total > 0) memcpy(ranges, F->rays.v.h, total * sizeof(double));
     return RDA_OK;
 }
 
 // ---- rda_fleet_rollout_lidar: the closed loop around the simulated sensor -------------------------------------------------------------------------------
 // Per tick, on the fleet's stream: k_raycast_fleet from the pose the advance kernel left (row k of the device state log; row 0: the caller's) into
-// d_w_ranges, k_scan_fleet_at on those ranges at that pose, the ONE wait for the B box counts (they choose the LamMuZ launch form, apply the zero-box rule
-// and size the staging launches - fleet_scan_stage), then k_track_fleet, the ADMM launches and k_rollout_advance as in fleet_rollout_body, and behind them
-// (moving) scene::k_move_fleet on the WORLD and (clearance_log) k_clearance_fleet against the world.  Everything is allocated before tick 0.
+// rays.v.d, k_scan_fleet_at on those ranges at that pose, the ONE wait for the B box counts (they choose the LamMuZ launch form, apply the zero-box rule
+// and size the staging launches - fleet_scan_stage), then the tick's tail as in fleet_rollout_scenes (fleet_roll_tail): k_track_fleet, the ADMM launches
+// and k_rollout_advance, and behind them (moving) scene::k_move_fleet on the WORLD and (clearance_log) k_clearance_fleet against the world.  Everything is
+// allocated before tick 0.
 extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
                                        int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
                                        const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
                                        const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
                                        int32_t *arrived_at, int32_t *nbox_log, double *clearance_log)
 {
-    if (!F || K < 1 || K > 4096 || !states || !ref_speed || !cur_index || !states_log || !u_log || !index_log || !arrived_at) return RDA_ERR_ARG;
-    if (ind_range < 1 || goal_margin < 1 || !order || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
+    const RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    int rc = roll_check_args(F, a);
+    if (rc != RDA_OK) return rc;
+    if (!order || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
     size_t total = 0;
-    int rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
+    rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
+    if (rc == RDA_OK) rc = roll_check_members(F, cur_index);
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
-    for (size_t i = 0; i < B; ++i) {
-        const rda_handle *H = F->egos[i];
-        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
-    }
     for (const rda_handle *H : F->egos) {
         if (H->follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member; a box has four vertices)
         if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
     }
     // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
-    FleetTrackTables ttrk; FleetClearLog tclr; FleetRayBuf tray;
-    hbuf::Group gtab, glog; rollout::Member *hm = nullptr, *dm = nullptr; EgoIO *hio = nullptr, *dio = nullptr; char *hlog = nullptr, *dlog = nullptr;
-    const bool need_trk = !F->d_trk_in, need_tab = !F->d_ro_m, need_log = !F->d_ro_log || K > F->roll_cap;
-    const bool need_clr = clearance_log && (size_t)K * B > F->cl_cap, need_ray = total > F->w_rcap;
+    RollReserve rsv; FleetDoubles tray;
     std::vector<SceneGrow> grow(B), none(B);                                    // a raw scene for the most boxes a member's beams can give | per tick: nothing to grow
     {
-        int bad = 0;
-        if (need_trk) bad |= ttrk.alloc(B);
-        if (need_tab) { bad |= gtab.dev(&dm, B); bad |= gtab.dev(&dio, 2 * B); bad |= gtab.pin(&hm, B); bad |= gtab.pin(&hio, 2 * B); }
-        if (need_log) { const size_t nb = roll_layout((size_t)K, B, T).bytes; bad |= glog.dev(&dlog, nb); bad |= glog.pin(&hlog, nb); }
-        if (need_clr) bad |= tclr.alloc((size_t)K * B);
-        if (need_ray) bad |= tray.alloc(total);
+        int bad = rsv.alloc(F, K, clearance_log != nullptr);
+        if (total > F->rays.v.n) bad |= tray.alloc(total);
         for (size_t i = 0; i < B && !bad; ++i) if (n_beams[i] > 0) bad |= scene_grow_alloc(F->egos[i], n_beams[i], grow[i]);
         if (!bad) bad |= fleet_lidar_reserve(F, false);                         // (last: what it makes stays with the fleet)
         if (bad) return RDA_ERR_HIP;
     }
     rc = fleet_refresh(F);                                                      // behind whatever the members still have queued
     if (rc != RDA_OK) return rc;
-    HIPCHK(hipStreamSynchronize(F->stream));                                    // shorter blocks are freed below; the pinned tables are rewritten
-    if (need_trk) ttrk.commit(F);
-    if (need_tab) { F->roll = std::move(gtab); F->d_ro_m = dm; F->d_io_roll = dio; F->h_ro_m = hm; F->h_io_roll = hio; }
-    if (need_log) { F->roll_log = std::move(glog); F->d_ro_log = dlog; F->h_ro_log = hlog; F->roll_cap = K; }
-    if (need_clr) tclr.commit(F);
-    if (need_ray) tray.commit(F);
+    rc = rsv.move_in(F, true);                                                  // (the wait: shorter blocks are freed; the pinned tables are rewritten)
+    if (rc != RDA_OK) return rc;
+    if (tray.have()) F->rays = std::move(tray);
     for (size_t i = 0; i < B; ++i) scene_grow_commit(F->egos[i], grow[i]);
-    F->roll_K = 0;                                                              // (until this rollout's logs are on the host)
     RollView rv;
     if (fleet_roll_view(F, nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
     const RollLayout lay = roll_layout((size_t)K, B, T);
     rollout::Logs lg;
-    rc = fleet_roll_inputs(F, lay, states, ref_speed, cur_index, threshold, ind_range, nom_u, lg);
+    rc = fleet_roll_inputs(F, lay, a, lg);
     if (rc != RDA_OK) return rc;
     // the sensor, scan, move and clearance tables; tick 0's poses into row 0 of the device state log
+    FleetLidar &li = F->li;
+    FleetWorld &w = F->world;
     int maxb = 0, gmax = 0;
     rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
     if (rc != RDA_OK) return rc;
-    memcpy(F->h_w_st, states, 3 * B * sizeof(double));
-    HIPCHK(hipMemcpyAsync(lg.states, F->h_w_st, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    memcpy(w.st.h, states, 3 * B * sizeof(double));
+    HIPCHK(hipMemcpyAsync(lg.states, w.st.h, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
     {
         size_t off = 0;
         for (size_t i = 0; i < B; ++i) {
-            const rda_handle *H = F->egos[i];
-            lidar::Args &a = F->h_li_args[i];
-            memset((void *)&a, 0, sizeof(a));
-            a.n_beams = n_beams[i]; a.ranges = F->d_w_ranges + off; a.angle_min = angle_min[i]; a.angle_max = angle_max[i]; a.range_max = range_max[i];
-            a.eps = eps; a.min_samples = min_samples;                            // (the pose: k_scan_fleet_at's second argument)
-            a.boxes = F->d_li_boxes + i * lidar::MAXB * 8; a.count = F->h_li_count + 2 * i;
+            lidar::Args &s = li.args.h[i];
+            memset((void *)&s, 0, sizeof(s));
+            s.n_beams = n_beams[i]; s.ranges = F->rays.v.d + off; s.angle_min = angle_min[i]; s.angle_max = angle_max[i]; s.range_max = range_max[i];
+            s.eps = eps; s.min_samples = min_samples;                            // (the pose: k_scan_fleet_at's second argument)
+            s.boxes = li.d_boxes + i * lidar::MAXB * 8; s.count = li.h_count + 2 * i;
             off += (size_t)n_beams[i];
-            scene::Move &m = F->h_w_mv[i]; rollout::Clear &c = F->h_w_cl[i];
-            memset((void *)&m, 0, sizeof(m)); memset((void *)&c, 0, sizeof(c));
-            const size_t at = F->w_off[i];
-            m.geom = F->d_w_geom + at * F->w_e * 2; m.base = F->d_w_base + at * F->w_e * 2; m.vel = F->d_w_vel + at * 2;
-            m.kind = F->d_w_kind + at; m.nvert = F->d_w_nvert + at; m.n = F->w_counts[i]; m.E = F->w_e; m.dt = H->d.c.dt;
-            clear_robot(H, c);
-            c.geom = m.geom; c.kind = m.kind; c.nvert = m.nvert; c.n = m.n; c.E = F->w_e;
-            gmax = m.n * m.E > gmax ? m.n * m.E : gmax;
+            const size_t at = w.off[i];
+            member_move_clear(F->egos[i], w.geom + at * w.e * 2, w.base + at * w.e * 2, w.vel + at * 2, w.kind + at, w.nvert + at, w.counts[i], w.e,
+                              w.mv.h[i], w.cl.h[i]);
+            gmax = w.counts[i] * w.e > gmax ? w.counts[i] * w.e : gmax;
         }
     }
-    HIPCHK(hipMemcpyAsync(F->d_li_args, F->h_li_args, B * sizeof(lidar::Args), hipMemcpyHostToDevice, F->stream));
-    HIPCHK(hipMemcpyAsync(F->d_w_mv, F->h_w_mv, B * sizeof(scene::Move), hipMemcpyHostToDevice, F->stream));
-    HIPCHK(hipMemcpyAsync(F->d_w_cl, F->h_w_cl, B * sizeof(rollout::Clear), hipMemcpyHostToDevice, F->stream));
+    HIPCHK(li.args.push(F->stream));
+    HIPCHK(w.mv.push(F->stream));
+    HIPCHK(w.cl.push(F->stream));
     const bool moves = moving && gmax > 0;
     const dim3 gmove((unsigned)((gmax + 255) / 256), (unsigned)B);
-    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_w_mv);    // `base`: the world as the call finds it
+    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)w.mv.d);       // `base`: the world as the call finds it
     for (int k = 0; k < K; ++k) {
         const double *pose = lg.states + (size_t)k * B * 3;                     // where the advance kernel of tick k - 1 wrote the states
-        for (size_t i = 0; i < B; ++i) { F->h_li_count[2 * i] = 0; F->h_li_count[2 * i + 1] = 0; }
+        for (size_t i = 0; i < B; ++i) { li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0; }
         fleet_ray_launch(F, pose, maxb);
-        hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)F->d_li_args, pose);
+        hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d, pose);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(F->stream));                                // the tick's one wait: the B box counts
-        if (nbox_log) for (size_t i = 0; i < B; ++i) nbox_log[(size_t)k * B + i] = F->h_li_count[2 * i];
+        if (nbox_log) for (size_t i = 0; i < B; ++i) nbox_log[(size_t)k * B + i] = li.h_count[2 * i];
         rc = fleet_scan_stage(F, none, nullptr, pose, order);
+        if (rc == RDA_OK) rc = fleet_roll_tail(F, k, lg, goal_margin, nullptr, moves ? w.mv.d : nullptr, gmove, clearance_log ? w.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
-        const EgoIO *io = F->d_io_roll + (k == 0 ? 0 : B);
-        hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->d_devs, io, F->d_trk_in, F->d_paths, F->d_lens, F->d_trk_out, (int)B);
-        rc = fleet_enqueue(F, io, 0);
-        if (rc != RDA_OK) return rc;
-        hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->d_ro_m,
-                           (const track::Out *)F->d_trk_out, F->d_trk_in, (double *)nullptr, lg, k, goal_margin, (int)B);
-        if (moves) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->d_w_mv, k + 1);     // where tick k + 1 finds it
-        if (clearance_log)                                                       // state k + 1 against the world of tick k + 1
-            hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->d_w_cl,
-                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->d_cl_log + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
-    return fleet_roll_fetch(F, K, lay, states, states_log, u_log, index_log, info_log, arrived_at, clearance_log);
+    return fleet_roll_fetch(F, lay, a);
 }
 
 // What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls
@@ -4006,8 +4007,8 @@ extern "C" int rda_fleet_rollout_last(rda_fleet *F, double *out_u, double *end_h
 {
     if (!F || F->roll_K < 1) return RDA_ERR_ARG;
     const RollLayout lay = roll_layout((size_t)F->roll_K, (size_t)F->B, (size_t)F->T);
-    if (out_u) memcpy(out_u, F->h_ro_log + lay.lastu, (size_t)F->B * traj_u(F->T) * sizeof(double));
-    if (end_heading) memcpy(end_heading, F->h_ro_log + lay.endh, (size_t)F->B * sizeof(double));
+    if (out_u) memcpy(out_u, F->ro_log.log.h + lay.lastu, (size_t)F->B * traj_u(F->T) * sizeof(double));
+    if (end_heading) memcpy(end_heading, F->ro_log.log.h + lay.endh, (size_t)F->B * sizeof(double));
     return RDA_OK;
 }
 
