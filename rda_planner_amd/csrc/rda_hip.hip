@@ -1368,55 +1368,120 @@ __global__ __launch_bounds__(64) void k_follow_back(Dev d, const int *map, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// A handle owns its device / pinned buffers through the groups near the end (Dev and the members below hold views into them), its
-// events and its streams: deleting a handle releases everything, the streams first (each is synchronised before it is destroyed).
+// The two blocks every tick passes through: offsets and sizes in doubles, functions of the horizon T.  Host code takes them from here.
+// Three device places spell the same layouts out and keep their own text (the code of the su kernels follows how their source is
+// cut into functions): publish_result (result block), k_track and k_su_tracked (step block).  Whoever changes a block visits those three.
+constexpr size_t traj_s(size_t T) { return 3 * (T + 1); }      // a state trajectory [3][T+1]
+constexpr size_t traj_u(size_t T) { return 2 * T; }            // a control trajectory [2][T]
+// Step block  nom_s [3(T+1)] | nom_u [2T] | ref [3(T+1)] | speed [1]:  rda_handle::step (its four parts on the device: step_views), and one per member in
+// the fleet's `in`
+constexpr size_t step_u(size_t T) { return traj_s(T); }
+constexpr size_t step_ref(size_t T) { return step_u(T) + traj_u(T); }
+constexpr size_t step_speed(size_t T) { return step_ref(T) + traj_s(T); }     // (= the block without its speed: what a tracked tick reads back)
+constexpr size_t step_doubles(size_t T) { return step_speed(T) + 1; }
+// Result block  u [2T] | s [3(T+1)] | rda_info | track::Out | non-convex count (long long) | sequence word:  rda_handle::res (ResultBlock: the parts
+// are computed from these offsets, nowhere stored), identical on the device and in pinned memory.  The zero-copy form publishes the sequence word behind the mirrored block; the D2H form copies the block without it.
+constexpr size_t res_s(size_t T) { return traj_u(T); }
+constexpr size_t res_info(size_t T) { return res_s(T) + traj_s(T); }          // (= u | s alone: a member's block of the fleet's h_out / d_out)
+constexpr size_t res_track(size_t T) { return res_info(T) + sizeof(rda_info) / sizeof(double); }
+constexpr size_t res_nonconvex(size_t T) { return res_track(T) + sizeof(track::Out) / sizeof(double); }
+constexpr size_t res_seq(size_t T) { return res_nonconvex(T) + 1; }
+constexpr size_t res_copied_doubles(size_t T) { return res_seq(T); }
+constexpr size_t res_doubles(size_t T) { return res_seq(T) + 1; }
+static_assert(sizeof(rda_info) % sizeof(double) == 0 && sizeof(track::Out) % sizeof(double) == 0, "info and track output are whole doubles of the result block");
+static_assert(res_doubles(1) == 2 * 1 + 3 * (1 + 1) + 8 && res_doubles(RDA_TMAX) == 2 * RDA_TMAX + 3 * (RDA_TMAX + 1) + 8, "the result block keeps its size (publish_result)");
+static_assert(step_doubles(1) == 2 * 3 * (1 + 1) + 2 * 1 + 1 && step_doubles(RDA_TMAX) == 2 * 3 * (RDA_TMAX + 1) + 2 * RDA_TMAX + 1, "the step block keeps its size (k_track, k_su_tracked)");
+static_assert(9 * su::NT >= track::LDS_DOUBLES, "TrackedRefWait runs track::run in the su solve's `part` scratch");
+
+// The table sets of a handle, each a struct held by value.  Those that rda_create_opts makes hold views into rda_handle::mem; those made on first use and
+// regrown on demand own their Group: a call builds the new set beside the old one and moves it in (H->x = std::move(built)); H->x = {} releases one.
+struct StageBufs { double *A = nullptr, *b = nullptr; int *cone = nullptr; };     // pinned, N slots: the host-staged obstacles on their way to Dev::A, b, cone
+struct ResultBlock {                      // the step path's result block on the device and its pinned mirror, which k_finish writes (see there) or a D2H copy
+    hbuf::Pair<double> blk; size_t T = 0; unsigned long long seq = 0;
+    double *out_u() const { return blk.d; }
+    double *out_s() const { return blk.d + res_s(T); }
+    rda_info *info() const { return (rda_info *)(blk.d + res_info(T)); }
+    track::Out *track() const { return (track::Out *)(blk.d + res_track(T)); }
+    const rda_info *h_info() const { return (const rda_info *)(blk.h + res_info(T)); }
+    const track::Out *h_track() const { return (const track::Out *)(blk.h + res_track(T)); }
+};
+struct TraceSet {                         // rda_upload_trace: K steps' inputs and where their results go
+    hbuf::Group g; int K = 0; double *s = nullptr, *u = nullptr, *ref = nullptr, *speed = nullptr, *out_u = nullptr, *out_s = nullptr; rda_info *info = nullptr;
+    int alloc(size_t k, size_t ns, size_t nu)
+    {
+        K = (int)k;
+        return (g.dev(&s, k * ns) | g.dev(&u, k * nu) | g.dev(&ref, k * ns) | g.dev(&speed, k) |
+                g.dev(&out_u, k * nu) | g.dev(&out_s, k * ns) | g.dev(&info, k)) ? RDA_ERR_HIP : RDA_OK;
+    }
+};
+struct PathSet { hbuf::Group g; double *d = nullptr; int len = 0; };     // device-side pre_process (rda_upload_path / rda_step_tracked): the path [len][3]
+// The raw scene block, identical on the host (pinned) and on the device:  geom [n][E][2] | vel [n][2] | robot [2] | nonconvex counter (int, padded to 8
+// bytes) | kind [n] | nvert [n].  Offsets in doubles, size in bytes.
+struct SceneLayout { size_t vel, robot, nonconvex, ints, bytes; };
+static SceneLayout scene_layout(size_t n, size_t E)
+{
+    SceneLayout l;
+    l.vel = n * E * 2; l.robot = l.vel + n * 2; l.nonconvex = l.robot + 2; l.ints = l.nonconvex + 1; l.bytes = l.ints * sizeof(double) + 2 * n * sizeof(int);
+    return l;
+}
+// device-side obstacle pipeline (rda_upload_scene): the raw scene and the kernels' scratch for up to `cap` obstacles | the pinned staging block (ONE H2D copy
+// per upload).  Grown on demand, each on its own.
+struct SceneDev {
+    hbuf::Group g; double *blk = nullptr, *key = nullptr; int *sel = nullptr; int cap = 0;
+    int alloc(int n, size_t E)
+    {
+        cap = n;
+        return (g.dev(&blk, scene_layout((size_t)n, E).bytes / sizeof(double) + 1) | g.dev(&sel, (size_t)n) | g.dev(&key, (size_t)n)) ? RDA_ERR_HIP : RDA_OK;
+    }
+    bool have() const { return blk != nullptr; }
+};
+struct SceneHost {
+    hbuf::Group g; char *blk = nullptr; size_t bytes = 0;
+    int alloc(size_t n) { bytes = n; return g.pin(&blk, n) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return blk != nullptr; }
+};
+struct SceneSet { SceneDev dev; SceneHost host; scene::Args args; int n = 0; };     // args, n: the resident raw scene as the conversion kernels were last given it (n = 0: none)
+// device-side lidar front end (rda_scan_boxes / rda_upload_scan), made by the first scan: the boxes of the last scan on the device; pinned, read / written by
+// the kernel itself: the ranges, the two counters, and the host's copy of labels and boxes
+struct LidarSet {
+    hbuf::Group g; double *d_boxes = nullptr, *h_ranges = nullptr, *h_boxes = nullptr; int *h_count = nullptr, *h_labels = nullptr;
+    int alloc()
+    {
+        return (g.dev(&d_boxes, (size_t)lidar::MAXB * 8) | g.pin(&h_ranges, (size_t)lidar::MAXB) | g.pin(&h_count, 2) | g.pin(&h_labels, (size_t)lidar::MAXB) |
+                g.pin(&h_boxes, (size_t)lidar::MAXB * 8)) ? RDA_ERR_HIP : RDA_OK;
+    }
+    bool have() const { return d_boxes != nullptr; }
+};
+// rda_opts::duals_follow: slot -> raw-scene entry of the staging the dual state is arranged by (prev_used = -1: none yet), the map and the gathered rows
+struct FollowSet { int *prev_sel = nullptr, *map = nullptr; double *tmp = nullptr; int prev_used = -1; };
+struct ShardLink {                        // obstacle-shard exchange (RCCL, resolved lazily with dlopen so that single-GPU use has no rccl dependency)
+    void *lib = nullptr, *comm = nullptr;
+    int (*allgather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
+    int (*comm_destroy)(void *) = nullptr;
+    hbuf::Group g; unsigned long long *verdict = nullptr, vseq = 0;     // pinned early-stop verdict word of the su launches (made with the communicator)
+};
+struct OpenTick {                         // a tick opened by rda_tracked_begin and not yet closed by rda_tracked_finish
+    int pending = 0, pending_scene = 0; const double *in_u = nullptr;
+    int stages = 0, has_event = 0;        // see rda_tracked_begin
+    int scene_on_s2 = 0;                  // in-tick scene staging runs beside the first su-problem (stream2, ev_tick, ev_scene)
+};
+
+// ------------------------------------------------------------------------------------------------
+// A handle owns its device / pinned buffers through `mem`, `terms` and the table sets above (Dev holds views into the first two), its events and its
+// streams: deleting a handle releases everything, the streams first (each is synchronised before it is destroyed).
 struct rda_handle {
     Dev d;
-    rda_opts opts;                                        // as handed to rda_create_opts (copied)
-    size_t su_lds;
-    // staging
-    double *h_stage_A, *h_stage_b; int *h_stage_cone;    // pinned, N slots
-    double *h_step;                                       // pinned: the step block (step_doubles)
-    double *d_step;                                       // device copy of the above (slot 0 of the step path)
-    double *d_out_u, *d_out_s; rda_info *d_info;          // result block of the step path (res_doubles) and pointers into it
-    double *h_out; rda_info *h_info;                      // pinned
-    unsigned long long res_seq; int zero_copy;           // result mirror written by k_finish (see there); RDA_ZERO_COPY=0: D2H copy + stream sync
-    unsigned long long *h_verdict = nullptr; unsigned long long vseq = 0;   // pinned early-stop verdict word of the su launches (sharded handles with a communicator)
-    // trace path
-    int K; double *d_tr_s, *d_tr_u, *d_tr_ref, *d_tr_speed, *d_tr_out_u, *d_tr_out_s; rda_info *d_tr_info;
-    // obstacle-shard exchange (RCCL, resolved lazily with dlopen so that single-GPU use has no rccl dependency)
-    void *nccl_lib, *comm;
-    int (*p_allgather)(const void *, void *, size_t, int, void *, hipStream_t);
-    int (*p_comm_destroy)(void *);
-    // a tick opened by rda_tracked_begin and not yet closed by rda_tracked_finish
-    int pending, pending_scene; const double *pending_in_u;
-    int tick_stages, tick_has_event;     // see rda_tracked_begin
-    int fuse_track; size_t su_trk_lds; unsigned long long trk_seq;
-    int lmz_split;                        // dense LamMuZ grids as two launches: common path, then the deferred rows (RDA_LMZ_SPLIT=0: one fused kernel)
-    int early_finish;                     // the su launch that detects the early stop writes the result slot (RDA_EARLY_FINISH=0: k_finish does)    // k_su_tracked (RDA_FUSE_TRACK=0: k_track and k_su as two launches)
-    int scene_on_s2;                      // in-tick scene staging runs beside the first su-problem (stream2, ev_tick, ev_scene)
-    // timing
-    int timing; size_t ev_used[4];       // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers, 3 lidar scans (second stream)
-    // device-side obstacle pipeline (rda_upload_scene): scene description and scratch, grown on demand
-    int sc_cap; int *d_sc_sel; double *d_sc_blk, *d_sc_key;     // d_sc_blk mirrors the pinned block h_sc (ONE H2D copy per upload)
-    scene::Args sc_args; int sc_n;                              // the resident raw scene as the conversion kernels were last given it (sc_n = 0: none)
-    char *h_sc; size_t h_sc_bytes;
-    // device-side lidar front end (rda_scan_boxes / rda_upload_scan), allocated by the first scan: the boxes of the last scan on the device; pinned,
-    // read / written by the kernel itself: the ranges, the two counters, and the host's copy of labels and boxes
-    double *d_li_boxes, *h_li_ranges, *h_li_boxes; int *h_li_count, *h_li_labels;
-    // device-side pre_process (rda_upload_path / rda_step_tracked)
-    double *d_path; int path_len; track::Out *d_trk, *h_trk;
-    int dense_from;          // grids above this many workgroups use the dense form of the LamMuZ launch (rda_opts::lmz_dense_from)
-    int ip_rows;             // interior-point mode runs the row-parallel kernel (shape allows it and rda_opts::lmz_ip_rows)
-    int admm_it;             // host-driven ADMM pieces (rda_admm_*): the iteration rda_admm_su was last called with
-    int stepped;             // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
-    // rda_opts::duals_follow: slot -> raw-scene entry of the staging the dual state is arranged by (prev_used = -1: none yet)
-    int follow; int *d_prev_sel, *d_follow_map; double *d_follow_tmp; int prev_used;
+    rda_opts opts;                        // sanitised (opts_sanitised): what the host code reads its switches from
+    size_t su_lds = 0, su_trk_lds = 0; unsigned long long trk_seq = 0;
+    int ip_rows = 0;         // interior-point mode runs the row-parallel kernel (shape allows it and rda_opts::lmz_ip_rows)
+    int admm_it = 0;         // host-driven ADMM pieces (rda_admm_*): the iteration rda_admm_su was last called with
+    int stepped = 0;         // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
+    int timing = 0; size_t ev_used[4] = {0, 0, 0, 0};     // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers, 3 lidar scans (second stream)
     std::vector<double> rob_G, rob_h;     // the robot's G x <= h as handed to rda_create (host copy: the clearance's robot vertices are solved from it)
-    // owners
-    hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL), staging, result slot, follow tables
+    hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL) and the four sets below
     hbuf::Group terms;                    // Dev::coef, coefL (rda_shard_config replaces them)
-    hbuf::Group trace, path, scene, scene_host, verdict, lidar;    // d_tr_*; d_path; d_sc_*; h_sc; h_verdict; d_li_*, h_li_*
+    StageBufs stage; hbuf::Pair<double> step; ResultBlock res; FollowSet fol;      // step: the step block (step_doubles), pinned and on the device
+    TraceSet trace; PathSet path; SceneSet sc; LidarSet li; ShardLink shard; OpenTick tick;
     std::vector<hbuf::Event> ev[4];
     hbuf::Event ev_tick, ev_scene;
     hbuf::Stream stream, stream2;         // (last: destroyed first)
@@ -1436,31 +1501,7 @@ extern "C" const char *rda_strerror(int code)
 extern "C" int rda_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 extern "C" int rda_set_device(int dev) { HIPCHK(hipSetDevice(dev)); return RDA_OK; }
 
-// The two blocks every tick passes through: offsets and sizes in doubles, functions of the horizon T.  Host code takes them from here.
-// Three device places spell the same layouts out and keep their own text (the code of the su kernels follows how their source is
-// cut into functions): publish_result (result block), k_track and k_su_tracked (step block).  Whoever changes a block visits those three.
-constexpr size_t traj_s(size_t T) { return 3 * (T + 1); }      // a state trajectory [3][T+1]
-constexpr size_t traj_u(size_t T) { return 2 * T; }            // a control trajectory [2][T]
-// Step block  nom_s [3(T+1)] | nom_u [2T] | ref [3(T+1)] | speed [1]:  h_step / d_step, and one per member in the fleet's h_in / d_in
-constexpr size_t step_u(size_t T) { return traj_s(T); }
-constexpr size_t step_ref(size_t T) { return step_u(T) + traj_u(T); }
-constexpr size_t step_speed(size_t T) { return step_ref(T) + traj_s(T); }     // (= the block without its speed: what a tracked tick reads back)
-constexpr size_t step_doubles(size_t T) { return step_speed(T) + 1; }
-// Result block  u [2T] | s [3(T+1)] | rda_info | track::Out | non-convex count (long long) | sequence word:  d_out_u / h_out, identical on the
-// device and in pinned memory.  The zero-copy form publishes the sequence word behind the mirrored block; the D2H form copies the block without it.
-constexpr size_t res_s(size_t T) { return traj_u(T); }
-constexpr size_t res_info(size_t T) { return res_s(T) + traj_s(T); }          // (= u | s alone: a member's block of the fleet's h_out / d_out)
-constexpr size_t res_track(size_t T) { return res_info(T) + sizeof(rda_info) / sizeof(double); }
-constexpr size_t res_nonconvex(size_t T) { return res_track(T) + sizeof(track::Out) / sizeof(double); }
-constexpr size_t res_seq(size_t T) { return res_nonconvex(T) + 1; }
-constexpr size_t res_copied_doubles(size_t T) { return res_seq(T); }
-constexpr size_t res_doubles(size_t T) { return res_seq(T) + 1; }
-static_assert(sizeof(rda_info) % sizeof(double) == 0 && sizeof(track::Out) % sizeof(double) == 0, "info and track output are whole doubles of the result block");
-static_assert(res_doubles(1) == 2 * 1 + 3 * (1 + 1) + 8 && res_doubles(RDA_TMAX) == 2 * RDA_TMAX + 3 * (RDA_TMAX + 1) + 8, "the result block keeps its size (publish_result)");
-static_assert(step_doubles(1) == 2 * 3 * (1 + 1) + 2 * 1 + 1 && step_doubles(RDA_TMAX) == 2 * 3 * (RDA_TMAX + 1) + 2 * RDA_TMAX + 1, "the step block keeps its size (k_track, k_su_tracked)");
-static_assert(9 * su::NT >= track::LDS_DOUBLES, "TrackedRefWait runs track::run in the su solve's `part` scratch");
-
-// Solver options: library defaults, then the RDA_* environment overrides (experiments and A/B runs; read HERE only)
+// Solver options: the library defaults.  No environment is read here or anywhere else in the library
 extern "C" void rda_opts_init(rda_opts *o)
 {
     if (!o) return;
@@ -1476,7 +1517,7 @@ extern "C" void rda_opts_init(rda_opts *o)
     // mu <= 1e-11 (1 + |grad|), |r_p| <= 1e-10), so that the stop test can accept the start when the new su-problem's optimality
     // conditions already hold there (a converging ADMM in a static scene: 57 % of the north-star solves) - zero Newton steps
     { const double ez[5] = {1e-12, 1e-12, 1e-12, 0.999999, 1e-7}; for (int i = 0; i < 5; ++i) o->su_easy[i] = ez[i]; }
-    // (No environment overrides here since round 5: a library call has no process-global configuration.  The RDA_* switches of the A/B tools and
+    // (A library call has no process-global configuration: the RDA_* switches of the A/B tools and
     // tests are applied by the Python host package - rda_planner_amd.rda_solver.hip_options - to the struct it hands to rda_create_opts.)
 }
 // The options as the solver uses them (null: the defaults): entries outside their range clamped or replaced by the values of rda_opts_init.
@@ -1534,10 +1575,9 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     std::unique_ptr<rda_handle> owner(new rda_handle());     // a failure on the way drops the handle and with it what was built
     rda_handle *H = owner.get();
     memset(&H->d, 0, sizeof(Dev));
-    H->d.c = *cfg; H->d.nt = 1; H->d.obstacle_num = 0; H->K = 0; H->timing = 0;
-    const rda_opts o = opts_sanitised(opts);
-    H->opts = opts ? *opts : o;
-    H->d.warm = o.lmz_warm; H->dense_from = o.lmz_dense_from;
+    H->d.c = *cfg; H->d.nt = 1; H->d.obstacle_num = 0;
+    const rda_opts &o = H->opts = opts_sanitised(opts);
+    H->d.warm = o.lmz_warm;
     H->d.rows = (cfg->E + cfg->R + 1 <= 16) && o.lmz_rows != 0;
     H->d.nmv = robot_candidates(cfg->R, G, h, H->d.muc, H->d.rv, &H->d.nrv);
     H->rob_G.assign(G, G + 2 * cfg->R); H->rob_h.assign(h, h + cfg->R);
@@ -1554,8 +1594,6 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     H->d.su_land_first = o.su_land_first; H->d.su_land_blind_from = o.su_land_blind_from;
     H->d.su_land = o.su_land; H->d.su_land_rho = o.su_land_rho;
     for (int i = 0; i < 3; ++i) { H->d.su_tol[i] = o.su_tol[i]; H->d.su_tol_early[i] = o.su_tol_early[i]; H->d.su_land_tol[i] = o.su_land_tol[i]; }
-    H->follow = o.duals_follow != 0; H->prev_used = -1;
-    H->nccl_lib = nullptr; H->comm = nullptr; H->p_allgather = nullptr; H->p_comm_destroy = nullptr; H->ev_used[0] = H->ev_used[1] = H->ev_used[2] = H->ev_used[3] = 0;
     const size_t T = cfg->T, N = cfg->N, E = cfg->E, R = cfg->R;
     HIPCHK(hipStreamCreate(H->stream.out()));
     HIPCHK(hipStreamCreate(H->stream2.out()));
@@ -1576,9 +1614,9 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     rc |= m.dev(&d.s, traj_s(T)); rc |= m.dev(&d.u, traj_u(T)); rc |= m.dev(&d.pose, 4 * T);
     rc |= m.dev(&d.ctrl, 1);
     rc |= m.dev(&d.su_lam_keep, 10 * T);
-    if (H->follow) {
-        rc |= m.dev(&H->d_prev_sel, N); rc |= m.dev(&H->d_follow_map, N);
-        rc |= m.dev(&H->d_follow_tmp, N * (T + 1) * (E + R + 2) + 2 * N * T);
+    if (H->opts.duals_follow) {
+        rc |= m.dev(&H->fol.prev_sel, N); rc |= m.dev(&H->fol.map, N);
+        rc |= m.dev(&H->fol.tmp, N * (T + 1) * (E + R + 2) + 2 * N * T);
     }
 #if defined(SU_TRACE)
     if (o.su_prof) rc |= m.dev(&d.su_prof, su::PROF_WORDS);                   // 16 + the per-wave event trace of the LAST su launch (tools/su_trace.py)
@@ -1587,14 +1625,13 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
 #else
     if (o.su_prof) return RDA_ERR_UNSUPPORTED;     // phase counters: profiling builds only (-DSU_PROF / -DSU_FINE, tools/su_phase_profile.py)
 #endif
-    rc |= m.dev(&H->d_step, step_doubles(T));
-    rc |= m.dev(&H->d_out_u, res_doubles(T));
-    rc |= m.pin(&H->h_stage_A, N * (T + 1) * E * 2); rc |= m.pin(&H->h_stage_b, N * (T + 1) * E); rc |= m.pin(&H->h_stage_cone, N);
-    rc |= m.pin(&H->h_step, step_doubles(T)); rc |= m.pin(&H->h_out, res_doubles(T));
+    rc |= m.dev(&H->step.d, step_doubles(T)); rc |= m.dev(&H->res.blk.d, res_doubles(T));
+    rc |= m.pin(&H->stage.A, N * (T + 1) * E * 2); rc |= m.pin(&H->stage.b, N * (T + 1) * E); rc |= m.pin(&H->stage.cone, N);
+    rc |= m.pin(&H->step.h, step_doubles(T)); rc |= m.pin(&H->res.blk.h, res_doubles(T));
+    H->step.n = step_doubles(T); H->res.blk.n = res_doubles(T); H->res.T = T;      // (the two pairs filled in by hand: the allocations keep their order)
     H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated);
     if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
     if (rc) return RDA_ERR_HIP;
-    H->d_out_s = H->d_out_u + res_s(T); H->d_info = (rda_info *)(H->d_out_u + res_info(T)); H->d_trk = (track::Out *)(H->d_out_u + res_track(T));
     { const int hard = 99; HIPCHK(hipMemcpy(&d.ctrl->su_last, &hard, sizeof(int), hipMemcpyHostToDevice)); }     // no su history yet
     HIPCHK(hipMemcpy(d.G, G, 2 * R * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.h, h, R * sizeof(double), hipMemcpyHostToDevice));
@@ -1602,20 +1639,13 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     HIPCHK(hipMemcpy(d.dis, ones.data(), T * sizeof(double), hipMemcpyHostToDevice));
     std::vector<int> cn(N, 1);                                              // para_cone init, rda_solver.py:158
     HIPCHK(hipMemcpy(d.cone, cn.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    H->res_seq = 0; H->zero_copy = o.zero_copy;
-    H->h_info = (rda_info *)(H->h_out + res_info(T)); H->h_trk = (track::Out *)(H->h_out + res_track(T));
     H->su_lds = su::lds_bytes((int)T);
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_lds)));
     HIPCHK(hipFuncSetAttribute((const void *)k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_lds));
     H->su_trk_lds = H->su_lds > track::LDS_DOUBLES * sizeof(double) ? H->su_lds : track::LDS_DOUBLES * sizeof(double);
     RDA_SU_DISPATCH((int)T, HIPCHK(hipFuncSetAttribute((const void *)k_su_tracked<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)H->su_trk_lds)));
-    H->fuse_track = o.fuse_track; H->tick_stages = 0; H->tick_has_event = 0; H->trk_seq = 0;
-    H->early_finish = o.early_finish;
-    H->lmz_split = o.lmz_split;
-    H->admm_it = 0;
     // the terms of a fresh handle are all zero: their block partials (zero sums, every slot NEAR: a = 0 puts the hinge at -d < 0)
-    int rcf = terms_rebuild(H);
-    if (rcf != RDA_OK) return rcf;
+    if (int rcf = terms_rebuild(H)) return rcf;
     HIPCHK(hipStreamSynchronize(H->stream));
     *out = owner.release();
     return RDA_OK;
@@ -1627,7 +1657,7 @@ extern "C" void rda_destroy(rda_handle *H)
     if (!H) return;
     (void)hipStreamSynchronize(H->stream);         // nothing is released while a launch or a collective may still use it
     (void)hipStreamSynchronize(H->stream2);
-    if (H->comm && H->p_comm_destroy) H->p_comm_destroy(H->comm);
+    if (H->shard.comm && H->shard.comm_destroy) H->shard.comm_destroy(H->shard.comm);  // (before the streams go: not a destructor's work)
     delete H;
 }
 
@@ -1722,15 +1752,6 @@ extern "C" int rda_debug_su_prof(rda_handle *H, long long *out16)
     return RDA_OK;
 }
 
-extern "C" int rda_debug_su_land(rda_handle *H, int32_t *out4)
-{
-    if (!H || !out4) return RDA_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(H->stream));
-    HIPCHK(hipMemcpy(out4, H->d.ctrl->land_stat, 4 * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(H->d.ctrl->land_stat, 0, su::LAND_STATS * sizeof(int)));
-    return RDA_OK;
-}
-
 extern "C" int rda_debug_su_land_n(rda_handle *H, int32_t *out, int n)
 {
     if (!H || !out || n < 1 || n > su::LAND_STATS) return RDA_ERR_ARG;
@@ -1739,6 +1760,7 @@ extern "C" int rda_debug_su_land_n(rda_handle *H, int32_t *out, int n)
     HIPCHK(hipMemset(H->d.ctrl->land_stat, 0, su::LAND_STATS * sizeof(int)));
     return RDA_OK;
 }
+extern "C" int rda_debug_su_land(rda_handle *H, int32_t *out4) { return rda_debug_su_land_n(H, out4, 4); }      // the first four, as before the counters grew
 
 // debug, -DSU_TRACE builds only: (event id, clock64) pairs of the four waves of the LAST su launch of this handle, [4][cap][2]; *n_out = events per wave
 extern "C" int rda_debug_su_trace(rda_handle *H, long long *out, int cap, int *n_out)
@@ -1774,7 +1796,7 @@ extern "C" int rda_debug_slot_src(rda_handle *H, int32_t *src, int32_t *used)
 {
     if (!H || !src || !used) return RDA_ERR_ARG;
     HIPCHK(hipStreamSynchronize(H->stream));
-    if (H->scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
+    if (H->tick.scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
     *used = H->d.slot_src ? H->d.src_used : 0;
     if (*used > 0) HIPCHK(hipMemcpy(src, H->d.slot_src, (size_t)*used * sizeof(int), hipMemcpyDeviceToHost));
     return RDA_OK;
@@ -1804,25 +1826,25 @@ static int obstacles_stage(rda_handle *H, int n_obs, const double *A, const doub
     const size_t T = d.c.T, N = d.c.N, E = d.c.E;
     if (n_obs <= 0) { d.obstacle_num = 0; return RDA_OK; }       // nothing written: stale A, b stay
     if (!A || !b || !cone) return RDA_ERR_ARG;
-    if (H->follow) return RDA_ERR_UNSUPPORTED;                   // duals_follow: host-staged slots carry no obstacle identity
+    if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;        // duals_follow: host-staged slots carry no obstacle identity
     d.sc_bad = nullptr;
-    H->sc_n = 0;                                                 // the slots no longer come from the resident raw scene: rda_scene_resort must not rebuild them from it
+    H->sc.n = 0;                                                 // the slots no longer come from the resident raw scene: rda_scene_resort must not rebuild them from it
     const size_t nt = per_t ? T + 1 : 1;
     for (size_t n = 0; n < N; ++n) {
         size_t src = n < (size_t)n_obs ? n : (size_t)n_obs - 1;   // quirk Q3: duplicate the last obstacle
-        memcpy(&H->h_stage_A[n * nt * E * 2], &A[src * nt * E * 2], nt * E * 2 * sizeof(double));
-        memcpy(&H->h_stage_b[n * nt * E], &b[src * nt * E], nt * E * sizeof(double));
-        H->h_stage_cone[n] = cone[src];
+        memcpy(&H->stage.A[n * nt * E * 2], &A[src * nt * E * 2], nt * E * 2 * sizeof(double));
+        memcpy(&H->stage.b[n * nt * E], &b[src * nt * E], nt * E * sizeof(double));
+        H->stage.cone[n] = cone[src];
         if (cone[src] == 1) {         // canonical circle only (mpc.py:440-458)
             for (size_t t = 0; t < nt; ++t) {
-                const double *At = &H->h_stage_A[(n * nt + t) * E * 2];
+                const double *At = &H->stage.A[(n * nt + t) * E * 2];
                 if (E < 3 || At[0] != 1 || At[1] != 0 || At[2] != 0 || At[3] != 1 || At[4] != 0 || At[5] != 0) return RDA_ERR_UNSUPPORTED;
             }
         }
     }
-    HIPCHK(hipMemcpyAsync(d.A, H->h_stage_A, N * nt * E * 2 * sizeof(double), hipMemcpyHostToDevice, H->stream));
-    HIPCHK(hipMemcpyAsync(d.b, H->h_stage_b, N * nt * E * sizeof(double), hipMemcpyHostToDevice, H->stream));
-    HIPCHK(hipMemcpyAsync(d.cone, H->h_stage_cone, N * sizeof(int), hipMemcpyHostToDevice, H->stream));
+    HIPCHK(hipMemcpyAsync(d.A, H->stage.A, N * nt * E * 2 * sizeof(double), hipMemcpyHostToDevice, H->stream));
+    HIPCHK(hipMemcpyAsync(d.b, H->stage.b, N * nt * E * sizeof(double), hipMemcpyHostToDevice, H->stream));
+    HIPCHK(hipMemcpyAsync(d.cone, H->stage.cone, N * sizeof(int), hipMemcpyHostToDevice, H->stream));
     d.nt = (int)nt; d.obstacle_num = (int)N;
     d.slot_src = nullptr; d.src_used = 0;                    // host-staged slots: the remembered supports are keyed by slot
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)((N * nt + 3) / 4)), dim3(256), 0, H->stream, d);
@@ -1836,31 +1858,21 @@ extern "C" int rda_upload_obstacles(rda_handle *H, int n_obs, const double *A, c
 }
 
 // ---- device-side obstacle pipeline -----------------------------------------------------------------------------
-// raw scene block, identical on the host (pinned) and on the device: geom [n][E][2] | vel [n][2] | robot [2] | nonconvex
-// counter (int, padded to 8 bytes) | kind [n] | nvert [n]
-static size_t scene_block_bytes(size_t n, size_t E) { return n * (E * 2 + 2) * sizeof(double) + 3 * sizeof(double) + 2 * n * sizeof(int); }
-// the larger buffers a scene of n obstacles needs, built beside the old ones (alloc) and moved in (commit) only when all of them exist - rda_fleet_upload_scans
-// allocates for every member before it commits for any
-struct SceneGrow {
-    bool grow_dev = false, grow_host = false; int cap = 0; size_t need = 0;
-    hbuf::Group dev, host;
-    double *blk = nullptr, *key = nullptr; int *sel = nullptr; char *hsc = nullptr;
-};
+// the grown scene set, built beside the old one (alloc) and moved in (commit) only when all of it exists - rda_fleet_upload_scans allocates for every member
+// before it commits for any.  A part that stays empty has nothing to grow.
+struct SceneGrow { SceneDev dev; SceneHost host; };
 static int scene_grow_alloc(const rda_handle *H, int n, SceneGrow &g)
 {
-    const size_t E = H->d.c.E;
-    g.need = scene_block_bytes((size_t)n, E);
-    g.grow_dev = n > H->sc_cap; g.grow_host = g.need > H->h_sc_bytes;
-    g.cap = n + n / 2 + 16;
+    const size_t E = H->d.c.E, need = scene_layout((size_t)n, E).bytes;
     int rc = 0;
-    if (g.grow_dev) { rc |= g.dev.dev(&g.blk, scene_block_bytes((size_t)g.cap, E) / sizeof(double) + 1); rc |= g.dev.dev(&g.sel, (size_t)g.cap); rc |= g.dev.dev(&g.key, (size_t)g.cap); }
-    if (g.grow_host) rc |= g.host.pin(&g.hsc, g.need * 2);
+    if (n > H->sc.dev.cap) rc |= g.dev.alloc(n + n / 2 + 16, E);
+    if (need > H->sc.host.bytes) rc |= g.host.alloc(need * 2);
     return rc ? RDA_ERR_HIP : RDA_OK;
 }
 static void scene_grow_commit(rda_handle *H, SceneGrow &g)
 {
-    if (g.grow_dev) { H->scene = std::move(g.dev); H->d_sc_blk = g.blk; H->d_sc_sel = g.sel; H->d_sc_key = g.key; H->sc_cap = g.cap; H->sc_n = 0; }
-    if (g.grow_host) { H->scene_host = std::move(g.host); H->h_sc = g.hsc; H->h_sc_bytes = g.need * 2; }
+    if (g.dev.have()) { H->sc.dev = std::move(g.dev); H->sc.n = 0; }      // (the resident raw scene went with the old block)
+    if (g.host.have()) H->sc.host = std::move(g.host);
 }
 static int scene_reserve(rda_handle *H, int n)
 {
@@ -1869,27 +1881,48 @@ static int scene_reserve(rda_handle *H, int n)
     scene_grow_commit(H, g);
     return RDA_OK;
 }
+// the conversion kernels' arguments for a raw scene of n obstacles in the handle's (reserved) device block, its slots built for nt stages
+static scene::Args scene_args(const rda_handle *H, int n, int nt, int order)
+{
+    const Dev &d = H->d;
+    const SceneLayout l = scene_layout((size_t)n, (size_t)d.c.E);
+    double *db = H->sc.dev.blk;
+    scene::Args a;
+    a.n = n; a.N = d.c.N; a.E = d.c.E; a.T = d.c.T; a.nt = nt; a.order = order; a.dt = d.c.dt;
+    a.kind = (int *)(db + l.ints); a.nvert = (int *)(db + l.ints) + n; a.geom = db; a.vel = db + l.vel; a.robot = db + l.robot;
+    a.key = H->sc.dev.key; a.sel = H->sc.dev.sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = (int *)(db + l.nonconvex);
+    a.rx = 0; a.ry = 0; a.robot_val = 0;
+    return a;
+}
+// The host-side record that the handle's slots now come from the raw scene `a`.  store: `a` is also the resident raw scene from now on (rda_scene_resort
+// runs the kernels on modified arguments and keeps what is stored).
+static void scene_bind(rda_handle *H, const scene::Args &a, bool store)
+{
+    Dev &d = H->d;
+    if (store) { H->sc.args = a; H->sc.n = a.n; }
+    d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;
+    d.slot_src = H->sc.dev.sel; d.src_used = a.n < a.N ? a.n : a.N;  // the remembered supports follow the obstacles through the re-binding (Dev::hint)
+}
 
-// the conversion kernels on a raw scene that is in device memory: distance keys, stable rank, half-space slots, candidate lists
-static void scene_kernels(rda_handle *H, const scene::Args &a, hipStream_t st)
+// the binding and the conversion kernels on a raw scene that is in device memory: distance keys, stable rank, half-space slots, candidate lists
+static void scene_kernels(rda_handle *H, const scene::Args &a, hipStream_t st, bool store)
 {
     Dev &d = H->d;
     const int n = a.n, N = a.N;
+    scene_bind(H, a, store);
     hipLaunchKernelGGL(scene::k_keys, dim3((n + 255) / 256), dim3(256), 0, st, a);
     hipLaunchKernelGGL(scene::k_rank, dim3((n + 15) / 16), dim3(256), 0, st, a);
     hipLaunchKernelGGL(scene::k_build, dim3((N * a.nt + 255) / 256), dim3(256), 0, st, a);
-    d.nt = a.nt; d.obstacle_num = N; d.sc_bad = a.nonconvex;
-    d.slot_src = H->d_sc_sel; d.src_used = n < N ? n : N;          // the remembered supports follow the obstacles through the re-binding (Dev::hint)
-    if (H->follow) {
+    if (H->opts.duals_follow) {
         // rda_opts::duals_follow: the dual state is re-arranged from the previous binding to this one.  Nothing of a tick's head reads
         // lam, mu, xi, z, zeta (the su-problem reads the condensed terms, which the first LamMuZ launch of the tick rewrites for every
         // slot): inside a tick this runs on the second stream beside the first su-problem like the rest of the staging.
         const int used = d.src_used;
-        const bool have = H->prev_used >= 0;
-        if (have) hipLaunchKernelGGL(k_follow_gather, dim3(N), dim3(64), 0, st, d, (const int *)H->d_sc_sel, used, (const int *)H->d_prev_sel, H->prev_used, H->d_follow_map, H->d_follow_tmp);
-        hipLaunchKernelGGL(k_follow_back, dim3(N), dim3(64), 0, st, d, have ? (const int *)H->d_follow_map : (const int *)nullptr, (const double *)H->d_follow_tmp,
-                           (const int *)H->d_sc_sel, used, H->d_prev_sel);
-        H->prev_used = used;
+        const bool have = H->fol.prev_used >= 0;
+        if (have) hipLaunchKernelGGL(k_follow_gather, dim3(N), dim3(64), 0, st, d, (const int *)H->sc.dev.sel, used, (const int *)H->fol.prev_sel, H->fol.prev_used, H->fol.map, H->fol.tmp);
+        hipLaunchKernelGGL(k_follow_back, dim3(N), dim3(64), 0, st, d, have ? (const int *)H->fol.map : (const int *)nullptr, (const double *)H->fol.tmp,
+                           (const int *)H->sc.dev.sel, used, H->fol.prev_sel);
+        H->fol.prev_used = used;
     }
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)((N * a.nt + 3) / 4)), dim3(256), 0, st, d);
 }
@@ -1903,39 +1936,31 @@ static int scene_stage(rda_handle *H, int n, const int32_t *kind, const int32_t 
     if (n_nonconvex) *n_nonconvex = 0;
     if (n <= 0) { d.obstacle_num = 0; return RDA_OK; }           // nothing written: stale A, b stay (rda_solver.py:485)
     if (!kind || !nvert || !geom || !vel || (order && !robot_xy)) return RDA_ERR_ARG;
-    const int E = d.c.E, T = d.c.T, N = d.c.N;
+    const int E = d.c.E, T = d.c.T;
     bool any_moving = false;
     for (int i = 0; i < n; ++i) {
         if (kind[i] == 1) { if (E < 3) return RDA_ERR_UNSUPPORTED; }
         else if (kind[i] != 0 || nvert[i] < 0 || nvert[i] > E) return RDA_ERR_ARG;
         any_moving = any_moving || sqrt(vel[2 * i] * vel[2 * i] + vel[2 * i + 1] * vel[2 * i + 1]) > 0.01;
     }
-    int rc = scene_reserve(H, n);
-    if (rc != RDA_OK) return rc;
+    if (int rc = scene_reserve(H, n)) return rc;
     // one pinned staging block -> its device mirror, one copy
-    const size_t o_vel = (size_t)n * E * 2, o_rob = o_vel + (size_t)n * 2, o_bad = o_rob + 2, o_int = o_bad + 1;   // in doubles
-    double *hb = (double *)H->h_sc, *db = H->d_sc_blk;
-    memcpy(hb, geom, o_vel * sizeof(double));
-    memcpy(hb + o_vel, vel, (size_t)n * 2 * sizeof(double));
-    hb[o_rob] = robot_xy ? robot_xy[0] : 0; hb[o_rob + 1] = robot_xy ? robot_xy[1] : 0;
-    hb[o_bad] = 0.0;                                                       // all-zero bits: the int counter starts at 0
-    memcpy((int *)(hb + o_int), kind, (size_t)n * sizeof(int));
-    memcpy((int *)(hb + o_int) + n, nvert, (size_t)n * sizeof(int));
-    HIPCHK(hipMemcpyAsync(db, hb, scene_block_bytes((size_t)n, (size_t)E), hipMemcpyHostToDevice, st));
-    int *const d_bad = (int *)(db + o_bad);
-    d.sc_bad = d_bad;
-    scene::Args a;
-    a.n = n; a.N = N; a.E = E; a.T = T; a.nt = any_moving ? T + 1 : 1; a.order = order; a.dt = d.c.dt;
-    a.kind = (int *)(db + o_int); a.nvert = (int *)(db + o_int) + n; a.geom = db; a.vel = db + o_vel; a.robot = db + o_rob;
-    a.key = H->d_sc_key; a.sel = H->d_sc_sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = d_bad;
-    a.rx = 0; a.ry = 0; a.robot_val = 0;
-    H->sc_args = a; H->sc_n = n;
-    scene_kernels(H, a, st);
+    const SceneLayout l = scene_layout((size_t)n, (size_t)E);
+    double *hb = (double *)H->sc.host.blk;
+    memcpy(hb, geom, l.vel * sizeof(double));
+    memcpy(hb + l.vel, vel, (size_t)n * 2 * sizeof(double));
+    hb[l.robot] = robot_xy ? robot_xy[0] : 0; hb[l.robot + 1] = robot_xy ? robot_xy[1] : 0;
+    hb[l.nonconvex] = 0.0;                                                 // all-zero bits: the int counter starts at 0
+    memcpy((int *)(hb + l.ints), kind, (size_t)n * sizeof(int));
+    memcpy((int *)(hb + l.ints) + n, nvert, (size_t)n * sizeof(int));
+    HIPCHK(hipMemcpyAsync(H->sc.dev.blk, hb, l.bytes, hipMemcpyHostToDevice, st));
+    const scene::Args a = scene_args(H, n, any_moving ? T + 1 : 1, order);
+    scene_kernels(H, a, st, true);
     HIPCHK(hipGetLastError());
     if (n_nonconvex) {
-        HIPCHK(hipMemcpyAsync(H->h_sc, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(H->sc.host.blk, a.nonconvex, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        *n_nonconvex = *(int *)H->h_sc;
+        *n_nonconvex = *(int *)H->sc.host.blk;
     } else if (sync) {
         HIPCHK(hipStreamSynchronize(st));                  // the staging block is reused by the next call
     }
@@ -1945,7 +1970,7 @@ static int scene_stage(rda_handle *H, int n, const int32_t *kind, const int32_t 
 extern "C" int rda_last_nonconvex(rda_handle *H)
 {
     if (!H) return RDA_ERR_ARG;
-    return (int)*(const long long *)(H->h_out + res_nonconvex(H->d.c.T));
+    return (int)*(const long long *)(H->res.blk.h + res_nonconvex(H->d.c.T));
 }
 
 extern "C" int rda_upload_scene(rda_handle *H, int n, const int32_t *kind, const int32_t *nvert, const double *geom,
@@ -1972,9 +1997,9 @@ extern "C" int rda_debug_scene_geom(rda_handle *H, double *geom, int32_t *n)
 {
     if (!H || !geom || !n) return RDA_ERR_ARG;
     HIPCHK(hipStreamSynchronize(H->stream));
-    if (H->scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
-    *n = H->sc_n > 0 ? H->sc_n : 0;
-    if (*n > 0) HIPCHK(hipMemcpy(geom, H->sc_args.geom, (size_t)*n * H->d.c.E * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (H->tick.scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
+    *n = H->sc.n > 0 ? H->sc.n : 0;
+    if (*n > 0) HIPCHK(hipMemcpy(geom, H->sc.args.geom, (size_t)*n * H->d.c.E * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
 
@@ -1983,6 +2008,14 @@ static hipEvent_t next_event(rda_handle *H, int which)
     if (H->ev_used[which] == H->ev[which].size()) { hbuf::Event e; (void)hipEventCreate(e.out()); H->ev[which].push_back(std::move(e)); }
     return H->ev[which][H->ev_used[which]++];
 }
+// the event pair around a timed launch (rda_timing_*): one recorded where the guard is made, one where it goes; nothing with the timing off
+struct TimedLaunch {
+    rda_handle *H; int which; hipStream_t st;
+    TimedLaunch(rda_handle *h, int w, hipStream_t s) : H(h->timing ? h : nullptr), which(w), st(s) { if (H) (void)hipEventRecord(next_event(H, which), st); }
+    ~TimedLaunch() { if (H) (void)hipEventRecord(next_event(H, which), st); }
+    TimedLaunch(const TimedLaunch &) = delete;          // (a copy would record a third event)
+    TimedLaunch &operator=(const TimedLaunch &) = delete;
+};
 
 // K1 launch of ADMM iteration `it`.  Packed rows when the shape allows: a small grid is ONE launch that also forms the block
 // partials; a dense grid is the common-path kernel + the work-list kernel, with k_lmz_finalize (partials) behind them.  One sub-problem per wave (big
@@ -2006,8 +2039,8 @@ static LmzPlan lammuz_plan(const rda_handle *H, const Dev &d)
         // (moving obstacles) lose the remembered support of more rows per launch, so the work list of the split form is longer and the
         // single launch stays ahead up to a larger grid: measured cross-over ~280 CUs for static scenes (N = 300, T = 20: 35.7 vs 38.7 us),
         // ~560 for moving ones (T = 30: N = 200 40.9 vs 47.1 us for the single launch, N = 300 52.2 vs 50.1, N = 400 60.7 vs 51.1).
-        if (cus <= (d.nt > 1 ? H->dense_from * 7 / 4 : H->dense_from)) return { LMZ_ROWS, nb, 0 };
-        if (!H->lmz_split) return { LMZ_ROWS_DENSE, nb, 0 };
+        if (cus <= (d.nt > 1 ? H->opts.lmz_dense_from * 7 / 4 : H->opts.lmz_dense_from)) return { LMZ_ROWS, nb, 0 };
+        if (!H->opts.lmz_split) return { LMZ_ROWS_DENSE, nb, 0 };
         int ne = units / 32; if (ne < 64) ne = 64; if (ne > 2048) ne = 2048;
         return { LMZ_ROWS_SPLIT, nb, ne };
     }
@@ -2039,27 +2072,26 @@ static void launch_lammuz(rda_handle *H, const Dev &d, int it, const Fin &fin)
     hipLaunchKernelGGL(k_lmz_finalize, dim3((d.c.T * d.J + FPB - 1) / FPB), dim3(256), 0, H->stream, d, it, fin);      // block partials and the tail of the forms that do not make them
 }
 
-// queue the whole ADMM loop of one MPC step (rda_solver.py:588-596) - no host synchronisation
-// The ADMM loop of one MPC step in two parts.  The HEAD (the first su-problem, which also resets the step's control block) reads the nominal trajectory and the
-// condensed terms of the PREVIOUS step (quirk Q4) but nothing of the staged obstacles, so a caller may stage this tick's
-// obstacles on the stream between head and tail while the first su-problem is being solved (rda_tracked_begin/_finish).
+// The ADMM loop of one MPC step (rda_solver.py:588-596) is queued without host synchronisation, in two parts.  The HEAD (the first su-problem,
+// which also resets the step's control block) reads the nominal trajectory and the condensed terms of the PREVIOUS step (quirk Q4) but nothing of
+// the staged obstacles, so a caller may stage this tick's obstacles on the stream between head and tail while the first su-problem is being
+// solved (rda_tracked_begin/_finish).  launch_su: one su-problem, ADMM iteration `it`.
 static void launch_su(rda_handle *H, const Dev &d, int it, const double *in_s, const double *in_u, const Fin &fin = Fin{})
 {
     const int T = d.c.T;
-    if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
+    TimedLaunch timed(H, 1, H->stream);
     RDA_SU_DISPATCH(T, hipLaunchKernelGGL(k_su<TT>, dim3(1), dim3(su::NT), H->su_lds, H->stream, d, it, in_s, in_u, fin));
-    if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
 }
-// Hand-over of a step's result slot to the host block h_out.  Zero-copy form: the launch that ends the step (the su launch that
+// Hand-over of a step's result slot to the pinned result block res.blk.h.  Zero-copy form: the launch that ends the step (the su launch that
 // detects the early stop, else k_finish) writes the block itself and the host polls the sequence word behind it.  Everything the
 // step queued before that launch has completed by then; what is still queued behind it are launches that return at once.
 // After 20 ms without the word - or with the timing events on, or RDA_ZERO_COPY=0 - the stream is synchronised the ordinary
 // way, which also surfaces a device fault.
 static Fin make_fin(rda_handle *H, double *out_u, double *out_s, rda_info *info)
 {
-    const bool zc = H->zero_copy && !H->timing && out_u == H->d_out_u;
-    if (zc) H->res_seq += 1;
-    return Fin{ out_u, out_s, info, zc ? H->h_out : nullptr, H->res_seq, out_u == H->d_out_u ? 1 : 0 };
+    const bool zc = H->opts.zero_copy && !H->timing && out_u == H->res.out_u();
+    if (zc) H->res.seq += 1;
+    return Fin{ out_u, out_s, info, zc ? H->res.blk.h : nullptr, H->res.seq, out_u == H->res.out_u() ? 1 : 0 };
 }
 static int launch_finish(rda_handle *H, const Dev &d, const Fin &fin)
 {
@@ -2088,18 +2120,18 @@ static bool poll_word(volatile unsigned long long *w, int shift, unsigned long l
 static int fetch_result(rda_handle *H)
 {
     const size_t T = H->d.c.T;
-    if (H->zero_copy && !H->timing) {
-        volatile unsigned long long *flag = (volatile unsigned long long *)(H->h_out + res_seq(T));
-        if (poll_word(flag, 0, H->res_seq, 20)) return RDA_OK;
+    if (H->opts.zero_copy && !H->timing) {
+        volatile unsigned long long *flag = (volatile unsigned long long *)(H->res.blk.h + res_seq(T));
+        if (poll_word(flag, 0, H->res.seq, 20)) return RDA_OK;
         // 20 ms without the word (a healthy step takes a fraction of a millisecond): synchronise the ordinary way.  A device fault -
         // in this step, or in the launches that were still queued behind the hand-over of the PREVIOUS step (the zero-copy hand-over
         // returns before they have drained) - never publishes the word and surfaces here as the stream's error.
         HIPCHK(hipStreamSynchronize(H->stream));
-        if (*flag == H->res_seq) return RDA_OK;
+        if (*flag == H->res.seq) return RDA_OK;
         return RDA_ERR_HIP;
     }
     // D2H form: the result block without the sequence word behind it (that word belongs to the zero-copy protocol)
-    HIPCHK(hipMemcpyAsync(H->h_out, H->d_out_u, res_copied_doubles(T) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
+    HIPCHK(hipMemcpyAsync(H->res.blk.h, H->res.out_u(), res_copied_doubles(T) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
     HIPCHK(hipStreamSynchronize(H->stream));
     return RDA_OK;
 }
@@ -2110,15 +2142,22 @@ static void result_out(const double *blk, const rda_info *blk_info, size_t T, do
     if (out_s) memcpy(out_s, blk + res_s(T), traj_s(T) * sizeof(double));
     if (info) *info = *blk_info;
 }
+struct StepViews { double *s, *u, *ref, *speed; };            // the four parts of the step block on the device
+static inline StepViews step_views(const rda_handle *H)
+{
+    const size_t T = H->d.c.T;
+    double *const b = H->step.d;
+    return { b, b + step_u(T), b + step_ref(T), b + step_speed(T) };
+}
 // fills the pinned step block and queues its copy to the device
 static int step_block_upload(rda_handle *H, const double *nom_s, const double *nom_u, const double *ref_s, double ref_speed)
 {
     const size_t T = H->d.c.T;
-    memcpy(H->h_step, nom_s, traj_s(T) * sizeof(double));
-    memcpy(H->h_step + step_u(T), nom_u, traj_u(T) * sizeof(double));
-    memcpy(H->h_step + step_ref(T), ref_s, traj_s(T) * sizeof(double));
-    H->h_step[step_speed(T)] = ref_speed;
-    HIPCHK(hipMemcpyAsync(H->d_step, H->h_step, step_doubles(T) * sizeof(double), hipMemcpyHostToDevice, H->stream));
+    memcpy(H->step.h, nom_s, traj_s(T) * sizeof(double));
+    memcpy(H->step.h + step_u(T), nom_u, traj_u(T) * sizeof(double));
+    memcpy(H->step.h + step_ref(T), ref_s, traj_s(T) * sizeof(double));
+    H->step.h[step_speed(T)] = ref_speed;
+    HIPCHK(H->step.push(H->stream));
     return RDA_OK;
 }
 static int enqueue_admm_head(rda_handle *H, const double *in_s, const double *in_u, const double *ref, const double *speed)
@@ -2138,28 +2177,25 @@ static int enqueue_admm_tail(rda_handle *H, const double *in_s, const double *in
     const Fin fin = make_fin(H, out_u, out_s, info);  // the su launch that detects the early stop hands the result over itself
     for (int it = 0; it < d.c.iter_num; ++it) {
         if (it > 0) {
-            Fin f = H->early_finish ? fin : Fin{};
-            if (H->comm) { f.verdict = H->h_verdict; f.vseq = ++H->vseq; }
+            Fin f = H->opts.early_finish ? fin : Fin{};
+            if (H->shard.comm) { f.verdict = H->shard.verdict; f.vseq = ++H->shard.vseq; }
             launch_su(H, d, it, in_s, in_u, f);
         }
-        if (it > 0 && H->comm) {
+        if (it > 0 && H->shard.comm) {
             // The early stop (rda_solver.py:594) is a device flag and kernels queued behind it return at once - a collective cannot, so
             // with a communicator no all-gather may be queued for an iteration that does not run.  The su launch publishes its verdict
             // in pinned host memory as soon as it has reduced the residuals (before its solve; every rank takes the same verdict: the
             // su-problems are bitwise identical); the host polls that word - no copy, no stream synchronisation - and goes on queueing
             // (or stops) while the su-problem is being solved.
-            volatile unsigned long long *vw = H->h_verdict;
-            if (!poll_word(vw, 1, H->vseq, 50)) { HIPCHK(hipStreamSynchronize(H->stream)); if ((*vw >> 1) != H->vseq) return RDA_ERR_HIP; }
+            volatile unsigned long long *vw = H->shard.verdict;
+            if (!poll_word(vw, 1, H->shard.vseq, 50)) { HIPCHK(hipStreamSynchronize(H->stream)); if ((*vw >> 1) != H->shard.vseq) return RDA_ERR_HIP; }
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             if (*vw & 1ull) break;
         }
-        if (H->timing) (void)hipEventRecord(next_event(H, 0), H->stream);
-        launch_lammuz(H, d, it, H->early_finish ? fin : Fin{});
-        if (H->timing) (void)hipEventRecord(next_event(H, 0), H->stream);
-        if (H->comm) {      // one exchange per ADMM iteration: every rank's chunk to every rank (in place)
-            if (H->timing) (void)hipEventRecord(next_event(H, 2), H->stream);
-            int nrc = H->p_allgather(d.coef + (size_t)d.rank * d.chunk, d.coef, d.chunk, /*ncclDouble*/ 8, H->comm, H->stream);
-            if (H->timing) (void)hipEventRecord(next_event(H, 2), H->stream);
+        { TimedLaunch timed(H, 0, H->stream); launch_lammuz(H, d, it, H->opts.early_finish ? fin : Fin{}); }
+        if (H->shard.comm) {  // one exchange per ADMM iteration: every rank's chunk to every rank (in place)
+            int nrc;
+            { TimedLaunch timed(H, 2, H->stream); nrc = H->shard.allgather(d.coef + (size_t)d.rank * d.chunk, d.coef, d.chunk, /*ncclDouble*/ 8, H->shard.comm, H->stream); }
             if (nrc != 0) { fprintf(stderr, "librda_hip: ncclAllGather failed (%d)\n", nrc); return RDA_ERR_HIP; }
         }
     }
@@ -2180,17 +2216,18 @@ template <typename Stage>
 static int step_common(rda_handle *H, const double *nom_s, const double *nom_u, const double *ref_s, double ref_speed,
                        double *out_u, double *out_s, rda_info *info, Stage stage)
 {
-    if (H->pending) return RDA_ERR_ARG;
+    if (H->tick.pending) return RDA_ERR_ARG;
     int rc = stage();
     if (rc != RDA_OK) { (void)hipStreamSynchronize(H->stream); return rc; }
     const size_t T = H->d.c.T;
     rc = step_block_upload(H, nom_s, nom_u, ref_s, ref_speed);
     if (rc != RDA_OK) return rc;
-    rc = enqueue_admm(H, H->d_step, H->d_step + step_u(T), H->d_step + step_ref(T), H->d_step + step_speed(T), H->d_out_u, H->d_out_s, H->d_info);
+    const StepViews v = step_views(H);
+    rc = enqueue_admm(H, v.s, v.u, v.ref, v.speed, H->res.out_u(), H->res.out_s(), H->res.info());
     if (rc != RDA_OK) return rc;
     rc = fetch_result(H);
     if (rc != RDA_OK) return rc;
-    result_out(H->h_out, H->h_info, T, out_u, out_s, info);
+    result_out(H->res.blk.h, H->res.h_info(), T, out_u, out_s, info);
     return RDA_OK;
 }
 
@@ -2282,51 +2319,51 @@ extern "C" int rda_upload_path(rda_handle *H, int L, const double *path)
 {
     if (!H || L < 1 || !path) return RDA_ERR_ARG;
     HIPCHK(hipStreamSynchronize(H->stream));
-    hbuf::Group g;                                      // a longer path goes to a new buffer that replaces the old one once it holds the path
-    double *dst = H->d_path;
-    const bool grow = L > H->path_len || !H->d_path;
-    if (grow && g.dev(&dst, (size_t)3 * L)) return RDA_ERR_HIP;
-    HIPCHK(hipMemcpy(dst, path, (size_t)3 * L * sizeof(double), hipMemcpyHostToDevice));
-    if (grow) { H->path = std::move(g); H->d_path = dst; }
-    H->path_len = L;
+    PathSet t;                                          // a longer path goes to a new buffer that replaces the old one once it holds the path
+    const bool grow = L > H->path.len || !H->path.d;
+    if (grow && t.g.dev(&t.d, (size_t)3 * L)) return RDA_ERR_HIP;
+    HIPCHK(hipMemcpy(grow ? t.d : H->path.d, path, (size_t)3 * L * sizeof(double), hipMemcpyHostToDevice));
+    if (grow) H->path = std::move(t);
+    H->path.len = L;
     return RDA_OK;
 }
 
 extern "C" int rda_tracked_begin(rda_handle *H, const double *state, double ref_speed, int cur_index, double threshold, int ind_range,
                                  const double *nom_u)
 {
-    if (!H || !state || H->pending) return RDA_ERR_ARG;
-    if (!H->d_path || cur_index < 0 || cur_index >= H->path_len || ind_range < 1) return RDA_ERR_ARG;
+    if (!H || !state || H->tick.pending) return RDA_ERR_ARG;
+    if (!H->path.d || cur_index < 0 || cur_index >= H->path.len || ind_range < 1) return RDA_ERR_ARG;
     const size_t T = H->d.c.T;
+    const StepViews v = step_views(H);
     const double *in_u = H->d.u;                       // the controls of the last solve are still resident
     if (nom_u) {
-        memcpy(H->h_step + step_u(T), nom_u, traj_u(T) * sizeof(double));
-        HIPCHK(hipMemcpyAsync(H->d_step + step_u(T), H->h_step + step_u(T), traj_u(T) * sizeof(double), hipMemcpyHostToDevice, H->stream));
-        in_u = H->d_step + step_u(T);
+        memcpy(H->step.h + step_u(T), nom_u, traj_u(T) * sizeof(double));
+        HIPCHK(hipMemcpyAsync(v.u, H->step.h + step_u(T), traj_u(T) * sizeof(double), hipMemcpyHostToDevice, H->stream));
+        in_u = v.u;
     }
     track::In in; in.sx = state[0]; in.sy = state[1]; in.sth = state[2]; in.speed = ref_speed; in.threshold = threshold;
     in.cur_index = cur_index; in.ind_range = ind_range;
     // everything queued before this tick: an in-tick scene staging (rda_upload_scene_async) starts behind this event, beside the first
     // su-problem.  Recorded only for callers that stage inside their ticks (learned from the previous tick); a first in-tick staging
     // without it orders itself behind the head of the tick instead.
-    H->tick_has_event = 0;
-    if (H->tick_stages) { HIPCHK(hipEventRecord(H->ev_tick, H->stream)); H->tick_has_event = 1; }
-    H->tick_stages = 0;
-    if (H->fuse_track) {
+    H->tick.has_event = 0;
+    if (H->tick.stages) { HIPCHK(hipEventRecord(H->ev_tick, H->stream)); H->tick.has_event = 1; }
+    H->tick.stages = 0;
+    if (H->opts.fuse_track) {
         Dev d = H->d;
-        d.ref = H->d_step + step_ref(T); d.ref_speed = H->d_step + step_speed(T);
-        if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
+        d.ref = v.ref; d.ref_speed = v.speed;
         H->trk_seq += 1;
-        RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su_tracked<TT>, dim3(2), dim3(su::NT), H->su_trk_lds, H->stream, d, in, H->d_path, H->path_len,
-                                                   in_u, H->d_step, H->d_trk, H->trk_seq));
-        if (H->timing) (void)hipEventRecord(next_event(H, 1), H->stream);
+        {
+            TimedLaunch timed(H, 1, H->stream);
+            RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su_tracked<TT>, dim3(2), dim3(su::NT), H->su_trk_lds, H->stream, d, in, H->path.d, H->path.len,
+                                                       in_u, v.s, H->res.track(), H->trk_seq));
+        }
         HIPCHK(hipGetLastError());
     } else {
-        hipLaunchKernelGGL(k_track, dim3(1), dim3(64), 0, H->stream, H->d, in, H->d_path, H->path_len, in_u, H->d_step, H->d_trk);
-        int rc = enqueue_admm_head(H, H->d_step, in_u, H->d_step + step_ref(T), H->d_step + step_speed(T));
-        if (rc != RDA_OK) return rc;
+        hipLaunchKernelGGL(k_track, dim3(1), dim3(64), 0, H->stream, H->d, in, H->path.d, H->path.len, in_u, v.s, H->res.track());
+        if (int rc = enqueue_admm_head(H, v.s, in_u, v.ref, v.speed)) return rc;
     }
-    H->pending = 1; H->pending_in_u = in_u;
+    H->tick.pending = 1; H->tick.in_u = in_u;
     return RDA_OK;
 }
 
@@ -2335,19 +2372,19 @@ template <typename Stage> static int scene_async(rda_handle *H, bool live, Stage
 {
     // one pinned staging block per handle: a second upload before the caller's synchronising call (rda_tracked_finish,
     // rda_sync, a fleet step) has to wait for the first one to have been copied
-    if (H->pending_scene) { HIPCHK(hipStreamSynchronize(H->stream)); HIPCHK(hipStreamSynchronize(H->stream2)); H->pending_scene = 0; H->scene_on_s2 = 0; }
-    if (!H->pending) {
+    if (H->tick.pending_scene) { HIPCHK(hipStreamSynchronize(H->stream)); HIPCHK(hipStreamSynchronize(H->stream2)); H->tick.pending_scene = 0; H->tick.scene_on_s2 = 0; }
+    if (!H->tick.pending) {
         int rc = stage(H->stream);
-        if (rc == RDA_OK && live) H->pending_scene = 1;
+        if (rc == RDA_OK && live) H->tick.pending_scene = 1;
         return rc;
     }
     // inside a tick: the copy and the conversion kernels touch only the obstacle slots, which nothing of the head (k_track,
     // the first su-problem) reads - they run on the second stream BESIDE the first su-problem; rda_tracked_finish joins
-    if (!H->tick_has_event) { HIPCHK(hipEventRecord(H->ev_tick, H->stream)); H->tick_has_event = 1; }
-    H->tick_stages = 1;
+    if (!H->tick.has_event) { HIPCHK(hipEventRecord(H->ev_tick, H->stream)); H->tick.has_event = 1; }
+    H->tick.stages = 1;
     HIPCHK(hipStreamWaitEvent(H->stream2, H->ev_tick, 0));
     int rc = stage(H->stream2);
-    if (rc == RDA_OK && live) { HIPCHK(hipEventRecord(H->ev_scene, H->stream2)); H->pending_scene = 1; H->scene_on_s2 = 1; }
+    if (rc == RDA_OK && live) { HIPCHK(hipEventRecord(H->ev_scene, H->stream2)); H->tick.pending_scene = 1; H->tick.scene_on_s2 = 1; }
     return rc;
 }
 
@@ -2366,12 +2403,12 @@ extern "C" int rda_upload_scene_async(rda_handle *H, int n, const int32_t *kind,
 extern "C" int rda_scene_resort(rda_handle *H, const double *robot_xy)
 {
     if (!H || !robot_xy) return RDA_ERR_ARG;
-    if (H->sc_n <= 0 || H->d.obstacle_num == 0) return RDA_ERR_ARG;              // no resident raw scene
+    if (H->sc.n <= 0 || H->d.obstacle_num == 0) return RDA_ERR_ARG;              // no resident raw scene
     return scene_async(H, true, [&](hipStream_t st) -> int {
-        scene::Args a = H->sc_args;
+        scene::Args a = H->sc.args;
         a.order = 1; a.robot_val = 1; a.rx = robot_xy[0]; a.ry = robot_xy[1];
         HIPCHK(hipMemsetAsync(a.nonconvex, 0, sizeof(int), st));
-        scene_kernels(H, a, st);
+        scene_kernels(H, a, st, false);
         HIPCHK(hipGetLastError());
         return (int)RDA_OK;
     });
@@ -2380,48 +2417,35 @@ extern "C" int rda_scene_resort(rda_handle *H, const double *robot_xy)
 // ---- lidar front end on the device (lidar_device.h) ------------------------------------------------------------------------------
 static int lidar_reserve(rda_handle *H)
 {
-    if (H->d_li_boxes) return RDA_OK;
-    hbuf::Group g;
-    double *db = nullptr, *hr = nullptr, *hb = nullptr; int *hc = nullptr, *hl = nullptr;
-    int rc = 0;
-    rc |= g.dev(&db, (size_t)lidar::MAXB * 8);
-    rc |= g.pin(&hr, (size_t)lidar::MAXB); rc |= g.pin(&hc, 2); rc |= g.pin(&hl, (size_t)lidar::MAXB); rc |= g.pin(&hb, (size_t)lidar::MAXB * 8);
-    if (rc) return RDA_ERR_HIP;
+    if (H->li.have()) return RDA_OK;
+    LidarSet t;
+    if (t.alloc()) return RDA_ERR_HIP;
     HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
-    H->lidar = std::move(g);
-    H->d_li_boxes = db; H->h_li_ranges = hr; H->h_li_count = hc; H->h_li_labels = hl; H->h_li_boxes = hb;
+    H->li = std::move(t);
     return RDA_OK;
-}
-static void lidar_release(rda_handle *H)
-{
-    H->lidar = hbuf::Group();
-    H->d_li_boxes = nullptr; H->h_li_ranges = nullptr; H->h_li_count = nullptr; H->h_li_labels = nullptr; H->h_li_boxes = nullptr;
 }
 
 // One scan through lidar::k_scan, and the wait for it.  The kernel runs on the SECOND stream and touches nothing but the lidar buffers, so inside a
-// tick the wait is for this kernel alone, not for the first su-problem.  The boxes stay in d_li_boxes; to_host: labels and boxes also in h_li_*.
+// tick the wait is for this kernel alone, not for the first su-problem.  The boxes stay in li.d_boxes; to_host: labels and boxes also in li.h_labels, li.h_boxes.
 static int scan_run(rda_handle *H, int n_beams, const double *ranges, double angle_min, double angle_max, double range_max,
                     const double *state, double eps, int min_samples, bool to_host, int *n_boxes)
 {
     if (!H || n_beams < 0 || !ranges || !state || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
     if (n_beams > lidar::MAXB || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;
     // a staging that is still queued may be reading the boxes of the previous scan
-    if (H->pending_scene) { HIPCHK(hipStreamSynchronize(H->stream)); HIPCHK(hipStreamSynchronize(H->stream2)); }
-    int rc = lidar_reserve(H);
-    if (rc != RDA_OK) return rc;
-    memcpy(H->h_li_ranges, ranges, (size_t)n_beams * sizeof(double));
-    H->h_li_count[0] = 0; H->h_li_count[1] = 0;
+    if (H->tick.pending_scene) { HIPCHK(hipStreamSynchronize(H->stream)); HIPCHK(hipStreamSynchronize(H->stream2)); }
+    if (int rc = lidar_reserve(H)) return rc;
+    memcpy(H->li.h_ranges, ranges, (size_t)n_beams * sizeof(double));
+    H->li.h_count[0] = 0; H->li.h_count[1] = 0;
     lidar::Args a;
-    a.n_beams = n_beams; a.ranges = H->h_li_ranges; a.angle_min = angle_min; a.angle_max = angle_max; a.range_max = range_max;
+    a.n_beams = n_beams; a.ranges = H->li.h_ranges; a.angle_min = angle_min; a.angle_max = angle_max; a.range_max = range_max;
     a.sx = state[0]; a.sy = state[1]; a.sth = state[2]; a.eps = eps; a.min_samples = min_samples;
-    a.boxes = H->d_li_boxes; a.count = H->h_li_count;
-    a.labels_h = to_host ? H->h_li_labels : nullptr; a.boxes_h = to_host ? H->h_li_boxes : nullptr;
-    if (H->timing) (void)hipEventRecord(next_event(H, 3), H->stream2);
-    hipLaunchKernelGGL(lidar::k_scan, dim3(1), dim3(lidar::NT), lidar::LDS_BYTES, H->stream2, a);
-    if (H->timing) (void)hipEventRecord(next_event(H, 3), H->stream2);
+    a.boxes = H->li.d_boxes; a.count = H->li.h_count;
+    a.labels_h = to_host ? H->li.h_labels : nullptr; a.boxes_h = to_host ? H->li.h_boxes : nullptr;
+    { TimedLaunch timed(H, 3, H->stream2); hipLaunchKernelGGL(lidar::k_scan, dim3(1), dim3(lidar::NT), lidar::LDS_BYTES, H->stream2, a); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(H->stream2));
-    *n_boxes = H->h_li_count[0];
+    *n_boxes = H->li.h_count[0];
     return RDA_OK;
 }
 
@@ -2430,27 +2454,11 @@ extern "C" int rda_scan_boxes(rda_handle *H, int n_beams, const double *ranges, 
 {
     if (!n_boxes || cap < 0 || (cap > 0 && !boxes)) return RDA_ERR_ARG;
     int n = 0;
-    int rc = scan_run(H, n_beams, ranges, angle_min, angle_max, range_max, state, eps, min_samples, true, &n);
-    if (rc != RDA_OK) return rc;
+    if (int rc = scan_run(H, n_beams, ranges, angle_min, angle_max, range_max, state, eps, min_samples, true, &n)) return rc;
     *n_boxes = n;
-    if (boxes) memcpy(boxes, H->h_li_boxes, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
-    if (labels) memcpy(labels, H->h_li_labels, (size_t)n_beams * sizeof(int32_t));
+    if (boxes) memcpy(boxes, H->li.h_boxes, (size_t)(n < cap ? n : cap) * 8 * sizeof(double));
+    if (labels) memcpy(labels, H->li.h_labels, (size_t)n_beams * sizeof(int32_t));
     return RDA_OK;
-}
-
-// the conversion kernels' arguments for n boxes laid out as a raw scene in the handle's (reserved) scene block: 4-vertex polygons without velocity
-static scene::Args scan_scene_args(const rda_handle *H, int n, int order)
-{
-    const Dev &d = H->d;
-    const int E = d.c.E, T = d.c.T, N = d.c.N;
-    const size_t o_vel = (size_t)n * E * 2, o_rob = o_vel + (size_t)n * 2, o_bad = o_rob + 2, o_int = o_bad + 1;   // in doubles (scene_stage)
-    double *db = H->d_sc_blk;
-    scene::Args a;
-    a.n = n; a.N = N; a.E = E; a.T = T; a.nt = 1; a.order = order; a.dt = d.c.dt;
-    a.kind = (int *)(db + o_int); a.nvert = (int *)(db + o_int) + n; a.geom = db; a.vel = db + o_vel; a.robot = db + o_rob;
-    a.key = H->d_sc_key; a.sel = H->d_sc_sel; a.A = d.A; a.b = d.b; a.cone = d.cone; a.nonconvex = (int *)(db + o_bad);
-    a.rx = 0; a.ry = 0; a.robot_val = 0;
-    return a;
 }
 
 // the boxes of the last scan as the handle's raw scene (what scene_stage does with a host scene, from device memory) and the conversion kernels
@@ -2458,14 +2466,11 @@ static int scan_stage(rda_handle *H, int n, const double *state, int order, hipS
 {
     Dev &d = H->d;
     if (n <= 0) { d.obstacle_num = 0; return RDA_OK; }           // nothing written: stale A, b stay (rda_solver.py:485)
-    int rc = scene_reserve(H, n);
-    if (rc != RDA_OK) return rc;
-    const scene::Args a = scan_scene_args(H, n, order);
-    hipLaunchKernelGGL(lidar::k_scene_fill, dim3((n + 255) / 256), dim3(256), 0, st, (const double *)H->d_li_boxes, n, a.E, const_cast<double *>(a.geom),
+    if (int rc = scene_reserve(H, n)) return rc;
+    const scene::Args a = scene_args(H, n, 1, order);                  // (boxes: 4-vertex polygons without velocity)
+    hipLaunchKernelGGL(lidar::k_scene_fill, dim3((n + 255) / 256), dim3(256), 0, st, (const double *)H->li.d_boxes, n, a.E, const_cast<double *>(a.geom),
                        const_cast<double *>(a.vel), const_cast<double *>(a.robot), a.nonconvex, const_cast<int *>(a.kind), const_cast<int *>(a.nvert), state[0], state[1]);
-    d.sc_bad = a.nonconvex;
-    H->sc_args = a; H->sc_n = n;
-    scene_kernels(H, a, st);
+    scene_kernels(H, a, st, true);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
@@ -2474,12 +2479,12 @@ extern "C" int rda_upload_scan(rda_handle *H, int n_beams, const double *ranges,
                                const double *state, double eps, int min_samples, int order, int32_t *n_boxes)
 {
     if (!H) return RDA_ERR_ARG;
-    const bool fresh = !H->d_li_boxes;
+    const bool fresh = !H->li.have();
     int n = 0;
     int rc = scan_run(H, n_beams, ranges, angle_min, angle_max, range_max, state, eps, min_samples, false, &n);
     if (rc != RDA_OK) return rc;
     rc = scene_async(H, n > 0, [&](hipStream_t st) -> int { return scan_stage(H, n, state, order, st); });
-    if (rc != RDA_OK) { if (fresh) lidar_release(H); return rc; }       // a failed call leaves what the handle holds as it was
+    if (rc != RDA_OK) { if (fresh) H->li = {}; return rc; }       // a failed call leaves what the handle holds as it was
     if (n_boxes) *n_boxes = n;
     return RDA_OK;
 }
@@ -2487,24 +2492,25 @@ extern "C" int rda_upload_scan(rda_handle *H, int n_beams, const double *ranges,
 extern "C" int rda_tracked_finish(rda_handle *H, double *out_u, double *out_s, rda_info *info,
                                   double *nom_s_out, double *ref_out, int32_t *min_index, double *end_heading)
 {
-    if (!H || !H->pending) return RDA_ERR_ARG;
+    if (!H || !H->tick.pending) return RDA_ERR_ARG;
     const size_t T = H->d.c.T;
-    const double *in_u = H->pending_in_u;
-    if (H->scene_on_s2) HIPCHK(hipStreamWaitEvent(H->stream, H->ev_scene, 0));
-    H->pending = 0; H->pending_scene = 0; H->scene_on_s2 = 0;
-    int rc = enqueue_admm_tail(H, H->d_step, in_u, H->d_step + step_ref(T), H->d_step + step_speed(T), H->d_out_u, H->d_out_s, H->d_info);
+    const double *in_u = H->tick.in_u;
+    if (H->tick.scene_on_s2) HIPCHK(hipStreamWaitEvent(H->stream, H->ev_scene, 0));
+    H->tick.pending = 0; H->tick.pending_scene = 0; H->tick.scene_on_s2 = 0;
+    const StepViews v = step_views(H);
+    int rc = enqueue_admm_tail(H, v.s, in_u, v.ref, v.speed, H->res.out_u(), H->res.out_s(), H->res.info());
     if (rc != RDA_OK) { (void)hipStreamSynchronize(H->stream); return rc; }
     if (nom_s_out || ref_out) {
-        HIPCHK(hipMemcpyAsync(H->h_step, H->d_step, step_speed(T) * sizeof(double), hipMemcpyDeviceToHost, H->stream));
+        HIPCHK(H->step.pull(H->stream, step_speed(T)));
         HIPCHK(hipStreamSynchronize(H->stream));
     }
     rc = fetch_result(H);
     if (rc != RDA_OK) return rc;
-    result_out(H->h_out, H->h_info, T, out_u, out_s, info);
-    if (nom_s_out) memcpy(nom_s_out, H->h_step, traj_s(T) * sizeof(double));
-    if (ref_out) memcpy(ref_out, H->h_step + step_ref(T), traj_s(T) * sizeof(double));
-    if (min_index) *min_index = H->h_trk->min_index;
-    if (end_heading) *end_heading = H->h_trk->end_heading;
+    result_out(H->res.blk.h, H->res.h_info(), T, out_u, out_s, info);
+    if (nom_s_out) memcpy(nom_s_out, H->step.h, traj_s(T) * sizeof(double));
+    if (ref_out) memcpy(ref_out, H->step.h + step_ref(T), traj_s(T) * sizeof(double));
+    if (min_index) *min_index = H->res.h_track()->min_index;
+    if (end_heading) *end_heading = H->res.h_track()->end_heading;
     return RDA_OK;
 }
 
@@ -2522,34 +2528,28 @@ extern "C" int rda_upload_trace(rda_handle *H, int K, const double *nom_s, const
 {
     if (!H || K < 1 || !nom_s || !nom_u || !ref_s || !ref_speed) return RDA_ERR_ARG;
     const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
-    hbuf::Group g;                                      // the new trace replaces the old one once it is complete: a failed upload keeps the old
-    double *s, *u, *ref, *speed, *out_u, *out_s; rda_info *info;
-    int rc = 0;
-    rc |= g.dev(&s, K * ns); rc |= g.dev(&u, K * nu); rc |= g.dev(&ref, K * ns); rc |= g.dev(&speed, (size_t)K);
-    rc |= g.dev(&out_u, K * nu); rc |= g.dev(&out_s, K * ns); rc |= g.dev(&info, (size_t)K);
-    if (rc) return RDA_ERR_HIP;
-    HIPCHK(hipMemcpy(s, nom_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(u, nom_u, K * nu * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ref, ref_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(speed, ref_speed, K * sizeof(double), hipMemcpyHostToDevice));
-    H->trace = std::move(g);
-    H->d_tr_s = s; H->d_tr_u = u; H->d_tr_ref = ref; H->d_tr_speed = speed; H->d_tr_out_u = out_u; H->d_tr_out_s = out_s; H->d_tr_info = info;
-    H->K = K;
+    TraceSet t;                                         // the new trace replaces the old one once it is complete: a failed upload keeps the old
+    if (t.alloc((size_t)K, ns, nu)) return RDA_ERR_HIP;
+    HIPCHK(hipMemcpy(t.s, nom_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.u, nom_u, K * nu * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.ref, ref_s, K * ns * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.speed, ref_speed, K * sizeof(double), hipMemcpyHostToDevice));
+    H->trace = std::move(t);
     return RDA_OK;
 }
 
 extern "C" int rda_enqueue_step(rda_handle *H, int k)
 {
-    if (!H || k < 0 || k >= H->K) return RDA_ERR_ARG;
+    if (!H || k < 0 || k >= H->trace.K) return RDA_ERR_ARG;
     const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
-    return enqueue_admm(H, H->d_tr_s + k * ns, H->d_tr_u + k * nu, H->d_tr_ref + k * ns, H->d_tr_speed + k,
-                        H->d_tr_out_u + k * nu, H->d_tr_out_s + k * ns, H->d_tr_info + k);
+    return enqueue_admm(H, H->trace.s + k * ns, H->trace.u + k * nu, H->trace.ref + k * ns, H->trace.speed + k,
+                        H->trace.out_u + k * nu, H->trace.out_s + k * ns, H->trace.info + k);
 }
 
 // steps k0 .. k1-1 of the uploaded trace, queued back to back (one host call instead of k1-k0)
 extern "C" int rda_enqueue_range(rda_handle *H, int k0, int k1)
 {
-    if (!H || k0 < 0 || k1 > H->K || k0 > k1) return RDA_ERR_ARG;
+    if (!H || k0 < 0 || k1 > H->trace.K || k0 > k1) return RDA_ERR_ARG;
     for (int k = k0; k < k1; ++k) { int rc = rda_enqueue_step(H, k); if (rc != RDA_OK) return rc; }
     return RDA_OK;
 }
@@ -2594,16 +2594,16 @@ extern "C" int rda_debug_lmz_stats(rda_handle *H, unsigned *out)
     return RDA_OK;
 }
 #endif
-extern "C" int rda_sync(rda_handle *H) { if (!H) return RDA_ERR_ARG; HIPCHK(hipStreamSynchronize(H->stream)); H->pending_scene = 0; return RDA_OK; }
+extern "C" int rda_sync(rda_handle *H) { if (!H) return RDA_ERR_ARG; HIPCHK(hipStreamSynchronize(H->stream)); H->tick.pending_scene = 0; return RDA_OK; }
 
 extern "C" int rda_fetch_result(rda_handle *H, int k, double *out_u, double *out_s, rda_info *info)
 {
-    if (!H || k < 0 || k >= H->K) return RDA_ERR_ARG;
+    if (!H || k < 0 || k >= H->trace.K) return RDA_ERR_ARG;
     const size_t ns = traj_s(H->d.c.T), nu = traj_u(H->d.c.T);
     HIPCHK(hipStreamSynchronize(H->stream));
-    if (out_u) HIPCHK(hipMemcpy(out_u, H->d_tr_out_u + k * nu, nu * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_s) HIPCHK(hipMemcpy(out_s, H->d_tr_out_s + k * ns, ns * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) HIPCHK(hipMemcpy(info, H->d_tr_info + k, sizeof(rda_info), hipMemcpyDeviceToHost));
+    if (out_u) HIPCHK(hipMemcpy(out_u, H->trace.out_u + k * nu, nu * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_s) HIPCHK(hipMemcpy(out_s, H->trace.out_s + k * ns, ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) HIPCHK(hipMemcpy(info, H->trace.info + k, sizeof(rda_info), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
 
@@ -2732,7 +2732,7 @@ extern "C" int rda_shard_config(rda_handle *H, int rank, int world)
 {
     if (!H || world < 1 || rank < 0 || rank >= world) return RDA_ERR_ARG;
     if (H->d.c.N % world != 0 && !H->d.c.accelerated) return RDA_ERR_UNSUPPORTED;    // padded shards rely on the hinge of the accelerated cost
-    if (world > 1 && H->follow) return RDA_ERR_UNSUPPORTED;                          // duals_follow moves rows between slots = between ranks
+    if (world > 1 && H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;               // duals_follow moves rows between slots = between ranks
     HIPCHK(hipStreamSynchronize(H->stream));
     Dev &d = H->d;
     const int Nloc = (d.c.N + world - 1) / world, first = rank * Nloc;
@@ -2757,11 +2757,11 @@ static void *rccl_sym(rda_handle *H, const char *name);
 extern "C" int rda_shard_comm_count(rda_handle *H)
 {
     if (!H) return RDA_ERR_ARG;
-    if (!H->comm) return 0;
+    if (!H->shard.comm) return 0;
     typedef int (*fn)(void *, int *);
     fn f = (fn)rccl_sym(H, "ncclCommCount");
     int n = 0;
-    if (!f || f(H->comm, &n) != 0) return RDA_ERR_HIP;
+    if (!f || f(H->shard.comm, &n) != 0) return RDA_ERR_HIP;
     return n;
 }
 extern "C" int rda_shard_chunk_doubles(rda_handle *H) { return H ? (int)H->d.chunk : RDA_ERR_ARG; }
@@ -2781,16 +2781,16 @@ extern "C" int rda_shard_set_chunks(rda_handle *H, const double *host_all)
 }
 static void *rccl_sym(rda_handle *H, const char *name)
 {
-    if (!H->nccl_lib) {
+    if (!H->shard.lib) {
         // The RCCL the process ALREADY has, if any: a host that imported torch brought its own librccl.so.1 (and HIP runtime) with it,
         // and a second copy next to it breaks - default-visibility symbols of the second resolve into the first (measured:
         // ncclCommInitRank of /opt/rocm's copy fails with ncclUnhandledCudaError once torch's is mapped).  RTLD_NOLOAD matches by SONAME.
-        H->nccl_lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-        if (!H->nccl_lib) H->nccl_lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-        if (!H->nccl_lib) H->nccl_lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-        if (!H->nccl_lib) H->nccl_lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
+        H->shard.lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
+        if (!H->shard.lib) H->shard.lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
+        if (!H->shard.lib) H->shard.lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
+        if (!H->shard.lib) H->shard.lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
     }
-    return H->nccl_lib ? dlsym(H->nccl_lib, name) : nullptr;
+    return H->shard.lib ? dlsym(H->shard.lib, name) : nullptr;
 }
 extern "C" int rda_shard_unique_id(rda_handle *H, void *out128)
 {
@@ -2807,15 +2807,15 @@ extern "C" int rda_shard_comm_init(rda_handle *H, const void *uid128)
     memcpy(&uid, uid128, 128);
     typedef int (*init_fn)(void **, int, uid_t, int);
     init_fn f = (init_fn)rccl_sym(H, "ncclCommInitRank");
-    H->p_allgather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t))rccl_sym(H, "ncclAllGather");
-    H->p_comm_destroy = (int (*)(void *))rccl_sym(H, "ncclCommDestroy");
-    if (!f || !H->p_allgather) return RDA_ERR_UNSUPPORTED;
+    H->shard.allgather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t))rccl_sym(H, "ncclAllGather");
+    H->shard.comm_destroy = (int (*)(void *))rccl_sym(H, "ncclCommDestroy");
+    if (!f || !H->shard.allgather) return RDA_ERR_UNSUPPORTED;
     hbuf::Group g;                                      // the verdict word (zero) exists before the communicator does
-    unsigned long long *verdict = H->h_verdict;
+    unsigned long long *verdict = H->shard.verdict;
     if (!verdict && g.pin(&verdict, 1)) return RDA_ERR_HIP;
-    int rc = f(&H->comm, H->d.P, uid, H->d.rank);
-    if (rc != 0) { fprintf(stderr, "librda_hip: ncclCommInitRank failed (%d)\n", rc); H->comm = nullptr; return RDA_ERR_HIP; }
-    if (!H->h_verdict) { H->verdict = std::move(g); H->h_verdict = verdict; }
+    int rc = f(&H->shard.comm, H->d.P, uid, H->d.rank);
+    if (rc != 0) { fprintf(stderr, "librda_hip: ncclCommInitRank failed (%d)\n", rc); H->shard.comm = nullptr; return RDA_ERR_HIP; }
+    if (!H->shard.verdict) { H->shard.g = std::move(g); H->shard.verdict = verdict; }
     return RDA_OK;
 }
 
@@ -2836,8 +2836,9 @@ extern "C" int rda_admm_su(rda_handle *H, int it, int *stopped)
     const size_t T = H->d.c.T;
     H->admm_it = it;
     Dev d = H->d;
-    d.ref = H->d_step + step_ref(T); d.ref_speed = H->d_step + step_speed(T);
-    RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su<TT>, dim3(1), dim3(su::NT), H->su_lds, H->stream, d, it, H->d_step, H->d_step + step_u(T), Fin{}));
+    const StepViews v = step_views(H);
+    d.ref = v.ref; d.ref_speed = v.speed;
+    RDA_SU_DISPATCH((int)T, hipLaunchKernelGGL(k_su<TT>, dim3(1), dim3(su::NT), H->su_lds, H->stream, d, it, v.s, v.u, Fin{}));
     HIPCHK(hipGetLastError());
     if (stopped) {
         Ctrl c;
@@ -2859,9 +2860,9 @@ extern "C" int rda_admm_finish(rda_handle *H, double *out_u, double *out_s, rda_
 {
     if (!H || !out_u || !out_s) return RDA_ERR_ARG;
     Dev d = H->d;
-    { int rc = launch_finish(H, d, make_fin(H, H->d_out_u, H->d_out_s, H->d_info)); if (rc != RDA_OK) return rc; }
+    { int rc = launch_finish(H, d, make_fin(H, H->res.out_u(), H->res.out_s(), H->res.info())); if (rc != RDA_OK) return rc; }
     { int rc = fetch_result(H); if (rc != RDA_OK) return rc; }
-    result_out(H->h_out, H->h_info, H->d.c.T, out_u, out_s, info);
+    result_out(H->res.blk.h, H->res.h_info(), H->d.c.T, out_u, out_s, info);
     return RDA_OK;
 }
 
@@ -3038,8 +3039,8 @@ template <typename T, typename Get> static hipError_t mirror_upload(const hbuf::
 }
 template <typename T> static auto records(const std::vector<T> &v) { return [&v](size_t i) -> const T & { return v[i]; }; }
 static auto member_devs(const rda_fleet *F) { return [F](size_t i) -> const Dev & { return F->egos[i]->d; }; }
-static auto member_paths(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->d_path; }; }
-static auto member_lens(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path_len; }; }
+static auto member_paths(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path.d; }; }
+static auto member_lens(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path.len; }; }
 
 // Member i's locations on the step path: its step block in `in` (in_u: nominal controls that live elsewhere, else null), its u | s block
 // under out_base, its info under info_base
@@ -3073,7 +3074,7 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
         const rda_cfg &a = egos[0]->d.c, &b = egos[i]->d.c;
         // one grid for all members: the problem SHAPE must agree (weights, bounds, kinematics and robots may differ)
         if (a.T != b.T || a.N != b.N || a.E != b.E || a.R != b.R || a.iter_num != b.iter_num) return RDA_ERR_UNSUPPORTED;
-        if (egos[i]->comm || egos[i]->d.P != 1) return RDA_ERR_UNSUPPORTED;        // egos are replicas, obstacle shards are not
+        if (egos[i]->shard.comm || egos[i]->d.P != 1) return RDA_ERR_UNSUPPORTED;  // egos are replicas, obstacle shards are not
         if (egos[i]->d.lmz_mode) return RDA_ERR_UNSUPPORTED;                       // the fused fleet launches run the enumeration kernels
     }
     std::unique_ptr<rda_fleet> owner(new rda_fleet());     // a failure on the way drops the fleet and with it what was built
@@ -3100,7 +3101,7 @@ static void fleet_refresh_flags(rda_fleet *F)
 {
     F->rows = 1;
     F->lmz_split = 1;
-    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->lmz_split) F->lmz_split = 0;
+    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->opts.lmz_split) F->lmz_split = 0;
     for (int i = 0; i < F->B; ++i) if (!F->egos[i]->d.rows || !F->egos[i]->d.obstacle_num) F->rows = 0;
 }
 
@@ -3173,7 +3174,7 @@ extern "C" int rda_fleet_step(rda_fleet *F, const double *nom_s, const double *n
     HIPCHK(F->info.pull(F->stream, B));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
-    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
+    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;  // their staged scenes have been consumed
     for (size_t i = 0; i < B; ++i) fleet_result_out(F, i, out_u, out_s, info);
     return RDA_OK;
 }
@@ -3216,14 +3217,14 @@ extern "C" int rda_fleet_upload_scenes(rda_fleet *F, const int32_t *counts, cons
 // rda_scene_resort for every member in ONE launch set (round 6): the members' resident raw scenes (rda_upload_scene*, static obstacles) re-ranked about
 // states[i * stride + 0..1] and their slots rebuilt on the fleet's stream; the next fleet step runs behind it.  Same device code per member as
 // rda_scene_resort: bit-identical slots.  Members with rda_opts::duals_follow, without a resident scene, or inside a tick: RDA_ERR_UNSUPPORTED / _ARG.
-static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc_args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from res.rob)
+static scene::Args fleet_resort_args(const rda_handle *H) { scene::Args a = H->sc.args; a.order = 1; a.robot_val = 0; a.rx = 0; a.ry = 0; return a; }      // (the position: from res.rob)
 // the members' scene arguments (uploaded when they changed) and their robots' positions -> res.sc, res.rob; nmax, wmax: what sizes the launches
 static int fleet_resort_positions(rda_fleet *F, const double *states, int stride, int &nmax, int &wmax)
 {
     const size_t B = F->B;
     const auto args = [F](size_t i) { return fleet_resort_args(F->egos[i]); };
     for (size_t i = 0; i < B; ++i) {
-        const scene::Args &a = F->egos[i]->sc_args;
+        const scene::Args &a = F->egos[i]->sc.args;
         nmax = a.n > nmax ? a.n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
     const bool changed = mirror_differs(F->res.sc, args);
@@ -3247,8 +3248,8 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
 {
     if (!F || !states || stride < 2) return RDA_ERR_ARG;
     for (rda_handle *H : F->egos) {
-        if (H->sc_n <= 0 || H->d.obstacle_num == 0 || H->pending) return RDA_ERR_ARG;
-        if (H->follow) return RDA_ERR_UNSUPPORTED;
+        if (H->sc.n <= 0 || H->d.obstacle_num == 0 || H->tick.pending) return RDA_ERR_ARG;
+        if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;
     }
     if (!F->res.have()) {                               // first use: the tables (zeroed) take their place once all of them exist
         FleetResort t;
@@ -3363,15 +3364,13 @@ static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const do
             continue;
         }
         scene_grow_commit(H, grow[i]);
-        const scene::Args a = scan_scene_args(H, n, order[i] ? 1 : 0);
+        const scene::Args a = scene_args(H, n, 1, order[i] ? 1 : 0);
         f.boxes = li.d_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
         f.geom = const_cast<double *>(a.geom); f.vel = const_cast<double *>(a.vel); f.robot = const_cast<double *>(a.robot);
         f.nonconvex = a.nonconvex; f.kind = const_cast<int *>(a.kind); f.nvert = const_cast<int *>(a.nvert);
         f.rx = states ? states[3 * i] : 0.0; f.ry = states ? states[3 * i + 1] : 0.0; f.rob = pose_dev ? pose_dev + 3 * i : nullptr;
         memcpy((void *)&li.sc.h[i], &a, sizeof(a));
-        H->sc_args = a; H->sc_n = n;
-        d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;                        // (scene_kernels)
-        d.slot_src = H->d_sc_sel; d.src_used = n < a.N ? n : a.N;
+        scene_bind(H, a, true);                         // (no per-member kernels: the launches below take every member)
         nmax = n > nmax ? n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
     // the members' records as they are now (the stream is idle: nothing reads the pinned mirrors)
@@ -3395,8 +3394,8 @@ extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, cons
     int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
     if (rc != RDA_OK) return rc;
     const size_t B = F->B;
-    for (rda_handle *H : F->egos) if (H->pending) return RDA_ERR_ARG;                     // a member inside a tick of its own
-    for (rda_handle *H : F->egos) if (H->follow) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member)
+    for (rda_handle *H : F->egos) if (H->tick.pending) return RDA_ERR_ARG;                // a member inside a tick of its own
+    for (rda_handle *H : F->egos) if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member)
     const bool fresh = !F->li.have();
     rc = fleet_lidar_reserve(F, false);
     if (rc != RDA_OK) return rc;
@@ -3447,13 +3446,13 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
     // fire-and-forget stores over the link, complete at the end of their kernels) instead of three device-to-host copies queued behind the last launch
     // (~10 us each on the tick's critical path).  rda_opts::zero_copy = 0 on any member keeps the copies.
     bool zc = true;
-    for (size_t i = 0; i < B; ++i) if (!F->egos[i]->zero_copy) zc = false;
+    for (size_t i = 0; i < B; ++i) if (!F->egos[i]->opts.zero_copy) zc = false;
     double *const out_base = zc ? F->out.h : F->out.d;
     rda_info *const info_base = zc ? F->info.h : F->info.d;
     FleetTrack &trk = F->trk;
     for (size_t i = 0; i < B; ++i) {
         const rda_handle *H = F->egos[i];
-        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len) return RDA_ERR_ARG;
+        if (!H->path.d || cur_index[i] < 0 || cur_index[i] >= H->path.len) return RDA_ERR_ARG;
     }
     const auto io = [&](size_t i) { return fleet_member_io(F, i, nom_u ? nullptr : F->egos[i]->d.u, out_base, info_base); };
     const bool tables = mirror_differs(trk.io, io) || mirror_differs(trk.paths, member_paths(F)) || mirror_differs(trk.lens, member_lens(F));
@@ -3478,7 +3477,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
     }
     if (ref_out) HIPCHK(F->in.pull(F->stream, F->in.n));
     HIPCHK(hipStreamSynchronize(F->stream));
-    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;      // their staged scenes have been consumed
+    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;  // their staged scenes have been consumed
     for (size_t i = 0; i < B; ++i) {
         fleet_result_out(F, i, out_u, out_s, info);
         if (ref_out) memcpy(ref_out + i * ns, F->in.h + i * nin + step_ref(T), ns * sizeof(double));
@@ -3506,7 +3505,7 @@ static int roll_check_members(const rda_fleet *F, const int32_t *cur_index)
 {
     for (int i = 0; i < F->B; ++i) {
         const rda_handle *H = F->egos[i];
-        if (!H->d_path || cur_index[i] < 0 || cur_index[i] >= H->path_len || H->pending) return RDA_ERR_ARG;
+        if (!H->path.d || cur_index[i] < 0 || cur_index[i] >= H->path.len || H->tick.pending) return RDA_ERR_ARG;
     }
     return RDA_OK;
 }
@@ -3534,7 +3533,7 @@ static void member_move_clear(const rda_handle *H, double *geom, double *base, c
 }
 // The moving entry's per-member tables as the members' raw scenes stand now.  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
 struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
-static bool member_raw_scene(const rda_handle *H) { return H->sc_n > 0 && H->d.obstacle_num != 0; }
+static bool member_raw_scene(const rda_handle *H) { return H->sc.n > 0 && H->d.obstacle_num != 0; }
 static void fleet_move_view(const rda_fleet *F, MoveView &v)
 {
     const size_t B = F->B;
@@ -3544,7 +3543,7 @@ static void fleet_move_view(const rda_fleet *F, MoveView &v)
         const bool raw = member_raw_scene(H);
         scene::Args &a = v.sc[i];
         memset((void *)&a, 0, sizeof(a));
-        if (raw) a = H->sc_args;
+        if (raw) a = H->sc.args;
         member_move_clear(H, raw ? const_cast<double *>(a.geom) : nullptr, nullptr, a.vel, a.kind, a.nvert, a.n, H->d.c.E, v.mv[i], v.cl[i]);      // (Move::base is set by the rollout)
         if (!raw) continue;
         v.off[i] = v.mv_total;                                                    // (its place in the snapshot buffer)
@@ -3604,7 +3603,7 @@ static bool fleet_roll_view(const rda_fleet *F, bool have_nom_u, RollView &v)
         v.wio[B + i] = fleet_member_io(F, i, H->d.u, F->out.d, F->info.d);                         // later ticks: the resident controls
         rollout::Member &m = v.wm[i];
         memset((void *)&m, 0, sizeof(m));
-        m.out_u = v.wio[i].out_u; m.info = v.wio[i].info; m.T = (int)T; m.L = H->path_len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
+        m.out_u = v.wio[i].out_u; m.info = v.wio[i].info; m.T = (int)T; m.L = H->path.len; m.dynamics = H->d.c.dynamics; m.dt = H->d.c.dt; m.wheelbase = H->d.c.L;
     }
     return mirror_differs(F->trk.paths, member_paths(F)) || mirror_differs(F->trk.lens, member_lens(F)) || mirror_differs(F->ro.m, records(v.wm)) ||
            mirror_differs(F->ro.io, records(v.wio));
@@ -3660,7 +3659,7 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
-    for (rda_handle *Hm : F->egos) Hm->pending_scene = 0;                       // their staged scenes have been consumed
+    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;                  // their staged scenes have been consumed
     F->roll_K = a.K;
     memcpy(a.states_log, a.states, B * 3 * sizeof(double));                     // row 0: the input
     memcpy(a.states_log + B * 3, log + lay.states + B * 3 * sizeof(double), K * B * 3 * sizeof(double));
@@ -3679,16 +3678,16 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
-    for (const rda_handle *H : F->egos) if (resort && (H->sc_n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
+    for (const rda_handle *H : F->egos) if (resort && (H->sc.n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
     for (const rda_handle *H : F->egos) {
-        if (H->follow) return RDA_ERR_UNSUPPORTED;                              // (k_follow_* are per member)
+        if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;                   // (k_follow_* are per member)
         if (!moving && H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
     }
     MoveView mvw;
     if (moving) {
         for (const rda_handle *H : F->egos) {
-            if (!resort && member_raw_scene(H) && H->sc_args.order != 0) return RDA_ERR_ARG;          // slots rebuilt in the staged order: only meaningful for order = 0
-            if (H->d.obstacle_num != 0 && H->d.nt > 1 && H->sc_n <= 0) return RDA_ERR_UNSUPPORTED;    // host-staged per-stage slots: no raw scene to move
+            if (!resort && member_raw_scene(H) && H->sc.args.order != 0) return RDA_ERR_ARG;          // slots rebuilt in the staged order: only meaningful for order = 0
+            if (H->d.obstacle_num != 0 && H->d.nt > 1 && H->sc.n <= 0) return RDA_ERR_UNSUPPORTED;    // host-staged per-stage slots: no raw scene to move
             if (a.clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
         }
         fleet_move_view(F, mvw);
@@ -3769,7 +3768,7 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
     if (!F || !states || !clearance) return RDA_ERR_ARG;
     const size_t B = F->B;
     for (const rda_handle *H : F->egos) {
-        if (H->pending) return RDA_ERR_ARG;
+        if (H->tick.pending) return RDA_ERR_ARG;
         if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
     }
     FleetMove tmov; FleetDoubles tclr;
@@ -3931,7 +3930,7 @@ extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
     for (const rda_handle *H : F->egos) {
-        if (H->follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;              // (k_follow_* are per member; a box has four vertices)
+        if (H->opts.duals_follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member; a box has four vertices)
         if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
     }
     // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
@@ -4019,10 +4018,10 @@ extern "C" int rda_fleet_enqueue_range(rda_fleet *F, int k0, int k1)
     if (!F || k0 < 0 || k0 > k1) return RDA_ERR_ARG;
     for (int i = 0; i < F->B; ++i) {
         rda_handle *H = F->egos[i];
-        if (k1 > H->K) return RDA_ERR_ARG;
+        if (k1 > H->trace.K) return RDA_ERR_ARG;
         EgoIO &e = F->h_io[i];
-        e.s = H->d_tr_s; e.u = H->d_tr_u; e.ref = H->d_tr_ref; e.speed = H->d_tr_speed;
-        e.out_u = H->d_tr_out_u; e.out_s = H->d_tr_out_s; e.info = H->d_tr_info;
+        e.s = H->trace.s; e.u = H->trace.u; e.ref = H->trace.ref; e.speed = H->trace.speed;
+        e.out_u = H->trace.out_u; e.out_s = H->trace.out_s; e.info = H->trace.info;
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
