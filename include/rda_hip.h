@@ -324,11 +324,21 @@ int  rda_upload_scan(rda_handle *h, int n_beams, const double *ranges, double an
  * their ADMM iterations as ONE grid with an ego dimension, which is what fills the 256 CUs.  Members must agree on
  * T, N, E, R and iter_num (weights, bounds, kinematics, robot polygons and obstacles may differ), must live on the
  * current device and must not be obstacle shards.  Results are identical to stepping every member with rda_step /
- * rda_enqueue_step.  Between rda_fleet_enqueue_range and rda_fleet_sync the members must not be used. */
+ * rda_enqueue_step.  Between rda_fleet_enqueue_range and rda_fleet_sync the members must not be used.
+ * LamMuZ mode: ALL members or NONE run the interior-point mode (rda_opts::lmz_mode = 1; lmz_mu may differ per member) - a mix is
+ * RDA_ERR_UNSUPPORTED.  Every fleet entry (step, tracked step, trace replay, the three rollouts) serves such a fleet; the launch form
+ * is chosen per member by the rule of a solo handle (the row-parallel kernel where the shape allows it and obstacles are staged, else
+ * the per-thread kernel), the kept central-path points stay in the members (rda_get / rda_set_lmz_history between fleet ticks).
+ * A member with a norm2 (circle) robot is refused with RDA_ERR_UNSUPPORTED: out of scope (the clearance log has no circle-robot form). */
 typedef struct rda_fleet rda_fleet;
 int  rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out);   /* does not take ownership of the members */
 void rda_fleet_destroy(rda_fleet *f);
 int  rda_fleet_size(rda_fleet *f);
+/* the fleet counterpart of rda_lammuz_kernel: the LamMuZ launches the next fleet tick issues per ADMM iteration as the members stand now
+ * (kernel names joined by '+').  Enumeration fleets: "k_lammuz_fleet_rows_fast+k_lammuz_fleet_enum+k_lmz_finalize_fleet", "k_lammuz_fleet_rows" or
+ * "k_lammuz_fleet+k_lmz_finalize_fleet".  Interior-point fleets: "k_lammuz_ip_fleet" when every member runs the row-parallel form,
+ * "k_lammuz_cp_fleet_small|large+k_lmz_finalize_fleet" when none does, all three names when both forms have members. */
+const char *rda_fleet_lammuz_kernel(rda_fleet *f);
 /* one synchronous MPC step of every member with the obstacles each member has staged (rda_upload_obstacles /
  * rda_upload_scene): per-ego arrays of rda_step, concatenated ego-major */
 int  rda_fleet_step(rda_fleet *f, const double *nom_s /*B*3*(T+1)*/, const double *nom_u /*B*2*T*/,

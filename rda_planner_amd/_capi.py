@@ -168,6 +168,9 @@ class CApi:
             f("fleet_sync").argtypes = [C.c_void_p]
             for name in ("fleet_create", "fleet_size", "fleet_step", "fleet_enqueue_range", "fleet_sync"):
                 f(name).restype = C.c_int
+            if hasattr(lib, f"{prefix}_fleet_lammuz_kernel"):       # the LamMuZ launches of the next fleet tick, names joined by '+'
+                f("fleet_lammuz_kernel").argtypes = [C.c_void_p]
+                f("fleet_lammuz_kernel").restype = C.c_char_p
             if hasattr(lib, f"{prefix}_fleet_scene_resort"):
                 f("fleet_scene_resort").argtypes = [C.c_void_p, c_double_p, C.c_int]
                 f("fleet_scene_resort").restype = C.c_int

@@ -105,6 +105,8 @@ struct Dev {
     double su_warm_wfl, su_warm_mu0;   // interior-point start of the su-problems of ADMM iterations >= 1 ("0,0" = cold)
     double su_hard_wfl, su_hard_mu0;   // ... of the steps that follow an UNCONVERGED step (rda_opts::su_hard_warm; mu0 = 0: the rule is off)
     int lmz_mode;            // 0: support enumeration + tie-breaks T1-T3 (default), 1: interior point, central path at lmz_mu (norm2 robots: always)
+    int ip_rows;             // mode 1 and the row-parallel kernel takes this shape (rda_handle::ip_rows): with staged obstacles the launch form is k_lammuz_ip, else the
+                             // per-thread kernel + k_lmz_finalize (lammuz_plan; the fleet kernels decide per member from this record)
     double lmz_mu;           // barrier parameter of the returned central-path point (mode 1)
     int centre;              // tie-break T1: central separating normal in the slack regime
     int obstacle_num;        // 0 or N
@@ -1036,11 +1038,11 @@ __global__ __launch_bounds__(256) void k_lmz_finalize(Dev d, int it, Fin fin) { 
 // updates as lammuz_body.  A solve that does not end on the central path keeps the previous duals of its stage and makes the
 // residual inf (rda_solver.py:781-793); unlike non-finite data (where everything of the stage is left alone) the xi / zeta
 // updates then run with the kept duals, as the reference's do.
-template <int NX, int MX> __device__ __forceinline__ void lammuz_cp_body(const Dev &d)
+template <int NX, int MX> __device__ __forceinline__ void lammuz_cp_body(const Dev &d, const int block)
 {
     const int T = d.c.T, E = d.c.E, R = d.c.R;
     if (d.ctrl->stop) return;
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    const int w = block * blockDim.x + threadIdx.x;
     if (d.obstacle_num == 0) {          // quirk Q9, as in lammuz_body
         if (w < T && d.rank == (d.c.N - 1) / d.Nloc) {
             const int i = w * d.Nloc + (d.c.N - 1) % d.Nloc;
@@ -1100,8 +1102,8 @@ template <int NX, int MX> __device__ __forceinline__ void lammuz_cp_body(const D
     ro.res = fail ? INFINITY : res; ro.hh = hx * hx + hy * hy;
     store_row(d, k, ro);
 }
-__global__ __launch_bounds__(64) void k_lammuz_cp_small(Dev d) { lammuz_cp_body<16, 24>(d); }      // E, R <= 4
-__global__ __launch_bounds__(64) void k_lammuz_cp_large(Dev d) { lammuz_cp_body<24, 36>(d); }      // E, R <= 8
+__global__ __launch_bounds__(64) void k_lammuz_cp_small(Dev d) { lammuz_cp_body<16, 24>(d, blockIdx.x); }      // E, R <= 4
+__global__ __launch_bounds__(64) void k_lammuz_cp_large(Dev d) { lammuz_cp_body<24, 36>(d, blockIdx.x); }      // E, R <= 8
 
 // K1, interior-point variant, ROW-PARALLEL (lammuz_ip_device.h): one sub-problem per 16-lane row, lane i = variable i of the cone
 // program, GS rows per workgroup in the launch order and with the epilogue of the packed enumeration kernel - duals, condensed terms,
@@ -1492,7 +1494,7 @@ extern "C" const char *rda_strerror(int code)
     switch (code) {
         case RDA_OK: return "ok";
         case RDA_ERR_ARG: return "invalid argument";
-        case RDA_ERR_UNSUPPORTED: return "unsupported configuration (E/R/T above the compiled limits, non-canonical circle obstacle, interior-point mode in a fleet)";
+        case RDA_ERR_UNSUPPORTED: return "unsupported configuration (E/R/T above the compiled limits, non-canonical circle obstacle, a norm2 robot or mixed LamMuZ modes in a fleet)";
         case RDA_ERR_HIP: return "HIP runtime error";
         case RDA_ERR_NODEVICE: return "no HIP device";
         default: return code > 0 ? "soft status" : "unknown error";
@@ -1630,6 +1632,7 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     rc |= m.pin(&H->step.h, step_doubles(T)); rc |= m.pin(&H->res.blk.h, res_doubles(T));
     H->step.n = step_doubles(T); H->res.blk.n = res_doubles(T); H->res.T = T;      // (the two pairs filled in by hand: the allocations keep their order)
     H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated);
+    d.ip_rows = (d.lmz_mode && H->ip_rows) ? 1 : 0;
     if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
     if (rc) return RDA_ERR_HIP;
     { const int hard = 99; HIPCHK(hipMemcpy(&d.ctrl->su_last, &hard, sizeof(int), hipMemcpyHostToDevice)); }     // no su history yet
@@ -2884,8 +2887,8 @@ template <int TT> __global__ __launch_bounds__(su::NT) void k_su_fleet(const Dev
     su_body<TT>(d, it, e.s + k * ns, e.u + k * nu, e.ref + k * ns, e.speed + k);
 }
 
-// a member without obstacles (Q9) or of a shape the packed body does not take runs the one-per-wave body on the first quarter
-// of the (packed-size) grid... kept simple: the fleet uses the packed kernel only when every member can
+// Enumeration mode: a member without obstacles (Q9) or of a shape the packed body does not take runs the one-per-wave body on the first quarter
+// of the (packed-size) grid... kept simple: the fleet uses the packed kernel only when every member can (its forms agree bit for bit)
 __device__ __forceinline__ Fin fleet_fin(const Dev &d, const EgoIO &e, int k)
 {
     const size_t ns = 3 * (d.c.T + 1), nu = 2 * d.c.T;
@@ -2901,8 +2904,35 @@ __global__ __launch_bounds__(64 * GS / 4, 2) void k_lammuz_fleet_rows(const Dev 
 #endif
 __global__ __launch_bounds__(64 * GS / 4, LMZ_FLEET_FAST_OCC) void k_lammuz_fleet_rows_fast(const Dev *devs, int it) { lammuz_body_rows<1>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
 __global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_fleet_enum(const Dev *devs, int it) { lammuz_body_rows<2>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
+// Interior-point mode: the launch form is chosen PER MEMBER by lammuz_plan's rule - the row-parallel kernel for a member whose shape it takes
+// (Dev::ip_rows) and that has staged obstacles, else the per-thread kernel (with its quirk-Q9 branch) + k_lmz_finalize_fleet.  The two kernels agree only to
+// ~4e-6, so a fleet-wide choice would make a member's result depend on its neighbours.  A kernel of one form returns at once for the members of the other; the
+// host launches only the forms some member needs (fleet_refresh_flags).
+__device__ __forceinline__ bool member_ip_rows(const Dev &d) { return d.ip_rows && d.obstacle_num; }
+#ifndef LMZ_FLEET_IP_OCC
+#define LMZ_FLEET_IP_OCC 1
+#endif
+__global__ __launch_bounds__(64 * GS / 4, LMZ_FLEET_IP_OCC) void k_lammuz_ip_fleet(const Dev *devs, int it)
+{
+    const Dev &d = devs[blockIdx.y];
+    if (!member_ip_rows(d)) return;
+    lammuz_ip_body(d, blockIdx.x, it, Fin{});
+}
+__global__ __launch_bounds__(64) void k_lammuz_cp_fleet_small(const Dev *devs)      // E, R <= 4
+{
+    const Dev &d = devs[blockIdx.y];
+    if (member_ip_rows(d)) return;
+    lammuz_cp_body<16, 24>(d, blockIdx.x);
+}
+__global__ __launch_bounds__(64) void k_lammuz_cp_fleet_large(const Dev *devs)      // E, R <= 8
+{
+    const Dev &d = devs[blockIdx.y];
+    if (member_ip_rows(d)) return;
+    lammuz_cp_body<24, 36>(d, blockIdx.x);
+}
 __global__ __launch_bounds__(256) void k_lmz_finalize_fleet(const Dev *devs, const EgoIO *io, int it, int k)
 {
+    if (member_ip_rows(devs[blockIdx.y])) return;      // (the row-parallel interior-point kernel made this member's block partials: the solo path launches no k_lmz_finalize behind it)
     finalize_body(devs[blockIdx.y], blockIdx.x, gridDim.x, it, fleet_fin(devs[blockIdx.y], io[blockIdx.y], k));
 }
 
@@ -3013,6 +3043,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     hbuf::Pair<double> out;               // per ego: u | s, the head of a result block (res_info doubles)
     hbuf::Pair<rda_info> info;
     int T, iter_num, J, rows, lmz_split;
+    int ip, ip_rows, ip_cp;               // interior-point fleet; some member runs the row-parallel kernel | the per-thread kernel this tick (fleet_refresh_flags)
     size_t su_lds;
     FleetTrack trk;
     FleetResort res; int rob_pending;     // rob_pending: a copy out of res.rob.h may be queued
@@ -3075,7 +3106,8 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
         // one grid for all members: the problem SHAPE must agree (weights, bounds, kinematics and robots may differ)
         if (a.T != b.T || a.N != b.N || a.E != b.E || a.R != b.R || a.iter_num != b.iter_num) return RDA_ERR_UNSUPPORTED;
         if (egos[i]->shard.comm || egos[i]->d.P != 1) return RDA_ERR_UNSUPPORTED;  // egos are replicas, obstacle shards are not
-        if (egos[i]->d.lmz_mode) return RDA_ERR_UNSUPPORTED;                       // the fused fleet launches run the enumeration kernels
+        if (b.robot_norm2) return RDA_ERR_UNSUPPORTED;                             // (no enumeration candidates, no clearance form: out of scope)
+        if ((egos[i]->d.lmz_mode != 0) != (egos[0]->d.lmz_mode != 0)) return RDA_ERR_UNSUPPORTED;      // one LamMuZ mode per fleet (lmz_mu may differ)
     }
     std::unique_ptr<rda_fleet> owner(new rda_fleet());     // a failure on the way drops the fleet and with it what was built
     rda_fleet *F = owner.get();
@@ -3103,6 +3135,23 @@ static void fleet_refresh_flags(rda_fleet *F)
     F->lmz_split = 1;
     for (int i = 0; i < F->B; ++i) if (!F->egos[i]->opts.lmz_split) F->lmz_split = 0;
     for (int i = 0; i < F->B; ++i) if (!F->egos[i]->d.rows || !F->egos[i]->d.obstacle_num) F->rows = 0;
+    // interior-point mode (all members or none, rda_fleet_create): every member's own form, lammuz_plan's rule
+    F->ip = F->egos[0]->d.lmz_mode != 0; F->ip_rows = 0; F->ip_cp = 0;
+    if (F->ip) for (int i = 0; i < F->B; ++i) { const Dev &d = F->egos[i]->d; if (d.ip_rows && d.obstacle_num) F->ip_rows = 1; else F->ip_cp = 1; }
+}
+// the LamMuZ launches of the next tick as the members stand now (kernel names joined by '+')
+extern "C" const char *rda_fleet_lammuz_kernel(rda_fleet *F)
+{
+    if (!F) return "";
+    fleet_refresh_flags(F);
+    if (F->ip) {
+        const bool small = F->egos[0]->d.c.E <= 4 && F->egos[0]->d.c.R <= 4;
+        if (!F->ip_cp) return "k_lammuz_ip_fleet";
+        if (!F->ip_rows) return small ? "k_lammuz_cp_fleet_small+k_lmz_finalize_fleet" : "k_lammuz_cp_fleet_large+k_lmz_finalize_fleet";
+        return small ? "k_lammuz_ip_fleet+k_lammuz_cp_fleet_small+k_lmz_finalize_fleet" : "k_lammuz_ip_fleet+k_lammuz_cp_fleet_large+k_lmz_finalize_fleet";
+    }
+    if (F->rows && F->lmz_split) return "k_lammuz_fleet_rows_fast+k_lammuz_fleet_enum+k_lmz_finalize_fleet";
+    return F->rows ? "k_lammuz_fleet_rows" : "k_lammuz_fleet+k_lmz_finalize_fleet";
 }
 
 // members' records (obstacle count, staged pointers, weights may have changed since the last call) -> device; the fleet
@@ -3138,7 +3187,15 @@ static int fleet_enqueue(rda_fleet *F, const EgoIO *io, int k)
         // a shared plan would branch on its caller.)
         constexpr int NTH = LMZ_NTH;
         const int nbr = F->T * F->J, nfin = (nbr + FPB - 1) / FPB, nbp = packed_grid(F->T, F->J);       // one workgroup per (stage, GS-slot block), XCD-aware order
-        if (F->rows && F->lmz_split) {
+        if (F->ip) {                                    // interior point: only the forms some member needs this tick (a kernel returns at once for the others' members)
+            if (F->ip_rows) hipLaunchKernelGGL(k_lammuz_ip_fleet, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, it);
+            if (F->ip_cp) {
+                const int ncp = (F->egos[0]->d.c.N * F->T + 63) / 64;      // a thread per (slot, stage); the Q9 branch needs T threads
+                if (F->egos[0]->d.c.E <= 4 && F->egos[0]->d.c.R <= 4) hipLaunchKernelGGL(k_lammuz_cp_fleet_small, dim3(ncp, B), dim3(64), 0, F->stream, devs);
+                else hipLaunchKernelGGL(k_lammuz_cp_fleet_large, dim3(ncp, B), dim3(64), 0, F->stream, devs);
+                hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
+            }
+        } else if (F->rows && F->lmz_split) {
             hipLaunchKernelGGL(k_lammuz_fleet_rows_fast, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, it);
             int ne = nbr / 8; if (ne < 8) ne = 8; if (ne > 128) ne = 128;
             hipLaunchKernelGGL(k_lammuz_fleet_enum, dim3(ne, B), dim3(NTH), 0, F->stream, devs, it);

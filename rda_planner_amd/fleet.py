@@ -44,7 +44,8 @@ def sensor_arrays(sensors, B):
 class Fleet:
     def __init__(self, members):
         """members: `MPC` objects with equal receding / max_obs_num / max_edge_num / iter_num and robots with the same
-        number of edges (anything else may differ)."""
+        number of edges.  Either all members or none use the interior-point LamMuZ mode (`lmz_central=`; its value may differ
+        per member), and no member is a circle (norm2) robot.  Anything else may differ."""
         self.members = list(members)
         if not self.members:
             raise ValueError("a fleet needs at least one member")
@@ -56,7 +57,8 @@ class Fleet:
         self._handle = C.c_void_p()
         rc = self.api.fleet_create(arr, B, C.byref(self._handle))
         if rc != 0:
-            raise RuntimeError(f"rda_fleet_create failed with code {rc} (members must agree on T, N, E, R, iter_num)")
+            raise RuntimeError(f"rda_fleet_create failed with code {rc} (members must agree on T, N, E, R, iter_num; "
+                               "either all members or none use lmz_central; a circle (norm2) robot cannot be a member)")
         T = self.members[0].receding
         self._in_s, self._in_u = np.zeros((B, 3, T + 1)), np.zeros((B, 2, T))
         self._ref, self._speed = np.zeros((B, 3, T + 1)), np.zeros(B)
@@ -66,6 +68,10 @@ class Fleet:
 
     def __len__(self):
         return len(self.members)
+
+    def lammuz_kernel(self):
+        """the LamMuZ launches the next tick issues per ADMM iteration as the members stand now (rda_fleet_lammuz_kernel): kernel names joined by '+'"""
+        return self.api.fleet_lammuz_kernel(self._handle).decode()
 
     def close(self):
         if self._handle:
