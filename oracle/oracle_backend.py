@@ -5,11 +5,42 @@ classes on top of oracle/librda_oracle.so instead of the HIP library.
 """
 import ctypes as C
 
-from rda_planner_amd._capi import CApi, Cfg, c_double_p, c_int_p
+from rda_planner_amd._capi import CApi, CODES, declare
 from rda_planner_amd.rda_solver import _Backend
 from . import oracle_lib
 
 _api = None
+
+ORC_CODES = dict(CODES, L=C.POINTER(C.c_long))      # long *
+# what oracle/rda_oracle.h declares beyond the shared C-ABI (rda_planner_amd/_capi.py PROTOTYPES, which CApi applies): name without prefix ->
+# "<return> <parameters>"; tests/test_capi_symbols.py holds it against the header
+ORC_PROTOTYPES = {
+    "set_threads":          "v i",
+    "set_su_dump":          "v s",
+    "set_su_trace":         "v i",
+    "set_lmz_mode":         "v i",
+    "lmz_failures":         "i h",
+    "set_lmz_ipm_tol":      "v d",
+    "set_lmz_ipm_mu":       "v d",
+    "lammuz_ipm_one":       "i iiDDiiDdDDDdddiDDDDI",
+    "set_centre":           "v i",
+    "lammuz_one":           "i iiDDiDdDDDddddiDDDD",
+    "set_su_warm":          "v ddi",
+    "set_su_warm_endgame":  "v dd",
+    "set_su_warm_clip":     "v d",
+    "set_su_easy":          "v dddddi",
+    "set_su_hard_warm":     "v dd",
+    "set_su_cold_from":     "v ii",
+    "set_su_first_attempt": "v i",
+    "get_su_ipm_hist":      "v hIi",
+    "set_su_tol":           "v ddd",
+    "set_su_tol_early":     "v ddd",
+    "set_su_accept":        "v i",
+    "set_su_land":          "v i",
+    "set_su_land_tol":      "v ddd",
+    "get_su_land_stats":    "v L",
+    "get_su_landed":        "i",
+}
 
 
 def api():
@@ -17,13 +48,7 @@ def api():
     if _api is None:
         lib = oracle_lib.load()
         _api = CApi(lib, "orc")
-        lib.orc_lammuz_one.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, C.c_double,
-                                       c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double,
-                                       C.c_double, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
-        lib.orc_lammuz_one.restype = C.c_int
-        lib.orc_su_solve.argtypes = [C.POINTER(Cfg)] + [c_double_p] * 3 + [C.c_double] + [c_double_p] * 7 + [c_int_p]
-        lib.orc_su_solve.restype = C.c_int
-        lib.orc_set_threads.argtypes = [C.c_int]
+        declare(lib, "orc", ORC_PROTOTYPES, ORC_CODES)
     return _api
 
 

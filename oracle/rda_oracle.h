@@ -118,6 +118,14 @@ void orc_set_su_first_attempt(int first);   /* test switch (= rda_opts::su_first
 void orc_get_su_ipm_hist(const orc_handle *h, int *out, int n);   /* debug: interior-point iterations of the su-solve of each ADMM iteration of the last step */
 /* interior-point stop of the su-problem: |r_dual| <= rd (1+|g|), |r_prim| <= rp, mean complementarity <= mu (1+|g|) */
 void orc_set_su_tol(double rd, double rp, double mu);
+void orc_set_su_tol_early(double rd, double rp, double mu);   /* mirror of rda_opts::su_tol_early: stop of the su-problems before the last ADMM iteration of a step (0, 0, 0: su_tol) */
+void orc_set_su_accept(int on);           /* mirror of rda_opts::su_accept: the near-converged iterate kept as a safety net; 2 = test switch, always return it */
+/* mirrors of rda_opts::su_land / su_land_tol (the landing of the su interior point on its vertex, default on); orc_get_su_landed: whether the calling
+ * thread's last su-solve was landed; orc_get_su_land_stats: debug counters since the last call (calls, accepted, rounds, the last verdicts, rows moved) */
+void orc_set_su_land(int on);
+void orc_set_su_land_tol(double rd, double rp, double mu);
+int  orc_get_su_landed(void);
+void orc_get_su_land_stats(long *out8);
 int  orc_su_solve(const orc_cfg *cfg, const double *nom_s, const double *nom_u, const double *ref_s,
                   double ref_speed, const double *a, const double *cc, const double *g,
                   const double *d0, double *s, double *u, double *d, int *ipm_iters);

@@ -3,6 +3,9 @@
 The binding class is parametrised by the symbol prefix: the product instantiates it on
 `librda_hip.so` (symbols `rda_*`); the test suite re-uses it on its CPU checker, which
 deliberately shares struct layouts and argument order (symbols `orc_*`).
+
+Every prototype is one line of `PROTOTYPES`; tests/test_capi_symbols.py holds the table against
+the header, so a new entry point is a header prototype plus one line here.
 """
 import ctypes as C
 import numpy as np
@@ -42,6 +45,122 @@ class Info(C.Structure):
 
 DYNAMICS = {"acker": 0, "diff": 1, "omni": 2}
 
+# one letter per C type of a prototype; `v` and `s` also serve as return types
+CODES = {"v": None, "i": C.c_int, "d": C.c_double, "s": C.c_char_p,
+         "D": c_double_p,                   # [const] double *
+         "I": c_int_p,                      # [const] int32_t *, int *
+         "Q": C.POINTER(C.c_longlong),      # long long *
+         "h": C.c_void_p,                   # rda_handle *, rda_fleet *, [const] void *
+         "H": C.POINTER(C.c_void_p),        # rda_handle **, rda_fleet **, rda_handle *const *
+         "C": C.POINTER(Cfg), "O": C.POINTER(Opts), "N": C.POINTER(Info)}
+
+# name without prefix -> "<return> <parameters>", in the order of include/rda_hip.h
+PROTOTYPES = {
+    "opts_init":            "v O",
+    "create":               "i CDDH",
+    "create_opts":          "i CODDH",
+    "destroy":              "v h",
+    "set_adjust":           "i hddddd",
+    "reset":                "i h",
+    "strerror":             "s i",
+    "device_count":         "i",
+    "set_device":           "i i",
+    "step":                 "i hDDDdiDDIiDDN",
+    "upload_scene":         "i hiIIDDDiI",
+    "step_scene":           "i hDDDdiIIDDDiDDN",
+    "get_obstacles":        "i hDDII",
+    "debug_scene_geom":     "i hDI",
+    "upload_obstacles":     "i hiDDIi",
+    "upload_trace":         "i hiDDDD",
+    "enqueue_step":         "i hi",
+    "enqueue_range":        "i hii",
+    "sync":                 "i h",
+    "fetch_result":         "i hiDDN",
+    "timing_reset":         "i hi",
+    "timing_read":          "i hiDI",
+    "timing_launches":      "i hiDiI",
+    "lammuz_kernel":        "s h",
+    "last_nonconvex":       "i h",
+    "upload_path":          "i hiD",
+    "step_tracked":         "i hDdidiDDDNDDID",
+    "tracked_begin":        "i hDdidiD",
+    "upload_scene_async":   "i hiIIDDDi",
+    "tracked_finish":       "i hDDNDDID",
+    "scene_resort":         "i hD",
+    "scan_boxes":           "i hiDdddDdiIDiI",
+    "upload_scan":          "i hiDdddDdiiI",
+    "fleet_create":         "i HiH",
+    "fleet_destroy":        "v h",
+    "fleet_size":           "i h",
+    "fleet_lammuz_kernel":  "s h",
+    "fleet_step":           "i hDDDDDDN",
+    "fleet_upload_scenes":  "i hIIIDDDI",
+    "fleet_step_tracked":   "i hDDIdiDDDNDID",
+    "fleet_scene_resort":   "i hDi",
+    "fleet_scan_boxes":     "i hIDDDDDdiIDiI",
+    "fleet_upload_scans":   "i hIDDDDDdiII",
+    "fleet_rollout":        "i hiDDIdiiiDDDINI",
+    "fleet_rollout_last":   "i hDD",
+    "fleet_rollout_moving": "i hiDDIdiiiDDDINID",
+    "fleet_clearance":      "i hDD",
+    "fleet_upload_worlds":  "i hIiIIDD",
+    "fleet_raycast":        "i hIDDDDDD",
+    "fleet_rollout_lidar":  "i hiDDIdiiDIDDDDdiIiDDINIID",
+    "debug_fleet_world":    "i hDII",
+    "fleet_enqueue_range":  "i hii",
+    "fleet_sync":           "i h",
+    "get_state":            "i hDDDDDDDD",
+    "set_state":            "i hDDDDDDDD",
+    "get_su_history":       "i hID",
+    "set_su_history":       "i hID",
+    "get_su_history_n":     "i hIiD",
+    "set_su_history_n":     "i hIiD",
+    "lmz_history_doubles":  "i h",
+    "get_lmz_history":      "i hDI",
+    "set_lmz_history":      "i hDI",
+    "debug_su_prof":        "i hQ",
+    "debug_su_trace":       "i hQiI",
+    "debug_su_land":        "i hI",
+    "debug_su_land_n":      "i hIi",
+    "debug_flush_supports": "i h",
+    "debug_slot_src":       "i hII",
+    "debug_worklist":       "i hI",
+    "debug_alloc_fail":     "i i",
+    "debug_alloc_stats":    "i QQ",
+    "shard_config":         "i hii",
+    "shard_chunk_doubles":  "i h",
+    "shard_get_chunk":      "i hD",
+    "shard_set_chunks":     "i hD",
+    "shard_unique_id":      "i hh",
+    "shard_comm_init":      "i hh",
+    "shard_comm_count":     "i h",
+    "admm_begin":           "i hDDDd",
+    "admm_su":              "i hiI",
+    "admm_lammuz":          "i h",
+    "admm_finish":          "i hDDN",
+    "lammuz_batch":         "i iiiDDIDDDDDDDddiDDDD",
+    "su_solve":             "i CDDDdDDDDDDDI",
+    "su_solve_opts":        "i CODDDdDDDDDDDI",
+    # exported by profiling builds only (-DRDA_LMZ_CLK / -DRDA_LMZ_STATS), not in the header: the caller's buffer as an address
+    "debug_lmz_clk":        "i hhi",
+    "debug_lmz_stats":      "i hh",
+}
+PROFILING_ONLY = frozenset(("debug_lmz_clk", "debug_lmz_stats"))
+
+
+def signature(proto, codes=CODES):
+    """(restype, argtypes) of one table entry"""
+    ret, _, params = proto.partition(" ")
+    return codes[ret], [codes[c] for c in params]
+
+
+def declare(lib, prefix, table, codes=CODES):
+    """set restype and argtypes of every `<prefix>_<name>` of `table` that `lib` exports"""
+    for name, proto in table.items():
+        fn = getattr(lib, f"{prefix}_{name}", None)
+        if fn is not None:
+            fn.restype, fn.argtypes = signature(proto, codes)
+
 
 def dptr(a):
     return a.ctypes.data_as(c_double_p) if a is not None else None
@@ -63,158 +182,26 @@ class CApi:
 
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
-        f = self._f
-        f("create").argtypes = [C.POINTER(Cfg), c_double_p, c_double_p, C.POINTER(C.c_void_p)]
-        f("create").restype = C.c_int
-        self.has_opts = hasattr(lib, f"{prefix}_create_opts")
-        if self.has_opts:
-            f("opts_init").argtypes = [C.POINTER(Opts)]
-            f("opts_init").restype = None
-            f("create_opts").argtypes = [C.POINTER(Cfg), C.POINTER(Opts), c_double_p, c_double_p, C.POINTER(C.c_void_p)]
-            f("create_opts").restype = C.c_int
-            f("get_su_history").argtypes = [C.c_void_p, c_int_p, c_double_p]
-            f("set_su_history").argtypes = [C.c_void_p, c_int_p, c_double_p]
-            f("get_su_history").restype = f("set_su_history").restype = C.c_int
-            if hasattr(lib, f"{prefix}_get_su_history_n"):
-                f("get_su_history_n").argtypes = [C.c_void_p, c_int_p, C.c_int, c_double_p]
-                f("set_su_history_n").argtypes = [C.c_void_p, c_int_p, C.c_int, c_double_p]
-                f("get_su_history_n").restype = f("set_su_history_n").restype = C.c_int
-        f("destroy").argtypes = [C.c_void_p]
-        f("destroy").restype = None
-        f("set_adjust").argtypes = [C.c_void_p] + [C.c_double] * 5
-        f("set_adjust").restype = C.c_int
-        f("reset").argtypes = [C.c_void_p]
-        f("reset").restype = C.c_int
-        f("step").argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
-                              c_double_p, c_double_p, c_int_p, C.c_int, c_double_p, c_double_p,
-                              C.POINTER(Info)]
-        f("step").restype = C.c_int
-        if hasattr(lib, f"{prefix}_debug_alloc_fail"):          # (HIP library only: the allocation rule's test hooks)
-            f("debug_alloc_fail").argtypes = [C.c_int]
-            f("debug_alloc_stats").argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-            f("debug_alloc_fail").restype = f("debug_alloc_stats").restype = C.c_int
-        f("get_state").argtypes = [C.c_void_p] + [c_double_p] * 8
-        f("get_state").restype = C.c_int
-        f("set_state").argtypes = [C.c_void_p] + [c_double_p] * 8
-        f("set_state").restype = C.c_int
-        # obstacle sharding + host-driven ADMM pieces
-        f("upload_obstacles").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_int]
-        f("shard_config").argtypes = [C.c_void_p, C.c_int, C.c_int]
-        f("shard_chunk_doubles").argtypes = [C.c_void_p]
-        f("shard_get_chunk").argtypes = [C.c_void_p, c_double_p]
-        f("shard_set_chunks").argtypes = [C.c_void_p, c_double_p]
-        f("admm_begin").argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_double]
-        f("admm_su").argtypes = [C.c_void_p, C.c_int, c_int_p]
-        f("admm_lammuz").argtypes = [C.c_void_p]
-        f("admm_finish").argtypes = [C.c_void_p, c_double_p, c_double_p, C.POINTER(Info)]
-        for name in ("upload_obstacles", "shard_config", "shard_chunk_doubles", "shard_get_chunk", "shard_set_chunks",
-                     "admm_begin", "admm_su", "admm_lammuz", "admm_finish"):
-            f(name).restype = C.c_int
-
-        # caller-side obstacle pipeline on the device (HIP library only)
-        self.has_scene = hasattr(lib, f"{prefix}_step_scene")
-        if self.has_scene:
-            f("upload_scene").argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_int, c_int_p]
-            f("upload_scene").restype = C.c_int
-            f("step_scene").argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int, c_int_p, c_int_p,
-                                        c_double_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, C.POINTER(Info)]
-            f("step_scene").restype = C.c_int
-            f("get_obstacles").argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p]
-            f("get_obstacles").restype = C.c_int
-
-        # lidar front end on the device (HIP library only)
-        self.has_scan = hasattr(lib, f"{prefix}_upload_scan")
-        if self.has_scan:
-            f("scan_boxes").argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_double, C.c_double, c_double_p, C.c_double, C.c_int,
-                                        c_int_p, c_double_p, C.c_int, c_int_p]
-            f("upload_scan").argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_double, C.c_double, c_double_p, C.c_double, C.c_int,
-                                         C.c_int, c_int_p]
-            f("scan_boxes").restype = f("upload_scan").restype = C.c_int
-
-        # caller-side pre_process on the device (HIP library only)
-        self.has_track = hasattr(lib, f"{prefix}_step_tracked")
-        self.has_pipeline = False
-        if self.has_track:
-            f("upload_path").argtypes = [C.c_void_p, C.c_int, c_double_p]
-            f("upload_path").restype = C.c_int
-            f("step_tracked").argtypes = [C.c_void_p, c_double_p, C.c_double, C.c_int, C.c_double, C.c_int, c_double_p,
-                                          c_double_p, c_double_p, C.POINTER(Info), c_double_p, c_double_p, c_int_p, c_double_p]
-            f("step_tracked").restype = C.c_int
-            self.has_pipeline = hasattr(lib, f"{prefix}_tracked_begin")
-            if self.has_pipeline:
-                f("tracked_begin").argtypes = [C.c_void_p, c_double_p, C.c_double, C.c_int, C.c_double, C.c_int, c_double_p]
-                f("upload_scene_async").argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_int]
-                f("tracked_finish").argtypes = [C.c_void_p, c_double_p, c_double_p, C.POINTER(Info), c_double_p, c_double_p,
-                                                c_int_p, c_double_p]
-                for name in ("tracked_begin", "upload_scene_async", "tracked_finish"):
-                    f(name).restype = C.c_int
-                if hasattr(lib, f"{prefix}_scene_resort"):
-                    f("scene_resort").argtypes = [C.c_void_p, c_double_p]
-                    f("scene_resort").restype = C.c_int
-            if hasattr(lib, f"{prefix}_fleet_step_tracked"):
-                f("fleet_step_tracked").argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, c_double_p,
-                                                    c_double_p, c_double_p, C.POINTER(Info), c_double_p, c_int_p, c_double_p]
-                f("fleet_step_tracked").restype = C.c_int
-        # batched multi-ego stepping (HIP library only)
-        self.has_fleet = hasattr(lib, f"{prefix}_fleet_step")
-        if self.has_fleet:
-            f("fleet_create").argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
-            f("fleet_destroy").argtypes = [C.c_void_p]
-            f("fleet_destroy").restype = None
-            f("fleet_size").argtypes = [C.c_void_p]
-            f("fleet_step").argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
-                                        C.POINTER(Info)]
-            f("fleet_enqueue_range").argtypes = [C.c_void_p, C.c_int, C.c_int]
-            f("fleet_sync").argtypes = [C.c_void_p]
-            for name in ("fleet_create", "fleet_size", "fleet_step", "fleet_enqueue_range", "fleet_sync"):
-                f(name).restype = C.c_int
-            if hasattr(lib, f"{prefix}_fleet_lammuz_kernel"):       # the LamMuZ launches of the next fleet tick, names joined by '+'
-                f("fleet_lammuz_kernel").argtypes = [C.c_void_p]
-                f("fleet_lammuz_kernel").restype = C.c_char_p
-            if hasattr(lib, f"{prefix}_fleet_scene_resort"):
-                f("fleet_scene_resort").argtypes = [C.c_void_p, c_double_p, C.c_int]
-                f("fleet_scene_resort").restype = C.c_int
-            self.has_fleet_scenes = hasattr(lib, f"{prefix}_fleet_upload_scenes")
-            if self.has_fleet_scenes:
-                f("fleet_upload_scenes").argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
-                f("fleet_upload_scenes").restype = C.c_int
-            # fleet lidar: every member's scan in one launch
-            self.has_fleet_scans = hasattr(lib, f"{prefix}_fleet_upload_scans")
-            if self.has_fleet_scans:
-                f("fleet_scan_boxes").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
-                                                  c_int_p, c_double_p, C.c_int, c_int_p]
-                f("fleet_upload_scans").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int,
-                                                    c_int_p, c_int_p]
-                f("fleet_scan_boxes").restype = f("fleet_upload_scans").restype = C.c_int
-            # fleet rollout: K closed-loop ticks on the device, one host wait
-            self.has_fleet_rollout = hasattr(lib, f"{prefix}_fleet_rollout")
-            if self.has_fleet_rollout:
-                f("fleet_rollout").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, C.c_int, c_double_p,
-                                               c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p]
-                f("fleet_rollout_last").argtypes = [C.c_void_p, c_double_p, c_double_p]
-                f("fleet_rollout").restype = f("fleet_rollout_last").restype = C.c_int
-            # ... for scenes that move (obstacle motion and the clearance log on the device), the clearance on its own, the raw-geometry test hook
-            self.has_fleet_rollout_moving = hasattr(lib, f"{prefix}_fleet_rollout_moving")
-            if self.has_fleet_rollout_moving:
-                f("fleet_rollout_moving").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, C.c_int, c_double_p,
-                                                      c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p, c_double_p]
-                f("fleet_clearance").argtypes = [C.c_void_p, c_double_p, c_double_p]
-                f("debug_scene_geom").argtypes = [C.c_void_p, c_double_p, c_int_p]
-                f("fleet_rollout_moving").restype = f("fleet_clearance").restype = f("debug_scene_geom").restype = C.c_int
-            # the simulated sensor: a resident world per member, the fleet ray caster, the rollout around it, the world test hook
-            self.has_fleet_rollout_lidar = hasattr(lib, f"{prefix}_fleet_rollout_lidar")
-            if self.has_fleet_rollout_lidar:
-                f("fleet_upload_worlds").argtypes = [C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p]
-                f("fleet_raycast").argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
-                f("fleet_rollout_lidar").argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_int_p, C.c_double, C.c_int, C.c_int, c_double_p,
-                                                     c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_int, c_int_p, C.c_int,
-                                                     c_double_p, c_double_p, c_int_p, C.POINTER(Info), c_int_p, c_int_p, c_double_p]
-                f("debug_fleet_world").argtypes = [C.c_void_p, c_double_p, c_int_p, c_int_p]
-                for name in ("fleet_upload_worlds", "fleet_raycast", "fleet_rollout_lidar", "debug_fleet_world"):
-                    f(name).restype = C.c_int
+        declare(lib, prefix, PROTOTYPES)
+        has = lambda name: hasattr(lib, f"{prefix}_{name}")     # noqa: E731
+        self.has_opts = has("create_opts")
+        self.has_scene = has("step_scene")              # caller-side obstacle pipeline on the device (HIP library only, like all below)
+        self.has_scan = has("upload_scan")              # lidar front end on the device
+        self.has_track = has("step_tracked")            # caller-side pre_process on the device
+        self.has_pipeline = self.has_track and has("tracked_begin")
+        self.has_fleet = has("fleet_step")              # batched multi-ego stepping
+        self.has_fleet_scenes = has("fleet_upload_scenes")
+        self.has_fleet_scans = has("fleet_upload_scans")                    # fleet lidar: every member's scan in one launch
+        self.has_fleet_rollout = has("fleet_rollout")                       # K closed-loop ticks on the device, one host wait
+        self.has_fleet_rollout_moving = has("fleet_rollout_moving")         # ... for scenes that move
+        self.has_fleet_rollout_lidar = has("fleet_rollout_lidar")           # ... around the simulated sensor
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")
 
     def __getattr__(self, name):
         return self._f(name)
+
+    def failed(self, name, rc):
+        """the exception of a refused call: `if rc < 0: raise api.failed("step", rc)`"""
+        return RuntimeError(f"{self.prefix}_{name} failed with code {rc}")

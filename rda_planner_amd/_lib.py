@@ -3,7 +3,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._capi import CApi, Cfg, c_double_p, c_int_p
+from ._capi import CApi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _BUILT_SO = os.path.join(_HERE, "librda_hip.so")
@@ -50,39 +50,6 @@ def hip_api():
     if _api is None:
         lib = load_library()
         api = CApi(lib, "rda")
-        lib.rda_device_count.restype = C.c_int
-        lib.rda_set_device.argtypes = [C.c_int]
-        lib.rda_set_device.restype = C.c_int
-        lib.rda_strerror.restype = C.c_char_p
-        lib.rda_strerror.argtypes = [C.c_int]
-        lib.rda_last_nonconvex.argtypes = [C.c_void_p]
-        lib.rda_last_nonconvex.restype = C.c_int
-        lib.rda_lammuz_kernel.argtypes = [C.c_void_p]
-        lib.rda_lammuz_kernel.restype = C.c_char_p
-        lib.rda_shard_comm_count.argtypes = [C.c_void_p]
-        lib.rda_shard_comm_count.restype = C.c_int
-        lib.rda_debug_su_prof.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
-        lib.rda_debug_su_prof.restype = C.c_int
-        lib.rda_shard_unique_id.argtypes = [C.c_void_p, C.c_void_p]
-        lib.rda_shard_comm_init.argtypes = [C.c_void_p, C.c_void_p]
-        lib.rda_shard_unique_id.restype = C.c_int
-        lib.rda_shard_comm_init.restype = C.c_int
-        lib.rda_upload_trace.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
-        lib.rda_enqueue_step.argtypes = [C.c_void_p, C.c_int]
-        lib.rda_sync.argtypes = [C.c_void_p]
-        lib.rda_fetch_result.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_void_p]
-        lib.rda_timing_reset.argtypes = [C.c_void_p, C.c_int]
-        lib.rda_timing_read.argtypes = [C.c_void_p, C.c_int, c_double_p, c_int_p]
-        lib.rda_timing_launches.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int, c_int_p]
-        lib.rda_lammuz_batch.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
-                                         c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double,
-                                         C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
-        lib.rda_su_solve.argtypes = [C.POINTER(Cfg)] + [c_double_p] * 3 + [C.c_double] + [c_double_p] * 7 + [c_int_p]
-        lib.rda_su_solve_opts.argtypes = [C.POINTER(Cfg), C.c_void_p] + [c_double_p] * 3 + [C.c_double] + [c_double_p] * 7 + [c_int_p]
-        lib.rda_su_solve_opts.restype = C.c_int
-        for name in ("upload_trace", "enqueue_step", "sync", "fetch_result", "timing_reset",
-                     "timing_read", "timing_launches", "lammuz_batch", "su_solve"):
-            getattr(lib, "rda_" + name).restype = C.c_int
         if lib.rda_device_count() < 1:
             raise RuntimeError("librda_hip.so loaded but no HIP device is visible; rda_planner_amd has no CPU fallback")
         _api = api

@@ -41,6 +41,11 @@ def sensor_arrays(sensors, B):
     return (np.array(cols[0], np.int32),) + tuple(f64(c) for c in cols[1:])
 
 
+def states_array(states, B):
+    """B states - (3,), (3, 1) or longer - as one contiguous (B, 3) array"""
+    return f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+
+
 class Fleet:
     def __init__(self, members):
         """members: `MPC` objects with equal receding / max_obs_num / max_edge_num / iter_num and robots with the same
@@ -128,11 +133,11 @@ class Fleet:
                 rda_obs = obstacles if m.rda_obstacle else m.convert_rda_obstacle(obstacles, m.state, m.obstacle_order)
                 m.rda.upload_obstacles(rda_obs)
         if stage is not None:
-            stage(np.array([np.asarray(m.state, float).ravel()[0:3] for m in self.members]))
+            stage(states_array([m.state for m in self.members], len(self.members)))
         rc = self.api.fleet_step(self._handle, dptr(self._in_s), dptr(self._in_u), dptr(self._ref), dptr(self._speed),
                                  dptr(self._out_u), dptr(self._out_s), self._info)
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_step failed with code {rc}")
+            raise self.api.failed("fleet_step", rc)
         out = []
         for i, m in enumerate(self.members):
             cur_ref_path, ref_list = begun[i]
@@ -163,7 +168,7 @@ class Fleet:
         order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, len(ms))
         rc = self.api.fleet_upload_scenes(self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob), iptr(order))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_upload_scenes failed with code {rc}")
+            raise self.api.failed("fleet_upload_scenes", rc)
         self.batched_ticks += 1
         return True
 
@@ -176,8 +181,7 @@ class Fleet:
         n_beams = np.fromiter((r.size for r in ranges), np.int32, B)
         allr = np.concatenate(ranges) if n_beams.sum() else np.zeros(1)
         lo, hi, rmax = (f64([float(s[k]) for s in scans]) for k in ("angle_min", "angle_max", "range_max"))
-        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
-        return n_beams, allr, lo, hi, rmax, st
+        return n_beams, allr, lo, hi, rmax, states_array(states, B)
 
     def scan_boxes(self, states, scans, eps=2.0, min_samples=6):
         """`RDA_solver.scan_boxes` for every member in one kernel launch: the list of (n_i, 4, 2) corner arrays"""
@@ -189,7 +193,7 @@ class Fleet:
         rc = self.api.fleet_scan_boxes(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
                                        iptr(n), dptr(boxes), cap, None)
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_scan_boxes failed with code {rc}")
+            raise self.api.failed("fleet_scan_boxes", rc)
         return [boxes[i, :n[i]].copy() for i in range(B)]
 
     def upload_scans(self, states, scans, eps=2.0, min_samples=6):
@@ -204,7 +208,7 @@ class Fleet:
         rc = self.api.fleet_upload_scans(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
                                          iptr(order), iptr(n))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_upload_scans failed with code {rc}")
+            raise self.api.failed("fleet_upload_scans", rc)
         return n
 
     def upload_worlds(self, obstacle_lists):
@@ -231,7 +235,7 @@ class Fleet:
         kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
         rc = self.api.fleet_upload_worlds(self._handle, iptr(counts), int(we), iptr(kind), iptr(nvert), dptr(f64(geom)), dptr(f64(vel)))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_upload_worlds failed with code {rc}")
+            raise self.api.failed("fleet_upload_worlds", rc)
 
     def raycast(self, states, sensors):
         """every member's lidar scan of its resident world (`upload_worlds`) from `states[i]`, ray-cast on the device by one launch
@@ -244,7 +248,7 @@ class Fleet:
         nb, lo, hi, rmin, rmax = sensor_arrays(sensors, B)
         if len(states) != B:
             raise ValueError("Fleet.raycast: one state per member")
-        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+        st = states_array(states, B)
         ranges = np.zeros(max(int(nb.sum()), 1))
         rc = self.api.fleet_raycast(self._handle, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges))
         if rc < 0:
@@ -256,7 +260,7 @@ class Fleet:
     def sync(self):
         rc = self.api.fleet_sync(self._handle)
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_sync failed with code {rc}")
+            raise self.api.failed("fleet_sync", rc)
 
     def rollout(self, states, ref_speeds, steps, resort=True, **kwargs):
         """`steps` closed-loop ticks of every member on the device with ONE host wait (rda_fleet_rollout): per tick what `control` does with the
@@ -313,24 +317,12 @@ class Fleet:
         B, T, K = len(ms), ms[0].receding, int(steps)
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
-        st, cur, speed = np.zeros((B, 3)), np.zeros(B, np.int32), np.zeros(B)
-        resident = True
-        for i, m in enumerate(ms):
-            cur_ref_path, gear = m._piece(states[i])
-            m._sync_path(cur_ref_path)
-            st[i] = np.asarray(m.state, float).ravel()[0:3]
-            speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
-            resident = resident and m._nominal_u() is None
+        st, speed, cur, _, nom_u = self._gather(states, ref_speeds)
         if world is not None:
             self.upload_worlds(world)
         if obstacle_lists is not None and not self._stage_all(obstacle_lists, st):
             for i, m in enumerate(ms):
                 m._stage_obstacles(obstacle_lists[i])
-        nom_u = None
-        if not resident:            # some member's cur_vel_array was replaced since its last solve: send them all
-            for i, m in enumerate(ms):
-                self._in_u[i] = f64(m.cur_vel_array, (2, T))
-            nom_u = self._in_u
         s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
         i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
         infos = (Info * (max(K, 1) * B))()
@@ -341,17 +333,17 @@ class Fleet:
             order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
             b_log = np.zeros((max(K, 0), B), np.int32)
             rc, name = self.api.fleet_rollout_lidar(*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples,
-                                                    iptr(order), 1 if moving else 0, *logs, iptr(b_log), dptr(c_log)), "rda_fleet_rollout_lidar"
+                                                    iptr(order), 1 if moving else 0, *logs, iptr(b_log), dptr(c_log)), "fleet_rollout_lidar"
         else:
             args = head + (1 if resort else 0, dptr(nom_u)) + logs
             rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
-            name = "rda_fleet_rollout_moving" if moving else "rda_fleet_rollout"
+            name = "fleet_rollout_moving" if moving else "fleet_rollout"
         if rc < 0:
-            raise RuntimeError(f"{name} failed with code {rc}")
+            raise self.api.failed(name, rc)
         eh = np.zeros(B)
         rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_rollout_last failed with code {rc}")
+            raise self.api.failed("fleet_rollout_last", rc)
         for i, m in enumerate(ms):
             path = m.ref_path
             m.state = s_log[K, i].reshape(3, 1).copy()
@@ -380,43 +372,50 @@ class Fleet:
         if any(m.car_tuple.cone_type == "norm2" for m in self.members):
             raise RuntimeError("Fleet.clearance is for polygon robots; a circle (norm2) robot is not supported")
         B = len(self.members)
-        st = f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
+        st = states_array(states, B)
         out = np.zeros(B)
         rc = self.api.fleet_clearance(self._handle, dptr(st), dptr(out))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_clearance failed with code {rc}")
+            raise self.api.failed("fleet_clearance", rc)
         return out
 
-    def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
-        """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the
-        signed speed and the path index travel"""
+    def _gather(self, states, ref_speeds):
+        """what a device-tracked tick takes from the members, before anything is staged: every member's piece of its path chosen (`_piece`) and
+        brought to the device (`_sync_path`); returns the states (B, 3), the signed speeds (B,), `cur_index` (B,), the pieces, and the nominal
+        controls (B, 2, T) - None while the device still holds every member's"""
         B, T = len(self.members), self.members[0].receding
-        st, cur = np.zeros((B, 3)), np.zeros(B, np.int32)
+        st, speed, cur = np.zeros((B, 3)), np.zeros(B), np.zeros(B, np.int32)
         pieces, resident = [], True
         for i, m in enumerate(self.members):
             cur_ref_path, gear = m._piece(states[i])
             m._sync_path(cur_ref_path)
             st[i] = np.asarray(m.state, float).ravel()[0:3]
-            self._speed[i] = gear * ref_speeds[i]
-            cur[i] = m.cur_index
+            speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
             resident = resident and m._nominal_u() is None
             pieces.append(cur_ref_path)
-        if stage is not None:
-            stage(st)
-        elif not self._stage_all(obstacle_lists, st):
-            for i, m in enumerate(self.members):
-                m._stage_obstacles(obstacle_lists[i])
         nom_u = None
         if not resident:            # some member's cur_vel_array was replaced since its last solve: send them all
             for i, m in enumerate(self.members):
                 self._in_u[i] = f64(m.cur_vel_array, (2, T))
             nom_u = self._in_u
+        return st, speed, cur, pieces, nom_u
+
+    def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
+        """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the
+        signed speed and the path index travel"""
+        B, T = len(self.members), self.members[0].receding
+        st, speed, cur, pieces, nom_u = self._gather(states, ref_speeds)
+        if stage is not None:
+            stage(st)
+        elif not self._stage_all(obstacle_lists, st):
+            for i, m in enumerate(self.members):
+                m._stage_obstacles(obstacle_lists[i])
         mi, eh = np.zeros(B, np.int32), np.zeros(B)
-        rc = self.api.fleet_step_tracked(self._handle, dptr(st), dptr(self._speed), iptr(cur), float(threshold), int(ind_range),
+        rc = self.api.fleet_step_tracked(self._handle, dptr(st), dptr(speed), iptr(cur), float(threshold), int(ind_range),
                                          dptr(nom_u), dptr(self._out_u), dptr(self._out_s), self._info, dptr(self._ref),
                                          iptr(mi), dptr(eh))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_step_tracked failed with code {rc}")
+            raise self.api.failed("fleet_step_tracked", rc)
         out = []
         for i, m in enumerate(self.members):
             if self._info[i].su_status and m.rda.time_print:

@@ -41,7 +41,7 @@ class _Backend:
         else:
             rc = api.create(C.byref(cfg), dptr(G), dptr(h), C.byref(self.handle))
         if rc != 0:
-            raise RuntimeError(f"{api.prefix}_create failed with code {rc}")
+            raise api.failed("create", rc)
 
     def close(self):
         if self.handle:
@@ -354,7 +354,7 @@ class RDA_solver:
                                      iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob), int(bool(order)),
                                      dptr(out_u), dptr(out_s), C.byref(info_c))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_step_scene failed with code {rc}")
+            raise self._be.api.failed("step_scene", rc)
         if info_c.su_status and self.time_print:
             print("No update of state and control vector")        # reference :699
         self._timing_report(info_c, start)
@@ -369,13 +369,13 @@ class RDA_solver:
         rc = self._be.api.upload_scene(self._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob),
                                        int(bool(order)), None)
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_upload_scene failed with code {rc}")
+            raise self._be.api.failed("upload_scene", rc)
 
     def upload_obstacles(self, obstacle_list):
         n_obs, A, b, cone, per_t = self._stage(obstacle_list)
         rc = self._be.api.upload_obstacles(self._be.handle, n_obs, dptr(A), dptr(b), iptr(cone), per_t)
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_upload_obstacles failed with code {rc}")
+            raise self._be.api.failed("upload_obstacles", rc)
 
     def pack_info(self, ref_states, out_s, info_c, start):
         """the `info` dict of the reference (:603-608) plus the solver counters"""
@@ -402,7 +402,7 @@ class RDA_solver:
         P = np.ascontiguousarray(np.hstack(ref_path)[0:3, :].T, dtype=float)
         rc = self._be.api.upload_path(self._be.handle, int(P.shape[0]), dptr(P))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_upload_path failed with code {rc}")
+            raise self._be.api.failed("upload_path", rc)
 
     def iterative_solve_tracked(self, state, ref_speed, cur_index, nom_u=None, threshold=0.1, ind_range=10):
         """`iterative_solve` with MPC.pre_process (nominal roll-out, closest waypoint, arc-length reference sampling)
@@ -418,7 +418,7 @@ class RDA_solver:
         rc = self._be.api.step_tracked(self._be.handle, dptr(st), float(ref_speed), int(cur_index), float(threshold), int(ind_range),
                                        dptr(un), dptr(out_u), dptr(out_s), C.byref(info_c), None, dptr(ref), iptr(mi), dptr(eh))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_step_tracked failed with code {rc}")
+            raise self._be.api.failed("step_tracked", rc)
         if info_c.su_status and self.time_print:
             print("No update of state and control vector")        # reference :699
         self._timing_report(info_c, start)
@@ -440,7 +440,7 @@ class RDA_solver:
         rc = self._be.api.tracked_begin(self._be.handle, dptr(st), float(ref_speed), int(cur_index), float(threshold),
                                         int(ind_range), dptr(un))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_tracked_begin failed with code {rc}")
+            raise self._be.api.failed("tracked_begin", rc)
 
     def upload_scene_async(self, scene, robot_xy, order):
         """`upload_scene` inside an open tick: staged on the stream behind the first su-problem, no wait"""
@@ -451,7 +451,7 @@ class RDA_solver:
         rc = self._be.api.upload_scene_async(self._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob),
                                              int(bool(order)))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_upload_scene_async failed with code {rc}")
+            raise self._be.api.failed("upload_scene_async", rc)
 
     def scene_resort(self, robot_xy):
         """re-rank the RESIDENT raw scene by distance to `robot_xy` and rebuild the obstacle slots on the device (the reference's per-tick
@@ -459,7 +459,7 @@ class RDA_solver:
         rob = f64(np.asarray(robot_xy, float).ravel()[0:2])
         rc = self._be.api.scene_resort(self._be.handle, dptr(rob))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_scene_resort failed with code {rc}")
+            raise self._be.api.failed("scene_resort", rc)
 
     # ---- lidar front end on the device (rda_scan_boxes / rda_upload_scan; host specification: lidar.py) ---------------------
     @property
@@ -481,7 +481,7 @@ class RDA_solver:
         boxes, n, labels = np.zeros((cap, 4, 2)), np.zeros(1, np.int32), np.zeros(cap, np.int32)
         rc = self._be.api.scan_boxes(*head, iptr(n), dptr(boxes), cap, iptr(labels))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_scan_boxes failed with code {rc}")
+            raise self._be.api.failed("scan_boxes", rc)
         return (boxes[:n[0]], labels[:keep[0].size]) if with_labels else boxes[:n[0]]
 
     def upload_scan(self, state, scan_data, eps=2.0, min_samples=6, order=True):
@@ -491,7 +491,7 @@ class RDA_solver:
         n = np.zeros(1, np.int32)
         rc = self._be.api.upload_scan(*head, int(bool(order)), iptr(n))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_upload_scan failed with code {rc}")
+            raise self._be.api.failed("upload_scan", rc)
         return int(n[0])
 
     def iterative_solve_staged(self, nom_s, nom_u, ref_states, ref_speed):
@@ -523,7 +523,7 @@ class RDA_solver:
         if discard:
             return None
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_tracked_finish failed with code {rc}")
+            raise self._be.api.failed("tracked_finish", rc)
         if info_c.su_status and self.time_print:
             print("No update of state and control vector")        # reference :699
         self._timing_report(info_c, self._tick_start)
@@ -577,7 +577,7 @@ class RDA_solver:
                                n_obs, dptr(A), dptr(b), iptr(cone), per_t, dptr(out_u), dptr(out_s),
                                C.byref(info_c))
         if rc < 0:
-            raise RuntimeError(f"{self._be.api.prefix}_step failed with code {rc}")
+            raise self._be.api.failed("step", rc)
         if info_c.su_status and self.time_print:
             print("No update of state and control vector")        # reference :699
         self._timing_report(info_c, start)

@@ -61,7 +61,7 @@ class ShardedRDA:
 
         def ok(rc, what):           # never `assert` a call with side effects: python -O would drop the call itself
             if rc != 0:
-                raise RuntimeError(f"{api.prefix}_{what} failed with code {rc}")
+                raise api.failed(what, rc)
         ok(api.upload_obstacles(h, n_obs, dptr(A), dptr(b), iptr(cone), per_t), "upload_obstacles")
         ok(api.admm_begin(h, dptr(nom_s), dptr(nom_u), dptr(ref), float(ref_speed)), "admm_begin")
         stopped = C.c_int(0)

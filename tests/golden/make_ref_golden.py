@@ -22,7 +22,6 @@ ref_problems.npz  - mode "ipm": LamMuZ and su problems BUILT BY THE REFERENCE's 
                     generic interior-point stand-in: inputs in the layout of rda_lammuz_batch / rda_su_solve and the unique part
                     of the answers (LamMuZ: optimal value, min(Im, 0), Hm; su: s, u, d).
 """
-import ctypes as C
 import os
 import sys
 
@@ -280,7 +279,6 @@ if __name__ == "__main__":
     if backend == "cvxpy":
         SUFFIX, INJECT_ORACLE = "_cvxpy", False
     orc = orc_api()
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     if args.only_na:
         lammuz_problems_nonaccelerated(rs, mp)

@@ -10,7 +10,6 @@ What is compared per step
     iters    ADMM iteration counts (early stop, rda_solver.py:594)
     status   su-solves that did not converge (either side)
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -98,10 +97,6 @@ def run_soak(scenes=12, steps=100, seed=0, lmz_central=0.0, cold_oracle=False, o
     if so:
         from rda_planner_amd import _lib
         _lib.SO_PATH = os.path.abspath(so)
-    lib.orc_set_su_dump.argtypes = [C.c_char_p]
-    lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
-    lib.orc_set_threads.argtypes = [C.c_int]
-    lib.orc_set_lmz_ipm_mu.argtypes = [C.c_double]
     if su_dump:
         os.makedirs(os.path.dirname(os.path.abspath(su_dump)), exist_ok=True)
         lib.orc_set_su_dump(os.path.abspath(su_dump).encode())

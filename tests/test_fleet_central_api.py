@@ -35,9 +35,8 @@ def test_fleet_lammuz_kernel_is_declared_exported_and_bound():
 def test_header_and_strerror_state_the_rules():
     doc = " ".join(_header(comments=True).split())
     assert "ALL members or NONE" in doc and "lmz_mu may differ per member" in doc and "norm2 (circle) robot is refused" in doc
-    lib = _lib()
-    lib.rda_strerror.restype, lib.rda_strerror.argtypes = C.c_char_p, [C.c_int]
-    msg = lib.rda_strerror(RDA_ERR_UNSUPPORTED).decode()
+    from rda_planner_amd._capi import CApi
+    msg = CApi(_lib(), "rda").strerror(RDA_ERR_UNSUPPORTED).decode()
     assert "norm2 robot" in msg and "mixed LamMuZ modes in a fleet" in msg and "interior-point mode in a fleet" not in msg
 
 

@@ -21,7 +21,6 @@ HIP-vs-oracle test (tests/helpers.py, where the reason for its size is written d
     compared at TOL_U with no exclusion.
 Measured values are printed by the tests (run with -s).
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -36,8 +35,6 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture()
 def cold_orc(orc):
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
-    orc.lib.orc_set_threads.argtypes = [C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     orc.lib.orc_set_threads(16)
     yield orc

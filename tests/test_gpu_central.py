@@ -8,7 +8,6 @@ Both return the point of the central path of the reference's cone program at the
 function of the data - so the two implementations agree to ~1e-5 in the duals (un-normalised half-spaces put factors of 100 between
 a multiplier and Im) and within the stated 1e-4 closed-loop tolerance of tests/test_gpu_baseline_sizes.py in the controls.
 Covers the norm2 (circle) ROBOT cone of rda_solver.py:1034-1039, which the enumeration kernels do not have."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -20,8 +19,6 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture()
 def central_orc(orc):
-    orc.lib.orc_set_lmz_ipm_mu.argtypes = [C.c_double]
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_lmz_mode(1)
     yield orc
     orc.lib.orc_set_lmz_mode(0)
@@ -92,7 +89,6 @@ def test_norm2_robot_is_not_rejected_any_more(hip):
 def test_central_path_at_the_north_star_size(central_orc):
     """T=20, N=200 (4000 sub-problems per launch: the size the kernel's launch time is quoted on), robust mode mu = 1e-3"""
     from test_gpu_baseline_sizes import _workload
-    central_orc.lib.orc_set_threads.argtypes = [C.c_int]
     central_orc.lib.orc_set_threads(16)
     try:
         car_t, path, obstacles, kw = _workload(200, 20, 40)

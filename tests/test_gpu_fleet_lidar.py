@@ -66,7 +66,6 @@ def _same_slots(a, b):
 # ---- this file's own ---------------------------------------------------------------------------------------------------------------------------------
 def _slot_src(mpc):
     lib = mpc.rda._be.api.lib
-    lib.rda_debug_slot_src.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     N = mpc.rda.max_obs_num
     src, used = (C.c_int32 * N)(), C.c_int32(0)
     assert lib.rda_debug_slot_src(mpc.rda._be.handle, src, C.byref(used)) == 0

@@ -140,9 +140,7 @@ class Twin:
 
     def staged(self, i):
         src, used = (C.c_int32 * N)(), C.c_int32(0)
-        fn = self.hip.lib.rda_debug_slot_src
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int
-        assert fn(self.svs[i]._be.handle, src, C.byref(used)) == 0
+        assert self.hip.lib.rda_debug_slot_src(self.svs[i]._be.handle, src, C.byref(used)) == 0
         return sorted(src[:used.value])
 
     def host_tick(self, st, cur, first, geom=None, order=None, resort=False):

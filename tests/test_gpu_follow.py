@@ -61,7 +61,6 @@ def test_result_does_not_depend_on_the_slot_order(n_obs, moving):
 def _slot_src(mpc):
     from rda_planner_amd._lib import hip_api
     lib = hip_api().lib
-    lib.rda_debug_slot_src.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     N = mpc.rda.max_obs_num
     src, used = (C.c_int32 * N)(), C.c_int32(0)
     assert lib.rda_debug_slot_src(mpc.rda._be.handle, src, C.byref(used)) == 0
@@ -80,7 +79,6 @@ def test_obstacles_entering_and_leaving_the_slots_match_the_oracle(n_obs, slots,
     gpu = MPC(car_t, [p.copy() for p in path], duals_follow_obstacles=True, **kw)
     papi = PiecewiseOracle(orc_api(), kw["iter_num"])
     cpu = MPC(car_t, [p.copy() for p in path], _backend=lambda cfg, G, h: _Backend(papi, cfg, G, h), **kw)
-    orc_api().lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc_api().lib.orc_set_su_warm(0.0, 0.0, 0)                   # the cold oracle: the independent checker
     try:
         state = path[0].copy().reshape(3, 1)

@@ -68,7 +68,6 @@ def test_hard_start_same_loop_fewer_iterations_no_lock_out(hip):
 
 def test_hard_start_equals_the_oracle_with_the_mirrored_rule(hip, orc):
     from oracle.oracle_backend import oracle_backend
-    orc.lib.orc_set_su_hard_warm.argtypes = [C.c_double, C.c_double]
     orc.lib.orc_set_su_hard_warm(1.0, 1e-3)
     uc, ipmc, itsc = _loop(True, None, backend=oracle_backend, steps=30)
     per_c = list(_loop.per_step)
@@ -90,7 +89,6 @@ def test_safety_net_hands_back_the_best_near_converged_iterate(hip, orc, T, N, d
     remembered iterate): the result must be a solve of that class - next to the converged one, and next to the oracle's remembered iterate."""
     from rda_planner_amd._capi import Opts, dptr
     import helpers as hp
-    orc.lib.orc_set_su_accept.argtypes = [C.c_int]
     rng = np.random.default_rng(100 + T)
     cfg = hp.make_cfg(T=T, N=N, dynamics=dyn)
     inp = hp.su_inputs(rng, cfg)
@@ -137,7 +135,6 @@ def test_last_resort_attempt_converges_on_every_recorded_hard_instance_like_the_
     s, u, d, it = np.zeros((3, T + 1)), np.zeros((2, T)), np.zeros(T), C.c_int(0)
     st = hip.lib.rda_su_solve_opts(C.byref(cfg), C.byref(o), dptr(inp["nom_s"]), dptr(inp["nom_u"]), dptr(inp["ref"]), inp["vref"], dptr(inp["a"]),
                                    dptr(inp["cc"]), dptr(inp["g"]), dptr(inp["d0"]), dptr(s), dptr(u), dptr(d), C.byref(it))
-    orc.lib.orc_set_su_first_attempt.argtypes = [C.c_int]
     try:
         orc.lib.orc_set_su_first_attempt(1)
         so = hp.su_solve(orc.lib.orc_su_solve, cfg, inp)

@@ -24,7 +24,6 @@ TOL_U_LANDED = 1e-9            # applied control and whole horizon, GPU (landed)
 
 @pytest.fixture()
 def landed_cold_orc(orc):
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     orc.lib.orc_set_su_land(1)
     orc.lib.orc_set_threads(16)

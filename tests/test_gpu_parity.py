@@ -476,7 +476,6 @@ def test_su_weakly_active_instances_from_the_round4_soak(orc, hip, name):
     - within 5e-5, a tenth of the stated closed-loop tolerance of the interior-point-only mode (rounds 4-5).  Round 6: the kernel's solve is LANDED (default):
     it ends on the vertex the tight oracle converges to (8e-9 .. 1e-9: what that interior point is still short of it)"""
     import ctypes as C
-    orc.lib.orc_set_su_tol.argtypes = [C.c_double] * 3
     cfg, inp = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", name + ".npz"))
     try:
         orc.lib.orc_set_su_tol(1e-12, 1e-12, 1e-15)
@@ -538,7 +537,6 @@ def test_closed_loop_dynamic_obs_example(orc):
     def car_of(env):
         ri = env.get_robot_info()
         return sc.car(ri.G, ri.h, ri.cone_type, ri.wheelbase, [10, 1], [10, 1.0], "acker")
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     try:
         env = irsim.make(yaml_path)

@@ -22,7 +22,6 @@ def _first_launch_worklist(order, moving, n_obs=600, T=20, steps=14):
     mpc = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, receding=T, iter_num=1, max_edge_num=4, max_obs_num=n_obs,
               ro1=200, obstacle_order=order)
     lib = hip_api().lib
-    lib.rda_debug_worklist.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     assert lib.rda_lammuz_kernel(mpc.rda._be.handle) is not None
     state = path[0].copy().reshape(3, 1)
     rows, hist = C.c_int(0), []
@@ -78,7 +77,6 @@ def test_flushing_the_supports_cache_mid_loop_changes_no_bit(n_obs, order, movin
     a = MPC(car_t, [p.copy() for p in path], **kw)
     b = MPC(car_t, [p.copy() for p in path], **kw)
     lib = hip_api().lib
-    lib.rda_debug_flush_supports.argtypes = [C.c_void_p]
     state = path[0].copy().reshape(3, 1)
     for k in range(18):
         cur = obstacles if not moving else [o._replace(vertex=o.vertex + o.velocity * (0.1 * k)) if o.cone_type == "Rpositive" else o._replace(center=o.center + o.velocity * (0.1 * k))

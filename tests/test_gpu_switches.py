@@ -198,8 +198,6 @@ def test_su_tol_early_saves_interior_point_iterations_and_stays_near_the_default
     fast = MPC(car_t, [p.copy() for p in path], hip_opts=hip_options(su_tol_early=early), **kw)
     cpu = MPC(car_t, [p.copy() for p in path], _backend=oracle_backend, **kw)
     lib = orc_api().lib
-    lib.orc_set_su_tol_early.argtypes = [C.c_double] * 3
-    lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     lib.orc_set_su_tol_early(*early); lib.orc_set_su_warm(0.0, 0.0, 0)
     try:
         st = path[0].copy().reshape(3, 1)

@@ -33,13 +33,7 @@ def emu():
 
 
 def _oracle(orc):
-    L = orc.lib
-    L.orc_lammuz_ipm_one.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, C.c_double, c_double_p,
-                                     c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_double_p,
-                                     c_double_p, c_double_p, c_int_p]
-    L.orc_lammuz_ipm_one.restype = C.c_int
-    L.orc_set_lmz_ipm_mu.argtypes = [C.c_double]
-    return L
+    return orc.lib
 
 
 def _case(rng, E, circle_obstacle):

@@ -298,11 +298,6 @@ def test_ipm_norm2_robot_certifies_exactly_the_geometric_distance(orc):
     import ctypes as C
     from rda_planner_amd._capi import c_double_p, c_int_p, dptr
     L = orc.lib
-    L.orc_lammuz_ipm_one.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, C.c_double, c_double_p,
-                                     c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_double_p,
-                                     c_double_p, c_double_p, c_int_p]
-    L.orc_lammuz_ipm_one.restype = C.c_int
-    L.orc_set_lmz_ipm_mu.argtypes = [C.c_double]
     L.orc_set_lmz_ipm_mu(0.0)
     r = 0.8
     G = np.ascontiguousarray([[1.0, 0.0], [0.0, 1.0], [0.0, 0.0]])

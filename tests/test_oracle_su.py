@@ -222,8 +222,6 @@ def test_stop_tolerance_vs_weakly_active_rows(orc, name):
     tolerances of the reference's solver (1e-8 throughout) lands 2e-4 ... 3e-3 away.  The TOL_U = 5e-4 of rounds 3-5 (TOL_U_IP today: the interior-point-only
     mode) sits between the two; the landed solve of round 6 is checked against the same three problems below."""
     import os
-    import ctypes as C
-    orc.lib.orc_set_su_tol.argtypes = [C.c_double] * 3
     cfg, si = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", name + ".npz"))
     try:
         orc.lib.orc_set_su_tol(1e-12, 1e-12, 1e-15)
@@ -257,13 +255,10 @@ def test_warm_started_su_reaches_the_cold_solution():
     from the same solver state must coincide to the solver tolerance, with the same ADMM iteration count.  What the warm start
     saves depends on the workload (one interior-point iteration per solve on the N=200 benchmark, nothing on this small scene);
     it must not cost more than a few per cent anywhere."""
-    import ctypes as C
     from oracle.oracle_backend import api, oracle_backend
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.mpc import MPC
     lib = api().lib
-    lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
-    lib.orc_set_su_warm.restype = None
     try:
         for dyn in ("acker", "diff", "omni"):
             car_t = sc.rectangle_robot(dynamics=dyn, wheelbase=3.0 if dyn == "acker" else 0)
@@ -327,10 +322,8 @@ def test_end_game_lost_in_rounding_returns_the_near_converged_iterate(orc):
     orc_set_su_accept, since round 5 also rda_opts::su_accept of the kernel) returned its remembered iterate instead of `no update`.  Round 5: the
     last-resort attempt is a plain long-step path-following iteration and CONVERGES here (16 + 20 iterations), with or without the net; the net's
     own hand-over is exercised by its test switch (accept = 2: always hand the remembered iterate back).  Either way the point is a minimiser to 1e-6."""
-    import ctypes as C
     import os
     cfg, si = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", "omni_T25_N20_end_game_noise.npz"))
-    orc.lib.orc_set_su_accept.argtypes = [C.c_int]
     try:
         orc.lib.orc_set_su_accept(0)
         st0, _, u0, _, it0 = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
@@ -367,11 +360,9 @@ def test_warm_start_after_an_unconverged_step_saves_iterations_and_moves_nothing
     is locked out of its easy start: a hard-started solve costs three iterations whatever the problem).
     Same su-problems, same stop tolerance: fewer interior-point iterations,
     the controls of the closed loop within 1e-4; a loop whose steps converge never sees the rule (bit-identical)."""
-    import ctypes as C
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.mpc import MPC
     from oracle.oracle_backend import oracle_backend
-    orc.lib.orc_set_su_hard_warm.argtypes = [C.c_double, C.c_double]
     car_t = sc.rectangle_robot(dynamics="acker")
     path = sc.line_path([4, 25, 0], [40, 25, 0], 0.1)
     clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])
@@ -410,12 +401,10 @@ def test_landing_makes_the_su_answer_independent_of_the_interior_point_path(orc,
     interior-point paths - warm starts that mirror the kernel's start rules, and cold starts - step by step from the same solver state.  Without the
     landing the two stop at different points of the central path (1e-6 .. 4e-5 apart in the controls: a row that is only just active keeps the slack
     mu / lam*); landed, both end on the same vertex: 1e-10."""
-    import ctypes as C
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.mpc import MPC
     from rda_planner_amd import scenarios as sc
     lib = orc.lib
-    lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     car_t = sc.rectangle_robot(dynamics="acker")
     path = sc.line_path([4, 25, 0], [40, 25, 0], 0.1)
     clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])

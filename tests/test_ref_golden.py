@@ -90,7 +90,6 @@ def _replay(make_solver, name, tol_state, tol_u, digest_tol):
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture()
 def cold_orc(orc):
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     orc.lib.orc_set_su_land(0)          # (the plumbing fixtures were recorded with the oracle's interior-point argmins injected: make_ref_golden.py, before the landing)
     yield orc

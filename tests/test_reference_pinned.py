@@ -121,7 +121,6 @@ def _shim_on_path():
 @pytest.fixture()
 def cold_orc(orc):
     """the oracle's pure hooks start cold; make `orc_admm_su` do the same so both sides call the same function"""
-    orc.lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     orc.lib.orc_set_su_warm(0.0, 0.0, 0)
     yield orc
     orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
@@ -567,15 +566,7 @@ def test_reference_su_problem_vs_oracle_argmin(ref, orc, dyn, accelerated):
 # the interior-point restatement of one sub-problem (oracle/lmz_ipm.c) on the reference's own one-stage problems
 # ---------------------------------------------------------------------------------------------------------
 def _ipm_api(orc):
-    from rda_planner_amd._capi import c_double_p, c_int_p
-    L = orc.lib
-    L.orc_lammuz_ipm_one.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, C.c_double, c_double_p,
-                                     c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_double_p,
-                                     c_double_p, c_double_p, c_int_p]
-    L.orc_lammuz_ipm_one.restype = C.c_int
-    L.orc_set_lmz_ipm_mu.argtypes = [C.c_double]
-    L.orc_set_lmz_ipm_tol.argtypes = [C.c_double]
-    return L
+    return orc.lib
 
 
 @pytest.mark.parametrize("robot", ["rectangle", "circle"])

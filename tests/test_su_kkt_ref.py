@@ -283,7 +283,6 @@ def test_rebuilt_su_problems_equal_what_the_oracle_solves(orc, tmp_path, name):
     is what orc_admm_su records (orc_set_su_dump) bit for bit; the oracle's in-loop answers are within TOL_U_FIXED of the certified optimum"""
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.rda_solver import RDA_solver
-    orc.lib.orc_set_su_dump.argtypes = [C.c_char_p]
     dump = tmp_path / "su.bin"
     rebuilt, worst = [], [0.0]
 

@@ -1,6 +1,5 @@
 """how far do two identical loops drift when one forgets its remembered supports before every third step (diagnostic of
 tests/test_gpu_supports.py::test_flushing_the_supports_cache_mid_loop_changes_no_bit)"""
-import ctypes as C
 import sys
 import numpy as np
 from rda_planner_amd import scenarios as sc
@@ -16,8 +15,6 @@ kw = dict(sample_time=0.1, time_print=False, receding=20, iter_num=3, max_edge_n
 a = MPC(car_t, [p.copy() for p in path], **kw)
 b = MPC(car_t, [p.copy() for p in path], **kw)
 lib = hip_api().lib
-lib.rda_debug_flush_supports.argtypes = [C.c_void_p]
-lib.rda_lammuz_kernel.restype = C.c_char_p
 state = path[0].copy().reshape(3, 1)
 for k in range(18):
     if k % 3 == 2:

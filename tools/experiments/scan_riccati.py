@@ -102,7 +102,6 @@ def scan(Hs, Fs):
 
 if __name__ == "__main__":
     l = _lib(); probs = load(sys.argv[1])
-    l.orc_set_su_dump.argtypes = [__import__("ctypes").c_char_p]
     LD = np.longdouble
     rel = lambda X, R: float(np.abs(X - R.astype(np.float64)).max() / np.abs(R.astype(np.float64)).max())
     print("problem it   mean lam*w   max lam/w   rel err of P_t (worst stage): sequential fp64 | scan fp64 | worst cond(I + C_i J_j)")

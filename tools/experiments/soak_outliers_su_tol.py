@@ -4,7 +4,6 @@ TIGHTER su_tol on both sides (rda_opts::su_tol / orc_set_su_tol): does the diffe
     python tools/experiments/soak_outliers_su_tol.py [--scale 1e-2]
 """
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -23,7 +22,6 @@ if __name__ == "__main__":
     ap.add_argument("--scale", type=float, nargs="+", default=[1.0, 1e-2])
     a = ap.parse_args()
     lib = orc_api().lib
-    lib.orc_set_su_tol.argtypes = [C.c_double] * 3
     for sc_ in a.scale:
         tol = tuple(t * sc_ for t in BASE)
         lib.orc_set_su_tol(*tol)

@@ -4,7 +4,6 @@
 Prints interior-point iterations per su-solve (steps 10.. of each loop).  Round-4 results: floors (1e-3, 1e-3) 7.54, (1e-2, 1e-2) 7.30,
 (0.1, 1e-3) 5.88, (1, 1e-3) 5.29, (1, 1e-2) 5.71, (3, 1e-2) 6.13;  key: north star re-sorted 7.29 -> 5.75, C4 re-sorted 25.5 -> 14.1,
 converged / easy loops unchanged (iter_num = 1 with the first condition alone: 1.0 -> 3.0)."""
-import ctypes as C
 import os
 import sys
 
@@ -16,9 +15,6 @@ from rda_planner_amd import scenarios as sc  # noqa: E402
 from oracle.oracle_backend import oracle_backend, api as orc_api  # noqa: E402
 
 lib = orc_api().lib
-lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
-lib.orc_set_su_hard_warm.argtypes = [C.c_double, C.c_double]
-lib.orc_set_threads.argtypes = [C.c_int]
 lib.orc_set_threads(min(16, os.cpu_count() or 1))
 
 

@@ -18,7 +18,6 @@ from rda_planner_amd import scenarios as sc                    # noqa: E402
 
 def run(n_obs, T, steps, polish, moving=False, tight=False):
     lib = orc_api().lib
-    lib.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
     lib.orc_set_threads(8)
     lib.orc_set_su_land(polish)
     car_t, path, obstacles, kw = bench.build_workload(n_obs=n_obs, T=T, n_steps=steps + 20, moving=moving)

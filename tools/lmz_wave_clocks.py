@@ -4,7 +4,6 @@
 clock64 ticks per section of a wave, summed over the waves of the executed launches of a closed loop; the sections are the LMZ_CLK(k)
 marks of lammuz_body_rows<0> in csrc/rda_hip.hip."""
 import argparse
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -75,7 +74,6 @@ def main():
     lib = _lib.hip_api().lib
     import numpy as np
     W = 4096
-    lib.rda_debug_lmz_clk.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     buf = np.zeros((W, 16), dtype=np.uint64)
     flog = np.zeros(1 + 3 * 200000, dtype=np.int32)
     state = path[0].copy().reshape(3, 1)

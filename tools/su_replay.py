@@ -20,20 +20,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from rda_planner_amd._capi import Cfg, c_double_p, c_int_p  # noqa: E402
-from oracle import oracle_lib  # noqa: E402
+from rda_planner_amd._capi import Cfg, c_double_p  # noqa: E402
+from oracle import oracle_backend  # noqa: E402
 
 
 def _lib():
-    oracle_lib.build(force=False)
-    l = oracle_lib.load()
-    l.orc_su_solve.argtypes = [C.POINTER(Cfg)] + [c_double_p] * 3 + [C.c_double] + [c_double_p] * 7 + [c_int_p]
-    l.orc_su_solve.restype = C.c_int
-    l.orc_set_su_dump.argtypes = [C.c_char_p]
-    l.orc_set_su_trace.argtypes = [C.c_int]
-    l.orc_set_su_warm.argtypes = [C.c_double, C.c_double, C.c_int]
-    l.orc_set_threads.argtypes = [C.c_int]
-    return l
+    return oracle_backend.api().lib
 
 
 SCRATCH = os.environ.get("RDA_SU_REPLAY_DIR", "/tmp/rda_su_replay")     # recordings are tens of MB: kept out of the tree (it travels to the GPU box)

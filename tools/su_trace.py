@@ -37,8 +37,6 @@ def main():
     car_t, path, obstacles, kw = bench.build_workload(n_obs=args.n_obs, T=args.horizon, n_steps=args.steps + 20, moving=args.moving)
     mpc = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, hip_opts=hip_options(su_prof=1), **kw)
     lib = hip_api().lib
-    lib.rda_debug_su_trace.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]
-    lib.rda_debug_su_trace.restype = C.c_int
     cap = 1024
     buf, n = (C.c_longlong * (4 * cap * 2))(), C.c_int(0)
     state = path[0].copy().reshape(3, 1)

@@ -17,7 +17,6 @@ kw["obstacle_order"] = bool(a.order)
 if a.iter_num: kw["iter_num"] = a.iter_num
 mpc = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, **kw)
 lib = hip_api().lib
-lib.rda_debug_worklist.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
 state = path[0].copy().reshape(3, 1); rows = C.c_int(0); hist = []
 for k in range(a.steps):
     cur = obstacles if not a.moving else [o._replace(vertex=o.vertex + o.velocity * (0.1 * k)) for o in obstacles]
