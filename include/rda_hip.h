@@ -223,6 +223,8 @@ int  rda_step_scene(rda_handle *h, const double *nom_s, const double *nom_u, con
 int  rda_get_obstacles(rda_handle *h, double *A, double *b, int32_t *cone, int32_t *nt);
 /* test hook: the resident raw geometry [n][E][2] of the device pipeline as it stands (rda_fleet_rollout_moving advances it on the device); *n = 0: none */
 int  rda_debug_scene_geom(rda_handle *h, double *geom /*n*E*2*/, int32_t *n);
+/* ... and its velocities [n][2] (the peer rows of rda_fleet_upload_scenes_peers are written on the device) */
+int  rda_debug_scene_vel(rda_handle *h, double *vel /*n*2*/, int32_t *n);
 
 /* Device-resident pipeline (what bench.py times): obstacles and a trace of K step inputs are
  * uploaded once; rda_enqueue_step queues the whole ADMM loop of step k on the handle's stream
@@ -427,6 +429,45 @@ int  rda_fleet_rollout_moving(rda_fleet *f, int K, const double *states /*B*3*/,
 /* every member's clearance (as in clearance_log above) at states [B][3] against its resident raw scene as it stands: one launch, one wait.
  * RDA_ERR_UNSUPPORTED: a norm2 robot; RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_clearance(rda_fleet *f, const double *states /*B*3*/, double *clearance /*B*/);
+/* Members that avoid each other: every other member is an ordinary moving polygon obstacle of member i's raw scene, staged on the device
+ * (scene::k_peers_fleet; scenarios.peer_obstacles of the Python package is the specification).  rda_fleet_upload_scenes with a larger scene: member i's
+ * resident raw scene becomes its counts[i] own obstacles followed by B - 1 PEER ROWS, row counts[i] + (j < i ? j : j - 1) for member j: kind 0, nvert R, the
+ * vertices of j's footprint at states[j] - Rot(theta_j) rv_j + p_j, rv_j the body-frame intersections of consecutive rows of j's G x <= h - and the velocity
+ * (v cos a, v sin a), (v, w) = controls[j] the control j applied on the previous tick (zeros before its first tick and once it has arrived), a = theta_j for
+ * Ackermann and differential robots, a = w for omni (the rule of the rollout's kinematic step); products rounded separately.  The conversion kernels are
+ * those of every other scene: peers compete with the own obstacles for the N slots by distance (ranked about states[i], order = 1) and are predicted stage
+ * by stage at constant velocity.  The slots are always built for nt = T + 1 stages, because the host does not see the velocities the device writes.  Every
+ * member's scene set is grown before any is committed; the fleet remembers counts.  Runs on the fleet's stream behind whatever the members have queued and
+ * returns when the staging is done.  B = 1: no peer rows (counts[0] = 0: as rda_upload_scene with n = 0).
+ * RDA_ERR_UNSUPPORTED: a norm2 (circle) robot, a robot whose consecutive rows do not intersect, R > E (a footprint does not fit a polygon row), a member with
+ * rda_opts::duals_follow, a circle obstacle with E < 3.  RDA_ERR_ARG: a missing array, a negative count, nvert outside 0..E, a member inside
+ * rda_tracked_begin.  A refused allocation: RDA_ERR_HIP, fleet and members as they were. */
+int  rda_fleet_upload_scenes_peers(rda_fleet *f, const int32_t *counts /*B*/, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                   const double *vel, const double *states /*B*3*/, const double *controls /*B*2*/);
+/* rda_fleet_scene_resort for such scenes: the peer rows rewritten from states and controls, then the four re-sort launches about states; no waiting, the
+ * next fleet step runs behind it.  RDA_ERR_ARG unless every member's resident raw scene is the one the last rda_fleet_upload_scenes_peers of this fleet staged
+ * (any other staging of a member since ends that).  Plain rda_fleet_scene_resort (and rda_fleet_rollout / _moving) on such scenes stays legal: it treats
+ * the peer rows as the obstacles they are and leaves them where the last refresh put them (rda_fleet_rollout_moving moves and counts them like any row). */
+int  rda_fleet_scene_resort_peers(rda_fleet *f, const double *states /*B*3*/, const double *controls /*B*2*/);
+/* The rollout of such a fleet: rda_fleet_rollout_moving's arguments, logs, arrival rule and refusals without `resort` (every tick re-sorts), plus controls0
+ * [B][2], the controls applied on the tick before this call (zeros at the start of a run; row K - 1 of the previous rollout's u_log to continue one).  Per
+ * tick k, on the fleet's stream: (1) the peer rows from the states at the start of the tick and the controls applied one tick earlier - tick 0: states and
+ * controls0, later: the device logs' states row k and controls row k - 1; (2) the re-sort launches; (3) the tick of rda_fleet_rollout_moving on the OWN rows:
+ * peer rows are neither moved nor snapshotted, and clearance_log stays the clearance against the member's own obstacles; (4) peer_clearance_log [K][B] (may
+ * be NULL): member i's separation from the nearest other member at state k+1 (scenarios.peer_clearance: separating axes of the two footprints, negative =
+ * overlap; +inf for B = 1).  Still one host wait.  Given the states, the previous controls and the own geometry of tick k, a tick computes bit for bit what
+ * rda_fleet_upload_scenes_peers + rda_fleet_step_tracked compute.  After the call the own geometry stands where tick K finds it; the PEER ROWS ARE THOSE OF
+ * TICK K - 1: refresh them (rda_fleet_scene_resort_peers, or the next rollout, which does) before a host-driven tick.  Additional refusal: RDA_ERR_ARG
+ * without controls0 or unless the scenes are those of rda_fleet_upload_scenes_peers.  rda_fleet_rollout_last serves this entry too. */
+int  rda_fleet_rollout_peers(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                             const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                             const double *nom_u /*B*2*T or NULL = resident*/, const double *controls0 /*B*2*/,
+                             double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                             rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                             double *clearance_log /*K*B, or NULL*/, double *peer_clearance_log /*K*B, or NULL*/);
+/* every member's separation from the nearest other member (as in peer_clearance_log above) at states [B][3]: one launch, one wait; needs no staged scene.
+ * RDA_ERR_UNSUPPORTED: a robot the clearance does not take (see rda_fleet_clearance); RDA_ERR_ARG: a member inside rda_tracked_begin. */
+int  rda_fleet_peer_clearance(rda_fleet *f, const double *states /*B*3*/, double *out /*B*/);
 /* A resident WORLD per member: the true obstacles a simulated lidar sees (rda_fleet_raycast, rda_fleet_rollout_lidar), kept apart from the member's raw
  * scene, which a lidar tick overwrites with boxes.  The layout of rda_fleet_upload_scenes with a vertex stride of its own: member i owns counts[i]
  * consecutive entries (0 = an empty world), kind 0 polygon / 1 circle, geom[j] = `we` vertex pairs | centre, (radius, -), 3 <= we <= RDA_EMAX; vel NULL =

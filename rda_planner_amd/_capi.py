@@ -70,6 +70,7 @@ PROTOTYPES = {
     "step_scene":           "i hDDDdiIIDDDiDDN",
     "get_obstacles":        "i hDDII",
     "debug_scene_geom":     "i hDI",
+    "debug_scene_vel":      "i hDI",
     "upload_obstacles":     "i hiDDIi",
     "upload_trace":         "i hiDDDD",
     "enqueue_step":         "i hi",
@@ -103,6 +104,10 @@ PROTOTYPES = {
     "fleet_rollout_last":   "i hDD",
     "fleet_rollout_moving": "i hiDDIdiiiDDDINID",
     "fleet_clearance":      "i hDD",
+    "fleet_upload_scenes_peers": "i hIIIDDDD",
+    "fleet_scene_resort_peers":  "i hDD",
+    "fleet_rollout_peers":  "i hiDDIdiiDDDDINIDD",
+    "fleet_peer_clearance": "i hDD",
     "fleet_upload_worlds":  "i hIiIIDD",
     "fleet_raycast":        "i hIDDDDDD",
     "fleet_rollout_lidar":  "i hiDDIdiiDIDDDDdiIiDDINIID",
@@ -195,6 +200,7 @@ class CApi:
         self.has_fleet_rollout = has("fleet_rollout")                       # K closed-loop ticks on the device, one host wait
         self.has_fleet_rollout_moving = has("fleet_rollout_moving")         # ... for scenes that move
         self.has_fleet_rollout_lidar = has("fleet_rollout_lidar")           # ... around the simulated sensor
+        self.has_fleet_peers = has("fleet_rollout_peers")                   # members as each other's obstacles, staged on the device
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

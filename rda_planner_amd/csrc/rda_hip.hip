@@ -1442,7 +1442,10 @@ struct SceneHost {
     int alloc(size_t n) { bytes = n; return g.pin(&blk, n) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return blk != nullptr; }
 };
-struct SceneSet { SceneDev dev; SceneHost host; scene::Args args; int n = 0; };     // args, n: the resident raw scene as the conversion kernels were last given it (n = 0: none)
+struct SceneSet {                         // args, n: the resident raw scene as the conversion kernels were last given it (n = 0: none)
+    SceneDev dev; SceneHost host; scene::Args args; int n = 0;
+    const void *peers_of = nullptr;       // the fleet whose rda_fleet_upload_scenes_peers staged it (its last B - 1 rows are peer rows), null: any other staging
+};
 // device-side lidar front end (rda_scan_boxes / rda_upload_scan), made by the first scan: the boxes of the last scan on the device; pinned, read / written by
 // the kernel itself: the ranges, the two counters, and the host's copy of labels and boxes
 struct LidarSet {
@@ -1902,7 +1905,7 @@ static scene::Args scene_args(const rda_handle *H, int n, int nt, int order)
 static void scene_bind(rda_handle *H, const scene::Args &a, bool store)
 {
     Dev &d = H->d;
-    if (store) { H->sc.args = a; H->sc.n = a.n; }
+    if (store) { H->sc.args = a; H->sc.n = a.n; H->sc.peers_of = nullptr; }
     d.nt = a.nt; d.obstacle_num = a.N; d.sc_bad = a.nonconvex;
     d.slot_src = H->sc.dev.sel; d.src_used = a.n < a.N ? a.n : a.N;  // the remembered supports follow the obstacles through the re-binding (Dev::hint)
 }
@@ -2003,6 +2006,17 @@ extern "C" int rda_debug_scene_geom(rda_handle *H, double *geom, int32_t *n)
     if (H->tick.scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
     *n = H->sc.n > 0 ? H->sc.n : 0;
     if (*n > 0) HIPCHK(hipMemcpy(geom, H->sc.args.geom, (size_t)*n * H->d.c.E * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return RDA_OK;
+}
+
+// ... and its velocities [n][2] (rda_fleet_upload_scenes_peers: the peer rows' are written on the device)
+extern "C" int rda_debug_scene_vel(rda_handle *H, double *vel, int32_t *n)
+{
+    if (!H || !vel || !n) return RDA_ERR_ARG;
+    HIPCHK(hipStreamSynchronize(H->stream));
+    if (H->tick.scene_on_s2) HIPCHK(hipStreamSynchronize(H->stream2));
+    *n = H->sc.n > 0 ? H->sc.n : 0;
+    if (*n > 0) HIPCHK(hipMemcpy(vel, H->sc.args.vel, (size_t)*n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
 
@@ -3013,6 +3027,13 @@ struct FleetDoubles {                     // v.n doubles, regrown when a call ne
     int alloc(size_t n) { return v.alloc(g, n) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return v.d != nullptr; }
 };
+// members as each other's obstacles (rda_fleet_*_peers, rda_fleet_peer_clearance): the peer table, the states [B][3] and the controls [B][2] of a host-driven
+// refresh or of a rollout's tick 0
+struct FleetPeers {
+    hbuf::Group g; hbuf::Pair<scene::Peer> tab; hbuf::Pair<double> st, ctl;
+    int alloc(size_t B) { return (tab.alloc(g, B) | st.alloc(g, 3 * B) | ctl.alloc(g, 2 * B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return tab.d != nullptr; }
+};
 // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
 // tick overwrites with boxes.  Member-major geometry [total][e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
 // vertex counts; off[i]: member i's first obstacle.  Per member the ray caster's, the move kernel's and the clearance kernel's arguments and the poses of
@@ -3051,6 +3072,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     FleetRollTables ro; FleetRollLog ro_log; int roll_K;      // roll_K: the ticks of the rollout whose logs are on the host
     FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
     FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
+    FleetPeers pe; FleetDoubles pc_log; std::vector<int> n_own;   // pc_log: the peer clearance log; n_own: every member's own obstacles as the last peers upload staged them
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -3551,6 +3573,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
 struct RollArgs {
     int K; const double *states, *ref_speed; const int32_t *cur_index; double threshold; int ind_range, goal_margin; const double *nom_u;
     double *states_log, *u_log; int32_t *index_log; rda_info *info_log; int32_t *arrived_at; double *clearance_log;
+    bool peers = false; const double *controls0 = nullptr; double *peer_clearance_log = nullptr;     // rda_fleet_rollout_peers
 };
 // the argument rules every entry has: of the arrays and counts, and (roll_check_members) of the members' paths
 static int roll_check_args(const rda_fleet *F, const RollArgs &a)
@@ -3591,7 +3614,14 @@ static void member_move_clear(const rda_handle *H, double *geom, double *base, c
 // The moving entry's per-member tables as the members' raw scenes stand now.  mv_total: doubles of all members' raw geometry; gmax: the largest n * E.
 struct MoveView { std::vector<scene::Move> mv; std::vector<rollout::Clear> cl; std::vector<scene::Args> sc; std::vector<size_t> off; size_t mv_total = 0; int gmax = 0, nmax = 0, wmax = 0; };
 static bool member_raw_scene(const rda_handle *H) { return H->sc.n > 0 && H->d.obstacle_num != 0; }
-static void fleet_move_view(const rda_fleet *F, MoveView &v)
+// a member whose resident raw scene is the one this fleet's last peers upload staged: n_own own obstacles and B - 1 peer rows
+static bool member_peers_scene(const rda_fleet *F, size_t i)
+{
+    const rda_handle *H = F->egos[i];
+    return H->sc.peers_of == F && member_raw_scene(H) && F->n_own.size() == (size_t)F->B && H->sc.n == F->n_own[i] + F->B - 1;
+}
+// own: the move and clearance records end at the members' own obstacles (scenes of the peers upload: the peer rows are neither moved nor counted)
+static void fleet_move_view(const rda_fleet *F, MoveView &v, bool own = false)
 {
     const size_t B = F->B;
     v.mv.resize(B); v.cl.resize(B); v.sc.resize(B); v.off.assign(B, 0);
@@ -3601,11 +3631,12 @@ static void fleet_move_view(const rda_fleet *F, MoveView &v)
         scene::Args &a = v.sc[i];
         memset((void *)&a, 0, sizeof(a));
         if (raw) a = H->sc.args;
-        member_move_clear(H, raw ? const_cast<double *>(a.geom) : nullptr, nullptr, a.vel, a.kind, a.nvert, a.n, H->d.c.E, v.mv[i], v.cl[i]);      // (Move::base is set by the rollout)
+        const int nm = own && raw ? F->n_own[i] : a.n;
+        member_move_clear(H, raw ? const_cast<double *>(a.geom) : nullptr, nullptr, a.vel, a.kind, a.nvert, nm, H->d.c.E, v.mv[i], v.cl[i]);      // (Move::base is set by the rollout)
         if (!raw) continue;
         v.off[i] = v.mv_total;                                                    // (its place in the snapshot buffer)
-        v.mv_total += (size_t)a.n * a.E * 2;
-        v.gmax = a.n * a.E > v.gmax ? a.n * a.E : v.gmax;
+        v.mv_total += (size_t)nm * a.E * 2;
+        v.gmax = nm * a.E > v.gmax ? nm * a.E : v.gmax;
         v.nmax = a.n > v.nmax ? a.n : v.nmax; v.wmax = a.N * a.nt > v.wmax ? a.N * a.nt : v.wmax;
     }
 }
@@ -3618,6 +3649,35 @@ static bool member_clearance_ok(const rda_handle *H)
     for (int k = 0; k < R; ++k) { const int j = (k + R - 1) % R; if (G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k] == 0) return false; }
     return true;
 }
+
+// The peer table as the members stand now: every member's footprint and kinematics, and its tail where its scene came from the peers upload
+static void fleet_peer_view(const rda_fleet *F, std::vector<scene::Peer> &v)
+{
+    const size_t B = F->B;
+    v.resize(B);
+    for (size_t i = 0; i < B; ++i) {
+        const rda_handle *H = F->egos[i];
+        scene::Peer &p = v[i];
+        scene::Move m; rollout::Clear c;
+        memset((void *)&p, 0, sizeof(p));
+        member_move_clear(H, nullptr, nullptr, nullptr, nullptr, nullptr, 0, H->d.c.E, m, c);
+        p.E = H->d.c.E; p.R = c.R; p.dynamics = H->d.c.dynamics;
+        memcpy(p.rv, c.rv, sizeof(p.rv));
+        if (!member_peers_scene(F, i)) continue;
+        p.n_own = F->n_own[i];
+        p.geom = const_cast<double *>(H->sc.args.geom) + (size_t)p.n_own * p.E * 2;
+        p.vel = const_cast<double *>(H->sc.args.vel) + (size_t)p.n_own * 2;
+    }
+}
+// scene::k_peers_fleet from states [B][3] and controls [B][2] in device memory; a fleet of one has no peer rows (and a grid of zero blocks is a launch error)
+static void fleet_peers_launch(rda_fleet *F, const double *states, const double *controls)
+{
+    const int B = F->B, E = F->egos[0]->d.c.E;
+    if (B < 2) return;
+    hipLaunchKernelGGL(scene::k_peers_fleet, dim3((unsigned)(((B - 1) * E + 255) / 256), (unsigned)B), dim3(256), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
+                       states, controls, B);
+}
+static_assert(sizeof(((scene::Peer *)nullptr)->rv) == sizeof(((rollout::Clear *)nullptr)->rv), "the peer table takes the clearance record's robot vertices");
 
 // What every rollout reserves before its first tick - the tracker's tables, the rollout tables, a log block of K ticks and (clearance) a clearance log of
 // K * B.  alloc: whatever of it the fleet lacks, beside the fleet, so that a refusal changes nothing; the entry allocates its own sets next to it and, when
@@ -3711,6 +3771,8 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     const size_t T = F->T, nu = traj_u(T), B = F->B, K = a.K;
     const char *log = F->ro_log.log.h;
     if (a.clearance_log) HIPCHK(F->cl_log.v.pull(F->stream, K * B));
+    const bool peer_log = a.peer_clearance_log && B > 1;                        // (a fleet of one: +inf, nothing was launched)
+    if (peer_log) HIPCHK(F->pc_log.v.pull(F->stream, K * B));
     HIPCHK(hipMemcpy2DAsync(F->ro_log.log.d + lay.lastu, nu * sizeof(double), F->out.d, res_info(T) * sizeof(double), nu * sizeof(double), B,
                             hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
     HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
@@ -3725,16 +3787,23 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     if (a.info_log) memcpy(a.info_log, log + lay.info, K * B * sizeof(rda_info));
     memcpy(a.arrived_at, log + lay.arrived, B * sizeof(int32_t));
     if (a.clearance_log) memcpy(a.clearance_log, F->cl_log.v.h, K * B * sizeof(double));
+    if (peer_log) memcpy(a.peer_clearance_log, F->pc_log.v.h, K * B * sizeof(double));
+    else if (a.peer_clearance_log) for (size_t k = 0; k < K; ++k) a.peer_clearance_log[k] = INFINITY;
     return RDA_OK;
 }
 
-// rda_fleet_rollout (moving = false: exactly the static entry) and rda_fleet_rollout_moving share this body
+// rda_fleet_rollout (moving = false: exactly the static entry), rda_fleet_rollout_moving and (a.peers: resort and moving set) rda_fleet_rollout_peers share
+// this body
 static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, bool moving)
 {
     int rc = roll_check_args(F, a);
     if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
+    if (a.peers) {
+        if (!a.controls0) return RDA_ERR_ARG;
+        for (size_t i = 0; i < B; ++i) if (!member_peers_scene(F, i)) return RDA_ERR_ARG;      // the scenes of rda_fleet_upload_scenes_peers, nothing staged since
+    }
     for (const rda_handle *H : F->egos) if (resort && (H->sc.n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
     for (const rda_handle *H : F->egos) {
         if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;                   // (k_follow_* are per member)
@@ -3747,19 +3816,22 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
             if (H->d.obstacle_num != 0 && H->d.nt > 1 && H->sc.n <= 0) return RDA_ERR_UNSUPPORTED;    // host-staged per-stage slots: no raw scene to move
             if (a.clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
         }
-        fleet_move_view(F, mvw);
+        fleet_move_view(F, mvw, a.peers);
     }
+    const bool peer_log = a.peers && a.peer_clearance_log && B > 1;
     // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap;
+    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc;
     {
         int bad = rsv.alloc(F, a.K, a.clearance_log != nullptr);
+        if (peer_log && (size_t)a.K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)a.K * B);
         if (resort && !F->res.have()) bad |= tres.alloc(B);
         if (moving && !F->mov.have()) bad |= tmov.alloc(B);
         if (moving && mvw.mv_total > F->snap.cap) bad |= tsnap.alloc(mvw.mv_total);
         if (bad) return RDA_ERR_HIP;
     }
-    rc = rsv.move_in(F, tsnap.have());
+    rc = rsv.move_in(F, tsnap.have() || tpc.have());
     if (rc != RDA_OK) return rc;
+    if (tpc.have()) F->pc_log = std::move(tpc);
     if (tres.have()) F->res = std::move(tres);
     if (tmov.have()) F->mov = std::move(tmov);
     if (tsnap.have()) F->snap = std::move(tsnap);
@@ -3772,8 +3844,11 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         for (size_t i = 0; i < B; ++i) if (mvw.mv[i].n > 0) mvw.mv[i].base = F->snap.d + mvw.off[i];
         if (mirror_differs(F->mov.mv, records(mvw.mv)) || mirror_differs(F->mov.cl, records(mvw.cl)) || mirror_differs(F->mov.sc, records(mvw.sc))) tables = true;
     }
+    std::vector<scene::Peer> pv;
+    if (a.peers) { fleet_peer_view(F, pv); if (mirror_differs(F->pe.tab, records(pv))) tables = true; }
     if (tables) {
         HIPCHK(hipStreamSynchronize(F->stream));
+        if (a.peers) HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
         if (moving) {
             HIPCHK(mirror_upload(F->mov.mv, records(mvw.mv), F->stream));
             HIPCHK(mirror_upload(F->mov.cl, records(mvw.cl), F->stream));
@@ -3785,6 +3860,10 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     // tick 0's inputs, as rda_fleet_scene_resort and rda_fleet_step_tracked upload them
     int nmax = 0, wmax = 0;
     if (resort) { rc = fleet_resort_positions(F, a.states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
+    if (a.peers) {                                                              // (behind fleet_resort_positions: no copy out of the pinned mirrors is queued)
+        memcpy(F->pe.st.h, a.states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, a.controls0, 2 * B * sizeof(double));
+        HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
+    }
     const RollLayout lay = roll_layout((size_t)a.K, B, T);
     rollout::Logs lg;
     rc = fleet_roll_inputs(F, lay, a, lg);
@@ -3793,11 +3872,16 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
     if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->mov.mv.d);      // `base`: the geometry as the call finds it
     for (int k = 0; k < a.K; ++k) {
+        // the peer rows of tick k: the members' states at its start and the controls applied one tick earlier (tick 0: the caller's, then the device logs)
+        if (a.peers) fleet_peers_launch(F, k == 0 ? F->pe.st.d : lg.states + (size_t)k * B * 3, k == 0 ? F->pe.ctl.d : lg.u + (size_t)(k - 1) * B * 2);
         if (resort) fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);            // about res.rob: the caller's positions (tick 0), then the advance kernel's
         else if (moves) fleet_resort_launch(F, F->mov.sc.d, nullptr, mvw.nmax, mvw.wmax);     // a scene that moved: its slots rebuilt in the staged order
         rc = fleet_roll_tail(F, k, lg, a.goal_margin, resort ? F->res.rob.d : nullptr, moves ? F->mov.mv.d : nullptr, gmove,
                              a.clearance_log ? F->mov.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
+        if (peer_log)
+            hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
+                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->pc_log.v.d + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
     return fleet_roll_fetch(F, lay, a);                                         // the rollout's one wait
@@ -3855,6 +3939,153 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     memcpy(clearance, F->cl_log.v.h, B * sizeof(double));
+    return RDA_OK;
+}
+// ---- members as each other's obstacles (scene::k_peers_fleet, rollout::k_peer_clearance_fleet) ---------------------------------------------------------
+// The refresh of the peer rows from the caller's states and controls and the four re-sort launches behind it, on the fleet's stream
+static int fleet_peers_resort(rda_fleet *F, const double *states, const double *controls)
+{
+    const size_t B = F->B;
+    int nmax = 0, wmax = 0;
+    int rc = fleet_resort_positions(F, states, 3, nmax, wmax);                  // (waits for an earlier copy out of the pinned mirrors)
+    if (rc != RDA_OK) return rc;
+    memcpy(F->pe.st.h, states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, controls, 2 * B * sizeof(double));
+    HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
+    fleet_peers_launch(F, F->pe.st.d, F->pe.ctl.d);
+    fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);
+    HIPCHK(hipGetLastError());
+    return RDA_OK;
+}
+// rda_fleet_upload_scenes with B - 1 peer rows behind every member's own obstacles.  Everything the call needs is allocated before anything of the fleet or
+// of a member changes; the staging runs on the fleet's stream and the call returns when it is done.
+extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                             const double *vel, const double *states, const double *controls)
+{
+    if (!F || !counts || !states || !controls) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    const int E = F->egos[0]->d.c.E, R = F->egos[0]->d.c.R, T = F->T;
+    size_t total = 0;
+    for (size_t i = 0; i < B; ++i) { if (counts[i] < 0) return RDA_ERR_ARG; total += (size_t)counts[i]; }
+    if (total && (!kind || !nvert || !geom || !vel)) return RDA_ERR_ARG;
+    for (const rda_handle *H : F->egos) if (H->tick.pending) return RDA_ERR_ARG;                       // a member inside a tick of its own
+    for (const rda_handle *H : F->egos)
+        if (H->d.c.robot_norm2 || !member_clearance_ok(H) || R > E || H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;      // (a footprint is a polygon row of R <= E vertices)
+    for (size_t e = 0; e < total; ++e) {                                        // scene_stage's rules
+        if (kind[e] == 1) { if (E < 3) return RDA_ERR_UNSUPPORTED; }
+        else if (kind[e] != 0 || nvert[e] < 0 || nvert[e] > E) return RDA_ERR_ARG;
+    }
+    if (B == 1 && counts[0] == 0) { F->egos[0]->d.obstacle_num = 0; return RDA_OK; }      // nothing written: stale A, b stay (rda_upload_scene with n = 0)
+    FleetPeers tpe; FleetResort tres; std::vector<SceneGrow> grow(B);
+    {
+        int bad = 0;
+        if (!F->pe.have()) bad |= tpe.alloc(B);
+        if (!F->res.have()) bad |= tres.alloc(B);
+        for (size_t i = 0; i < B; ++i) bad |= scene_grow_alloc(F->egos[i], counts[i] + (int)B - 1, grow[i]);
+        if (bad) return RDA_ERR_HIP;
+    }
+    int rc = fleet_refresh(F);                          // behind whatever the members still have queued ...
+    if (rc != RDA_OK) return rc;
+    HIPCHK(hipStreamSynchronize(F->stream));            // ... and done: the members' pinned staging blocks are free
+    F->rob_pending = 0;
+    if (tpe.have()) F->pe = std::move(tpe);
+    if (tres.have()) F->res = std::move(tres);
+    F->n_own.assign(counts, counts + B);
+    size_t off = 0;
+    for (size_t i = 0; i < B; ++i) {
+        rda_handle *H = F->egos[i];
+        const size_t own = (size_t)counts[i], n = own + B - 1;
+        H->tick.pending_scene = 0;
+        scene_grow_commit(H, grow[i]);
+        // one pinned staging block -> its device mirror, one copy: the own rows as given; the peer rows as polygons of R vertices, zeroed until k_peers_fleet
+        const SceneLayout l = scene_layout(n, (size_t)E);
+        double *hb = (double *)H->sc.host.blk;
+        memset(hb, 0, l.bytes);
+        if (own) {
+            memcpy(hb, geom + off * E * 2, own * E * 2 * sizeof(double));
+            memcpy(hb + l.vel, vel + off * 2, own * 2 * sizeof(double));
+            memcpy((int *)(hb + l.ints), kind + off, own * sizeof(int));
+            memcpy((int *)(hb + l.ints) + n, nvert + off, own * sizeof(int));
+        }
+        hb[l.robot] = states[3 * i]; hb[l.robot + 1] = states[3 * i + 1];
+        for (size_t r = own; r < n; ++r) ((int *)(hb + l.ints))[n + r] = R;
+        HIPCHK(hipMemcpyAsync(H->sc.dev.blk, hb, l.bytes, hipMemcpyHostToDevice, F->stream));
+        // per-stage slots always: the peer rows' velocities are known on the device only
+        scene_bind(H, scene_args(H, (int)n, T + 1, 1), true);
+        H->sc.peers_of = F;
+        off += own;
+    }
+    std::vector<scene::Peer> pv;
+    fleet_peer_view(F, pv);
+    HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
+    HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
+    fleet_refresh_flags(F);
+    rc = fleet_peers_resort(F, states, controls);
+    if (rc != RDA_OK) return rc;
+    HIPCHK(hipStreamSynchronize(F->stream));            // the staging blocks are reused by the next call; the members' own calls see the scene
+    F->rob_pending = 0;
+    return RDA_OK;
+}
+// rda_fleet_scene_resort for scenes of the peers upload: the peer rows refreshed from states and controls, then the re-sort
+extern "C" int rda_fleet_scene_resort_peers(rda_fleet *F, const double *states, const double *controls)
+{
+    if (!F || !states || !controls) return RDA_ERR_ARG;
+    for (size_t i = 0; i < (size_t)F->B; ++i) {
+        if (!member_peers_scene(F, i) || F->egos[i]->tick.pending) return RDA_ERR_ARG;
+        if (F->egos[i]->opts.duals_follow) return RDA_ERR_UNSUPPORTED;
+    }
+    int rc = fleet_refresh(F);
+    if (rc != RDA_OK) return rc;
+    std::vector<scene::Peer> pv;
+    fleet_peer_view(F, pv);
+    if (mirror_differs(F->pe.tab, records(pv))) {
+        HIPCHK(hipStreamSynchronize(F->stream));
+        HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
+    }
+    return fleet_peers_resort(F, states, controls);
+}
+// The rollout of a fleet whose members see each other: per tick the peer rows, the re-sort, the tick's tail on the own rows, the peer clearance
+extern "C" int rda_fleet_rollout_peers(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                       int ind_range, int goal_margin, const double *nom_u, const double *controls0, double *states_log, double *u_log,
+                                       int32_t *index_log, rda_info *info_log, int32_t *arrived_at, double *clearance_log, double *peer_clearance_log)
+{
+    RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    a.peers = true; a.controls0 = controls0; a.peer_clearance_log = peer_clearance_log;
+    return fleet_rollout_scenes(F, a, 1, true);
+}
+// every member's separation from the nearest other member at states [B][3]: the rollout's kernel, one launch, one wait
+extern "C" int rda_fleet_peer_clearance(rda_fleet *F, const double *states, double *out)
+{
+    if (!F || !states || !out) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    for (const rda_handle *H : F->egos) {
+        if (H->tick.pending) return RDA_ERR_ARG;
+        if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+    }
+    if (B == 1) { out[0] = INFINITY; return RDA_OK; }  // no peer, no launch
+    FleetPeers tpe; FleetDoubles tpc;
+    {
+        int bad = 0;
+        if (!F->pe.have()) bad |= tpe.alloc(B);
+        if (B > F->pc_log.v.n) bad |= tpc.alloc(B);
+        if (bad) return RDA_ERR_HIP;
+    }
+    if (tpc.have() || F->rob_pending) { HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; }
+    if (tpe.have()) F->pe = std::move(tpe);
+    if (tpc.have()) F->pc_log = std::move(tpc);
+    std::vector<scene::Peer> pv;
+    fleet_peer_view(F, pv);
+    if (mirror_differs(F->pe.tab, records(pv))) {
+        HIPCHK(hipStreamSynchronize(F->stream));
+        HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
+    }
+    memcpy(F->pe.st.h, states, 3 * B * sizeof(double));
+    HIPCHK(F->pe.st.push(F->stream));
+    hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d, (const double *)F->pe.st.d,
+                       F->pc_log.v.d, (int)B);
+    HIPCHK(hipGetLastError());
+    HIPCHK(F->pc_log.v.pull(F->stream, B));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    memcpy(out, F->pc_log.v.h, B * sizeof(double));
     return RDA_OK;
 }
 // ---- the members' worlds and the simulated sensor (lidar::k_raycast_fleet) -----------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include <math.h>
 #include "../../include/rda_hip.h"
 #include "track_device.h"
+#include "scene_device.h"
 
 namespace rollout {
 
@@ -146,6 +147,38 @@ __global__ __launch_bounds__(CLEAR_NT) void k_clearance_fleet(const Clear *cs, c
         for (int w = 1; w < CLEAR_NT / 64; ++w) best = fmin(best, part[w]);
         out[b] = best;
     }
+}
+
+// Member-to-member separation (rda_fleet_rollout_peers' peer clearance log, rda_fleet_peer_clearance): scenarios.peer_clearance - for member i the minimum
+// over j != i of _poly_sep(RV_i, RV_j), both footprints rotated and shifted by their states as in k_clearance_fleet.  One wave per member; its lanes stride
+// over the peers, each runs sep_half both ways, the minimum goes through the wave by shuffles (exact: its order is free).  Launched for B >= 2 only.
+__device__ __forceinline__ void peer_footprint(const scene::Peer &p, const double *state, double *fx, double *fy)
+{
+#pragma clang fp contract(off)
+    const double x = state[0], y = state[1], co = cos(state[2]), si = sin(state[2]);
+    for (int v = 0; v < p.R; ++v) {
+        fx[v] = (co * p.rv[v][0] - si * p.rv[v][1]) + x;
+        fy[v] = (si * p.rv[v][0] + co * p.rv[v][1]) + y;
+    }
+}
+__global__ __launch_bounds__(64) void k_peer_clearance_fleet(const scene::Peer *ps, const double *states, double *out, int B)
+{
+    const int i = blockIdx.x;
+    if (i >= B) return;                                   // (uniform)
+    double rx[RDA_RMAX], ry[RDA_RMAX], qx[RDA_RMAX], qy[RDA_RMAX];
+    const int R = ps[i].R;
+    peer_footprint(ps[i], states + 3 * i, rx, ry);
+    double best = INFINITY;
+    for (int j = threadIdx.x; j < B; j += 64) {
+        if (j == i) continue;
+        peer_footprint(ps[j], states + 3 * j, qx, qy);
+        double d = sep_half(rx, ry, R, qx, qy, ps[j].R, -INFINITY);
+        d = sep_half(qx, qy, ps[j].R, rx, ry, R, d);
+        if (d < best) best = d;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) best = fmin(best, __shfl_xor(best, off, 64));
+    if (threadIdx.x == 0) out[i] = best;
 }
 
 }  // namespace rollout

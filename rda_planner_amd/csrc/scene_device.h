@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "../../include/rda_hip.h"
 
 namespace scene {
 
@@ -173,6 +174,42 @@ __global__ void k_move_fleet(const Move *ms, int k)
     const double tk = m.dt * (double)k;
     m.geom[2 * w] = m.base[2 * w] + m.vel[2 * i] * tk;
     m.geom[2 * w + 1] = m.base[2 * w + 1] + m.vel[2 * i + 1] * tk;
+}
+
+// Fleet members as each other's obstacles (rda_fleet_upload_scenes_peers, rda_fleet_scene_resort_peers, rda_fleet_rollout_peers): what
+// scenarios.peer_obstacles builds on the host, written into the B - 1 rows that follow the member's own obstacles in its resident raw scene - blockIdx.y =
+// the member i, one thread per (peer row, vertex entry).  Row r of the tail is member j = r < i ? r : r + 1 (ascending j without i): the R vertices of j's
+// footprint Rot(theta_j) rv_j + p_j (scenarios.robot_vertices; rv: the body-frame vertices the host solves, member_move_clear) and, by the thread of entry
+// 0, the row's velocity (v cos a, v sin a) with (v, w) = controls[j], a = theta_j for acker / diff and a = w for omni (scenarios.kinematic_step's rule).
+// kind = 0, nvert = R and the zero padding of entries >= R are staged by the host once; nothing but the tail rows is written.
+struct Peer {                 // per member: its tail (null before the peers upload) and what the others need of it
+    double *geom;             // first peer row of its raw geometry: Args::geom + n_own * E * 2
+    double *vel;              // ... of its velocities: Args::vel + n_own * 2
+    int n_own, E, R, dynamics;     // own obstacles in front of the tail; vertex stride; robot vertices; rda_cfg::dynamics
+    double rv[RDA_RMAX][2];   // body frame
+};
+__global__ void k_peers_fleet(const Peer *ps, const double *states, const double *controls, int B)
+{
+#pragma clang fp contract(off)
+    const int i = blockIdx.y;
+    const Peer &me = ps[i];
+    const int E = me.E;
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= (B - 1) * E) return;
+    const int r = w / E, v = w - r * E;
+    const int j = r < i ? r : r + 1;
+    const Peer &p = ps[j];
+    if (v >= p.R) return;
+    const double x = states[3 * j], y = states[3 * j + 1], th = states[3 * j + 2];
+    const double co = cos(th), si = sin(th);
+    double *g = me.geom + ((size_t)r * E + v) * 2;
+    g[0] = (co * p.rv[v][0] - si * p.rv[v][1]) + x;
+    g[1] = (si * p.rv[v][0] + co * p.rv[v][1]) + y;
+    if (v == 0) {
+        const double sp = controls[2 * j], a = p.dynamics == 2 ? controls[2 * j + 1] : th;
+        me.vel[2 * r] = sp * cos(a);
+        me.vel[2 * r + 1] = sp * sin(a);
+    }
 }
 
 }  // namespace scene

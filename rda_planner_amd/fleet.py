@@ -70,6 +70,7 @@ class Fleet:
         self._out_u, self._out_s = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1))
         self._info = (Info * B)()
         self.batched_ticks = 0          # ticks whose scenes went through the one-pass staging (diagnostics)
+        self._peers_staged = False      # the members' resident scenes are those of rda_fleet_upload_scenes_peers
 
     def __len__(self):
         return len(self.members)
@@ -89,15 +90,33 @@ class Fleet:
         except Exception:
             pass
 
-    def control(self, states, ref_speeds, obstacle_lists=None, scans=None, scan_eps=2.0, scan_min_samples=6, **kwargs):
+    def control(self, states, ref_speeds, obstacle_lists=None, scans=None, scan_eps=2.0, scan_min_samples=6, peers=False, peer_controls=None, **kwargs):
         """one MPC step of every member: `states[i]`, `ref_speeds[i]` (a scalar is shared) and `obstacle_lists[i]` are
         what `members[i].control` takes; returns the list of its `(u, info)` results.
         scans: instead of obstacle lists, `scans[i]` is the range scan (the dict `MPC.control(scan=)` takes) member i took from
         `states[i]` - all members' scans are clustered, boxed and staged on the device by one library call
-        (rda_fleet_upload_scans); result i is what `members[i].control(states[i], ref_speeds[i], scan=scans[i])` returns."""
+        (rda_fleet_upload_scans); result i is what `members[i].control(states[i], ref_speeds[i], scan=scans[i])` returns.
+        peers=True: the members avoid each other.  Every member's scene is `obstacle_lists[i]` followed by the other members as moving polygon
+        obstacles - their footprints at `states`, their velocity the control `peer_controls[j]` = (v, w) they applied on the previous tick along
+        their heading (default: `members[j].cur_vel_array[:, 0]`, which is zero before the first tick and once the member has arrived) - written on
+        the device by rda_fleet_upload_scenes_peers; result i is what `members[i].control(states[i], ref_speeds[i], obstacle_lists[i] +
+        scenarios.peer_obstacles(cars, states, peer_controls, i))` returns.  Device-tracked members with `obstacle_order=True` and polygon robots only;
+        anything else raises, there is no host fallback."""
         B, start = len(self.members), time.time()
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
+        if peers:
+            if scans is not None:
+                raise ValueError("Fleet.control: peers=True takes obstacle_lists, not scans=")
+            self._check_peers(kwargs)
+            if peer_controls is None:
+                peer_controls = [np.asarray(m.cur_vel_array, float)[:, 0] for m in self.members]
+            if len(peer_controls) != B or (obstacle_lists is not None and len(obstacle_lists) != B):
+                raise ValueError("Fleet.control: one obstacle list and one peer control per member")
+            ctl = f64([np.asarray(c, float).ravel()[0:2] for c in peer_controls], (B, 2))
+            own = obstacle_lists if obstacle_lists is not None else [[] for _ in range(B)]
+            return self._control_tracked(states, ref_speeds, own, start, stage=lambda st: self._stage_peers(own, st, ctl), **kwargs)
+        self._peers_staged = False
         if scans is not None:
             if obstacle_lists is not None and any(len(ol) for ol in obstacle_lists):
                 raise ValueError("Fleet.control: pass either obstacle_lists or scans=, not both")
@@ -171,6 +190,52 @@ class Fleet:
             raise self.api.failed("fleet_upload_scenes", rc)
         self.batched_ticks += 1
         return True
+
+    def _check_peers(self, kwargs):
+        """what peers=True needs of the library and of every member, checked before any library call"""
+        ms = self.members
+        if not getattr(self.api, "has_fleet_peers", False):
+            raise RuntimeError("the loaded solver library has no peer entry points (rda_fleet_upload_scenes_peers, rda_fleet_rollout_peers)")
+        if any(not m.obstacle_order for m in ms):
+            raise RuntimeError("peers=True ranks every member's obstacles and peers by distance: obstacle_order=False is not supported")
+        if any(m.car_tuple.cone_type == "norm2" for m in ms):
+            raise RuntimeError("peers=True stages footprints as polygons; a circle (norm2) robot is not supported")
+        if any(m.rda_obstacle or not m.device_obstacles or not m.rda.has_scene for m in ms):
+            raise RuntimeError("peers=True needs the device-side obstacle pipeline on every member (rda_obstacle=False); there is no host fallback")
+        if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
+            raise RuntimeError("peers=True needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
+
+    def _stage_peers(self, obstacle_lists, st, controls):
+        """`_stage_all` with the other members behind every member's own obstacles (rda_fleet_upload_scenes_peers); st (B, 3), controls (B, 2)"""
+        ms = self.members
+        counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(ms))
+        every = [o for ol in obstacle_lists for o in ol]
+        scene = ms[0].rda.flatten_scene(every)
+        if scene is None or scene[0] != len(every):
+            raise RuntimeError("peers=True: an obstacle cannot be staged through the device pipeline; there is no host fallback")
+        _, kind, nvert, geom, vel = scene
+        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
+        geom = f64(geom); vel = f64(vel)
+        rc = self.api.fleet_upload_scenes_peers(self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(f64(st)), dptr(f64(controls)))
+        if rc < 0:
+            raise self.api.failed("fleet_upload_scenes_peers", rc)
+        self._peers_staged = True
+        self.batched_ticks += 1
+
+    def peer_clearance(self, states):
+        """(B,) every member's separation from the nearest other member at `states` (rda_fleet_peer_clearance: `scenarios.peer_clearance`
+        evaluated on the device, one launch; negative = overlap, +inf for a fleet of one)"""
+        if not getattr(self.api, "has_fleet_peers", False):
+            raise RuntimeError("the loaded solver library has no peer entry points (rda_fleet_peer_clearance)")
+        if any(m.car_tuple.cone_type == "norm2" for m in self.members):
+            raise RuntimeError("Fleet.peer_clearance is for polygon robots; a circle (norm2) robot is not supported")
+        B = len(self.members)
+        st = states_array(states, B)
+        out = np.zeros(B)
+        rc = self.api.fleet_peer_clearance(self._handle, dptr(st), dptr(out))
+        if rc < 0:
+            raise self.api.failed("fleet_peer_clearance", rc)
+        return out
 
     def _scan_arrays(self, states, scans):
         """the member-major arrays of rda_fleet_scan_boxes / rda_fleet_upload_scans"""
@@ -282,9 +347,23 @@ class Fleet:
         every member's world is ray-cast from its pose on the device, the scan is clustered, boxed and staged as `control(scans=)` does (`scan_eps`,
         `scan_min_samples`, the member's `obstacle_order`) with one short wait for the B box counts, then the tick runs as above.  `moving=True` puts
         the WORLD forward between ticks by the rule above, `clearance=True` logs the clearance against the world (the true obstacles, not the boxes;
-        no `moving` needed).  The result has `"boxes"` (steps, B) as well: the boxes every member saw.  `resort` and `obstacle_lists` do not apply."""
+        no `moving` needed).  The result has `"boxes"` (steps, B) as well: the boxes every member saw.  `resort` and `obstacle_lists` do not apply.
+        `peers=True` (rda_fleet_rollout_peers): the members avoid each other as in `control(peers=True)`.  Before every tick the device rewrites the
+        peer obstacles of every member's scene from the states of that tick and the controls applied on the tick before (tick 0: every member's
+        `cur_vel_array[:, 0]`), re-sorts, and runs the tick of `moving=True` on the member's own obstacles.  `obstacle_lists=` is required on the first
+        call and optional once such scenes are resident.  The result always has `"peer_clearance"` (steps, B): every member's separation from the
+        nearest other member after each tick (`scenarios.peer_clearance`; negative = overlap); `clearance=True` keeps its meaning (own obstacles
+        only).  `resort` does not apply, `lidar=` / `scans=` cannot be combined with it, and it has the refusals of `control(peers=True)`."""
         ms = self.members
         kwargs = dict(kwargs)
+        peers = bool(kwargs.pop("peers", False))
+        if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
+            raise ValueError("Fleet.rollout: peers=True cannot be combined with lidar= / scans=")
+        if peers:
+            self._check_peers({k: v for k, v in kwargs.items() if k in ("threshold", "ind_range")})
+            if kwargs.get("obstacle_lists") is None and not getattr(self, "_peers_staged", False):
+                raise ValueError("Fleet.rollout: peers=True needs obstacle_lists= until such scenes are resident")
+            kwargs["moving"] = True                      # (the peers rollout is a moving rollout)
         obstacle_lists, moving, clearance = kwargs.pop("obstacle_lists", None), bool(kwargs.pop("moving", False)), bool(kwargs.pop("clearance", False))
         lidar, world = kwargs.pop("lidar", None), kwargs.pop("world", None)
         scan_eps, scan_min_samples = float(kwargs.pop("scan_eps", 2.0)), int(kwargs.pop("scan_min_samples", 6))
@@ -320,16 +399,24 @@ class Fleet:
         st, speed, cur, _, nom_u = self._gather(states, ref_speeds)
         if world is not None:
             self.upload_worlds(world)
-        if obstacle_lists is not None and not self._stage_all(obstacle_lists, st):
-            for i, m in enumerate(ms):
-                m._stage_obstacles(obstacle_lists[i])
+        ctl0 = f64([np.asarray(m.cur_vel_array, float)[:, 0] for m in ms], (B, 2)) if peers else None
+        if peers and obstacle_lists is not None:
+            self._stage_peers(obstacle_lists, st, ctl0)
+        elif obstacle_lists is not None:
+            self._peers_staged = False
+            if not self._stage_all(obstacle_lists, st):
+                for i, m in enumerate(ms):
+                    m._stage_obstacles(obstacle_lists[i])
         s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
         i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
         infos = (Info * (max(K, 1) * B))()
         head = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)), margins.pop())
         logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
         c_log = np.zeros((max(K, 0), B)) if clearance else None
-        if sensors is not None:
+        p_log = np.zeros((max(K, 0), B)) if peers else None
+        if peers:
+            rc, name = self.api.fleet_rollout_peers(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log)), "fleet_rollout_peers"
+        elif sensors is not None:
             order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
             b_log = np.zeros((max(K, 0), B), np.int32)
             rc, name = self.api.fleet_rollout_lidar(*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples,
@@ -362,6 +449,8 @@ class Fleet:
             out["clearance"] = c_log
         if sensors is not None:
             out["boxes"] = b_log
+        if peers:
+            out["peer_clearance"] = p_log
         return out
 
     def clearance(self, states):

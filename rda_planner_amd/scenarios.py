@@ -218,3 +218,30 @@ def clearance(car_tuple, state, obstacles, t=0.0):
         else:
             out = min(out, _poly_sep(RV, o.vertex + o.velocity * t))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Fleet members as each other's obstacles: the specification of scene::k_peers_fleet and rollout::k_peer_clearance_fleet
+# (rda_fleet_upload_scenes_peers, Fleet.control(peers=True), Fleet.rollout(peers=True)) and the host loop they replace.
+def peer_obstacles(cars, states, controls, i):
+    """the obstacles member i sees in place of the other members, one per j != i in ascending j: member j's footprint at
+    `states[j]` as a polygon that moves with the control `controls[j]` = (v, w) it applied on the previous tick (zero
+    before its first tick and from its arrival tick on) along its heading - the heading of `states[j]` for acker / diff,
+    w itself for omni, the rule of `kinematic_step`"""
+    out = []
+    for j in range(len(cars)):
+        if j == i:
+            continue
+        st = np.asarray(states[j], float).ravel()
+        v, w = (float(x) for x in np.asarray(controls[j], float).ravel()[0:2])
+        a = w if cars[j].dynamics == "omni" else float(st[2])
+        out.append(Obstacle(None, None, robot_vertices(cars[j], st), "Rpositive", np.array([[v * cos(a)], [v * sin(a)]])))
+    return out
+
+
+def peer_clearance(cars, states):
+    """(B,) every member's separation from the nearest other member: min over j != i of `_poly_sep` of the two
+    footprints (negative = overlap); +inf for a fleet of one"""
+    RV = [robot_vertices(c, np.asarray(s, float).ravel()) for c, s in zip(cars, states)]
+    B = len(RV)
+    return np.array([min([_poly_sep(RV[i], RV[j]) for j in range(B) if j != i], default=np.inf) for i in range(B)])
