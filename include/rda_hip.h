@@ -465,6 +465,44 @@ int  rda_fleet_rollout_peers(rda_fleet *f, int K, const double *states /*B*3*/, 
                              double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
                              rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
                              double *clearance_log /*K*B, or NULL*/, double *peer_clearance_log /*K*B, or NULL*/);
+/* The second peers mode: peers predicted ALONG THEIR PLANNED TRAJECTORIES instead of at constant velocity (scene::k_build_plan_fleet in k_build_fleet's place
+ * in the re-sort launch set, so the launches per tick are those of the entries above; scenarios.peer_plan_poses / peer_plan_obstacles are the specification).
+ * plans [B][3][T+1]: every member's planned states, the out_s of its last solve; plan_valid [B]: 0 = member j has no plan that counts - no solve yet, after
+ * rda_reset, arrived - and is predicted at constant velocity exactly as above.  The peer rows, the ranking by current distance, the competition with the own
+ * obstacles for the N slots, nt = T + 1 and the padding (quirk Q3) are unchanged.  What changes is stages 1 .. T of a slot whose source row is the peer row of a
+ * valid member j: stage t is the half-space form (the edge expressions, orientation test and zeroed spare rows of every polygon) of j's footprint
+ * Rot(pose_t.theta) rv_j + pose_t.xy with
+ *     pose_t = x_j + (q_t - P[:,1]),   q_t = P[:,t+1] for t < T,   q_T = P[:,T] + (P[:,T] - P[:,T-1])            (x, y and heading alike)
+ * x_j = states[j], P = plans[j]: the plan is a sequence of displacements ANCHORED at the peer's actual state (a plant that did not follow its plan exactly
+ * produces no jump at stage 1), and the LAST STAGE repeats the plan's last increment.  Every difference and sum is rounded separately, parenthesised as
+ * written.  Stage 0, own obstacles and the slots of members that are not valid are bit-identical to rda_fleet_upload_scenes_peers; a padded copy of a peer
+ * carries the plan too.  The scenes are the peers scenes: the two modes may alternate on the same staged fleet.  Refusals of rda_fleet_upload_scenes_peers,
+ * plus RDA_ERR_ARG without plans / plan_valid; a refused allocation: RDA_ERR_HIP, fleet and members as they were.  Not covered: lidar rollouts with peers,
+ * circle (norm2) robots, the gear pieces of enable_reverse paths. */
+int  rda_fleet_upload_scenes_peers_plan(rda_fleet *f, const int32_t *counts /*B*/, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                        const double *vel, const double *states /*B*3*/, const double *controls /*B*2*/,
+                                        const double *plans /*B*3*(T+1)*/, const int32_t *plan_valid /*B*/);
+/* rda_fleet_scene_resort_peers in this mode: the peer rows rewritten, then the re-sort launches with the plans; no waiting.  Its refusals, plus RDA_ERR_ARG
+ * without plans / plan_valid. */
+int  rda_fleet_scene_resort_peers_plan(rda_fleet *f, const double *states /*B*3*/, const double *controls /*B*2*/,
+                                       const double *plans /*B*3*(T+1)*/, const int32_t *plan_valid /*B*/);
+/* rda_fleet_rollout_peers in this mode (its arguments, logs and refusals; plans0 / plan_valid0 behind them, RDA_ERR_ARG when either is missing).  Per tick k
+ * the peer rows are written as there; the slots are built from the states at the start of tick k and the plans the members' solves of tick k - 1 left in
+ * the fleet's result block on the device - tick 0: plans0 / plan_valid0 - and from tick 1 on a member is valid while it has not arrived (arrival tick <=
+ * k - 1: predicted standing).  Still one host wait.  Given the states, the previous controls, the previous tick's out_s and the own geometry of tick k, a
+ * tick computes bit for bit what rda_fleet_upload_scenes_peers_plan + rda_fleet_step_tracked compute.  rda_fleet_rollout_last serves this entry too, and
+ * rda_fleet_rollout_last_plan gives the plans0 that continue it. */
+int  rda_fleet_rollout_peers_plan(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                                  const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                                  const double *nom_u /*B*2*T or NULL = resident*/, const double *controls0 /*B*2*/,
+                                  double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                                  rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                                  double *clearance_log /*K*B, or NULL*/, double *peer_clearance_log /*K*B, or NULL*/,
+                                  const double *plans0 /*B*3*(T+1)*/, const int32_t *plan_valid0 /*B*/);
+/* of the last tick of the last rollout (any rollout entry): every member's planned states out_s [3][T+1], what rda_fleet_step_tracked returns as out_s - the
+ * plans0 of a rda_fleet_rollout_peers_plan, or the plans of a host-driven plan tick, that continues it.  No device work.  RDA_ERR_ARG before the first
+ * rollout or without out_s. */
+int  rda_fleet_rollout_last_plan(rda_fleet *f, double *out_s /*B*3*(T+1)*/);
 /* every member's separation from the nearest other member (as in peer_clearance_log above) at states [B][3]: one launch, one wait; needs no staged scene.
  * RDA_ERR_UNSUPPORTED: a robot the clearance does not take (see rda_fleet_clearance); RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_peer_clearance(rda_fleet *f, const double *states /*B*3*/, double *out /*B*/);

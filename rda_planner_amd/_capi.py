@@ -107,6 +107,10 @@ PROTOTYPES = {
     "fleet_upload_scenes_peers": "i hIIIDDDD",
     "fleet_scene_resort_peers":  "i hDD",
     "fleet_rollout_peers":  "i hiDDIdiiDDDDINIDD",
+    "fleet_upload_scenes_peers_plan": "i hIIIDDDDDI",
+    "fleet_scene_resort_peers_plan":  "i hDDDI",
+    "fleet_rollout_peers_plan": "i hiDDIdiiDDDDINIDDDI",
+    "fleet_rollout_last_plan":  "i hD",
     "fleet_peer_clearance": "i hDD",
     "fleet_upload_worlds":  "i hIiIIDD",
     "fleet_raycast":        "i hIDDDDDD",
@@ -201,6 +205,7 @@ class CApi:
         self.has_fleet_rollout_moving = has("fleet_rollout_moving")         # ... for scenes that move
         self.has_fleet_rollout_lidar = has("fleet_rollout_lidar")           # ... around the simulated sensor
         self.has_fleet_peers = has("fleet_rollout_peers")                   # members as each other's obstacles, staged on the device
+        self.has_fleet_peers_plan = has("fleet_rollout_peers_plan")         # ... predicted along their planned trajectories
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

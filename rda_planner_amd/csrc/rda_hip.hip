@@ -2996,12 +2996,12 @@ struct FleetRollTables {
     int alloc(size_t B) { return (m.alloc(g, B) | io.alloc(g, 2 * B)) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return m.d != nullptr; }
 };
-struct RollLayout { size_t states, u, endh, lastu, info, index, arrived, bytes; };     // byte offsets of the log block's parts (rollout::Logs; lastu [B][2][T]: the last tick's controls)
+struct RollLayout { size_t states, u, endh, last, info, index, arrived, bytes; };      // byte offsets of the log block's parts (rollout::Logs; last [B][res_info]: the last tick's u | s)
 static RollLayout roll_layout(size_t K, size_t B, size_t T)
 {
     RollLayout l;
-    l.states = 0; l.u = l.states + (K + 1) * B * 3 * sizeof(double); l.endh = l.u + K * B * 2 * sizeof(double); l.lastu = l.endh + B * sizeof(double);
-    l.info = l.lastu + B * traj_u(T) * sizeof(double);
+    l.states = 0; l.u = l.states + (K + 1) * B * 3 * sizeof(double); l.endh = l.u + K * B * 2 * sizeof(double); l.last = l.endh + B * sizeof(double);
+    l.info = l.last + B * res_info(T) * sizeof(double);
     l.index = l.info + K * B * sizeof(rda_info); l.arrived = l.index + K * B * sizeof(int); l.bytes = l.arrived + B * sizeof(int);
     return l;
 }
@@ -3033,6 +3033,12 @@ struct FleetPeers {
     hbuf::Group g; hbuf::Pair<scene::Peer> tab; hbuf::Pair<double> st, ctl;
     int alloc(size_t B) { return (tab.alloc(g, B) | st.alloc(g, 3 * B) | ctl.alloc(g, 2 * B)) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return tab.d != nullptr; }
+};
+// peers predicted along their plans (rda_fleet_*_peers_plan): the plans [B][3][T+1] and their validity [B] of a host-driven call or of a rollout's tick 0
+struct FleetPlan {
+    hbuf::Group g; hbuf::Pair<double> plan; hbuf::Pair<int> valid;
+    int alloc(size_t B, size_t T) { return (plan.alloc(g, B * traj_s(T)) | valid.alloc(g, B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return plan.d != nullptr; }
 };
 // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
 // tick overwrites with boxes.  Member-major geometry [total][e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
@@ -3073,6 +3079,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
     FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
     FleetPeers pe; FleetDoubles pc_log; std::vector<int> n_own;   // pc_log: the peer clearance log; n_own: every member's own obstacles as the last peers upload staged them
+    FleetPlan pl;
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -3315,12 +3322,16 @@ static int fleet_resort_positions(rda_fleet *F, const double *states, int stride
     return RDA_OK;
 }
 // the four launches of a re-sort: the members' scene arguments `sc` re-ranked about the positions `rob` (null: every member's arguments as they stand)
-static void fleet_resort_launch(rda_fleet *F, const scene::Args *sc, const double *rob, int nmax, int wmax)
+// plan (scenes of the peers upload, B >= 2): scene::k_build_plan_fleet in k_build_fleet's place - peers predicted along their plans
+static void fleet_resort_launch(rda_fleet *F, const scene::Args *sc, const double *rob, int nmax, int wmax, const scene::Plan *plan = nullptr)
 {
     const unsigned B = (unsigned)F->B;
     hipLaunchKernelGGL(scene::k_keys_fleet, dim3((nmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
     hipLaunchKernelGGL(scene::k_rank_fleet, dim3((nmax + 15) / 16, B), dim3(256), 0, F->stream, sc, rob);
-    hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
+    if (plan && B > 1)
+        hipLaunchKernelGGL(scene::k_build_plan_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob, (const scene::Peer *)F->pe.tab.d, *plan, (int)B);
+    else
+        hipLaunchKernelGGL(scene::k_build_fleet, dim3((wmax + 255) / 256, B), dim3(256), 0, F->stream, sc, rob);
     hipLaunchKernelGGL(k_prepare_fleet, dim3((unsigned)((wmax + 3) / 4), B), dim3(256), 0, F->stream, (const Dev *)F->devs.d);
 }
 extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int stride)
@@ -3574,6 +3585,7 @@ struct RollArgs {
     int K; const double *states, *ref_speed; const int32_t *cur_index; double threshold; int ind_range, goal_margin; const double *nom_u;
     double *states_log, *u_log; int32_t *index_log; rda_info *info_log; int32_t *arrived_at; double *clearance_log;
     bool peers = false; const double *controls0 = nullptr; double *peer_clearance_log = nullptr;     // rda_fleet_rollout_peers
+    bool plan = false; const double *plans0 = nullptr; const int32_t *plan_valid0 = nullptr;          // rda_fleet_rollout_peers_plan (with peers)
 };
 // the argument rules every entry has: of the arrays and counts, and (roll_check_members) of the members' paths
 static int roll_check_args(const rda_fleet *F, const RollArgs &a)
@@ -3768,13 +3780,12 @@ static int fleet_roll_tail(rda_fleet *F, int k, const rollout::Logs &lg, int goa
 // the logs to the host behind the last tick, the wait for them, and out to the caller's arrays
 static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs &a)
 {
-    const size_t T = F->T, nu = traj_u(T), B = F->B, K = a.K;
+    const size_t T = F->T, B = F->B, K = a.K;
     const char *log = F->ro_log.log.h;
     if (a.clearance_log) HIPCHK(F->cl_log.v.pull(F->stream, K * B));
     const bool peer_log = a.peer_clearance_log && B > 1;                        // (a fleet of one: +inf, nothing was launched)
     if (peer_log) HIPCHK(F->pc_log.v.pull(F->stream, K * B));
-    HIPCHK(hipMemcpy2DAsync(F->ro_log.log.d + lay.lastu, nu * sizeof(double), F->out.d, res_info(T) * sizeof(double), nu * sizeof(double), B,
-                            hipMemcpyDeviceToDevice, F->stream));                // the last tick's full controls, beside the logs
+    HIPCHK(hipMemcpyAsync(F->ro_log.log.d + lay.last, F->out.d, B * res_info(T) * sizeof(double), hipMemcpyDeviceToDevice, F->stream));      // the last tick's full controls and planned states, beside the logs
     HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
@@ -3801,7 +3812,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
     if (a.peers) {
-        if (!a.controls0) return RDA_ERR_ARG;
+        if (!a.controls0 || (a.plan && (!a.plans0 || !a.plan_valid0))) return RDA_ERR_ARG;
         for (size_t i = 0; i < B; ++i) if (!member_peers_scene(F, i)) return RDA_ERR_ARG;      // the scenes of rda_fleet_upload_scenes_peers, nothing staged since
     }
     for (const rda_handle *H : F->egos) if (resort && (H->sc.n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
@@ -3820,10 +3831,11 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     }
     const bool peer_log = a.peers && a.peer_clearance_log && B > 1;
     // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc;
+    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc; FleetPlan tpl;
     {
         int bad = rsv.alloc(F, a.K, a.clearance_log != nullptr);
         if (peer_log && (size_t)a.K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)a.K * B);
+        if (a.plan && !F->pl.have()) bad |= tpl.alloc(B, T);
         if (resort && !F->res.have()) bad |= tres.alloc(B);
         if (moving && !F->mov.have()) bad |= tmov.alloc(B);
         if (moving && mvw.mv_total > F->snap.cap) bad |= tsnap.alloc(mvw.mv_total);
@@ -3832,6 +3844,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     rc = rsv.move_in(F, tsnap.have() || tpc.have());
     if (rc != RDA_OK) return rc;
     if (tpc.have()) F->pc_log = std::move(tpc);
+    if (tpl.have()) F->pl = std::move(tpl);
     if (tres.have()) F->res = std::move(tres);
     if (tmov.have()) F->mov = std::move(tmov);
     if (tsnap.have()) F->snap = std::move(tsnap);
@@ -3864,6 +3877,10 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         memcpy(F->pe.st.h, a.states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, a.controls0, 2 * B * sizeof(double));
         HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
     }
+    if (a.plan) {
+        memcpy(F->pl.plan.h, a.plans0, B * traj_s(T) * sizeof(double)); memcpy(F->pl.valid.h, a.plan_valid0, B * sizeof(int));
+        HIPCHK(F->pl.plan.push(F->stream)); HIPCHK(F->pl.valid.push(F->stream));
+    }
     const RollLayout lay = roll_layout((size_t)a.K, B, T);
     rollout::Logs lg;
     rc = fleet_roll_inputs(F, lay, a, lg);
@@ -3874,7 +3891,10 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     for (int k = 0; k < a.K; ++k) {
         // the peer rows of tick k: the members' states at its start and the controls applied one tick earlier (tick 0: the caller's, then the device logs)
         if (a.peers) fleet_peers_launch(F, k == 0 ? F->pe.st.d : lg.states + (size_t)k * B * 3, k == 0 ? F->pe.ctl.d : lg.u + (size_t)(k - 1) * B * 2);
-        if (resort) fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);            // about res.rob: the caller's positions (tick 0), then the advance kernel's
+        // the plans of tick k: the caller's (tick 0), then what the members' solves of tick k - 1 left in the fleet's result block; valid while not arrived
+        const scene::Plan pk = k == 0 ? scene::Plan{ F->pe.st.d, F->pl.plan.d, traj_s(T), F->pl.valid.d, nullptr }
+                                      : scene::Plan{ lg.states + (size_t)k * B * 3, F->out.d + res_s(T), res_info(T), nullptr, lg.arrived_at };
+        if (resort) fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax, a.plan ? &pk : nullptr);      // about res.rob: the caller's positions (tick 0), then the advance kernel's
         else if (moves) fleet_resort_launch(F, F->mov.sc.d, nullptr, mvw.nmax, mvw.wmax);     // a scene that moved: its slots rebuilt in the staged order
         rc = fleet_roll_tail(F, k, lg, a.goal_margin, resort ? F->res.rob.d : nullptr, moves ? F->mov.mv.d : nullptr, gmove,
                              a.clearance_log ? F->mov.cl.d : nullptr);
@@ -3943,25 +3963,32 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
 }
 // ---- members as each other's obstacles (scene::k_peers_fleet, rollout::k_peer_clearance_fleet) ---------------------------------------------------------
 // The refresh of the peer rows from the caller's states and controls and the four re-sort launches behind it, on the fleet's stream
-static int fleet_peers_resort(rda_fleet *F, const double *states, const double *controls)
+// plans (null: the constant-velocity mode): with plan_valid into the fleet's staging buffers, and scene::k_build_plan_fleet builds the slots
+static int fleet_peers_resort(rda_fleet *F, const double *states, const double *controls, const double *plans, const int32_t *plan_valid)
 {
-    const size_t B = F->B;
+    const size_t B = F->B, T = F->T;
     int nmax = 0, wmax = 0;
     int rc = fleet_resort_positions(F, states, 3, nmax, wmax);                  // (waits for an earlier copy out of the pinned mirrors)
     if (rc != RDA_OK) return rc;
     memcpy(F->pe.st.h, states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, controls, 2 * B * sizeof(double));
     HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
+    if (plans) {
+        memcpy(F->pl.plan.h, plans, B * traj_s(T) * sizeof(double)); memcpy(F->pl.valid.h, plan_valid, B * sizeof(int));
+        HIPCHK(F->pl.plan.push(F->stream)); HIPCHK(F->pl.valid.push(F->stream));
+    }
     fleet_peers_launch(F, F->pe.st.d, F->pe.ctl.d);
-    fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax);
+    const scene::Plan pk{ F->pe.st.d, F->pl.plan.d, traj_s(T), F->pl.valid.d, nullptr };
+    fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax, plans ? &pk : nullptr);
     HIPCHK(hipGetLastError());
     return RDA_OK;
 }
 // rda_fleet_upload_scenes with B - 1 peer rows behind every member's own obstacles.  Everything the call needs is allocated before anything of the fleet or
 // of a member changes; the staging runs on the fleet's stream and the call returns when it is done.
-extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom,
-                                             const double *vel, const double *states, const double *controls)
+// plan: the _plan entry (plans and plan_valid required)
+static int fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom, const double *vel,
+                                     const double *states, const double *controls, bool plan, const double *plans, const int32_t *plan_valid)
 {
-    if (!F || !counts || !states || !controls) return RDA_ERR_ARG;
+    if (!F || !counts || !states || !controls || (plan && (!plans || !plan_valid))) return RDA_ERR_ARG;
     const size_t B = F->B;
     const int E = F->egos[0]->d.c.E, R = F->egos[0]->d.c.R, T = F->T;
     size_t total = 0;
@@ -3975,10 +4002,11 @@ extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts
         else if (kind[e] != 0 || nvert[e] < 0 || nvert[e] > E) return RDA_ERR_ARG;
     }
     if (B == 1 && counts[0] == 0) { F->egos[0]->d.obstacle_num = 0; return RDA_OK; }      // nothing written: stale A, b stay (rda_upload_scene with n = 0)
-    FleetPeers tpe; FleetResort tres; std::vector<SceneGrow> grow(B);
+    FleetPeers tpe; FleetResort tres; FleetPlan tpl; std::vector<SceneGrow> grow(B);
     {
         int bad = 0;
         if (!F->pe.have()) bad |= tpe.alloc(B);
+        if (plan && !F->pl.have()) bad |= tpl.alloc(B, (size_t)T);
         if (!F->res.have()) bad |= tres.alloc(B);
         for (size_t i = 0; i < B; ++i) bad |= scene_grow_alloc(F->egos[i], counts[i] + (int)B - 1, grow[i]);
         if (bad) return RDA_ERR_HIP;
@@ -3988,6 +4016,7 @@ extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts
     HIPCHK(hipStreamSynchronize(F->stream));            // ... and done: the members' pinned staging blocks are free
     F->rob_pending = 0;
     if (tpe.have()) F->pe = std::move(tpe);
+    if (tpl.have()) F->pl = std::move(tpl);
     if (tres.have()) F->res = std::move(tres);
     F->n_own.assign(counts, counts + B);
     size_t off = 0;
@@ -4019,19 +4048,35 @@ extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts
     HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
     HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
     fleet_refresh_flags(F);
-    rc = fleet_peers_resort(F, states, controls);
+    rc = fleet_peers_resort(F, states, controls, plan ? plans : nullptr, plan_valid);
     if (rc != RDA_OK) return rc;
     HIPCHK(hipStreamSynchronize(F->stream));            // the staging blocks are reused by the next call; the members' own calls see the scene
     F->rob_pending = 0;
     return RDA_OK;
 }
-// rda_fleet_scene_resort for scenes of the peers upload: the peer rows refreshed from states and controls, then the re-sort
-extern "C" int rda_fleet_scene_resort_peers(rda_fleet *F, const double *states, const double *controls)
+extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                             const double *vel, const double *states, const double *controls)
 {
-    if (!F || !states || !controls) return RDA_ERR_ARG;
+    return fleet_upload_scenes_peers(F, counts, kind, nvert, geom, vel, states, controls, false, nullptr, nullptr);
+}
+extern "C" int rda_fleet_upload_scenes_peers_plan(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom,
+                                                  const double *vel, const double *states, const double *controls, const double *plans,
+                                                  const int32_t *plan_valid)
+{
+    return fleet_upload_scenes_peers(F, counts, kind, nvert, geom, vel, states, controls, true, plans, plan_valid);
+}
+// rda_fleet_scene_resort for scenes of the peers upload: the peer rows refreshed from states and controls, then the re-sort
+static int fleet_scene_resort_peers(rda_fleet *F, const double *states, const double *controls, bool plan, const double *plans, const int32_t *plan_valid)
+{
+    if (!F || !states || !controls || (plan && (!plans || !plan_valid))) return RDA_ERR_ARG;
     for (size_t i = 0; i < (size_t)F->B; ++i) {
         if (!member_peers_scene(F, i) || F->egos[i]->tick.pending) return RDA_ERR_ARG;
         if (F->egos[i]->opts.duals_follow) return RDA_ERR_UNSUPPORTED;
+    }
+    if (plan && !F->pl.have()) {                        // first use: the staging buffers take their place once all of them exist
+        FleetPlan t;
+        if (t.alloc((size_t)F->B, (size_t)F->T)) return RDA_ERR_HIP;
+        F->pl = std::move(t);
     }
     int rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
@@ -4041,7 +4086,16 @@ extern "C" int rda_fleet_scene_resort_peers(rda_fleet *F, const double *states, 
         HIPCHK(hipStreamSynchronize(F->stream));
         HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
     }
-    return fleet_peers_resort(F, states, controls);
+    return fleet_peers_resort(F, states, controls, plan ? plans : nullptr, plan_valid);
+}
+extern "C" int rda_fleet_scene_resort_peers(rda_fleet *F, const double *states, const double *controls)
+{
+    return fleet_scene_resort_peers(F, states, controls, false, nullptr, nullptr);
+}
+// ... with the peers predicted along their plans
+extern "C" int rda_fleet_scene_resort_peers_plan(rda_fleet *F, const double *states, const double *controls, const double *plans, const int32_t *plan_valid)
+{
+    return fleet_scene_resort_peers(F, states, controls, true, plans, plan_valid);
 }
 // The rollout of a fleet whose members see each other: per tick the peer rows, the re-sort, the tick's tail on the own rows, the peer clearance
 extern "C" int rda_fleet_rollout_peers(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
@@ -4050,6 +4104,17 @@ extern "C" int rda_fleet_rollout_peers(rda_fleet *F, int K, const double *states
 {
     RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
     a.peers = true; a.controls0 = controls0; a.peer_clearance_log = peer_clearance_log;
+    return fleet_rollout_scenes(F, a, 1, true);
+}
+// ... with the peers predicted along their plans: tick 0 from plans0 / plan_valid0, tick k >= 1 from the states the members' solves of tick k - 1 planned
+extern "C" int rda_fleet_rollout_peers_plan(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                            int ind_range, int goal_margin, const double *nom_u, const double *controls0, double *states_log, double *u_log,
+                                            int32_t *index_log, rda_info *info_log, int32_t *arrived_at, double *clearance_log, double *peer_clearance_log,
+                                            const double *plans0, const int32_t *plan_valid0)
+{
+    RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    a.peers = true; a.controls0 = controls0; a.peer_clearance_log = peer_clearance_log;
+    a.plan = true; a.plans0 = plans0; a.plan_valid0 = plan_valid0;
     return fleet_rollout_scenes(F, a, 1, true);
 }
 // every member's separation from the nearest other member at states [B][3]: the rollout's kernel, one launch, one wait
@@ -4294,8 +4359,19 @@ extern "C" int rda_fleet_rollout_last(rda_fleet *F, double *out_u, double *end_h
 {
     if (!F || F->roll_K < 1) return RDA_ERR_ARG;
     const RollLayout lay = roll_layout((size_t)F->roll_K, (size_t)F->B, (size_t)F->T);
-    if (out_u) memcpy(out_u, F->ro_log.log.h + lay.lastu, (size_t)F->B * traj_u(F->T) * sizeof(double));
+    const size_t T = F->T;
+    const double *last = (const double *)(F->ro_log.log.h + lay.last);
+    if (out_u) for (size_t i = 0; i < (size_t)F->B; ++i) memcpy(out_u + i * traj_u(T), last + i * res_info(T), traj_u(T) * sizeof(double));
     if (end_heading) memcpy(end_heading, F->ro_log.log.h + lay.endh, (size_t)F->B * sizeof(double));
+    return RDA_OK;
+}
+// ... and every member's planned states out_s [B][3][T+1] of that tick: plans0 of a rda_fleet_rollout_peers_plan or of a host-driven plan tick that continues
+extern "C" int rda_fleet_rollout_last_plan(rda_fleet *F, double *out_s)
+{
+    if (!F || F->roll_K < 1 || !out_s) return RDA_ERR_ARG;
+    const size_t T = F->T;
+    const double *last = (const double *)(F->ro_log.log.h + roll_layout((size_t)F->roll_K, (size_t)F->B, T).last);
+    for (size_t i = 0; i < (size_t)F->B; ++i) memcpy(out_s + i * traj_s(T), last + i * res_info(T) + res_s(T), traj_s(T) * sizeof(double));
     return RDA_OK;
 }
 

@@ -67,6 +67,36 @@ __device__ __forceinline__ void rank_body(const Args &a, const int blk)
 }
 __global__ void k_rank(Args a) { rank_body(a, blockIdx.x); }
 
+// The slot rows of one polygon at one stage, shared by build_body and plan_body: all E rows zeroed (the spare rows stay zero) ...
+__device__ __forceinline__ void zero_rows(double *A, double *b, const int E)
+{
+    for (int e = 0; e < E; ++e) { A[2 * e] = 0; A[2 * e + 1] = 0; b[e] = 0; }
+}
+// ... and rows 0 .. k-1 from the k vertices (px, py): the orientation test and the edge expressions of gen_inequal_global; returns is_convex_and_ordered
+__device__ __forceinline__ bool polygon_rows(const double *px, const double *py, const int k, double *A, double *b)
+{
+#pragma clang fp contract(off)
+    // is_convex_and_ordered, mpc.py:527-549
+    int direction = 0; bool convex = k >= 3;
+    for (int j = 0; j < k && convex; ++j) {
+        int j1 = (j + 1) % k, j2 = (j + 2) % k;
+        double cr = (px[j1] - px[j]) * (py[j2] - py[j]) - (py[j1] - py[j]) * (px[j2] - px[j]);
+        if (cr != 0) {
+            if (direction == 0) direction = cr > 0 ? 1 : -1;
+            else if ((cr > 0) != (direction > 0)) convex = false;
+        }
+    }
+    const bool cw = convex && direction <= 0;                      // order == 'CW' (direction 0 also reports CW), :500-501
+    for (int j = 0; j < k; ++j) {
+        int c0 = cw ? k - 1 - j : j, c1 = cw ? (k - 1 - ((j + 1) % k)) : (j + 1) % k;
+        double ex = px[c1] - px[c0], ey = py[c1] - py[c0];
+        double a0 = ey, a1 = -ex;                                  // A = [edge_y, -edge_x]   :505-506
+        A[2 * j] = a0; A[2 * j + 1] = a1;
+        b[j] = a0 * px[c0] + a1 * py[c0];   // sum(A * cur, axis=1)   :507
+    }
+    return convex;
+}
+
 // one thread per (slot, time slot): half-space form of the selected obstacle at time t
 __device__ __forceinline__ void build_body(const Args &a, const int w)
 {
@@ -78,7 +108,7 @@ __device__ __forceinline__ void build_body(const Args &a, const int w)
     const int E = a.E;
     const double *g = a.geom + (size_t)i * E * 2;
     double *A = a.A + ((size_t)s * a.nt + t) * E * 2, *b = a.b + ((size_t)s * a.nt + t) * E;
-    for (int e = 0; e < E; ++e) { A[2 * e] = 0; A[2 * e + 1] = 0; b[e] = 0; }
+    zero_rows(A, b, E);
     const double vx = a.vel[2 * i], vy = a.vel[2 * i + 1];
     const bool moving = sqrt(vx * vx + vy * vy) > 0.01;     // mpc.py:443,462
     const double tt = (double)t * a.dt;
@@ -95,25 +125,8 @@ __device__ __forceinline__ void build_body(const Args &a, const int w)
     const int k = a.nvert[i];
     double px[16], py[16];
     for (int j = 0; j < k; ++j) { px[j] = moving ? g[2 * j] + sx : g[2 * j]; py[j] = moving ? g[2 * j + 1] + sy : g[2 * j + 1]; }
-    // is_convex_and_ordered, mpc.py:527-549
-    int direction = 0; bool convex = k >= 3;
-    for (int j = 0; j < k && convex; ++j) {
-        int j1 = (j + 1) % k, j2 = (j + 2) % k;
-        double cr = (px[j1] - px[j]) * (py[j2] - py[j]) - (py[j1] - py[j]) * (px[j2] - px[j]);
-        if (cr != 0) {
-            if (direction == 0) direction = cr > 0 ? 1 : -1;
-            else if ((cr > 0) != (direction > 0)) convex = false;
-        }
-    }
+    const bool convex = polygon_rows(px, py, k, A, b);
     if (!convex && t == 0 && s < used) atomicAdd(a.nonconvex, 1);
-    const bool cw = convex && direction <= 0;                      // order == 'CW' (direction 0 also reports CW), :500-501
-    for (int j = 0; j < k; ++j) {
-        int c0 = cw ? k - 1 - j : j, c1 = cw ? (k - 1 - ((j + 1) % k)) : (j + 1) % k;
-        double ex = px[c1] - px[c0], ey = py[c1] - py[c0];
-        double a0 = ey, a1 = -ex;                                  // A = [edge_y, -edge_x]   :505-506
-        A[2 * j] = a0; A[2 * j + 1] = a1;
-        b[j] = a0 * px[c0] + a1 * py[c0];   // sum(A * cur, axis=1)   :507
-    }
 }
 __global__ void k_build(Args a) { build_body(a, blockIdx.x * blockDim.x + threadIdx.x); }
 
@@ -210,6 +223,56 @@ __global__ void k_peers_fleet(const Peer *ps, const double *states, const double
         me.vel[2 * r] = sp * cos(a);
         me.vel[2 * r + 1] = sp * sin(a);
     }
+}
+
+// Peers predicted along their PLANNED trajectories (rda_fleet_*_peers_plan; scenarios.peer_plan_poses / peer_plan_obstacles are the specification):
+// k_build_fleet's grid and body, but stage t >= 1 of a slot whose source row is the peer row of a VALID member j is the half-space form of j's footprint
+// at pose_t = x_j + (q_t - P[:,1]), q_t = P[:,t+1] for t < T and q_T = P[:,T] + (P[:,T] - P[:,T-1]): the plan P [3][T+1] (the states j's last solve left)
+// taken as displacements anchored at j's state x_j at the start of the tick, all three components alike, every difference and sum rounded separately.
+// Everything else - own obstacles, stage 0, peers that are not valid (no solve yet, after a reset, arrived: predicted at constant velocity as before) -
+// is build_body itself; a padded copy of a peer (quirk Q3) goes through the same `sel` entry and gets the plan too.
+struct Plan {
+    const double *states;     // [B][3] the members' states at the start of the tick
+    const double *base;       // member j's plan: base + j * stride, [3][T+1]
+    size_t stride;
+    const int *valid;         // [B] != 0: j's plan counts; null: arrived_at decides
+    const int *arrived_at;    // [B] the rollout's log: j counts while arrived_at[j] < 0
+};
+__device__ __forceinline__ void plan_body(const Args &a, const int w, const Peer *ps, const Plan &pl, const int B)
+{
+#pragma clang fp contract(off)
+    if (w >= a.N * a.nt) return;
+    const int s = w / a.nt, t = w % a.nt;
+    const int used = a.n < a.N ? a.n : a.N;
+    const int i = a.sel[s < used ? s : used - 1];
+    const int me = blockIdx.y, r = i - ps[me].n_own, T = a.T;
+    const int j = r < me ? r : r + 1;
+    const bool peer = r >= 0 && r < B - 1 && t >= 1 && t <= T && a.kind[i] == 0;
+    if (!peer || !(pl.valid ? pl.valid[j] != 0 : pl.arrived_at[j] < 0)) { build_body(a, w); return; }
+    const Peer &p = ps[j];
+    const int E = a.E, R = p.R < E ? p.R : E;
+    double *A = a.A + ((size_t)s * a.nt + t) * E * 2, *b = a.b + ((size_t)s * a.nt + t) * E;
+    zero_rows(A, b, E);
+    const double *P = pl.base + (size_t)j * pl.stride;
+    double pose[3];
+    for (int c = 0; c < 3; ++c) {
+        const double *Pc = P + (size_t)c * (T + 1);
+        const double q = t < T ? Pc[t + 1] : Pc[T] + (Pc[T] - Pc[T - 1]);
+        pose[c] = pl.states[3 * j + c] + (q - Pc[1]);
+    }
+    const double co = cos(pose[2]), si = sin(pose[2]);
+    double px[RDA_RMAX], py[RDA_RMAX];
+    for (int v = 0; v < R; ++v) {
+        px[v] = (co * p.rv[v][0] - si * p.rv[v][1]) + pose[0];
+        py[v] = (si * p.rv[v][0] + co * p.rv[v][1]) + pose[1];
+    }
+    polygon_rows(px, py, R, A, b);
+}
+__global__ void k_build_plan_fleet(const Args *as, const double *rob, const Peer *ps, Plan pl, int B)
+{
+    const Args a = fleet_args(as, rob);
+    if (a.n <= 0) return;
+    plan_body(a, blockIdx.x * blockDim.x + threadIdx.x, ps, pl, B);
 }
 
 }  // namespace scene

@@ -41,6 +41,17 @@ def sensor_arrays(sensors, B):
     return (np.array(cols[0], np.int32),) + tuple(f64(c) for c in cols[1:])
 
 
+def peers_mode(peers):
+    """the `peers=` argument of `Fleet.control` / `Fleet.rollout` -> (peers on, predicted along their plans)"""
+    if isinstance(peers, str):
+        if peers != "plan":
+            raise ValueError(f'peers={peers!r}: False, True (constant velocity) or "plan" (along the planned trajectories)')
+        return True, True
+    if peers is None or isinstance(peers, (bool, int, np.bool_, np.integer)):
+        return bool(peers), False
+    raise ValueError(f'peers={peers!r}: False, True (constant velocity) or "plan" (along the planned trajectories)')
+
+
 def states_array(states, B):
     """B states - (3,), (3, 1) or longer - as one contiguous (B, 3) array"""
     return f64([np.asarray(x, float).ravel()[0:3] for x in states], (B, 3))
@@ -71,9 +82,35 @@ class Fleet:
         self._info = (Info * B)()
         self.batched_ticks = 0          # ticks whose scenes went through the one-pass staging (diagnostics)
         self._peers_staged = False      # the members' resident scenes are those of rda_fleet_upload_scenes_peers
+        self._plan_state()
 
     def __len__(self):
         return len(self.members)
+
+    def _plan_state(self):
+        """every member's last planned states (B, 3, T+1) - the `opt_state_list` of its last tick through this fleet - and whether they count
+        (B,): not before its first tick, not after `reset`, not once it has arrived.  What peers="plan" predicts the members along."""
+        if getattr(self, "_plans", None) is None:
+            B, T = len(self.members), self.members[0].receding
+            self._plans, self._plan_valid = np.zeros((B, 3, T + 1)), np.zeros(B, np.int32)
+        return self._plans, self._plan_valid
+
+    @property
+    def plan_valid(self):
+        """(B,) bool: member i has a plan that peers="plan" uses"""
+        return self._plan_state()[1].astype(bool)
+
+    def _note_plan(self, i, out_s, arrived):
+        plans, valid = self._plan_state()
+        plans[i] = f64(out_s, plans[i].shape)
+        valid[i] = 0 if arrived else 1
+
+    def reset(self, which=None):
+        """`MPC.reset` of the members `which` (indices; default: all), and their plans no longer count for peers="plan" """
+        _, valid = self._plan_state()
+        for i in (range(len(self.members)) if which is None else which):
+            self.members[i].reset()
+            valid[i] = 0
 
     def lammuz_kernel(self):
         """the LamMuZ launches the next tick issues per ADMM iteration as the members stand now (rda_fleet_lammuz_kernel): kernel names joined by '+'"""
@@ -101,21 +138,26 @@ class Fleet:
         their heading (default: `members[j].cur_vel_array[:, 0]`, which is zero before the first tick and once the member has arrived) - written on
         the device by rda_fleet_upload_scenes_peers; result i is what `members[i].control(states[i], ref_speeds[i], obstacle_lists[i] +
         scenarios.peer_obstacles(cars, states, peer_controls, i))` returns.  Device-tracked members with `obstacle_order=True` and polygon robots only;
-        anything else raises, there is no host fallback."""
+        anything else raises, there is no host fallback.
+        peers="plan": the same, but a member that has a plan - it went through a tick of this fleet, was not `reset` since and has not arrived - is
+        predicted along it instead of at constant velocity: at stage t >= 1 its footprint stands at `scenarios.peer_plan_poses` of its state and the
+        `opt_state_list` of its last tick (the plan as displacements anchored at the actual state, the last increment repeated at stage T);
+        rda_fleet_upload_scenes_peers_plan, `scenarios.peer_plan_obstacles` is the specification.  Any other value of `peers` is a ValueError."""
         B, start = len(self.members), time.time()
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
+        peers, plan = peers_mode(peers)
         if peers:
             if scans is not None:
                 raise ValueError("Fleet.control: peers=True takes obstacle_lists, not scans=")
-            self._check_peers(kwargs)
+            self._check_peers(kwargs, plan)
             if peer_controls is None:
                 peer_controls = [np.asarray(m.cur_vel_array, float)[:, 0] for m in self.members]
             if len(peer_controls) != B or (obstacle_lists is not None and len(obstacle_lists) != B):
                 raise ValueError("Fleet.control: one obstacle list and one peer control per member")
             ctl = f64([np.asarray(c, float).ravel()[0:2] for c in peer_controls], (B, 2))
             own = obstacle_lists if obstacle_lists is not None else [[] for _ in range(B)]
-            return self._control_tracked(states, ref_speeds, own, start, stage=lambda st: self._stage_peers(own, st, ctl), **kwargs)
+            return self._control_tracked(states, ref_speeds, own, start, stage=lambda st: self._stage_peers(own, st, ctl, plan), **kwargs)
         self._peers_staged = False
         if scans is not None:
             if obstacle_lists is not None and any(len(ol) for ol in obstacle_lists):
@@ -164,6 +206,7 @@ class Fleet:
                 print("No update of state and control vector")        # reference rda_solver.py:699
             info = m.rda.pack_info(ref_list, self._out_s[i].copy(), self._info[i], start)
             out.append(m._end(cur_ref_path, self._out_u[i].copy(), info))
+            self._note_plan(i, self._out_s[i], info["arrive"])
         return out
 
     def _stage_all(self, obstacle_lists, st):
@@ -191,11 +234,13 @@ class Fleet:
         self.batched_ticks += 1
         return True
 
-    def _check_peers(self, kwargs):
-        """what peers=True needs of the library and of every member, checked before any library call"""
+    def _check_peers(self, kwargs, plan=False):
+        """what peers=True / peers="plan" needs of the library and of every member, checked before any library call"""
         ms = self.members
         if not getattr(self.api, "has_fleet_peers", False):
             raise RuntimeError("the loaded solver library has no peer entry points (rda_fleet_upload_scenes_peers, rda_fleet_rollout_peers)")
+        if plan and not getattr(self.api, "has_fleet_peers_plan", False):
+            raise RuntimeError('peers="plan": the loaded solver library has no plan entry points (rda_fleet_upload_scenes_peers_plan, rda_fleet_rollout_peers_plan)')
         if any(not m.obstacle_order for m in ms):
             raise RuntimeError("peers=True ranks every member's obstacles and peers by distance: obstacle_order=False is not supported")
         if any(m.car_tuple.cone_type == "norm2" for m in ms):
@@ -205,8 +250,9 @@ class Fleet:
         if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
             raise RuntimeError("peers=True needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
 
-    def _stage_peers(self, obstacle_lists, st, controls):
-        """`_stage_all` with the other members behind every member's own obstacles (rda_fleet_upload_scenes_peers); st (B, 3), controls (B, 2)"""
+    def _stage_peers(self, obstacle_lists, st, controls, plan=False):
+        """`_stage_all` with the other members behind every member's own obstacles (rda_fleet_upload_scenes_peers; plan: _peers_plan with the members'
+        last plans and their validity); st (B, 3), controls (B, 2)"""
         ms = self.members
         counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(ms))
         every = [o for ol in obstacle_lists for o in ol]
@@ -216,9 +262,14 @@ class Fleet:
         _, kind, nvert, geom, vel = scene
         kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
         geom = f64(geom); vel = f64(vel)
-        rc = self.api.fleet_upload_scenes_peers(self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(f64(st)), dptr(f64(controls)))
+        head = (self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(f64(st)), dptr(f64(controls)))
+        if plan:
+            plans, valid = self._plan_state()
+            rc, name = self.api.fleet_upload_scenes_peers_plan(*head, dptr(plans), iptr(valid)), "fleet_upload_scenes_peers_plan"
+        else:
+            rc, name = self.api.fleet_upload_scenes_peers(*head), "fleet_upload_scenes_peers"
         if rc < 0:
-            raise self.api.failed("fleet_upload_scenes_peers", rc)
+            raise self.api.failed(name, rc)
         self._peers_staged = True
         self.batched_ticks += 1
 
@@ -353,14 +404,17 @@ class Fleet:
         `cur_vel_array[:, 0]`), re-sorts, and runs the tick of `moving=True` on the member's own obstacles.  `obstacle_lists=` is required on the first
         call and optional once such scenes are resident.  The result always has `"peer_clearance"` (steps, B): every member's separation from the
         nearest other member after each tick (`scenarios.peer_clearance`; negative = overlap); `clearance=True` keeps its meaning (own obstacles
-        only).  `resort` does not apply, `lidar=` / `scans=` cannot be combined with it, and it has the refusals of `control(peers=True)`."""
+        only).  `resort` does not apply, `lidar=` / `scans=` cannot be combined with it, and it has the refusals of `control(peers=True)`.
+        `peers="plan"` (rda_fleet_rollout_peers_plan): as `control(peers="plan")` - tick 0 predicts every member along the plan this fleet holds of
+        it (if it counts), every later tick along the plan its solve of the tick before left on the device, while it has not arrived.  Returns what
+        `peers=True` returns; the same number of launches per tick."""
         ms = self.members
         kwargs = dict(kwargs)
-        peers = bool(kwargs.pop("peers", False))
+        peers, plan = peers_mode(kwargs.pop("peers", False))
         if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
             raise ValueError("Fleet.rollout: peers=True cannot be combined with lidar= / scans=")
         if peers:
-            self._check_peers({k: v for k, v in kwargs.items() if k in ("threshold", "ind_range")})
+            self._check_peers({k: v for k, v in kwargs.items() if k in ("threshold", "ind_range")}, plan)
             if kwargs.get("obstacle_lists") is None and not getattr(self, "_peers_staged", False):
                 raise ValueError("Fleet.rollout: peers=True needs obstacle_lists= until such scenes are resident")
             kwargs["moving"] = True                      # (the peers rollout is a moving rollout)
@@ -401,7 +455,7 @@ class Fleet:
             self.upload_worlds(world)
         ctl0 = f64([np.asarray(m.cur_vel_array, float)[:, 0] for m in ms], (B, 2)) if peers else None
         if peers and obstacle_lists is not None:
-            self._stage_peers(obstacle_lists, st, ctl0)
+            self._stage_peers(obstacle_lists, st, ctl0, plan)
         elif obstacle_lists is not None:
             self._peers_staged = False
             if not self._stage_all(obstacle_lists, st):
@@ -414,7 +468,11 @@ class Fleet:
         logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
         c_log = np.zeros((max(K, 0), B)) if clearance else None
         p_log = np.zeros((max(K, 0), B)) if peers else None
-        if peers:
+        if plan:
+            plans, valid = self._plan_state()
+            rc, name = self.api.fleet_rollout_peers_plan(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log), dptr(plans),
+                                                         iptr(valid)), "fleet_rollout_peers_plan"
+        elif peers:
             rc, name = self.api.fleet_rollout_peers(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log)), "fleet_rollout_peers"
         elif sensors is not None:
             order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
@@ -431,6 +489,12 @@ class Fleet:
         rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
         if rc < 0:
             raise self.api.failed("fleet_rollout_last", rc)
+        if getattr(self.api, "has_fleet_peers_plan", False):        # the plans the last tick left: what a peers="plan" tick that continues predicts along
+            plans, valid = self._plan_state()
+            rc = self.api.fleet_rollout_last_plan(self._handle, dptr(plans))
+            if rc < 0:
+                raise self.api.failed("fleet_rollout_last_plan", rc)
+            valid[:] = arrived < 0
         for i, m in enumerate(ms):
             path = m.ref_path
             m.state = s_log[K, i].reshape(3, 1).copy()
@@ -513,4 +577,5 @@ class Fleet:
             ref_list = [ref_own[:, j:j + 1] for j in range(T + 1)]
             info = m.rda.pack_info(ref_list, self._out_s[i].copy(), self._info[i], start)
             out.append(m._tracked_done(pieces[i], self._out_u[i].copy(), info, int(mi[i]), float(eh[i])))
+            self._note_plan(i, self._out_s[i], info["arrive"])
         return out

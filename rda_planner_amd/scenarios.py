@@ -245,3 +245,56 @@ def peer_clearance(cars, states):
     RV = [robot_vertices(c, np.asarray(s, float).ravel()) for c, s in zip(cars, states)]
     B = len(RV)
     return np.array([min([_poly_sep(RV[i], RV[j]) for j in range(B) if j != i], default=np.inf) for i in range(B)])
+
+
+# ---------------------------------------------------------------------------------------------
+# Peers predicted along their planned trajectories: the specification of scene::k_build_plan_fleet
+# (rda_fleet_*_peers_plan, Fleet.control(peers="plan"), Fleet.rollout(peers="plan")).
+PlanObstacle = namedtuple("PlanObstacle", "center radius vertex cone_type velocity A b vertices")
+
+
+def peer_plan_poses(state_j, plan_j, T):
+    """(T+1, 3) the poses a peer is predicted at over the horizon from its state at the start of the tick and its previous
+    plan P [3][T+1] (the `opt_state_list` / out_s of its last solve): pose_0 = x_j, pose_t = x_j + (q_t - P[:,1]) with
+    q_t = P[:,t+1] for t < T and q_T = P[:,T] + (P[:,T] - P[:,T-1]) - the plan as displacements anchored at the actual
+    state, the last increment repeated; x, y and heading alike, every difference and sum rounded separately"""
+    x = np.asarray(state_j, float).ravel()[0:3]
+    P = np.asarray(plan_j, float).reshape(3, T + 1)
+    out = np.zeros((T + 1, 3))
+    out[0] = x
+    for t in range(1, T + 1):
+        q = P[:, t + 1] if t < T else P[:, T] + (P[:, T] - P[:, T - 1])
+        out[t] = x + (q - P[:, 1])
+    return out
+
+
+def _ordered_halfspaces(vertex):
+    """(A kx2, b kx1) of a convex polygon as MPC.gen_inequal_global gives them: vertices reversed first when they run
+    clockwise (all turns collinear counts as clockwise)"""
+    V = np.asarray(vertex, float)[0:2]
+    o, a, b = V, np.roll(V, -1, axis=1), np.roll(V, -2, axis=1)
+    turns = (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+    turns = turns[turns != 0]
+    if not (turns.size and turns[0] > 0):
+        V = V[:, ::-1]
+    return polygon_halfspaces(V)
+
+
+def peer_plan_obstacles(cars, states, controls, plans, valid, i, T, dt=0.1):
+    """the obstacles of `peer_obstacles`, in its order, in the form `RDA_solver._stage` takes for time-varying obstacles
+    (`isinstance(o.A, list)`), so that a host loop can stage them with `rda_obstacle=True`: `vertices`, `A`, `b` are lists
+    of T + 1 per-stage arrays.  A peer j with `valid[j]` is at `peer_plan_poses(states[j], plans[j], T)`; any other peer
+    (no solve yet, after a reset, arrived) is predicted at constant velocity like every moving polygon - vertex +
+    velocity * (t * dt) above 0.01 m/s, standing below.  `vertex` is the footprint at stage 0, which is what ranks the
+    obstacle by distance."""
+    out = []
+    for o, j in zip(peer_obstacles(cars, states, controls, i), [j for j in range(len(cars)) if j != i]):
+        if valid[j]:
+            verts = [robot_vertices(cars[j], p) for p in peer_plan_poses(states[j], plans[j], T)]
+            verts[0] = o.vertex
+        else:
+            moving = np.linalg.norm(o.velocity) > 0.01
+            verts = [o.vertex + o.velocity * (t * dt) if moving else o.vertex for t in range(T + 1)]
+        hs = [_ordered_halfspaces(v) for v in verts]
+        out.append(PlanObstacle(None, None, o.vertex, "Rpositive", o.velocity, [h[0] for h in hs], [h[1] for h in hs], verts))
+    return out

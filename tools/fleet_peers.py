@@ -15,6 +15,11 @@ legs are interleaved (a b c a b c ...), medians over --repeats.  No ratio is ask
 
     python tools/fleet_peers.py [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6]         (output: profiles/fleet_peers.txt)
     python tools/fleet_peers.py --leg peers --B 16                                           (one measurement alone)
+    python tools/fleet_peers.py --plan                                                       (output: profiles/fleet_peers_plan.txt)
+
+--plan: the rollout with the peers predicted along their planned trajectories, `Fleet.rollout(peers="plan")` (rda_fleet_rollout_peers_plan:
+scene::k_build_plan_fleet in k_build_fleet's place, the same number of launches per tick), beside leg (b), the constant-velocity peers rollout, on the
+same members, shapes and windows; legs interleaved (b p b p ...).  No ratio is asked of it either.
 """
 import argparse
 import json
@@ -70,7 +75,7 @@ def leg(name, B, K, warm):
         sep = float(sc.peer_clearance(cars, states).min())
         u_last = [float(x) for x in controls[0].ravel()]
     else:
-        kw = dict(peers=True) if name == "peers" else dict(moving=True)
+        kw = dict(peers=True) if name == "peers" else dict(peers="plan") if name == "plan" else dict(moving=True)
         els = []
         for win in range(2):
             t0 = time.perf_counter()
@@ -80,7 +85,7 @@ def leg(name, B, K, warm):
             states = [out["states"][K, i].reshape(3, 1) for i in range(B)]
         el, first = els[1], els[0]
         iters = float(out["iters"].mean())
-        sep = float(out["peer_clearance"].min()) if name == "peers" else float(sc.peer_clearance(cars, states).min())
+        sep = float(out["peer_clearance"].min()) if name in ("peers", "plan") else float(sc.peer_clearance(cars, states).min())
         u_last = [float(x) for x in out["controls"][-1, 0]]
     f.close()
     return {"leg": name, "B": B, "K": K, "ego_steps_per_s": B * K / el, "ms_per_tick": 1e3 * el / K, "first_window_ego_steps_per_s": B * K / first,
@@ -95,6 +100,28 @@ def child(name, B, args):
     return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
 
 
+def plan_table(args):
+    print("peers predicted along their planned trajectories against peers at constant velocity, C5 shape with moving scenes (T = %d, N = %d slots, %d moving "
+          "polygons per ego, lanes %.0f m apart, re-sorted every tick): timed window of K = %d ticks behind a first window of K ticks; %d interleaved repeats"
+          % (T, N, N, LANE, args.K, args.repeats))
+    print('(b) Fleet.rollout(peers=True), the constant-velocity mode (the baseline);  (p) Fleet.rollout(peers="plan")')
+    print("%4s | %-32s | %-32s | %s" % ("B", "(b) peers rollout ego-steps/s", "(p) plan rollout ego-steps/s", "(p) / (b)"))
+    for B in args.fleets:
+        runs = {"peers": [], "plan": []}
+        for _ in range(args.repeats):
+            for name in runs:
+                runs[name].append(child(name, B, args))
+        rate = {name: [x["ego_steps_per_s"] for x in v] for name, v in runs.items()}
+        med = {name: float(np.median(v)) for name, v in rate.items()}
+        fmt = lambda v: " ".join("%9.0f" % x for x in v)        # noqa: E731
+        print("%4d | %-32s | %-32s | %.3fx" % (B, fmt(rate["peers"]), fmt(rate["plan"]), med["plan"] / med["peers"]))
+        print("       ms per fleet tick (medians): peers %.3f, plan %.3f; mean ADMM iterations per ego-step: peers %.3f, plan %.3f"
+              % tuple([np.median([x["ms_per_tick"] for x in runs[n]]) for n in runs] + [runs[n][0]["mean_admm_iters"] for n in runs]))
+        print("       first window (one-time set-up and the staging of the scenes included), medians: peers %.0f, plan %.0f ego-steps/s"
+              % tuple(np.median([x["first_window_ego_steps_per_s"] for x in runs[n]]) for n in runs))
+        print("       smallest member-to-member separation over the last window: peers %.3f m, plan %.3f m" % tuple(runs[n][0]["min_separation"] for n in runs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
@@ -103,11 +130,15 @@ def main():
     ap.add_argument("--warm", type=int, default=6)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--leg-timeout", type=float, default=400.0)
-    ap.add_argument("--leg", choices=["host", "peers", "blind"], default=None, help="(internal) run one measurement in this process and print it as JSON")
+    ap.add_argument("--plan", action="store_true", help="the plan rollout beside the constant-velocity peers rollout")
+    ap.add_argument("--leg", choices=["host", "peers", "blind", "plan"], default=None, help="(internal) run one measurement in this process and print it as JSON")
     ap.add_argument("--B", type=int, default=16)
     args = ap.parse_args()
     if args.leg:
         print(json.dumps(leg(args.leg, args.B, args.K, args.warm)))
+        return
+    if args.plan:
+        plan_table(args)
         return
     print("fleet members that avoid each other, C5 shape with moving scenes (T = %d, N = %d slots, %d moving polygons per ego, lanes %.0f m apart, re-sorted every tick): "
           "timed window of K = %d ticks behind %d host-driven ticks (host loop) or a first window of K ticks (rollouts); %d interleaved repeats"
