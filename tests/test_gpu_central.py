@@ -7,7 +7,9 @@ additionally pinned on the CPU (tests/test_ip_rows_emu.py: the same template on 
 Both return the point of the central path of the reference's cone program at the same barrier parameter mu - a well-conditioned
 function of the data - so the two implementations agree to ~1e-5 in the duals (un-normalised half-spaces put factors of 100 between
 a multiplier and Im) and within the stated 1e-4 closed-loop tolerance of tests/test_gpu_baseline_sizes.py in the controls.
-Covers the norm2 (circle) ROBOT cone of rda_solver.py:1034-1039, which the enumeration kernels do not have."""
+Covers the norm2 (circle) ROBOT cone of rda_solver.py:1034-1039, which the enumeration kernels do not have.
+The tight check of the kernels is tests/test_gpu_central_rows.py: every row of every launch form against an independent certified central point
+(tests/lmz_central_ref.py), measured <= 8.2e-9 (mu* = 1e-3) and <= 1.1e-8 (mu* = 1e-6) relative when accelerated, <= 1.3e-8 when not."""
 
 import numpy as np
 import pytest
