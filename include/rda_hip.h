@@ -262,6 +262,12 @@ const char *rda_lammuz_kernel(rda_handle *h);
  * with the step's result, costs no synchronisation (rda_upload_scene's n_nonconvex is the synchronous form). */
 int  rda_last_nonconvex(rda_handle *h);
 int  rda_upload_path(rda_handle *h, int L, const double *path /*L*3*/);
+/* All gear pieces of a path at once (MPC.split_path / curve_list of an enable_reverse path), for rda_fleet_rollout_gears: P pieces of len[p] waypoints and
+ * gear[p] = +1 / -1, `path` the pieces one behind the other, row-major [sum len][3].  They live in a buffer of their own, owned by the handle: rda_upload_path's
+ * path and everything that reads it are not touched.  A plain path is one piece with gear +1.  The last waypoint's heading of EVERY piece is rewritten by the
+ * ticks that reach its end (quirk Q12).  RDA_ERR_ARG: P < 1, a len < 1, a missing array.  A new upload replaces the old pieces once it holds everything: a
+ * refused allocation (RDA_ERR_HIP) leaves them in place. */
+int  rda_upload_path_pieces(rda_handle *h, int P, const int32_t *len /*P*/, const double *gear /*P*/, const double *path /*sum(len)*3*/);
 int  rda_step_tracked(rda_handle *h, const double *state /*3*/, double ref_speed, int cur_index, double threshold, int ind_range,
                       const double *nom_u, double *out_u, double *out_s, rda_info *info,
                       double *nom_s_out, double *ref_out, int32_t *min_index, double *end_heading);
@@ -426,6 +432,29 @@ int  rda_fleet_rollout_moving(rda_fleet *f, int K, const double *states /*B*3*/,
                               double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
                               rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
                               double *clearance_log /*K*B, or NULL*/);
+/* The two rollouts above for members whose paths have GEAR PIECES (reverse parking, the reference's example/reverse with enable_reverse=True): what MPC._piece,
+ * MPC._end (mpc.py:166-187) and the upload of the piece that comes into force do between two ticks, done by the gear form of the advance kernel.  moving = 0:
+ * rda_fleet_rollout's arguments, logs and refusals (clearance_log must be NULL); moving != 0: rda_fleet_rollout_moving's.  Differences: every member's pieces
+ * are those of rda_upload_path_pieces (its rda_upload_path path is neither needed nor read, and a host-driven tick afterwards still uses it); ref_speed [B] is
+ * UNSIGNED - the tracker's speed on piece p is the single product gear[p] * ref_speed; piece0 [B] is the piece in force at tick 0 and cur_index [B] an index
+ * within it.  Rule of the tick that ends with min_index in piece p of length Lp: with min_index >= Lp - goal_margin and p + 1 < P the member has NOT arrived -
+ * the tick's first control is applied as usual, piece p + 1 is in force from the next tick on with cur_index = 0 and its signed speed, and the nominal
+ * controls are kept; with p + 1 == P it arrives as in rda_fleet_rollout and stays on its last piece; otherwise nothing changes.  piece_log [K][B]: the piece
+ * in force during tick k; index_log is the index within that piece.  Given a state, a tick computes bit for bit what rda_upload_path of the piece (on the tick
+ * it comes into force) + rda_fleet_scene_resort / rda_fleet_upload_scenes + rda_fleet_step_tracked compute.  Additional refusals (RDA_ERR_ARG): a member
+ * without resident pieces, piece0[i] outside [0, P_i), cur_index[i] outside that piece, a missing piece0 / piece_log.  A refused call queues nothing; a
+ * refused allocation: RDA_ERR_HIP, fleet and members as they were.  Members as each other's obstacles and lidar rollouts are not served with gear pieces.
+ * rda_fleet_rollout_last serves this entry too (end_heading: of the piece of the last tick). */
+int  rda_fleet_rollout_gears(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B, unsigned*/,
+                             const int32_t *piece0 /*B*/, const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                             int resort, int moving, const double *nom_u /*B*2*T or NULL = resident*/,
+                             double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                             rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                             int32_t *piece_log /*K*B*/, double *clearance_log /*K*B, or NULL*/);
+/* of the last rda_fleet_rollout_gears, what the host needs to continue: every member's piece after its last tick (the last piece for a member that arrived)
+ * and the heading the last waypoint of every piece has now (quirk Q12), member-major [sum P_i].  Either may be NULL.  No device work.  RDA_ERR_ARG unless the
+ * fleet's last rollout was a gear rollout. */
+int  rda_fleet_rollout_last_pieces(rda_fleet *f, int32_t *piece /*B or NULL*/, double *end_headings /*sum P_i or NULL*/);
 /* every member's clearance (as in clearance_log above) at states [B][3] against its resident raw scene as it stands: one launch, one wait.
  * RDA_ERR_UNSUPPORTED: a norm2 robot; RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_clearance(rda_fleet *f, const double *states /*B*3*/, double *clearance /*B*/);

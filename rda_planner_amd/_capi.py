@@ -83,6 +83,7 @@ PROTOTYPES = {
     "lammuz_kernel":        "s h",
     "last_nonconvex":       "i h",
     "upload_path":          "i hiD",
+    "upload_path_pieces":   "i hiIDD",
     "step_tracked":         "i hDdidiDDDNDDID",
     "tracked_begin":        "i hDdidiD",
     "upload_scene_async":   "i hiIIDDDi",
@@ -103,6 +104,8 @@ PROTOTYPES = {
     "fleet_rollout":        "i hiDDIdiiiDDDINI",
     "fleet_rollout_last":   "i hDD",
     "fleet_rollout_moving": "i hiDDIdiiiDDDINID",
+    "fleet_rollout_gears":  "i hiDDIIdiiiiDDDINIID",
+    "fleet_rollout_last_pieces": "i hID",
     "fleet_clearance":      "i hDD",
     "fleet_upload_scenes_peers": "i hIIIDDDD",
     "fleet_scene_resort_peers":  "i hDD",
@@ -204,6 +207,7 @@ class CApi:
         self.has_fleet_rollout = has("fleet_rollout")                       # K closed-loop ticks on the device, one host wait
         self.has_fleet_rollout_moving = has("fleet_rollout_moving")         # ... for scenes that move
         self.has_fleet_rollout_lidar = has("fleet_rollout_lidar")           # ... around the simulated sensor
+        self.has_fleet_rollout_gears = has("fleet_rollout_gears")           # ... over the gear pieces of reverse paths
         self.has_fleet_peers = has("fleet_rollout_peers")                   # members as each other's obstacles, staged on the device
         self.has_fleet_peers_plan = has("fleet_rollout_peers_plan")         # ... predicted along their planned trajectories
 

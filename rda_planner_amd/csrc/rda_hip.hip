@@ -17,6 +17,7 @@
 // between iterations and between MPC steps, exactly like the reference keeps it in CVXPY Parameter
 // values (quirks Q4-Q6 come for free).
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1417,6 +1418,13 @@ struct TraceSet {                         // rda_upload_trace: K steps' inputs a
     }
 };
 struct PathSet { hbuf::Group g; double *d = nullptr; int len = 0; };     // device-side pre_process (rda_upload_path / rda_step_tracked): the path [len][3]
+// the gear pieces of a path (rda_upload_path_pieces / rda_fleet_rollout_gears), apart from `path`: all P pieces in one buffer [off[P]][3], the first waypoint
+// of every piece off [P+1] and its gear [P] on the device, the tables' host copies beside them
+struct PieceSet {
+    hbuf::Group g; double *buf = nullptr, *gear = nullptr; int *off = nullptr; int P = 0; std::vector<int> h_off; std::vector<double> h_gear;
+    int alloc(int p, size_t total) { P = p; return (g.dev(&buf, 3 * total) | g.dev(&off, (size_t)p + 1) | g.dev(&gear, (size_t)p)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return buf != nullptr; }
+};
 // The raw scene block, identical on the host (pinned) and on the device:  geom [n][E][2] | vel [n][2] | robot [2] | nonconvex counter (int, padded to 8
 // bytes) | kind [n] | nvert [n].  Offsets in doubles, size in bytes.
 struct SceneLayout { size_t vel, robot, nonconvex, ints, bytes; };
@@ -1486,7 +1494,7 @@ struct rda_handle {
     hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL) and the four sets below
     hbuf::Group terms;                    // Dev::coef, coefL (rda_shard_config replaces them)
     StageBufs stage; hbuf::Pair<double> step; ResultBlock res; FollowSet fol;      // step: the step block (step_doubles), pinned and on the device
-    TraceSet trace; PathSet path; SceneSet sc; LidarSet li; ShardLink shard; OpenTick tick;
+    TraceSet trace; PathSet path; PieceSet pieces; SceneSet sc; LidarSet li; ShardLink shard; OpenTick tick;
     std::vector<hbuf::Event> ev[4];
     hbuf::Event ev_tick, ev_scene;
     hbuf::Stream stream, stream2;         // (last: destroyed first)
@@ -2345,6 +2353,26 @@ extern "C" int rda_upload_path(rda_handle *H, int L, const double *path)
     return RDA_OK;
 }
 
+// All gear pieces of a path (MPC.curve_list) resident at once, for rda_fleet_rollout_gears: `path` holds the P pieces one behind the other.  `H->path` and
+// what reads it are not involved.  The new set is built beside the old one and replaces it once it holds everything.
+extern "C" int rda_upload_path_pieces(rda_handle *H, int P, const int32_t *len, const double *gear, const double *path)
+{
+    if (!H || P < 1 || !len || !gear || !path) return RDA_ERR_ARG;
+    PieceSet t;
+    t.h_off.assign((size_t)P + 1, 0); t.h_gear.assign(gear, gear + P);
+    for (int p = 0; p < P; ++p) {
+        if (len[p] < 1 || len[p] > INT_MAX / 3 - t.h_off[p]) return RDA_ERR_ARG;
+        t.h_off[p + 1] = t.h_off[p] + len[p];
+    }
+    HIPCHK(hipStreamSynchronize(H->stream));
+    if (t.alloc(P, (size_t)t.h_off[P])) return RDA_ERR_HIP;
+    HIPCHK(hipMemcpy(t.buf, path, (size_t)3 * t.h_off[P] * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.off, t.h_off.data(), ((size_t)P + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.gear, t.h_gear.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    H->pieces = std::move(t);
+    return RDA_OK;
+}
+
 extern "C" int rda_tracked_begin(rda_handle *H, const double *state, double ref_speed, int cur_index, double threshold, int ind_range,
                                  const double *nom_u)
 {
@@ -3040,6 +3068,18 @@ struct FleetPlan {
     int alloc(size_t B, size_t T) { return (plan.alloc(g, B * traj_s(T)) | valid.alloc(g, B)) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return plan.d != nullptr; }
 };
+// the gear rollout (rda_fleet_rollout_gears): per member the record of its resident pieces; the tables the tracker and the advance kernel share - the piece in
+// force and what k_track_fleet reads as the member's path and length [B] (the rollout's own: trk.paths / lens keep the rda_upload_path paths)
+struct FleetGears {
+    hbuf::Group g; hbuf::Pair<rollout::Gears> rec; hbuf::Pair<int> piece, lens; hbuf::Pair<double *> paths;
+    int alloc(size_t B) { return (rec.alloc(g, B) | piece.alloc(g, B) | lens.alloc(g, B) | paths.alloc(g, B)) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return rec.d != nullptr; }
+};
+struct FleetInts {                        // v.n ints, regrown when a call needs more: the piece log [K][B]
+    hbuf::Group g; hbuf::Pair<int> v;
+    int alloc(size_t n) { return v.alloc(g, n) ? RDA_ERR_HIP : RDA_OK; }
+    bool have() const { return v.d != nullptr; }
+};
 // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
 // tick overwrites with boxes.  Member-major geometry [total][e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
 // vertex counts; off[i]: member i's first obstacle.  Per member the ray caster's, the move kernel's and the clearance kernel's arguments and the poses of
@@ -3080,6 +3120,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
     FleetPeers pe; FleetDoubles pc_log; std::vector<int> n_own;   // pc_log: the peer clearance log; n_own: every member's own obstacles as the last peers upload staged them
     FleetPlan pl;
+    FleetGears gr; FleetInts gr_log; FleetDoubles gr_endh; int gear_total;      // gr_endh: the pieces' end headings; gear_total: the pieces of all members of the gear rollout whose logs are on the host (0: none)
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
@@ -3580,12 +3621,13 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
 // ---- rda_fleet_rollout: K closed-loop ticks queued back to back, ONE host wait ---------------------------------------------------------------------
 // Per tick the launches of the host loop (closed_loop_fleet_run: re-sort, k_track_fleet, the ADMM launches) and rollout::k_rollout_advance, which does on
 // the device what that loop's host does between two ticks and writes the next tick's inputs where these kernels read them.
-// What the three entries (rda_fleet_rollout, _moving, _lidar) take alike; clearance_log: null for the static entry
+// What the entries (rda_fleet_rollout, _moving, _lidar, _peers*, _gears) take alike; clearance_log: null for the static entry
 struct RollArgs {
     int K; const double *states, *ref_speed; const int32_t *cur_index; double threshold; int ind_range, goal_margin; const double *nom_u;
     double *states_log, *u_log; int32_t *index_log; rda_info *info_log; int32_t *arrived_at; double *clearance_log;
     bool peers = false; const double *controls0 = nullptr; double *peer_clearance_log = nullptr;     // rda_fleet_rollout_peers
     bool plan = false; const double *plans0 = nullptr; const int32_t *plan_valid0 = nullptr;          // rda_fleet_rollout_peers_plan (with peers)
+    bool gears = false; const int32_t *piece0 = nullptr; int32_t *piece_log = nullptr;                // rda_fleet_rollout_gears: ref_speed unsigned, cur_index within piece0
 };
 // the argument rules every entry has: of the arrays and counts, and (roll_check_members) of the members' paths
 static int roll_check_args(const rda_fleet *F, const RollArgs &a)
@@ -3598,6 +3640,17 @@ static int roll_check_members(const rda_fleet *F, const int32_t *cur_index)
     for (int i = 0; i < F->B; ++i) {
         const rda_handle *H = F->egos[i];
         if (!H->path.d || cur_index[i] < 0 || cur_index[i] >= H->path.len || H->tick.pending) return RDA_ERR_ARG;
+    }
+    return RDA_OK;
+}
+// ... of their resident pieces: the gear rollout does not read the members' rda_upload_path paths
+static int roll_check_pieces(const rda_fleet *F, const RollArgs &a)
+{
+    if (!a.piece0 || !a.piece_log) return RDA_ERR_ARG;
+    for (int i = 0; i < F->B; ++i) {
+        const PieceSet &ps = F->egos[i]->pieces;
+        if (!ps.have() || a.piece0[i] < 0 || a.piece0[i] >= ps.P || F->egos[i]->tick.pending) return RDA_ERR_ARG;
+        if (a.cur_index[i] < 0 || a.cur_index[i] >= ps.h_off[a.piece0[i] + 1] - ps.h_off[a.piece0[i]]) return RDA_ERR_ARG;
     }
     return RDA_OK;
 }
@@ -3713,7 +3766,7 @@ struct RollReserve {
         if (tab.have()) F->ro = std::move(tab);
         if (log.have()) F->ro_log = std::move(log);
         if (clr.have()) F->cl_log = std::move(clr);
-        F->roll_K = 0;                                                          // (until this rollout's logs are on the host)
+        F->roll_K = 0; F->gear_total = 0;                                       // (until this rollout's logs are on the host)
         return RDA_OK;
     }
 };
@@ -3749,7 +3802,9 @@ static int fleet_roll_upload(rda_fleet *F, const RollView &v)
 // tick 0's nominal controls and tracker inputs, as rda_fleet_step_tracked uploads them; lg: the device logs of this rollout, arrived_at reset to -1
 static int fleet_roll_inputs(rda_fleet *F, const RollLayout &lay, const RollArgs &a, rollout::Logs &lg)
 {
-    int rc = fleet_track_inputs(F, a.states, a.ref_speed, a.cur_index, a.threshold, a.ind_range, a.nom_u);
+    std::vector<double> signed_speed;                                           // gears: the single product gear * ref_speed of every member's first piece
+    if (a.gears) for (int i = 0; i < F->B; ++i) signed_speed.push_back(F->egos[i]->pieces.h_gear[a.piece0[i]] * a.ref_speed[i]);
+    int rc = fleet_track_inputs(F, a.states, a.gears ? signed_speed.data() : a.ref_speed, a.cur_index, a.threshold, a.ind_range, a.nom_u);
     if (rc != RDA_OK) return rc;
     char *log = F->ro_log.log.d;
     lg.states = (double *)(log + lay.states); lg.u = (double *)(log + lay.u); lg.end_heading = (double *)(log + lay.endh);
@@ -3761,16 +3816,22 @@ static int fleet_roll_inputs(rda_fleet *F, const RollLayout &lay, const RollArgs
 // the robots' positions for the next re-sort, or null), then (mv: the raw scenes' or the world's move table, null: nothing moves) scene::k_move_fleet over
 // `gmove` and (cl: their clearance table, null: no clearance log) k_clearance_fleet of state k + 1 against the geometry of tick k + 1.
 static int fleet_roll_tail(rda_fleet *F, int k, const rollout::Logs &lg, int goal_margin, double *rob, const scene::Move *mv, dim3 gmove,
-                           const rollout::Clear *cl)
+                           const rollout::Clear *cl, const rollout::GearTab *gt = nullptr)
 {
     const size_t B = F->B;
     FleetTrack &trk = F->trk;
     const EgoIO *io = F->ro.io.d + (k == 0 ? 0 : B);
-    hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->devs.d, io, trk.in.d, trk.paths.d, trk.lens.d, trk.out.d, (int)B);
+    // gt: a gear rollout - the tracker reads the piece in force from the rollout's tables, which the gear form of the advance kernel rewrites at a switch
+    hipLaunchKernelGGL(k_track_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, F->devs.d, io, trk.in.d, gt ? gt->paths : trk.paths.d,
+                       gt ? (const int *)gt->lens : trk.lens.d, trk.out.d, (int)B);
     int rc = fleet_enqueue(F, io, 0);
     if (rc != RDA_OK) return rc;
-    hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->ro.m.d,
-                       (const track::Out *)trk.out.d, trk.in.d, rob, lg, k, goal_margin, (int)B);
+    if (gt)
+        hipLaunchKernelGGL(rollout::k_rollout_advance_gears, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->ro.m.d,
+                           (const track::Out *)trk.out.d, trk.in.d, rob, lg, k, goal_margin, (int)B, *gt);
+    else
+        hipLaunchKernelGGL(rollout::k_rollout_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Member *)F->ro.m.d,
+                           (const track::Out *)trk.out.d, trk.in.d, rob, lg, k, goal_margin, (int)B);
     if (mv) hipLaunchKernelGGL(scene::k_move_fleet, gmove, dim3(256), 0, F->stream, mv, k + 1);      // where tick k + 1 finds them
     if (cl)
         hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, cl,
@@ -3785,12 +3846,20 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     if (a.clearance_log) HIPCHK(F->cl_log.v.pull(F->stream, K * B));
     const bool peer_log = a.peer_clearance_log && B > 1;                        // (a fleet of one: +inf, nothing was launched)
     if (peer_log) HIPCHK(F->pc_log.v.pull(F->stream, K * B));
+    size_t gear_total = 0;
+    if (a.gears) {                                                              // the piece log, every member's piece now and the pieces' end headings (Q12)
+        for (const rda_handle *Hm : F->egos) gear_total += (size_t)Hm->pieces.P;
+        hipLaunchKernelGGL(rollout::k_gear_headings, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, F->stream, (const rollout::Gears *)F->gr.rec.d, F->gr_endh.v.d, (int)B);
+        HIPCHK(hipGetLastError());
+        HIPCHK(F->gr_log.v.pull(F->stream, K * B)); HIPCHK(F->gr.piece.pull(F->stream, B)); HIPCHK(F->gr_endh.v.pull(F->stream, gear_total));
+    }
     HIPCHK(hipMemcpyAsync(F->ro_log.log.d + lay.last, F->out.d, B * res_info(T) * sizeof(double), hipMemcpyDeviceToDevice, F->stream));      // the last tick's full controls and planned states, beside the logs
     HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;                  // their staged scenes have been consumed
-    F->roll_K = a.K;
+    F->roll_K = a.K; F->gear_total = (int)gear_total;
+    if (a.gears) memcpy(a.piece_log, F->gr_log.v.h, K * B * sizeof(int32_t));
     memcpy(a.states_log, a.states, B * 3 * sizeof(double));                     // row 0: the input
     memcpy(a.states_log + B * 3, log + lay.states + B * 3 * sizeof(double), K * B * 3 * sizeof(double));
     memcpy(a.u_log, log + lay.u, K * B * 2 * sizeof(double));
@@ -3808,9 +3877,11 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
 static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, bool moving)
 {
     int rc = roll_check_args(F, a);
-    if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
+    if (rc == RDA_OK) rc = a.gears ? roll_check_pieces(F, a) : roll_check_members(F, a.cur_index);
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
+    size_t gear_total = 0;
+    if (a.gears) for (const rda_handle *H : F->egos) gear_total += (size_t)H->pieces.P;
     if (a.peers) {
         if (!a.controls0 || (a.plan && (!a.plans0 || !a.plan_valid0))) return RDA_ERR_ARG;
         for (size_t i = 0; i < B; ++i) if (!member_peers_scene(F, i)) return RDA_ERR_ARG;      // the scenes of rda_fleet_upload_scenes_peers, nothing staged since
@@ -3831,9 +3902,12 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     }
     const bool peer_log = a.peers && a.peer_clearance_log && B > 1;
     // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc; FleetPlan tpl;
+    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc; FleetPlan tpl; FleetGears tgr; FleetInts tgl; FleetDoubles tge;
     {
         int bad = rsv.alloc(F, a.K, a.clearance_log != nullptr);
+        if (a.gears && !F->gr.have()) bad |= tgr.alloc(B);
+        if (a.gears && (size_t)a.K * B > F->gr_log.v.n) bad |= tgl.alloc((size_t)a.K * B);
+        if (a.gears && gear_total > F->gr_endh.v.n) bad |= tge.alloc(gear_total);
         if (peer_log && (size_t)a.K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)a.K * B);
         if (a.plan && !F->pl.have()) bad |= tpl.alloc(B, T);
         if (resort && !F->res.have()) bad |= tres.alloc(B);
@@ -3841,8 +3915,11 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         if (moving && mvw.mv_total > F->snap.cap) bad |= tsnap.alloc(mvw.mv_total);
         if (bad) return RDA_ERR_HIP;
     }
-    rc = rsv.move_in(F, tsnap.have() || tpc.have());
+    rc = rsv.move_in(F, tsnap.have() || tpc.have() || tgl.have() || tge.have());
     if (rc != RDA_OK) return rc;
+    if (tgr.have()) F->gr = std::move(tgr);
+    if (tgl.have()) F->gr_log = std::move(tgl);
+    if (tge.have()) F->gr_endh = std::move(tge);
     if (tpc.have()) F->pc_log = std::move(tpc);
     if (tpl.have()) F->pl = std::move(tpl);
     if (tres.have()) F->res = std::move(tres);
@@ -3885,6 +3962,20 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     rollout::Logs lg;
     rc = fleet_roll_inputs(F, lay, a, lg);
     if (rc != RDA_OK) return rc;
+    // gears: the members' piece records and tick 0's tables (the device rewrites them, so they travel on every call; nothing queued reads the mirrors)
+    rollout::GearTab gt;
+    if (a.gears) {
+        int hbase = 0;
+        for (size_t i = 0; i < B; ++i) {
+            const PieceSet &ps = F->egos[i]->pieces;
+            const int p = a.piece0[i];
+            F->gr.rec.h[i] = rollout::Gears{ ps.buf, ps.off, ps.gear, ps.P, hbase, a.ref_speed[i] };
+            F->gr.piece.h[i] = p; F->gr.paths.h[i] = ps.buf + 3 * (size_t)ps.h_off[p]; F->gr.lens.h[i] = ps.h_off[p + 1] - ps.h_off[p];
+            hbase += ps.P;
+        }
+        HIPCHK(F->gr.rec.push(F->stream)); HIPCHK(F->gr.piece.push(F->stream)); HIPCHK(F->gr.paths.push(F->stream)); HIPCHK(F->gr.lens.push(F->stream));
+        gt = rollout::GearTab{ F->gr.rec.d, F->gr.piece.d, F->gr.paths.d, F->gr.lens.d, F->gr_log.v.d };
+    }
     const bool moves = moving && mvw.gmax > 0;
     const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
     if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->mov.mv.d);      // `base`: the geometry as the call finds it
@@ -3897,7 +3988,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         if (resort) fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax, a.plan ? &pk : nullptr);      // about res.rob: the caller's positions (tick 0), then the advance kernel's
         else if (moves) fleet_resort_launch(F, F->mov.sc.d, nullptr, mvw.nmax, mvw.wmax);     // a scene that moved: its slots rebuilt in the staged order
         rc = fleet_roll_tail(F, k, lg, a.goal_margin, resort ? F->res.rob.d : nullptr, moves ? F->mov.mv.d : nullptr, gmove,
-                             a.clearance_log ? F->mov.cl.d : nullptr);
+                             a.clearance_log ? F->mov.cl.d : nullptr, a.gears ? &gt : nullptr);
         if (rc != RDA_OK) return rc;
         if (peer_log)
             hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
@@ -3922,6 +4013,26 @@ extern "C" int rda_fleet_rollout_moving(rda_fleet *F, int K, const double *state
 {
     return fleet_rollout_scenes(F, RollArgs{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log,
                                              arrived_at, clearance_log }, resort, true);
+}
+// The rollouts above for members whose paths have gear pieces (rda_upload_path_pieces): MPC._piece / _end / _sync_path of a reverse path on the device.
+// moving = 0: rda_fleet_rollout, else rda_fleet_rollout_moving; the same body, its tracker reading the rollout's own path tables.
+extern "C" int rda_fleet_rollout_gears(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *piece0, const int32_t *cur_index,
+                                       double threshold, int ind_range, int goal_margin, int resort, int moving, const double *nom_u, double *states_log,
+                                       double *u_log, int32_t *index_log, rda_info *info_log, int32_t *arrived_at, int32_t *piece_log, double *clearance_log)
+{
+    if (!moving && clearance_log) return RDA_ERR_ARG;                          // (the clearance log belongs to the moving form)
+    RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    a.gears = true; a.piece0 = piece0; a.piece_log = piece_log;
+    return fleet_rollout_scenes(F, a, resort, moving != 0);
+}
+// of the last rda_fleet_rollout_gears: every member's piece after its last tick, and the heading the last waypoint of every piece has now (quirk Q12),
+// member-major.  Either may be null.  No device work.
+extern "C" int rda_fleet_rollout_last_pieces(rda_fleet *F, int32_t *piece, double *end_headings)
+{
+    if (!F || F->roll_K < 1 || F->gear_total < 1) return RDA_ERR_ARG;
+    if (piece) memcpy(piece, F->gr.piece.h, (size_t)F->B * sizeof(int32_t));
+    if (end_headings) memcpy(end_headings, F->gr_endh.v.h, (size_t)F->gear_total * sizeof(double));
+    return RDA_OK;
 }
 // every member's clearance at states [B][3] against its resident raw scene as it stands: the rollout's kernel, one launch, one wait
 extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *clearance)

@@ -32,18 +32,40 @@ struct Logs {                 // device logs of one rollout (one block, copied t
     double *end_heading;      // [B]           track::Out::end_heading of the last tick (quirk Q12: the value the last waypoint's heading now has)
 };
 
-// rob: the re-sort's robot positions [B][2], null when the rollout does not re-sort
-__global__ void k_rollout_advance(const Member *ms, const track::Out *trk_out, track::In *trk_in, double *rob, Logs lg, int k, int goal_margin, int B)
+// The gear pieces of reverse paths (rda_fleet_rollout_gears): the bookkeeping of MPC._piece / _end / _sync_path (mpc.py:139-147, 166-187) on the device.
+// Per member, constant over a rollout: the resident pieces of rda_upload_path_pieces and the call's unsigned reference speed ...
+struct Gears {
+    double *buf;              // [sum len][3] all pieces, one behind the other (the last waypoint's heading of every piece is rewritten by the tracker, Q12)
+    const int *off;           // [P+1] first waypoint of every piece
+    const double *gear;       // [P] +1 / -1
+    int P, hbase;             // pieces; the member's first entry of the member-major heading array (k_gear_headings)
+    double ref_speed;         // unsigned: In::speed of a piece is the single product gear[p] * ref_speed
+};
+// ... and the tables of a gear rollout, written by the host for tick 0 and by the advance kernel for tick k + 1: the piece in force [B], what k_track_fleet
+// reads as the members' paths and lengths [B] (the piece's place in `buf`), and the log piece_log [K][B] of the piece in force during tick k
+struct GearTab { const Gears *rec; int *piece; double **paths; int *lens; int *piece_log; };
+
+// One member's step between two ticks.  gt null: a plain path of m.L waypoints.  With gear pieces the arrival rule is MPC._end's: at the end of a piece
+// that another one follows the member has not arrived - the control is applied, the next piece comes into force with cur_index = 0 and its signed speed; at
+// the end of the last piece it arrives as a plain member does and stays on that piece.  The nominal controls are not touched (the reference keeps
+// cur_vel_array over a switch).
+__device__ __forceinline__ void advance_member(const Member *ms, const track::Out *trk_out, track::In *trk_in, double *rob, const Logs &lg, int k, int goal_margin,
+                                               int B, int i, const GearTab *gt)
 {
 #pragma clang fp contract(off)        // the host loop's compiler does not fuse either: every product and sum separately rounded
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
     const Member m = ms[i];
     const track::Out o = trk_out[i];
     track::In in = trk_in[i];
     const size_t row = (size_t)k * B + i;
     int arrived = lg.arrived_at[i];
-    if (arrived < 0 && o.min_index >= m.L - goal_margin) { arrived = k; lg.arrived_at[i] = k; }
+    const int L = gt ? gt->lens[i] : m.L;
+    int p = 0;
+    bool next_piece = false;
+    if (gt) { p = gt->piece[i]; gt->piece_log[row] = p; }
+    if (arrived < 0 && o.min_index >= L - goal_margin) {
+        if (gt && p + 1 < gt->rec[i].P) next_piece = true;
+        else { arrived = k; lg.arrived_at[i] = k; }
+    }
     double v = 0.0, w = 0.0;
     if (arrived < 0) {
         v = m.out_u[0]; w = m.out_u[m.T];
@@ -53,6 +75,13 @@ __global__ void k_rollout_advance(const Member *ms, const track::Out *trk_out, t
         else { in.sx += m.dt * (v * cos(w)); in.sy += m.dt * (v * sin(w)); }
     }
     in.cur_index = o.min_index;
+    if (next_piece) {
+        const Gears g = gt->rec[i];
+        p = p + 1;
+        const int first = g.off[p];
+        gt->piece[i] = p; gt->paths[i] = g.buf + 3 * (size_t)first; gt->lens[i] = g.off[p + 1] - first;
+        in.cur_index = 0; in.speed = g.gear[p] * g.ref_speed;
+    }
     trk_in[i] = in;
     if (rob) { rob[2 * i] = in.sx; rob[2 * i + 1] = in.sy; }
     double *s = lg.states + ((size_t)(k + 1) * B + i) * 3;
@@ -61,6 +90,30 @@ __global__ void k_rollout_advance(const Member *ms, const track::Out *trk_out, t
     lg.index[row] = o.min_index;
     lg.info[row] = *m.info;
     lg.end_heading[i] = o.end_heading;
+}
+
+// rob: the re-sort's robot positions [B][2], null when the rollout does not re-sort
+__global__ void k_rollout_advance(const Member *ms, const track::Out *trk_out, track::In *trk_in, double *rob, Logs lg, int k, int goal_margin, int B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    advance_member(ms, trk_out, trk_in, rob, lg, k, goal_margin, B, i, nullptr);
+}
+// ... of a gear rollout
+__global__ void k_rollout_advance_gears(const Member *ms, const track::Out *trk_out, track::In *trk_in, double *rob, Logs lg, int k, int goal_margin, int B,
+                                        GearTab gt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    advance_member(ms, trk_out, trk_in, rob, lg, k, goal_margin, B, i, &gt);
+}
+// behind the last tick: the heading the last waypoint of every piece has now (quirk Q12), member-major - out[hbase + p]
+__global__ void k_gear_headings(const Gears *gs, double *out, int B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const Gears g = gs[i];
+    for (int p = 0; p < g.P; ++p) out[g.hbase + p] = g.buf[3 * (size_t)(g.off[p + 1] - 1) + 2];
 }
 
 // Robot / obstacle clearance of every member on the device (rda_fleet_rollout_moving's clearance log, rda_fleet_clearance): scenarios.clearance for a polygon

@@ -407,10 +407,20 @@ class Fleet:
         only).  `resort` does not apply, `lidar=` / `scans=` cannot be combined with it, and it has the refusals of `control(peers=True)`.
         `peers="plan"` (rda_fleet_rollout_peers_plan): as `control(peers="plan")` - tick 0 predicts every member along the plan this fleet holds of
         it (if it counts), every later tick along the plan its solve of the tick before left on the device, while it has not arrived.  Returns what
-        `peers=True` returns; the same number of launches per tick."""
+        `peers=True` returns; the same number of launches per tick.
+        `gears=True` (rda_fleet_rollout_gears): members with `enable_reverse=True` are taken, plain members may be mixed in (one piece, gear +1).
+        Every member's `curve_list` is uploaded, and the device does what `MPC._piece` / `_end` do between two ticks: at the end of a piece that
+        another one follows the member goes on with the next piece from its index 0 at `gear * ref_speed` (`ref_speeds` unsigned, as for `control`),
+        at the end of the last piece it arrives.  `moving`, `clearance`, `resort` and `obstacle_lists` keep their meaning; `peers`, `lidar` and
+        `scans` cannot be combined with it.  The result has `"piece"` (steps, B) as well, the piece in force during each tick, and `index` counts
+        within that piece.  Afterwards `curve_index` / `cur_index` are as `_end` leaves them and every piece's last waypoint carries the heading the
+        device gave it (Q12), so `control` continues on the right piece.  Without `gears=True` such members are refused."""
         ms = self.members
         kwargs = dict(kwargs)
+        gears = bool(kwargs.pop("gears", False))
         peers, plan = peers_mode(kwargs.pop("peers", False))
+        if gears and (peers or kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
+            raise ValueError("Fleet.rollout: gears=True cannot be combined with peers / lidar= / scans=")
         if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
             raise ValueError("Fleet.rollout: peers=True cannot be combined with lidar= / scans=")
         if peers:
@@ -432,8 +442,10 @@ class Fleet:
                 raise ValueError("Fleet.rollout: scan_eps > 0 and scan_min_samples >= 1")
             if not getattr(self.api, "has_fleet_rollout_lidar", False) or any(m.rda_obstacle for m in ms):
                 raise RuntimeError("Fleet.rollout(lidar=...) needs the lidar rollout (rda_fleet_rollout_lidar); there is no host fallback")
-        if any(m.enable_reverse for m in ms) or not all(m._tracks(kwargs) for m in ms):
-            raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False; there is no host fallback")
+        if (not gears and any(m.enable_reverse for m in ms)) or not all(m._tracks(kwargs) for m in ms):
+            raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False (or gears=True); there is no host fallback")
+        if gears and not getattr(self.api, "has_fleet_rollout_gears", False):
+            raise RuntimeError("the loaded solver library has no rollout over gear pieces (rda_fleet_rollout_gears)")
         if not getattr(self.api, "has_fleet_rollout", False):
             raise RuntimeError("the loaded solver library has no fleet rollout entry point (rda_fleet_rollout)")
         if moving and not getattr(self.api, "has_fleet_rollout_moving", False):
@@ -450,7 +462,10 @@ class Fleet:
         B, T, K = len(ms), ms[0].receding, int(steps)
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
-        st, speed, cur, _, nom_u = self._gather(states, ref_speeds)
+        if gears:
+            st, speed, cur, piece0, nom_u = self._gather_gears(states, ref_speeds)
+        else:
+            st, speed, cur, _, nom_u = self._gather(states, ref_speeds)
         if world is not None:
             self.upload_worlds(world)
         ctl0 = f64([np.asarray(m.cur_vel_array, float)[:, 0] for m in ms], (B, 2)) if peers else None
@@ -468,7 +483,11 @@ class Fleet:
         logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
         c_log = np.zeros((max(K, 0), B)) if clearance else None
         p_log = np.zeros((max(K, 0), B)) if peers else None
-        if plan:
+        g_log = np.zeros((max(K, 0), B), np.int32) if gears else None
+        if gears:
+            rc, name = self.api.fleet_rollout_gears(self._handle, K, dptr(st), dptr(speed), iptr(piece0), iptr(cur), *head[5:], 1 if resort else 0,
+                                                    1 if moving else 0, dptr(nom_u), *logs, iptr(g_log), dptr(c_log)), "fleet_rollout_gears"
+        elif plan:
             plans, valid = self._plan_state()
             rc, name = self.api.fleet_rollout_peers_plan(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log), dptr(plans),
                                                          iptr(valid)), "fleet_rollout_peers_plan"
@@ -495,13 +514,16 @@ class Fleet:
             if rc < 0:
                 raise self.api.failed("fleet_rollout_last_plan", rc)
             valid[:] = arrived < 0
+        if gears:
+            self._scatter_gears(g_log[K - 1], i_log[K - 1], arrived)
         for i, m in enumerate(ms):
             path = m.ref_path
             m.state = s_log[K, i].reshape(3, 1).copy()
-            m.cur_index = int(i_log[K - 1, i])
-            path[-1][2, 0] = eh[i]                         # quirk Q12: the device rewrote the last waypoint's heading in its copy
-            if m._dev_path_key is not None and m._dev_path_key[0] is path:
-                m._dev_path_key[1][-1] = path[-1].tobytes()
+            if not gears:
+                m.cur_index = int(i_log[K - 1, i])
+                path[-1][2, 0] = eh[i]                     # quirk Q12: the device rewrote the last waypoint's heading in its copy
+                if m._dev_path_key is not None and m._dev_path_key[0] is path:
+                    m._dev_path_key[1][-1] = path[-1].tobytes()
             if arrived[i] >= 0:                            # like _end: the robot stands, the next solve starts from zero controls
                 m.cur_vel_array = np.zeros((2, T))
                 m._dev_u = None
@@ -515,6 +537,8 @@ class Fleet:
             out["boxes"] = b_log
         if peers:
             out["peer_clearance"] = p_log
+        if gears:
+            out["piece"] = g_log
         return out
 
     def clearance(self, states):
@@ -546,12 +570,65 @@ class Fleet:
             speed[i], cur[i] = gear * ref_speeds[i], m.cur_index
             resident = resident and m._nominal_u() is None
             pieces.append(cur_ref_path)
-        nom_u = None
-        if not resident:            # some member's cur_vel_array was replaced since its last solve: send them all
-            for i, m in enumerate(self.members):
-                self._in_u[i] = f64(m.cur_vel_array, (2, T))
-            nom_u = self._in_u
-        return st, speed, cur, pieces, nom_u
+        return st, speed, cur, pieces, self._nominal_all(resident)
+
+    def _nominal_all(self, resident):
+        """the nominal controls (B, 2, T) of a device-tracked tick; None when the device still holds every member's (`resident`)"""
+        if resident:
+            return None
+        T = self.members[0].receding
+        for i, m in enumerate(self.members):        # some member's cur_vel_array was replaced since its last solve: send them all
+            self._in_u[i] = f64(m.cur_vel_array, (2, T))
+        return self._in_u
+
+    @staticmethod
+    def _gear_pieces(m):
+        """a member's pieces as `MPC._piece` indexes them; a plain member is one piece with gear +1"""
+        return m.curve_list if m.enable_reverse else [m.ref_path]
+
+    def _gather_gears(self, states, ref_speeds):
+        """`_gather` for `rollout(gears=True)`: ALL pieces of every member's path to the device (rda_upload_path_pieces); returns the states (B, 3),
+        the UNSIGNED speeds (B,), `cur_index` (B,), the pieces in force `curve_index` (B,), and the nominal controls as `_gather` does"""
+        B = len(self.members)
+        st, speed, cur, piece0 = np.zeros((B, 3)), np.zeros(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        resident = True
+        for i, m in enumerate(self.members):
+            state = states[i]
+            m.state = state[0:3] if np.shape(state)[0] > 3 else state
+            pieces = self._gear_pieces(m)
+            piece0[i] = m.curve_index if m.enable_reverse else 0
+            if piece0[i] >= len(pieces):
+                raise RuntimeError(f"Fleet.rollout: member {i} is past the last piece of its path (it has arrived); update_ref_path or reset starts it again")
+            m.rda.upload_path_pieces(pieces)
+            st[i] = np.asarray(m.state, float).ravel()[0:3]
+            speed[i], cur[i] = ref_speeds[i], m.cur_index
+            resident = resident and m._nominal_u() is None
+        return st, speed, cur, piece0, self._nominal_all(resident)
+
+    def _scatter_gears(self, last_piece, last_index, arrived):
+        """after a gear rollout: the headings the device gave the last waypoint of every piece (Q12) into the members' paths, and `curve_index` /
+        `cur_index` as `_end` leaves them - past the last piece after arrival, index 0 of the new piece when the last tick changed it, else the last tick's
+        `min_index` (`last_piece`, `last_index`: the piece in force during the last tick and its `min_index`).  The rda_upload_path copy has not seen the rewrites: the next `control` uploads again."""
+        ms = self.members
+        B = len(ms)
+        piece, heads = np.zeros(B, np.int32), np.zeros(sum(len(self._gear_pieces(m)) for m in ms))
+        rc = self.api.fleet_rollout_last_pieces(self._handle, iptr(piece), dptr(heads))
+        if rc < 0:
+            raise self.api.failed("fleet_rollout_last_pieces", rc)
+        at = 0
+        for i, m in enumerate(ms):
+            pieces = self._gear_pieces(m)
+            for p, pts in enumerate(pieces):
+                pts[-1][2, 0] = heads[at + p]
+            at += len(pieces)
+            m._dev_path_key = None
+            m.cur_index = int(last_index[i])
+            if m.enable_reverse and arrived[i] >= 0:
+                m.curve_index, m.cur_index = len(pieces), 0
+            elif m.enable_reverse:
+                m.curve_index = int(piece[i])
+                if piece[i] != last_piece[i]:
+                    m.cur_index = 0
 
     def _control_tracked(self, states, ref_speeds, obstacle_lists, start, threshold=0.1, ind_range=10, stage=None):
         """the same with every member's pre_process on the device (rda_fleet_step_tracked): per ego only the state, the

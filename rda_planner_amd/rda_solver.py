@@ -404,6 +404,16 @@ class RDA_solver:
         if rc < 0:
             raise self._be.api.failed("upload_path", rc)
 
+    def upload_path_pieces(self, pieces):
+        """all gear pieces of a path (MPC.curve_list: lists of 4x1 waypoints whose last row is the gear; a list of 3x1 waypoints is a piece with
+        gear +1) resident at once, for `Fleet.rollout(gears=True)` (rda_upload_path_pieces)"""
+        lens = np.fromiter((len(p) for p in pieces), np.int32, len(pieces))
+        gear = np.array([float(p[0][3, 0]) if np.shape(p[0])[0] > 3 else 1.0 for p in pieces])
+        P = np.ascontiguousarray(np.hstack([w for p in pieces for w in p])[0:3, :].T, dtype=float)
+        rc = self._be.api.upload_path_pieces(self._be.handle, len(pieces), iptr(lens), dptr(gear), dptr(P))
+        if rc < 0:
+            raise self._be.api.failed("upload_path_pieces", rc)
+
     def iterative_solve_tracked(self, state, ref_speed, cur_index, nom_u=None, threshold=0.1, ind_range=10):
         """`iterative_solve` with MPC.pre_process (nominal roll-out, closest waypoint, arc-length reference sampling)
         done on the device from the robot state; obstacles are whatever is staged (upload_scene / upload_obstacles).

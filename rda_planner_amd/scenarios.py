@@ -96,6 +96,21 @@ def line_path(start, goal, step=0.1):
             for i in range(n + 1)]
 
 
+def gear_path(legs, step=0.1):
+    """A path with gear flags for `MPC(enable_reverse=True)` (the reference's example/reverse): waypoints of shape (4, 1) - x, y, heading, gear -
+    from straight legs `(start, goal, gear)`, each sampled like `line_path`.  On a leg with gear -1 the robot backs up, so the heading is the
+    direction from goal to start.  `MPC.split_path` cuts the result where the gear flips: one piece per run of legs with the same gear."""
+    out = []
+    for start, goal, gear in legs:
+        start, goal = np.asarray(start, float), np.asarray(goal, float)
+        if gear not in (1, -1):
+            raise ValueError(f"gear_path: gear = {gear!r} is neither +1 nor -1")
+        nose = (goal - start)[0:2] if gear == 1 else (start - goal)[0:2]
+        th = np.arctan2(nose[1], nose[0])
+        out += [np.vstack((p[0:2], [[th]], [[float(gear)]])) for p in line_path(start, goal, step)]
+    return out
+
+
 def path_track_ref():
     """The (137,3,1) reference path of the reference's path_track examples (an INPUT fixture there:
     example/path_track/path_track_ref.npy, byte-identical copies under lidar_nav/ and dynamic_obs/); the numbers

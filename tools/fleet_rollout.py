@@ -20,6 +20,14 @@ Both legs exist only from the commit that added the moving rollout on, so both r
 
     python tools/fleet_rollout.py --moving [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6]         (output: profiles/fleet_rollout_moving.txt)
 
+--gears: the parking fleet of examples/reverse_headless.py (forward / back / forward on a path with gear pieces, two boxes beside every bay; legs long
+enough for the ticks asked for), through the Python interface on the same `MPC` members:
+  (a) host loop  per tick ONE Fleet.control (every piece brought to the device when it comes into force, MPC._end on the host) + the plants on the host
+  (b) rollout    ONE Fleet.rollout(gears=True) of K ticks: all pieces resident, the piece bookkeeping by rollout::k_rollout_advance_gears, one host wait
+The host loop is the yardstick and exists before the gear rollout did.  Both rates and their ratio also go to --out.
+
+    python tools/fleet_rollout.py --gears [--fleets 16,64] [--K 100] [--repeats 3] [--warm 6]          (output: profiles/fleet_rollout_gears.txt)
+
 One measurement alone (what a kernel trace is taken of: the launches per tick are those of the host loop plus k_rollout_advance):
     python tools/fleet_rollout.py --leg rollout --B 16        (or --leg host)
 """
@@ -126,11 +134,77 @@ def leg(name, B, K, warm, moving=False):
     return out
 
 
+def gears_leg(name, B, K, warm):
+    """one measurement of the parking fleet in this process: `warm` ticks of Fleet.control, then two windows of K ticks by the leg's method -> dict"""
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import reverse_headless as rh
+    from rda_planner_amd import scenarios as scn
+    from rda_planner_amd.fleet import Fleet
+    from rda_planner_amd.mpc import MPC
+    reach = 0.3 * (warm + 2 * K) / 3 + 4.0                 # three legs that outlast the run at 3 m/s
+    made = [rh.parking(lane, forward=reach + 2.0, back=reach, out=reach + 2.0) for lane in range(B)]
+    fleet = Fleet([MPC(car, path, sample_time=rh.DT, **rh.MPC_KW) for car, path, _, _ in made])
+    cars, obs = [m[0] for m in made], [m[2] for m in made]
+    states = [m[3] for m in made]
+    pieces = []
+
+    def host_ticks(n):
+        nonlocal states
+        for _ in range(n):
+            for m in fleet.members:
+                if m.curve_index >= len(m.curve_list):
+                    rh.hold_arrived(m)
+            pieces.append([m.curve_index for m in fleet.members])
+            res = fleet.control(states, rh.SPEED, obs)
+            states = [scn.kinematic_step(states[i], res[i][0], cars[i], rh.DT) for i in range(B)]
+    host_ticks(warm)
+    els = []
+    for win in range(2):
+        t0 = time.perf_counter()
+        if name == "host":
+            host_ticks(K)
+        else:
+            out = fleet.rollout(states, rh.SPEED, K, gears=True)
+            states = [out["states"][K, i].reshape(3, 1) for i in range(B)]
+            pieces.extend(out["piece"].tolist())
+        els.append(time.perf_counter() - t0)
+    el = els[1]
+    fleet.close()
+    return {"leg": name, "B": B, "K": K, "ego_steps_per_s": B * K / el, "ms_per_tick": 1e3 * el / K, "first_window_ego_steps_per_s": B * K / els[0],
+            "pieces_seen": sorted({p for row in pieces for p in row}), "x_last": float(np.asarray(states[0], float).ravel()[0])}
+
+
+def gears_main(args):
+    lines = ["parking fleet (examples/reverse_headless.py: forward / back / forward on gear pieces, T = 10, N = 4 slots, 2 boxes per member): %d ticks of "
+             "Fleet.control, a first window of K = %d ticks, then the timed window of K ticks; %d interleaved repeats, every measurement in a process of its own"
+             % (args.warm, args.K, args.repeats),
+             "(a) host loop: Fleet.control + the plants per tick; (b) ONE Fleet.rollout(gears=True) of K ticks",
+             "%4s | %-34s | %-34s | %s" % ("B", "(a) host loop ego-steps/s", "(b) gear rollout ego-steps/s", "median (b) / (a)")]
+    for B in args.fleets:
+        a, b = [], []
+        for _ in range(args.repeats):
+            a.append(child("host", B, args))
+            b.append(child("rollout", B, args))
+        ra, rb = [x["ego_steps_per_s"] for x in a], [x["ego_steps_per_s"] for x in b]
+        fmt = lambda v: " ".join("%9.0f" % x for x in v)        # noqa: E731
+        lines.append("%4d | %-34s | %-34s | %.2fx" % (B, fmt(ra), fmt(rb), np.median(rb) / np.median(ra)))
+        lines.append("       ms per fleet tick (medians): host %.3f, rollout %.3f; first window (one-time set-up included): host %.0f, rollout %.0f ego-steps/s"
+                     % (np.median([x["ms_per_tick"] for x in a]), np.median([x["ms_per_tick"] for x in b]),
+                        np.median([x["first_window_ego_steps_per_s"] for x in a]), np.median([x["first_window_ego_steps_per_s"] for x in b])))
+        lines.append("       pieces in force during the run: host %s, rollout %s; x of member 0 at the end: host %.6f, rollout %.6f"
+                     % (a[0]["pieces_seen"], b[0]["pieces_seen"], a[0]["x_last"], b[0]["x_last"]))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
 def child(name, B, args):
     env = dict(os.environ)
     if name == "host" and args.baseline_so and not args.moving:
         env["RDA_HIP_SO"] = os.path.abspath(args.baseline_so)
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--B", str(B), "--K", str(args.K), "--warm", str(args.warm)] + (["--moving"] if args.moving else [])
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--B", str(B), "--K", str(args.K), "--warm", str(args.warm)] + (["--moving"] if args.moving else []) + (["--gears"] if args.gears else [])
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.leg_timeout)
     if res.returncode != 0:
         raise RuntimeError(f"leg {name} B={B} ended with {res.returncode}: {res.stderr[-400:]}")
@@ -152,15 +226,20 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-so", default=None)
     ap.add_argument("--moving", action="store_true", help="scenes that move: closed_loop_fleet_run_moving against rda_fleet_rollout_moving, both on this build")
+    ap.add_argument("--gears", action="store_true", help="the parking fleet: Fleet.control + plant per tick against ONE Fleet.rollout(gears=True)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_rollout_gears.txt"), help="--gears: where the table is written as well")
     ap.add_argument("--leg-timeout", type=float, default=300.0)
     ap.add_argument("--leg", choices=["host", "rollout"], default=None, help="(internal) run one measurement in this process and print it as JSON")
     ap.add_argument("--B", type=int, default=16)
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     if args.leg:
-        print(json.dumps(leg(args.leg, args.B, args.K, args.warm, args.moving)))
+        print(json.dumps(gears_leg(args.leg, args.B, args.K, args.warm) if args.gears else leg(args.leg, args.B, args.K, args.warm, args.moving)))
         return
     assert args.repeats >= 3
+    if args.gears:
+        gears_main(args)
+        return
     if args.moving:
         print("fleet closed loop with MOVING scenes, C5 shape (T = %d, N = %d moving polygons per ego, velocities U[-1,1]^2 m/s, own seeded scene per ego, re-sorted every "
               "tick): %d host-driven ticks, a first window of K = %d ticks, then the timed window of K ticks; %d interleaved repeats" % (T, N, args.warm, args.K, args.repeats))
