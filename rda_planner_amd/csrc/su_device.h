@@ -1366,10 +1366,17 @@ template <int TT, typename RefWait = NoRefWait> __device__ __forceinline__ bool 
         status = 1;
     }
     TR(150);
-    pair_rows();
+    // (uniform: launch arguments and the attempt number, so every wave meets the same barriers) an attempt that starts with a blind landing does not form the
+    // interior point's rows first: land_rows() below writes every array pair_rows() writes (L.bw, L.cy, L.xd, L.lw, L.ra, each entry by the thread that owns it) and
+    // the residual registers; the reciprocals / complementarity targets pair_rows() leaves in registers are read by interior-point passes only, and
+    // land_refuse() forms them (pair_rows) before the first such pass.  ONE barrier then stands between the start and the first stage phase: it orders the
+    // set-up's last writes (L.Q1 / L.Q2, the near list) and the rows before their readers.  L.sav / L.base overlay nothing and are read behind later barriers
+    // only (land_refuse, the next round); L.u / L.d are not written between the set-up's barriers and the first update.
+    const bool blind_start = attempt < 0 && a.land != 0 && a.land_blind != 0 && a.land_rho_prev > 0;
+    if (!blind_start) pair_rows();
     TR(151);
-    __syncthreads();
-    if (attempt < 0 && a.land != 0 && a.land_blind != 0 && a.land_rho_prev > 0) {
+    if (!blind_start) __syncthreads();
+    else {
         // ---- blind landing (Args::land_blind): the state a speculative landing starts in, without the measuring pass in front of it
         for (int i = tid; i < 2 * T; i += NT) { L.sav[i] = L.u[i]; L.base[i] = L.u[i]; }
         for (int i = tid; i < T; i += NT) { L.sav[2 * T + i] = L.d[i]; L.base[2 * T + i] = L.d[i]; }
@@ -1381,7 +1388,6 @@ template <int TT, typename RefWait = NoRefWait> __device__ __forceinline__ bool 
         land_rho = a.land_rho_prev;
         land = 1; land_rounds = 1; expect_conv = false; spec = true; blind = true;
         LSTAT(4, 1); LSTAT(18, 1);
-        __syncthreads();
         land_rows(land_rho);
         __syncthreads();
     }
@@ -1939,21 +1945,63 @@ template <int TT, typename RefWait = NoRefWait> __device__ __forceinline__ bool 
                     ratio = fmax(ratio, fmax(fmax(-dwp * Piwp[j], -dwm * Piwm[j]), fmax(-dlp * Pilp[j], -dlm * Pilm[j])));
                 }
             MF(15); TR(28 + 10 * pass);
-            ratio = block_reduce1(ratio, L.red + 272 + 4 * pass, tid, true);
+            // (uniform: `land` is the same in every thread, so the barriers stay matched) a landing round takes the full step of its model: no ratio, no step-length
+            // reduction, no sigma.  What the reduction's barrier ordered besides its own slots, walked through both passes:
+            //   pass 0: between the barrier in front of the row steps and the one behind the second right-hand side the pair threads read L.dy / L.vv[8 t + 3..4] /
+            //           L.m7 / L.gst (written in front of the former, by the sweeps and the stage phase) and read / write their OWN entries of L.xd and L.vv[8 t + 5]
+            //           (pair (t, k) sits on one thread in both pair maps); L.pv and L.red 272.. / 280.. are not touched - nothing to order, no barrier;
+            //   pass 1: pair_step of the distance pair (k == 2) leaves dd in L.vv[8 t + 5] and thread t of the update reads it as v[2] - another thread, in the
+            //           compile-time pair map another wave: ONE barrier.  (The update writes L.u / L.d / L.s, which the row steps do not read.)
+            if (land == 1) { if (pass == 1) __syncthreads(); }
+            else ratio = block_reduce1(ratio, L.red + 272 + 4 * pass, tid, true);
             MF(0); TR(29 + 10 * pass);
             // fraction to the boundary: 1 for the predictor; corrector: 0.995 far from the solution, -> 1 with the complementarity (superlinear end game)
             double fr = 1.0;
             if (pass) { fr = 1.0 - mu; if (fr < tau_min) fr = tau_min; if (safe) fr = SU_SAFE_TAU; }
             const double al = land == 1 ? 1.0 : (ratio > fr ? fr / ratio : 1.0);      // (a landing takes the full step of its model)
             if (pass == 0) {
+                if (land != 1) {       // (uniform; the second pass of a landing round reads no sigma)
                 // centering parameter from the predictor step length, floored (see the oracle for why)
                 double q = 1 - al, fl = al >= 0.95 ? (attempt < 0 ? a.warm_sig : SIGMA_FLOOR) : 0.03;
                 if (it >= 25) fl = it >= 50 ? 0.3 : 0.1;      /* a solve that is still running is cycling: centre harder */
                 sigma = q * q * q; if (sigma < fl) sigma = fl;
+                }
+            } else if (land == 1) {
+                // ---- tail of a landing round (uniform branch: `land` is the same in every thread, every wave meets the same ONE barrier).  The full step of the
+                // model, the reach check of the hinge screening (`screened` depends on it) and the rows of the verification pass.  Not here: the complementarity
+                // sum and its reduction - the pass that follows a landing round is always its verification (land == 2), which measures for itself, and neither
+                // the recentring nor the light-check prediction exists in a landing.  Thread t checks the position column it has just written (t >= 1: column t
+                // against reference t - 1; t == 0: the end column T, which it also writes), so no barrier stands between the update and the check - the same
+                // sums in the same order as in the interior point's update, al = 1.  The rows (verify_rows) are formed from registers and go to entries the
+                // thread owns; their readers come behind the barrier below.  For readers of the trace: events 40 and 41 stand back to back here only to keep
+                // the numbering (no barrier between them), so in a landing round 39 -> 40 is the update WITH the reach check, 40 -> 41 is empty and 41 -> 42 is
+                // the wave reduction and verify_rows.  al_prev is set for form's sake: only the `safe` iteration reads it.
+                double dv = 0;
+                if (tid < T) {
+                    const int t = tid; const double *y = &L.dy[8 * t], *v = &L.vv[8 * t + 3];
+                    L.u[t] += v[0]; L.u[T + t] += v[1]; L.d[t] += v[2];
+                    const int tc = t >= 1 ? t : T;
+                    const double *dq = t >= 1 ? y : L.pv;
+                    const double nx = L.s[tc] + dq[0], ny = L.s[(T + 1) + tc] + dq[1], nz = L.s[2 * (T + 1) + tc] + dq[2];
+                    L.s[tc] = nx; L.s[(T + 1) + tc] = ny; L.s[2 * (T + 1) + tc] = nz;
+                    if (screened) { const double ex = nx - L.p0[tc - 1], ey = ny - L.p0[T + tc - 1]; dv = sqrt(ex * ex + ey * ey); }
+                }
+                TR(40); TR(41);
+                dv = wave_allreduce(dv, true);
+                if (lane == 0) L.red[280 + wave] = dv;
+                verify_rows();
+                TR(42);
+                __syncthreads();
+                TR(43);
+                dv = fmax(fmax(L.red[280], L.red[281]), fmax(L.red[282], L.red[283]));
+                if (screened && dv > DELTA) screened = false;      // from the next pass on: every term (the streaming loop)
+                MF(13);
+                al_prev = 1.0;
+                land = 2; expect_conv = true;                      // (the next pass verifies the landing: true measures only)
             } else {
 #pragma unroll
                 for (int j = 0; j < NPR; ++j)
-                    if (p_on[j] && land != 1) { Pwp[j] += al * Pdwp[j]; Pwm[j] += al * Pdwm[j]; Plp[j] += al * Pdlp[j]; Plm[j] += al * Pdlm[j]; }
+                    if (p_on[j]) { Pwp[j] += al * Pdwp[j]; Pwm[j] += al * Pdwm[j]; Plp[j] += al * Pdlp[j]; Plm[j] += al * Pdlm[j]; }
                 if (tid < T) {
                     int t = tid; const double *y = &L.dy[8 * t], *v = &L.vv[8 * t + 3];
                     L.u[t] += al * v[0]; L.u[T + t] += al * v[1]; L.d[t] += al * v[2];
@@ -1972,7 +2020,7 @@ template <int TT, typename RefWait = NoRefWait> __device__ __forceinline__ bool 
                 for (int j = 0; j < NPR; ++j) if (p_on[j]) m_ += Plp[j] * Pwp[j] + Plm[j] * Pwm[j];
                 dv = wave_allreduce(dv, true); m_ = wave_allreduce(m_, false);
                 if (lane == 0) { L.red[280 + wave] = dv; L.red[284 + wave] = m_; }
-                if (land == 1) verify_rows(); else pair_rows();
+                pair_rows();
                 TR(42);
                 __syncthreads();
                 TR(43);
@@ -2004,7 +2052,6 @@ template <int TT, typename RefWait = NoRefWait> __device__ __forceinline__ bool 
                 const double prd = (1 - al) * rdn, prp = (1 - al) * rpn;
                 expect_conv = c.light_check && ((prd <= t_rd * sc && prp <= t_rp && m_ <= t_mu * sc) ||
                                                 (prd <= 100 * t_rd * sc && prp <= t_rp && m_ <= 0.1 * t_mu * sc));
-                if (land == 1) { land = 2; expect_conv = true; }      // (the next pass verifies the landing: true measures only)
             }
             mark(8);
         }
