@@ -506,8 +506,8 @@ int  rda_fleet_rollout_peers(rda_fleet *f, int K, const double *states /*B*3*/, 
  * produces no jump at stage 1), and the LAST STAGE repeats the plan's last increment.  Every difference and sum is rounded separately, parenthesised as
  * written.  Stage 0, own obstacles and the slots of members that are not valid are bit-identical to rda_fleet_upload_scenes_peers; a padded copy of a peer
  * carries the plan too.  The scenes are the peers scenes: the two modes may alternate on the same staged fleet.  Refusals of rda_fleet_upload_scenes_peers,
- * plus RDA_ERR_ARG without plans / plan_valid; a refused allocation: RDA_ERR_HIP, fleet and members as they were.  Not covered: lidar rollouts with peers,
- * circle (norm2) robots, the gear pieces of enable_reverse paths. */
+ * plus RDA_ERR_ARG without plans / plan_valid; a refused allocation: RDA_ERR_HIP, fleet and members as they were.  Not covered: staging combined with lidar
+ * (members that see each other through the simulated lidar: rda_fleet_rollout_lidar_peers), circle (norm2) robots, the gear pieces of enable_reverse paths. */
 int  rda_fleet_upload_scenes_peers_plan(rda_fleet *f, const int32_t *counts /*B*/, const int32_t *kind, const int32_t *nvert, const double *geom,
                                         const double *vel, const double *states /*B*3*/, const double *controls /*B*2*/,
                                         const double *plans /*B*3*(T+1)*/, const int32_t *plan_valid /*B*/);
@@ -576,6 +576,36 @@ int  rda_fleet_rollout_lidar(rda_fleet *f, int K, const double *states /*B*3*/, 
                              double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
                              rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
                              int32_t *nbox_log /*K*B, may be NULL*/, double *clearance_log /*K*B, may be NULL*/);
+/* The simulated sensor of a fleet whose members SEE EACH OTHER: rda_fleet_raycast's arguments, one launch (lidar::k_raycast_fleet_peers) and one wait.
+ * Member i's beams are cast against its resident world and against the footprints of all members j != i at states[j] - polygons of R vertices,
+ * Rot(theta_j) rv_j + p_j with the expressions of rda_fleet_upload_scenes_peers' peer rows (scenarios.peer_footprints is the specification: the scan is
+ * World.get_lidar_scan on world_i + peer_footprints(cars, states, i)).  A member never sees itself; a footprint that contains the beam origin is hit from
+ * the inside like any polygon; range = clip(min(range_max, world hits, peer hits), range_min, range_max).  This is perception, not staging: nothing of
+ * the members' scenes is read or written, and the peers modes (rda_fleet_*_peers) stay separate.  rda_fleet_raycast's refusals - a world must be
+ * resident; count 0 per member (an empty world) is the way to see only the others - plus RDA_ERR_UNSUPPORTED for a robot the clearance does not take (a
+ * norm2 robot, consecutive rows that do not intersect: see rda_fleet_clearance).  B = 1: rda_fleet_raycast. */
+int  rda_fleet_raycast_peers(rda_fleet *f, const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,
+                             const double *range_min, const double *range_max /*B each*/, const double *states /*B*3*/,
+                             double *ranges /*sum(n_beams)*/);
+/* rda_fleet_rollout_lidar for such a fleet: its arguments, logs, arrival rule and refusals, plus peer_clearance_log.  Per tick the launches of
+ * rda_fleet_rollout_lidar with the ray cast replaced by lidar::k_raycast_fleet_peers on the poses the advance kernel left for ALL members (tick 0: the
+ * caller's) - no extra launch; with peer_clearance_log [K][B] one launch more, member i's separation from the nearest other member at state k+1 (as in
+ * rda_fleet_rollout_peers; +inf for B = 1).  Still one short wait per tick for the 4 * B bytes of box counts, nothing else crosses the link.  Members
+ * that have arrived stand where they are and are still seen.  A seen member reaches the planner as standing boxes like every lidar obstacle (no
+ * velocity from perception).  `moving`, nbox_log, clearance_log (against the WORLD, the true obstacles) and rda_fleet_rollout_last keep their meaning; a
+ * refused call queues nothing and leaves world and members as they were; every buffer is allocated before tick 0.  Given the states of tick k and the
+ * world of tick k, a tick computes bit for bit what a host-driven tick computes: rda_fleet_raycast_peers, then rda_fleet_upload_scans of those ranges at
+ * those states, then rda_fleet_step_tracked.  Additional refusal: RDA_ERR_UNSUPPORTED for a robot the clearance does not take. */
+int  rda_fleet_rollout_lidar_peers(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                                   const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                                   const double *nom_u /*B*2*T or NULL = resident*/,
+                                   const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,
+                                   const double *range_min, const double *range_max /*B each*/,
+                                   double eps, int min_samples, const int32_t *order /*B*/, int moving,
+                                   double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                                   rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                                   int32_t *nbox_log /*K*B, may be NULL*/, double *clearance_log /*K*B, may be NULL*/,
+                                   double *peer_clearance_log /*K*B, may be NULL*/);
 /* test hook: the geometry of the resident worlds as it stands, member-major [*n_total][*we][2] (geom and we may be NULL; *n_total = 0: no world) */
 int  rda_debug_fleet_world(rda_fleet *f, double *geom, int32_t *n_total, int32_t *we);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */

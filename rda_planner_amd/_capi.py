@@ -118,6 +118,8 @@ PROTOTYPES = {
     "fleet_upload_worlds":  "i hIiIIDD",
     "fleet_raycast":        "i hIDDDDDD",
     "fleet_rollout_lidar":  "i hiDDIdiiDIDDDDdiIiDDINIID",
+    "fleet_raycast_peers":  "i hIDDDDDD",
+    "fleet_rollout_lidar_peers": "i hiDDIdiiDIDDDDdiIiDDINIIDD",
     "debug_fleet_world":    "i hDII",
     "fleet_enqueue_range":  "i hii",
     "fleet_sync":           "i h",
@@ -210,6 +212,7 @@ class CApi:
         self.has_fleet_rollout_gears = has("fleet_rollout_gears")           # ... over the gear pieces of reverse paths
         self.has_fleet_peers = has("fleet_rollout_peers")                   # members as each other's obstacles, staged on the device
         self.has_fleet_peers_plan = has("fleet_rollout_peers_plan")         # ... predicted along their planned trajectories
+        self.has_fleet_lidar_peers = has("fleet_rollout_lidar_peers")       # members that see each other in the simulated lidar
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/rda_hip.h"
+#include "scene_device.h"
 
 namespace lidar {
 
@@ -350,6 +351,60 @@ struct Ray {                  // per member
 };
 constexpr int RAY_NT = 64, RAY_TILE = 32;
 
+// one beam (origin o, direction d) against a circle g = centre, (radius, -) | against the polygon edge p -> q: `rng` becomes the hit's range when it is nearer
+__device__ __forceinline__ void ray_circle(const double ox, const double oy, const double dx, const double dy, const double *g, double &rng)
+{
+#pragma clang fp contract(off)
+    const double fx = ox - g[0], fy = oy - g[1];
+    const double bq = dx * fx + dy * fy;
+    const double disc = bq * bq - ((fx * fx + fy * fy) - g[2] * g[2]);
+    if (disc >= 0) { const double t = -bq - sqrt(disc); if (t >= 0 && t < rng) rng = t; }
+}
+__device__ __forceinline__ void ray_edge(const double ox, const double oy, const double dx, const double dy, const double px, const double py,
+                                         const double qx, const double qy, double &rng)
+{
+#pragma clang fp contract(off)
+    const double ex = qx - px, ey = qy - py;
+    const double den = dx * ey - dy * ex;
+    const double wx = px - ox, wy = py - oy;
+    const double t = (wx * ey - wy * ex) / den, s = (wx * dy - wy * dx) / den;
+    if (fabs(den) > 1e-12 && t >= 0 && s >= 0 && s <= 1 && t < rng) rng = t;
+}
+// the member's direction of beam b (live beams only) and its world, tile by tile through tg / tk / tv: the part the two ray casters share.  Every barrier is
+// reached by the whole workgroup; returns min(range_max, world hits)
+__device__ __forceinline__ double ray_world(const Ray &r, const int E, const bool live, const double ox, const double oy, const double dx, const double dy,
+                                            double *tg, int *tk, int *tv)
+{
+    double rng = r.range_max;
+    for (int o0 = 0; o0 < r.n; o0 += RAY_TILE) {
+        const int m = r.n - o0 < RAY_TILE ? r.n - o0 : RAY_TILE;
+        __syncthreads();                                                                 // (the tile before this one has been read)
+        for (int w = threadIdx.x; w < m * E * 2; w += RAY_NT) tg[w] = r.geom[(size_t)o0 * E * 2 + w];
+        for (int w = threadIdx.x; w < m; w += RAY_NT) { tk[w] = r.kind[o0 + w]; tv[w] = r.nvert[o0 + w]; }
+        __syncthreads();
+        if (!live) continue;
+        for (int j = 0; j < m; ++j) {
+            const double *g = tg + j * E * 2;
+            if (tk[j] == 1) { ray_circle(ox, oy, dx, dy, g, rng); continue; }
+            const int nv = tv[j] < E ? tv[j] : E;
+            for (int k = 0; k < nv; ++k) {
+                const int k1 = k + 1 < nv ? k + 1 : 0;
+                ray_edge(ox, oy, dx, dy, g[2 * k], g[2 * k + 1], g[2 * k1], g[2 * k1 + 1], rng);
+            }
+        }
+    }
+    return rng;
+}
+__device__ __forceinline__ void ray_direction(const Ray &r, const int b, const double heading, double &dx, double &dy)
+{
+#pragma clang fp contract(off)
+    const int nb = r.n_beams;
+    const double step = nb > 1 ? (r.angle_max - r.angle_min) / (double)(nb - 1) : 0.0;
+    const double ang = (nb > 1 && b == nb - 1) ? r.angle_max : (double)b * step + r.angle_min;
+    const double th = heading + ang;
+    dx = cos(th); dy = sin(th);
+}
+
 __global__ __launch_bounds__(RAY_NT) void k_raycast_fleet(const Ray *rs, const double *poses)
 {
 #pragma clang fp contract(off)        // numpy does not fuse: keep every product and sum separately rounded
@@ -362,38 +417,73 @@ __global__ __launch_bounds__(RAY_NT) void k_raycast_fleet(const Ray *rs, const d
     const bool live = b < nb;
     const double ox = poses[3 * blockIdx.y], oy = poses[3 * blockIdx.y + 1];
     double dx = 1.0, dy = 0.0;
-    if (live) {
-        const double step = nb > 1 ? (r.angle_max - r.angle_min) / (double)(nb - 1) : 0.0;
-        const double ang = (nb > 1 && b == nb - 1) ? r.angle_max : (double)b * step + r.angle_min;
-        const double th = poses[3 * blockIdx.y + 2] + ang;
-        dx = cos(th); dy = sin(th);
-    }
-    double rng = r.range_max;
-    for (int o0 = 0; o0 < r.n; o0 += RAY_TILE) {
-        const int m = r.n - o0 < RAY_TILE ? r.n - o0 : RAY_TILE;
-        __syncthreads();                                                                 // (the tile before this one has been read)
-        for (int w = threadIdx.x; w < m * E * 2; w += RAY_NT) tg[w] = r.geom[(size_t)o0 * E * 2 + w];
-        for (int w = threadIdx.x; w < m; w += RAY_NT) { tk[w] = r.kind[o0 + w]; tv[w] = r.nvert[o0 + w]; }
+    if (live) ray_direction(r, b, poses[3 * blockIdx.y + 2], dx, dy);
+    const double rng = ray_world(r, E, live, ox, oy, dx, dy, tg, tk, tv);
+    if (live) r.ranges[b] = fmin(fmax(rng, r.range_min), r.range_max);                   // np.clip
+}
+
+// The sensor that also sees the other MEMBERS (rda_fleet_raycast_peers, rda_fleet_rollout_lidar_peers): k_raycast_fleet - same grid, same beam rule, same
+// world loop - and behind the world the footprints of the members j != i at the poses of the same array, as polygons of ps[j].R vertices
+// (scenarios.peer_footprints is the specification: robot_vertices(cars[j], states[j]), ascending j).  The B - 1 peers go through LDS in tiles of RAY_TILE:
+// for a tile, lane w < m takes peer row p0 + w (row r is member j = r < i ? r : r + 1, the mapping of scene::k_peers_fleet), computes cos / sin of that ONE
+// heading and writes the R vertices with k_peers_fleet's expressions, (co rv.x - si rv.y) + x | (si rv.x + co rv.y) + y, at a stride of RDA_RMAX vertices;
+// then every beam runs ray_edge over the R edges of each footprint, all lanes on the same vertex (broadcast reads).  So the trigonometry costs one cos / sin
+// pair per peer and workgroup, never per beam.  A member does not see itself; a peer that contains the origin is hit from the inside like any polygon.  The
+// minimum over world and peers is exact, its order free.  The lane that owns a peer also drops it when it is out of reach - centre farther from the origin
+// than range_max plus the footprint's radius, so no hit of it can lower the minimum: the result is the same bit for bit, and a beam pays the edge tests
+// (two double divisions each, what this kernel's time is made of) only for the members its lidar can reach, not for all B - 1.
+// LDS: the peer tile reuses the world tile's block (the world has been read when the first peer tile is written), so the launch costs what k_raycast_fleet's
+// does, 32 * 8 * 2 doubles + 2 * 32 ints = 4352 B per workgroup of one wave: 32 resident workgroups (the wave limit of a CU) hold 136 KiB of its 160 KiB, the
+// LDS does not bound the occupancy.  Workgroups: B * ceil(n_beams / 64), 1088 at 64 members x 1080 beams, as many as the blind caster; each tests
+// at most 63 * 4 peer edges per beam besides the world's (all members within reach of each other).
+static_assert(RDA_RMAX <= RDA_EMAX, "a peer tile lies in the world tile's block");
+__global__ __launch_bounds__(RAY_NT) void k_raycast_fleet_peers(const Ray *rs, const scene::Peer *ps, const double *poses, int B)
+{
+#pragma clang fp contract(off)
+    __shared__ double tg[RAY_TILE * RDA_EMAX * 2];
+    __shared__ int tk[RAY_TILE], tv[RAY_TILE];
+    const int i = blockIdx.y;
+    const Ray r = rs[i];
+    const int nb = r.n_beams, E = r.E < RDA_EMAX ? r.E : RDA_EMAX;
+    if ((int)(blockIdx.x * RAY_NT) >= nb) return;                                        // (the whole workgroup)
+    const int b = blockIdx.x * RAY_NT + threadIdx.x;
+    const bool live = b < nb;
+    const double ox = poses[3 * i], oy = poses[3 * i + 1];
+    double dx = 1.0, dy = 0.0;
+    if (live) ray_direction(r, b, poses[3 * i + 2], dx, dy);
+    double rng = ray_world(r, E, live, ox, oy, dx, dy, tg, tk, tv);
+    for (int p0 = 0; p0 < B - 1; p0 += RAY_TILE) {
+        const int m = B - 1 - p0 < RAY_TILE ? B - 1 - p0 : RAY_TILE;
+        __syncthreads();                                                                 // (the world's last tile | the peer tile before this one has been read)
+        if ((int)threadIdx.x < m) {
+            const int row = p0 + threadIdx.x, j = row < i ? row : row + 1;
+            const scene::Peer &p = ps[j];
+            const int R = p.R < RDA_RMAX ? p.R : RDA_RMAX;
+            const double x = poses[3 * j], y = poses[3 * j + 1], th = poses[3 * j + 2];
+            // out of reach: every point of the footprint lies within rad of (x, y), so a hit is at least |p_j - o| - rad away; beyond range_max it
+            // cannot lower min(range_max, ...) (the margin of 1e-6 relative stands for the rounding of these few operations)
+            double rad2 = 0.0;
+            for (int v = 0; v < R; ++v) rad2 = fmax(rad2, p.rv[v][0] * p.rv[v][0] + p.rv[v][1] * p.rv[v][1]);
+            const double reach = (r.range_max + sqrt(rad2)) * 1.000001, cx = x - ox, cy = y - oy;
+            const bool near_enough = !(cx * cx + cy * cy > reach * reach);                  // (a NaN pose is kept: the edge tests then hit nothing, as before)
+            if (near_enough) {
+                const double co = cos(th), si = sin(th);
+                double *g = tg + threadIdx.x * RDA_RMAX * 2;
+                for (int v = 0; v < R; ++v) {
+                    g[2 * v] = (co * p.rv[v][0] - si * p.rv[v][1]) + x;
+                    g[2 * v + 1] = (si * p.rv[v][0] + co * p.rv[v][1]) + y;
+                }
+            }
+            tv[threadIdx.x] = near_enough ? R : 0;
+        }
         __syncthreads();
         if (!live) continue;
-        for (int j = 0; j < m; ++j) {
-            const double *g = tg + j * E * 2;
-            if (tk[j] == 1) {
-                const double fx = ox - g[0], fy = oy - g[1];
-                const double bq = dx * fx + dy * fy;
-                const double disc = bq * bq - ((fx * fx + fy * fy) - g[2] * g[2]);
-                if (disc >= 0) { const double t = -bq - sqrt(disc); if (t >= 0 && t < rng) rng = t; }
-                continue;
-            }
-            const int nv = tv[j] < E ? tv[j] : E;
+        for (int q = 0; q < m; ++q) {
+            const double *g = tg + q * RDA_RMAX * 2;
+            const int nv = tv[q];
             for (int k = 0; k < nv; ++k) {
                 const int k1 = k + 1 < nv ? k + 1 : 0;
-                const double px = g[2 * k], py = g[2 * k + 1];
-                const double ex = g[2 * k1] - px, ey = g[2 * k1 + 1] - py;
-                const double den = dx * ey - dy * ex;
-                const double wx = px - ox, wy = py - oy;
-                const double t = (wx * ey - wy * ex) / den, s = (wx * dy - wy * dx) / den;
-                if (fabs(den) > 1e-12 && t >= 0 && s >= 0 && s <= 1 && t < rng) rng = t;
+                ray_edge(ox, oy, dx, dy, g[2 * k], g[2 * k + 1], g[2 * k1], g[2 * k1 + 1], rng);
             }
         }
     }

@@ -4336,40 +4336,71 @@ static int fleet_ray_table(rda_fleet *F, const int32_t *n_beams, const double *a
     HIPCHK(w.ray.push(F->stream));
     return RDA_OK;
 }
-static void fleet_ray_launch(rda_fleet *F, const double *poses, int maxb)
+// see: the form that also casts against the other members' footprints at `poses` (the peer table is on the device); a fleet of one has no peer to see
+static void fleet_ray_launch(rda_fleet *F, const double *poses, int maxb, bool see = false)
 {
     if (maxb <= 0) return;
-    hipLaunchKernelGGL(lidar::k_raycast_fleet, dim3((unsigned)((maxb + lidar::RAY_NT - 1) / lidar::RAY_NT), (unsigned)F->B), dim3(lidar::RAY_NT), 0, F->stream,
-                       (const lidar::Ray *)F->world.ray.d, poses);
+    const dim3 grid((unsigned)((maxb + lidar::RAY_NT - 1) / lidar::RAY_NT), (unsigned)F->B);
+    if (see && F->B > 1)
+        hipLaunchKernelGGL(lidar::k_raycast_fleet_peers, grid, dim3(lidar::RAY_NT), 0, F->stream, (const lidar::Ray *)F->world.ray.d,
+                           (const scene::Peer *)F->pe.tab.d, poses, F->B);
+    else
+        hipLaunchKernelGGL(lidar::k_raycast_fleet, grid, dim3(lidar::RAY_NT), 0, F->stream, (const lidar::Ray *)F->world.ray.d, poses);
+}
+// the peer table as the members stand now -> device, when it differs from what the device holds (the wait: an earlier copy out of the mirror may be queued)
+static int fleet_peer_table(rda_fleet *F)
+{
+    std::vector<scene::Peer> pv;
+    fleet_peer_view(F, pv);
+    if (!mirror_differs(F->pe.tab, records(pv))) return RDA_OK;
+    HIPCHK(hipStreamSynchronize(F->stream));
+    HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
+    return RDA_OK;
 }
 
-// the resident worlds as they stand, ray-cast from states [B][3]: one launch, one wait
-extern "C" int rda_fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
-                                 const double *range_max, const double *states, double *ranges)
+// the resident worlds as they stand (see: and the other members at `states`), ray-cast from states [B][3]: one launch, one wait
+static int fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                         const double *range_max, const double *states, double *ranges, bool see)
 {
     size_t total = 0;
     int rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
     if (rc != RDA_OK) return rc;
     if (!states || (total > 0 && !ranges)) return RDA_ERR_ARG;
     const size_t B = F->B;
-    if (total > F->rays.v.n) {
-        FleetDoubles t;
-        if (t.alloc(total)) return RDA_ERR_HIP;
-        HIPCHK(hipStreamSynchronize(F->stream));
-        F->rays = std::move(t);
+    if (see) for (const rda_handle *H : F->egos) if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;      // (a footprint needs the vertices of a polygon robot)
+    FleetDoubles t; FleetPeers tpe;
+    {
+        int bad = 0;
+        if (total > F->rays.v.n) bad |= t.alloc(total);
+        if (see && !F->pe.have()) bad |= tpe.alloc(B);
+        if (bad) return RDA_ERR_HIP;
     }
+    if (t.have()) { HIPCHK(hipStreamSynchronize(F->stream)); F->rays = std::move(t); }
+    if (tpe.have()) F->pe = std::move(tpe);
+    if (see) { rc = fleet_peer_table(F); if (rc != RDA_OK) return rc; }
     int maxb = 0;
     rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
     if (rc != RDA_OK) return rc;
     memcpy(F->world.st.h, states, 3 * B * sizeof(double));
     HIPCHK(F->world.st.push(F->stream));
-    fleet_ray_launch(F, F->world.st.d, maxb);
+    fleet_ray_launch(F, F->world.st.d, maxb, see);
     HIPCHK(hipGetLastError());
     if (total > 0) HIPCHK(F->rays.v.pull(F->stream, total));
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
     if (total > 0) memcpy(ranges, F->rays.v.h, total * sizeof(double));
     return RDA_OK;
+}
+extern "C" int rda_fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                                 const double *range_max, const double *states, double *ranges)
+{
+    return fleet_raycast(F, n_beams, angle_min, angle_max, range_min, range_max, states, ranges, false);
+}
+// ... with every member seeing the others' footprints at `states` too (lidar::k_raycast_fleet_peers); B = 1: rda_fleet_raycast
+extern "C" int rda_fleet_raycast_peers(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
+                                       const double *range_max, const double *states, double *ranges)
+{
+    return fleet_raycast(F, n_beams, angle_min, angle_max, range_min, range_max, states, ranges, true);
 }
 
 // ---- rda_fleet_rollout_lidar: the closed loop around the simulated sensor -------------------------------------------------------------------------------
@@ -4378,32 +4409,37 @@ extern "C" int rda_fleet_raycast(rda_fleet *F, const int32_t *n_beams, const dou
 // and size the staging launches - fleet_scan_stage), then the tick's tail as in fleet_rollout_scenes (fleet_roll_tail): k_track_fleet, the ADMM launches
 // and k_rollout_advance, and behind them (moving) scene::k_move_fleet on the WORLD and (clearance_log) k_clearance_fleet against the world.  Everything is
 // allocated before tick 0.
-extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
-                                       int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
-                                       const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
-                                       const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
-                                       int32_t *arrived_at, int32_t *nbox_log, double *clearance_log)
+// see (rda_fleet_rollout_lidar_peers): the same ticks with k_raycast_fleet_peers in the ray caster's place - row k of the state log holds the poses of ALL
+// members, arrived ones where they stand - and (a.peer_clearance_log) k_peer_clearance_fleet of state k + 1 behind the tail.
+struct LidarArgs {
+    const int32_t *n_beams; const double *angle_min, *angle_max, *range_min, *range_max; double eps; int min_samples; const int32_t *order; int moving;
+    int32_t *nbox_log;
+};
+static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs &s, bool see)
 {
-    const RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
     int rc = roll_check_args(F, a);
     if (rc != RDA_OK) return rc;
-    if (!order || !(eps > 0) || min_samples < 1) return RDA_ERR_ARG;
+    if (!s.order || !(s.eps > 0) || s.min_samples < 1) return RDA_ERR_ARG;
     size_t total = 0;
-    rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
-    if (rc == RDA_OK) rc = roll_check_members(F, cur_index);
+    rc = fleet_ray_check(F, s.n_beams, s.angle_min, s.angle_max, s.range_min, s.range_max, total);
+    if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
+    const int K = a.K;
     for (const rda_handle *H : F->egos) {
         if (H->opts.duals_follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member; a box has four vertices)
-        if (clearance_log && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+        if ((a.clearance_log || see) && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
     }
+    const bool peer_log = see && a.peer_clearance_log && B > 1;
     // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
-    RollReserve rsv; FleetDoubles tray;
+    RollReserve rsv; FleetDoubles tray, tpc; FleetPeers tpe;
     std::vector<SceneGrow> grow(B), none(B);                                    // a raw scene for the most boxes a member's beams can give | per tick: nothing to grow
     {
-        int bad = rsv.alloc(F, K, clearance_log != nullptr);
+        int bad = rsv.alloc(F, K, a.clearance_log != nullptr);
         if (total > F->rays.v.n) bad |= tray.alloc(total);
-        for (size_t i = 0; i < B && !bad; ++i) if (n_beams[i] > 0) bad |= scene_grow_alloc(F->egos[i], n_beams[i], grow[i]);
+        if (see && !F->pe.have()) bad |= tpe.alloc(B);
+        if (peer_log && (size_t)K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)K * B);
+        for (size_t i = 0; i < B && !bad; ++i) if (s.n_beams[i] > 0) bad |= scene_grow_alloc(F->egos[i], s.n_beams[i], grow[i]);
         if (!bad) bad |= fleet_lidar_reserve(F, false);                         // (last: what it makes stays with the fleet)
         if (bad) return RDA_ERR_HIP;
     }
@@ -4412,9 +4448,12 @@ extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states
     rc = rsv.move_in(F, true);                                                  // (the wait: shorter blocks are freed; the pinned tables are rewritten)
     if (rc != RDA_OK) return rc;
     if (tray.have()) F->rays = std::move(tray);
+    if (tpe.have()) F->pe = std::move(tpe);
+    if (tpc.have()) F->pc_log = std::move(tpc);
     for (size_t i = 0; i < B; ++i) scene_grow_commit(F->egos[i], grow[i]);
     RollView rv;
-    if (fleet_roll_view(F, nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
+    if (fleet_roll_view(F, a.nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
+    if (see) { rc = fleet_peer_table(F); if (rc != RDA_OK) return rc; }
     const RollLayout lay = roll_layout((size_t)K, B, T);
     rollout::Logs lg;
     rc = fleet_roll_inputs(F, lay, a, lg);
@@ -4423,19 +4462,19 @@ extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states
     FleetLidar &li = F->li;
     FleetWorld &w = F->world;
     int maxb = 0, gmax = 0;
-    rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
+    rc = fleet_ray_table(F, s.n_beams, s.angle_min, s.angle_max, s.range_min, s.range_max, maxb);
     if (rc != RDA_OK) return rc;
-    memcpy(w.st.h, states, 3 * B * sizeof(double));
+    memcpy(w.st.h, a.states, 3 * B * sizeof(double));
     HIPCHK(hipMemcpyAsync(lg.states, w.st.h, 3 * B * sizeof(double), hipMemcpyHostToDevice, F->stream));
     {
         size_t off = 0;
         for (size_t i = 0; i < B; ++i) {
-            lidar::Args &s = li.args.h[i];
-            memset((void *)&s, 0, sizeof(s));
-            s.n_beams = n_beams[i]; s.ranges = F->rays.v.d + off; s.angle_min = angle_min[i]; s.angle_max = angle_max[i]; s.range_max = range_max[i];
-            s.eps = eps; s.min_samples = min_samples;                            // (the pose: k_scan_fleet_at's second argument)
-            s.boxes = li.d_boxes + i * lidar::MAXB * 8; s.count = li.h_count + 2 * i;
-            off += (size_t)n_beams[i];
+            lidar::Args &sa = li.args.h[i];
+            memset((void *)&sa, 0, sizeof(sa));
+            sa.n_beams = s.n_beams[i]; sa.ranges = F->rays.v.d + off; sa.angle_min = s.angle_min[i]; sa.angle_max = s.angle_max[i]; sa.range_max = s.range_max[i];
+            sa.eps = s.eps; sa.min_samples = s.min_samples;                      // (the pose: k_scan_fleet_at's second argument)
+            sa.boxes = li.d_boxes + i * lidar::MAXB * 8; sa.count = li.h_count + 2 * i;
+            off += (size_t)s.n_beams[i];
             const size_t at = w.off[i];
             member_move_clear(F->egos[i], w.geom + at * w.e * 2, w.base + at * w.e * 2, w.vel + at * 2, w.kind + at, w.nvert + at, w.counts[i], w.e,
                               w.mv.h[i], w.cl.h[i]);
@@ -4445,23 +4484,45 @@ extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states
     HIPCHK(li.args.push(F->stream));
     HIPCHK(w.mv.push(F->stream));
     HIPCHK(w.cl.push(F->stream));
-    const bool moves = moving && gmax > 0;
+    const bool moves = s.moving && gmax > 0;
     const dim3 gmove((unsigned)((gmax + 255) / 256), (unsigned)B);
     if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)w.mv.d);       // `base`: the world as the call finds it
     for (int k = 0; k < K; ++k) {
         const double *pose = lg.states + (size_t)k * B * 3;                     // where the advance kernel of tick k - 1 wrote the states
         for (size_t i = 0; i < B; ++i) { li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0; }
-        fleet_ray_launch(F, pose, maxb);
+        fleet_ray_launch(F, pose, maxb, see);
         hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d, pose);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(F->stream));                                // the tick's one wait: the B box counts
-        if (nbox_log) for (size_t i = 0; i < B; ++i) nbox_log[(size_t)k * B + i] = li.h_count[2 * i];
-        rc = fleet_scan_stage(F, none, nullptr, pose, order);
-        if (rc == RDA_OK) rc = fleet_roll_tail(F, k, lg, goal_margin, nullptr, moves ? w.mv.d : nullptr, gmove, clearance_log ? w.cl.d : nullptr);
+        if (s.nbox_log) for (size_t i = 0; i < B; ++i) s.nbox_log[(size_t)k * B + i] = li.h_count[2 * i];
+        rc = fleet_scan_stage(F, none, nullptr, pose, s.order);
+        if (rc == RDA_OK) rc = fleet_roll_tail(F, k, lg, a.goal_margin, nullptr, moves ? w.mv.d : nullptr, gmove, a.clearance_log ? w.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
+        if (peer_log)
+            hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
+                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->pc_log.v.d + (size_t)k * B, (int)B);
     }
     HIPCHK(hipGetLastError());
     return fleet_roll_fetch(F, lay, a);
+}
+extern "C" int rda_fleet_rollout_lidar(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                       int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
+                                       const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
+                                       const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
+                                       int32_t *arrived_at, int32_t *nbox_log, double *clearance_log)
+{
+    const RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    return fleet_rollout_lidar(F, a, LidarArgs{ n_beams, angle_min, angle_max, range_min, range_max, eps, min_samples, order, moving, nbox_log }, false);
+}
+extern "C" int rda_fleet_rollout_lidar_peers(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                             int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
+                                             const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
+                                             const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
+                                             int32_t *arrived_at, int32_t *nbox_log, double *clearance_log, double *peer_clearance_log)
+{
+    RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    a.peer_clearance_log = peer_clearance_log;
+    return fleet_rollout_lidar(F, a, LidarArgs{ n_beams, angle_min, angle_max, range_min, range_max, eps, min_samples, order, moving, nbox_log }, true);
 }
 
 // What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls

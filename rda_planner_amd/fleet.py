@@ -357,18 +357,40 @@ class Fleet:
         """every member's lidar scan of its resident world (`upload_worlds`) from `states[i]`, ray-cast on the device by one launch
         (rda_fleet_raycast; `World.get_lidar_scan` is the specification).  `sensors[i]`: a mapping or object with `number`, `angle_min`, `angle_max`,
         `range_min`, `range_max` (`World.lidar` has them).  Returns one scan dict per member in the ir-sim layout of `World.get_lidar_scan`, which
-        `control(scans=)` takes as it is."""
+        `control(scans=)` takes as it is.  The members do not see each other here: `raycast_peers` is the scan with see_peers, what
+        `rollout(lidar=, see_peers=True)` casts per tick."""
+        return self._raycast(states, sensors, False)
+
+    def raycast_peers(self, states, sensors):
+        """`raycast` with see_peers: every member's scan also ends on the other members' footprints at `states` (rda_fleet_raycast_peers, one
+        launch of lidar::k_raycast_fleet_peers).  The specification is `World.get_lidar_scan` on the member's world followed by
+        `scenarios.peer_footprints(cars, states, i)`: polygons, a member never sees itself, an empty world (`upload_worlds` with an empty list) sees
+        only the others.  Polygon robots only.  The scans go into `control(scans=)` like any other: a seen member reaches the planner as standing
+        boxes, like every lidar obstacle."""
+        return self._raycast(states, sensors, True)
+
+    def _check_see_peers(self):
+        """what see_peers needs of the library and of every member, checked before any library call"""
+        if not getattr(self.api, "has_fleet_lidar_peers", False):
+            raise RuntimeError("the loaded solver library has no lidar that sees the other members (rda_fleet_raycast_peers, rda_fleet_rollout_lidar_peers)")
+        if any(m.car_tuple.cone_type == "norm2" for m in self.members):
+            raise RuntimeError("see_peers casts against the members' footprints as polygons; a circle (norm2) robot is not supported")
+
+    def _raycast(self, states, sensors, see_peers):
         if not getattr(self.api, "has_fleet_rollout_lidar", False):
             raise RuntimeError("the loaded solver library has no ray caster (rda_fleet_raycast)")
+        if see_peers:
+            self._check_see_peers()
         B = len(self.members)
         nb, lo, hi, rmin, rmax = sensor_arrays(sensors, B)
         if len(states) != B:
             raise ValueError("Fleet.raycast: one state per member")
         st = states_array(states, B)
         ranges = np.zeros(max(int(nb.sum()), 1))
-        rc = self.api.fleet_raycast(self._handle, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges))
+        cast, name = (self.api.fleet_raycast_peers, "rda_fleet_raycast_peers") if see_peers else (self.api.fleet_raycast, "rda_fleet_raycast")
+        rc = cast(self._handle, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges))
         if rc < 0:
-            raise RuntimeError(f"rda_fleet_raycast failed with code {rc} (worlds are uploaded with Fleet.upload_worlds)")
+            raise RuntimeError(f"{name} failed with code {rc} (worlds are uploaded with Fleet.upload_worlds)")
         cut = np.concatenate([[0], np.cumsum(nb)])
         return [{"ranges": ranges[cut[i]:cut[i + 1]].copy(), "angle_min": lo[i], "angle_max": hi[i], "range_min": rmin[i], "range_max": rmax[i],
                  "angle_increment": (hi[i] - lo[i]) / max(int(nb[i]) - 1, 1)} for i in range(B)]
@@ -399,6 +421,13 @@ class Fleet:
         `scan_min_samples`, the member's `obstacle_order`) with one short wait for the B box counts, then the tick runs as above.  `moving=True` puts
         the WORLD forward between ticks by the rule above, `clearance=True` logs the clearance against the world (the true obstacles, not the boxes;
         no `moving` needed).  The result has `"boxes"` (steps, B) as well: the boxes every member saw.  `resort` and `obstacle_lists` do not apply.
+        `see_peers=True` (with `lidar=`; rda_fleet_rollout_lidar_peers): the members see each other in the simulated lidar.  Every tick's ray cast
+        also ends on the other members' footprints at the poses of that tick (`raycast_peers`; `scenarios.peer_footprints` is the specification),
+        at no extra launch; members that have arrived stand and are still seen.  A seen member reaches the planner as standing boxes, like every
+        lidar obstacle: its velocity is not estimated.  The result has `"peer_clearance"` (steps, B) as well, every member's separation from the
+        nearest other member after each tick (`scenarios.peer_clearance`; negative = overlap), while `clearance=True` stays the clearance against
+        the world.  Polygon robots only (a circle robot: RuntimeError); without `lidar=` it is a ValueError.  This is perception, not staging:
+        `peers=` with `lidar=` stays refused.
         `peers=True` (rda_fleet_rollout_peers): the members avoid each other as in `control(peers=True)`.  Before every tick the device rewrites the
         peer obstacles of every member's scene from the states of that tick and the controls applied on the tick before (tick 0: every member's
         `cur_vel_array[:, 0]`), re-sorts, and runs the tick of `moving=True` on the member's own obstacles.  `obstacle_lists=` is required on the first
@@ -419,10 +448,13 @@ class Fleet:
         kwargs = dict(kwargs)
         gears = bool(kwargs.pop("gears", False))
         peers, plan = peers_mode(kwargs.pop("peers", False))
+        see_peers = bool(kwargs.pop("see_peers", False))
         if gears and (peers or kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
             raise ValueError("Fleet.rollout: gears=True cannot be combined with peers / lidar= / scans=")
         if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
             raise ValueError("Fleet.rollout: peers=True cannot be combined with lidar= / scans=")
+        if see_peers and kwargs.get("lidar") is None:
+            raise ValueError("Fleet.rollout: see_peers=True belongs to lidar= (members that avoid each other through staged scenes: peers=True)")
         if peers:
             self._check_peers({k: v for k, v in kwargs.items() if k in ("threshold", "ind_range")}, plan)
             if kwargs.get("obstacle_lists") is None and not getattr(self, "_peers_staged", False):
@@ -442,6 +474,8 @@ class Fleet:
                 raise ValueError("Fleet.rollout: scan_eps > 0 and scan_min_samples >= 1")
             if not getattr(self.api, "has_fleet_rollout_lidar", False) or any(m.rda_obstacle for m in ms):
                 raise RuntimeError("Fleet.rollout(lidar=...) needs the lidar rollout (rda_fleet_rollout_lidar); there is no host fallback")
+            if see_peers:
+                self._check_see_peers()
         if (not gears and any(m.enable_reverse for m in ms)) or not all(m._tracks(kwargs) for m in ms):
             raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False (or gears=True); there is no host fallback")
         if gears and not getattr(self.api, "has_fleet_rollout_gears", False):
@@ -482,7 +516,7 @@ class Fleet:
         head = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)), margins.pop())
         logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
         c_log = np.zeros((max(K, 0), B)) if clearance else None
-        p_log = np.zeros((max(K, 0), B)) if peers else None
+        p_log = np.zeros((max(K, 0), B)) if peers or see_peers else None
         g_log = np.zeros((max(K, 0), B), np.int32) if gears else None
         if gears:
             rc, name = self.api.fleet_rollout_gears(self._handle, K, dptr(st), dptr(speed), iptr(piece0), iptr(cur), *head[5:], 1 if resort else 0,
@@ -496,8 +530,12 @@ class Fleet:
         elif sensors is not None:
             order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
             b_log = np.zeros((max(K, 0), B), np.int32)
-            rc, name = self.api.fleet_rollout_lidar(*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples,
-                                                    iptr(order), 1 if moving else 0, *logs, iptr(b_log), dptr(c_log)), "fleet_rollout_lidar"
+            args = (*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples, iptr(order), 1 if moving else 0,
+                    *logs, iptr(b_log), dptr(c_log))
+            if see_peers:
+                rc, name = self.api.fleet_rollout_lidar_peers(*args, dptr(p_log)), "fleet_rollout_lidar_peers"
+            else:
+                rc, name = self.api.fleet_rollout_lidar(*args), "fleet_rollout_lidar"
         else:
             args = head + (1 if resort else 0, dptr(nom_u)) + logs
             rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
@@ -535,7 +573,7 @@ class Fleet:
             out["clearance"] = c_log
         if sensors is not None:
             out["boxes"] = b_log
-        if peers:
+        if peers or see_peers:
             out["peer_clearance"] = p_log
         if gears:
             out["piece"] = g_log

@@ -254,6 +254,14 @@ def peer_obstacles(cars, states, controls, i):
     return out
 
 
+def peer_footprints(cars, states, i):
+    """the polygon obstacles member i's LIDAR sees in place of the other members (lidar::k_raycast_fleet_peers, rda_fleet_raycast_peers,
+    Fleet.raycast(see_peers=True)): `robot_vertices(cars[j], states[j])` for j != i in ascending j, with zero velocity.  The scan
+    of member i is `World.get_lidar_scan` on its world followed by these."""
+    return [Obstacle(None, None, robot_vertices(cars[j], np.asarray(states[j], float).ravel()), "Rpositive", np.zeros((2, 1)))
+            for j in range(len(cars)) if j != i]
+
+
 def peer_clearance(cars, states):
     """(B,) every member's separation from the nearest other member: min over j != i of `_poly_sep` of the two
     footprints (negative = overlap); +inf for a fleet of one"""

@@ -8,7 +8,13 @@
 Every member has a world of its own (obstacles on both sides of its straight path, none on it) and a full-turn lidar of 15 m.  The baseline is the host loop
 on the same box; medians over --repeats.
 
-    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3]
+--see-peers (output: profiles/fleet_lidar_rollout_peers.txt): the members that see each other against the blind ones.  The same fleet for both - member k
+on a lane of its own, LANE m from the next, so that a 15 m lidar reaches the neighbours - and the same windows, the repeats interleaved:
+
+  (c) the sensor alone, ms per call (one launch, one wait): Fleet.raycast (lidar::k_raycast_fleet) | Fleet.raycast_peers (lidar::k_raycast_fleet_peers);
+  (d) the closed loop of K ticks, in ego-steps/s: Fleet.rollout(lidar=, world=) | the same with see_peers=True.
+
+    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3] [--see-peers]
 """
 import argparse
 import os
@@ -20,32 +26,35 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 T, N = 10, 10
+LANE = 10.0             # --see-peers: metres between two members' lanes
 
 
-def world(k, beams, n_obs):
-    """member k's world: a robot at the head of the line (0, 20) -> (60, 20), n_obs circles and rectangles 4 .. 12 m to both sides of it"""
+def world(k, beams, n_obs, y0=20.0):
+    """member k's world: a robot at the head of the line (0, y0) -> (60, y0), n_obs circles and rectangles 4 .. 12 m to both sides of it"""
     from rda_planner_amd import world as irsim
     rng = np.random.default_rng(71000 + k)
     obstacles = []
     for j in range(n_obs):
         side = 1.0 if j % 2 else -1.0
-        pos = [float(rng.uniform(2.0, 70.0)), 20.0 + side * float(rng.uniform(4.0, 12.0)), float(rng.uniform(-np.pi, np.pi))]
+        pos = [float(rng.uniform(2.0, 70.0)), y0 + side * float(rng.uniform(4.0, 12.0)), float(rng.uniform(-np.pi, np.pi))]
         shape = {"name": "circle", "radius": float(rng.uniform(0.3, 0.8))} if j % 3 == 0 else \
                 {"name": "rectangle", "length": float(rng.uniform(0.5, 2.0)), "width": float(rng.uniform(0.3, 1.2))}
         obstacles.append({"number": 1, "distribution": {"name": "manual"}, "state": [pos], "shape": [shape]})
-    cfg = {"world": {"step_time": 0.1, "width": 100, "height": 100},
-           "robot": [{"kinematics": {"name": "acker"}, "shape": {"name": "rectangle", "length": 4.6, "width": 1.6, "wheelbase": 3}, "state": [1.0, 20.0, 0.0],
+    cfg = {"world": {"step_time": 0.1, "width": 100, "height": max(100, y0 + 50)},
+           "robot": [{"kinematics": {"name": "acker"}, "shape": {"name": "rectangle", "length": 4.6, "width": 1.6, "wheelbase": 3}, "state": [1.0, y0, 0.0],
                       "sensors": [{"type": "lidar2d", "range_max": 15.0, "angle_range": 2 * np.pi - 0.01, "number": beams}]}],
            "obstacle": obstacles}
     return irsim.World(cfg)
 
 
-def fleet(B, beams, n_obs):
+def fleet(B, beams, n_obs, lane=0.0):
+    """lane: metres between the members' lanes (0: every member in a world of its own at the same place)"""
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.fleet import Fleet
     from rda_planner_amd.mpc import MPC
-    envs = [world(k, beams, n_obs) for k in range(B)]
-    ms = [MPC(sc.rectangle_robot(), sc.line_path([0, 20, 0], [90, 20, 0]), receding=T, max_edge_num=4, max_obs_num=N, iter_num=2) for _ in envs]
+    ys = [20.0 + lane * k for k in range(B)]
+    envs = [world(k, beams, n_obs, y) for k, y in enumerate(ys)]
+    ms = [MPC(sc.rectangle_robot(), sc.line_path([0, y, 0], [90, y, 0]), receding=T, max_edge_num=4, max_obs_num=N, iter_num=2) for y in ys]
     return Fleet(ms), envs
 
 
@@ -96,6 +105,48 @@ def loop_table(args):
         print("%4d | %12.0f | %12.0f | %.1fx   (boxes seen per tick and member: %.1f)" % (B, np.median(ra), np.median(rb), np.median(rb) / np.median(ra), out["boxes"].mean()))
 
 
+def peers_tables(args):
+    n_obs, K, calls = args.obstacles[0], args.K, 20
+    print("(c) one scan of every member, %d world obstacles per member, lanes %g m apart, ms per call = one launch + one wait (medians of %d x %d calls, "
+          "interleaved): Fleet.raycast | Fleet.raycast_peers" % (n_obs, LANE, args.repeats, calls))
+    print("%4s %6s | %12s | %12s | %s" % ("B", "beams", "blind", "seeing", "seeing / blind"))
+    for B in args.fleets:
+        for beams in args.beams:
+            f, envs = fleet(B, beams, n_obs, LANE)
+            f.upload_worlds([e.obstacles for e in envs])
+            states, sensors = [e.robot.state for e in envs], [e.lidar for e in envs]
+            blind, seeing = f.raycast(states, sensors), f.raycast_peers(states, sensors)      # first use: the ranges buffer, the peer table
+            hit = sum(int((s["ranges"] < b["ranges"]).sum()) for s, b in zip(seeing, blind))
+            tb, ts = [], []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter(); [f.raycast(states, sensors) for _c in range(calls)]; tb.append((time.perf_counter() - t0) / calls)
+                t0 = time.perf_counter(); [f.raycast_peers(states, sensors) for _c in range(calls)]; ts.append((time.perf_counter() - t0) / calls)
+            print("%4d %6d | %12.3f | %12.3f | %.2fx   (beams that end on a member: %d of %d)"
+                  % (B, beams, 1e3 * np.median(tb), 1e3 * np.median(ts), np.median(ts) / np.median(tb), hit, B * beams))
+            f.close()
+    print()
+    print("(d) closed loop of K = %d ticks, %d world obstacles per member, lanes %g m apart, ego-steps/s (medians of %d, interleaved): "
+          "Fleet.rollout(lidar=, world=) | ... see_peers=True" % (K, n_obs, LANE, args.repeats))
+    print("%4s %6s | %12s | %12s | %s" % ("B", "beams", "blind", "seeing", "seeing / blind"))
+    for B in args.fleets:
+        for beams in args.beams:
+            rate, boxes, sep = {False: [], True: []}, {}, None
+            for _ in range(args.repeats):
+                for see in (False, True):
+                    f, envs = fleet(B, beams, n_obs, LANE)
+                    kw = dict(lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs], see_peers=see)
+                    out = f.rollout([e.robot.state.copy() for e in envs], 4.0, 2, **kw)    # first use: tables, logs and the members' raw scenes
+                    t0 = time.perf_counter()
+                    out = f.rollout([out["states"][-1, i].reshape(3, 1) for i in range(B)], 4.0, K, lidar=kw["lidar"], see_peers=see)
+                    rate[see].append(B * K / (time.perf_counter() - t0))
+                    boxes[see] = out["boxes"].mean()
+                    if see:
+                        sep = out["peer_clearance"].min()
+                    f.close()
+            print("%4d %6d | %12.0f | %12.0f | %.2fx   (boxes per tick and member: %.1f | %.1f; least member-to-member separation %.2f m)"
+                  % (B, beams, np.median(rate[False]), np.median(rate[True]), np.median(rate[True]) / np.median(rate[False]), boxes[False], boxes[True], sep))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
@@ -104,7 +155,11 @@ def main():
     ap.add_argument("--obstacles", type=ints, default=[50, 200])
     ap.add_argument("--K", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--see-peers", action="store_true", help="the members that see each other against the blind ones (tables c, d)")
     args = ap.parse_args()
+    if args.see_peers:
+        peers_tables(args)
+        return
     sensor_table(args)
     print()
     loop_table(args)
