@@ -479,6 +479,13 @@ template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v)
     int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+// the same move with bound_ctrl: a lane whose source lies beyond its row reads +0, and the destination needs no initial value (two moves fewer per call)
+template <int CTRL> __device__ __forceinline__ double dpp_mov0_f64(double v)
+{
+    int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
 __device__ __forceinline__ double wave_max(double v)
 {
     double o;
@@ -745,7 +752,16 @@ template <int GW> __device__ __forceinline__ bool solve_wave_warm(WaveLDS &W, co
 // obstacle contributes its centre and -radius): one (obstacle vertex, robot vertex) pair per lane, its admissible arc is
 // centred at the direction of w_kj with half-width acos(-c_j/|w_kj|); the feasible arc is the intersection (two wave
 // minima).  Same steps as oracle/lammuz_np.py:central_normal.  All lanes call, after prepare_wave; `best` is wave-uniform.
-template <int GW> __device__ __forceinline__ bool central_normal_wave(const WaveLDS &W, const RobotLDS &Rb, const Params &P, int wlane, Sol &best)
+// (`clk`: the -DRDA_LMZ_CLK debug build's stamps - before the pair loop, behind it, behind the half angles, the lam solve, the mu solve)
+#ifdef RDA_LMZ_CLK
+#define LMZ_CN_MARK(k) do { if (clk) clk[k] = clock64(); } while (0)
+#else
+#define LMZ_CN_MARK(k) do { } while (0)
+#endif
+// SIDE (the single-ego latency form): the long operations that do not depend on each other - the two tangents of a pair, the two half-angle rsqrts - are formed
+// whatever the case and chosen afterwards, so they run side by side instead of one behind the other in branches of their own; where a value is used it is the same
+// operation on the same operands.
+template <int GW, bool SIDE = false> __device__ __forceinline__ bool central_normal_wave(const WaveLDS &W, const RobotLDS &Rb, const Params &P, int wlane, Sol &best, long long *clk = nullptr)
 {
     const int lane = wlane & (GW - 1);
     if (!(best.m > 0) || !(best.H0 * best.H0 + best.H1 * best.H1 < 1e-8)) return false;
@@ -765,6 +781,7 @@ template <int GW> __device__ __forceinline__ bool central_normal_wave(const Wave
     const double off = P.norm2 ? W.b[2] : 0.0;
     const double ins = rsqrt(as0 * as0 + as1 * as1), u0 = as0 * ins, u1 = as1 * ins;
     bool fail = false; double thi = INFINITY, tlo = INFINITY;           // tan(hi/2), tan(lo/2); INFINITY = the cap hi = lo = pi
+    LMZ_CN_MARK(0);
     for (int pi = lane; pi < nv * nr; pi += GW) {           // one (obstacle vertex, robot vertex) pair per lane and round
         const int k = pi / nr, j = pi - k * nr;
         const double vx = P.norm2 ? W.b[0] : W.vtx[k][0], vy = P.norm2 ? W.b[1] : W.vtx[k][1];
@@ -785,25 +802,40 @@ template <int GW> __device__ __forceinline__ bool central_normal_wave(const Wave
                     const double cp = u0 * epx + u1 * epy, sp = u0 * epy - u1 * epx;     // angle a* -> upper end
                     const double cm = u0 * emx + u1 * emy, sm = emx * u1 - emy * u0;     // angle lower end -> a*
                     double th = INFINITY, tl = INFINITY;
+                    if (SIDE) {
+                        const double qh = sp / (1.0 + cp), ql = sm / (1.0 + cm);
+                        th = (sp >= 0 && cp > -1.0) ? qh : ((sp < 0 && sp > -1e-15) ? 0.0 : INFINITY);
+                        tl = (sm >= 0 && cm > -1.0) ? ql : ((sm < 0 && sm > -1e-15) ? 0.0 : INFINITY);
+                    } else {
                     if (sp >= 0 && cp > -1.0) th = sp / (1.0 + cp);
                     else if (sp < 0 && sp > -1e-15) th = 0.0;                     // a* on the upper end up to rounding
                     if (sm >= 0 && cm > -1.0) tl = sm / (1.0 + cm);
                     else if (sm < 0 && sm > -1e-15) tl = 0.0;
+                    }
                     if (th < thi) thi = th;
                     if (tl < tlo) tlo = tl;
                 }
             }
         }
     }
+    LMZ_CN_MARK(1);
     if (Grp<GW>::ballot(fail, wlane)) return false;
     thi = -Grp<GW>::max(-thi); tlo = -Grp<GW>::max(-tlo);
     if (isinf(thi) && isinf(tlo)) return false;
     // a_c = a* rotated by (hi - lo)/2, from the half-angle tangents
     double chh, shh, chl, shl;
+    if (SIDE) {
+        const double rh = rsqrt(1.0 + thi * thi), rl = rsqrt(1.0 + tlo * tlo);
+        const double sh = thi * rh, sl = tlo * rl;
+        const bool ih = isinf(thi), il = isinf(tlo);
+        chh = ih ? 0.0 : rh; shh = ih ? 1.0 : sh; chl = il ? 0.0 : rl; shl = il ? 1.0 : sl;
+    } else {
     if (isinf(thi)) { chh = 0; shh = 1; } else { const double r = rsqrt(1.0 + thi * thi); chh = r; shh = thi * r; }
     if (isinf(tlo)) { chl = 0; shl = 1; } else { const double r = rsqrt(1.0 + tlo * tlo); chl = r; shl = tlo * r; }
+    }
     const double Cr = chh * chl + shh * shl, Sr = shh * chl - chh * shl;
     const double a0 = u0 * Cr - u1 * Sr, a1 = u1 * Cr + u0 * Sr;
+    LMZ_CN_MARK(2);
     // supporting duals: lam for a, mu for g = -R'a - xi  (argmax over the vertices, lowest index on ties)
     int i1 = -1, i2 = -1; double l1 = 0, l2 = 0;
     if (P.norm2) { i1 = 0; i2 = 1; l1 = a0; l2 = a1; }
@@ -818,6 +850,7 @@ template <int GW> __device__ __forceinline__ bool central_normal_wave(const Wave
         if (l1 < 0) l1 = 0;
         if (l2 < 0) l2 = 0;
     }
+    LMZ_CN_MARK(3);
     const double gx = -(P.cs * a0 + P.sn * a1) - P.xi0, gy = -(-P.sn * a0 + P.cs * a1) - P.xi1;
     int j1, j2; double g1, g2;
     {
@@ -831,6 +864,7 @@ template <int GW> __device__ __forceinline__ bool central_normal_wave(const Wave
         if (g1 < 0) g1 = 0;
         if (g2 < 0) g2 = 0;
     }
+    LMZ_CN_MARK(4);
     double m = P.kappa0 - g1 * Rb.h[j1] - g2 * Rb.h[j2];
     double H0 = P.xi0 + g1 * Rb.G[j1][0] + g2 * Rb.G[j2][0], H1 = P.xi1 + g1 * Rb.G[j1][1] + g2 * Rb.G[j2][1];
     if (P.norm2) {
@@ -856,6 +890,8 @@ __device__ __forceinline__ double lam_of(const Sol &s, int norm2, int e)
     return e == s.i1 ? s.l1 : (e == s.i2 ? s.l2 : 0.0);
 }
 __device__ __forceinline__ double mu_of(const Sol &s, int j) { return j == s.j1 ? s.g1 : (j == s.j2 ? s.g2 : 0.0); }
+
+#undef LMZ_CN_MARK
 
 }  // namespace lmz
 

@@ -544,6 +544,12 @@ __device__ __forceinline__ int hint_read(const Dev &d, int par, int n, int t, bo
     return d.hint[(size_t)(par ^ 1) * d.hint_len + hint_key(d, n, first && t + 1 < d.c.T ? t + 1 : t)];
 }
 __device__ __forceinline__ void hint_write(const Dev &d, int par, int n, int t, int v) { d.hint[(size_t)par * d.hint_len + hint_key(d, n, t)] = v; }
+// ... with the slot's source already at hand (`src` = slot_src[n], or -1 where hint_key would not read it): the same key without the trip to memory for it
+__device__ __forceinline__ void hint_write_src(const Dev &d, int par, int n, int t, int src, int v)
+{
+    const int key = (src >= 0 && src < d.src_cap) ? d.c.N + src : n;
+    d.hint[(size_t)par * d.hint_len + (size_t)t * d.hint_stride + key] = v;
+}
 
 __device__ __forceinline__ void lammuz_body(const Dev &d, const int block, const int it)
 {
@@ -682,23 +688,32 @@ __global__ __launch_bounds__(256) void k_lammuz(Dev d, int it) { lammuz_body(d, 
 //         then k_lmz_finalize: block partials from the stored terms (same function, same order as mode 0) and the tail.
 #ifdef RDA_LMZ_CLK
 __device__ unsigned long long *g_lmz_clk = nullptr;
+constexpr int LMZ_CLK_WORDS = 32;                  // per wave: [0..7] sections, [8..14] counts / totals / wall clock, [16..31] sub-marks (tools/lmz_wave_clocks.py)
 __device__ int *g_lmz_faillog = nullptr;          // [0] count, then (old hint, new support id, circle?) triples of the rows whose certificate failed
 #endif
 template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_body_rows(const Dev &d, const int block, const int nblocks, const int it, const Fin &fin)
 {
 #pragma clang fp contract(on)          // see lammuz_device.h
     constexpr int WPB = GS / 4;        // waves per workgroup (4 rows each)
+    // The single-ego latency form (k_lammuz_rows, one wave per SIMD: the launch is one wave's dependent chain) runs the tail of the row on the row's lanes and
+    // takes three trips to memory off the chain (hint_par inside the batch, the robot tables, the slot's source for the hint write): DESIGN.md 3.1.  The forms
+    // that share their SIMD (dense, common path, work list, fleet) keep the one-lane tail: the lane-parallel one costs them 6 - 14 more spilled registers, and
+    // they are bound by issue, not by latency.
+    constexpr bool LANES = CW;
     __shared__ lmz::WaveLDS wl[GS];
     __shared__ lmz::RobotLDS rb;
     __shared__ double rowv[MODE == 0 ? GS : 1][6];
     const int T = d.c.T, E = d.c.E, R = d.c.R;
 #ifdef RDA_LMZ_CLK
-    // debug build only (tools/lmz_wave_clocks.py): clock64 ticks per section of a wave, in the wave's own 16-word slot of g_lmz_clk
+    // debug build only (tools/lmz_wave_clocks.py): clock64 ticks per section of a wave, in the wave's own LMZ_CLK_WORDS-word slot of g_lmz_clk
     long long clk_prev = clock64(); const long long clk_in = clk_prev; bool clk_enum = false; const unsigned long long clk_wall_in = (unsigned long long)wall_clock64();
-    unsigned long long *const clk_slot = g_lmz_clk ? g_lmz_clk + 16 * (size_t)(block * (GS / 4) + (threadIdx.x >> 6)) : nullptr;
-#define LMZ_CLK(k) do { if (MODE == 0) { const long long now_ = clock64(); if (clk_slot && (threadIdx.x & 63) == 0) clk_slot[k] += (unsigned long long)(now_ - clk_prev); clk_prev = now_; } } while (0)
+    unsigned long long *const clk_slot = g_lmz_clk ? g_lmz_clk + LMZ_CLK_WORDS * (size_t)(block * (GS / 4) + (threadIdx.x >> 6)) : nullptr;
+    long long clk_sub = clk_prev;      // LMZ_SUB(k): ticks since the previous mark of either kind, into word 16 + k - the sub-marks split a section, its rest is what follows the last one
+#define LMZ_CLK(k) do { if (MODE == 0) { const long long now_ = clock64(); if (clk_slot && (threadIdx.x & 63) == 0) clk_slot[k] += (unsigned long long)(now_ - clk_prev); clk_prev = now_; clk_sub = now_; } } while (0)
+#define LMZ_SUB(k) do { if (MODE == 0) { const long long now_ = clock64(); if (clk_slot && (threadIdx.x & 63) == 0) clk_slot[16 + (k)] += (unsigned long long)(now_ - clk_sub); clk_sub = now_; } } while (0)
 #else
 #define LMZ_CLK(k) do { } while (0)
+#define LMZ_SUB(k) do { } while (0)
 #endif
     int tb = 0, jb = 0;                                        // (modes 0, 1) the workgroup's block: stage and GS-slot group
     if (MODE != 2) { block_of(d, block, tb, jb); if (tb < 0) return; }      // a filler of the XCD-aware launch order
@@ -707,12 +722,25 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
     // stop flag, half-spaces, pose / duals, support cache, slot -> obstacle, remembered support): everything a row reads is requested
     // here, in two batches, before the first of them is waited for.  The throughput forms (modes 1, 2) keep their loads where the
     // values are used: there the registers are worth more than the latency (three waves per SIMD hide it).
-    struct Early { double px, py, cs, sn, xi0, xi1, zeta, dbar, prev, vtx[4], A, b, G, h, zold; int cone, src, hpar, hint, npv, nlv; unsigned char lamc[3]; } ey;
+    struct Early { double px, py, cs, sn, xi0, xi1, zeta, dbar, prev, vtx[4], A, b, G, h, zold, rv; int cone, src, hpar, hint, npv, nlv; unsigned char lamc[3], muc; } ey;
     if (MODE == 0) {
         const int nl0 = jb * GS + wv * 4 + row, nl = nl0 < d.Nlive ? nl0 : 0, n = d.rank * d.Nloc + nl;
         ey.src = (d.slot_src && n < d.src_used) ? d.slot_src[n] : -1;
         ey.hpar = d.ctrl->hint_par & 1;
+        // the robot's candidate tables sit in the kernel arguments and are indexed per thread: a trip to memory of their own, which stood between the batch
+        // below and the barrier (load, wait, LDS store).  One element per thread (56 <= the workgroup), requested here with the first loads of the launch
+        static_assert(64 * WPB >= 56, "one element of the robot tables per thread");
+        if (LANES) { ey.muc = d.muc[(int)threadIdx.x < 40 ? threadIdx.x : 0]; ey.rv = (&d.rv[0][0])[(int)threadIdx.x < 56 ? threadIdx.x : 0]; }
     }
+    if (LANES) {
+        // hint_par was requested above, yet it is only used by the batch below, and the compiler moved its load there: issued in the middle of the batch and waited
+        // for at once (the address of the remembered support needs it) - a whole trip to the L2 inside the issue of the batch.  Pinned: it arrives with the stop flag,
+        // a word of the same line
+        int stop = d.ctrl->stop;
+        asm volatile("" : "+v"(ey.hpar), "+v"(stop));
+        ey.hpar = __builtin_amdgcn_readfirstlane(ey.hpar);      // (both are the same for every lane: scalar again behind the pin)
+        if (__builtin_amdgcn_readfirstlane(stop)) return;
+    } else
     if (d.ctrl->stop) return;                                 // (not merged into the batch below: launches behind the stop flag are on the next tick's way and must stay short - measured)
     if (MODE == 2 && block * WPB >= d.ctrl->wl_count + (d.ctrl->wlc_count + 3) / 4) return;  // work-list form: nothing for this workgroup (the list is short or empty since round 3: no trip for the robot data)
     LMZ_CLK(0);
@@ -743,6 +771,7 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
             ey.hint = d.hint[(size_t)(ey.hpar ^ 1) * d.hint_len + (size_t)tr * d.hint_stride + key];
         }
     }
+    LMZ_SUB(0);
     if (MODE == 0) {                                          // (2 R <= 16 < the workgroup: one element per thread, from the batch above)
         if ((int)threadIdx.x < 2 * R) rb.G[threadIdx.x >> 1][threadIdx.x & 1] = ey.G;
         if ((int)threadIdx.x < R) rb.h[threadIdx.x] = ey.h;
@@ -750,9 +779,15 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
         for (int i = threadIdx.x; i < 2 * R; i += 64 * WPB) rb.G[i >> 1][i & 1] = d.G[i];
         for (int i = threadIdx.x; i < R; i += 64 * WPB) rb.h[i] = d.h[i];
     }
-    for (int i = threadIdx.x; i < 40; i += 64 * WPB) rb.muc[i] = d.muc[i];
-    for (int i = threadIdx.x; i < 56; i += 64 * WPB) (&rb.rv[0][0])[i] = (&d.rv[0][0])[i];
+    if (LANES) {
+        if ((int)threadIdx.x < 40) rb.muc[threadIdx.x] = ey.muc;
+        if ((int)threadIdx.x < 56) (&rb.rv[0][0])[threadIdx.x] = ey.rv;
+    } else {
+        for (int i = threadIdx.x; i < 40; i += 64 * WPB) rb.muc[i] = d.muc[i];
+        for (int i = threadIdx.x; i < 56; i += 64 * WPB) (&rb.rv[0][0])[i] = (&d.rv[0][0])[i];
+    }
     if (threadIdx.x == 0) { rb.nmv = d.nmv; rb.nrv = d.nrv; }
+    LMZ_SUB(1);
     // Work-list form: the list has two ends.  Polygon rows (from the front, Ctrl::wl_count) take a wave each: they go straight to the 64-lane enumeration.
     // Circle rows (from the back, Ctrl::wlc_count) take a 16-lane row each, FOUR per wave: their remembered case runs side by side like in the single-ego
     // form, and only a row whose certificate fails is enumerated by its wave (round 6).  A wave slot = one polygon row or one group of four circle rows.
@@ -783,6 +818,7 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
         if (gl < 2 * E) W.A[gl >> 1][gl & 1] = d.A[ao * 2 + gl];
         if (gl < E) W.b[gl] = d.b[ao + gl];
     }
+    LMZ_SUB(2);
     __syncthreads();
     LMZ_CLK(1);
     lmz::Params P;
@@ -923,14 +959,35 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
         lmz::solve_wave(wl[wv * 4 + g], rb, Pg, lane, bg);
         if (row == g) best = bg;
     }
-    if (gl == 0 && live && !defer) hint_write(d, hpar, n, t, best.id >> 1);
-    if (d.centre) lmz::central_normal_wave<16>(W, rb, P, lane, best);
+    if (gl == 0 && live && !defer) {      // (single-ego form: hint_key's read of the slot's source was a trip to memory in front of the central normal)
+        if (LANES) hint_write_src(d, hpar, n, t, ey.src, best.id >> 1); else hint_write(d, hpar, n, t, best.id >> 1);
+    }
+    LMZ_SUB(3);
+#ifdef RDA_LMZ_CLK
+    {
+        long long cn[5]; for (int q = 0; q < 5; ++q) cn[q] = 0;
+        if (d.centre) lmz::central_normal_wave<16, LANES>(W, rb, P, lane, best, cn);
+        // (a row that leaves early has no later stamps: a stamp counts for the wave only when its first lane took it)
+        if (MODE == 0 && clk_slot && (threadIdx.x & 63) == 0) { long long pv = clk_sub; for (int q = 0; q < 5; ++q) if (cn[q]) { clk_slot[20 + q] += (unsigned long long)(cn[q] - pv); pv = cn[q]; } }
+    }
+#else
+    if (d.centre) lmz::central_normal_wave<16, LANES>(W, rb, P, lane, best);
+#endif
     LMZ_CLK(5);
     bad = bad || !(isfinite(best.cost) && isfinite(best.m) && isfinite(best.H0) && isfinite(best.H1));      // uniform over the row
     // ---- fused dual / residual updates (every lane of the row holds the row's winner) ----------------
     const double znew = (d.c.accelerated ? 0.5 : 1.0) * (best.m > 0 ? best.m : 0.0);     // tie-break T2
     double res = 0;
     const bool wr = live && !bad && !defer;
+    if (LANES) {
+        // one selected value through one selected address: as three branches the stores fetched their three base pointers one after the other
+        const bool isl = gl < E, ism = !isl && gl < E + R, isz = gl == E + R;
+        const double vlam = lmz::lam_of(best, P.norm2, gl), vmu = lmz::mu_of(best, gl - E);
+        const double v = isl ? vlam : (ism ? vmu : znew), old = isz ? ey.zold : prev;
+        res = (isl || ism || isz) ? (v - old) * (v - old) : 0.0;
+        double *const p = isl ? &d.lam[o * E + gl] : (ism ? &d.mu[o * R + gl - E] : &d.z[zi]);
+        if (wr && gl <= E + R) *p = v;
+    } else
     if (gl < E) {
         double v = lmz::lam_of(best, P.norm2, gl);
         res = (v - prev) * (v - prev); if (wr) d.lam[o * E + gl] = v;
@@ -942,8 +999,41 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
         const double old = MODE == 0 ? ey.zold : d.z[zi];
         res = (znew - old) * (znew - old); if (wr) d.z[zi] = znew;
     }
+    LMZ_SUB(9);
+    // the row's dual residual: the xor butterfly (8, 4, 2, 1) on DPP row operations instead of four dependent LDS-crossbar permutes.  A rotation by 8 IS xor 8;
+    // behind it the partial sums have period 8 along the row, so the rotation by 4 hands every lane the value of lane ^ 4; xor 2 and xor 1 are quad
+    // permutations.  Every lane adds the same two operands as before.
+    if (LANES) {
+        res += lmz::dpp_mov0_f64<0x128>(res);      // row_ror:8
+        res += lmz::dpp_mov0_f64<0x124>(res);      // row_ror:4
+        res += lmz::dpp_mov0_f64<0x4E>(res);       // quad_perm [2, 3, 0, 1]
+        res += lmz::dpp_mov0_f64<0xB1>(res);       // quad_perm [1, 0, 3, 2]
+    } else {
 #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) res += __shfl_xor(res, off, 16);
+        for (int off = 8; off >= 1; off >>= 1) res += __shfl_xor(res, off, 16);
+    }
+    LMZ_SUB(10);
+    // The row's six sums a = A'lam (2), b'lam, h'mu, G'mu (2) on the row's lanes.  They were one lane's loops over the E and the R rows, an LDS read and the
+    // lam_of / mu_of selects per trip in front of three dependent fused multiply-adds, while the other lanes of the row waited.  Now lane gl holds the
+    // operands of element E-1-gl of the lam sums and of element R-1-gl of the mu sums, and the partial sums travel DOWN the row (row_shl:1: a lane reads
+    // its upper neighbour): lane E-1 adds element 0 to the +0 of lane E, lane E-2 element 1 to that, ... and after E steps lane 0 holds
+    // fma(v[E-1], c[E-1], ... fma(v[0], c[0], +0)) - the operands, the order and the contraction of the loop.  Lanes beyond the sum hold v = c = +0 and
+    // stay +0 (lane 15 reads +0 from beyond the row), a lane that has its final value recomputes it, so max(E, R) steps serve both families.
+    double ax = 0, ay = 0, bl = 0, mh = 0, gx = 0, gy = 0;
+    if (LANES) {
+        const bool le = gl < E, lr = gl < R;
+        const int ie = le ? E - 1 - gl : 0, je = lr ? R - 1 - gl : 0;
+        // (the six operands are read whatever the lane, from a clamped index, and zeroed by a select: as `le ? W.A[ie][0] : 0.0` each read was a branch of its own)
+        const double a0r = W.A[ie][0], a1r = W.A[ie][1], bbr = W.b[ie], hhr = rb.h[je], g0r = rb.G[je][0], g1r = rb.G[je][1];
+        const double vl = le ? lmz::lam_of(best, P.norm2, ie) : 0.0, vm = lr ? lmz::mu_of(best, je) : 0.0;
+        const double a0 = le ? a0r : 0.0, a1 = le ? a1r : 0.0, bb = le ? bbr : 0.0, hh = lr ? hhr : 0.0, g0 = lr ? g0r : 0.0, g1 = lr ? g1r : 0.0;
+        const int ns = E > R ? E : R;
+        for (int s = 0; s < ns; ++s) {
+            ax = vl * a0 + lmz::dpp_mov0_f64<0x101>(ax); ay = vl * a1 + lmz::dpp_mov0_f64<0x101>(ay); bl = vl * bb + lmz::dpp_mov0_f64<0x101>(bl);
+            mh = vm * hh + lmz::dpp_mov0_f64<0x101>(mh); gx = vm * g0 + lmz::dpp_mov0_f64<0x101>(gx); gy = vm * g1 + lmz::dpp_mov0_f64<0x101>(gy);
+        }
+        LMZ_SUB(11);
+    }
     if (gl == 0) {
         const int k = t * d.Nloc + nl;
         RowOut ro;
@@ -951,17 +1041,19 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
         if (live && bad) {
             ro = failed_row(d, k); have = true;
             store_row(d, k, ro);
-            hint_write(d, hpar, n, t, -1);
+            if (LANES) hint_write_src(d, hpar, n, t, ey.src, -1); else hint_write(d, hpar, n, t, -1);
             atomicAdd(&d.ctrl->lmz_fail, 1);
         } else if (wr) {
-            double ax = 0, ay = 0, bl = 0, mh = 0, gx = 0, gy = 0;
-            for (int i = 0; i < E; ++i) {
-                double v = lmz::lam_of(best, P.norm2, i);
-                ax += v * W.A[i][0]; ay += v * W.A[i][1]; bl += v * W.b[i];
-            }
-            for (int j = 0; j < R; ++j) {
-                double v = lmz::mu_of(best, j);
-                mh += v * rb.h[j]; gx += v * rb.G[j][0]; gy += v * rb.G[j][1];
+            if (!LANES) {                 // one lane's loops over the E and the R rows
+                for (int i = 0; i < E; ++i) {
+                    double v = lmz::lam_of(best, P.norm2, i);
+                    ax += v * W.A[i][0]; ay += v * W.A[i][1]; bl += v * W.b[i];
+                }
+                for (int j = 0; j < R; ++j) {
+                    double v = lmz::mu_of(best, j);
+                    mh += v * rb.h[j]; gx += v * rb.G[j][0]; gy += v * rb.G[j][1];
+                }
+                LMZ_SUB(11);
             }
             const double hx = gx + P.cs * ax + P.sn * ay, hy = gy - P.sn * ax + P.cs * ay;      // Hm, :682
             const double xin0 = P.xi0 + hx, xin1 = P.xi1 + hy;                                  // :683
@@ -972,6 +1064,7 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
             ro.ax = ax; ro.ay = ay; ro.bl = bl; ro.c3 = mh + znew - zetan; ro.c4 = gx + xin0; ro.c5 = gy + xin1;
             ro.res = res; ro.hh = hx * hx + hy * hy; have = true;
             store_row(d, k, ro);
+            LMZ_SUB(12);
         }
         if (MODE == 0) {                  // this row's record for the block partial (a dead slot: zeros)
             double *rv = rowv[wv * 4 + row];
@@ -982,6 +1075,7 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
     LMZ_CLK(6);
     if (MODE == 0) {
         __syncthreads();
+        LMZ_SUB(13);
         block_partial(d, tb, jb, rowv, threadIdx.x);
         if (block == 0 && threadIdx.x == 0) d.ctrl->pose_ok = 1;
     }
@@ -996,6 +1090,7 @@ template <int MODE = 0, bool CW = false> __device__ __forceinline__ void lammuz_
 #endif
     }
 #undef LMZ_CLK
+#undef LMZ_SUB
 }
 
 // two builds: all registers and one wave per SIMD (no spills: the shorter critical path a single ego wants), or two
@@ -2600,14 +2695,14 @@ extern "C" int rda_enqueue_range(rda_handle *H, int k0, int k1)
 }
 
 #ifdef RDA_LMZ_CLK
-extern "C" int rda_debug_lmz_clk(rda_handle *H, unsigned long long *out, int max_waves)     // out[max_waves][16]; reads and clears
+extern "C" int rda_debug_lmz_clk(rda_handle *H, unsigned long long *out, int max_waves)     // out[max_waves][LMZ_CLK_WORDS]; reads and clears
 {
     static unsigned long long *buf = nullptr; static int cap = 0;
     static hbuf::Group &keep = *new hbuf::Group;      // the armed buffers live as long as the process (the device globals point into them)
     HIPCHK(hipStreamSynchronize(H->stream));
     if (!buf) {
         hbuf::Group g; unsigned long long *b;
-        if (g.dev(&b, (size_t)max_waves * 16)) return RDA_ERR_HIP;
+        if (g.dev(&b, (size_t)max_waves * LMZ_CLK_WORDS)) return RDA_ERR_HIP;
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lmz_clk), &b, sizeof(b)));
         keep.d.push_back(std::move(g.d[0])); buf = b; cap = max_waves;
         return RDA_OK;
@@ -2626,8 +2721,8 @@ extern "C" int rda_debug_lmz_clk(rda_handle *H, unsigned long long *out, int max
         return RDA_OK;
     }
     if (max_waves > cap) return RDA_ERR_ARG;
-    HIPCHK(hipMemcpy(out, buf, (size_t)max_waves * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(buf, 0, (size_t)cap * 16 * sizeof(unsigned long long)));
+    HIPCHK(hipMemcpy(out, buf, (size_t)max_waves * LMZ_CLK_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(buf, 0, (size_t)cap * LMZ_CLK_WORDS * sizeof(unsigned long long)));
     return RDA_OK;
 }
 #endif

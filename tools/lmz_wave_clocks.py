@@ -13,6 +13,13 @@ sys.path.insert(0, ROOT)
 SO = os.environ.get("RDA_LMZ_CLK_SO") or os.path.join(ROOT, "tools", "librda_hip_clk.so")      # (RDA_LMZ_CLK_SO: another -DRDA_LMZ_CLK build, A/B)
 NAMES = ["stop flag", "robot data, half-spaces -> LDS, barrier", "pose, duals, pose products, support cache", "warm candidate + certificate",
          "shared enumeration of failing rows (2 barriers)", "central normal (T1)", "dual / residual updates, row record", "block partial"]
+WORDS = 32          # per wave slot (LMZ_CLK_WORDS in csrc/rda_hip.hip): [0..7] sections, [8..14] counts / totals, [16..31] sub-marks
+# sub-marks (LMZ_SUB(k) / the central normal's stamps): (section, word - 16, what ends there); a section's rest is what follows its last sub-mark
+SUBS = [(1, 0, "early batch of loads issued"), (1, 1, "robot tables -> LDS"), (1, 2, "half-spaces -> LDS (waits for the batch)"),
+        (5, 3, "hint write issued"), (5, 4, "early outs, a*, row-uniform values"), (5, 5, "pair loop"), (5, 6, "fail ballot, two row minima, half angles"),
+        (5, 7, "lam: arg max, 2 x 2 solve"), (5, 8, "mu: arg max, 2 x 2 solve"),
+        (6, 9, "dual updates, stores issued"), (6, 10, "residual reduction"), (6, 11, "the six sums"), (6, 12, "xi / zeta / row stores issued"),
+        (7, 13, "barrier")]
 
 
 def _decode(c, n):
@@ -74,7 +81,7 @@ def main():
     lib = _lib.hip_api().lib
     import numpy as np
     W = 4096
-    buf = np.zeros((W, 16), dtype=np.uint64)
+    buf = np.zeros((W, WORDS), dtype=np.uint64)
     flog = np.zeros(1 + 3 * 200000, dtype=np.int32)
     state = path[0].copy().reshape(3, 1)
     for k in range(args.steps):
@@ -92,8 +99,14 @@ def main():
     per = out[:, :8].sum(axis=0) / out[:, 8].sum()
     print(f"T={args.horizon} N={args.n_obs}: {int(used.sum())} waves per launch, {int(launches)} executed launches, {out[:, 9].sum() / out[:, 8].sum():.0f} ticks per wave, "
           f"slowest wave {int(out[:, 10].max())} ticks; {int(out[:, 11].sum())} wave-runs in a workgroup that enumerated ({out[:, 12].sum() / max(out[:, 11].sum(), 1):.0f} ticks each)")
+    sub = out[:, 16:32].sum(axis=0) / out[:, 8].sum()
     for k, name in enumerate(NAMES):
         print(f"  [{k}] {name:58s} {per[k]:8.0f} ticks/wave")
+        mine = [(w, what) for sec, w, what in SUBS if sec == k]
+        for w, what in mine:
+            print(f"        {what:52s} {sub[w]:8.0f}")
+        if mine:
+            print(f"        {'rest':52s} {per[k] - sum(sub[w] for w, _ in mine):8.0f}")
     # the LAST executed launch on the device-wide 100 MHz clock: when its waves started and ended
     st, en = out[:, 13] * 0.01, out[:, 14] * 0.01      # us
     t0 = st.min()
