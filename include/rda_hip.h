@@ -606,6 +606,49 @@ int  rda_fleet_rollout_lidar_peers(rda_fleet *f, int K, const double *states /*B
                                    rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
                                    int32_t *nbox_log /*K*B, may be NULL*/, double *clearance_log /*K*B, may be NULL*/,
                                    double *peer_clearance_log /*K*B, may be NULL*/);
+/* Tracked fleet lidar: the boxes of successive scans associated from tick to tick on the device, so that a lidar obstacle reaches the planner with a
+ * velocity and per-stage prediction like every other obstacle.  lidar::k_track_boxes_fleet (csrc/lidar_device.h; one workgroup per member, one launch
+ * whatever B is) keeps a resident table of tracks per member - at most 256, each the history of its box centres, at most 8 ticks - and computes
+ * lidar.track_boxes (rda_planner_amd/lidar.py, the specification) bit for bit: centre = (((x0 + x1) + x2) + x3) * 0.25; only the first 256 boxes of a
+ * scan take part; box i continues previous track j iff they are each other's nearest (lowest index among equals) and their squared distance is at most
+ * gate * gate; a continued track of history h gives v = (c - h[0]) / (dt * len(h)), dt the member's rda_cfg::dt, and keeps (h + [c])[-window:]; every other
+ * box gets v = 0 and starts a track; tracks nobody continues end; a scan without boxes empties the table.  Successive tracked calls are taken to be dt
+ * apart (a caller that skips ticks calls rda_fleet_reset_tracks); gate / dt is also the largest speed a new track can show.  gate > 0 and 1 <= window <= 8,
+ * else RDA_ERR_ARG.  A refused call or a refused allocation leaves tracks, fleet and members as they were.
+ * rda_fleet_upload_scans with the tracker queued directly behind the scan kernel, in front of the one wait for the B box counts (one launch more, no
+ * wait more), and the boxes staged with these velocities: every member with boxes gets slots for T + 1 stages, built by the unchanged conversion kernels
+ * (a box under 0.01 m/s is not predicted, mpc.py:443).  The host does not see the velocities.  Bit for bit rda_fleet_upload_scenes of the same boxes as
+ * 4-vertex polygons with lidar.track_boxes' velocities, where that call builds T + 1 stages too. */
+int  rda_fleet_upload_scans_tracked(rda_fleet *f, const int32_t *n_beams, const double *ranges, const double *angle_min,
+                                    const double *angle_max, const double *range_max, const double *states /*B*3*/,
+                                    double eps, int min_samples, const int32_t *order /*B*/, int32_t *n_boxes /*B or NULL*/,
+                                    double gate, int window);
+/* rda_fleet_rollout_lidar (see = 0) or rda_fleet_rollout_lidar_peers (see != 0: a seen member is tracked like any box; peer_clearance_log is read only
+ * then) with the tracker behind every tick's scan kernel and the tracked staging: their arguments, logs and refusals.  Given the states and the world of
+ * tick k and the tracks of tick k - 1, a tick computes bit for bit what rda_fleet_raycast(_peers), rda_fleet_upload_scans_tracked of those ranges at those
+ * states and rda_fleet_step_tracked compute.  The tracks continue those the fleet holds when the call starts. */
+int  rda_fleet_rollout_lidar_tracked(rda_fleet *f, int K, const double *states /*B*3*/, const double *ref_speed /*B*/,
+                                     const int32_t *cur_index /*B*/, double threshold, int ind_range, int goal_margin,
+                                     const double *nom_u /*B*2*T or NULL = resident*/,
+                                     const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,
+                                     const double *range_min, const double *range_max /*B each*/,
+                                     double eps, int min_samples, const int32_t *order /*B*/, int moving,
+                                     double *states_log /*(K+1)*B*3*/, double *u_log /*K*B*2*/, int32_t *index_log /*K*B*/,
+                                     rda_info *info_log /*K*B, may be NULL*/, int32_t *arrived_at /*B, -1 = not arrived*/,
+                                     int32_t *nbox_log /*K*B, may be NULL*/, double *clearance_log /*K*B, may be NULL*/,
+                                     double *peer_clearance_log /*K*B, may be NULL*/, int see, double gate, int window);
+/* the tracker alone, on boxes the caller supplies: n [B] boxes per member (0 .. min(cap, 4096); more than cap or negative: RDA_ERR_ARG), boxes
+ * [B][cap][4][2]; vel_out [B][cap][2] (may be NULL) gets the first n[i] velocities of member i.  The table advances by one tick, nothing is staged; the
+ * boxes take the place of the last scan's in the fleet's lidar block. */
+int  rda_fleet_track_boxes(rda_fleet *f, const int32_t *n /*B*/, const double *boxes /*B*cap*4*2*/, int cap, double gate, int window,
+                           double *vel_out /*B*cap*2 or NULL*/);
+/* the table as the last tracked call left it: n [B] tracks per member (track k belongs to box k of that call; n may exceed cap: the first cap are
+ * written), centres [B][cap][2] their positions, vel [B][cap][2] the velocities their boxes got, age [B][cap] the entries of their histories (1 .. 8);
+ * each of the three may be NULL.  Before the first tracked call: no tracks. */
+int  rda_fleet_box_tracks(rda_fleet *f, int cap, int32_t *n /*B*/, double *centres, double *vel, int32_t *age);
+/* the members which [count] (NULL: every member) lose their tracks: the boxes of their next tracked tick start new ones.  An index outside the fleet:
+ * RDA_ERR_ARG.  Runs on the fleet's stream. */
+int  rda_fleet_reset_tracks(rda_fleet *f, const int32_t *which /*count, or NULL = all*/, int count);
 /* test hook: the geometry of the resident worlds as it stands, member-major [*n_total][*we][2] (geom and we may be NULL; *n_total = 0: no world) */
 int  rda_debug_fleet_world(rda_fleet *f, double *geom, int32_t *n_total, int32_t *we);
 /* steps k0 .. k1-1 of every member's uploaded trace, asynchronous; read with rda_fetch_result after rda_fleet_sync */

@@ -120,6 +120,11 @@ PROTOTYPES = {
     "fleet_rollout_lidar":  "i hiDDIdiiDIDDDDdiIiDDINIID",
     "fleet_raycast_peers":  "i hIDDDDDD",
     "fleet_rollout_lidar_peers": "i hiDDIdiiDIDDDDdiIiDDINIIDD",
+    "fleet_upload_scans_tracked": "i hIDDDDDdiIIdi",
+    "fleet_rollout_lidar_tracked": "i hiDDIdiiDIDDDDdiIiDDINIIDDidi",
+    "fleet_track_boxes":    "i hIDidiD",
+    "fleet_box_tracks":     "i hiIDDI",
+    "fleet_reset_tracks":   "i hIi",
     "debug_fleet_world":    "i hDII",
     "fleet_enqueue_range":  "i hii",
     "fleet_sync":           "i h",
@@ -213,6 +218,7 @@ class CApi:
         self.has_fleet_peers = has("fleet_rollout_peers")                   # members as each other's obstacles, staged on the device
         self.has_fleet_peers_plan = has("fleet_rollout_peers_plan")         # ... predicted along their planned trajectories
         self.has_fleet_lidar_peers = has("fleet_rollout_lidar_peers")       # members that see each other in the simulated lidar
+        self.has_fleet_lidar_tracked = has("fleet_rollout_lidar_tracked")   # lidar boxes tracked across ticks, staged with velocities
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

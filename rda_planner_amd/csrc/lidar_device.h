@@ -510,6 +510,7 @@ struct Fill {
     double *geom, *vel, *robot; int *nonconvex, *kind, *nvert;
     double rx, ry;
     const double *rob;        // (may be null) the robot position [2] in device memory, taken instead of rx, ry (rda_fleet_rollout_lidar: where the advance kernel wrote it)
+    const double *vel_in;     // (may be null: zeros) the boxes' velocities [n][2] in device memory, where k_track_boxes_fleet wrote them
 };
 __global__ void k_scene_fill_fleet(const Fill *fs)
 {
@@ -520,8 +521,103 @@ __global__ void k_scene_fill_fleet(const Fill *fs)
     if (i >= f.n) return;
     double *g = f.geom + (size_t)i * f.E * 2;
     for (int e = 0; e < f.E; ++e) { g[2 * e] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e] : 0.0; g[2 * e + 1] = e < 4 ? f.boxes[(size_t)i * 8 + 2 * e + 1] : 0.0; }
-    f.vel[2 * i] = 0.0; f.vel[2 * i + 1] = 0.0;
+    f.vel[2 * i] = f.vel_in ? f.vel_in[2 * i] : 0.0; f.vel[2 * i + 1] = f.vel_in ? f.vel_in[2 * i + 1] : 0.0;
     f.kind[i] = 0; f.nvert[i] = 4;
+}
+
+// Boxes tracked from tick to tick (rda_fleet_upload_scans_tracked, rda_fleet_rollout_lidar_tracked, rda_fleet_track_boxes): a velocity for every box of
+// this tick's scan from a resident table of tracks per member.  The specification is lidar.track_boxes (rda_planner_amd/lidar.py), expression by expression
+// (FMA contraction off; only +, -, * and / on doubles occur), so velocities and table are bit-identical to it on the same boxes:
+//   centre       (((x0 + x1) + x2) + x3) * 0.25 per coordinate, the corners in the order scan_body writes them
+//   which boxes  the first m = min(n, MAX_TRACKS); the others get velocity 0 and leave no track
+//   association  mutual nearest neighbour on d2 = dx * dx + dy * dy against the previous tracks' positions: fwd[i] = the lowest j at the minimum of row i,
+//                back[j] = the lowest i at the minimum of column j; box i continues track j = fwd[i] iff back[j] == i and d2 <= gate * gate.  Independent of
+//                the order of the boxes, which follows the cluster order and changes from tick to tick
+//   continued    history h (oldest first, len entries): v = (c - h[0]) / (dt * len), the new history (h + [c])[-window:].  The difference over the track's
+//                AGE, not over one tick: beam spacing / dt puts 2 - 3 m/s of noise on a one-tick difference
+//   otherwise    v = 0, history [c]; tracks nobody continues end; the new table holds track i = box i, count m
+// One workgroup of TRK_NT = MAX_TRACKS threads per member (blockIdx.x), one launch whatever B is.  The table is double-buffered: buffer `par` is read, buffer
+// par ^ 1 written, so no thread overwrites what another still reads and a caller that gives up the tick keeps the old table by not switching.  LDS: the new
+// centres and the previous positions (both at most MAX_TRACKS, so the previous positions are one tile), the two index arrays - 4 * 256 doubles + 2 * 256 ints
+// = 10 KiB; every lane of a wave reads the same opposite entry at the same time (broadcast reads, no bank conflict).  Thread t serves box t in the row phase
+// and previous track t in the column phase; every barrier is reached by the whole workgroup.  The box count is read from where the scan kernel wrote it
+// (pinned host memory, the same stream: the launch sits behind the scan and in front of the tick's wait for the counts).
+constexpr int MAX_TRACKS = 256, TRK_HIST = 8, TRK_NT = MAX_TRACKS;
+struct Track {                // per member
+    const double *boxes;      // [n][4][2] this tick's boxes (device memory)
+    const int *count;         // [0] = n, where the scan kernel wrote it
+    int *cnt[2];              // [1] tracks in the table, per buffer
+    int *len[2];              // [MAX_TRACKS] entries of every track's history
+    double *hist[2];          // [MAX_TRACKS][TRK_HIST][2] oldest first
+    double *tvel[2];          // [MAX_TRACKS][2] the velocity the track's box got (rda_fleet_box_tracks)
+    double *vel;              // [MAXB][2] every box's velocity, what k_scene_fill_fleet reads
+    double dt;                // the member's sample time: successive launches are taken to be dt apart
+};
+__global__ __launch_bounds__(TRK_NT) void k_track_boxes_fleet(const Track *ts, const int par, const double gate, const int window)
+{
+#pragma clang fp contract(off)        // numpy does not fuse: keep every product and sum separately rounded
+    __shared__ double cx[MAX_TRACKS], cy[MAX_TRACKS], qx[MAX_TRACKS], qy[MAX_TRACKS];
+    __shared__ int fwd[MAX_TRACKS], back[MAX_TRACKS];
+    const Track t = ts[blockIdx.x];
+    const int tid = threadIdx.x;
+    int n = *(const volatile int *)t.count, np = *t.cnt[par];
+    n = n < 0 ? 0 : (n > MAXB ? MAXB : n);
+    np = np < 0 ? 0 : (np > MAX_TRACKS ? MAX_TRACKS : np);
+    const int m = n < MAX_TRACKS ? n : MAX_TRACKS;
+    const int *plen = t.len[par]; const double *ph = t.hist[par];
+    if (tid < m) {
+        const double *b = t.boxes + (size_t)tid * 8;
+        cx[tid] = (((b[0] + b[2]) + b[4]) + b[6]) * 0.25;
+        cy[tid] = (((b[1] + b[3]) + b[5]) + b[7]) * 0.25;
+    }
+    int hl = 0;
+    if (tid < np) {
+        hl = plen[tid]; hl = hl < 1 ? 1 : (hl > TRK_HIST ? TRK_HIST : hl);
+        qx[tid] = ph[((size_t)tid * TRK_HIST + hl - 1) * 2]; qy[tid] = ph[((size_t)tid * TRK_HIST + hl - 1) * 2 + 1];
+    }
+    __syncthreads();
+    double best = 0.0;
+    if (tid < m) {                                   // row tid: the nearest previous track
+        int bj = -1;
+        const double x = cx[tid], y = cy[tid];
+        for (int j = 0; j < np; ++j) {
+            const double dx = x - qx[j], dy = y - qy[j], d2 = dx * dx + dy * dy;
+            if (bj < 0 || d2 < best) { best = d2; bj = j; }
+        }
+        fwd[tid] = bj;
+    }
+    if (tid < np) {                                  // column tid: the nearest new box
+        int bi = -1; double bd = 0.0;
+        const double x = qx[tid], y = qy[tid];
+        for (int i = 0; i < m; ++i) {
+            const double dx = cx[i] - x, dy = cy[i] - y, d2 = dx * dx + dy * dy;
+            if (bi < 0 || d2 < bd) { bd = d2; bi = i; }
+        }
+        back[tid] = bi;
+    }
+    __syncthreads();
+    int *nlen = t.len[par ^ 1]; double *nh = t.hist[par ^ 1], *nv = t.tvel[par ^ 1];
+    if (tid < m) {
+        const int j = fwd[tid];
+        const double x = cx[tid], y = cy[tid];
+        double vx = 0.0, vy = 0.0;
+        double *h = nh + (size_t)tid * TRK_HIST * 2;
+        int l = 0;
+        if (j >= 0 && back[j] == tid && best <= gate * gate) {
+            int pl = plen[j]; pl = pl < 1 ? 1 : (pl > TRK_HIST ? TRK_HIST : pl);
+            const double *o = ph + (size_t)j * TRK_HIST * 2;
+            const double span = t.dt * (double)pl;
+            vx = (x - o[0]) / span; vy = (y - o[1]) / span;
+            const int from = pl + 1 > window ? pl + 1 - window : 0;        // (h + [c])[-window:]
+            for (int k = from; k < pl; ++k) { h[2 * l] = o[2 * k]; h[2 * l + 1] = o[2 * k + 1]; ++l; }
+        }
+        h[2 * l] = x; h[2 * l + 1] = y;
+        nlen[tid] = l + 1;
+        nv[2 * tid] = vx; nv[2 * tid + 1] = vy;
+        t.vel[2 * tid] = vx; t.vel[2 * tid + 1] = vy;
+    }
+    for (int i = MAX_TRACKS + tid; i < n; i += TRK_NT) { t.vel[2 * i] = 0.0; t.vel[2 * i + 1] = 0.0; }
+    if (tid == 0) *t.cnt[par ^ 1] = m;
 }
 
 }  // namespace lidar

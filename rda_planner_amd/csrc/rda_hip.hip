@@ -3112,6 +3112,23 @@ struct FleetLidarHost {                   // for rda_fleet_scan_boxes alone: the
     int alloc(size_t B) { return (g.pin(&h_boxes, B * lidar::MAXB * 8) | g.pin(&h_labels, B * lidar::MAXB)) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return h_boxes != nullptr; }
 };
+// Tracked fleet lidar (rda_fleet_upload_scans_tracked, rda_fleet_rollout_lidar_tracked, rda_fleet_track_boxes): lidar::k_track_boxes_fleet's member table and
+// every member's resident table of tracks, double-buffered - buffer `par` holds the tracks as the last tracked tick left them, the kernel writes the other
+// one and the host switches when the tick goes through.  Per buffer and member: the count, per track its length, its history [MAX_TRACKS][8][2] and the
+// velocity its box got; vel [B][MAXB][2]: every box's velocity of the last launch, what the fill kernel reads.  Device memory comes zeroed: no tracks.
+struct FleetTracks {
+    hbuf::Group g; hbuf::Pair<lidar::Track> tab;
+    int *cnt = nullptr, *len = nullptr, *h_cnt = nullptr, *h_len = nullptr; double *hist = nullptr, *tvel = nullptr, *vel = nullptr, *h_hist = nullptr, *h_tvel = nullptr;
+    int par = 0;
+    int alloc(size_t B)
+    {
+        const size_t M = lidar::MAX_TRACKS;
+        return (tab.alloc(g, B) | g.dev(&cnt, 2 * B) | g.dev(&len, 2 * B * M) | g.dev(&hist, 2 * B * M * lidar::TRK_HIST * 2) | g.dev(&tvel, 2 * B * M * 2) |
+                g.dev(&vel, B * lidar::MAXB * 2) | g.pin(&h_cnt, B) | g.pin(&h_len, B * M) | g.pin(&h_hist, B * M * lidar::TRK_HIST * 2) |
+                g.pin(&h_tvel, B * M * 2)) ? RDA_ERR_HIP : RDA_OK;
+    }
+    bool have() const { return cnt != nullptr; }
+};
 // the rollouts: the advance kernel's member table, the io tables of tick 0 | of the later ticks [2][B] (results in the fleet's `out` whatever the members'
 // zero_copy says)
 struct FleetRollTables {
@@ -3209,7 +3226,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     size_t su_lds;
     FleetTrack trk;
     FleetResort res; int rob_pending;     // rob_pending: a copy out of res.rob.h may be queued
-    FleetLidar li; FleetLidarHost li_host;
+    FleetLidar li; FleetLidarHost li_host; FleetTracks tk;
     FleetRollTables ro; FleetRollLog ro_log; int roll_K;      // roll_K: the ticks of the rollout whose logs are on the host
     FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
     FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
@@ -3523,8 +3540,40 @@ static int fleet_scan_check(const rda_fleet *F, const int32_t *n_beams, const do
 
 // All members' scans through ONE lidar::k_scan_fleet launch on the fleet's stream (a workgroup and so a compute unit per member), and the ONE wait for
 // it: the counters are then in li.h_count [B][2], the boxes in li.d_boxes; to_host: labels (at the member's beam offset) and boxes also in li_host.
+struct TrackArgs { double gate; int window; };      // tracked mode: lidar::k_track_boxes_fleet's association gate [m] and history length
+static int track_check(const TrackArgs &t) { return (t.gate > 0 && t.window >= 1 && t.window <= lidar::TRK_HIST) ? RDA_OK : RDA_ERR_ARG; }
+// the tracker's member table -> device: member i's boxes and box count where the scan kernels leave them (li.d_boxes, li.h_count), its part of both buffers
+// of F->tk, its sample time.  The pinned mirror is rewritten only when it differs, which it does on the first tracked call and after the lidar block was
+// made anew (the wait: an earlier copy out of the mirror may still be queued)
+static int fleet_track_table(rda_fleet *F)
+{
+    FleetTracks &tk = F->tk;
+    const size_t B = F->B, M = lidar::MAX_TRACKS;
+    std::vector<lidar::Track> tv(B);
+    for (size_t i = 0; i < B; ++i) {
+        lidar::Track &t = tv[i];
+        memset((void *)&t, 0, sizeof(t));
+        t.boxes = F->li.d_boxes + i * lidar::MAXB * 8; t.count = F->li.h_count + 2 * i;
+        for (size_t p = 0; p < 2; ++p) {
+            t.cnt[p] = tk.cnt + p * B + i; t.len[p] = tk.len + (p * B + i) * M; t.hist[p] = tk.hist + (p * B + i) * M * lidar::TRK_HIST * 2;
+            t.tvel[p] = tk.tvel + (p * B + i) * M * 2;
+        }
+        t.vel = tk.vel + i * lidar::MAXB * 2; t.dt = F->egos[i]->d.c.dt;
+    }
+    if (!mirror_differs(tk.tab, records(tv))) return RDA_OK;
+    HIPCHK(hipStreamSynchronize(F->stream));
+    HIPCHK(mirror_upload(tk.tab, records(tv), F->stream));
+    return RDA_OK;
+}
+// one launch for the fleet, behind the scan kernel that wrote the counts; the caller switches tk.par once the tick goes through
+static void fleet_track_launch(rda_fleet *F, const TrackArgs &t)
+{
+    hipLaunchKernelGGL(lidar::k_track_boxes_fleet, dim3((unsigned)F->B), dim3(lidar::TRK_NT), 0, F->stream, (const lidar::Track *)F->tk.tab.d, F->tk.par, t.gate,
+                       t.window);
+}
+
 static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
-                          const double *range_max, const double *states, double eps, int min_samples, bool to_host)
+                          const double *range_max, const double *states, double eps, int min_samples, bool to_host, const TrackArgs *track = nullptr)
 {
     const size_t B = F->B;
     FleetLidar &li = F->li;
@@ -3541,6 +3590,7 @@ static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ra
     memcpy(li.h_ranges, ranges, off * sizeof(double));                  // one pinned copy of all ranges (off <= B * MAXB)
     HIPCHK(li.args.push(F->stream));
     hipLaunchKernelGGL(lidar::k_scan_fleet, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d);
+    if (track) fleet_track_launch(F, *track);                           // (in front of the wait: the tick gains a launch, no wait)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(F->stream));
     F->rob_pending = 0;
@@ -3574,7 +3624,9 @@ extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const 
 // zero-box rule, the members' records and the LamMuZ launch form follow the counts.  grow: every member's larger raw scene where it needs one, allocated
 // by the caller (nothing of any member has changed when an allocation is refused).  The robot positions: states [B][3] on the host, or (pose_dev) [B][3]
 // in device memory - rda_fleet_rollout_lidar, where only the device knows them.  Host-side member state ends as scan_stage / scene_kernels leave it.
-static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const double *states, const double *pose_dev, const int32_t *order)
+// tracked: the boxes carry the velocities lidar::k_track_boxes_fleet left in tk.vel and every member with boxes gets slots for T + 1 stages - the host does
+// not see the velocities (as with the peers modes); scene::build_body's 0.01 m/s rule decides per box whether it is predicted.
+static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const double *states, const double *pose_dev, const int32_t *order, bool tracked = false)
 {
     const size_t B = F->B;
     FleetLidar &li = F->li;
@@ -3590,8 +3642,8 @@ static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const do
             continue;
         }
         scene_grow_commit(H, grow[i]);
-        const scene::Args a = scene_args(H, n, 1, order[i] ? 1 : 0);
-        f.boxes = li.d_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E;
+        const scene::Args a = scene_args(H, n, tracked ? d.c.T + 1 : 1, order[i] ? 1 : 0);
+        f.boxes = li.d_boxes + i * lidar::MAXB * 8; f.n = n; f.E = a.E; f.vel_in = tracked ? F->tk.vel + i * lidar::MAXB * 2 : nullptr;
         f.geom = const_cast<double *>(a.geom); f.vel = const_cast<double *>(a.vel); f.robot = const_cast<double *>(a.robot);
         f.nonconvex = a.nonconvex; f.kind = const_cast<int *>(a.kind); f.nvert = const_cast<int *>(a.nvert);
         f.rx = states ? states[3 * i] : 0.0; f.ry = states ? states[3 * i + 1] : 0.0; f.rob = pose_dev ? pose_dev + 3 * i : nullptr;
@@ -3613,27 +3665,126 @@ static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const do
 }
 
 // rda_upload_scan for every member: one scan launch, one wait for the B counts, then the staging above, all on the fleet's stream.
-extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
-                                      const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes)
+// track: the tracked form - the tracker's launch behind the scan's, the table switched once nothing can refuse the tick any more
+static int fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                              const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes,
+                              const TrackArgs *track)
 {
     if (!order) return RDA_ERR_ARG;
     int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
+    if (rc == RDA_OK && track) rc = track_check(*track);
     if (rc != RDA_OK) return rc;
     const size_t B = F->B;
     for (rda_handle *H : F->egos) if (H->tick.pending) return RDA_ERR_ARG;                // a member inside a tick of its own
     for (rda_handle *H : F->egos) if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member)
-    const bool fresh = !F->li.have();
-    rc = fleet_lidar_reserve(F, false);
+    const bool fresh = !F->li.have(), fresh_tk = track && !F->tk.have();
+    if (fresh_tk) { FleetTracks t; if (t.alloc(B)) return RDA_ERR_HIP; rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; F->tk = std::move(t); }
+    else rc = fleet_lidar_reserve(F, false);
     if (rc != RDA_OK) return rc;
     rc = fleet_refresh(F);                              // behind whatever the members still have queued
-    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false);
+    if (rc == RDA_OK && track) rc = fleet_track_table(F);
+    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false, track);
     // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
     std::vector<SceneGrow> grow(B);
     for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->li.h_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->li.h_count[2 * i], grow[i]);
-    if (rc != RDA_OK) { if (fresh) F->li = FleetLidar(); return rc; }        // a failed call leaves what the fleet and the members hold as it was
-    rc = fleet_scan_stage(F, grow, states, nullptr, order);
+    if (rc != RDA_OK) {                                 // a failed call leaves what the fleet and the members hold as it was (the tracks: not switched)
+        if (fresh) F->li = FleetLidar();
+        if (fresh_tk) F->tk = FleetTracks();
+        return rc;
+    }
+    if (track) F->tk.par ^= 1;
+    rc = fleet_scan_stage(F, grow, states, nullptr, order, track != nullptr);
     if (rc != RDA_OK) return rc;
     if (n_boxes) for (size_t i = 0; i < B; ++i) n_boxes[i] = F->li.h_count[2 * i];
+    return RDA_OK;
+}
+extern "C" int rda_fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                                      const double *range_max, const double *states, double eps, int min_samples, const int32_t *order, int32_t *n_boxes)
+{
+    return fleet_upload_scans(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, order, n_boxes, nullptr);
+}
+extern "C" int rda_fleet_upload_scans_tracked(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                                              const double *range_max, const double *states, double eps, int min_samples, const int32_t *order,
+                                              int32_t *n_boxes, double gate, int window)
+{
+    const TrackArgs t{ gate, window };
+    return fleet_upload_scans(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, order, n_boxes, &t);
+}
+
+// The tracker alone, on boxes the caller supplies: n [B] counts (at most 4096 each and at most cap), boxes [B][cap][4][2]; vel_out [B][cap][2] (may be
+// null).  The table advances by one tick; nothing is staged.  The boxes take the place of the last scan's in the fleet's lidar block.
+extern "C" int rda_fleet_track_boxes(rda_fleet *F, const int32_t *n, const double *boxes, int cap, double gate, int window, double *vel_out)
+{
+    if (!F || !n || cap < 0 || (cap > 0 && !boxes)) return RDA_ERR_ARG;
+    const TrackArgs t{ gate, window };
+    if (track_check(t)) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    for (size_t i = 0; i < B; ++i) if (n[i] < 0 || n[i] > cap) return RDA_ERR_ARG;
+    for (size_t i = 0; i < B; ++i) if (n[i] > lidar::MAXB) return RDA_ERR_UNSUPPORTED;
+    int rc;
+    if (!F->tk.have()) { FleetTracks nt; if (nt.alloc(B)) return RDA_ERR_HIP; rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; F->tk = std::move(nt); }
+    else { rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; }
+    HIPCHK(hipStreamSynchronize(F->stream));            // (a staging that is still queued may be reading the boxes of the last scan)
+    rc = fleet_track_table(F);
+    if (rc != RDA_OK) return rc;
+    for (size_t i = 0; i < B; ++i) {
+        F->li.h_count[2 * i] = n[i]; F->li.h_count[2 * i + 1] = 0;
+        if (n[i] > 0) HIPCHK(hipMemcpyAsync(F->li.d_boxes + i * lidar::MAXB * 8, boxes + i * (size_t)cap * 8, (size_t)n[i] * 8 * sizeof(double), hipMemcpyHostToDevice, F->stream));
+    }
+    fleet_track_launch(F, t);
+    HIPCHK(hipGetLastError());
+    std::vector<double> v;
+    if (vel_out) {
+        v.resize(B * lidar::MAXB * 2);
+        HIPCHK(hipMemcpyAsync(v.data(), F->tk.vel, v.size() * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    }
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    F->tk.par ^= 1;
+    if (vel_out) for (size_t i = 0; i < B; ++i) memcpy(vel_out + i * (size_t)cap * 2, v.data() + i * lidar::MAXB * 2, (size_t)n[i] * 2 * sizeof(double));
+    return RDA_OK;
+}
+
+// the table as the last tracked call left it: n [B] tracks per member (may exceed cap: the first cap are written), per track its position centres
+// [B][cap][2], the velocity its box got vel [B][cap][2] and the entries of its history age [B][cap] (each may be null).  No tracked call yet: no tracks.
+extern "C" int rda_fleet_box_tracks(rda_fleet *F, int cap, int32_t *n, double *centres, double *vel, int32_t *age)
+{
+    if (!F || !n || cap < 0) return RDA_ERR_ARG;
+    const size_t B = F->B, M = lidar::MAX_TRACKS;
+    FleetTracks &tk = F->tk;
+    if (!tk.have()) { for (size_t i = 0; i < B; ++i) n[i] = 0; return RDA_OK; }
+    const size_t p = (size_t)tk.par;
+    HIPCHK(hipMemcpyAsync(tk.h_cnt, tk.cnt + p * B, B * sizeof(int), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipMemcpyAsync(tk.h_len, tk.len + p * B * M, B * M * sizeof(int), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipMemcpyAsync(tk.h_hist, tk.hist + p * B * M * lidar::TRK_HIST * 2, B * M * lidar::TRK_HIST * 2 * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipMemcpyAsync(tk.h_tvel, tk.tvel + p * B * M * 2, B * M * 2 * sizeof(double), hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    F->rob_pending = 0;
+    for (size_t i = 0; i < B; ++i) {
+        int c = tk.h_cnt[i]; c = c < 0 ? 0 : (c > (int)M ? (int)M : c);
+        n[i] = c;
+        for (int k = 0; k < c && k < cap; ++k) {
+            int l = tk.h_len[i * M + k]; l = l < 1 ? 1 : (l > lidar::TRK_HIST ? lidar::TRK_HIST : l);
+            const size_t o = i * (size_t)cap + k;
+            if (centres) { const double *h = tk.h_hist + ((i * M + k) * lidar::TRK_HIST + (l - 1)) * 2; centres[2 * o] = h[0]; centres[2 * o + 1] = h[1]; }
+            if (vel) { vel[2 * o] = tk.h_tvel[(i * M + k) * 2]; vel[2 * o + 1] = tk.h_tvel[(i * M + k) * 2 + 1]; }
+            if (age) age[o] = l;
+        }
+    }
+    return RDA_OK;
+}
+
+// the members which [count] (NULL: all) lose their tracks: their boxes of the next tracked tick start new ones
+extern "C" int rda_fleet_reset_tracks(rda_fleet *F, const int32_t *which, int count)
+{
+    if (!F || (which && count < 0)) return RDA_ERR_ARG;
+    const size_t B = F->B;
+    if (which) for (int k = 0; k < count; ++k) if (which[k] < 0 || (size_t)which[k] >= B) return RDA_ERR_ARG;
+    FleetTracks &tk = F->tk;
+    if (!tk.have()) return RDA_OK;
+    int *cur = tk.cnt + (size_t)tk.par * B;
+    if (!which) HIPCHK(hipMemsetAsync(cur, 0, B * sizeof(int), F->stream));
+    else for (int k = 0; k < count; ++k) HIPCHK(hipMemsetAsync(cur + which[k], 0, sizeof(int), F->stream));
     return RDA_OK;
 }
 
@@ -4510,11 +4661,12 @@ struct LidarArgs {
     const int32_t *n_beams; const double *angle_min, *angle_max, *range_min, *range_max; double eps; int min_samples; const int32_t *order; int moving;
     int32_t *nbox_log;
 };
-static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs &s, bool see)
+// track (rda_fleet_rollout_lidar_tracked): lidar::k_track_boxes_fleet behind every tick's scan kernel, in front of the wait, and the tracked staging.
+static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs &s, bool see, const TrackArgs *track = nullptr)
 {
     int rc = roll_check_args(F, a);
     if (rc != RDA_OK) return rc;
-    if (!s.order || !(s.eps > 0) || s.min_samples < 1) return RDA_ERR_ARG;
+    if (!s.order || !(s.eps > 0) || s.min_samples < 1 || (track && track_check(*track))) return RDA_ERR_ARG;
     size_t total = 0;
     rc = fleet_ray_check(F, s.n_beams, s.angle_min, s.angle_max, s.range_min, s.range_max, total);
     if (rc == RDA_OK) rc = roll_check_members(F, a.cur_index);
@@ -4527,10 +4679,11 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
     }
     const bool peer_log = see && a.peer_clearance_log && B > 1;
     // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
-    RollReserve rsv; FleetDoubles tray, tpc; FleetPeers tpe;
+    RollReserve rsv; FleetDoubles tray, tpc; FleetPeers tpe; FleetTracks ttk;
     std::vector<SceneGrow> grow(B), none(B);                                    // a raw scene for the most boxes a member's beams can give | per tick: nothing to grow
     {
         int bad = rsv.alloc(F, K, a.clearance_log != nullptr);
+        if (track && !F->tk.have()) bad |= ttk.alloc(B);
         if (total > F->rays.v.n) bad |= tray.alloc(total);
         if (see && !F->pe.have()) bad |= tpe.alloc(B);
         if (peer_log && (size_t)K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)K * B);
@@ -4545,7 +4698,9 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
     if (tray.have()) F->rays = std::move(tray);
     if (tpe.have()) F->pe = std::move(tpe);
     if (tpc.have()) F->pc_log = std::move(tpc);
+    if (ttk.have()) F->tk = std::move(ttk);
     for (size_t i = 0; i < B; ++i) scene_grow_commit(F->egos[i], grow[i]);
+    if (track) { rc = fleet_track_table(F); if (rc != RDA_OK) return rc; }
     RollView rv;
     if (fleet_roll_view(F, a.nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
     if (see) { rc = fleet_peer_table(F); if (rc != RDA_OK) return rc; }
@@ -4587,10 +4742,11 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
         for (size_t i = 0; i < B; ++i) { li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0; }
         fleet_ray_launch(F, pose, maxb, see);
         hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d, pose);
+        if (track) { fleet_track_launch(F, *track); F->tk.par ^= 1; }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(F->stream));                                // the tick's one wait: the B box counts
         if (s.nbox_log) for (size_t i = 0; i < B; ++i) s.nbox_log[(size_t)k * B + i] = li.h_count[2 * i];
-        rc = fleet_scan_stage(F, none, nullptr, pose, s.order);
+        rc = fleet_scan_stage(F, none, nullptr, pose, s.order, track != nullptr);
         if (rc == RDA_OK) rc = fleet_roll_tail(F, k, lg, a.goal_margin, nullptr, moves ? w.mv.d : nullptr, gmove, a.clearance_log ? w.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
         if (peer_log)
@@ -4618,6 +4774,19 @@ extern "C" int rda_fleet_rollout_lidar_peers(rda_fleet *F, int K, const double *
     RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
     a.peer_clearance_log = peer_clearance_log;
     return fleet_rollout_lidar(F, a, LidarArgs{ n_beams, angle_min, angle_max, range_min, range_max, eps, min_samples, order, moving, nbox_log }, true);
+}
+
+extern "C" int rda_fleet_rollout_lidar_tracked(rda_fleet *F, int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold,
+                                               int ind_range, int goal_margin, const double *nom_u, const int32_t *n_beams, const double *angle_min,
+                                               const double *angle_max, const double *range_min, const double *range_max, double eps, int min_samples,
+                                               const int32_t *order, int moving, double *states_log, double *u_log, int32_t *index_log, rda_info *info_log,
+                                               int32_t *arrived_at, int32_t *nbox_log, double *clearance_log, double *peer_clearance_log, int see, double gate,
+                                               int window)
+{
+    RollArgs a{ K, states, ref_speed, cur_index, threshold, ind_range, goal_margin, nom_u, states_log, u_log, index_log, info_log, arrived_at, clearance_log };
+    if (see) a.peer_clearance_log = peer_clearance_log;
+    const TrackArgs t{ gate, window };
+    return fleet_rollout_lidar(F, a, LidarArgs{ n_beams, angle_min, angle_max, range_min, range_max, eps, min_samples, order, moving, nbox_log }, see != 0, &t);
 }
 
 // What a caller that mirrors the members needs besides the logs, of the last tick of the last rollout: every member's full controls (the nominal controls

@@ -106,11 +106,15 @@ class Fleet:
         valid[i] = 0 if arrived else 1
 
     def reset(self, which=None):
-        """`MPC.reset` of the members `which` (indices; default: all), and their plans no longer count for peers="plan" """
+        """`MPC.reset` of the members `which` (indices; default: all); their plans no longer count for peers="plan" and their box tracks
+        (`track=True`) end"""
         _, valid = self._plan_state()
-        for i in (range(len(self.members)) if which is None else which):
+        which = list(range(len(self.members)) if which is None else which)
+        for i in which:
             self.members[i].reset()
             valid[i] = 0
+        if getattr(self.api, "has_fleet_lidar_tracked", False):
+            self.reset_tracks(which)
 
     def lammuz_kernel(self):
         """the LamMuZ launches the next tick issues per ADMM iteration as the members stand now (rda_fleet_lammuz_kernel): kernel names joined by '+'"""
@@ -127,7 +131,8 @@ class Fleet:
         except Exception:
             pass
 
-    def control(self, states, ref_speeds, obstacle_lists=None, scans=None, scan_eps=2.0, scan_min_samples=6, peers=False, peer_controls=None, **kwargs):
+    def control(self, states, ref_speeds, obstacle_lists=None, scans=None, scan_eps=2.0, scan_min_samples=6, peers=False, peer_controls=None,
+                track=False, track_gate=1.0, track_window=8, **kwargs):
         """one MPC step of every member: `states[i]`, `ref_speeds[i]` (a scalar is shared) and `obstacle_lists[i]` are
         what `members[i].control` takes; returns the list of its `(u, info)` results.
         scans: instead of obstacle lists, `scans[i]` is the range scan (the dict `MPC.control(scan=)` takes) member i took from
@@ -142,10 +147,19 @@ class Fleet:
         peers="plan": the same, but a member that has a plan - it went through a tick of this fleet, was not `reset` since and has not arrived - is
         predicted along it instead of at constant velocity: at stage t >= 1 its footprint stands at `scenarios.peer_plan_poses` of its state and the
         `opt_state_list` of its last tick (the plan as displacements anchored at the actual state, the last increment repeated at stage T);
-        rda_fleet_upload_scenes_peers_plan, `scenarios.peer_plan_obstacles` is the specification.  Any other value of `peers` is a ValueError."""
+        rda_fleet_upload_scenes_peers_plan, `scenarios.peer_plan_obstacles` is the specification.  Any other value of `peers` is a ValueError.
+        track=True (with scans=; rda_fleet_upload_scans_tracked): the boxes are associated with those of the previous tracked tick on the device and
+        staged with the velocity of their track (`lidar.track_boxes` is the specification: mutual nearest neighbour within `track_gate` metres,
+        displacement over the track's age of up to `track_window` <= 8 ticks), so a lidar obstacle is predicted over the horizon like any obstacle with
+        a velocity.  Successive tracked ticks are taken to be one `sample_time` apart; `reset_tracks` after a gap.  Result i is what
+        `members[i].control(states[i], ref_speeds[i], lidar.scan_box_tracked(...)[0])` returns with the same tracks.  Without scans= a ValueError."""
         B, start = len(self.members), time.time()
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
+        if track and scans is None:
+            raise ValueError("Fleet.control: track=True tracks the boxes of scans=")
+        if track:
+            self._check_track(track_gate, track_window)
         peers, plan = peers_mode(peers)
         if peers:
             if scans is not None:
@@ -166,13 +180,16 @@ class Fleet:
                 raise ValueError("Fleet.control: one scan per member")
             if not getattr(self.api, "has_fleet_scans", False) or any(m.rda_obstacle for m in self.members):
                 raise RuntimeError("Fleet.control(scans=...) needs the fleet lidar front end (rda_fleet_upload_scans); there is no host fallback")
-            stage = lambda st: self.upload_scans(st, scans, scan_eps, scan_min_samples)      # noqa: E731
+            stage = lambda st: self.upload_scans(st, scans, scan_eps, scan_min_samples,       # noqa: E731
+                                                 track=(float(track_gate), int(track_window)) if track else None)
         else:
             if obstacle_lists is None:
                 obstacle_lists = [[] for _ in range(B)]
             stage = None
         if hasattr(self.api.lib, "rda_fleet_step_tracked") and all(m._tracks(kwargs) for m in self.members):
             return self._control_tracked(states, ref_speeds, obstacle_lists, start, stage=stage, **kwargs)
+        if track:
+            raise RuntimeError("Fleet.control(track=True) needs device-side tracking of the path on every member; there is no host fallback")
         begun = []
         for i, m in enumerate(self.members):
             cur_ref_path, speed, nom_s, ref_list = m._begin(states[i], ref_speeds[i], **kwargs)
@@ -312,20 +329,71 @@ class Fleet:
             raise self.api.failed("fleet_scan_boxes", rc)
         return [boxes[i, :n[i]].copy() for i in range(B)]
 
-    def upload_scans(self, states, scans, eps=2.0, min_samples=6):
+    def upload_scans(self, states, scans, eps=2.0, min_samples=6, track=None):
         """`RDA_solver.upload_scan` for every member (its own `obstacle_order`) in one library call; returns the box counts.
-        Until `sync` or the next `control` the members are not used on their own."""
+        Until `sync` or the next `control` the members are not used on their own.  track=(gate, window): the tracked form
+        (rda_fleet_upload_scans_tracked, see `control`)."""
         if not getattr(self.api, "has_fleet_scans", False):
             raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_upload_scans)")
+        if track is not None:
+            self._check_track(*track)
         n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
         B = len(self.members)
         order = np.fromiter((bool(m.obstacle_order) for m in self.members), np.int32, B)
         n = np.zeros(B, np.int32)
-        rc = self.api.fleet_upload_scans(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
-                                         iptr(order), iptr(n))
+        args = (self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples), iptr(order), iptr(n))
+        if track is not None:
+            rc, name = self.api.fleet_upload_scans_tracked(*args, float(track[0]), int(track[1])), "fleet_upload_scans_tracked"
+        else:
+            rc, name = self.api.fleet_upload_scans(*args), "fleet_upload_scans"
         if rc < 0:
-            raise self.api.failed("fleet_upload_scans", rc)
+            raise self.api.failed(name, rc)
         return n
+
+    def _check_track(self, gate, window):
+        """what track=True needs of the library and of its two parameters, checked before any library call"""
+        if not getattr(self.api, "has_fleet_lidar_tracked", False):
+            raise RuntimeError("the loaded solver library has no box tracker (rda_fleet_upload_scans_tracked, rda_fleet_rollout_lidar_tracked, "
+                               "rda_fleet_track_boxes, rda_fleet_box_tracks, rda_fleet_reset_tracks)")
+        if not float(gate) > 0 or int(window) != window or not 1 <= int(window) <= 8:
+            raise ValueError(f"track_gate > 0 and 1 <= track_window <= 8, got {gate!r}, {window!r}")
+
+    def track_boxes(self, boxes, gate=1.0, window=8):
+        """the tracker alone (rda_fleet_track_boxes; `lidar.track_boxes` per member, bit for bit): `boxes[i]` is member i's (n_i, 4, 2) corner array of
+        this tick; the members' tables advance by one tick and nothing is staged.  Returns the list of (n_i, 2) velocities."""
+        self._check_track(gate, window)
+        B = len(self.members)
+        if boxes is None or len(boxes) != B:
+            raise ValueError("Fleet.track_boxes: one box array per member")
+        arrs = [f64(b).reshape(-1, 4, 2) for b in boxes]
+        n = np.fromiter((len(a) for a in arrs), np.int32, B)
+        cap = max(1, int(n.max()))
+        allb, vel = np.zeros((B, cap, 4, 2)), np.zeros((B, cap, 2))
+        for i, a in enumerate(arrs):
+            allb[i, :len(a)] = a
+        rc = self.api.fleet_track_boxes(self._handle, iptr(n), dptr(allb), cap, float(gate), int(window), dptr(vel))
+        if rc < 0:
+            raise self.api.failed("fleet_track_boxes", rc)
+        return [vel[i, :n[i]].copy() for i in range(B)]
+
+    def box_tracks(self):
+        """every member's tracks as the last tracked call left them (rda_fleet_box_tracks): a list of dicts with `centres` (n_i, 2), `velocities`
+        (n_i, 2) and `age` (n_i,), the entries of the track's history; track k belongs to box k of that call"""
+        self._check_track(1.0, 1)
+        B, cap = len(self.members), 256
+        n, c, v, age = np.zeros(B, np.int32), np.zeros((B, cap, 2)), np.zeros((B, cap, 2)), np.zeros((B, cap), np.int32)
+        rc = self.api.fleet_box_tracks(self._handle, cap, iptr(n), dptr(c), dptr(v), iptr(age))
+        if rc < 0:
+            raise self.api.failed("fleet_box_tracks", rc)
+        return [dict(centres=c[i, :n[i]].copy(), velocities=v[i, :n[i]].copy(), age=age[i, :n[i]].copy()) for i in range(B)]
+
+    def reset_tracks(self, which=None):
+        """the members `which` (indices; default: all) lose their tracks (rda_fleet_reset_tracks): after a gap in the ticks, or a jump of the robot"""
+        self._check_track(1.0, 1)
+        w = None if which is None else np.ascontiguousarray(list(which), np.int32)
+        rc = self.api.fleet_reset_tracks(self._handle, iptr(w), 0 if w is None else len(w))
+        if rc < 0:
+            raise self.api.failed("fleet_reset_tracks", rc)
 
     def upload_worlds(self, obstacle_lists):
         """every member's WORLD - the true obstacles its simulated lidar sees (`raycast`, `rollout(lidar=)`), apart from the obstacles the planner
@@ -424,10 +492,14 @@ class Fleet:
         `see_peers=True` (with `lidar=`; rda_fleet_rollout_lidar_peers): the members see each other in the simulated lidar.  Every tick's ray cast
         also ends on the other members' footprints at the poses of that tick (`raycast_peers`; `scenarios.peer_footprints` is the specification),
         at no extra launch; members that have arrived stand and are still seen.  A seen member reaches the planner as standing boxes, like every
-        lidar obstacle: its velocity is not estimated.  The result has `"peer_clearance"` (steps, B) as well, every member's separation from the
+        lidar obstacle, unless `track=True` estimates its velocity.  The result has `"peer_clearance"` (steps, B) as well, every member's separation from the
         nearest other member after each tick (`scenarios.peer_clearance`; negative = overlap), while `clearance=True` stays the clearance against
         the world.  Polygon robots only (a circle robot: RuntimeError); without `lidar=` it is a ValueError.  This is perception, not staging:
         `peers=` with `lidar=` stays refused.
+        `track=True` (with `lidar=`; rda_fleet_rollout_lidar_tracked; `track_gate`, `track_window` as in `control`): every tick's boxes are tracked
+        on the device behind the scan (one launch more per tick, no wait more) and staged with their tracks' velocities, so what the lidar sees is
+        predicted over the horizon - a crossing obstacle, and with `see_peers=True` another member, is anticipated instead of met as a standing
+        box.  The tracks continue those the fleet holds (`reset_tracks`, `reset`).  Without `lidar=` it is a ValueError.
         `peers=True` (rda_fleet_rollout_peers): the members avoid each other as in `control(peers=True)`.  Before every tick the device rewrites the
         peer obstacles of every member's scene from the states of that tick and the controls applied on the tick before (tick 0: every member's
         `cur_vel_array[:, 0]`), re-sorts, and runs the tick of `moving=True` on the member's own obstacles.  `obstacle_lists=` is required on the first
@@ -449,6 +521,11 @@ class Fleet:
         gears = bool(kwargs.pop("gears", False))
         peers, plan = peers_mode(kwargs.pop("peers", False))
         see_peers = bool(kwargs.pop("see_peers", False))
+        track, track_gate, track_window = bool(kwargs.pop("track", False)), kwargs.pop("track_gate", 1.0), kwargs.pop("track_window", 8)
+        if track and kwargs.get("lidar") is None:
+            raise ValueError("Fleet.rollout: track=True tracks the boxes of lidar=")
+        if track:
+            self._check_track(track_gate, track_window)
         if gears and (peers or kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
             raise ValueError("Fleet.rollout: gears=True cannot be combined with peers / lidar= / scans=")
         if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
@@ -532,7 +609,10 @@ class Fleet:
             b_log = np.zeros((max(K, 0), B), np.int32)
             args = (*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples, iptr(order), 1 if moving else 0,
                     *logs, iptr(b_log), dptr(c_log))
-            if see_peers:
+            if track:
+                rc, name = self.api.fleet_rollout_lidar_tracked(*args, dptr(p_log), 1 if see_peers else 0, float(track_gate),
+                                                                int(track_window)), "fleet_rollout_lidar_tracked"
+            elif see_peers:
                 rc, name = self.api.fleet_rollout_lidar_peers(*args, dptr(p_log)), "fleet_rollout_lidar_peers"
             else:
                 rc, name = self.api.fleet_rollout_lidar(*args), "fleet_rollout_lidar"

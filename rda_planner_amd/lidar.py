@@ -21,6 +21,9 @@ import numpy as np
 
 Obstacle = namedtuple("obstacle", "center radius vertex cone_type velocity")
 
+MAX_TRACKS = 256            # boxes of one scan that take part in the tracking (lidar::MAX_TRACKS)
+MAX_WINDOW = 8              # the longest history a track keeps (lidar::TRK_HIST)
+
 
 def scan_points(scan_data):
     """hits of a scan (`ranges`, `angle_min`, `angle_max`, `range_max`) as an (n, 2) array in the sensor frame;
@@ -137,3 +140,60 @@ def scan_box_device_fleet(fleet, states, scans, eps=2.0, min_samples=6):
     `states[i]`; the list of the members' obstacle lists"""
     return [[Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]
             for boxes in fleet.scan_boxes(states, scans, eps, min_samples)]
+
+
+def box_centres(boxes):
+    """(n, 2) centres of (n, 4, 2) boxes, the corners added in the order the scan kernel writes them: (((x0 + x1) + x2) + x3) * 0.25"""
+    B = np.asarray(boxes, float).reshape(-1, 4, 2)
+    return (((B[:, 0] + B[:, 1]) + B[:, 2]) + B[:, 3]) * 0.25
+
+
+def track_boxes(tracks, boxes, dt, gate=1.0, window=8, max_tracks=MAX_TRACKS):
+    """Velocities of this tick's `boxes` (n, 4, 2) from the tracks of the previous tick: the specification of lidar::k_track_boxes_fleet
+    (csrc/lidar_device.h), which computes the same numbers bit for bit.  Returns (velocities (n, 2), tracks).
+    `tracks`: None or the list this function returned one tick - `dt` - earlier; a track is the list of its past centres, oldest first, 1 .. `window`
+    entries, its position the last one; track i of the returned list belongs to box i.
+      which boxes  the first m = min(n, max_tracks); the others get velocity 0 and leave no track
+      distance     d2[i][j] = dx * dx + dy * dy of centre i against the position of previous track j, every operation rounded separately
+      association  mutual nearest neighbour: fwd[i] = the lowest j at the minimum of row i, back[j] = the lowest i at the minimum of column j; box i
+                   continues track j = fwd[i] if and only if back[j] == i and d2[i][j] <= gate * gate (so the result does not depend on the order of the
+                   boxes, which changes with the cluster order from tick to tick; gate / dt is also the largest speed a new track can show)
+      continued    history h: v = (c - h[0]) / (dt * len(h)) - the difference over the track's age, not over one tick - and the new history is
+                   (h + [c])[-window:]
+      otherwise    v = 0, history [c]; previous tracks that nobody continues end; no boxes: no tracks
+    Boxes are finite numbers."""
+    window = int(window)
+    if not 1 <= window <= MAX_WINDOW or not gate > 0 or not dt > 0:
+        raise ValueError(f"track_boxes: need 1 <= window <= {MAX_WINDOW}, gate > 0 and dt > 0")
+    c = box_centres(boxes)
+    n = len(c)
+    m = min(n, int(max_tracks))
+    prev = list(tracks) if tracks else []
+    vel, out = np.zeros((n, 2)), []
+    fwd = back = d2 = None
+    if m and prev:
+        p = np.array([h[-1] for h in prev], float).reshape(-1, 2)
+        dx, dy = c[:m, None, 0] - p[None, :, 0], c[:m, None, 1] - p[None, :, 1]
+        d2 = dx * dx + dy * dy
+        fwd, back = d2.argmin(axis=1), d2.argmin(axis=0)                      # (argmin: the first, so the lowest, index at the minimum)
+    gate2 = float(gate) * float(gate)
+    for i in range(m):
+        ci = np.array([c[i, 0], c[i, 1]])
+        j = int(fwd[i]) if fwd is not None else -1
+        if j >= 0 and back[j] == i and d2[i, j] <= gate2:
+            h = prev[j]
+            span = float(dt) * float(len(h))
+            first = np.asarray(h[0], float)
+            vel[i] = (ci - first) / span
+            out.append(([np.asarray(q, float) for q in h] + [ci])[-window:])
+        else:
+            out.append([ci])
+    return vel, out
+
+
+def scan_box_tracked(state, scan_data, tracks, dt, eps=2.0, min_samples=6, gate=1.0, window=8):
+    """`scan_box` with the velocities of `track_boxes` in the obstacles' `velocity`: (obstacles, tracks) - `tracks` goes into the next tick's call"""
+    obs = scan_box(state, scan_data, eps, min_samples)
+    boxes = np.array([o.vertex.T for o in obs], float).reshape(-1, 4, 2)
+    vel, tracks = track_boxes(tracks, boxes, dt, gate, window)
+    return [o._replace(velocity=vel[i].reshape(2, 1).copy()) for i, o in enumerate(obs)], tracks

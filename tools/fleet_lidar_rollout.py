@@ -14,7 +14,14 @@ on a lane of its own, LANE m from the next, so that a 15 m lidar reaches the nei
   (c) the sensor alone, ms per call (one launch, one wait): Fleet.raycast (lidar::k_raycast_fleet) | Fleet.raycast_peers (lidar::k_raycast_fleet_peers);
   (d) the closed loop of K ticks, in ego-steps/s: Fleet.rollout(lidar=, world=) | the same with see_peers=True.
 
-    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3] [--see-peers]
+--track (output: profiles/fleet_lidar_rollout_track.txt): the rollout that tracks its boxes against the one that does not, the same scene for both (a
+world per member, as in (b)), the repeats interleaved:
+
+  (e) the closed loop of K ticks, in ego-steps/s: Fleet.rollout(lidar=, world=) | the same with track=True.  The baseline is the untracked rollout.  A
+      tracked tick has one launch more (lidar::k_track_boxes_fleet, behind the scan kernel) and builds and solves slots for T + 1 stages instead of one.
+      The tracker's own time per launch comes from a run under `rocprofv3 --kernel-trace --stats` (--track --profile-run: one short tracked rollout).
+
+    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3] [--see-peers | --track [--profile-run]]
 """
 import argparse
 import os
@@ -147,6 +154,40 @@ def peers_tables(args):
                   % (B, beams, np.median(rate[False]), np.median(rate[True]), np.median(rate[True]) / np.median(rate[False]), boxes[False], boxes[True], sep))
 
 
+def track_table(args):
+    n_obs, K = args.obstacles[0], args.K
+    if args.profile_run:                                                         # for the profiler: one fleet, one short tracked rollout, no timing
+        B, beams = args.fleets[-1], args.beams[-1]
+        f, envs = fleet(B, beams, n_obs)
+        out = f.rollout([e.robot.state.copy() for e in envs], 4.0, K, lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs], track=True)
+        print("tracked rollout of K = %d ticks, B = %d, %d beams: boxes per tick and member %.1f" % (K, B, beams, out["boxes"].mean()))
+        f.close()
+        return
+    print("(e) closed loop of K = %d ticks, %d world obstacles per member, ego-steps/s (medians of %d, interleaved): Fleet.rollout(lidar=, world=) | "
+          "... track=True" % (K, n_obs, args.repeats))
+    print("%4s %6s | %12s | %12s | %s" % ("B", "beams", "untracked", "tracked", "tracked / untracked"))
+    for B in args.fleets:
+        for beams in args.beams:
+            rate, boxes, tracks, fast = {False: [], True: []}, {}, 0.0, 0.0
+            for _ in range(args.repeats):
+                for track in (False, True):
+                    f, envs = fleet(B, beams, n_obs)
+                    kw = dict(lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs], track=track)
+                    out = f.rollout([e.robot.state.copy() for e in envs], 4.0, 2, **kw)    # first use: tables, logs and the members' raw scenes
+                    t0 = time.perf_counter()
+                    out = f.rollout([out["states"][-1, i].reshape(3, 1) for i in range(B)], 4.0, K, lidar=kw["lidar"], track=track)
+                    rate[track].append(B * K / (time.perf_counter() - t0))
+                    boxes[track] = out["boxes"].mean()
+                    if track:
+                        tb = f.box_tracks()
+                        tracks = float(np.mean([len(t["age"]) for t in tb]))
+                        fast = float(np.mean([(np.hypot(t["velocities"][:, 0], t["velocities"][:, 1]) > 0.01).mean() if len(t["age"]) else 0.0 for t in tb]))
+                    f.close()
+            print("%4d %6d | %12.0f | %12.0f | %.2fx   (boxes per tick and member: %.1f | %.1f; tracks per member after the run %.1f, of them predicted %.0f%%)"
+                  % (B, beams, np.median(rate[False]), np.median(rate[True]), np.median(rate[True]) / np.median(rate[False]), boxes[False], boxes[True],
+                     tracks, 100 * fast))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
@@ -156,9 +197,14 @@ def main():
     ap.add_argument("--K", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--see-peers", action="store_true", help="the members that see each other against the blind ones (tables c, d)")
+    ap.add_argument("--track", action="store_true", help="the rollout that tracks its boxes against the one that does not (table e)")
+    ap.add_argument("--profile-run", action="store_true", help="with --track: one short tracked rollout and nothing else, for a profiler")
     args = ap.parse_args()
     if args.see_peers:
         peers_tables(args)
+        return
+    if args.track:
+        track_table(args)
         return
     sensor_table(args)
     print()
