@@ -456,6 +456,12 @@ int  rda_fleet_rollout_gears(rda_fleet *f, int K, const double *states /*B*3*/, 
  * fleet's last rollout was a gear rollout. */
 int  rda_fleet_rollout_last_pieces(rda_fleet *f, int32_t *piece /*B or NULL*/, double *end_headings /*sum P_i or NULL*/);
 /* every member's clearance (as in clearance_log above) at states [B][3] against its resident raw scene as it stands: one launch, one wait.
+ * The figure (scenarios.clearance is the specification; a member without a scene: +inf) is the smallest over the member's obstacles of
+ *   polygon  overlapping: minus the penetration depth (the smallest overlap over the outward edge normals of footprint and obstacle); apart: the distance
+ *            where a vertex faces an edge, and where two vertices face each other the separating-axis gap - positive, never above the distance
+ *   circle   the distance of the centre to the footprint's boundary, negative when the centre lies in the footprint, minus the radius
+ * Convex polygons of either winding (obstacles, and the footprint: the rows of G in either order), read off the sign of the shoelace sum; a repeated
+ * vertex is allowed (zero-length edges are skipped).  Not defined: non-convex polygons, polygons with a zero shoelace sum.
  * RDA_ERR_UNSUPPORTED: a norm2 robot; RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_clearance(rda_fleet *f, const double *states /*B*3*/, double *clearance /*B*/);
 /* Members that avoid each other: every other member is an ordinary moving polygon obstacle of member i's raw scene, staged on the device
@@ -533,6 +539,7 @@ int  rda_fleet_rollout_peers_plan(rda_fleet *f, int K, const double *states /*B*
  * rollout or without out_s. */
 int  rda_fleet_rollout_last_plan(rda_fleet *f, double *out_s /*B*3*(T+1)*/);
 /* every member's separation from the nearest other member (as in peer_clearance_log above) at states [B][3]: one launch, one wait; needs no staged scene.
+ * The polygon figure of rda_fleet_clearance between two footprints, each of either winding.
  * RDA_ERR_UNSUPPORTED: a robot the clearance does not take (see rda_fleet_clearance); RDA_ERR_ARG: a member inside rda_tracked_begin. */
 int  rda_fleet_peer_clearance(rda_fleet *f, const double *states /*B*3*/, double *out /*B*/);
 /* A resident WORLD per member: the true obstacles a simulated lidar sees (rda_fleet_raycast, rda_fleet_rollout_lidar), kept apart from the member's raw

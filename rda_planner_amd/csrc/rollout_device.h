@@ -117,12 +117,16 @@ __global__ void k_gear_headings(const Gears *gs, double *out, int B)
 }
 
 // Robot / obstacle clearance of every member on the device (rda_fleet_rollout_moving's clearance log, rda_fleet_clearance): scenarios.clearance for a polygon
-// robot (scenarios.py:205-220) against ALL n obstacles of the member's resident raw scene as it stands, not only the N staged ones.  One workgroup per
-// member; its threads stride over the obstacles, the minimum is reduced by shuffles and LDS (a minimum is exact: its order is free).
+// robot against ALL n obstacles of the member's resident raw scene as it stands, not only the N staged ones.  One workgroup per member; its threads stride
+// over the obstacles, the minimum is reduced by shuffles and LDS (a minimum is exact: its order is free).
 //   robot vertices    body-frame intersections of consecutive rows of G x <= h (solved once on the host: Clear::rv), rotated and shifted by the state
-//   polygon obstacle  _poly_sep: the edge normals of both polygons, normalised with the 1e-300 floor; the larger gap wins; no winding fix-up
-//   circle obstacle   point-segment distance of the centre to the robot's edges, minus the radius
-// A member without a raw scene (n = 0): +inf.
+//   winding           either, for the robot and for every obstacle polygon: `clockwise` (scenarios._clockwise) reads it off the shoelace sum of the
+//                     world-frame vertices, products and sums rounded one by one; a zero sum counts as counter-clockwise
+//   polygon obstacle  _poly_sep: the outward edge normals of both polygons (those of a clockwise polygon flipped), normalised with the 1e-300 floor; the
+//                     larger gap wins; zero-length edges (a repeated vertex) are skipped.  Overlapping: minus the penetration depth.  Apart: the distance
+//                     where a vertex faces an edge, the conservative separating-axis gap (never above the distance) where two vertices face each other
+//   circle obstacle   point-segment distance of the centre to the robot's edges, negated when the centre lies in the footprint, minus the radius
+// Convex polygons only; a polygon with a zero shoelace sum is not defined.  A member without a raw scene (n = 0): +inf.
 struct Clear {                // per member
     const double *geom;       // [n][E][2] resident raw geometry (scene::Args::geom)
     const int *kind, *nvert;  // [n]
@@ -131,16 +135,29 @@ struct Clear {                // per member
 };
 constexpr int CLEAR_NT = 256;
 
-// gap of polygon W [kw] along the outward edge normals of polygon V [kv] (one half of _poly_sep)
-__device__ __forceinline__ double sep_half(const double *vx, const double *vy, int kv, const double *wx, const double *wy, int kw, double best)
+// scenarios._clockwise: the shoelace sum of polygon V [k] is negative
+__device__ __forceinline__ bool clockwise(const double *vx, const double *vy, int k)
+{
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int i = 0; i < k; ++i) {
+        const int i1 = i + 1 < k ? i + 1 : 0;
+        s = s + (vx[i] * vy[i1] - vx[i1] * vy[i]);
+    }
+    return s < 0.0;
+}
+
+// gap of polygon W [kw] along the outward edge normals of polygon V [kv] (one half of _poly_sep); cw: V runs clockwise
+__device__ __forceinline__ double sep_half(const double *vx, const double *vy, int kv, bool cw, const double *wx, const double *wy, int kw, double best)
 {
 #pragma clang fp contract(off)
     for (int i = 0; i < kv; ++i) {
         const int i1 = i + 1 < kv ? i + 1 : 0;
         const double ex = vx[i1] - vx[i], ey = vy[i1] - vy[i];
+        if (ex == 0.0 && ey == 0.0) continue;             // a repeated vertex: no normal
         double len = sqrt(ey * ey + ex * ex);
         if (!(len > 1e-300)) len = 1e-300;
-        const double nx = ey / len, ny = -ex / len;
+        const double nx = (cw ? -ey : ey) / len, ny = (cw ? ex : -ex) / len;
         double lo = INFINITY;
         for (int j = 0; j < kw; ++j) { const double p = nx * wx[j] + ny * wy[j]; if (p < lo) lo = p; }
         const double gap = lo - (nx * vx[i] + ny * vy[i]);
@@ -165,12 +182,14 @@ __global__ __launch_bounds__(CLEAR_NT) void k_clearance_fleet(const Clear *cs, c
         ry[threadIdx.x] = (si * c.rv[threadIdx.x][0] + co * c.rv[threadIdx.x][1]) + y;
     }
     __syncthreads();
+    const bool rcw = clockwise(rx, ry, R);
     double best = INFINITY;
     for (int i = threadIdx.x; i < c.n; i += CLEAR_NT) {
         const double *g = c.geom + (size_t)i * E * 2;
         double d;
         if (c.kind[i] == 1) {
             const double cx = g[0], cy = g[1];
+            bool inside = true;
             d = INFINITY;
             for (int j = 0; j < R; ++j) {
                 const int j1 = j + 1 < R ? j + 1 : 0;
@@ -180,15 +199,17 @@ __global__ __launch_bounds__(CLEAR_NT) void k_clearance_fleet(const Clear *cs, c
                 const double px = (ax + s * abx) - cx, py = (ay + s * aby) - cy;
                 const double e = sqrt(px * px + py * py);
                 if (e < d) d = e;
+                const double side = abx * (cy - ay) - aby * (cx - ax);
+                inside = inside && (rcw ? side <= 0.0 : side >= 0.0);
             }
-            d = d - g[2];
+            d = (inside ? -d : d) - g[2];
         } else {
             int k = c.nvert[i];
             if (k > RDA_EMAX) k = RDA_EMAX;
             double qx[RDA_EMAX], qy[RDA_EMAX];
             for (int j = 0; j < k; ++j) { qx[j] = g[2 * j]; qy[j] = g[2 * j + 1]; }
-            d = sep_half(rx, ry, R, qx, qy, k, -INFINITY);
-            d = sep_half(qx, qy, k, rx, ry, R, d);
+            d = sep_half(rx, ry, R, rcw, qx, qy, k, -INFINITY);
+            d = sep_half(qx, qy, k, clockwise(qx, qy, k), rx, ry, R, d);
         }
         if (d < best) best = d;
     }
@@ -204,7 +225,8 @@ __global__ __launch_bounds__(CLEAR_NT) void k_clearance_fleet(const Clear *cs, c
 
 // Member-to-member separation (rda_fleet_rollout_peers' peer clearance log, rda_fleet_peer_clearance): scenarios.peer_clearance - for member i the minimum
 // over j != i of _poly_sep(RV_i, RV_j), both footprints rotated and shifted by their states as in k_clearance_fleet.  One wave per member; its lanes stride
-// over the peers, each runs sep_half both ways, the minimum goes through the wave by shuffles (exact: its order is free).  Launched for B >= 2 only.
+// over the peers, each runs sep_half both ways (footprints of either winding, as there), the minimum goes through the wave by shuffles (exact: its order is
+// free).  Launched for B >= 2 only.
 __device__ __forceinline__ void peer_footprint(const scene::Peer &p, const double *state, double *fx, double *fy)
 {
 #pragma clang fp contract(off)
@@ -221,12 +243,13 @@ __global__ __launch_bounds__(64) void k_peer_clearance_fleet(const scene::Peer *
     double rx[RDA_RMAX], ry[RDA_RMAX], qx[RDA_RMAX], qy[RDA_RMAX];
     const int R = ps[i].R;
     peer_footprint(ps[i], states + 3 * i, rx, ry);
+    const bool rcw = clockwise(rx, ry, R);
     double best = INFINITY;
     for (int j = threadIdx.x; j < B; j += 64) {
         if (j == i) continue;
         peer_footprint(ps[j], states + 3 * j, qx, qy);
-        double d = sep_half(rx, ry, R, qx, qy, ps[j].R, -INFINITY);
-        d = sep_half(qx, qy, ps[j].R, rx, ry, R, d);
+        double d = sep_half(rx, ry, R, rcw, qx, qy, ps[j].R, -INFINITY);
+        d = sep_half(qx, qy, ps[j].R, clockwise(qx, qy, ps[j].R), rx, ry, R, d);
         if (d < best) best = d;
     }
 #pragma unroll

@@ -182,21 +182,44 @@ def kinematic_step(state, u, car_tuple, dt):
     return np.array([[x], [y], [phi]]) + dt * d.reshape(3, 1)
 
 
+def _clockwise(V):
+    """a 2xk polygon runs clockwise: its shoelace sum sum_i (x_i y_i+1 - x_i+1 y_i), every product and sum rounded separately, is negative.  A zero sum
+    (no area, or lost to rounding) counts as counter-clockwise"""
+    W = np.roll(V, -1, axis=1)
+    s = 0.0
+    for i in range(V.shape[1]):
+        s = s + (V[0, i] * W[1, i] - W[0, i] * V[1, i])
+    return s < 0.0
+
+
 def _poly_sep(P, Q):
-    """separating-axis test for two convex polygons given as 2xk CCW arrays -> signed gap (>0: apart)"""
+    """separating-axis test for two convex polygons given as 2xk arrays -> signed gap (> 0: apart; < 0: minus the penetration depth).  Either winding:
+    the edge normals of a clockwise polygon (`_clockwise`) are flipped so that they point outward.  Zero-length edges (a repeated vertex) have no normal
+    and are skipped.  Apart, the value is the largest gap along an edge normal of either polygon: the Euclidean distance when that is attained between
+    a vertex and an edge, smaller when it is attained between two vertices (two rectangles corner to corner on the diagonal: 1 / sqrt 2 of it) -
+    conservative, never above the distance.  Non-convex input is outside the contract; so is a polygon whose shoelace sum is zero."""
     best = -np.inf
     for V, W in ((P, Q), (Q, P)):
         e = np.roll(V, -1, axis=1) - V
         nrm = np.stack((e[1], -e[0]))
+        if _clockwise(V):
+            nrm = -nrm
         nrm = nrm / np.maximum(np.linalg.norm(nrm, axis=0), 1e-300)
         for i in range(V.shape[1]):
+            if e[0, i] == 0.0 and e[1, i] == 0.0:
+                continue
             gap = np.min(nrm[:, i] @ W) - nrm[:, i] @ V[:, i]
             best = max(best, gap)
     return best
 
 
 def clearance(car_tuple, state, obstacles, t=0.0):
-    """conservative robot/obstacle clearance (separating-axis for polygons, vertex/edge for circles)"""
+    """conservative robot/obstacle clearance: the smallest over the obstacles of
+      polygon robot, polygon obstacle   `_poly_sep` of the footprint and the obstacle
+      polygon robot, circle obstacle    the distance of the centre to the footprint's nearest edge, negated when the centre lies in the footprint, minus
+                                        the radius - the signed distance of the disc to the footprint
+      disc robot                        the same with the roles exchanged; disc against disc: centre distance minus both radii
+    Polygons of either winding (`_clockwise` decides on which side of an edge the inside is); zero-length edges are skipped.  Negative = overlap."""
     if car_tuple.cone_type == "norm2":                     # circle robot: centre distance minus the radii
         c0 = np.asarray(state, float).ravel()[0:2]
         r0 = -float(np.asarray(car_tuple.h).ravel()[-1])
@@ -207,29 +230,37 @@ def clearance(car_tuple, state, obstacles, t=0.0):
             else:
                 V = o.vertex + o.velocity * t
                 k = V.shape[1]
+                cw = _clockwise(V)
                 inside = True
                 d = np.inf
                 for i in range(k):
                     a, b2 = V[:, i], V[:, (i + 1) % k]
                     ab = b2 - a
+                    if ab[0] == 0.0 and ab[1] == 0.0:
+                        continue
                     s_ = np.clip((c0 - a) @ ab / (ab @ ab), 0, 1)
                     d = min(d, np.linalg.norm(a + s_ * ab - c0))
-                    inside = inside and (ab[0] * (c0[1] - a[1]) - ab[1] * (c0[0] - a[0])) >= 0
+                    side = ab[0] * (c0[1] - a[1]) - ab[1] * (c0[0] - a[0])
+                    inside = inside and ((side <= 0) if cw else (side >= 0))
                 out = min(out, (-d if inside else d) - r0)
         return out
     RV = robot_vertices(car_tuple, np.asarray(state, float).ravel())
+    cw = _clockwise(RV)
     out = np.inf
     for o in obstacles:
         if o.cone_type == "norm2":
             c = (o.center + o.velocity * t).ravel()
             d = np.inf
+            inside = True
             k = RV.shape[1]
             for i in range(k):
                 a, b2 = RV[:, i], RV[:, (i + 1) % k]
                 ab = b2 - a
                 s = np.clip((c - a) @ ab / (ab @ ab), 0, 1)
                 d = min(d, np.linalg.norm(a + s * ab - c))
-            out = min(out, d - o.radius)
+                side = ab[0] * (c[1] - a[1]) - ab[1] * (c[0] - a[0])
+                inside = inside and ((side <= 0) if cw else (side >= 0))
+            out = min(out, (-d if inside else d) - o.radius)
         else:
             out = min(out, _poly_sep(RV, o.vertex + o.velocity * t))
     return out
