@@ -2,10 +2,12 @@
 (with its ray-cast lidar) replaces `irsim`, `rda_planner_amd.lidar.scan_box` replaces the script's DBSCAN + cv2 `scan_box`,
 `rda_planner_amd.MPC` replaces `RDA_planner.mpc.MPC` (GPU backend).
 
-    python examples/lidar_path_track_headless.py [world.yaml] [--device-scan]
+    python examples/lidar_path_track_headless.py [world.yaml] [--device-scan] [--split TOL]
 
 --device-scan: the scan goes to `MPC.control(..., scan=scan_data)` - clustering, boxes and staging run on the GPU (rda_upload_scan);
 the default is the host front end, as in the reference.
+--split TOL: every cluster is cut into its straight runs at TOL metres and every run gets its own box (`scan_box_split` on the host,
+`scan_split=TOL` on the device) - for worlds with walls, where one box per cluster covers the free space next to the wall.
 """
 import os
 import sys
@@ -16,7 +18,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 import rda_planner_amd.world as irsim                      # instead of: import irsim
 from rda_planner_amd import scenarios as sc
-from rda_planner_amd.lidar import scan_box
+from rda_planner_amd.lidar import scan_box, scan_box_split
 from rda_planner_amd.mpc import MPC                        # instead of: from RDA_planner.mpc import MPC
 
 
@@ -24,6 +26,11 @@ def main():
     here = os.path.dirname(os.path.abspath(__file__))
     device_scan = "--device-scan" in sys.argv[1:]
     args = [a for a in sys.argv[1:] if a != "--device-scan"]
+    split = None
+    if "--split" in args:
+        k = args.index("--split")
+        split = float(args[k + 1])
+        del args[k:k + 2]
     world = args[0] if args else os.path.join(here, "..", "tests", "golden", "world_lidar_track.yaml")
     env = irsim.make(world, save_ani=False, display=False)
     car = namedtuple("car", "G h cone_type wheelbase max_speed max_acce dynamics")
@@ -36,9 +43,9 @@ def main():
     for i in range(500):
         scan_data = env.get_lidar_scan()
         if device_scan:
-            opt_vel, info = mpc_opt.control(env.robot.state, 4, scan=scan_data)
+            opt_vel, info = mpc_opt.control(env.robot.state, 4, scan=scan_data, **({"scan_split": split} if split else {}))
         else:
-            obs_list = scan_box(env.robot.state, scan_data)
+            obs_list = scan_box_split(env.robot.state, scan_data, tol=split) if split else scan_box(env.robot.state, scan_data)
             seen = max(seen, len(obs_list))
             for o in obs_list:
                 env.draw_box(o.vertex, refresh=True)

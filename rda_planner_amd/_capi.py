@@ -125,6 +125,8 @@ PROTOTYPES = {
     "fleet_track_boxes":    "i hIDidiD",
     "fleet_box_tracks":     "i hiIDDI",
     "fleet_reset_tracks":   "i hIi",
+    "set_scan_split":       "i hd",
+    "fleet_set_scan_split": "i hd",
     "debug_fleet_world":    "i hDII",
     "fleet_enqueue_range":  "i hii",
     "fleet_sync":           "i h",
@@ -219,6 +221,7 @@ class CApi:
         self.has_fleet_peers_plan = has("fleet_rollout_peers_plan")         # ... predicted along their planned trajectories
         self.has_fleet_lidar_peers = has("fleet_rollout_lidar_peers")       # members that see each other in the simulated lidar
         self.has_fleet_lidar_tracked = has("fleet_rollout_lidar_tracked")   # lidar boxes tracked across ticks, staged with velocities
+        self.has_scan_split = has("set_scan_split") and has("fleet_set_scan_split")     # scan clusters cut into straight runs, one box each
 
     def _f(self, name):
         return getattr(self.lib, f"{self.prefix}_{name}")

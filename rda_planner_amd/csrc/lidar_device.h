@@ -34,6 +34,7 @@ struct Args {
     int *count;                                      // [0] boxes, [1] hits (pinned host memory: the host waits for the kernel and reads them)
     int *labels_h;                                   // (may be null) [n_beams] -2 miss, -1 noise, >= 0 cluster, pinned host memory
     double *boxes_h;                                 // (may be null) the host's copy of `boxes`, pinned host memory
+    double split_tol;                                // 0: one box per cluster | > 0 [m]: one per straight run (split_stage); count[0], labels_h, boxes: segments
 };
 
 extern __shared__ __attribute__((aligned(16))) double smem_lidar[];
@@ -87,6 +88,201 @@ __device__ __forceinline__ Extent edge_extent(const double *px, const double *py
         x.lo = fmin(x.lo, a); x.hi = fmax(x.hi, a); x.wlo = fmin(x.wlo, b); x.whi = fmax(x.whi, b);
     }
     return x;
+}
+
+// The split stage (Args::split_tol > 0; lidar.split_runs is the specification, expression by expression): every cluster is cut into its straight runs,
+// the labels in ic become SEGMENT numbers and the hull stage boxes segments.  Called by the whole workgroup with the final cluster labels in ic [nh] and
+// the hits in beam order; returns the number of segments.  What it leaves: px, py, ic [nh] permuted alike into (cluster, beam) order with the noise
+// behind (the sort that follows takes any order), ic = the segment of the point at that position (-1 noise), and split_pos(ia)[i] = the position of hit i.
+//   order     the hits are in beam order already, so a cluster is a few STRETCHES of consecutive hits (one, unless clusters interleave): the heads of the R
+//             stretches are compacted by a block_scan, and stretch r starts at the number of hits in stretches of a lower cluster or of the same cluster
+//             and a lower r - R * R integer steps over R threads instead of an nh * nh rank pass; R is the number of clusters plus a few
+//   runs      a run starts where the cluster changes or the gap rule fails (`near` on neighbours).  start[p] = the first position of p's run, end[first] =
+//             its last one; both from a second block_scan over the run heads
+//   rounds    every run [a, b] with b - a >= 2 that has not been found straight is tested at once, a thread per position: s_p as the specification
+//             writes it, the maximum over a < p < b by a 64-bit LDS atomic max on the bits of s_p (non-negative doubles order like their bit patterns;
+//             a wave that lies inside one run reduces by shuffles first and issues one atomic), then the lowest p at the maximum by an atomic min if
+//             that maximum exceeds the bound.  A run that splits at m becomes [a, m - 1] and [m, b]; one that does not is marked final.  A run's test
+//             reads nothing but that run, so the rounds reach the fixed point of the specification whatever their order; they end when nothing splits
+//   slots     a run that can split has >= 3 points, so the heads of two such runs are >= 3 apart and head / 3 is a slot of its own for the maximum and
+//             the split point: SPLIT_SLOTS of 12 bytes instead of MAXB.  The head resets its slot at the end of the round
+//   numbers   segments are numbered in position order of their heads (cluster, then first point): a third block_scan
+// LDS: nothing added.  Four u16 arrays [MAXB] over ia | ib (positions fit 13 bits) - stretch / run heads, start (stretch bases before), pos, end - and
+// the slots over ic once the labels in it have been used.  Every barrier is reached by the whole workgroup.
+typedef unsigned short u16;
+constexpr int SPLIT_SLOTS = (MAXB - 3) / 3 + 1;           // the last head that can split is MAXB - 3
+constexpr int SPLIT_FINAL = 0x8000;                       // in end[head]: the run has been found straight
+static_assert(MAXB < SPLIT_FINAL, "a position and the final mark share a u16");
+static_assert(4 * MAXB * sizeof(u16) <= 2 * MAXB * sizeof(int), "heads, start, pos, end lie in ia | ib");
+static_assert(SPLIT_SLOTS * (sizeof(unsigned long long) + sizeof(int)) <= (MAXB + 1) * sizeof(int), "the slots lie in ic");
+static_assert((2 * MAXB * sizeof(double) + 2 * MAXB * sizeof(int)) % sizeof(unsigned long long) == 0, "ic is aligned for the 64-bit slots");
+__device__ __forceinline__ const u16 *split_pos(const int *ia) { return reinterpret_cast<const u16 *>(ia) + 2 * MAXB; }
+
+__device__ __forceinline__ int split_stage(double *px, double *py, int *ia, int *ic, int *wtot, const int nh, const double eps2, const double tol)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, lane = tid & 63;
+    u16 *hl = reinterpret_cast<u16 *>(ia), *start = hl + MAXB, *pos = hl + 2 * MAXB, *end = hl + 3 * MAXB;
+    int *first_noise = wtot + NW + 1, *changed = wtot + NW + 2;                 // (behind what block_scan uses)
+    if (tid == 0) *first_noise = nh;
+
+    // ---- (cluster, beam) order: stretches of consecutive hits with one label ----------------------------------------------------------------------
+    int heads = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { const int i = tid * PER + k; heads += (i < nh && (i == 0 || ic[i] != ic[i - 1])) ? 1 : 0; }
+    int R;
+    int r0 = block_scan(heads, wtot, R);
+    {
+        int o = r0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) { const int i = tid * PER + k; if (i < nh && (i == 0 || ic[i] != ic[i - 1])) hl[o++] = (u16)i; }
+    }
+    __syncthreads();
+    for (int r = tid; r < R; r += NT) {                                         // start[r] = where stretch r begins
+        const int c = ic[hl[r]] < 0 ? NONE : ic[hl[r]];
+        int base = 0, j0 = hl[0];
+        for (int q = 0; q < R; ++q) {
+            const int j1 = q + 1 < R ? hl[q + 1] : nh;
+            const int cq = ic[j0] < 0 ? NONE : ic[j0];
+            if (cq < c || (cq == c && q < r)) base += j1 - j0;
+            j0 = j1;
+        }
+        start[r] = (u16)base;
+    }
+    __syncthreads();
+    {
+        double tx[PER], ty[PER]; int tc[PER], tp[PER];
+        int o = r0 - 1;                                                         // (a thread's first hit is a head or belongs to the stretch before)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid * PER + k;
+            tp[k] = 0;
+            if (i < nh) {
+                if (i == 0 || ic[i] != ic[i - 1]) ++o;
+                tp[k] = start[o] + (i - hl[o]); tx[k] = px[i]; ty[k] = py[i]; tc[k] = ic[i];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid * PER + k;
+            if (i < nh) { px[tp[k]] = tx[k]; py[tp[k]] = ty[k]; ic[tp[k]] = tc[k]; pos[i] = (u16)tp[k]; }
+        }
+        __syncthreads();
+    }
+
+    // ---- runs: a head where the cluster changes or the gap rule fails; a noise point is a run of its own that nobody tests ----------------------
+    bool hd[PER];
+    heads = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int p = tid * PER + k;
+        hd[k] = false;
+        if (p < nh) {
+            const int c = ic[p];
+            hd[k] = p == 0 || c < 0 || ic[p - 1] != c || !near(px[p - 1], py[p - 1], px[p], py[p], eps2);
+            if (c < 0 && (p == 0 || ic[p - 1] >= 0)) *first_noise = p;
+            heads += hd[k] ? 1 : 0;
+        }
+    }
+    int R2;
+    r0 = block_scan(heads, wtot, R2);
+    {
+        int o = r0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) if (hd[k]) hl[o++] = (u16)(tid * PER + k);
+    }
+    __syncthreads();
+    {
+        int o = r0 - 1;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int p = tid * PER + k;
+            if (p < nh) {
+                if (hd[k]) { ++o; end[p] = (u16)((o + 1 < R2 ? hl[o + 1] : nh) - 1); }
+                start[p] = hl[o];
+            }
+        }
+    }
+    const int ncp = *first_noise;                                               // clustered points: positions 0 .. ncp - 1
+    unsigned long long *smax = reinterpret_cast<unsigned long long *>(ic);      // (the labels in ic have been used: block_scan's barriers lie between)
+    int *arg = reinterpret_cast<int *>(smax + SPLIT_SLOTS);
+    for (int s = tid; s < SPLIT_SLOTS; s += NT) { smax[s] = 0ull; arg[s] = NONE; }
+    __syncthreads();
+
+    // ---- rounds of the end-point fit -------------------------------------------------------------------------------------------------------------
+    const double tol2 = tol * tol;
+    for (;;) {
+        if (tid == 0) *changed = 0;
+        int ra[PER], rb[PER]; double sv[PER], thr[PER]; bool act[PER], open[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int p = k * NT + tid;                                         // (a wave's lanes on consecutive positions)
+            ra[k] = 0; rb[k] = 0; sv[k] = 0.0; thr[k] = 0.0; act[k] = false; open[k] = false;
+            if (p < ncp) {
+                const int a = start[p], e = end[a], b = e & (SPLIT_FINAL - 1);
+                ra[k] = a; rb[k] = b;
+                open[k] = !(e & SPLIT_FINAL) && b - a >= 2;
+                if (open[k] && p > a && p < b) {
+                    const double ex = px[b] - px[a], ey = py[b] - py[a];
+                    const double L2 = ex * ex + ey * ey;
+                    const double rx = px[p] - px[a], ry = py[p] - py[a];
+                    if (L2 > 0) { const double cr = rx * ey - ry * ex; sv[k] = cr * cr; thr[k] = tol2 * L2; }
+                    else { sv[k] = rx * rx + ry * ry; thr[k] = tol2; }
+                    act[k] = true;
+                }
+            }
+            unsigned long long bits = act[k] ? (unsigned long long)__double_as_longlong(sv[k]) : 0ull;
+            const int a0 = __shfl(ra[k], 0);
+            if (__all(act[k] && ra[k] == a0)) {                                 // the wave lies inside one run: one atomic
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) { const unsigned long long o = __shfl_xor(bits, off); bits = o > bits ? o : bits; }
+                if (lane == 0) atomicMax(&smax[a0 / 3], bits);
+            } else if (act[k]) atomicMax(&smax[ra[k] / 3], bits);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PER; ++k)                                           // the lowest position at the maximum, if the maximum is beyond the bound
+            if (act[k] && (unsigned long long)__double_as_longlong(sv[k]) == smax[ra[k] / 3] && sv[k] > thr[k]) atomicMin(&arg[ra[k] / 3], k * NT + tid);
+        __syncthreads();
+        int m[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) m[k] = open[k] ? arg[ra[k] / 3] : NONE;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int p = k * NT + tid;
+            if (!open[k]) continue;
+            if (m[k] != NONE) {                                                 // [a, b] -> [a, m - 1], [m, b]
+                if (p >= m[k]) start[p] = (u16)m[k];
+                if (p == m[k]) end[p] = (u16)rb[k];
+                if (p == ra[k]) { end[p] = (u16)(m[k] - 1); *changed = 1; }
+            } else if (p == ra[k]) end[p] = (u16)(rb[k] | SPLIT_FINAL);
+            if (p == ra[k]) { smax[p / 3] = 0ull; arg[p / 3] = NONE; }
+        }
+        __syncthreads();
+        const int again = *changed;
+        __syncthreads();
+        if (!again) break;
+    }
+
+    // ---- segment numbers in position order of the run heads ---------------------------------------------------------------------------------------
+    heads = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { const int p = tid * PER + k; hd[k] = p < ncp && start[p] == p; heads += hd[k] ? 1 : 0; }
+    int nseg;
+    r0 = block_scan(heads, wtot, nseg);
+    {
+        int o = r0 - 1;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int p = tid * PER + k;
+            if (hd[k]) ++o;
+            if (p < nh) ic[p] = p < ncp ? o : -1;                               // (the slots are dead: the last round ended with a barrier)
+        }
+    }
+    __syncthreads();
+    return nseg;
 }
 
 // one scan by one workgroup of NT threads with LDS_BYTES of dynamic LDS (every return below is taken by the whole workgroup)
@@ -180,12 +376,16 @@ __device__ __forceinline__ void scan_body(const Args &a)
         ic[i] = root == NONE ? -1 : ib[root];
     }
     __syncthreads();
+    // ---- (split_tol > 0) clusters -> straight runs: from here on a "cluster" is a segment, ic is indexed through split_pos -------------------------
+    const bool split = a.split_tol > 0 && nclus > 0;                           // (uniform)
+    if (split) nclus = split_stage(px, py, ia, ic, wtot, nh, eps2, a.split_tol);
     if (a.labels_h) {
+        const u16 *pos = split_pos(ia);
         int o = first;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int b = tid * PER + k;
-            if (b < nb) a.labels_h[b] = hit[k] ? ic[o] : -2;
+            if (b < nb) a.labels_h[b] = hit[k] ? ic[split ? (int)pos[o] : o] : -2;
             if (hit[k]) ++o;
         }
     }

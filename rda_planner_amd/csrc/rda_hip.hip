@@ -17,6 +17,7 @@
 // between iterations and between MPC steps, exactly like the reference keeps it in CVXPY Parameter
 // values (quirks Q4-Q6 come for free).
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -1584,6 +1585,7 @@ struct rda_handle {
     int ip_rows = 0;         // interior-point mode runs the row-parallel kernel (shape allows it and rda_opts::lmz_ip_rows)
     int admm_it = 0;         // host-driven ADMM pieces (rda_admm_*): the iteration rda_admm_su was last called with
     int stepped = 0;         // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
+    double scan_split = 0.0; // rda_set_scan_split: lidar::Args::split_tol of this handle's scans (0: one box per cluster)
     int timing = 0; size_t ev_used[4] = {0, 0, 0, 0};     // events in use of ev[]: 0 LamMuZ launches, 1 su launches, 2 shard all-gathers, 3 lidar scans (second stream)
     std::vector<double> rob_G, rob_h;     // the robot's G x <= h as handed to rda_create (host copy: the clearance's robot vertices are solved from it)
     hbuf::Group mem;                      // what lives as long as the handle: the Dev arrays (but coef / coefL) and the four sets below
@@ -2581,11 +2583,21 @@ static int scan_run(rda_handle *H, int n_beams, const double *ranges, double ang
     a.n_beams = n_beams; a.ranges = H->li.h_ranges; a.angle_min = angle_min; a.angle_max = angle_max; a.range_max = range_max;
     a.sx = state[0]; a.sy = state[1]; a.sth = state[2]; a.eps = eps; a.min_samples = min_samples;
     a.boxes = H->li.d_boxes; a.count = H->li.h_count;
-    a.labels_h = to_host ? H->li.h_labels : nullptr; a.boxes_h = to_host ? H->li.h_boxes : nullptr;
+    a.labels_h = to_host ? H->li.h_labels : nullptr; a.boxes_h = to_host ? H->li.h_boxes : nullptr; a.split_tol = H->scan_split;
     { TimedLaunch timed(H, 3, H->stream2); hipLaunchKernelGGL(lidar::k_scan, dim3(1), dim3(lidar::NT), lidar::LDS_BYTES, H->stream2, a); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(H->stream2));
     *n_boxes = H->li.h_count[0];
+    return RDA_OK;
+}
+
+// The split stage of the scan kernels (lidar::split_stage): 0 = off, the default; the value stays until it is set again.  The handle's value is read by
+// rda_scan_boxes and rda_upload_scan, the fleet's by every fleet call that scans - the members' own values are not read there.
+static bool scan_split_ok(double tol) { return tol >= 0 && tol <= DBL_MAX; }      // (a NaN fails both)
+extern "C" int rda_set_scan_split(rda_handle *H, double tol)
+{
+    if (!H || !scan_split_ok(tol)) return RDA_ERR_ARG;
+    H->scan_split = tol;
     return RDA_OK;
 }
 
@@ -3227,6 +3239,7 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     FleetTrack trk;
     FleetResort res; int rob_pending;     // rob_pending: a copy out of res.rob.h may be queued
     FleetLidar li; FleetLidarHost li_host; FleetTracks tk;
+    double scan_split = 0.0;              // rda_fleet_set_scan_split: lidar::Args::split_tol of every member's scan in the fleet's calls
     FleetRollTables ro; FleetRollLog ro_log; int roll_K;      // roll_K: the ticks of the rollout whose logs are on the host
     FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
     FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
@@ -3528,6 +3541,14 @@ static int fleet_lidar_reserve(rda_fleet *F, bool host_copy)
     return RDA_OK;
 }
 
+// rda_set_scan_split for the fleet's scans (fleet_scan_run, fleet_rollout_lidar)
+extern "C" int rda_fleet_set_scan_split(rda_fleet *F, double tol)
+{
+    if (!F || !scan_split_ok(tol)) return RDA_ERR_ARG;
+    F->scan_split = tol;
+    return RDA_OK;
+}
+
 // the argument rules of scan_run, for every member
 static int fleet_scan_check(const rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
                             const double *range_max, const double *states, double eps, int min_samples)
@@ -3584,6 +3605,7 @@ static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ra
         a.sx = states[3 * i]; a.sy = states[3 * i + 1]; a.sth = states[3 * i + 2]; a.eps = eps; a.min_samples = min_samples;
         a.boxes = li.d_boxes + i * lidar::MAXB * 8; a.count = li.h_count + 2 * i;
         a.labels_h = to_host ? F->li_host.h_labels + off : nullptr; a.boxes_h = to_host ? F->li_host.h_boxes + i * lidar::MAXB * 8 : nullptr;
+        a.split_tol = F->scan_split;
         li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0;
         off += (size_t)n_beams[i];
     }
@@ -4722,7 +4744,7 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
             lidar::Args &sa = li.args.h[i];
             memset((void *)&sa, 0, sizeof(sa));
             sa.n_beams = s.n_beams[i]; sa.ranges = F->rays.v.d + off; sa.angle_min = s.angle_min[i]; sa.angle_max = s.angle_max[i]; sa.range_max = s.range_max[i];
-            sa.eps = s.eps; sa.min_samples = s.min_samples;                      // (the pose: k_scan_fleet_at's second argument)
+            sa.eps = s.eps; sa.min_samples = s.min_samples; sa.split_tol = F->scan_split;      // (the pose: k_scan_fleet_at's second argument)
             sa.boxes = li.d_boxes + i * lidar::MAXB * 8; sa.count = li.h_count + 2 * i;
             off += (size_t)s.n_beams[i];
             const size_t at = w.off[i];

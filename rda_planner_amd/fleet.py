@@ -15,6 +15,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from ._capi import Info, dptr, iptr, f64
+from .mpc import scan_split_arg
 
 SENSOR_FIELDS = ("number", "angle_min", "angle_max", "range_min", "range_max")
 WORLD_EMAX = 8              # RDA_EMAX of include/rda_hip.h: the most vertices a world polygon may have
@@ -152,10 +153,16 @@ class Fleet:
         staged with the velocity of their track (`lidar.track_boxes` is the specification: mutual nearest neighbour within `track_gate` metres,
         displacement over the track's age of up to `track_window` <= 8 ticks), so a lidar obstacle is predicted over the horizon like any obstacle with
         a velocity.  Successive tracked ticks are taken to be one `sample_time` apart; `reset_tracks` after a gap.  Result i is what
-        `members[i].control(states[i], ref_speeds[i], lidar.scan_box_tracked(...)[0])` returns with the same tracks.  Without scans= a ValueError."""
+        `members[i].control(states[i], ref_speeds[i], lidar.scan_box_tracked(...)[0])` returns with the same tracks.  Without scans= a ValueError.
+        scan_split=tol (with scans=; rda_fleet_set_scan_split): every member's clusters are cut into their straight runs on the device, one box per run
+        (`lidar.scan_box_split` is the specification) - for scenes with walls, where one box per cluster covers the free space the robot stands in.
+        tol [m] finite and > 0; omitted: off, also after a split tick.  Combines with track=True: the tracker only ever sees boxes."""
         B, start = len(self.members), time.time()
         if np.isscalar(ref_speeds):
             ref_speeds = [ref_speeds] * B
+        split = scan_split_arg(kwargs, "Fleet.control", scans is not None, "scans=")
+        if split:
+            self._check_split()
         if track and scans is None:
             raise ValueError("Fleet.control: track=True tracks the boxes of scans=")
         if track:
@@ -181,7 +188,7 @@ class Fleet:
             if not getattr(self.api, "has_fleet_scans", False) or any(m.rda_obstacle for m in self.members):
                 raise RuntimeError("Fleet.control(scans=...) needs the fleet lidar front end (rda_fleet_upload_scans); there is no host fallback")
             stage = lambda st: self.upload_scans(st, scans, scan_eps, scan_min_samples,       # noqa: E731
-                                                 track=(float(track_gate), int(track_window)) if track else None)
+                                                 track=(float(track_gate), int(track_window)) if track else None, split=split)
         else:
             if obstacle_lists is None:
                 obstacle_lists = [[] for _ in range(B)]
@@ -316,10 +323,27 @@ class Fleet:
         lo, hi, rmax = (f64([float(s[k]) for s in scans]) for k in ("angle_min", "angle_max", "range_max"))
         return n_beams, allr, lo, hi, rmax, states_array(states, B)
 
-    def scan_boxes(self, states, scans, eps=2.0, min_samples=6):
-        """`RDA_solver.scan_boxes` for every member in one kernel launch: the list of (n_i, 4, 2) corner arrays"""
+    def _check_split(self):
+        if not getattr(self.api, "has_scan_split", False):
+            raise RuntimeError("the loaded solver library cannot split scan clusters (rda_set_scan_split, rda_fleet_set_scan_split)")
+
+    def set_scan_split(self, tol):
+        """the split tolerance [m] of every member's scan in the fleet's calls (rda_fleet_set_scan_split; the members' own values are not read): 0
+        switches the stage off.  The library is called only when the value changes."""
+        tol = float(tol)
+        if tol == getattr(self, "_scan_split", 0.0):
+            return
+        self._check_split()
+        rc = self.api.fleet_set_scan_split(self._handle, tol)
+        if rc < 0:
+            raise ValueError("scan split: tol must be finite and greater than 0") if rc == -1 else self.api.failed("fleet_set_scan_split", rc)
+        self._scan_split = tol
+
+    def scan_boxes(self, states, scans, eps=2.0, min_samples=6, split=0.0):
+        """`RDA_solver.scan_boxes` for every member in one kernel launch: the list of (n_i, 4, 2) corner arrays (split = tol > 0: one per straight run)"""
         if not getattr(self.api, "has_fleet_scans", False):
             raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_scan_boxes)")
+        self.set_scan_split(split)
         n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
         B, cap = len(self.members), max(1, int(n_beams.max()))
         boxes, n = np.zeros((B, cap, 4, 2)), np.zeros(B, np.int32)
@@ -329,12 +353,13 @@ class Fleet:
             raise self.api.failed("fleet_scan_boxes", rc)
         return [boxes[i, :n[i]].copy() for i in range(B)]
 
-    def upload_scans(self, states, scans, eps=2.0, min_samples=6, track=None):
+    def upload_scans(self, states, scans, eps=2.0, min_samples=6, track=None, split=0.0):
         """`RDA_solver.upload_scan` for every member (its own `obstacle_order`) in one library call; returns the box counts.
         Until `sync` or the next `control` the members are not used on their own.  track=(gate, window): the tracked form
-        (rda_fleet_upload_scans_tracked, see `control`)."""
+        (rda_fleet_upload_scans_tracked, see `control`).  split = tol > 0: the boxes of `lidar.scan_box_split`."""
         if not getattr(self.api, "has_fleet_scans", False):
             raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_upload_scans)")
+        self.set_scan_split(split)
         if track is not None:
             self._check_track(*track)
         n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
@@ -500,6 +525,8 @@ class Fleet:
         on the device behind the scan (one launch more per tick, no wait more) and staged with their tracks' velocities, so what the lidar sees is
         predicted over the horizon - a crossing obstacle, and with `see_peers=True` another member, is anticipated instead of met as a standing
         box.  The tracks continue those the fleet holds (`reset_tracks`, `reset`).  Without `lidar=` it is a ValueError.
+        `scan_split=tol` (with `lidar=`; rda_fleet_set_scan_split): every tick's clusters are cut into their straight runs, one box per run, as in
+        `control(scans=, scan_split=)`; combines with `track`, `see_peers` and `moving`.  Without `lidar=` it is a ValueError; omitted: off.
         `peers=True` (rda_fleet_rollout_peers): the members avoid each other as in `control(peers=True)`.  Before every tick the device rewrites the
         peer obstacles of every member's scene from the states of that tick and the controls applied on the tick before (tick 0: every member's
         `cur_vel_array[:, 0]`), re-sorts, and runs the tick of `moving=True` on the member's own obstacles.  `obstacle_lists=` is required on the first
@@ -518,6 +545,9 @@ class Fleet:
         device gave it (Q12), so `control` continues on the right piece.  Without `gears=True` such members are refused."""
         ms = self.members
         kwargs = dict(kwargs)
+        split = scan_split_arg(kwargs, "Fleet.rollout", kwargs.get("lidar") is not None, "lidar=")
+        if split:
+            self._check_split()
         gears = bool(kwargs.pop("gears", False))
         peers, plan = peers_mode(kwargs.pop("peers", False))
         see_peers = bool(kwargs.pop("see_peers", False))
@@ -607,6 +637,7 @@ class Fleet:
         elif sensors is not None:
             order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
             b_log = np.zeros((max(K, 0), B), np.int32)
+            self.set_scan_split(split)
             args = (*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples, iptr(order), 1 if moving else 0,
                     *logs, iptr(b_log), dptr(c_log))
             if track:

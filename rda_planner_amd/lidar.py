@@ -142,6 +142,106 @@ def scan_box_device_fleet(fleet, states, scans, eps=2.0, min_samples=6):
             for boxes in fleet.scan_boxes(states, scans, eps, min_samples)]
 
 
+def _split_tol(tol):
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("scan split: tol must be finite and greater than 0")
+    return tol
+
+
+def end_point_fit(x, y, a, b, tol2):
+    """(s, thr) of the run [a, b] (b - a >= 2) of the points x, y: s[i - a - 1] for a < i < b and the bound max s is compared with (`split_runs`)"""
+    ex, ey = x[b] - x[a], y[b] - y[a]
+    L2 = ex * ex + ey * ey
+    rx, ry = x[a + 1:b] - x[a], y[a + 1:b] - y[a]
+    if L2 > 0:
+        cr = rx * ey - ry * ex
+        return cr * cr, tol2 * L2
+    return rx * rx + ry * ry, tol2
+
+
+def split_runs(points, labels, eps, tol):
+    """Segment number of every hit, (n,): the clusters of `labels` (`dbscan`'s) cut into their straight runs by the end-point fit - the specification
+    of the split stage of lidar::scan_body (csrc/lidar_device.h), which takes every decision on the same numbers.  `points`: the hits in beam order
+    (`scan_points`).  Noise keeps -1.  For every cluster in ascending number, its points in beam order q_0 .. q_{k-1}; every product and sum rounded
+    separately, in the order written:
+      gap rule       a run ends between q_i and q_{i+1} when dx * dx + dy * dy <= eps * eps is false (`dbscan`'s `near`)
+      end-point fit  of a run [a, b] with b - a >= 2: e = q_b - q_a, L2 = ex * ex + ey * ey; for a < i < b r = q_i - q_a and
+                     L2 > 0:  cr = rx * ey - ry * ex, s_i = cr * cr, the run splits iff max s_i > (tol * tol) * L2
+                     L2 == 0 (a closed loop): s_i = rx * rx + ry * ry, the run splits iff max s_i > tol * tol
+                     (no square root, no division).  The split point m is the lowest index at the maximum; the run becomes [a, m - 1] and [m, b]: the
+                     corner starts the second run, no point belongs to two.  Runs of one or two points are final.
+      numbering      the fixed point of this rule, segments numbered by cluster number, then by the position of the run's first point.
+    Known and accepted: a cluster that crosses the first / last-beam seam is cut there by the gap rule unless every beam hits (two boxes for one wall);
+    two surfaces that interleave in beam order inside one cluster break into many short runs; a convex body seen corner-on becomes two thin boxes."""
+    P = np.asarray(points, float).reshape(-1, 2)
+    labels = np.asarray(labels)
+    eps, tol = float(eps), _split_tol(tol)
+    eps2, tol2 = eps * eps, tol * tol
+    seg = np.full(len(P), -1, dtype=np.int64)
+    nseg = 0
+    for c in np.unique(labels):
+        if c < 0:
+            continue
+        idx = np.flatnonzero(labels == c)
+        x, y = P[idx, 0], P[idx, 1]
+        dx, dy = x[:-1] - x[1:], y[:-1] - y[1:]
+        gap = ~(dx * dx + dy * dy <= eps2)
+        heads = np.concatenate(([0], np.flatnonzero(gap) + 1, [len(idx)]))
+        todo = [(int(heads[k]), int(heads[k + 1]) - 1) for k in range(len(heads) - 1)]
+        starts = []
+        while todo:
+            a, b = todo.pop()
+            m = -1
+            if b - a >= 2:
+                s, thr = end_point_fit(x, y, a, b, tol2)
+                if s.max() > thr:
+                    m = a + 1 + int(np.argmax(s))                          # (argmax: the first, so the lowest, index at the maximum)
+            if m < 0:
+                starts.append(a)
+            else:
+                todo += [(a, m - 1), (m, b)]
+        starts = np.sort(np.array(starts, dtype=np.int64))
+        of = np.zeros(len(idx), dtype=np.int64)
+        of[starts] = 1
+        seg[idx] = nseg + np.cumsum(of) - 1
+        nseg += len(starts)
+    return seg
+
+
+def scan_box_split(state, scan_data, eps=2.0, min_samples=6, tol=0.15):
+    """`scan_box` with one `min_area_rect` per segment of `split_runs`, in segment order: a concave cluster (an L-shaped wall, the two sides of a
+    corridor, the inside of a room) becomes one thin box per straight run instead of one box over the free space between them.  No boxes for fewer than
+    4 hits, as before; `tol` [m] finite and > 0, else a ValueError.  See `split_runs` for the rule and its accepted limits."""
+    tol = _split_tol(tol)
+    pts = scan_points(scan_data)
+    if len(pts) < 4:
+        return []
+    seg = split_runs(pts, dbscan(pts, eps, min_samples), eps, tol)
+    state = np.asarray(state, float)
+    rot = state[2, 0]
+    R = np.array([[np.cos(rot), -np.sin(rot)], [np.sin(rot), np.cos(rot)]])
+    out = []
+    for s in range(int(seg.max()) + 1 if len(seg) else 0):
+        box = min_area_rect(pts[seg == s])
+        out.append(Obstacle(None, None, state[0:2] + R @ box.T, "Rpositive", np.zeros((2, 1))))
+    return out
+
+
+def scan_box_split_device(solver, state, scan_data, eps=2.0, min_samples=6, tol=0.15):
+    """`scan_box_split` computed on the device by `solver` (an `RDA_solver`, or anything that has one as `.rda`): the same obstacles, corners within
+    rounding of the host function's"""
+    solver = getattr(solver, "rda", solver)
+    boxes = solver.scan_boxes(state, scan_data, eps, min_samples, split=_split_tol(tol))
+    return [Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]
+
+
+def scan_box_split_device_fleet(fleet, states, scans, eps=2.0, min_samples=6, tol=0.15):
+    """`scan_box_split_device` for every member of a `Fleet` in one kernel launch: the list of the members' obstacle lists"""
+    return [[Obstacle(None, None, np.ascontiguousarray(b.T), "Rpositive", np.zeros((2, 1))) for b in boxes]
+            for boxes in fleet.scan_boxes(states, scans, eps, min_samples, split=_split_tol(tol))]
+
+
 def box_centres(boxes):
     """(n, 2) centres of (n, 4, 2) boxes, the corners added in the order the scan kernel writes them: (((x0 + x1) + x2) + x3) * 0.25"""
     B = np.asarray(boxes, float).reshape(-1, 4, 2)

@@ -18,6 +18,20 @@ from .rda_solver import RDA_solver
 rdaobs = namedtuple("rdaobs", "A b cone_type center vertex")          # reference mpc.py:12
 
 
+def scan_split_arg(kwargs, who, has_scan, needs):
+    """`scan_split` popped from a call's keyword arguments: 0.0 when it is absent (splitting off), else the tolerance [m] - finite and > 0, and
+    only together with a scan (`needs` names the argument), anything else a ValueError"""
+    tol = kwargs.pop("scan_split", None)
+    if tol is None:
+        return 0.0
+    if not has_scan:
+        raise ValueError(f"{who}: scan_split splits the clusters of {needs}")
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"{who}: scan_split must be finite and greater than 0")
+    return tol
+
+
 class MPC:
     def __init__(self, car_tuple, ref_path, receding: int = 10, sample_time: float = 0.1, iter_num: int = 4,
                  enable_reverse: bool = False, rda_obstacle: bool = False, obstacle_order: bool = True,
@@ -48,8 +62,9 @@ class MPC:
 
     # ------------------------------------------------------------------ control (mpc.py:127-187)
     def control(self, state, ref_speed=5, obstacle_list=[], scan=None, scan_eps=2.0, scan_min_samples=6, **kwargs):
+        split = scan_split_arg(kwargs, "MPC.control", scan is not None, "scan=")
         if scan is not None:                             # extension: the lidar scan itself instead of an obstacle list (see _control_scan)
-            return self._control_scan(state, ref_speed, obstacle_list, scan, scan_eps, scan_min_samples, **kwargs)
+            return self._control_scan(state, ref_speed, obstacle_list, scan, scan_eps, scan_min_samples, split, **kwargs)
         if self._tracks(kwargs):
             return self._control_tracked(state, ref_speed, obstacle_list, **kwargs)
         cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
@@ -149,32 +164,35 @@ class MPC:
         return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
 
     # ---- extension: the lidar front end on the device (rda_upload_scan) ---------------------------------------------------
-    def _control_scan(self, state, ref_speed, obstacle_list, scan, eps, min_samples, **kwargs):
+    def _control_scan(self, state, ref_speed, obstacle_list, scan, eps, min_samples, split=0.0, **kwargs):
         """`control` fed with a range scan (the dict of ir-sim's `get_lidar_scan`) taken from `state`: what `lidar.scan_box` makes of
         it - DBSCAN clusters, one minimum-area box each - is computed AND staged on the device; no geometry crosses the host.
-        Same tick otherwise: the tracked path keeps its two halves (the scan is staged beside the first su-problem)."""
+        Same tick otherwise: the tracked path keeps its two halves (the scan is staged beside the first su-problem).
+        split (`control(scan_split=tol)`): what `lidar.scan_box_split` makes of it - one box per straight run of a cluster (rda_set_scan_split);
+        0: off, and a handle that was split on the previous call is unsplit on this one."""
         if len(obstacle_list):
             raise ValueError("MPC.control: pass either an obstacle_list or scan=, not both")
         if self.rda_obstacle or not self.rda.has_scan:
             raise RuntimeError("MPC.control(scan=...) needs the device-side lidar front end (rda_upload_scan); there is no host fallback")
+        sk = {"split": split} if split else {}                # (an unsplit call is the call it always was)
         if self._tracks(kwargs):
             cur_ref_path, gear_flag = self._piece(state)
             self._sync_path(cur_ref_path)
             if self.rda.has_pipeline:
                 self.rda.tracked_begin(self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
                 try:
-                    self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+                    self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
                 except BaseException:
                     self.rda.tracked_finish(discard=True)           # close the tick before reporting the error
                     raise
                 u_opt_array, info, min_index, end_heading = self.rda.tracked_finish()
             else:
-                self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+                self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
                 u_opt_array, info, min_index, end_heading = self.rda.iterative_solve_tracked(
                     self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
             return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
         cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
-        self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order)
+        self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
         u_opt_array, info = self.rda.iterative_solve_staged(state_pre_array, self.cur_vel_array, ref_traj_list, speed)
         return self._end(cur_ref_path, u_opt_array, info)
 

@@ -483,9 +483,24 @@ class RDA_solver:
                 float(scan_data["range_max"]), dptr(st), float(eps), int(min_samples))
         return head, (ranges, st)                        # (the arrays stay referenced until the call has returned)
 
-    def scan_boxes(self, state, scan_data, eps=2.0, min_samples=6, with_labels=False):
+    def set_scan_split(self, tol):
+        """the split tolerance [m] of this handle's scans (rda_set_scan_split; `lidar.split_runs` is the specification): 0 switches the stage off.
+        The library is called only when the value changes; one without the entry point is a RuntimeError as soon as a split is asked for."""
+        tol = float(tol)
+        if tol == getattr(self, "_scan_split", 0.0):
+            return
+        if not getattr(self._be.api, "has_scan_split", False):
+            raise RuntimeError("the loaded solver library cannot split scan clusters (rda_set_scan_split, rda_fleet_set_scan_split)")
+        rc = self._be.api.set_scan_split(self._be.handle, tol)
+        if rc < 0:
+            raise ValueError("scan split: tol must be finite and greater than 0") if rc == -1 else self._be.api.failed("set_scan_split", rc)
+        self._scan_split = tol
+
+    def scan_boxes(self, state, scan_data, eps=2.0, min_samples=6, with_labels=False, split=0.0):
         """`lidar.scan_box` on the device: the (n, 4, 2) corners (world frame, counter-clockwise) of one minimum-area rectangle per
-        DBSCAN cluster of the scan taken from `state`; with_labels: also the per-beam labels (-2 miss, -1 noise, >= 0 cluster)"""
+        DBSCAN cluster of the scan taken from `state`; with_labels: also the per-beam labels (-2 miss, -1 noise, >= 0 cluster).
+        split = tol > 0: `lidar.scan_box_split` - one rectangle per straight run, the labels are segment numbers"""
+        self.set_scan_split(split)
         head, keep = self._scan_args(state, scan_data, eps, min_samples)
         cap = max(1, keep[0].size)
         boxes, n, labels = np.zeros((cap, 4, 2)), np.zeros(1, np.int32), np.zeros(cap, np.int32)
@@ -494,9 +509,10 @@ class RDA_solver:
             raise self._be.api.failed("scan_boxes", rc)
         return (boxes[:n[0]], labels[:keep[0].size]) if with_labels else boxes[:n[0]]
 
-    def upload_scan(self, state, scan_data, eps=2.0, min_samples=6, order=True):
+    def upload_scan(self, state, scan_data, eps=2.0, min_samples=6, order=True, split=0.0):
         """the boxes of `scan_boxes` staged as this solver's obstacles without leaving the device (`upload_scene` of them, robot at
         state[0:2]); usable inside an open tick like `upload_scene_async`.  Returns the number of boxes."""
+        self.set_scan_split(split)
         head, keep = self._scan_args(state, scan_data, eps, min_samples)
         n = np.zeros(1, np.int32)
         rc = self._be.api.upload_scan(*head, int(bool(order)), iptr(n))

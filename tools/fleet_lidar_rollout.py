@@ -21,7 +21,7 @@ world per member, as in (b)), the repeats interleaved:
       tracked tick has one launch more (lidar::k_track_boxes_fleet, behind the scan kernel) and builds and solves slots for T + 1 stages instead of one.
       The tracker's own time per launch comes from a run under `rocprofv3 --kernel-trace --stats` (--track --profile-run: one short tracked rollout).
 
-    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3] [--see-peers | --track [--profile-run]]
+    python tools/fleet_lidar_rollout.py [--fleets 16,64] [--beams 360,1080] [--obstacles 50,200] [--K 100] [--repeats 3] [--see-peers | --track [--profile-run] | --split TOL [--corridor] [--profile-run]]
 """
 import argparse
 import os
@@ -188,6 +188,57 @@ def track_table(args):
                      tracks, 100 * fast))
 
 
+def corridor_fleet(B, beams):
+    """every member in the L-shaped corridor of tests/golden/world_lidar_corridor.yaml, 5 m before the bend, on a path round it"""
+    import yaml
+    from rda_planner_amd import scenarios as sc
+    from rda_planner_amd import world as irsim
+    from rda_planner_amd.fleet import Fleet
+    from rda_planner_amd.mpc import MPC
+    with open(os.path.join(ROOT, "tests", "golden", "world_lidar_corridor.yaml")) as fh:
+        cfg = yaml.safe_load(fh)
+    cfg["robot"][0]["sensors"][0]["number"] = beams
+    cfg["robot"][0]["state"] = [25.0, 0.0, 0.0]
+    envs = [irsim.World(cfg) for _ in range(B)]
+    car = sc.rectangle_robot(1.0, 0.6, 0, "diff", max_speed=(2, 1), max_acce=(2, 1))
+    path = sc.line_path([25, 0, 0], [30, 0, 0]) + sc.line_path([30, 0, np.pi / 2], [30, 20, np.pi / 2])[1:]
+    ms = [MPC(car, [p.copy() for p in path], receding=T, max_edge_num=4, max_obs_num=N, iter_num=2) for _ in range(B)]
+    return Fleet(ms), envs
+
+
+def split_table(args):
+    """(f) the rollout with the clusters split into straight runs (scan_split=TOL) against the one box per cluster, interleaved"""
+    n_obs, K, tol = args.obstacles[0], args.K, args.split
+    speed = 2.0 if args.corridor else 4.0
+    if args.profile_run:                                                         # for the profiler: one fleet, one rollout, no timing
+        B, beams = args.fleets[-1], args.beams[-1]
+        f, envs = corridor_fleet(B, beams) if args.corridor else fleet(B, beams, n_obs)
+        kw = dict(scan_split=tol) if tol > 0 else {}
+        out = f.rollout([e.robot.state.copy() for e in envs], speed, K, lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs], **kw)
+        print("rollout of K = %d ticks, B = %d, %d beams, split %g: boxes per tick and member %.1f" % (K, B, beams, tol, out["boxes"].mean()))
+        f.close()
+        return
+    print("(f) closed loop of K = %d ticks, %s, ego-steps/s (medians of %d, interleaved): Fleet.rollout(lidar=, world=) | ... scan_split=%g"
+          % (K, "the L-shaped corridor" if args.corridor else "%d world obstacles per member" % n_obs, args.repeats, tol))
+    print("%4s %6s | %12s | %12s | %s" % ("B", "beams", "unsplit", "split", "split / unsplit"))
+    for B in args.fleets:
+        for beams in args.beams:
+            rate, boxes = {False: [], True: []}, {}
+            for _ in range(args.repeats):
+                for on in (False, True):
+                    f, envs = corridor_fleet(B, beams) if args.corridor else fleet(B, beams, n_obs)
+                    kw = dict(lidar=[e.lidar for e in envs], world=[e.obstacles for e in envs], **(dict(scan_split=tol) if on else {}))
+                    out = f.rollout([e.robot.state.copy() for e in envs], speed, 2, **kw)  # first use: tables, logs and the members' raw scenes
+                    kw.pop("world")
+                    t0 = time.perf_counter()
+                    out = f.rollout([out["states"][-1, i].reshape(3, 1) for i in range(B)], speed, K, **kw)
+                    rate[on].append(B * K / (time.perf_counter() - t0))
+                    boxes[on] = out["boxes"].mean()
+                    f.close()
+            print("%4d %6d | %12.0f | %12.0f | %.2fx   (boxes per tick and member: %.1f | %.1f)"
+                  % (B, beams, np.median(rate[False]), np.median(rate[True]), np.median(rate[True]) / np.median(rate[False]), boxes[False], boxes[True]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ints = lambda s: [int(x) for x in s.split(",")]             # noqa: E731
@@ -198,8 +249,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--see-peers", action="store_true", help="the members that see each other against the blind ones (tables c, d)")
     ap.add_argument("--track", action="store_true", help="the rollout that tracks its boxes against the one that does not (table e)")
-    ap.add_argument("--profile-run", action="store_true", help="with --track: one short tracked rollout and nothing else, for a profiler")
+    ap.add_argument("--profile-run", action="store_true", help="with --track / --split: one short rollout of that kind and nothing else, for a profiler")
+    ap.add_argument("--split", type=float, default=None, metavar="TOL",
+                    help="the rollout that splits its clusters into straight runs at TOL metres against the one that does not (table f); with --profile-run, 0 = unsplit")
+    ap.add_argument("--corridor", action="store_true", help="with --split: every member in the L-shaped corridor instead of the obstacle field")
     args = ap.parse_args()
+    if args.split is not None:
+        split_table(args)
+        return
     if args.see_peers:
         peers_tables(args)
         return

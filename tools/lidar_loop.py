@@ -129,11 +129,12 @@ def closed_loop(mode, beams, steps):
         scan = env.get_lidar_scan()
         t1 = time.perf_counter()
         if mode == "host":
-            u, info = mpc.control(env.robot.state, 4, lidar.scan_box(env.robot.state, scan))
+            u, info = mpc.control(env.robot.state, 4, lidar.scan_box_split(env.robot.state, scan, tol=SPLIT) if SPLIT else lidar.scan_box(env.robot.state, scan))
         elif mode == "scan_box_device":
-            u, info = mpc.control(env.robot.state, 4, lidar.scan_box_device(mpc, env.robot.state, scan))
+            u, info = mpc.control(env.robot.state, 4, lidar.scan_box_split_device(mpc, env.robot.state, scan, tol=SPLIT) if SPLIT
+                                  else lidar.scan_box_device(mpc, env.robot.state, scan))
         else:
-            u, info = mpc.control(env.robot.state, 4, scan=scan)
+            u, info = mpc.control(env.robot.state, 4, scan=scan, **({"scan_split": SPLIT} if SPLIT else {}))
         t_plan += time.perf_counter() - t1
         env.step(u)
         done += 1
@@ -227,7 +228,7 @@ def fleet_part(args):
                 states = [e.robot.state.copy() for e in envs]
                 scans = [e.get_lidar_scan() for e in envs]
                 t0 = time.perf_counter()
-                res = fleet.control(states, 4.0, scans=scans)
+                res = fleet.control(states, 4.0, scans=scans, **({"scan_split": SPLIT} if SPLIT else {}))
                 if t >= 5:                                          # (warm-up: first launches, allocations)
                     per.append(time.perf_counter() - t0)
                 for e, (u, _) in zip(envs, res):
@@ -235,6 +236,9 @@ def fleet_part(args):
             ms = 1e3 * float(np.median(per))
             print("%4d %6d %6d %14.0f %22.3f" % (B, beams, len(per), B / (1e-3 * ms), ms))
             fleet.close()
+
+
+SPLIT = 0.0             # --split
 
 
 def main():
@@ -250,7 +254,11 @@ def main():
     ap.add_argument("--fleet-beams", type=ints, default=[360, 1080])
     ap.add_argument("--fleet-ticks", type=int, default=30)
     ap.add_argument("--fleet-steps", type=int, default=40)
+    ap.add_argument("--split", type=float, default=0.0, metavar="TOL",
+                    help="the closed loops (part 2, and the Fleet.control loop of --fleet) with the clusters split into straight runs at TOL metres")
     args = ap.parse_args()
+    global SPLIT
+    SPLIT = args.split
     if args.fleet:
         assert args.fleet_ticks >= 8 and args.repeats >= 3
         return fleet_part(args)
