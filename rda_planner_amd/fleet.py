@@ -10,6 +10,7 @@ what `member.control(...)` would have returned.
 """
 import ctypes as C
 import time
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -19,6 +20,52 @@ from .mpc import scan_split_arg
 
 SENSOR_FIELDS = ("number", "angle_min", "angle_max", "range_min", "range_max")
 WORLD_EMAX = 8              # RDA_EMAX of include/rda_hip.h: the most vertices a world polygon may have
+
+# the arguments of the eight rollout entries in the order of include/rda_hip.h, by name: `rollout_args` resolves a row against the values of a call.
+# `logs` (s_log u_log i_log infos arrived), `sensors` (n_beams angle_min angle_max range_min range_max) and `plans` (plans valid) stand for several.
+_HEAD = "F K states speed cur threshold ind_range margin"
+_LIDAR = _HEAD + " nom_u sensors scan_eps scan_min_samples order moving logs box_log clearance_log"
+ROLLOUT_ARGS = {
+    "fleet_rollout":               _HEAD + " resort nom_u logs",
+    "fleet_rollout_moving":        _HEAD + " resort nom_u logs clearance_log",
+    "fleet_rollout_gears":         "F K states speed piece0 cur threshold ind_range margin resort moving nom_u logs piece_log clearance_log",
+    "fleet_rollout_peers":         _HEAD + " nom_u ctl0 logs clearance_log peer_log",
+    "fleet_rollout_peers_plan":    _HEAD + " nom_u ctl0 logs clearance_log peer_log plans",
+    "fleet_rollout_lidar":         _LIDAR,
+    "fleet_rollout_lidar_peers":   _LIDAR + " peer_log",
+    "fleet_rollout_lidar_tracked": _LIDAR + " peer_log see_peers track_gate track_window",
+}
+
+
+def c_arg(v):
+    """a value as the C argument it is passed as: a float64 / int32 array as its pointer, a flag as 0 / 1, anything else (None, int, float, the
+    handle, the `Info` array) as it is"""
+    if isinstance(v, np.ndarray):
+        return {"float64": dptr, "int32": iptr}[v.dtype.name](v)       # an array of any other type is no argument of the library: KeyError
+    return int(v) if isinstance(v, (bool, np.bool_)) else v
+
+
+def rollout_args(entry, values):
+    """the positional arguments of the rollout entry `entry`: its row of ROLLOUT_ARGS resolved against `values` (name -> value, a tuple for a group)"""
+    named = (values[name] for name in ROLLOUT_ARGS[entry].split())
+    return [c_arg(v) for one in named for v in (one if isinstance(one, tuple) else (one,))]
+
+
+# what one `Fleet.rollout` call asks for, as `Fleet._rollout_options` returns it: once it exists, every refusal that needs no library call has happened.
+# sensors: the arrays of `sensor_arrays`, None without lidar=; margin: the members' common goal_index_threshold; entry: a key of ROLLOUT_ARGS
+RolloutOptions = namedtuple("RolloutOptions", "resort gears peers plan see_peers track track_gate track_window split moving clearance sensors scan_eps "
+                            "scan_min_samples obstacle_lists world threshold ind_range margin entry")
+
+
+def rollout_entry(o):
+    """the C entry point that runs the rollout of the options `o`"""
+    if o.gears:
+        return "fleet_rollout_gears"
+    if o.peers:
+        return "fleet_rollout_peers_plan" if o.plan else "fleet_rollout_peers"
+    if o.sensors is not None:
+        return "fleet_rollout_lidar_tracked" if o.track else "fleet_rollout_lidar_peers" if o.see_peers else "fleet_rollout_lidar"
+    return "fleet_rollout_moving" if o.moving else "fleet_rollout"
 
 
 def sensor_arrays(sensors, B):
@@ -44,9 +91,7 @@ def sensor_arrays(sensors, B):
 
 def peers_mode(peers):
     """the `peers=` argument of `Fleet.control` / `Fleet.rollout` -> (peers on, predicted along their plans)"""
-    if isinstance(peers, str):
-        if peers != "plan":
-            raise ValueError(f'peers={peers!r}: False, True (constant velocity) or "plan" (along the planned trajectories)')
+    if isinstance(peers, str) and peers == "plan":
         return True, True
     if peers is None or isinstance(peers, (bool, int, np.bool_, np.integer)):
         return bool(peers), False
@@ -67,7 +112,7 @@ class Fleet:
         if not self.members:
             raise ValueError("a fleet needs at least one member")
         self.api = self.members[0].rda._be.api
-        if not getattr(self.api, "has_fleet", False):
+        if not self._has("has_fleet"):
             raise RuntimeError("the loaded solver library has no fleet entry points")
         B = len(self.members)
         arr = (C.c_void_p * B)(*[m.rda._be.handle for m in self.members])
@@ -87,6 +132,16 @@ class Fleet:
 
     def __len__(self):
         return len(self.members)
+
+    def _call(self, name, *args):
+        """the library's `name(*args)`; a negative return code raises what the binding makes of it"""
+        rc = getattr(self.api, name)(*args)
+        if rc < 0:
+            raise self.api.failed(name, rc)
+        return rc
+
+    def _has(self, flag):
+        return getattr(self.api, flag, False)
 
     def _plan_state(self):
         """every member's last planned states (B, 3, T+1) - the `opt_state_list` of its last tick through this fleet - and whether they count
@@ -114,7 +169,7 @@ class Fleet:
         for i in which:
             self.members[i].reset()
             valid[i] = 0
-        if getattr(self.api, "has_fleet_lidar_tracked", False):
+        if self._has("has_fleet_lidar_tracked"):
             self.reset_tracks(which)
 
     def lammuz_kernel(self):
@@ -185,7 +240,7 @@ class Fleet:
                 raise ValueError("Fleet.control: pass either obstacle_lists or scans=, not both")
             if len(scans) != B:
                 raise ValueError("Fleet.control: one scan per member")
-            if not getattr(self.api, "has_fleet_scans", False) or any(m.rda_obstacle for m in self.members):
+            if not self._has("has_fleet_scans") or any(m.rda_obstacle for m in self.members):
                 raise RuntimeError("Fleet.control(scans=...) needs the fleet lidar front end (rda_fleet_upload_scans); there is no host fallback")
             stage = lambda st: self.upload_scans(st, scans, scan_eps, scan_min_samples,       # noqa: E731
                                                  track=(float(track_gate), int(track_window)) if track else None, split=split)
@@ -219,10 +274,8 @@ class Fleet:
                 m.rda.upload_obstacles(rda_obs)
         if stage is not None:
             stage(states_array([m.state for m in self.members], len(self.members)))
-        rc = self.api.fleet_step(self._handle, dptr(self._in_s), dptr(self._in_u), dptr(self._ref), dptr(self._speed),
-                                 dptr(self._out_u), dptr(self._out_s), self._info)
-        if rc < 0:
-            raise self.api.failed("fleet_step", rc)
+        self._call("fleet_step", self._handle, dptr(self._in_s), dptr(self._in_u), dptr(self._ref), dptr(self._speed),
+                   dptr(self._out_u), dptr(self._out_s), self._info)
         out = []
         for i, m in enumerate(self.members):
             cur_ref_path, ref_list = begun[i]
@@ -238,32 +291,34 @@ class Fleet:
         (rda_fleet_upload_scenes, no waiting); False when some member needs the per-member route (host conversion, cone
         types the reference skips, too many vertices)"""
         ms = self.members
-        if not getattr(self.api, "has_fleet_scenes", False):
+        if not self._has("has_fleet_scenes") or any(m.rda_obstacle or not m.device_obstacles or not m.rda.has_scene for m in ms):
             return False
-        if any(m.rda_obstacle or not m.device_obstacles or not m.rda.has_scene for m in ms):
+        flat = self._flatten(obstacle_lists)
+        if flat is None:
             return False
-        counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(ms))
-        every = [o for ol in obstacle_lists for o in ol]
-        scene = ms[0].rda.flatten_scene(every)
-        if scene is None or scene[0] != len(every):
-            return False
-        _, kind, nvert, geom, vel = scene
-        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
-        geom = f64(geom); vel = f64(vel)
         rob = np.ascontiguousarray(st[:, 0:2])
         order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, len(ms))
-        rc = self.api.fleet_upload_scenes(self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob), iptr(order))
-        if rc < 0:
-            raise self.api.failed("fleet_upload_scenes", rc)
+        self._call("fleet_upload_scenes", self._handle, *map(c_arg, flat), dptr(rob), iptr(order))
         self.batched_ticks += 1
         return True
+
+    def _flatten(self, obstacle_lists):
+        """all members' obstacle lists flattened in ONE pass over the obstacle objects: the arrays (counts, kind, nvert, geom, vel) of
+        rda_fleet_upload_scenes and its peers forms, or None when an obstacle cannot be staged through the device pipeline"""
+        every = [o for ol in obstacle_lists for o in ol]
+        scene = self.members[0].rda.flatten_scene(every)
+        if scene is None or scene[0] != len(every):
+            return None
+        _, kind, nvert, geom, vel = scene
+        counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(self.members))
+        return counts, np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32), f64(geom), f64(vel)
 
     def _check_peers(self, kwargs, plan=False):
         """what peers=True / peers="plan" needs of the library and of every member, checked before any library call"""
         ms = self.members
-        if not getattr(self.api, "has_fleet_peers", False):
+        if not self._has("has_fleet_peers"):
             raise RuntimeError("the loaded solver library has no peer entry points (rda_fleet_upload_scenes_peers, rda_fleet_rollout_peers)")
-        if plan and not getattr(self.api, "has_fleet_peers_plan", False):
+        if plan and not self._has("has_fleet_peers_plan"):
             raise RuntimeError('peers="plan": the loaded solver library has no plan entry points (rda_fleet_upload_scenes_peers_plan, rda_fleet_rollout_peers_plan)')
         if any(not m.obstacle_order for m in ms):
             raise RuntimeError("peers=True ranks every member's obstacles and peers by distance: obstacle_order=False is not supported")
@@ -277,39 +332,26 @@ class Fleet:
     def _stage_peers(self, obstacle_lists, st, controls, plan=False):
         """`_stage_all` with the other members behind every member's own obstacles (rda_fleet_upload_scenes_peers; plan: _peers_plan with the members'
         last plans and their validity); st (B, 3), controls (B, 2)"""
-        ms = self.members
-        counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(ms))
-        every = [o for ol in obstacle_lists for o in ol]
-        scene = ms[0].rda.flatten_scene(every)
-        if scene is None or scene[0] != len(every):
+        flat = self._flatten(obstacle_lists)
+        if flat is None:
             raise RuntimeError("peers=True: an obstacle cannot be staged through the device pipeline; there is no host fallback")
-        _, kind, nvert, geom, vel = scene
-        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
-        geom = f64(geom); vel = f64(vel)
-        head = (self._handle, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(f64(st)), dptr(f64(controls)))
+        head = (self._handle, *map(c_arg, flat), dptr(f64(st)), dptr(f64(controls)))
         if plan:
-            plans, valid = self._plan_state()
-            rc, name = self.api.fleet_upload_scenes_peers_plan(*head, dptr(plans), iptr(valid)), "fleet_upload_scenes_peers_plan"
+            self._call("fleet_upload_scenes_peers_plan", *head, *map(c_arg, self._plan_state()))
         else:
-            rc, name = self.api.fleet_upload_scenes_peers(*head), "fleet_upload_scenes_peers"
-        if rc < 0:
-            raise self.api.failed(name, rc)
+            self._call("fleet_upload_scenes_peers", *head)
         self._peers_staged = True
         self.batched_ticks += 1
 
     def peer_clearance(self, states):
         """(B,) every member's separation from the nearest other member at `states` (rda_fleet_peer_clearance: `scenarios.peer_clearance`
         evaluated on the device, one launch; negative = overlap, +inf for a fleet of one)"""
-        if not getattr(self.api, "has_fleet_peers", False):
+        if not self._has("has_fleet_peers"):
             raise RuntimeError("the loaded solver library has no peer entry points (rda_fleet_peer_clearance)")
         if any(m.car_tuple.cone_type == "norm2" for m in self.members):
             raise RuntimeError("Fleet.peer_clearance is for polygon robots; a circle (norm2) robot is not supported")
-        B = len(self.members)
-        st = states_array(states, B)
-        out = np.zeros(B)
-        rc = self.api.fleet_peer_clearance(self._handle, dptr(st), dptr(out))
-        if rc < 0:
-            raise self.api.failed("fleet_peer_clearance", rc)
+        st, out = states_array(states, len(self.members)), np.zeros(len(self.members))
+        self._call("fleet_peer_clearance", self._handle, dptr(st), dptr(out))
         return out
 
     def _scan_arrays(self, states, scans):
@@ -324,7 +366,7 @@ class Fleet:
         return n_beams, allr, lo, hi, rmax, states_array(states, B)
 
     def _check_split(self):
-        if not getattr(self.api, "has_scan_split", False):
+        if not self._has("has_scan_split"):
             raise RuntimeError("the loaded solver library cannot split scan clusters (rda_set_scan_split, rda_fleet_set_scan_split)")
 
     def set_scan_split(self, tol):
@@ -341,23 +383,21 @@ class Fleet:
 
     def scan_boxes(self, states, scans, eps=2.0, min_samples=6, split=0.0):
         """`RDA_solver.scan_boxes` for every member in one kernel launch: the list of (n_i, 4, 2) corner arrays (split = tol > 0: one per straight run)"""
-        if not getattr(self.api, "has_fleet_scans", False):
+        if not self._has("has_fleet_scans"):
             raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_scan_boxes)")
         self.set_scan_split(split)
         n_beams, allr, lo, hi, rmax, st = self._scan_arrays(states, scans)
         B, cap = len(self.members), max(1, int(n_beams.max()))
         boxes, n = np.zeros((B, cap, 4, 2)), np.zeros(B, np.int32)
-        rc = self.api.fleet_scan_boxes(self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
-                                       iptr(n), dptr(boxes), cap, None)
-        if rc < 0:
-            raise self.api.failed("fleet_scan_boxes", rc)
+        self._call("fleet_scan_boxes", self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples),
+                   iptr(n), dptr(boxes), cap, None)
         return [boxes[i, :n[i]].copy() for i in range(B)]
 
     def upload_scans(self, states, scans, eps=2.0, min_samples=6, track=None, split=0.0):
         """`RDA_solver.upload_scan` for every member (its own `obstacle_order`) in one library call; returns the box counts.
         Until `sync` or the next `control` the members are not used on their own.  track=(gate, window): the tracked form
         (rda_fleet_upload_scans_tracked, see `control`).  split = tol > 0: the boxes of `lidar.scan_box_split`."""
-        if not getattr(self.api, "has_fleet_scans", False):
+        if not self._has("has_fleet_scans"):
             raise RuntimeError("the loaded solver library has no fleet lidar entry points (rda_fleet_upload_scans)")
         self.set_scan_split(split)
         if track is not None:
@@ -368,16 +408,14 @@ class Fleet:
         n = np.zeros(B, np.int32)
         args = (self._handle, iptr(n_beams), dptr(allr), dptr(lo), dptr(hi), dptr(rmax), dptr(st), float(eps), int(min_samples), iptr(order), iptr(n))
         if track is not None:
-            rc, name = self.api.fleet_upload_scans_tracked(*args, float(track[0]), int(track[1])), "fleet_upload_scans_tracked"
+            self._call("fleet_upload_scans_tracked", *args, float(track[0]), int(track[1]))
         else:
-            rc, name = self.api.fleet_upload_scans(*args), "fleet_upload_scans"
-        if rc < 0:
-            raise self.api.failed(name, rc)
+            self._call("fleet_upload_scans", *args)
         return n
 
     def _check_track(self, gate, window):
         """what track=True needs of the library and of its two parameters, checked before any library call"""
-        if not getattr(self.api, "has_fleet_lidar_tracked", False):
+        if not self._has("has_fleet_lidar_tracked"):
             raise RuntimeError("the loaded solver library has no box tracker (rda_fleet_upload_scans_tracked, rda_fleet_rollout_lidar_tracked, "
                                "rda_fleet_track_boxes, rda_fleet_box_tracks, rda_fleet_reset_tracks)")
         if not float(gate) > 0 or int(window) != window or not 1 <= int(window) <= 8:
@@ -396,9 +434,7 @@ class Fleet:
         allb, vel = np.zeros((B, cap, 4, 2)), np.zeros((B, cap, 2))
         for i, a in enumerate(arrs):
             allb[i, :len(a)] = a
-        rc = self.api.fleet_track_boxes(self._handle, iptr(n), dptr(allb), cap, float(gate), int(window), dptr(vel))
-        if rc < 0:
-            raise self.api.failed("fleet_track_boxes", rc)
+        self._call("fleet_track_boxes", self._handle, iptr(n), dptr(allb), cap, float(gate), int(window), dptr(vel))
         return [vel[i, :n[i]].copy() for i in range(B)]
 
     def box_tracks(self):
@@ -407,25 +443,21 @@ class Fleet:
         self._check_track(1.0, 1)
         B, cap = len(self.members), 256
         n, c, v, age = np.zeros(B, np.int32), np.zeros((B, cap, 2)), np.zeros((B, cap, 2)), np.zeros((B, cap), np.int32)
-        rc = self.api.fleet_box_tracks(self._handle, cap, iptr(n), dptr(c), dptr(v), iptr(age))
-        if rc < 0:
-            raise self.api.failed("fleet_box_tracks", rc)
+        self._call("fleet_box_tracks", self._handle, cap, iptr(n), dptr(c), dptr(v), iptr(age))
         return [dict(centres=c[i, :n[i]].copy(), velocities=v[i, :n[i]].copy(), age=age[i, :n[i]].copy()) for i in range(B)]
 
     def reset_tracks(self, which=None):
         """the members `which` (indices; default: all) lose their tracks (rda_fleet_reset_tracks): after a gap in the ticks, or a jump of the robot"""
         self._check_track(1.0, 1)
         w = None if which is None else np.ascontiguousarray(list(which), np.int32)
-        rc = self.api.fleet_reset_tracks(self._handle, iptr(w), 0 if w is None else len(w))
-        if rc < 0:
-            raise self.api.failed("fleet_reset_tracks", rc)
+        self._call("fleet_reset_tracks", self._handle, iptr(w), 0 if w is None else len(w))
 
     def upload_worlds(self, obstacle_lists):
         """every member's WORLD - the true obstacles its simulated lidar sees (`raycast`, `rollout(lidar=)`), apart from the obstacles the planner
         stages - resident on the device (rda_fleet_upload_worlds).  `obstacle_lists[i]`: the objects `control` takes (circles and polygons of up to 8
         vertices, with their velocities); an empty list is an empty world.  A new upload replaces the old worlds."""
         from .rda_solver import RDA_solver
-        if not getattr(self.api, "has_fleet_rollout_lidar", False):
+        if not self._has("has_fleet_rollout_lidar"):
             raise RuntimeError("the loaded solver library has no world entry points (rda_fleet_upload_worlds)")
         B = len(self.members)
         if obstacle_lists is None or len(obstacle_lists) != B:
@@ -442,9 +474,7 @@ class Fleet:
         _, kind, nvert, geom, vel = scene
         counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, B)
         kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
-        rc = self.api.fleet_upload_worlds(self._handle, iptr(counts), int(we), iptr(kind), iptr(nvert), dptr(f64(geom)), dptr(f64(vel)))
-        if rc < 0:
-            raise self.api.failed("fleet_upload_worlds", rc)
+        self._call("fleet_upload_worlds", self._handle, iptr(counts), int(we), iptr(kind), iptr(nvert), dptr(f64(geom)), dptr(f64(vel)))
 
     def raycast(self, states, sensors):
         """every member's lidar scan of its resident world (`upload_worlds`) from `states[i]`, ray-cast on the device by one launch
@@ -464,13 +494,13 @@ class Fleet:
 
     def _check_see_peers(self):
         """what see_peers needs of the library and of every member, checked before any library call"""
-        if not getattr(self.api, "has_fleet_lidar_peers", False):
+        if not self._has("has_fleet_lidar_peers"):
             raise RuntimeError("the loaded solver library has no lidar that sees the other members (rda_fleet_raycast_peers, rda_fleet_rollout_lidar_peers)")
         if any(m.car_tuple.cone_type == "norm2" for m in self.members):
             raise RuntimeError("see_peers casts against the members' footprints as polygons; a circle (norm2) robot is not supported")
 
     def _raycast(self, states, sensors, see_peers):
-        if not getattr(self.api, "has_fleet_rollout_lidar", False):
+        if not self._has("has_fleet_rollout_lidar"):
             raise RuntimeError("the loaded solver library has no ray caster (rda_fleet_raycast)")
         if see_peers:
             self._check_see_peers()
@@ -489,9 +519,7 @@ class Fleet:
                  "angle_increment": (hi[i] - lo[i]) / max(int(nb[i]) - 1, 1)} for i in range(B)]
 
     def sync(self):
-        rc = self.api.fleet_sync(self._handle)
-        if rc < 0:
-            raise self.api.failed("fleet_sync", rc)
+        self._call("fleet_sync", self._handle)
 
     def rollout(self, states, ref_speeds, steps, resort=True, **kwargs):
         """`steps` closed-loop ticks of every member on the device with ONE host wait (rda_fleet_rollout): per tick what `control` does with the
@@ -543,31 +571,66 @@ class Fleet:
         `scans` cannot be combined with it.  The result has `"piece"` (steps, B) as well, the piece in force during each tick, and `index` counts
         within that piece.  Afterwards `curve_index` / `cur_index` are as `_end` leaves them and every piece's last waypoint carries the heading the
         device gave it (Q12), so `control` continues on the right piece.  Without `gears=True` such members are refused."""
+        o = self._rollout_options(resort, kwargs)
+        ms, B, K = self.members, len(self.members), int(steps)
+        if np.isscalar(ref_speeds):
+            ref_speeds = [ref_speeds] * B
+        st, speed, cur, piece0, nom_u = self._gather_gears(states, ref_speeds) if o.gears else self._gather(states, ref_speeds)
+        if o.world is not None:
+            self.upload_worlds(o.world)
+        ctl0 = f64([np.asarray(m.cur_vel_array, float)[:, 0] for m in ms], (B, 2)) if o.peers else None
+        if o.peers and o.obstacle_lists is not None:
+            self._stage_peers(o.obstacle_lists, st, ctl0, o.plan)
+        elif o.obstacle_lists is not None:
+            self._peers_staged = False
+            if not self._stage_all(o.obstacle_lists, st):
+                for i, m in enumerate(ms):
+                    m._stage_obstacles(o.obstacle_lists[i])
+        n, infos = max(K, 0), (Info * (max(K, 1) * B))()
+        log = {"states": np.zeros((n + 1, B, 3)), "controls": np.zeros((n, B, 2)), "index": np.zeros((n, B), np.int32),
+               "iters": np.zeros((n, B), np.int32), "arrived_at": np.zeros(B, np.int32)}
+        more = (("clearance", o.clearance, float), ("boxes", o.sensors is not None, np.int32), ("peer_clearance", o.peers or o.see_peers, float),
+                ("piece", o.gears, np.int32))
+        log.update({name: np.zeros((n, B), kind) for name, asked, kind in more if asked})       # the logs the options add, under their result names
+        if o.sensors is not None:
+            self.set_scan_split(o.split)
+        order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
+        values = dict(o._asdict(), F=self._handle, K=K, states=st, speed=speed, cur=cur, piece0=piece0, nom_u=nom_u, ctl0=ctl0, order=order,
+                      plans=self._plan_state(), logs=(log["states"], log["controls"], log["index"], infos, log["arrived_at"]), box_log=log.get("boxes"),
+                      clearance_log=log.get("clearance"), peer_log=log.get("peer_clearance"), piece_log=log.get("piece"))
+        self._call(o.entry, *rollout_args(o.entry, values))
+        return self._rollout_done(o, K, log, infos)
+
+    def _rollout_options(self, resort, kwargs):
+        """`rollout`'s `resort` and keyword arguments as one `RolloutOptions`.  Every refusal that needs no library call happens here, in its order,
+        before anything is allocated and before any member is touched."""
         ms = self.members
         kwargs = dict(kwargs)
-        split = scan_split_arg(kwargs, "Fleet.rollout", kwargs.get("lidar") is not None, "lidar=")
+        with_lidar, with_scans = kwargs.get("lidar") is not None, kwargs.get("scans") is not None      # scans= is only ever refused
+        split = scan_split_arg(kwargs, "Fleet.rollout", with_lidar, "lidar=")
         if split:
             self._check_split()
         gears = bool(kwargs.pop("gears", False))
         peers, plan = peers_mode(kwargs.pop("peers", False))
         see_peers = bool(kwargs.pop("see_peers", False))
         track, track_gate, track_window = bool(kwargs.pop("track", False)), kwargs.pop("track_gate", 1.0), kwargs.pop("track_window", 8)
-        if track and kwargs.get("lidar") is None:
+        if track and not with_lidar:
             raise ValueError("Fleet.rollout: track=True tracks the boxes of lidar=")
         if track:
             self._check_track(track_gate, track_window)
-        if gears and (peers or kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
+            track_gate, track_window = float(track_gate), int(track_window)
+        if gears and (peers or with_lidar or with_scans):
             raise ValueError("Fleet.rollout: gears=True cannot be combined with peers / lidar= / scans=")
-        if peers and (kwargs.get("lidar") is not None or kwargs.get("scans") is not None):
+        if peers and (with_lidar or with_scans):
             raise ValueError("Fleet.rollout: peers=True cannot be combined with lidar= / scans=")
-        if see_peers and kwargs.get("lidar") is None:
+        if see_peers and not with_lidar:
             raise ValueError("Fleet.rollout: see_peers=True belongs to lidar= (members that avoid each other through staged scenes: peers=True)")
         if peers:
             self._check_peers({k: v for k, v in kwargs.items() if k in ("threshold", "ind_range")}, plan)
             if kwargs.get("obstacle_lists") is None and not getattr(self, "_peers_staged", False):
                 raise ValueError("Fleet.rollout: peers=True needs obstacle_lists= until such scenes are resident")
-            kwargs["moving"] = True                      # (the peers rollout is a moving rollout)
-        obstacle_lists, moving, clearance = kwargs.pop("obstacle_lists", None), bool(kwargs.pop("moving", False)), bool(kwargs.pop("clearance", False))
+        obstacle_lists, clearance = kwargs.pop("obstacle_lists", None), bool(kwargs.pop("clearance", False))
+        moving = bool(kwargs.pop("moving", False)) or peers           # (the peers rollout is a moving rollout)
         lidar, world = kwargs.pop("lidar", None), kwargs.pop("world", None)
         scan_eps, scan_min_samples = float(kwargs.pop("scan_eps", 2.0)), int(kwargs.pop("scan_min_samples", 6))
         sensors = None
@@ -579,17 +642,18 @@ class Fleet:
             sensors = sensor_arrays(lidar, len(ms))
             if not (scan_eps > 0) or scan_min_samples < 1:
                 raise ValueError("Fleet.rollout: scan_eps > 0 and scan_min_samples >= 1")
-            if not getattr(self.api, "has_fleet_rollout_lidar", False) or any(m.rda_obstacle for m in ms):
+            if not self._has("has_fleet_rollout_lidar") or any(m.rda_obstacle for m in ms):
                 raise RuntimeError("Fleet.rollout(lidar=...) needs the lidar rollout (rda_fleet_rollout_lidar); there is no host fallback")
             if see_peers:
                 self._check_see_peers()
+        # what is left beyond threshold and ind_range (scans= among it) is refused by the members
         if (not gears and any(m.enable_reverse for m in ms)) or not all(m._tracks(kwargs) for m in ms):
             raise RuntimeError("Fleet.rollout needs device-side tracking on every member and enable_reverse=False (or gears=True); there is no host fallback")
-        if gears and not getattr(self.api, "has_fleet_rollout_gears", False):
+        if gears and not self._has("has_fleet_rollout_gears"):
             raise RuntimeError("the loaded solver library has no rollout over gear pieces (rda_fleet_rollout_gears)")
-        if not getattr(self.api, "has_fleet_rollout", False):
+        if not self._has("has_fleet_rollout"):
             raise RuntimeError("the loaded solver library has no fleet rollout entry point (rda_fleet_rollout)")
-        if moving and not getattr(self.api, "has_fleet_rollout_moving", False):
+        if moving and not self._has("has_fleet_rollout_moving"):
             raise RuntimeError("the loaded solver library has no rollout for moving scenes (rda_fleet_rollout_moving)")
         if clearance and not moving and lidar is None:
             raise ValueError("Fleet.rollout: clearance=True needs moving=True (the clearance log belongs to rda_fleet_rollout_moving)")
@@ -600,76 +664,30 @@ class Fleet:
         margins = {int(m.goal_index_threshold) for m in ms}
         if len(margins) != 1:
             raise ValueError("Fleet.rollout: the members must share one goal_index_threshold")
-        B, T, K = len(ms), ms[0].receding, int(steps)
-        if np.isscalar(ref_speeds):
-            ref_speeds = [ref_speeds] * B
-        if gears:
-            st, speed, cur, piece0, nom_u = self._gather_gears(states, ref_speeds)
-        else:
-            st, speed, cur, _, nom_u = self._gather(states, ref_speeds)
-        if world is not None:
-            self.upload_worlds(world)
-        ctl0 = f64([np.asarray(m.cur_vel_array, float)[:, 0] for m in ms], (B, 2)) if peers else None
-        if peers and obstacle_lists is not None:
-            self._stage_peers(obstacle_lists, st, ctl0, plan)
-        elif obstacle_lists is not None:
-            self._peers_staged = False
-            if not self._stage_all(obstacle_lists, st):
-                for i, m in enumerate(ms):
-                    m._stage_obstacles(obstacle_lists[i])
-        s_log, u_log = np.zeros((max(K, 0) + 1, B, 3)), np.zeros((max(K, 0), B, 2))
-        i_log, arrived = np.zeros((max(K, 0), B), np.int32), np.zeros(B, np.int32)
-        infos = (Info * (max(K, 1) * B))()
-        head = (self._handle, K, dptr(st), dptr(speed), iptr(cur), float(kwargs.get("threshold", 0.1)), int(kwargs.get("ind_range", 10)), margins.pop())
-        logs = (dptr(s_log), dptr(u_log), iptr(i_log), infos, iptr(arrived))
-        c_log = np.zeros((max(K, 0), B)) if clearance else None
-        p_log = np.zeros((max(K, 0), B)) if peers or see_peers else None
-        g_log = np.zeros((max(K, 0), B), np.int32) if gears else None
-        if gears:
-            rc, name = self.api.fleet_rollout_gears(self._handle, K, dptr(st), dptr(speed), iptr(piece0), iptr(cur), *head[5:], 1 if resort else 0,
-                                                    1 if moving else 0, dptr(nom_u), *logs, iptr(g_log), dptr(c_log)), "fleet_rollout_gears"
-        elif plan:
-            plans, valid = self._plan_state()
-            rc, name = self.api.fleet_rollout_peers_plan(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log), dptr(plans),
-                                                         iptr(valid)), "fleet_rollout_peers_plan"
-        elif peers:
-            rc, name = self.api.fleet_rollout_peers(*head, dptr(nom_u), dptr(ctl0), *logs, dptr(c_log), dptr(p_log)), "fleet_rollout_peers"
-        elif sensors is not None:
-            order = np.fromiter((bool(m.obstacle_order) for m in ms), np.int32, B)
-            b_log = np.zeros((max(K, 0), B), np.int32)
-            self.set_scan_split(split)
-            args = (*head, dptr(nom_u), iptr(sensors[0]), *(dptr(a) for a in sensors[1:]), scan_eps, scan_min_samples, iptr(order), 1 if moving else 0,
-                    *logs, iptr(b_log), dptr(c_log))
-            if track:
-                rc, name = self.api.fleet_rollout_lidar_tracked(*args, dptr(p_log), 1 if see_peers else 0, float(track_gate),
-                                                                int(track_window)), "fleet_rollout_lidar_tracked"
-            elif see_peers:
-                rc, name = self.api.fleet_rollout_lidar_peers(*args, dptr(p_log)), "fleet_rollout_lidar_peers"
-            else:
-                rc, name = self.api.fleet_rollout_lidar(*args), "fleet_rollout_lidar"
-        else:
-            args = head + (1 if resort else 0, dptr(nom_u)) + logs
-            rc = self.api.fleet_rollout_moving(*args, dptr(c_log)) if moving else self.api.fleet_rollout(*args)
-            name = "fleet_rollout_moving" if moving else "fleet_rollout"
-        if rc < 0:
-            raise self.api.failed(name, rc)
+        o = RolloutOptions(resort=bool(resort), gears=gears, peers=peers, plan=plan, see_peers=see_peers, track=track, track_gate=track_gate,
+                           track_window=track_window, split=split, moving=moving, clearance=clearance, sensors=sensors, scan_eps=scan_eps,
+                           scan_min_samples=scan_min_samples, obstacle_lists=obstacle_lists, world=world, threshold=float(kwargs.get("threshold", 0.1)),
+                           ind_range=int(kwargs.get("ind_range", 10)), margin=margins.pop(), entry=None)
+        return o._replace(entry=rollout_entry(o))
+
+    def _rollout_done(self, o, K, log, infos):
+        """after the rollout's entry has returned: what the last tick left on the device into the members, so `control` continues the loop; returns
+        `rollout`'s result, which is `log` with the `iters` of `infos`"""
+        ms = self.members
+        B, T, arrived = len(ms), ms[0].receding, log["arrived_at"]
         eh = np.zeros(B)
-        rc = self.api.fleet_rollout_last(self._handle, dptr(self._out_u), dptr(eh))
-        if rc < 0:
-            raise self.api.failed("fleet_rollout_last", rc)
-        if getattr(self.api, "has_fleet_peers_plan", False):        # the plans the last tick left: what a peers="plan" tick that continues predicts along
+        self._call("fleet_rollout_last", self._handle, dptr(self._out_u), dptr(eh))
+        if self._has("has_fleet_peers_plan"):        # the plans the last tick left: what a peers="plan" tick that continues predicts along
             plans, valid = self._plan_state()
-            rc = self.api.fleet_rollout_last_plan(self._handle, dptr(plans))
-            if rc < 0:
-                raise self.api.failed("fleet_rollout_last_plan", rc)
+            self._call("fleet_rollout_last_plan", self._handle, dptr(plans))
             valid[:] = arrived < 0
-        if gears:
-            self._scatter_gears(g_log[K - 1], i_log[K - 1], arrived)
+        if o.gears:
+            self._scatter_gears(log["piece"][K - 1], log["index"][K - 1], arrived)
         for i, m in enumerate(ms):
             path = m.ref_path
-            m.state = s_log[K, i].reshape(3, 1).copy()
-            if not gears:
-                m.cur_index = int(i_log[K - 1, i])
+            m.state = log["states"][K, i].reshape(3, 1).copy()
+            if not o.gears:
+                m.cur_index = int(log["index"][K - 1, i])
                 path[-1][2, 0] = eh[i]                     # quirk Q12: the device rewrote the last waypoint's heading in its copy
                 if m._dev_path_key is not None and m._dev_path_key[0] is path:
                     m._dev_path_key[1][-1] = path[-1].tobytes()
@@ -678,31 +696,18 @@ class Fleet:
                 m._dev_u = None
             else:                                          # the device holds the controls of the last solve
                 m.cur_vel_array = m._dev_u = self._out_u[i].copy()
-        iters = np.array([infos[j].iters for j in range(K * B)], np.int32).reshape(K, B)
-        out = {"states": s_log, "controls": u_log, "index": i_log, "iters": iters, "arrived_at": arrived}
-        if clearance:
-            out["clearance"] = c_log
-        if sensors is not None:
-            out["boxes"] = b_log
-        if peers or see_peers:
-            out["peer_clearance"] = p_log
-        if gears:
-            out["piece"] = g_log
-        return out
+        log["iters"][:] = np.array([infos[j].iters for j in range(K * B)], np.int32).reshape(K, B)
+        return log
 
     def clearance(self, states):
         """(B,) every member's clearance at `states[i]` against ALL obstacles of the scene it has staged, as they stand on the device
         (rda_fleet_clearance: `scenarios.clearance` for polygon robots, one launch; negative = overlap, +inf without a staged scene)"""
-        if not getattr(self.api, "has_fleet_rollout_moving", False):
+        if not self._has("has_fleet_rollout_moving"):
             raise RuntimeError("the loaded solver library has no clearance entry point (rda_fleet_clearance)")
         if any(m.car_tuple.cone_type == "norm2" for m in self.members):
             raise RuntimeError("Fleet.clearance is for polygon robots; a circle (norm2) robot is not supported")
-        B = len(self.members)
-        st = states_array(states, B)
-        out = np.zeros(B)
-        rc = self.api.fleet_clearance(self._handle, dptr(st), dptr(out))
-        if rc < 0:
-            raise self.api.failed("fleet_clearance", rc)
+        st, out = states_array(states, len(self.members)), np.zeros(len(self.members))
+        self._call("fleet_clearance", self._handle, dptr(st), dptr(out))
         return out
 
     def _gather(self, states, ref_speeds):
@@ -761,9 +766,7 @@ class Fleet:
         ms = self.members
         B = len(ms)
         piece, heads = np.zeros(B, np.int32), np.zeros(sum(len(self._gear_pieces(m)) for m in ms))
-        rc = self.api.fleet_rollout_last_pieces(self._handle, iptr(piece), dptr(heads))
-        if rc < 0:
-            raise self.api.failed("fleet_rollout_last_pieces", rc)
+        self._call("fleet_rollout_last_pieces", self._handle, iptr(piece), dptr(heads))
         at = 0
         for i, m in enumerate(ms):
             pieces = self._gear_pieces(m)
@@ -790,11 +793,8 @@ class Fleet:
             for i, m in enumerate(self.members):
                 m._stage_obstacles(obstacle_lists[i])
         mi, eh = np.zeros(B, np.int32), np.zeros(B)
-        rc = self.api.fleet_step_tracked(self._handle, dptr(st), dptr(speed), iptr(cur), float(threshold), int(ind_range),
-                                         dptr(nom_u), dptr(self._out_u), dptr(self._out_s), self._info, dptr(self._ref),
-                                         iptr(mi), dptr(eh))
-        if rc < 0:
-            raise self.api.failed("fleet_step_tracked", rc)
+        self._call("fleet_step_tracked", self._handle, dptr(st), dptr(speed), iptr(cur), float(threshold), int(ind_range),
+                   dptr(nom_u), dptr(self._out_u), dptr(self._out_s), self._info, dptr(self._ref), iptr(mi), dptr(eh))
         out = []
         for i, m in enumerate(self.members):
             if self._info[i].su_status and m.rda.time_print:

@@ -1,14 +1,13 @@
 """What the fleet ray caster's and the lidar rollout's tests share (tests/test_gpu_fleet_raycast.py, tests/test_gpu_fleet_rollout_lidar.py): the lanes of
-tests/test_gpu_fleet_rollout_moving.py with their 7 obstacles per member taken as the WORLD, the three sensors, and the numpy reference - World.get_lidar_scan
+tests/fleet_twin_lib.py with their 7 obstacles per member taken as the WORLD, the three sensors, and the numpy reference - World.get_lidar_scan
 itself, run on a World object that is given a pose, a sensor and an obstacle list."""
 from types import SimpleNamespace
 
 import numpy as np
 
+from fleet_twin_lib import DT, NOBS, lane                  # noqa: F401  (the shapes of the rollout tests, not copies of them)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd.world import World, _Obstacle
-
-from test_gpu_fleet_rollout_moving import DT, NOBS, lane                  # the shapes of that file, not copies of them
 
 WE = 4                                     # vertex stride of the lanes' worlds
 # beams, field of view, range_max (range_min 0): half a turn ahead at 10 m, a full turn at 10 m, a full turn that sees 3 m

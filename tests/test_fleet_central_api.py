@@ -1,42 +1,30 @@
 """Fleets of members in the interior-point LamMuZ mode (`lmz_central`): what can be checked without a GPU - rda_fleet_lammuz_kernel is declared, exported
 and bound, the header and rda_strerror state the new rules, and the Python constructor names them when the library refuses a fleet."""
 import ctypes as C
-import os
 import re
 import types
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RDA_ERR_UNSUPPORTED = -2
-
-
-def _header(comments=False):
-    text = open(os.path.join(ROOT, "include", "rda_hip.h")).read()
-    return text if comments else re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def _lib():
-    from rda_planner_amd import _lib
-    return C.CDLL(_lib.build())
+from capi_lib import RDA_ERR_UNSUPPORTED, header, lib
 
 
 def test_fleet_lammuz_kernel_is_declared_exported_and_bound():
     from rda_planner_amd._capi import CApi
-    assert re.search(r"\bconst\s+char\s*\*\s*rda_fleet_lammuz_kernel\s*\(\s*rda_fleet\s*\*\s*\w*\s*\)\s*;", _header())
-    lib = _lib()
-    assert hasattr(lib, "rda_fleet_lammuz_kernel")
-    api = CApi(lib, "rda")
+    assert re.search(r"\bconst\s+char\s*\*\s*rda_fleet_lammuz_kernel\s*\(\s*rda_fleet\s*\*\s*\w*\s*\)\s*;", header())
+    so = lib()
+    assert hasattr(so, "rda_fleet_lammuz_kernel")
+    api = CApi(so, "rda")
     fn = api.fleet_lammuz_kernel
     assert list(fn.argtypes) == [C.c_void_p] and fn.restype is C.c_char_p
     assert fn(None) == b""                                  # a null fleet has no launches (no device needed)
 
 
 def test_header_and_strerror_state_the_rules():
-    doc = " ".join(_header(comments=True).split())
+    doc = " ".join(header(comments=True).split())
     assert "ALL members or NONE" in doc and "lmz_mu may differ per member" in doc and "norm2 (circle) robot is refused" in doc
     from rda_planner_amd._capi import CApi
-    msg = CApi(_lib(), "rda").strerror(RDA_ERR_UNSUPPORTED).decode()
+    msg = CApi(lib(), "rda").strerror(RDA_ERR_UNSUPPORTED).decode()
     assert "norm2 robot" in msg and "mixed LamMuZ modes in a fleet" in msg and "interior-point mode in a fleet" not in msg
 
 

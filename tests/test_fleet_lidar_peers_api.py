@@ -5,48 +5,43 @@ refused before any library call."""
 import ctypes as C
 import inspect
 import os
-import types
+import re
 
 import numpy as np
 import pytest
 
-from test_fleet_lidar_rollout_api import SENSOR, _header, _header_argtypes, _lib
+from capi_lib import LIDAR_FLAGS, RDA_ERR_ARG, ROOT, SENSOR, Binding, bare_fleet, declared, header_argtypes, integration_rows, lib, pipeline_member
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NARGS = {"rda_fleet_raycast_peers": 8, "rda_fleet_rollout_lidar_peers": 26}
-RDA_ERR_ARG = -1
 
 
 @pytest.mark.parametrize("name", sorted(NARGS))
 def test_declared_exported_documented_and_bound_like_the_header(name):
-    import re
     from rda_planner_amd._capi import CApi
-    assert re.search(r"\bint\s+%s\s*\(" % name, _header()), name
-    lib = _lib()
-    assert hasattr(lib, name), f"{name} declared in include/rda_hip.h but not exported"
-    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert [ln for ln in doc.splitlines() if ln.startswith("|") and "`%s`" % name in ln], name
-    api = CApi(lib, "rda")
+    assert declared(name), name
+    so = lib()
+    assert hasattr(so, name), f"{name} declared in include/rda_hip.h but not exported"
+    assert integration_rows(name), name
+    api = CApi(so, "rda")
     assert api.has_fleet_lidar_peers is True
     fn = getattr(api, name[len("rda_"):])
-    want = _header_argtypes(name)
+    want = header_argtypes(name)
     assert len(want) == NARGS[name]
     assert list(fn.argtypes) == want and fn.restype is C.c_int
 
 
 def test_the_entries_take_the_blind_entries_arguments():
     from rda_planner_amd._capi import c_double_p
-    assert _header_argtypes("rda_fleet_raycast_peers") == _header_argtypes("rda_fleet_raycast")
-    blind, seeing = _header_argtypes("rda_fleet_rollout_lidar"), _header_argtypes("rda_fleet_rollout_lidar_peers")
+    assert header_argtypes("rda_fleet_raycast_peers") == header_argtypes("rda_fleet_raycast")
+    blind, seeing = header_argtypes("rda_fleet_rollout_lidar"), header_argtypes("rda_fleet_rollout_lidar_peers")
     assert seeing[:-1] == blind and seeing[-1] is c_double_p                              # ... plus peer_clearance_log
-    import re
     text = " ".join(re.sub(r"\n \* ", " ", open(os.path.join(ROOT, "include", "rda_hip.h")).read()).split())
     assert "rda_fleet_raycast_peers, then rda_fleet_upload_scans of those ranges at those states, then rda_fleet_step_tracked" in text      # the contract
 
 
 def test_null_arguments_are_argument_errors_without_a_device():
     from rda_planner_amd._capi import CApi, Info, dptr, iptr
-    api = CApi(_lib(), "rda")
+    api = CApi(lib(), "rda")
     K, B = 2, 1
     st, sp, cur, nb, one = np.zeros((B, 3)), np.ones(B), np.zeros(B, np.int32), np.full(B, 10, np.int32), np.ones(B)
     sl, ul, il, arr, info = np.zeros((K + 1, B, 3)), np.zeros((K, B, 2)), np.zeros((K, B), np.int32), np.zeros(B, np.int32), (Info * (K * B))()
@@ -69,15 +64,6 @@ def test_peer_footprints_are_the_peer_obstacles_standing():
     assert sc.peer_footprints(cars[:1], states[:1], 0) == []
 
 
-class _Binding:
-    """stands for the library binding: it answers the capability flags it is given and fails on any other use"""
-    def __init__(self, **flags):
-        self.__dict__.update(has_fleet_rollout=True, has_fleet_rollout_moving=True, has_fleet_rollout_lidar=True, has_fleet_peers=True, **flags)
-
-    def __getattr__(self, name):
-        raise AssertionError(f"library touched: {name}")
-
-
 def test_python_interface_and_refusals_before_any_device_call():
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.fleet import Fleet
@@ -87,16 +73,9 @@ def test_python_interface_and_refusals_before_any_device_call():
     assert all(word in doc for word in ("see_peers=True", "rda_fleet_rollout_lidar_peers", '"peer_clearance"', "standing boxes", "peer_footprints"))
     assert "see_peers" in Fleet.raycast.__doc__ and "see_peers" in Fleet.raycast_peers.__doc__ and "standing boxes" in " ".join(Fleet.raycast_peers.__doc__.split())
 
-    def member(car=None):
-        def no_solver(*a, **k):
-            raise AssertionError("member touched")
-        return types.SimpleNamespace(enable_reverse=False, _tracks=lambda kw: set(kw) <= {"threshold", "ind_range"}, goal_index_threshold=1, receding=5,
-                                     car_tuple=car or sc.rectangle_robot(), rda_obstacle=False, obstacle_order=True, device_obstacles=True,
-                                     rda=types.SimpleNamespace(has_scene=True), _piece=no_solver, _sync_path=no_solver)
+    member = pipeline_member
     states = [np.zeros((3, 1)), np.zeros((3, 1))]
-    f = Fleet.__new__(Fleet)                           # no device: a binding that fails on any use
-    f._handle = None
-    f.api, f.members = _Binding(has_fleet_lidar_peers=False), [member(), member()]        # a library without the entry points
+    f = bare_fleet(Binding(**LIDAR_FLAGS, has_fleet_lidar_peers=False), [member(), member()])        # no device; a library without the entry points
     with pytest.raises(ValueError, match="see_peers=True belongs to lidar="):
         f.rollout(states, 4.0, 5, see_peers=True)
     with pytest.raises(ValueError, match="see_peers=True belongs to lidar="):
@@ -105,7 +84,7 @@ def test_python_interface_and_refusals_before_any_device_call():
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], see_peers=True)
     with pytest.raises(RuntimeError, match="rda_fleet_raycast_peers"):
         f.raycast_peers(states, [SENSOR, SENSOR])
-    f.api = _Binding(has_fleet_lidar_peers=True)
+    f.api = Binding(**LIDAR_FLAGS, has_fleet_lidar_peers=True)
     f.members = [member(), member(sc.circle_robot())]
     with pytest.raises(RuntimeError, match="circle"):
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], see_peers=True)
@@ -128,6 +107,6 @@ def test_python_interface_and_refusals_before_any_device_call():
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], gears=True, see_peers=True)
     with pytest.raises(ValueError, match="world= belongs to lidar="):
         f.rollout(states, 4.0, 5, world=[[], []])
-    f.api = _Binding()                                 # see_peers not asked for: the flag is not even queried (the binding knows no such attribute)
+    f.api = Binding(**LIDAR_FLAGS)                             # see_peers not asked for: the flag is not even queried (the binding knows no such attribute)
     with pytest.raises(ValueError, match="scan_eps"):
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], scan_eps=0.0)

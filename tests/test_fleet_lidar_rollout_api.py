@@ -4,56 +4,35 @@ header's argument lists, a null fleet is an argument error, Fleet.rollout keeps 
 library call."""
 import ctypes as C
 import inspect
-import os
-import re
 import types
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from capi_lib import RDA_ERR_ARG, SENSOR, Binding, bare_fleet, declared, header_argtypes, integration_rows, lib, member
+
 NARGS = {"rda_fleet_upload_worlds": 7, "rda_fleet_raycast": 8, "rda_fleet_rollout_lidar": 25, "rda_debug_fleet_world": 4}
-RDA_ERR_ARG = -1
-SENSOR = dict(number=100, angle_min=-1.5, angle_max=1.5, range_min=0.0, range_max=10.0)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rda_hip.h")).read(), flags=re.S)
-
-
-def _lib():
-    from rda_planner_amd import _lib
-    return C.CDLL(_lib.build())
-
-
-def _header_argtypes(name):
-    from rda_planner_amd._capi import Info, c_double_p, c_int_p
-    kinds = {"rda_fleet *": C.c_void_p, "const int32_t *": c_int_p, "int32_t *": c_int_p, "const double *": c_double_p, "double *": c_double_p,
-             "double": C.c_double, "int": C.c_int, "rda_info *": C.POINTER(Info)}
-    args = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, _header(), re.S).group(1)
-    return [kinds[" ".join(re.match(r"\s*(.*?)(\w+)\s*$", a.strip(), re.S).group(1).split())] for a in args.split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(NARGS))
 def test_declared_exported_documented_and_bound_like_the_header(name):
     from rda_planner_amd._capi import CApi
-    assert re.search(r"\bint\s+%s\s*\(" % name, _header()), name
-    lib = _lib()
-    assert hasattr(lib, name), f"{name} declared in include/rda_hip.h but not exported"
-    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert [ln for ln in doc.splitlines() if ln.startswith("|") and "`%s`" % name in ln], name
-    api = CApi(lib, "rda")
+    assert declared(name), name
+    so = lib()
+    assert hasattr(so, name), f"{name} declared in include/rda_hip.h but not exported"
+    assert integration_rows(name), name
+    api = CApi(so, "rda")
     assert api.has_fleet_rollout_lidar
     fn = getattr(api, name[len("rda_"):])
-    want = _header_argtypes(name)
+    want = header_argtypes(name)
     assert len(want) == NARGS[name]
     assert list(fn.argtypes) == want and fn.restype is C.c_int
 
 
 def test_lidar_entry_takes_the_static_entry_s_arguments_without_resort():
     from rda_planner_amd._capi import c_double_p, c_int_p
-    static, lidar = _header_argtypes("rda_fleet_rollout"), _header_argtypes("rda_fleet_rollout_lidar")
-    sensor = _header_argtypes("rda_fleet_raycast")[1:6]
+    static, lidar = header_argtypes("rda_fleet_rollout"), header_argtypes("rda_fleet_rollout_lidar")
+    sensor = header_argtypes("rda_fleet_raycast")[1:6]
     assert lidar[:8] == static[:8] and lidar[8] == static[9]                              # ... , goal_margin | nom_u: `resort` is gone
     assert lidar[9:14] == sensor                                                          # the sensor arrays of rda_fleet_raycast
     assert lidar[14:18] == [C.c_double, C.c_int, c_int_p, C.c_int]                        # eps, min_samples, order, moving
@@ -62,7 +41,7 @@ def test_lidar_entry_takes_the_static_entry_s_arguments_without_resort():
 
 def test_null_arguments_are_argument_errors_without_a_device():
     from rda_planner_amd._capi import CApi, Info, dptr, iptr
-    api = CApi(_lib(), "rda")
+    api = CApi(lib(), "rda")
     K, B = 2, 1
     st, sp, cur, nb, one = np.zeros((B, 3)), np.ones(B), np.zeros(B, np.int32), np.full(B, 10, np.int32), np.ones(B)
     sl, ul, il, arr, info = np.zeros((K + 1, B, 3)), np.zeros((K, B, 2)), np.zeros((K, B), np.int32), np.zeros(B, np.int32), (Info * (K * B))()
@@ -92,15 +71,6 @@ def test_sensor_mappings_are_validated():
             sensor_arrays([s], 1)
 
 
-class _Binding:
-    """stands for the library binding: it answers the capability flags and fails on any other use"""
-    def __init__(self, lidar):
-        self.__dict__.update(has_fleet_rollout=True, has_fleet_rollout_moving=True, has_fleet_rollout_lidar=lidar)
-
-    def __getattr__(self, name):
-        raise AssertionError(f"library touched: {name}")
-
-
 def test_python_interface_and_refusals_before_any_device_call():
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.fleet import Fleet
@@ -111,22 +81,17 @@ def test_python_interface_and_refusals_before_any_device_call():
     doc = " ".join(Fleet.rollout.__doc__.split())
     assert all(word in doc for word in ("lidar=sensors", "world=obstacle_lists", "scan_eps", "scan_min_samples", '"boxes"', "rda_fleet_rollout_lidar"))
 
-    def member():
-        def no_solver(*a, **k):
-            raise AssertionError("member touched")
-        return types.SimpleNamespace(enable_reverse=False, _tracks=lambda kw: set(kw) <= {"threshold", "ind_range"}, goal_index_threshold=1, receding=5,
-                                     car_tuple=sc.rectangle_robot(), rda_obstacle=False, _piece=no_solver, _sync_path=no_solver)
+    def binding(lidar):
+        return Binding(has_fleet_rollout=True, has_fleet_rollout_moving=True, has_fleet_rollout_lidar=lidar)
     states = [np.zeros((3, 1)), np.zeros((3, 1))]
-    f = Fleet.__new__(Fleet)                           # no device: a binding that fails on any use
-    f._handle = None
-    f.api, f.members = _Binding(lidar=False), [member(), member()]
+    f = bare_fleet(binding(False), [member(car_tuple=sc.rectangle_robot(), rda_obstacle=False) for _ in range(2)])      # no device: a binding that fails on any use
     with pytest.raises(RuntimeError, match="rda_fleet_rollout_lidar"):
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR])         # a library without the entry
     with pytest.raises(RuntimeError, match="rda_fleet_raycast"):
         f.raycast(states, [SENSOR, SENSOR])
     with pytest.raises(RuntimeError, match="rda_fleet_upload_worlds"):
         f.upload_worlds([[], []])
-    f.api = _Binding(lidar=True)
+    f.api = binding(True)
     with pytest.raises(ValueError, match="one sensor per member"):
         f.rollout(states, 4.0, 5, lidar=[SENSOR])
     with pytest.raises(ValueError, match="world= belongs to lidar="):

@@ -4,17 +4,15 @@ Fleet.control(peers=True), Fleet.rollout(peers=True), Fleet.peer_clearance): wha
 prototype table, and on the CPU oracle the behaviour the feature is for: three robots whose paths cross drive through each other when they are blind and
 keep apart when every one sees the others as moving obstacles."""
 import ctypes as C
-import os
-import re
 import types
 from math import cos, pi, sin
 
 import numpy as np
 import pytest
 
+from capi_lib import Binding, bare_fleet, declared, integration_rows, lib, pipeline_member
 from rda_planner_amd import scenarios as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("rda_fleet_upload_scenes_peers", "rda_fleet_scene_resort_peers", "rda_fleet_rollout_peers", "rda_fleet_peer_clearance", "rda_debug_scene_vel")
 
 
@@ -64,21 +62,19 @@ def test_peer_clearance_on_hand_placed_rectangles():
 # ---- the entry points -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES)
 def test_entries_declared_bound_and_exported(name):
-    from rda_planner_amd import _capi, _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rda_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    from rda_planner_amd import _capi
+    assert declared(name), name
     assert name[len("rda_"):] in _capi.PROTOTYPES
-    api = _capi.CApi(C.CDLL(_lib.build()), "rda")
+    api = _capi.CApi(lib(), "rda")
     assert api.has_fleet_peers is True
     fn = getattr(api, name[len("rda_"):])
     assert list(fn.argtypes) == _capi.signature(_capi.PROTOTYPES[name[len("rda_"):]])[1] and fn.restype is C.c_int
-    assert "`%s`" % name in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert integration_rows(name, table=False)
 
 
 def test_null_fleet_is_an_argument_error_without_a_device():
-    from rda_planner_amd import _capi, _lib
-    from rda_planner_amd._capi import dptr, iptr
-    api = _capi.CApi(C.CDLL(_lib.build()), "rda")
+    from rda_planner_amd._capi import CApi, dptr, iptr
+    api = CApi(lib(), "rda")
     st, ctl, one = np.zeros((1, 3)), np.zeros((1, 2)), np.zeros(1, np.int32)
     assert api.fleet_upload_scenes_peers(None, iptr(one), None, None, None, None, dptr(st), dptr(ctl)) == -1
     assert api.fleet_scene_resort_peers(None, dptr(st), dptr(ctl)) == -1
@@ -89,19 +85,8 @@ def test_null_fleet_is_an_argument_error_without_a_device():
 
 
 # ---- the refusals of the Python interface -----------------------------------------------------------------------------------------------------------
-class _NoCalls:
-    """stands for the library binding: any use of it is an error (the capability flag is an instance attribute, so reading it is none)"""
-    def __init__(self, has_fleet_peers):
-        self.has_fleet_peers = has_fleet_peers
-
-    def __getattr__(self, name):
-        raise AssertionError(f"library touched: {name}")
-
-
-def _member(order=True, cone="Rpositive", rda_obstacle=False, tracks=True, reverse=False):
-    return types.SimpleNamespace(obstacle_order=order, car_tuple=types.SimpleNamespace(cone_type=cone), rda_obstacle=rda_obstacle, device_obstacles=True,
-                                 rda=types.SimpleNamespace(has_scene=True), enable_reverse=reverse, _tracks=lambda kw: tracks, goal_index_threshold=1,
-                                 receding=5, cur_vel_array=np.zeros((2, 5)))
+def _member(cone="Rpositive", **kw):
+    return pipeline_member(car=types.SimpleNamespace(cone_type=cone), cur_vel_array=np.zeros((2, 5)), **kw)
 
 
 @pytest.mark.parametrize("has,bad,exc", [
@@ -112,9 +97,7 @@ def _member(order=True, cone="Rpositive", rda_obstacle=False, tracks=True, rever
     (True, _member(tracks=False), RuntimeError),               # a member that does not track on the device
 ], ids=["no-entries", "obstacle_order=False", "norm2", "rda_obstacle", "not-tracked"])
 def test_python_refusals_before_any_library_call(has, bad, exc):
-    from rda_planner_amd.fleet import Fleet
-    f = Fleet.__new__(Fleet)
-    f.api, f._handle, f.members = _NoCalls(has), None, [_member(), bad]
+    f = bare_fleet(Binding(has_fleet_peers=has), [_member(), bad])
     states, obs = [np.zeros((3, 1)), np.ones((3, 1))], [[], []]
     with pytest.raises(exc):
         f.control(states, 2.0, obs, peers=True)
@@ -126,9 +109,7 @@ def test_python_refusals_before_any_library_call(has, bad, exc):
 
 
 def test_python_peers_with_scans_or_lidar_is_a_value_error():
-    from rda_planner_amd.fleet import Fleet
-    f = Fleet.__new__(Fleet)
-    f.api, f._handle, f.members = _NoCalls(True), None, [_member(), _member()]
+    f = bare_fleet(Binding(has_fleet_peers=True), [_member(), _member()])
     states = [np.zeros((3, 1)), np.ones((3, 1))]
     scan = dict(ranges=np.ones(8), angle_min=-1.0, angle_max=1.0, range_max=5.0)
     sensor = dict(number=8, angle_min=-1.0, angle_max=1.0, range_min=0.0, range_max=5.0)

@@ -3,17 +3,15 @@ rda_fleet_rollout_last_plan; Fleet.control(peers="plan"), Fleet.rollout(peers="p
 (scenarios.peer_plan_poses, scenarios.peer_plan_obstacles), the argument handling and the plan bookkeeping of `Fleet` on a stub binding, the entry points
 in the header and the prototype table."""
 import ctypes as C
-import os
-import re
 import types
 from math import cos, sin
 
 import numpy as np
 import pytest
 
+from capi_lib import Binding, bare_fleet, declared, integration_rows, lib, pipeline_member
 from rda_planner_amd import scenarios as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("rda_fleet_upload_scenes_peers_plan", "rda_fleet_scene_resort_peers_plan", "rda_fleet_rollout_peers_plan", "rda_fleet_rollout_last_plan")
 T, DT = 8, 0.1
 
@@ -91,21 +89,19 @@ def test_obstacle_form():
 # ---- the entry points -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES)
 def test_entries_declared_bound_and_exported(name):
-    from rda_planner_amd import _capi, _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rda_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    from rda_planner_amd import _capi
+    assert declared(name), name
     assert name[len("rda_"):] in _capi.PROTOTYPES
-    api = _capi.CApi(C.CDLL(_lib.build()), "rda")
+    api = _capi.CApi(lib(), "rda")
     assert api.has_fleet_peers_plan is True
     fn = getattr(api, name[len("rda_"):])
     assert list(fn.argtypes) == _capi.signature(_capi.PROTOTYPES[name[len("rda_"):]])[1] and fn.restype is C.c_int
-    assert "`%s`" % name in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert integration_rows(name, table=False)
 
 
 def test_null_fleet_is_an_argument_error_without_a_device():
-    from rda_planner_amd import _capi, _lib
-    from rda_planner_amd._capi import dptr, iptr
-    api = _capi.CApi(C.CDLL(_lib.build()), "rda")
+    from rda_planner_amd._capi import CApi, dptr, iptr
+    api = CApi(lib(), "rda")
     st, ctl, one, plan = np.zeros((1, 3)), np.zeros((1, 2)), np.zeros(1, np.int32), np.zeros((1, 3, T + 1))
     assert api.fleet_upload_scenes_peers_plan(None, iptr(one), None, None, None, None, dptr(st), dptr(ctl), dptr(plan), iptr(one)) == -1
     assert api.fleet_scene_resort_peers_plan(None, dptr(st), dptr(ctl), dptr(plan), iptr(one)) == -1
@@ -115,33 +111,19 @@ def test_null_fleet_is_an_argument_error_without_a_device():
 
 
 # ---- Fleet: argument handling and bookkeeping on a stub binding -------------------------------------------------------------------------------------
-class _NoCalls:
-    """stands for the library binding: any use of it is an error (the capability flags are instance attributes, so reading them is none)"""
-    def __init__(self, has_fleet_peers=True, has_fleet_peers_plan=True):
-        self.has_fleet_peers, self.has_fleet_peers_plan = has_fleet_peers, has_fleet_peers_plan
-
-    def __getattr__(self, name):
-        raise AssertionError(f"library touched: {name}")
+def _member(cone="Rpositive", **kw):
+    return pipeline_member(car=types.SimpleNamespace(cone_type=cone), cur_vel_array=np.zeros((2, 5)), **kw)
 
 
-def _member(order=True, cone="Rpositive", rda_obstacle=False, tracks=True, reverse=False):
-    return types.SimpleNamespace(obstacle_order=order, car_tuple=types.SimpleNamespace(cone_type=cone), rda_obstacle=rda_obstacle, device_obstacles=True,
-                                 rda=types.SimpleNamespace(has_scene=True), enable_reverse=reverse, _tracks=lambda kw: tracks, goal_index_threshold=1,
-                                 receding=5, cur_vel_array=np.zeros((2, 5)))
-
-
-def _bare(api, members):
-    from rda_planner_amd.fleet import Fleet
-    f = Fleet.__new__(Fleet)
-    f.api, f._handle, f.members = api, None, members
-    return f
+def _binding(has_fleet_peers=True, has_fleet_peers_plan=True):
+    return Binding(has_fleet_peers=has_fleet_peers, has_fleet_peers_plan=has_fleet_peers_plan)
 
 
 STATES, OBS = [np.zeros((3, 1)), np.ones((3, 1))], [[], []]
 
 
 def test_plan_mode_without_the_entry_points_raises_before_any_library_call():
-    f = _bare(_NoCalls(True, False), [_member(), _member()])
+    f = bare_fleet(_binding(True, False), [_member(), _member()])
     with pytest.raises(RuntimeError, match="plan"):
         f.control(STATES, 2.0, OBS, peers="plan")
     with pytest.raises(RuntimeError, match="plan"):
@@ -150,7 +132,7 @@ def test_plan_mode_without_the_entry_points_raises_before_any_library_call():
 
 @pytest.mark.parametrize("value", ["other", "Plan", "", 2.5, [True], ("plan",)])
 def test_any_other_value_of_peers_is_a_value_error(value):
-    f = _bare(_NoCalls(), [_member(), _member()])
+    f = bare_fleet(_binding(), [_member(), _member()])
     with pytest.raises(ValueError):
         f.control(STATES, 2.0, OBS, peers=value)
     with pytest.raises(ValueError):
@@ -160,13 +142,13 @@ def test_any_other_value_of_peers_is_a_value_error(value):
 @pytest.mark.parametrize("bad", [_member(order=False), _member(cone="norm2"), _member(rda_obstacle=True), _member(tracks=False)],
                          ids=["obstacle_order=False", "norm2", "rda_obstacle", "not-tracked"])
 def test_plan_mode_has_the_refusals_of_the_constant_velocity_mode(bad):
-    f = _bare(_NoCalls(), [_member(), bad])
+    f = bare_fleet(_binding(), [_member(), bad])
     with pytest.raises(RuntimeError):
         f.control(STATES, 2.0, OBS, peers="plan")
     with pytest.raises(RuntimeError):
         f.rollout(STATES, 2.0, 5, obstacle_lists=OBS, peers="plan")
     with pytest.raises(ValueError):
-        _bare(_NoCalls(), [_member(), _member()]).rollout(STATES, 2.0, 5, peers="plan")          # no obstacle_lists= and no such scenes resident
+        bare_fleet(_binding(), [_member(), _member()]).rollout(STATES, 2.0, 5, peers="plan")          # no obstacle_lists= and no such scenes resident
 
 
 class _StubApi:

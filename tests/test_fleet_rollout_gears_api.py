@@ -3,51 +3,30 @@ scenarios.gear_path): what can be checked without a GPU - the entry points are d
 a null fleet or handle is an argument error, the Python interface refuses what it does not support before any library call, and gear_path makes the
 pieces MPC.split_path is expected to cut."""
 import ctypes as C
-import os
-import re
-import types
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from capi_lib import RDA_ERR_ARG, Binding, bare_fleet, declared, header_argtypes, integration_rows, lib, member
+
 NAMES = ("rda_upload_path_pieces", "rda_fleet_rollout_gears", "rda_fleet_rollout_last_pieces")
-RDA_ERR_ARG = -1
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rda_hip.h")).read(), flags=re.S)
-
-
-def _lib():
-    from rda_planner_amd import _lib
-    return C.CDLL(_lib.build())
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_declared_exported_and_documented(name):
-    assert re.search(r"\bint\s+%s\s*\(" % name, _header()), name
-    assert hasattr(_lib(), name), f"{name} declared in include/rda_hip.h but not exported"
-    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    row = [ln for ln in doc.splitlines() if "`%s`" % name in ln]
+    assert declared(name), name
+    assert hasattr(lib(), name), f"{name} declared in include/rda_hip.h but not exported"
+    row = integration_rows(name, table=False)
     assert row and any("mpc.py:166-187" in ln or "mpc.py:232-249" in ln for ln in row)      # mapped to the reference's piece rule / split_path
-
-
-def _header_argtypes(name):
-    from rda_planner_amd._capi import Info, c_double_p, c_int_p
-    kinds = {"rda_fleet *": C.c_void_p, "rda_handle *": C.c_void_p, "const int32_t *": c_int_p, "int32_t *": c_int_p, "const double *": c_double_p,
-             "double *": c_double_p, "double": C.c_double, "int": C.c_int, "rda_info *": C.POINTER(Info)}
-    args = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, _header(), re.S).group(1)
-    return [kinds[" ".join(re.match(r"\s*(.*?)(\w+)\s*$", a.strip(), re.S).group(1).split())] for a in args.split(",")]
 
 
 @pytest.mark.parametrize("name,nargs", [("rda_upload_path_pieces", 5), ("rda_fleet_rollout_gears", 19), ("rda_fleet_rollout_last_pieces", 3)])
 def test_ctypes_prototype_follows_the_header(name, nargs):
     from rda_planner_amd._capi import CApi, PROTOTYPES, signature
-    api = CApi(_lib(), "rda")
+    api = CApi(lib(), "rda")
     assert api.has_fleet_rollout_gears
     fn = getattr(api, name[len("rda_"):])
-    want = _header_argtypes(name)
+    want = header_argtypes(name)
     assert len(want) == nargs
     assert list(fn.argtypes) == want and fn.restype is C.c_int
     assert signature(PROTOTYPES[name[len("rda_"):]]) == (C.c_int, want)
@@ -55,7 +34,7 @@ def test_ctypes_prototype_follows_the_header(name, nargs):
 
 def test_null_fleet_or_handle_is_an_argument_error_without_a_device():
     from rda_planner_amd._capi import CApi, Info, dptr, iptr
-    api = CApi(_lib(), "rda")
+    api = CApi(lib(), "rda")
     K, B = 2, 1
     st, sp, cur, p0 = np.zeros((B, 3)), np.ones(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
     sl, ul, il, arr, info = np.zeros((K + 1, B, 3)), np.zeros((K, B, 2)), np.zeros((K, B), np.int32), np.zeros(B, np.int32), (Info * (K * B))()
@@ -66,22 +45,9 @@ def test_null_fleet_or_handle_is_an_argument_error_without_a_device():
     assert api.upload_path_pieces(None, 1, iptr(np.ones(1, np.int32)), dptr(np.ones(1)), dptr(np.zeros((1, 3)))) == RDA_ERR_ARG
 
 
-class _NoCalls:
-    """stands for the library binding: any use of it is an error"""
-    def __getattr__(self, name):
-        raise AssertionError(f"library touched: {name}")
-
-
 def test_python_refusals_before_any_library_call():
-    from rda_planner_amd.fleet import Fleet
-
-    def member(reverse, tracks):
-        return types.SimpleNamespace(enable_reverse=reverse, _tracks=lambda kw: tracks and set(kw) <= {"threshold", "ind_range"}, goal_index_threshold=1,
-                                     receding=5)
-    f = Fleet.__new__(Fleet)                           # no device: a binding that fails on any use
-    f.api, f._handle = _NoCalls(), None
+    f = bare_fleet(Binding(), [member(), member(reverse=True)])         # no device: a binding that fails on any use
     states = [np.zeros((3, 1)), np.zeros((3, 1))]
-    f.members = [member(False, True), member(True, True)]
     sensor = dict(number=8, angle_min=-1.0, angle_max=1.0, range_min=0.0, range_max=5.0)
     with pytest.raises(ValueError):
         f.rollout(states, 3.0, 5, gears=True, peers=True)
@@ -91,10 +57,10 @@ def test_python_refusals_before_any_library_call():
         f.rollout(states, 3.0, 5, gears=True, lidar=[sensor, sensor])
     with pytest.raises(ValueError):
         f.rollout(states, 3.0, 5, gears=True, scans=[{}, {}])
-    f.members = [member(True, True), member(True, False)]
+    f.members = [member(reverse=True), member(reverse=True, tracks=False)]
     with pytest.raises(RuntimeError):
         f.rollout(states, 3.0, 5, gears=True)          # a member that does not track on the device
-    f.members = [member(False, True), member(True, True)]
+    f.members = [member(), member(reverse=True)]
     with pytest.raises(RuntimeError):
         f.rollout(states, 3.0, 5)                      # without gears=True a reverse member is refused as before
     with pytest.raises(RuntimeError):

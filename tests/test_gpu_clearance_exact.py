@@ -23,18 +23,14 @@ import clear_grid as grid
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr, iptr
 
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
 T, N, E, ITER, DT = 8, 4, 8, 2, 0.1
 RDA_ERR_UNSUPPORTED = -2
 TOL = grid.DEVICE_BOUND
 REACH = 2.5              # no robot of the grid reaches further from its origin (the car's corner: 2.44 m)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 class Fleet:

@@ -10,13 +10,9 @@ import helpers as hp
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 def _members(B, T, N, iter_num=3, per_ego_robot=False):

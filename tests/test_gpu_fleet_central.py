@@ -11,16 +11,12 @@ import helpers as hp
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
 RDA_ERR_UNSUPPORTED = -2
 ROWS, CP_SMALL, CP_LARGE, FIN = "k_lammuz_ip_fleet", "k_lammuz_cp_fleet_small", "k_lammuz_cp_fleet_large", "k_lmz_finalize_fleet"
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 def _fleet(hip, memb):

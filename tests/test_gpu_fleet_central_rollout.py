@@ -5,24 +5,18 @@ state, a tick of a rollout computes bit for bit what its host-driven tick comput
 import numpy as np
 import pytest
 
-from rda_planner_amd import scenarios as sc
-
 import test_gpu_fleet_rollout as static
-import test_gpu_fleet_rollout_moving as moving
 import test_gpu_fleet_rollout_lidar as lidar
+import test_gpu_fleet_rollout_moving as moving
+from fleet_twin_lib import RDA_ERR_UNSUPPORTED, compare_ticks
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from lidar_world_lib import flatten, sensor_c
+from rda_planner_amd import scenarios as sc
 
 pytestmark = pytest.mark.gpu
 
 MU, K = 1e-3, 5
-RDA_ERR_UNSUPPORTED = -2
 ROWS = "k_lammuz_ip_fleet"
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 def _kernel(hip, twin):
@@ -69,10 +63,7 @@ def test_moving_rollout_ticks_equal_upload_and_tracked_step(hip, resort):
     rc, logs = a.rollout(K, resort)
     assert rc == 0, rc
     ticks = b.forced(logs, K, b.base, b.cur0, True)
-    assert moving.compare_ticks(logs, ticks, K) == 2 * K
-    B = len(which)
-    for k, (u, s, info, mi, eh) in enumerate(ticks):
-        assert logs["info"][k * B:(k + 1) * B] == info, k       # the whole rda_info (compare_ticks looks at the iteration counts)
+    assert compare_ticks(logs, ticks, K, ("controls", "index", "iters", "info")) == 2 * K       # ... and the whole rda_info
     for sa, sb in zip(a.slots(), b.slots()):
         assert sa[3] == sb[3]
         for x, y in zip(sa[:3], sb[:3]):
@@ -110,7 +101,7 @@ def test_lidar_rollout_ticks_equal_raycast_upload_and_tracked_step(hip, monkeypa
     monkeypatch.setattr(lidar, "EPS", 1.0)                      # (the twin's host tick reads that module's constants)
     monkeypatch.setattr(lidar, "MIN_SAMPLES", 4)
     ticks = b.forced(logs, K, b.base, lambda k: lidar.DT * k, b.cur0, True)
-    assert lidar.compare_ticks(logs, ticks, K) == 2 * K
+    assert compare_ticks(logs, ticks, K, lidar.TICK) == 2 * K
     print("boxes per tick:", logs["boxes"].T.tolist())
     assert (logs["boxes"] > 0).any()                            # the sensor saw something: the row-parallel kernel ran
     last, names = logs["boxes"][K - 1], _kernel(hip, a).split("+")      # the members as the last tick staged them: each box count chose its member's form

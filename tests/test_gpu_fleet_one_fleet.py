@@ -14,11 +14,11 @@ Shapes and helpers are those of tests/test_gpu_fleet_rollout_moving.py and tests
 import numpy as np
 import pytest
 
-from rda_planner_amd._capi import dptr, iptr
-
+from fleet_twin_lib import DT, N, T, advanced, solver
 from lidar_world_lib import SENSORS, sensor_c
+from rda_planner_amd._capi import dptr, iptr
 from test_gpu_fleet_rollout_lidar import Twin as LidarTwin
-from test_gpu_fleet_rollout_moving import DT, N, T, Twin, advanced, solver
+from test_gpu_fleet_rollout_moving import Twin
 
 pytestmark = pytest.mark.gpu
 

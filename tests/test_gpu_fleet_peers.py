@@ -13,25 +13,19 @@ from math import pi
 import numpy as np
 import pytest
 
+from fleet_twin_lib import DT, DYN, E, ITER, MARGIN, N, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, T, FleetTwin, advanced, compare_ticks, info_tuple, same_logs
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
-from rda_planner_amd._capi import Info, dptr, iptr
+from rda_planner_amd._capi import dptr, iptr
 
 pytestmark = pytest.mark.gpu
 
-T, N, E, ITER, K, K2 = 8, 4, 4, 2, 12, 5
+K, K2 = 12, 5
 NOWN = 3
-DYN = ("acker", "diff", "omni")
 SIZE = ((4.6, 1.6), (1.6, 1.0), (2.4, 1.2))             # length, width: the footprints can be told apart
-DT, SPEED, MARGIN = 0.1, 3.0, 3
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
+SPEED = 3.0
 VEL = [(0.3, 0.0), (-0.2, 0.1), (0.0, 0.0)]
 TOL = 1e-9               # device geometry against its numpy specification (another maths library's sin / cos, a 2 x 2 solve, a few products at <= 100 m)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 def car(e):
@@ -46,46 +40,32 @@ def lane(e, nown=NOWN, edges=E):
     return path, own
 
 
-def info_tuple(i):
-    return (i.resi_dual, i.resi_pri, i.iters, i.su_status, i.su_ipm_iters, i.lmz_fail)
-
-
-class Twin:
+class Twin(FleetTwin):
     """a fleet of fresh handles (members `which`, their paths uploaded, no scene yet) and what a caller keeps beside it"""
     def __init__(self, hip, which=(0, 1, 2), nown=None, edges=E, **kw):
         from rda_planner_amd.rda_solver import RDA_solver
-        self.hip, self.B, self.which, self.edges = hip, len(which), which, edges
-        nown = [NOWN] * self.B if nown is None else nown
-        self.svs, st, flat, self.plen = [], [], [], []
+        self.which, self.edges = which, edges
+        nown = [NOWN] * len(which) if nown is None else nown
+        svs, st, flat, self.plen = [], [], [], []
         for e, n in zip(which, nown):
             sv = RDA_solver(T, car(e), edges, N, iter_num=ITER, step_time=DT, time_print=False, **kw)
             pts, obs = lane(e, n, edges)
             P = np.ascontiguousarray(np.hstack(pts)[0:3, :].T, dtype=float)
             assert hip.upload_path(sv._be.handle, int(P.shape[0]), dptr(P)) == 0
-            self.svs.append(sv); st.append(P[0].copy()); self.plen.append(len(pts))
+            svs.append(sv); st.append(P[0].copy()); self.plen.append(len(pts))
             flat.append(sv.flatten_scene(list(obs)) if n else (0, np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, edges, 2)), np.zeros((0, 2))))
+        self.make_fleet(hip, svs, SPEED)
         self.cars = [car(e) for e in which]
         self.states = np.ascontiguousarray(np.array(st))
         self.counts = np.array(nown, np.int32)
         self.kind, self.nvert = (np.ascontiguousarray(np.concatenate([f[j] for f in flat]), np.int32) for j in (1, 2))
         self.base, self.vel = (np.ascontiguousarray(np.concatenate([f[j] for f in flat]), float) for j in (3, 4))
         self.off = np.concatenate([[0], np.cumsum(self.counts)])
-        self.arr = (C.c_void_p * self.B)(*[s._be.handle for s in self.svs])
-        self.F = C.c_void_p()
-        assert hip.fleet_create(self.arr, self.B, C.byref(self.F)) == 0
-        self.cur0, self.nom0, self.speed, self.ctl0 = np.zeros(self.B, np.int32), np.zeros((self.B, 2, T)), np.full(self.B, SPEED), np.zeros((self.B, 2))
-
-    def close(self):
-        self.hip.fleet_destroy(self.F)
+        self.ctl0 = np.zeros((self.B, 2))
 
     def own_at(self, t, base=None):
         """the own geometry put forward by the rule of scene::k_move_fleet, base + vel * t (all own obstacles here are polygons)"""
-        base = self.base if base is None else base
-        full = base + self.vel[:, None, :] * t
-        mask = np.arange(self.edges)[None, :] < self.nvert[:, None]
-        out = base.copy()
-        out[mask] = full[mask]
-        return out
+        return advanced(self.kind, self.nvert, self.base if base is None else base, self.vel, t)[0]
 
     def upload_peers(self, states, controls, geom=None):
         geom = self.base if geom is None else geom
@@ -109,34 +89,8 @@ class Twin:
         return self.hip.fleet_upload_scenes(self.F, iptr(counts), iptr(kind), iptr(np.ascontiguousarray(nvert, np.int32)), dptr(geom), dptr(vel), dptr(rob),
                                             iptr(np.ones(self.B, np.int32)))
 
-    def slots(self):
-        out = []
-        for s in self.svs:
-            A, b, cone, nt = np.zeros((N, T + 1, self.edges, 2)), np.zeros((N, T + 1, self.edges)), np.zeros(N, np.int32), np.zeros(1, np.int32)
-            assert self.hip.get_obstacles(s._be.handle, dptr(A), dptr(b), iptr(cone), iptr(nt)) == 0
-            m = N * int(nt[0]) * self.edges
-            out.append((A.ravel()[:2 * m].copy(), b.ravel()[:m].copy(), cone.copy(), int(nt[0])))
-        return out
-
-    def staged(self, i):
-        src, used = (C.c_int32 * N)(), C.c_int32(0)
-        assert self.hip.lib.rda_debug_slot_src(self.svs[i]._be.handle, src, C.byref(used)) == 0
-        return sorted(src[:used.value])
-
-    def tick(self, st, cur, first):
-        """rda_fleet_step_tracked -> controls, states, infos, min_index, end_heading"""
-        B = self.B
-        st, cur = np.ascontiguousarray(st, float), np.ascontiguousarray(cur, np.int32)
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = self.hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                         None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh
-
     def _logs(self, k, clearance, peer):
-        B = self.B
-        return dict(states=np.zeros((k + 1, B, 3)), controls=np.zeros((k, B, 2)), index=np.zeros((k, B), np.int32), info=(Info * (k * B))(),
-                    arrived_at=np.full(B, -7, np.int32), clearance=np.full((k, B), -7.0) if clearance else None, peer=np.full((k, B), -7.0) if peer else None)
+        return self.logs(k, clearance=float if clearance else None, peer=float if peer else None)
 
     def rollout_peers(self, k, states=None, cur=None, nom_u="first", controls0=None, clearance=True, peer=True):
         out = self._logs(k, clearance, peer)
@@ -210,7 +164,7 @@ def test_host_driven_peers_tick_equals_a_plain_tick_on_the_same_rows(hip, kw):
             assert sa[3] == sb[3] == T + 1
             for x, y in zip(sa[:3], sb[:3]):
                 assert np.array_equal(x, y)
-        ra, rb = a.tick(states, cur, first), b.tick(states, cur, first)
+        ra, rb = a.step_tracked(states, cur, first), b.step_tracked(states, cur, first)
         for x, y in zip(ra, rb):
             assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y
         return ra
@@ -255,7 +209,7 @@ def run(hip):
         ticks = []
         for k in range(n):
             assert b.upload_peers(lg["states"][k], ctl0 if k == 0 else lg["controls"][k - 1], geom=b.own_at(DT * k, base)) == 0
-            ticks.append(b.tick(lg["states"][k], cur0 if k == 0 else lg["index"][k - 1], first and k == 0))
+            ticks.append(b.step_tracked(lg["states"][k], cur0 if k == 0 else lg["index"][k - 1], first and k == 0))
         return ticks
     base2 = b.own_at(DT * K)                            # the second rollout's base: the geometry the first one left
     out["ticks"] = forced(logs, K, b.base, b.cur0, b.ctl0, True)
@@ -270,21 +224,6 @@ def run(hip):
     out.update(own_clear=own_clear, own_at=[base2, b.own_at(DT * K2, base2)])
     a.close(); b.close(); c.close()
     return out
-
-
-def compare_ticks(logs, ticks):
-    arrived, B, live = logs["arrived_at"], len(logs["arrived_at"]), 0
-    for k, (u, s, info, mi, eh) in enumerate(ticks):
-        for i in range(B):
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {k} member {i}: |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  index {logs['index'][k, i]} / {mi[i]}  "
-                  f"iters {logs['info'][k * B + i][2]} / {info[i][2]}")
-            if arrived[i] < 0 or k < arrived[i]:
-                assert np.array_equal(logs["controls"][k, i], first), (k, i)
-                live += 1
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i][2] == info[i][2], (k, i)
-    return live
 
 
 def test_rollout_tick_equals_a_host_driven_peers_tick(run):
@@ -331,9 +270,7 @@ def test_a_fleet_of_one_has_no_peer_rows(hip):
     assert b.upload_rows([(b.base, b.vel)], b.states) == 0
     rc, lb = b.rollout_moving(5)
     assert rc == 0
-    for key in ("states", "controls", "index", "arrived_at", "clearance"):
-        assert np.array_equal(la[key], lb[key]), key
-    assert la["info"] == lb["info"]
+    same_logs(la, lb, ("states", "controls", "index", "arrived_at", "clearance"))
     got = np.zeros(1)
     assert hip.fleet_peer_clearance(a.F, dptr(a.states), dptr(got)) == 0 and got[0] == np.inf
     a.close(); b.close()
@@ -346,7 +283,7 @@ def test_a_member_without_own_obstacles(hip):
     assert g.shape[0] == 2 and np.abs(g - peer_rows(a, a.states, a.ctl0)[1][0]).max() <= TOL and np.array_equal(v, np.zeros((2, 2)))
     rc, logs = a.rollout_peers(3)
     assert rc == 0 and np.all(logs["clearance"][:, 1] == np.inf) and np.all(np.isfinite(logs["clearance"][:, [0, 2]])) and np.all(np.isfinite(logs["peer"]))
-    u, s, info, mi, eh = b.tick(b.states, b.cur0, True)
+    u, s, info, mi, eh = b.step_tracked(b.states, b.cur0, True)
     assert np.array_equal(logs["controls"][0], u[:, :, 0]) and np.array_equal(logs["index"][0], mi)
     a.close(); b.close()
 

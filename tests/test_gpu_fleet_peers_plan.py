@@ -14,19 +14,15 @@ import numpy as np
 import pytest
 
 import test_gpu_fleet_peers as base
+from fleet_twin_lib import DT, E, MARGIN, N, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, T, compare_ticks, info_tuple
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr, iptr
-from test_gpu_fleet_peers import CTL, DT, MARGIN, NOWN, START, TOL, E, K, K2, N, T, info_tuple
+from test_gpu_fleet_peers import CTL, NOWN, START, TOL, K, K2
 
 pytestmark = pytest.mark.gpu
 
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
+TICK = ("controls", "stands", "index", "info")          # what a rollout tick is compared for with a host-driven one; `stands`: the arrival rule
 
 
 def i32(a):
@@ -213,7 +209,7 @@ def test_host_driven_plan_tick_equals_a_plain_tick_on_the_same_slots(hip, kw):
             assert sa[3] == sb[3] and all(np.array_equal(x, y) for x, y in zip(sa[:3], sb[:3]))
         for sv in a.svs + b.svs:
             assert hip.debug_flush_supports(sv._be.handle) == 0
-        ra, rb = a.tick(states, cur, first), b.tick(states, cur, first)
+        ra, rb = a.step_tracked(states, cur, first), b.step_tracked(states, cur, first)
         for x, y in zip(ra, rb):
             assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y
         return ra
@@ -261,7 +257,7 @@ def run(hip):
         ticks, plans, valid = [], plans_first, valid_first
         for k in range(n):
             assert b.upload_plan(lg["states"][k], ctl_first if k == 0 else lg["controls"][k - 1], plans, valid, geom=b.own_at(DT * k, base_geom)) == 0
-            ticks.append(b.tick(lg["states"][k], cur_first if k == 0 else lg["index"][k - 1], first and k == 0))
+            ticks.append(b.step_tracked(lg["states"][k], cur_first if k == 0 else lg["index"][k - 1], first and k == 0))
             plans = ticks[-1][1]                                      # the out_s of this tick: the plans of the next
             valid = [int(lg["arrived_at"][j] < 0 or lg["arrived_at"][j] > k) for j in range(3)]      # valid while not arrived by the end of tick k
         return ticks, plans
@@ -281,23 +277,6 @@ def run(hip):
     return out
 
 
-def compare_ticks(logs, ticks, start):
-    arrived, live = logs["arrived_at"], 0
-    for k, (u, s, info, mi, eh) in enumerate(ticks):
-        for i in range(3):
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {start + k} member {i}: |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  index {logs['index'][k, i]} / {mi[i]}  "
-                  f"info {logs['info'][k * 3 + i]} / {info[i]}")
-            if arrived[i] < 0 or k < arrived[i]:
-                assert np.array_equal(logs["controls"][k, i], first), (k, i)
-                live += 1
-            else:
-                assert np.array_equal(logs["controls"][k, i], np.zeros(2)), (k, i)          # the arrival rule: it stands
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * 3 + i] == info[i], (k, i)
-    return live
-
-
 def test_rollout_tick_equals_a_host_driven_plan_tick(run):
     """every tick of both rollouts against rda_fleet_upload_scenes_peers_plan (the logged states, the controls of the tick before, the out_s of the tick
     before with validity = not arrived, own geometry base + vel * (dt * k)) + rda_fleet_step_tracked: first control, min_index and rda_info bit for bit;
@@ -306,7 +285,7 @@ def test_rollout_tick_equals_a_host_driven_plan_tick(run):
     arr = logs["arrived_at"]
     print("arrived_at", arr, logs2["arrived_at"])
     assert 0 < arr[1] < K - 1 and arr[0] == -1 and arr[2] == -1
-    live = compare_ticks(logs, run["ticks"], 0) + compare_ticks(logs2, run["ticks2"], K)
+    live = compare_ticks(logs, run["ticks"], what=TICK) + compare_ticks(logs2, run["ticks2"], what=TICK, start=K)
     assert live == 2 * (K + K2) + arr[1]
     assert np.abs(logs["controls"][:, [0, 2], 0]).max() > 1.0                                # the others drive
     assert np.array_equal(run["plans1"], run["end_plans"])                                   # rda_fleet_rollout_last_plan: the out_s of the last tick
@@ -385,7 +364,7 @@ def test_refused_allocation_leaves_scenes_and_memory(hip):
 def test_constant_velocity_mode_after_a_plan_tick(hip):
     a, c = Twin(hip), Twin(hip)
     assert a.upload_plan(START, CTL, PLANS, [1, 1, 1]) == 0
-    u, s, info, mi, eh = a.tick(START, a.cur0, True)
+    u, s, info, mi, eh = a.step_tracked(START, a.cur0, True)
     st2 = np.array([sc.kinematic_step(START[i].reshape(3, 1), u[i, :, 0:1], a.cars[i], DT).ravel() for i in range(3)])
     ctl2 = np.ascontiguousarray(u[:, :, 0])
     assert hip.fleet_scene_resort_peers(a.F, dptr(st2), dptr(ctl2)) == 0

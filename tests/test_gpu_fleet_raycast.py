@@ -17,8 +17,8 @@ import pytest
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr, iptr
 
+from fleet_twin_lib import solver
 from lidar_world_lib import SENSORS, WE, flatten, lane, numpy_scan, sensor_c
-from test_gpu_fleet_rollout_moving import solver
 
 pytestmark = pytest.mark.gpu
 
@@ -216,7 +216,7 @@ def test_python_raycast_feeds_control(hip):
     """Fleet.upload_worlds / Fleet.raycast: the scan dicts of World.get_lidar_scan, taken by Fleet.control(scans=) as they are"""
     from rda_planner_amd.fleet import Fleet
     from rda_planner_amd.mpc import MPC
-    from test_gpu_fleet_rollout_moving import DT, E, ITER, MARGIN, N, SPEED, T, car
+    from fleet_twin_lib import DT, E, ITER, MARGIN, N, SPEED, T, car
     ms, worlds, states = [], [], []
     for e in range(3):
         path, scene = lane(e)

@@ -10,30 +10,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fleet_twin_lib as L
+from fleet_twin_lib import DT, DYN, E, ITER, MARGIN, N, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, SPEED, T, FleetTwin, car, compare_ticks, info_tuple, same_logs
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
 pytestmark = pytest.mark.gpu
 
-T, N, E, ITER, K = 8, 4, 4, 2, 30
-DYN = ("acker", "diff", "omni")
+K = 30
 LENGTH = (30.0, 4.0, 30.0)             # metres of path: member 1 arrives during the run
-DT, SPEED, MARGIN = 0.1, 4.0, 3
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
-
-
-def info_tuple(i):
-    return (i.resi_dual, i.resi_pri, i.iters, i.su_status, i.su_ipm_iters, i.lmz_fail)
-
-
-def car(e):
-    return sc.rectangle_robot(dynamics=DYN[e], wheelbase=3.0 if DYN[e] == "acker" else 0)
+LOGS = ("states", "controls", "index", "arrived_at")
 
 
 def lane(e):
@@ -43,46 +30,28 @@ def lane(e):
     return path, scene
 
 
+def moving_lane(e):
+    pts, _ = lane(e)
+    y = np.ascontiguousarray(pts[0], float).ravel()[1]
+    return pts, [sc.regular_polygon(7.0 + 2.5 * j, y + 2.6, 4, 0.8, 0.0, velocity=(0.5, 0.0)) for j in range(7)]
+
+
 def solver(hip, e, path=True, scene=True, moving=False, **kw):
     """a fresh handle of member e: its path uploaded, its raw scene resident (sorted about the start)"""
-    from rda_planner_amd.rda_solver import RDA_solver
-    sv = RDA_solver(T, car(e), E, N, iter_num=ITER, step_time=DT, time_print=False, **kw)
-    pts, obs = lane(e)
-    st = np.ascontiguousarray(pts[0], float).ravel()[0:3].copy()
-    if path:
-        P = np.ascontiguousarray(np.hstack(pts)[0:3, :].T, dtype=float)
-        assert hip.upload_path(sv._be.handle, int(P.shape[0]), dptr(P)) == 0
-    if scene:
-        if moving:
-            obs = [sc.regular_polygon(7.0 + 2.5 * j, st[1] + 2.6, 4, 0.8, 0.0, velocity=(0.5, 0.0)) for j in range(7)]
-        n, kind, nvert, geom, vel = sv.flatten_scene(list(obs))
-        kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
-        geom, vel = np.ascontiguousarray(geom, float), np.ascontiguousarray(vel, float)
-        assert hip.upload_scene(sv._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(st), 1, None) == 0
-    return sv, st, len(pts)
+    return L.solver(hip, e, path=path, scene=scene, lane=moving_lane if moving else lane, **kw)[:3]
 
 
-class Twin:
-    """a fleet of fresh handles (members `which`) and what a caller keeps beside it"""
+class Twin(FleetTwin):
+    """a fleet of fresh handles (members `which`) with their raw scenes resident"""
     def __init__(self, hip, which=(0, 1, 2), svs=None):
-        self.hip, self.B = hip, len(which)
         made = svs if svs is not None else [solver(hip, e) for e in which]
-        self.svs = [m[0] for m in made]
+        self.make_fleet(hip, [m[0] for m in made])
         self.states = np.ascontiguousarray(np.array([m[1] for m in made]))
         self.plen = [m[2] for m in made]
-        self.arr = (C.c_void_p * self.B)(*[s._be.handle for s in self.svs])
-        self.F = C.c_void_p()
-        assert hip.fleet_create(self.arr, self.B, C.byref(self.F)) == 0
-        self.cur0, self.nom0, self.speed = np.zeros(self.B, np.int32), np.zeros((self.B, 2, T)), np.full(self.B, SPEED)
-
-    def close(self):
-        self.hip.fleet_destroy(self.F)
 
     def rollout(self, k, resort, cur=None, nom_u="first", **over):
         """rda_fleet_rollout -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((k + 1 if k > 0 else 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32))
+        out = self.logs(k)
         a = dict(states=self.states, ref_speed=self.speed, cur_index=self.cur0 if cur is None else cur, threshold=0.1,
                  ind_range=10, goal_margin=MARGIN, nom_u=self.nom0 if isinstance(nom_u, str) else nom_u, states_log=out["states"],
                  u_log=out["controls"], index_log=out["index"], info_log=out["info"], arrived_at=out["arrived_at"])
@@ -95,25 +64,14 @@ class Twin:
 
     def host_tick(self, st, cur, resort, first):
         """one host-driven tick: (re-sort,) rda_fleet_step_tracked -> controls, states, infos, min_index, end_heading"""
-        B, hip = self.B, self.hip
-        st, cur = np.ascontiguousarray(st, float), np.ascontiguousarray(cur, np.int32)
+        st = np.ascontiguousarray(st, float)
         if resort:
-            assert hip.fleet_scene_resort(self.F, dptr(st), 3) == 0
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                    None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh
+            assert self.hip.fleet_scene_resort(self.F, dptr(st), 3) == 0
+        return self.step_tracked(st, cur, first)
 
     def forced(self, logs, n, resort):
         """n host-driven ticks fed with the logged states and indices of a rollout"""
         return [self.host_tick(logs["states"][k], self.cur0 if k == 0 else logs["index"][k - 1], resort, k == 0) for k in range(n)]
-
-
-def same_logs(a, b):
-    for key in ("states", "controls", "index", "arrived_at"):
-        assert np.array_equal(a[key], b[key]), key
-    assert a["info"] == b["info"]
 
 
 @pytest.fixture(scope="module", params=[1, 0], ids=["resort", "no-resort"])
@@ -131,20 +89,8 @@ def run(hip, request):
 def test_teacher_forced_twin_bit_for_bit(run):
     """every tick of the rollout against the host-driven tick from the same logged state: first control (before the arrival: afterwards the applied control
     is zero), min_index and the executed ADMM iterations - the same kernels on the same inputs, so equality and nothing else"""
-    logs, arrived = run["logs"], run["logs"]["arrived_at"]
-    B = len(arrived)
-    moved = 0
-    for k, (u, s, info, mi, eh) in enumerate(run["ticks"]):
-        for i in range(B):
-            live = arrived[i] < 0 or k < arrived[i]
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {k} member {i}: |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  index {logs['index'][k, i]} / {mi[i]}  "
-                  f"iters {logs['info'][k * B + i][2]} / {info[i][2]}")
-            if live:
-                assert np.array_equal(logs["controls"][k, i], first), (k, i)
-                moved += 1
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i][2] == info[i][2], (k, i)
+    logs = run["logs"]
+    moved = compare_ticks(logs, run["ticks"], K)
     assert moved > 2 * K and np.abs(logs["controls"][:, 0, 0]).max() > 1.0        # the members drive
     if run["resort"]:
         assert logs["index"][-1, 0] > 60                                          # ... far enough for the nearest four polygons to change
@@ -237,7 +183,7 @@ def test_refusals_queue_and_change_nothing(hip):
     rc, lb = b.rollout(2, 1)
     assert rc == 0
     lb["info"] = la["info"]
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     a.close(); b.close()
     # members that cannot be rolled out (fleets of their own)
     def refused(code, resort, then=None, **kw):
@@ -264,7 +210,7 @@ def test_refusals_queue_and_change_nothing(hip):
     assert np.array_equal(u, u2)
     (rc1, l1), (rc2, l2) = f.rollout(2, 1, nom_u=None), g.rollout(2, 1, nom_u=None)
     assert rc1 == 0 and rc2 == 0
-    same_logs(l1, l2)
+    same_logs(l1, l2, LOGS)
     f.close(); g.close()
 
 
@@ -290,7 +236,7 @@ def test_refused_allocations_change_nothing(hip):
         assert rc == 0 and n - 1 == (20 if k == 2 else 2), (k, n)
         rc, lb = b.rollout(k, 1, nom_u="first" if k == 2 else None)
         assert rc == 0
-        same_logs(la, lb)
+        same_logs(la, lb, LOGS)
     a.close(); b.close()
 
 

@@ -15,31 +15,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from fleet_twin_lib import DT, DYN, E, ITER, N, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, T, FleetTwin, advanced, car, compare_ticks, info_tuple, same_logs
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
 pytestmark = pytest.mark.gpu
 
-T, N, E, ITER, K = 8, 4, 4, 2, 45
+K = 45
 NOBS = 5
-DYN = ("acker", "diff", "omni")
-DT, SPEED, MARGIN = 0.1, 3.0, 1
+SPEED, MARGIN = 3.0, 1
 SLANT = 0.3
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
-
-
-def info_tuple(i):
-    return (i.resi_dual, i.resi_pri, i.iters, i.su_status, i.su_ipm_iters, i.lmz_fail)
-
-
-def car(e):
-    return sc.rectangle_robot(dynamics=DYN[e], wheelbase=3.0 if DYN[e] == "acker" else 0)
+LOGS = ("states", "controls", "index", "arrived_at", "piece")
 
 
 def rows(points):
@@ -72,15 +59,6 @@ def obstacles(e, moving=False):
     return [sc.regular_polygon(*at(e, 1.5 * j - 1.0, 2.6 if j % 2 else -2.6), 3 + j % 2, 0.8, 0.3 * j, velocity=vel(j)) for j in range(NOBS)]
 
 
-def advanced(kind, nvert, base, vel, t):
-    """the rule of scene::k_move_fleet in numpy (tests/test_gpu_fleet_rollout_moving.py): base + vel * t on a polygon's nvert vertices"""
-    full = base + vel[:, None, :] * t
-    mask = np.arange(base.shape[1])[None, :] < nvert[:, None]
-    out = base.copy()
-    out[mask] = full[mask]
-    return out
-
-
 def solver(hip, e, moving=False, plain=False, upload=True, **kw):
     """a fresh handle of member e: its pieces resident (rda_upload_path_pieces; NOT rda_upload_path), its raw scene resident, sorted about the start"""
     from rda_planner_amd.rda_solver import RDA_solver
@@ -98,36 +76,27 @@ def solver(hip, e, moving=False, plain=False, upload=True, **kw):
     return sv, st, pc, (kind, nvert, geom, vel)
 
 
-class Twin:
-    """a fleet of fresh handles (members `which`) and what a caller keeps beside it"""
+class Twin(FleetTwin):
+    """a fleet of fresh handles (members `which`) with their pieces and raw scenes resident"""
     def __init__(self, hip, which=(0, 1, 2), moving=False, plain=False, svs=None):
-        self.hip, self.B, self.which = hip, len(which), which
+        self.which = which
         made = svs if svs is not None else [solver(hip, e, moving, plain) for e in which]
-        self.svs = [m[0] for m in made]
+        self.make_fleet(hip, [m[0] for m in made], SPEED)
+        self.zero = self.cur0
         self.states = np.ascontiguousarray(np.array([m[1] for m in made]))
         self.pieces = [m[2] for m in made]
         self.kind, self.nvert = (np.ascontiguousarray(np.concatenate([m[3][j] for m in made])) for j in (0, 1))
         self.base, self.vel = (np.ascontiguousarray(np.concatenate([m[3][j] for m in made])) for j in (2, 3))
-        self.arr = (C.c_void_p * self.B)(*[s._be.handle for s in self.svs])
-        self.F = C.c_void_p()
-        assert hip.fleet_create(self.arr, self.B, C.byref(self.F)) == 0
-        self.zero, self.nom0, self.speed = np.zeros(self.B, np.int32), np.zeros((self.B, 2, T)), np.full(self.B, SPEED)
         self.seen = set()                                                          # (member, piece) this fleet has uploaded with rda_upload_path
         self.heads = [[float(p[-1, 2]) for _, p in pc] for pc in self.pieces]      # the heading of every piece's last waypoint as host-driven ticks leave it
         self.piece = [0] * self.B                                                  # ... and the piece in force after the last of them
-
-    def close(self):
-        self.hip.fleet_destroy(self.F)
 
     def plen(self, i, p):
         return len(self.pieces[i][p][1])
 
     def rollout(self, k, resort, moving=0, clearance=False, piece0="zero", cur=None, nom_u="first", **over):
         """rda_fleet_rollout_gears -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((max(k, 0) + 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32), piece=np.full((max(k, 1), B), -7, np.int32),
-                   clearance=np.full((max(k, 1), B), -7.0) if clearance else None)
+        out = self.logs(k, piece=np.int32, clearance=float if clearance else None)
         a = dict(states=self.states, ref_speed=self.speed, piece0=self.zero if isinstance(piece0, str) else piece0, cur_index=self.zero if cur is None else cur,
                  threshold=0.1, ind_range=10, goal_margin=MARGIN, nom_u=self.nom0 if isinstance(nom_u, str) else nom_u, states_log=out["states"],
                  u_log=out["controls"], index_log=out["index"], info_log=out["info"], arrived_at=out["arrived_at"], piece_log=out["piece"])
@@ -140,9 +109,7 @@ class Twin:
 
     def plain_rollout(self, k, resort, moving):
         """rda_fleet_rollout / rda_fleet_rollout_moving (with the clearance log) on the members' rda_upload_path paths"""
-        B = self.B
-        out = dict(states=np.zeros((k + 1, B, 3)), controls=np.zeros((k, B, 2)), index=np.zeros((k, B), np.int32), info=(Info * (k * B))(),
-                   arrived_at=np.full(B, -7, np.int32), clearance=np.full((k, B), -7.0) if moving else None)
+        out = self.logs(k, clearance=float if moving else None)
         args = (self.F, k, dptr(self.states), dptr(self.speed), iptr(self.zero), 0.1, 10, MARGIN, resort, dptr(self.nom0), dptr(out["states"]),
                 dptr(out["controls"]), iptr(out["index"]), out["info"], iptr(out["arrived_at"]))
         rc = self.hip.fleet_rollout_moving(*args, dptr(out["clearance"])) if moving else self.hip.fleet_rollout(*args)
@@ -177,15 +144,12 @@ class Twin:
                                            dptr(self.vel), dptr(np.ascontiguousarray(st[:, 0:2])), iptr(np.full(B, 1, np.int32))) == 0
         elif resort:
             assert hip.fleet_scene_resort(self.F, dptr(st), 3) == 0
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = hip.fleet_step_tracked(self.F, dptr(st), dptr(speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                    None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
+        u, s, info, mi, eh = self.step_tracked(st, cur, first, speed)
         for i in range(B):
             p = int(piece[i])
             self.heads[i][p] = float(eh[i])
             self.piece[i] = p + 1 if mi[i] >= self.plen(i, p) - MARGIN and p + 1 < len(self.pieces[i]) else p
-        return u, s, [info_tuple(i) for i in info], mi, eh
+        return u, s, info, mi, eh
 
     def forced(self, logs, n, resort, moving=False, cur0=None, first=True, base=None):
         """n host-driven ticks fed with the logged states, pieces and indices of a rollout (moving: and the numpy-advanced geometry of every tick, from
@@ -193,7 +157,7 @@ class Twin:
         out = []
         for k in range(n):
             cur = np.array(self.zero if cur0 is None else cur0) if k == 0 else np.where(logs["piece"][k] != logs["piece"][k - 1], 0, logs["index"][k - 1])
-            geom = advanced(self.kind, self.nvert, self.base if base is None else base, self.vel, DT * k) if moving else None
+            geom = advanced(self.kind, self.nvert, self.base if base is None else base, self.vel, DT * k)[0] if moving else None
             out.append(self.host_tick(logs["states"][k], logs["piece"][k], cur, first and k == 0, resort, geom))
         return out
 
@@ -201,12 +165,6 @@ class Twin:
 def next_inputs(logs, piece_after):
     """the cur_index of the tick behind a rollout, as MPC._end leaves it: 0 for a member whose last tick changed its piece, else the last min_index"""
     return np.ascontiguousarray(np.where(piece_after != logs["piece"][-1], 0, logs["index"][-1]).astype(np.int32))
-
-
-def same_logs(a, b, keys=("states", "controls", "index", "arrived_at", "piece")):
-    for key in keys:
-        assert np.array_equal(a[key], b[key]), key
-    assert a["info"] == b["info"]
 
 
 CASES = {"resort": ((0, 1, 2), 1, 0), "no-resort": ((0, 1, 2), 0, 0), "moving": ((0, 1, 2), 1, 1), "B1": ((0,), 1, 0)}
@@ -229,35 +187,17 @@ def run(hip, request):
     for i in range(a.B):
         a.upload_piece(i, int(piece[i]), heads)
         a.seen.add((i, int(piece[i])))
-    geom = advanced(a.kind, a.nvert, a.base, a.vel, DT * K) if moving else None
+    geom = advanced(a.kind, a.nvert, a.base, a.vel, DT * K)[0] if moving else None
     out["cont_a"] = a.host_tick(logs["states"][K], piece, cur, False, resort, geom)
     out["cont_b"] = b.host_tick(logs["states"][K], piece, cur, False, resort, geom)
     a.close(); b.close()
     return out
 
 
-def live(arrived, i, k):
-    return arrived[i] < 0 or k < arrived[i]
-
-
 def same_as_forced(logs, ticks):
     """the ticks of a rollout against host-driven ticks from its logged states: for every live member the first control, min_index, the ADMM iterations
     and the whole rda_info, for equality -> the number of live (member, tick) pairs"""
-    arrived = logs["arrived_at"]
-    B, moved = len(arrived), 0
-    for k, (u, s, info, mi, eh) in enumerate(ticks):
-        for i in range(B):
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {k} member {i} piece {logs['piece'][k, i]}: |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  index {logs['index'][k, i]} / "
-                  f"{mi[i]}  iters {logs['info'][k * B + i][2]} / {info[i][2]}")
-            if not live(arrived, i, k):
-                continue
-            moved += 1
-            assert np.array_equal(logs["controls"][k, i], first), (k, i)
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i][2] == info[i][2], (k, i)
-            assert logs["info"][k * B + i] == info[i], (k, i)
-    return moved
+    return compare_ticks(logs, ticks, what=("controls", "index", "iters", "info"), arrived_too=False)
 
 
 def test_teacher_forced_twin_bit_for_bit(run):
@@ -357,7 +297,7 @@ def test_second_rollout_continues_the_first(hip, run):
     if moving:
         b = Twin(hip, run["which"], moving)
         b.forced(l1, K1, run["resort"], True)
-        base2 = advanced(b.kind, b.nvert, b.base, b.vel, DT * K1)
+        base2 = advanced(b.kind, b.nvert, b.base, b.vel, DT * K1)[0]
         assert same_as_forced(l2, b.forced(l2, K - K1, run["resort"], True, cur0=next_inputs(l1, piece), first=False, base=base2)) > 0
         b.close()
         assert np.array_equal(l2["piece"][-1], long["piece"][-1])
@@ -417,7 +357,7 @@ def test_refusals_queue_and_change_nothing(hip):
     rc, lb = b.rollout(3, 1)
     assert rc == 0
     lb["info"] = la["info"]
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     a.close(); b.close()
     # a member without resident pieces (its rda_upload_path path does not count)
     f = Twin(hip, (0,), svs=[solver(hip, 0, upload=False)])
@@ -465,7 +405,7 @@ def test_refused_allocations_change_nothing(hip):
     assert rc == 0 and n - 1 == 32, n
     rc, lb = b.rollout(K, 1)
     assert rc == 0
-    same_logs(la, lb)                                                             # (all three pieces of member 0: the refused uploads changed nothing)
+    same_logs(la, lb, LOGS)                                                         # (all three pieces of member 0: the refused uploads changed nothing)
     a.close(); b.close()
 
 

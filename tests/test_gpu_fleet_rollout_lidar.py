@@ -14,38 +14,33 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from fleet_twin_lib import (DT, E, ITER, MARGIN, N, NOBS, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, SPEED, T, FleetTwin, advanced, car, compare_ticks,
+                            info_tuple, same_logs, solver)
+from lidar_world_lib import EPS, MIN_SAMPLES, SENSORS, WE, lane, numpy_scan, sensor_c
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
-
-from lidar_world_lib import EPS, MIN_SAMPLES, SENSORS, WE, flatten, lane, numpy_scan, sensor_c
-from test_gpu_fleet_rollout_moving import DT, E, ITER, MARGIN, N, NOBS, SPEED, T, advanced, car, info_tuple, solver
 
 pytestmark = pytest.mark.gpu
 
 K, K2 = 12, 5
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
+LOGS = ("states", "controls", "index", "arrived_at", "boxes", "clearance")
+TICK = ("boxes", "controls", "index", "info")          # what a rollout tick is compared for with a host-driven one
 
 
-class Twin:
+class Twin(FleetTwin):
     """a fleet of fresh handles of the three lane members (paths uploaded, nothing staged), the flattened worlds, and what a caller keeps beside it"""
     def __init__(self, hip, which=(0, 1, 2), world=True, **kw):
-        self.hip, self.B, self.which = hip, len(which), which
+        self.which = which
         made = [solver(hip, e, scene=False, **kw) for e in which]
-        self.svs = [m[0] for m in made]
+        self.make_fleet(hip, [m[0] for m in made])
         self.states = np.ascontiguousarray(np.array([m[1] for m in made]))
         self.plen = [m[2] for m in made]
         self.kind, self.nvert, self.base, self.vel = (np.ascontiguousarray(np.concatenate([m[3][j] for m in made])) for j in range(4))
         self.counts = np.full(self.B, NOBS, np.int32)
         self.sensors = sensor_c([SENSORS[e] for e in which])
         self.order = np.ones(self.B, np.int32)
-        self.F = C.c_void_p()
-        assert hip.fleet_create((C.c_void_p * self.B)(*[s._be.handle for s in self.svs]), self.B, C.byref(self.F)) == 0
-        self.cur0, self.nom0, self.speed = np.zeros(self.B, np.int32), np.zeros((self.B, 2, T)), np.full(self.B, SPEED)
         if world:
             self.upload_world(self.base)
-
-    def close(self):
-        self.hip.fleet_destroy(self.F)
 
     def upload_world(self, geom, vel=True):
         assert self.hip.fleet_upload_worlds(self.F, iptr(self.counts), WE, iptr(self.kind), iptr(self.nvert), dptr(np.ascontiguousarray(geom)),
@@ -58,10 +53,7 @@ class Twin:
 
     def rollout(self, k, moving, clearance=True, **over):
         """rda_fleet_rollout_lidar -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((max(k, 0) + 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32), boxes=np.full((max(k, 1), B), -7, np.int32),
-                   clearance=np.full((max(k, 1), B), -7.0) if clearance else None)
+        out = self.logs(k, boxes=np.int32, clearance=float if clearance else None)
         nb, lo, hi, rmin, rmax = self.sensors
         a = dict(states=self.states, ref_speed=self.speed, cur_index=self.cur0, threshold=0.1, ind_range=10, goal_margin=MARGIN, nom_u=self.nom0,
                  n_beams=nb, angle_min=lo, angle_max=hi, range_min=rmin, range_max=rmax, eps=EPS, min_samples=MIN_SAMPLES, order=self.order,
@@ -76,16 +68,6 @@ class Twin:
         out["info"] = [info_tuple(i) for i in out["info"]]
         return rc, out
 
-    def slots(self):
-        """rda_get_obstacles of every member: [(A, b, cone, nt)]"""
-        out = []
-        for s in self.svs:
-            A, b, cone, nt = np.zeros((N, T + 1, E, 2)), np.zeros((N, T + 1, E)), np.zeros(N, np.int32), np.zeros(1, np.int32)
-            assert self.hip.get_obstacles(s._be.handle, dptr(A), dptr(b), iptr(cone), iptr(nt)) == 0
-            m = N * int(nt[0]) * E
-            out.append((A.ravel()[:2 * m].copy(), b.ravel()[:m].copy(), cone.copy(), int(nt[0])))
-        return out
-
     def host_tick(self, st, cur, first, geom=None):
         """one host-driven tick: (the world uploaded at `geom`,) rda_fleet_raycast, rda_fleet_upload_scans of those ranges at that state,
         rda_fleet_step_tracked -> controls, states, infos, min_index, end_heading, box counts"""
@@ -98,22 +80,12 @@ class Twin:
         assert hip.fleet_raycast(self.F, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges)) == 0
         assert hip.fleet_upload_scans(self.F, iptr(nb), dptr(ranges), dptr(lo), dptr(hi), dptr(rmax), dptr(st), EPS, MIN_SAMPLES, iptr(self.order),
                                       iptr(boxes)) == 0
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                    None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh, boxes
+        return (*self.step_tracked(st, cur, first), boxes)
 
     def forced(self, logs, n, base, t_of, cur0, first):
         """n host-driven ticks fed with the logged states and indices of a rollout and the world of every tick, advanced in numpy"""
         return [self.host_tick(logs["states"][k], cur0 if k == 0 else logs["index"][k - 1], first and k == 0,
                                geom=advanced(self.kind, self.nvert, base, self.vel, t_of(k))[0]) for k in range(n)]
-
-
-def same_logs(a, b, keys=("states", "controls", "index", "arrived_at", "boxes", "clearance")):
-    for key in keys:
-        assert np.array_equal(a[key], b[key]), key
-    assert a["info"] == b["info"]
 
 
 @pytest.fixture(scope="module", params=[1, 0], ids=["moving", "standing"])
@@ -154,29 +126,11 @@ def test_world_moves_by_the_rule_or_stands(run):
     assert np.array_equal(run["world2"][2 * NOBS:], base[2 * NOBS:])                          # member 2's world stands
 
 
-def compare_ticks(logs, ticks, n):
-    arrived = logs["arrived_at"]
-    B, moved = len(arrived), 0
-    for k, (u, s, info, mi, eh, boxes) in enumerate(ticks):
-        for i in range(B):
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {k} member {i}: boxes {logs['boxes'][k, i]} / {boxes[i]}  |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  "
-                  f"index {logs['index'][k, i]} / {mi[i]}  iters {logs['info'][k * B + i][2]} / {info[i][2]}")
-            assert logs["boxes"][k, i] == boxes[i], (k, i)
-            if arrived[i] < 0 or k < arrived[i]:
-                assert np.array_equal(logs["controls"][k, i], first), (k, i)
-                moved += 1
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i] == info[i], (k, i)
-    assert len(ticks) == n
-    return moved
-
-
 def test_teacher_forced_twin_bit_for_bit(run):
     """every tick of both rollouts against rda_fleet_raycast + rda_fleet_upload_scans + rda_fleet_step_tracked from the same logged state on the same
     world: box count, first control, min_index, the whole rda_info; after the last tick of the first rollout the staged slots of every member"""
     logs = run["logs"]
-    moved = compare_ticks(logs, run["ticks"], K) + compare_ticks(run["logs2"], run["ticks2"], K2)
+    moved = compare_ticks(logs, run["ticks"], K, TICK) + compare_ticks(run["logs2"], run["ticks2"], K2, TICK)
     assert moved == 3 * (K + K2) and np.all(logs["arrived_at"] == -1)
     assert np.abs(logs["controls"][:, :, 0]).max() > 1.0 and np.all(logs["states"][K, :, 0] - logs["states"][0, :, 0] > 1.0)       # the members drive
     boxes = np.concatenate([logs["boxes"], run["logs2"]["boxes"]])
@@ -254,7 +208,7 @@ def test_refusals_queue_and_change_nothing(hip):
     assert rc == 0
     rc, lb = b.rollout(2, 1)
     assert rc == 0
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     assert np.array_equal(a.world(), b.world()) and not np.array_equal(a.world(), w0)
     a.close(); b.close()
     f = Twin(hip, world=False)                                          # no uploaded world
@@ -291,7 +245,7 @@ def test_refused_allocations_change_nothing(hip):
     assert rc == 0 and n - 1 > 30
     rc, lb = b.rollout(3, 1)
     assert rc == 0
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     a.close(); b.close()
 
 

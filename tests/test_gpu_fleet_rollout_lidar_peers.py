@@ -23,17 +23,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from rda_planner_amd import scenarios as sc
-from rda_planner_amd._capi import Info, dptr, iptr
-
+from fleet_twin_lib import DT, DYN, E, ITER, MARGIN, N, RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, SPEED, T, advanced, car, compare_ticks, info_tuple, lane, same_logs
 from lidar_world_lib import EPS, SENSORS, numpy_scan, sensor_c
-from test_gpu_fleet_rollout_lidar import Twin, same_logs
-from test_gpu_fleet_rollout_moving import DT, DYN, E, ITER, MARGIN, N, SPEED, T, advanced, car, info_tuple
+from rda_planner_amd import scenarios as sc
+from rda_planner_amd._capi import dptr, iptr
+from test_gpu_fleet_rollout_lidar import LOGS, TICK, Twin
 
 pytestmark = pytest.mark.gpu
 
 K, BEAMS, MINS = 4, 65, 4
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED = -1, -2
 
 
 class PTwin(Twin):
@@ -44,10 +42,7 @@ class PTwin(Twin):
 
     def rollout_peers(self, k, moving, clearance=True, peer=True, **over):
         """rda_fleet_rollout_lidar_peers -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((max(k, 0) + 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32), boxes=np.full((max(k, 1), B), -7, np.int32),
-                   clearance=np.full((max(k, 1), B), -7.0) if clearance else None, peer_clearance=np.full((max(k, 1), B), -7.0) if peer else None)
+        out = self.logs(k, boxes=np.int32, clearance=float if clearance else None, peer_clearance=float if peer else None)
         nb, lo, hi, rmin, rmax = self.sensors
         a = dict(states=self.states, ref_speed=self.speed, cur_index=self.cur0, threshold=0.1, ind_range=10, goal_margin=MARGIN, nom_u=self.nom0,
                  n_beams=nb, angle_min=lo, angle_max=hi, range_min=rmin, range_max=rmax, eps=EPS, min_samples=MINS, order=self.order,
@@ -74,17 +69,12 @@ class PTwin(Twin):
         assert hip.fleet_raycast_peers(self.F, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges)) == 0
         assert hip.fleet_upload_scans(self.F, iptr(nb), dptr(ranges), dptr(lo), dptr(hi), dptr(rmax), dptr(st), EPS, MINS, iptr(self.order),
                                       iptr(boxes)) == 0
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                    None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh, boxes
+        return (*self.step_tracked(st, cur, first), boxes)
 
     def renew(self):
         """a new fleet over the same member handles, its world uploaded again: none of the old fleet's tables is left"""
-        self.hip.fleet_destroy(self.F)
-        self.F = C.c_void_p()
-        assert self.hip.fleet_create((C.c_void_p * self.B)(*[s._be.handle for s in self.svs]), self.B, C.byref(self.F)) == 0
+        self.close()
+        self.make_fleet(self.hip, self.svs)
         self.upload_world(self.base)
 
 
@@ -126,12 +116,7 @@ def test_a_rollout_tick_equals_the_host_driven_tick(run):
                   f"index {logs['index'][k, i]} / {mi[i]}  iters {logs['info'][k * B + i][2]} / {info[i][2]}  "
                   f"|state - plant| = {np.abs(logs['states'][k + 1, i] - nxt).max():.3e}")
     print(f"largest |state - numpy plant| = {worst:.3e}")
-    for k, (u, s, info, mi, eh, boxes) in enumerate(run["ticks"]):
-        for i in range(B):
-            assert logs["boxes"][k, i] == boxes[i], (k, i)
-            assert np.array_equal(logs["controls"][k, i], np.array([u[i, 0, 0], u[i, 1, 0]])), (k, i)
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i] == info[i], (k, i)
+    assert compare_ticks(logs, run["ticks"], K, TICK) == K * B                                    # (nobody has arrived: every control is compared)
     u, s, info, mi, eh, boxes = run["ticks"][K - 1]
     last_u, last_s, last_eh = run["last"]
     assert np.array_equal(last_u, u) and np.array_equal(last_s, s) and np.array_equal(last_eh, eh)
@@ -143,7 +128,6 @@ def test_the_members_are_seen(run):
     """tick 0 on the CPU: the numpy scan with the peer footprints gives members 0 and 1 other boxes than the blind scan, and the rollout logged the
     seeing count"""
     from rda_planner_amd import lidar
-    from test_gpu_fleet_rollout_moving import lane
     logs = run["logs"]
     cars, st = [car(i) for i in range(3)], logs["states"][0]
     differ = 0
@@ -175,7 +159,7 @@ def test_peer_clearance_log(hip, run):
     two = PTwin(hip, (1,))                                                       # B = 1 sees what the blind rollout sees
     rc, l3 = two.rollout(2, 0, min_samples=MINS)
     assert rc == 0
-    same_logs(dict(l1, peer_clearance=None), l3)
+    same_logs(dict(l1, peer_clearance=None), l3, LOGS)
     two.close()
 
 
@@ -223,7 +207,7 @@ def test_the_blind_rollout_is_unchanged(hip):
     assert rc == 0
     rc, lc = c.rollout(3, 0, min_samples=MINS)                                                 # blind, after
     assert rc == 0
-    same_logs(la, lc)
+    same_logs(la, lc, LOGS)
     assert not np.array_equal(la["boxes"], lb["boxes"]) or not np.array_equal(la["controls"], lb["controls"])       # seeing is another rollout
     # on the fleet that saw: the blind rollout that continues, reusing what the seeing call left | on a fleet made anew over the same members
     d = PTwin(hip)
@@ -236,7 +220,7 @@ def test_the_blind_rollout_is_unchanged(hip):
     d.renew()
     rc, ld2 = d.rollout(2, 0, **cont)
     assert rc == 0
-    same_logs(lb2, ld2)
+    same_logs(lb2, ld2, LOGS)
     for t in (a, b, c, d):
         t.close()
 

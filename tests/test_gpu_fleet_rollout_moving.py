@@ -13,103 +13,33 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from fleet_twin_lib import (DT, E, ITER, MARGIN, N, NOBS, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, SPEED, T, FleetTwin, advanced, car, compare_ticks,
+                            info_tuple, lane, same_logs, solver)
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
 pytestmark = pytest.mark.gpu
 
-T, N, E, ITER, K, K2 = 8, 4, 4, 2, 12, 5
-NOBS = 7
-DYN = ("acker", "diff", "omni")
-DT, SPEED, MARGIN = 0.1, 4.0, 3
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, RDA_ERR_HIP = -1, -2, -3
-VEL0 = [(-0.5, 0.0), (-0.3, 0.0), (0.0, -0.4), (-0.4, 0.3), (0.3, -0.3), (-0.6, 0.0), (0.2, 0.4)]
-VEL1 = [(0.4, 0.0), (0.005, 0.0), (0.0, -0.3), (-0.5, 0.1), (0.0, 0.0), (0.3, 0.3), (-0.2, 0.0)]
+K, K2 = 12, 5
 
 
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
-
-
-def car(e):
-    return sc.rectangle_robot(dynamics=DYN[e], wheelbase=3.0 if DYN[e] == "acker" else 0)
-
-
-def lane(e):
-    """member e's path and its obstacles where they are at tick 0 (behind, beside and ahead of the start: the nearest four change within 5 m)"""
-    y = 20.0 + 8.0 * e
-    path = sc.line_path([4, y, 0], [34, y, 0], 0.1)
-    scene = []
-    for j in range(NOBS):
-        cx, cy = 1.0 + 2.5 * j, y + (2.6 if j % 2 else -2.6)
-        if e == 0:
-            scene.append(sc.regular_polygon(cx, cy, 3 + j % 2, 0.8, 0.3 * j, velocity=VEL0[j]))
-        elif e == 1:
-            scene.append(sc.circle(cx, cy, 0.6, velocity=VEL1[j]) if j % 2 == 0 else sc.regular_polygon(cx, cy, 3 + (j // 2) % 2, 0.8, 0.3 * j, velocity=VEL1[j]))
-        else:
-            scene.append(sc.regular_polygon(cx, cy, 3 + j % 2, 0.8, 0.3 * j))
-    return path, scene
-
-
-def advanced(kind, nvert, base, vel, t):
-    """the rule of scene::k_move_fleet in numpy: base + vel * t on a polygon's nvert vertices and on a circle's centre; every other entry is base's"""
-    full = base + vel[:, None, :] * t
-    v = np.arange(base.shape[1])[None, :]
-    mask = np.where(kind[:, None] == 1, v == 0, v < nvert[:, None])
-    out = base.copy()
-    out[mask] = full[mask]
-    return out, mask
-
-
-def solver(hip, e, order=1, path=True, scene=True, robot=None, **kw):
-    """a fresh handle of member e: its path uploaded, its raw scene resident -> (solver, start state, path length, (kind, nvert, geom, vel))"""
-    from rda_planner_amd.rda_solver import RDA_solver
-    sv = RDA_solver(T, robot if robot is not None else car(e), E, N, iter_num=ITER, step_time=DT, time_print=False, **kw)
-    pts, obs = lane(e)
-    st = np.ascontiguousarray(pts[0], float).ravel()[0:3].copy()
-    if path:
-        P = np.ascontiguousarray(np.hstack(pts)[0:3, :].T, dtype=float)
-        assert hip.upload_path(sv._be.handle, int(P.shape[0]), dptr(P)) == 0
-    n, kind, nvert, geom, vel = sv.flatten_scene(list(obs))
-    kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
-    geom, vel = np.ascontiguousarray(geom, float), np.ascontiguousarray(vel, float)
-    assert n == NOBS and geom.shape == (NOBS, E, 2)
-    if scene:
-        assert hip.upload_scene(sv._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(st), order, None) == 0
-    return sv, st, len(pts), (kind, nvert, geom, vel)
-
-
-def info_tuple(i):
-    return (i.resi_dual, i.resi_pri, i.iters, i.su_status, i.su_ipm_iters, i.lmz_fail)
-
-
-class Twin:
-    """a fleet of fresh handles (members `which`) and what a caller keeps beside it"""
+class Twin(FleetTwin):
+    """a fleet of fresh handles (members `which`) with their raw scenes resident"""
     def __init__(self, hip, which=(0, 1, 2), order=1, svs=None):
-        self.hip, self.B, self.which = hip, len(which), which
+        self.which = which
         made = svs if svs is not None else [solver(hip, e, order) for e in which]
-        self.svs = [m[0] for m in made]
+        self.make_fleet(hip, [m[0] for m in made])
         self.states = np.ascontiguousarray(np.array([m[1] for m in made]))
         self.plen = [m[2] for m in made]
         self.kind, self.nvert = (np.ascontiguousarray(np.concatenate([m[3][j] for m in made])) for j in (0, 1))
         self.base, self.vel = (np.ascontiguousarray(np.concatenate([m[3][j] for m in made])) for j in (2, 3))
         self.counts = np.full(self.B, NOBS, np.int32)
         self.order = np.full(self.B, order, np.int32)
-        self.arr = (C.c_void_p * self.B)(*[s._be.handle for s in self.svs])
-        self.F = C.c_void_p()
-        assert hip.fleet_create(self.arr, self.B, C.byref(self.F)) == 0
-        self.cur0, self.nom0, self.speed = np.zeros(self.B, np.int32), np.zeros((self.B, 2, T)), np.full(self.B, SPEED)
-
-    def close(self):
-        self.hip.fleet_destroy(self.F)
 
     def rollout(self, k, resort, clearance=True, **over):
         """rda_fleet_rollout_moving -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((max(k, 0) + 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32), clearance=np.full((max(k, 1), B), -7.0) if clearance else None)
+        out = self.logs(k, clearance=float if clearance else None)
         a = dict(states=self.states, ref_speed=self.speed, cur_index=self.cur0, threshold=0.1, ind_range=10, goal_margin=MARGIN, nom_u=self.nom0,
                  states_log=out["states"], u_log=out["controls"], index_log=out["index"], info_log=out["info"], arrived_at=out["arrived_at"])
         a.update(over)
@@ -128,21 +58,6 @@ class Twin:
             out.append(g)
         return np.concatenate(out)
 
-    def slots(self):
-        """rda_get_obstacles of every member: [(A, b, cone, nt)]"""
-        out = []
-        for s in self.svs:
-            A, b, cone, nt = np.zeros((N, T + 1, E, 2)), np.zeros((N, T + 1, E)), np.zeros(N, np.int32), np.zeros(1, np.int32)
-            assert self.hip.get_obstacles(s._be.handle, dptr(A), dptr(b), iptr(cone), iptr(nt)) == 0
-            m = N * int(nt[0]) * E
-            out.append((A.ravel()[:2 * m].copy(), b.ravel()[:m].copy(), cone.copy(), int(nt[0])))
-        return out
-
-    def staged(self, i):
-        src, used = (C.c_int32 * N)(), C.c_int32(0)
-        assert self.hip.lib.rda_debug_slot_src(self.svs[i]._be.handle, src, C.byref(used)) == 0
-        return sorted(src[:used.value])
-
     def host_tick(self, st, cur, first, geom=None, order=None, resort=False):
         """one host-driven tick: (the scenes uploaded at `geom` | re-sorted,) rda_fleet_step_tracked -> controls, states, infos, min_index, end_heading"""
         B, hip = self.B, self.hip
@@ -154,11 +69,7 @@ class Twin:
                                            dptr(rob), iptr(order)) == 0
         if resort:
             assert hip.fleet_scene_resort(self.F, dptr(st), 3) == 0
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s), info,
-                                    None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh
+        return self.step_tracked(st, cur, first)
 
     def forced(self, logs, n, base, cur0, first):
         """n host-driven ticks fed with the logged states and indices of a rollout and the numpy-advanced geometry"""
@@ -166,10 +77,7 @@ class Twin:
                                geom=advanced(self.kind, self.nvert, base, self.vel, DT * k)[0]) for k in range(n)]
 
 
-def same_logs(a, b, keys=("states", "controls", "index", "arrived_at", "clearance")):
-    for key in keys:
-        assert np.array_equal(a[key], b[key]), key
-    assert a["info"] == b["info"]
+LOGS = ("states", "controls", "index", "arrived_at", "clearance")
 
 
 @pytest.fixture(scope="module", params=[1, 0], ids=["resort", "staged-order"])
@@ -205,24 +113,6 @@ def test_obstacles_move_by_the_rule(run):
     want2, _ = advanced(kind, nvert, want1, vel, DT * K2)
     assert np.array_equal(run["geom2"], want2)
     assert np.array_equal(run["geom2"][2 * NOBS:], base[2 * NOBS:])                        # member 2 stands
-
-
-def compare_ticks(logs, ticks, n):
-    arrived = logs["arrived_at"]
-    B, moved = len(arrived), 0
-    for k, (u, s, info, mi, eh) in enumerate(ticks):
-        for i in range(B):
-            live = arrived[i] < 0 or k < arrived[i]
-            first = np.array([u[i, 0, 0], u[i, 1, 0]])
-            print(f"tick {k} member {i}: |du| = {np.abs(logs['controls'][k, i] - first).max():.3e}  index {logs['index'][k, i]} / {mi[i]}  "
-                  f"iters {logs['info'][k * B + i][2]} / {info[i][2]}")
-            if live:
-                assert np.array_equal(logs["controls"][k, i], first), (k, i)
-                moved += 1
-            assert logs["index"][k, i] == mi[i], (k, i)
-            assert logs["info"][k * B + i][2] == info[i][2], (k, i)
-    assert len(ticks) == n
-    return moved
 
 
 def test_teacher_forced_twin_bit_for_bit(run):
@@ -332,7 +222,7 @@ def test_refusals_queue_and_change_nothing(hip):
     rc, lb = b.rollout(2, 1)
     assert rc == 0
     lb["info"] = la["info"]
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     assert np.array_equal(a.geometry(), b.geometry()) and not np.array_equal(a.geometry(), g0)
     a.close(); b.close()
 
@@ -380,7 +270,7 @@ def test_refused_allocations_change_nothing(hip):
     assert rc == 0 and n - 1 > 20
     rc, lb = b.rollout(3, 1)
     assert rc == 0
-    same_logs(la, lb)
+    same_logs(la, lb, LOGS)
     a.close(); b.close()
 
 

@@ -202,13 +202,14 @@ def test_fleet_of_three_equals_the_solo_calls_and_stages_the_same_boxes(hip, sca
 def test_rollout_ticks_equal_host_driven_ticks_under_the_same_setting(hip):
     """K = 3 ticks of rda_fleet_rollout_lidar with split, B = 2: every tick == rda_fleet_raycast + rda_fleet_upload_scans + rda_fleet_step_tracked of a
     twin fleet with the same setting (box count, first control, min_index, rda_info), and the split changes the box counts of these lanes"""
-    from test_gpu_fleet_rollout_lidar import Twin, compare_ticks
+    from fleet_twin_lib import compare_ticks
+    from test_gpu_fleet_rollout_lidar import TICK, Twin
     a, b, c = Twin(hip, which=(0, 1)), Twin(hip, which=(0, 1)), Twin(hip, which=(0, 1))
     assert hip.fleet_set_scan_split(a.F, TOL_SPLIT) == 0 and hip.fleet_set_scan_split(b.F, TOL_SPLIT) == 0
     rc, logs = a.rollout(3, 0)
     assert rc == 0, rc
     ticks = b.forced(logs, 3, b.base, lambda k: 0.0, b.cur0, True)
-    assert compare_ticks(logs, ticks, 3) == 6
+    assert compare_ticks(logs, ticks, 3, TICK) == 6
     rc, plain = c.rollout(3, 0)
     assert rc == 0
     print("boxes per tick, split:", logs["boxes"].T.tolist(), " unsplit:", plain["boxes"].T.tolist())

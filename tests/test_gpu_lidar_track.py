@@ -16,19 +16,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from rda_planner_amd import lidar
-from rda_planner_amd._capi import Info, dptr, iptr
-
 import lidar_track_lib as L
+from fleet_twin_lib import DT, E, MARGIN, RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, T, advanced, info_tuple, same_logs
 from lidar_world_lib import EPS
-from test_gpu_fleet_rollout_lidar import same_logs
+from rda_planner_amd import lidar
+from rda_planner_amd._capi import dptr, iptr
+from test_gpu_fleet_rollout_lidar import LOGS
 from test_gpu_fleet_rollout_lidar_peers import BEAMS, MINS, PTwin, plant
-from test_gpu_fleet_rollout_moving import DT, E, MARGIN, SPEED, T, advanced, info_tuple
 
 pytestmark = pytest.mark.gpu
 
 K, GATE, WINDOW = 4, 1.0, 8
-RDA_ERR_ARG, RDA_ERR_UNSUPPORTED = -1, -2
 CAP = 260
 
 
@@ -36,10 +34,7 @@ class TTwin(PTwin):
     """that file's twin with the tracked entries"""
     def rollout_tracked(self, k, moving, see, clearance=True, gate=GATE, window=WINDOW, **over):
         """rda_fleet_rollout_lidar_tracked -> (rc, dict of logs); over: arguments replaced (None = a missing array)"""
-        B = self.B
-        out = dict(states=np.zeros((max(k, 0) + 1, B, 3)), controls=np.zeros((max(k, 1), B, 2)), index=np.zeros((max(k, 1), B), np.int32),
-                   info=(Info * (max(k, 1) * B))(), arrived_at=np.full(B, -7, np.int32), boxes=np.full((max(k, 1), B), -7, np.int32),
-                   clearance=np.full((max(k, 1), B), -7.0) if clearance else None, peer_clearance=np.full((max(k, 1), B), -7.0) if see else None)
+        out = self.logs(k, boxes=np.int32, clearance=float if clearance else None, peer_clearance=float if see else None)
         nb, lo, hi, rmin, rmax = self.sensors
         a = dict(states=self.states, ref_speed=self.speed, cur_index=self.cur0, threshold=0.1, ind_range=10, goal_margin=MARGIN, nom_u=self.nom0,
                  n_beams=nb, angle_min=lo, angle_max=hi, range_min=rmin, range_max=rmax, eps=EPS, min_samples=MINS, order=self.order,
@@ -61,14 +56,6 @@ class TTwin(PTwin):
         assert f(self.F, iptr(nb), dptr(lo), dptr(hi), dptr(rmin), dptr(rmax), dptr(st), dptr(ranges)) == 0
         return ranges
 
-    def step(self, st, cur, first):
-        B = self.B
-        u, s, info, mi, eh = np.zeros((B, 2, T)), np.zeros((B, 3, T + 1)), (Info * B)(), np.zeros(B, np.int32), np.zeros(B)
-        rc = self.hip.fleet_step_tracked(self.F, dptr(st), dptr(self.speed), iptr(cur), 0.1, 10, dptr(self.nom0) if first else None, dptr(u), dptr(s),
-                                         info, None, iptr(mi), dptr(eh))
-        assert rc >= 0, rc
-        return u, s, [info_tuple(i) for i in info], mi, eh
-
     def upload_tracked(self, st, ranges, gate=GATE, window=WINDOW, **over):
         nb, lo, hi, rmin, rmax = self.sensors
         boxes = np.full(self.B, -7, np.int32)
@@ -85,7 +72,7 @@ class TTwin(PTwin):
             self.upload_world(geom)
         rc, boxes = self.upload_tracked(st, self.cast(st, see))
         assert rc == 0, rc
-        return self.step(st, cur, first) + (boxes,)
+        return (*self.step_tracked(st, cur, first), boxes)
 
     def scan_boxes(self, st, ranges):
         """rda_fleet_scan_boxes: the device's boxes of these ranges, a list of (n_i, 4, 2)"""
@@ -201,7 +188,7 @@ def test_a_host_driven_tracked_tick_equals_the_polygons_with_the_specifications_
         boxes = a.scan_boxes(st, ranges)
         rc, nbox = a.upload_tracked(st, ranges)
         assert rc == 0 and nbox.tolist() == [len(x) for x in boxes]
-        ua, sa, ia, mia, eha = a.step(st, cur, k == 0)
+        ua, sa, ia, mia, eha = a.step_tracked(st, cur, k == 0)
         vels = []
         for i in range(3):
             v, spec[i] = lidar.track_boxes(spec[i], boxes[i], DT, GATE, WINDOW)
@@ -209,7 +196,7 @@ def test_a_host_driven_tracked_tick_equals_the_polygons_with_the_specifications_
             fastest = max(fastest, float(np.sqrt((v * v).sum(axis=1)).max()) if len(v) else 0.0)
         assert all(same_table(x, table_of(spec[i], vels[i])) for i, x in enumerate(a.tracks()))
         b.upload_polygons(st, boxes, vels)
-        ub, sb, ib, mib, ehb = b.step(st, cur, k == 0)
+        ub, sb, ib, mib, ehb = b.step_tracked(st, cur, k == 0)
         print(f"tick {k}: boxes {nbox.tolist()}  fastest box so far {fastest:.3f} m/s  |du| = {np.abs(ua - ub).max():.3e}  |ds| = {np.abs(sa - sb).max():.3e}")
         assert np.array_equal(ua, ub) and np.array_equal(sa, sb) and ia == ib, k
         assert np.array_equal(mia, mib) and np.array_equal(eha, ehb)
@@ -351,13 +338,13 @@ def test_the_untracked_rollout_is_unchanged_and_refusals(hip):
     assert rc == 0
     rc, lc = c.rollout(3, 1, min_samples=MINS)                                      # untracked, after
     assert rc == 0
-    same_logs(la, lc)
+    same_logs(la, lc, LOGS)
     assert not np.array_equal(la["controls"], lb["controls"])                        # tracking is another rollout
     # on the fleet that tracked: the untracked rollout that continues equals the one on a fleet made anew over the same members
     d = TTwin(hip)
     rc, ld = d.rollout_tracked(3, 1, 0)
     assert rc == 0
-    same_logs(lb, ld)
+    same_logs(lb, ld, LOGS)
     cont = dict(min_samples=MINS, states=np.ascontiguousarray(lb["states"][3]), cur_index=np.ascontiguousarray(lb["index"][2]), nom_u=None)
     rc, lb2 = b.rollout(2, 0, **cont)
     assert rc == 0
@@ -365,7 +352,7 @@ def test_the_untracked_rollout_is_unchanged_and_refusals(hip):
     d.upload_world(advanced(d.kind, d.nvert, d.base, d.vel, DT * 3)[0])              # (the tracked rollout moved the world by three ticks)
     rc, ld2 = d.rollout(2, 0, **cont)
     assert rc == 0
-    same_logs(lb2, ld2)
+    same_logs(lb2, ld2, LOGS)
     # refusals: the rollout's own and the tracker's, and nothing has changed - neither the world nor the tracks
     w0, t0 = b.world(), b.tracks()
     assert b.rollout_tracked(0, 0, 0)[0] == RDA_ERR_ARG

@@ -15,14 +15,11 @@ import helpers as hp
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, Opts, dptr, iptr
 
+from fleet_twin_lib import hip          # noqa: F401  (the fixture)
+from fleet_twin_lib import info_tuple
+
 pytestmark = pytest.mark.gpu
 RDA_ERR_HIP = -3
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from rda_planner_amd._lib import hip_api
-    return hip_api()
 
 
 @pytest.fixture(autouse=True)
@@ -91,10 +88,6 @@ def step(hip, h, cfg, inp, obs):
                   dptr(u), dptr(s), C.byref(info))
     assert rc >= 0, rc
     return [rc, u, s, info_tuple(info)] + get_state(hip, h, cfg)
-
-
-def info_tuple(i):
-    return (i.resi_dual, i.resi_pri, i.iters, i.su_status, i.su_ipm_iters, i.lmz_fail)
 
 
 def get_state(hip, h, cfg, products=False):

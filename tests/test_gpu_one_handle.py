@@ -21,8 +21,8 @@ import pytest
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
+from fleet_twin_lib import E, N, T, info_tuple, solver
 from lidar_world_lib import numpy_scan
-from test_gpu_fleet_rollout_moving import E, N, T, info_tuple, solver
 from test_gpu_lifecycle import live, path_array, scene_arrays
 
 pytestmark = pytest.mark.gpu

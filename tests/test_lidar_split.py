@@ -5,7 +5,6 @@ the entry points declared, exported, documented and bound like the header; and t
 import ctypes as C
 import os
 import re
-import types
 
 import numpy as np
 import pytest
@@ -15,13 +14,10 @@ from rda_planner_amd import lidar
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd import world as irsim
 
-from test_fleet_lidar_peers_api import _Binding
-from test_fleet_lidar_rollout_api import SENSOR, _header, _lib
+from capi_lib import LIDAR_FLAGS, RDA_ERR_ARG, ROOT, SENSOR, Binding, bare_fleet, header, integration_rows, lib, pipeline_member
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CORRIDOR = os.path.join(ROOT, "tests", "golden", "world_lidar_corridor.yaml")
 TOL_SPLIT = 0.15
-RDA_ERR_ARG = -1
 
 
 def corridor_cfg():
@@ -171,13 +167,12 @@ def test_split_boxes_restore_the_clearance_one_box_per_cluster_hides(k):
 @pytest.mark.parametrize("name,first", [("rda_set_scan_split", "rda_handle *"), ("rda_fleet_set_scan_split", "rda_fleet *")])
 def test_entries_are_declared_exported_documented_and_bound(name, first):
     from rda_planner_amd._capi import CApi
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, _header(), re.S)
+    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, header(), re.S)
     assert m and [" ".join(a.split()) for a in m.group(1).split(",")] == [first + ("h" if "handle" in first else "f"), "double tol"]
-    lib = _lib()
-    assert hasattr(lib, name), f"{name} declared in include/rda_hip.h but not exported"
-    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert [ln for ln in doc.splitlines() if ln.startswith("|") and "`%s`" % name in ln], name
-    api = CApi(lib, "rda")
+    so = lib()
+    assert hasattr(so, name), f"{name} declared in include/rda_hip.h but not exported"
+    assert integration_rows(name), name
+    api = CApi(so, "rda")
     assert api.has_scan_split is True
     fn = getattr(api, name[len("rda_"):])
     assert list(fn.argtypes) == [C.c_void_p, C.c_double] and fn.restype is C.c_int
@@ -199,16 +194,8 @@ def test_python_interface_and_refusals_before_any_device_call():
     for fn in (Fleet.control, Fleet.rollout):
         assert "scan_split" in fn.__doc__ and "rda_fleet_set_scan_split" in fn.__doc__
 
-    def member():
-        def no_solver(*a, **k):
-            raise AssertionError("member touched")
-        return types.SimpleNamespace(enable_reverse=False, _tracks=lambda kw: set(kw) <= {"threshold", "ind_range"}, goal_index_threshold=1, receding=5,
-                                     car_tuple=sc.rectangle_robot(), rda_obstacle=False, obstacle_order=True, device_obstacles=True,
-                                     rda=types.SimpleNamespace(has_scene=True), _piece=no_solver, _sync_path=no_solver)
     states = [np.zeros((3, 1)), np.zeros((3, 1))]
-    f = Fleet.__new__(Fleet)                           # no device: a binding that fails on any use
-    f._handle = None
-    f.api, f.members = _Binding(has_scan_split=True, has_fleet_scans=True), [member(), member()]
+    f = bare_fleet(Binding(**LIDAR_FLAGS, has_scan_split=True, has_fleet_scans=True), [pipeline_member(), pipeline_member()])      # no device: a binding that fails on any use
     with pytest.raises(ValueError, match="scan_split splits the clusters of lidar="):
         f.rollout(states, 4.0, 5, scan_split=0.15)
     with pytest.raises(ValueError, match="scan_split splits the clusters of scans="):
@@ -218,14 +205,14 @@ def test_python_interface_and_refusals_before_any_device_call():
             f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], scan_split=bad)
         with pytest.raises(ValueError, match="scan_split must be finite and greater than 0"):
             f.control(states, 4.0, scans=[None, None], scan_split=bad)
-    f.api = _Binding(has_scan_split=False, has_fleet_scans=True)                             # a library without the two entries
+    f.api = Binding(**LIDAR_FLAGS, has_scan_split=False, has_fleet_scans=True)                             # a library without the two entries
     for call in (lambda: f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], scan_split=0.15), lambda: f.control(states, 4.0, scans=[None, None], scan_split=0.15),
                  lambda: f.set_scan_split(0.15)):
         with pytest.raises(RuntimeError, match="rda_set_scan_split, rda_fleet_set_scan_split"):
             call()
     f.set_scan_split(0.0)                                                                    # off on a fleet that is off: no library call
     # scan_split never reaches the tracking check: with it popped, these calls get as far as the next refusal
-    f.api = _Binding(has_scan_split=True)
+    f.api = Binding(**LIDAR_FLAGS, has_scan_split=True)
     with pytest.raises(ValueError, match="scan_eps"):
         f.rollout(states, 4.0, 5, lidar=[SENSOR, SENSOR], scan_split=0.15, scan_eps=0.0)
     # MPC.control on the CPU checker backend: the same ValueErrors before anything else, and no host fallback behind scan=
