@@ -59,6 +59,7 @@ template <typename T> struct Pair {          // n T on the device and their pinn
     T *h = nullptr, *d = nullptr; size_t n = 0;
     int alloc(Group &g, size_t count) { const int rc = g.dev(&d, count) | g.pin(&h, count); n = rc ? 0 : count; return rc; }     // (refused: n stays 0)
     hipError_t push(hipStream_t s) const { return hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s); }                        // all of the mirror
+    hipError_t upload(const T *src, hipStream_t s) const { memcpy((void *)h, src, n * sizeof(T)); return push(s); }                      // n T of the caller's -> mirror -> device
     hipError_t pull(hipStream_t s, size_t count) const { return hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s); }      // the first count
 };
 

@@ -3096,7 +3096,8 @@ __global__ __launch_bounds__(su::NT) void k_finish_fleet(const Dev *devs, const 
 
 // The table sets a fleet makes on first use.  Each owns its allocations (g: zeroed, counted) beside the views into them - a device array with its pinned
 // mirror (hbuf::Pair) or a plain pointer where only one side exists - and is built beside the fleet (alloc: all or RDA_ERR_HIP).  The call that needs a set
-// moves it in (F->set = std::move(t)) only when it can no longer be refused: a refused allocation leaves the fleet as it was.  have(): allocated.
+// moves it in (FleetReserve) only when it can no longer be refused: a refused allocation leaves the fleet as it was.  have(): allocated; size(): the
+// elements of a set that is regrown when a call needs more.
 struct FleetTrack {                       // tracked stepping (device-side pre_process): rda_fleet_step_tracked, the rollouts
     hbuf::Group g; hbuf::Pair<track::In> in; hbuf::Pair<track::Out> out; hbuf::Pair<double *> paths; hbuf::Pair<int> lens; hbuf::Pair<EgoIO> io;
     int alloc(size_t B) { return (in.alloc(g, B) | out.alloc(g, B) | paths.alloc(g, B) | lens.alloc(g, B) | io.alloc(g, B)) ? RDA_ERR_HIP : RDA_OK; }
@@ -3161,6 +3162,7 @@ struct FleetRollLog {                     // the rollouts' log block of `cap` ti
     hbuf::Group g; hbuf::Pair<char> log; int cap = 0;
     int alloc(int K, size_t B, size_t T) { cap = K; return log.alloc(g, roll_layout((size_t)K, B, T).bytes) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return log.d != nullptr; }
+    size_t size() const { return (size_t)cap; }
 };
 // rda_fleet_rollout_moving, rda_fleet_clearance: per member the move kernel's and the clearance kernel's arguments, the members' scene arguments as they
 // stand (resort = 0: slots rebuilt in the staged order), the states of rda_fleet_clearance [B][3]
@@ -3173,11 +3175,13 @@ struct FleetSnapshot {                    // rda_fleet_rollout_moving: the snaps
     hbuf::Group g; double *d = nullptr; size_t cap = 0;
     int alloc(size_t n) { cap = n; return g.dev(&d, n) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return d != nullptr; }
+    size_t size() const { return cap; }
 };
 struct FleetDoubles {                     // v.n doubles, regrown when a call needs more: the clearance log [K][B] | the ranges of the last ray cast
     hbuf::Group g; hbuf::Pair<double> v;
     int alloc(size_t n) { return v.alloc(g, n) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return v.d != nullptr; }
+    size_t size() const { return v.n; }
 };
 // members as each other's obstacles (rda_fleet_*_peers, rda_fleet_peer_clearance): the peer table, the states [B][3] and the controls [B][2] of a host-driven
 // refresh or of a rollout's tick 0
@@ -3203,6 +3207,7 @@ struct FleetInts {                        // v.n ints, regrown when a call needs
     hbuf::Group g; hbuf::Pair<int> v;
     int alloc(size_t n) { return v.alloc(g, n) ? RDA_ERR_HIP : RDA_OK; }
     bool have() const { return v.d != nullptr; }
+    size_t size() const { return v.n; }
 };
 // The members' resident WORLDS (rda_fleet_upload_worlds): what the simulated sensor sees (lidar::k_raycast_fleet), apart from the raw scenes that a lidar
 // tick overwrites with boxes.  Member-major geometry [total][e][2], its snapshot of the same size (rda_fleet_rollout_lidar, moving), velocities, kinds,
@@ -3224,7 +3229,24 @@ struct FleetWorld {
     bool have() const { return geom != nullptr; }
 };
 
-struct rda_fleet {                        // (owns its buffers, event and stream like rda_handle)
+// the on-demand sets a fleet holds - and a FleetReserve, one empty set of each, builds beside it
+struct FleetSets {
+    FleetTrack trk; FleetResort res;
+    FleetLidar li; FleetLidarHost li_host; FleetTracks tk;
+    FleetRollTables ro; FleetRollLog ro_log;
+    FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
+    FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
+    FleetPeers pe; FleetDoubles pc_log;                           // pc_log: the peer clearance log
+    FleetPlan pl;
+    FleetGears gr; FleetInts gr_log; FleetDoubles gr_endh;        // gr_endh: the pieces' end headings
+    template <typename Fn> static void each(Fn f)                 // f(&FleetSets::set) for every set
+    {
+        f(&FleetSets::trk); f(&FleetSets::res); f(&FleetSets::li); f(&FleetSets::li_host); f(&FleetSets::tk); f(&FleetSets::ro); f(&FleetSets::ro_log);
+        f(&FleetSets::mov); f(&FleetSets::snap); f(&FleetSets::cl_log); f(&FleetSets::world); f(&FleetSets::rays); f(&FleetSets::pe); f(&FleetSets::pc_log);
+        f(&FleetSets::pl); f(&FleetSets::gr); f(&FleetSets::gr_log); f(&FleetSets::gr_endh);
+    }
+};
+struct rda_fleet : FleetSets {            // (owns its buffers, event and stream like rda_handle; the sets outlive the stream)
     int B;
     std::vector<rda_handle *> egos;
     hbuf::Group mem;                      // what rda_fleet_create makes:
@@ -3236,23 +3258,28 @@ struct rda_fleet {                        // (owns its buffers, event and stream
     int T, iter_num, J, rows, lmz_split;
     int ip, ip_rows, ip_cp;               // interior-point fleet; some member runs the row-parallel kernel | the per-thread kernel this tick (fleet_refresh_flags)
     size_t su_lds;
-    FleetTrack trk;
-    FleetResort res; int rob_pending;     // rob_pending: a copy out of res.rob.h may be queued
-    FleetLidar li; FleetLidarHost li_host; FleetTracks tk;
+    int rob_pending;                      // a copy out of res.rob.h may be queued
     double scan_split = 0.0;              // rda_fleet_set_scan_split: lidar::Args::split_tol of every member's scan in the fleet's calls
-    FleetRollTables ro; FleetRollLog ro_log; int roll_K;      // roll_K: the ticks of the rollout whose logs are on the host
-    FleetMove mov; FleetSnapshot snap; FleetDoubles cl_log;      // cl_log: the clearance log
-    FleetWorld world; FleetDoubles rays;                          // rays: the ranges of the last ray cast
-    FleetPeers pe; FleetDoubles pc_log; std::vector<int> n_own;   // pc_log: the peer clearance log; n_own: every member's own obstacles as the last peers upload staged them
-    FleetPlan pl;
-    FleetGears gr; FleetInts gr_log; FleetDoubles gr_endh; int gear_total;      // gr_endh: the pieces' end headings; gear_total: the pieces of all members of the gear rollout whose logs are on the host (0: none)
+    int roll_K;                           // the ticks of the rollout whose logs are on the host
+    std::vector<int> n_own;               // every member's own obstacles as the last peers upload staged them
+    int gear_total;                       // the pieces of all members of the gear rollout whose logs are on the host (0: none)
     hbuf::Event ev;
     hbuf::Stream stream;                  // (last: destroyed first)
 };
 
+// The wait for the fleet's stream: nothing is queued behind it, so no copy out of res.rob.h either.  consumed: the call was a step or a rollout - the
+// members' staged scenes have been consumed.
+static hipError_t fleet_wait(rda_fleet *F, bool consumed = false)
+{
+    const hipError_t e = hipStreamSynchronize(F->stream);
+    if (e != hipSuccess) return e;
+    F->rob_pending = 0;
+    if (consumed) for (rda_handle *H : F->egos) H->tick.pending_scene = 0;
+    return e;
+}
 // The refresh of a pinned mirror, in its two halves; get(i): record i as it should be now.  mirror_differs: does any record differ from the mirror?
-// mirror_upload: the mirror rewritten and pushed.  Between the two the caller waits for the fleet's stream (an earlier copy out of the mirror may still be
-// queued): the wait is the caller's, because where one wait covers several tables the caller asks about all of them first.
+// mirror_upload: the mirror rewritten and pushed.  Between the two comes fleet_wait (an earlier copy out of the mirror may still be queued): fleet_table for
+// one table; where one wait covers several tables the caller asks about all of them first.
 template <typename T, typename Get> static bool mirror_differs(const hbuf::Pair<T> &p, Get get)
 {
     for (size_t i = 0; i < p.n; ++i) { const T &r = get(i); if (memcmp(&r, &p.h[i], sizeof(T)) != 0) return true; }
@@ -3267,6 +3294,54 @@ template <typename T> static auto records(const std::vector<T> &v) { return [&v]
 static auto member_devs(const rda_fleet *F) { return [F](size_t i) -> const Dev & { return F->egos[i]->d; }; }
 static auto member_paths(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path.d; }; }
 static auto member_lens(const rda_fleet *F) { return [F](size_t i) { return F->egos[i]->path.len; }; }
+// one table: uploaded when it differs from what the device holds
+template <typename T, typename Get> static int fleet_table(rda_fleet *F, const hbuf::Pair<T> &p, Get get)
+{
+    if (!mirror_differs(p, get)) return RDA_OK;
+    HIPCHK(fleet_wait(F));
+    HIPCHK(mirror_upload(p, get, F->stream));
+    return RDA_OK;
+}
+
+// What a call builds beside the fleet before it changes anything: one empty set of each kind.  need / grow / fresh allocate what the fleet lacks (alloc's
+// arguments follow the set) and remember a refusal.  adopt, once the call has asked for everything: RDA_ERR_HIP after a refusal - what was built goes with
+// the call, the fleet is as it was - else the sets move in.  It is the only place where a set of the fleet is assigned.
+struct FleetReserve {
+    rda_fleet *F; FleetSets s; int refused = 0;
+    explicit FleetReserve(rda_fleet *fleet) : F(fleet) {}
+    template <typename S, typename... A> void need(S FleetSets::*m, A... a) { if (!(F->*m).have()) refused |= (s.*m).alloc(a...); }                 // this set
+    template <typename S, typename... A> void grow(S FleetSets::*m, size_t n, A... a) { if (n > (F->*m).size()) refused |= (s.*m).alloc(a...); }    // ... of at least n elements
+    template <typename S, typename... A> void fresh(S FleetSets::*m, A... a) { refused |= (s.*m).alloc(a...); }                                     // a new one in its place
+    void need_lidar(bool host_copy)                     // the lidar block (the first one raises the scan kernels' LDS limit) and, host_copy, the host's copies
+    {
+        need(&FleetSets::li, (size_t)F->B);
+        if (s.li.have() && (hipFuncSetAttribute((const void *)lidar::k_scan_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES) != hipSuccess ||
+                            hipFuncSetAttribute((const void *)lidar::k_scan_fleet_at, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES) != hipSuccess))
+            refused = 1;
+        if (host_copy) need(&FleetSets::li_host, (size_t)F->B);
+    }
+    // what every rollout reserves before its first tick: the tracker's tables, the rollout tables, a log block of K ticks and (clearance) a clearance log
+    void need_rollout(int K, bool clearance)
+    {
+        const size_t B = F->B;
+        need(&FleetSets::trk, B); need(&FleetSets::ro, B); grow(&FleetSets::ro_log, (size_t)K, K, B, (size_t)F->T);
+        if (clearance) grow(&FleetSets::cl_log, (size_t)K * B, (size_t)K * B);
+    }
+    int bad() const { return refused ? RDA_ERR_HIP : RDA_OK; }
+    // the set a call that runs before it adopts works on: the fleet's, or the one built here
+    template <typename S> S &now(S FleetSets::*m) { return (s.*m).have() ? s.*m : F->*m; }
+    // Whatever was built moves in.  The wait comes first where a set the fleet holds is replaced - the old block may be in flight, and it is freed here - and
+    // where the caller goes on to rewrite pinned tables unconditionally (rewrites); a first-use set needs none.
+    int adopt(bool rewrites = false)
+    {
+        if (refused) return RDA_ERR_HIP;
+        bool wait = rewrites;
+        FleetSets::each([&](auto m) { if ((s.*m).have() && (F->*m).have()) wait = true; });
+        if (wait) HIPCHK(fleet_wait(F));
+        FleetSets::each([&](auto m) { if ((s.*m).have()) F->*m = std::move(s.*m); });
+        return RDA_OK;
+    }
+};
 
 // Member i's locations on the step path: its step block in `in` (in_u: nominal controls that live elsewhere, else null), its u | s block
 // under out_base, its info under info_base
@@ -3365,11 +3440,7 @@ static int fleet_refresh(rda_fleet *F)
         HIPCHK(hipStreamWaitEvent(F->stream, F->ev, 0));
     }
     fleet_refresh_flags(F);
-    if (mirror_differs(F->devs, member_devs(F))) {
-        HIPCHK(hipStreamSynchronize(F->stream));            // an earlier copy out of the pinned mirror may still be queued
-        HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
-    }
-    return RDA_OK;
+    return fleet_table(F, F->devs, member_devs(F));
 }
 
 static int fleet_enqueue(rda_fleet *F, const EgoIO *io, int k)
@@ -3424,9 +3495,7 @@ extern "C" int rda_fleet_step(rda_fleet *F, const double *nom_s, const double *n
     if (rc != RDA_OK) return rc;
     HIPCHK(F->out.pull(F->stream, F->out.n));
     HIPCHK(F->info.pull(F->stream, B));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
-    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;  // their staged scenes have been consumed
+    HIPCHK(fleet_wait(F, true));
     for (size_t i = 0; i < B; ++i) fleet_result_out(F, i, out_u, out_s, info);
     return RDA_OK;
 }
@@ -3444,6 +3513,31 @@ __global__ void k_track_fleet(const Dev *devs, const EgoIO *io, const track::In 
     e.speed = const_cast<double *>(io[b].speed);
     e.T = d.c.T; e.dynamics = d.c.dynamics; e.dt = d.c.dt; e.wheelbase = d.c.L;
     track::run(e, ins[b], outs[b], win, threadIdx.x);
+}
+
+// What the entries ask of the members.  An entry whose rules interleave per member (member 0's second rule in front of member 1's first) spells them out.
+// no member is inside a tick of its own (else RDA_ERR_ARG)
+static bool fleet_members_idle(const rda_fleet *F) { for (const rda_handle *H : F->egos) if (H->tick.pending) return false; return true; }
+// some member has rda_opts::duals_follow (RDA_ERR_UNSUPPORTED: k_follow_* are per member)
+static bool fleet_duals_follow(const rda_fleet *F) { for (const rda_handle *H : F->egos) if (H->opts.duals_follow) return true; return false; }
+// a polygon robot whose consecutive rows intersect: what the clearance kernel, the peer table and a footprint take (else RDA_ERR_UNSUPPORTED)
+static bool member_clearance_ok(const rda_handle *H)
+{
+    if (H->d.c.robot_norm2) return false;
+    const int R = H->d.c.R;
+    const double *G = H->rob_G.data();
+    for (int k = 0; k < R; ++k) { const int j = (k + R - 1) % R; if (G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k] == 0) return false; }
+    return true;
+}
+static bool fleet_clearance_ok(const rda_fleet *F) { for (const rda_handle *H : F->egos) if (!member_clearance_ok(H)) return false; return true; }
+// rda_fleet_clearance, rda_fleet_peer_clearance: member by member, idle and then a robot the kernel takes
+static int fleet_check_clearance_call(const rda_fleet *F)
+{
+    for (const rda_handle *H : F->egos) {
+        if (H->tick.pending) return RDA_ERR_ARG;
+        if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
+    }
+    return RDA_OK;
 }
 
 // every member's raw scene in one call (member i owns counts[i] consecutive entries of the arrays): staged on the members'
@@ -3480,7 +3574,7 @@ static int fleet_resort_positions(rda_fleet *F, const double *states, int stride
         nmax = a.n > nmax ? a.n : nmax; wmax = a.N * a.nt > wmax ? a.N * a.nt : wmax;
     }
     const bool changed = mirror_differs(F->res.sc, args);
-    if (changed || F->rob_pending) { HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; }
+    if (changed || F->rob_pending) HIPCHK(fleet_wait(F));
     if (changed) HIPCHK(mirror_upload(F->res.sc, args, F->stream));
     for (size_t i = 0; i < B; ++i) { F->res.rob.h[2 * i] = states[i * stride]; F->res.rob.h[2 * i + 1] = states[i * stride + 1]; }
     HIPCHK(F->res.rob.push(F->stream));
@@ -3507,12 +3601,10 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
         if (H->sc.n <= 0 || H->d.obstacle_num == 0 || H->tick.pending) return RDA_ERR_ARG;
         if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;
     }
-    if (!F->res.have()) {                               // first use: the tables (zeroed) take their place once all of them exist
-        FleetResort t;
-        if (t.alloc((size_t)F->B)) return RDA_ERR_HIP;
-        F->res = std::move(t);
-    }
-    int rc = fleet_refresh(F);
+    FleetReserve rsv(F);
+    rsv.need(&FleetSets::res, (size_t)F->B);
+    int rc = rsv.adopt();
+    if (rc == RDA_OK) rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     int nmax = 0, wmax = 0;
     rc = fleet_resort_positions(F, states, stride, nmax, wmax);
@@ -3523,24 +3615,6 @@ extern "C" int rda_fleet_scene_resort(rda_fleet *F, const double *states, int st
 }
 
 // ---- fleet lidar (lidar::k_scan_fleet): every member's range scan in one launch --------------------------------------------------------------------
-static int fleet_lidar_reserve(rda_fleet *F, bool host_copy)
-{
-    const size_t B = F->B;
-    if (!F->li.have()) {
-        FleetLidar t;
-        if (t.alloc(B)) return RDA_ERR_HIP;
-        HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
-        HIPCHK(hipFuncSetAttribute((const void *)lidar::k_scan_fleet_at, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lidar::LDS_BYTES));
-        F->li = std::move(t);
-    }
-    if (host_copy && !F->li_host.have()) {
-        FleetLidarHost t;
-        if (t.alloc(B)) return RDA_ERR_HIP;
-        F->li_host = std::move(t);
-    }
-    return RDA_OK;
-}
-
 // rda_set_scan_split for the fleet's scans (fleet_scan_run, fleet_rollout_lidar)
 extern "C" int rda_fleet_set_scan_split(rda_fleet *F, double tol)
 {
@@ -3564,40 +3638,37 @@ static int fleet_scan_check(const rda_fleet *F, const int32_t *n_beams, const do
 struct TrackArgs { double gate; int window; };      // tracked mode: lidar::k_track_boxes_fleet's association gate [m] and history length
 static int track_check(const TrackArgs &t) { return (t.gate > 0 && t.window >= 1 && t.window <= lidar::TRK_HIST) ? RDA_OK : RDA_ERR_ARG; }
 // the tracker's member table -> device: member i's boxes and box count where the scan kernels leave them (li.d_boxes, li.h_count), its part of both buffers
-// of F->tk, its sample time.  The pinned mirror is rewritten only when it differs, which it does on the first tracked call and after the lidar block was
-// made anew (the wait: an earlier copy out of the mirror may still be queued)
-static int fleet_track_table(rda_fleet *F)
+// of tk, its sample time.  The pinned mirror is rewritten only when it differs, which it does on the first tracked call and after the lidar block was
+// made anew.  li, tk: the fleet's, or (rda_fleet_upload_scans_tracked, whose scan runs before the call can no longer be refused) its reservation's.
+static int fleet_track_table(rda_fleet *F, const FleetLidar &li, const FleetTracks &tk)
 {
-    FleetTracks &tk = F->tk;
     const size_t B = F->B, M = lidar::MAX_TRACKS;
     std::vector<lidar::Track> tv(B);
     for (size_t i = 0; i < B; ++i) {
         lidar::Track &t = tv[i];
         memset((void *)&t, 0, sizeof(t));
-        t.boxes = F->li.d_boxes + i * lidar::MAXB * 8; t.count = F->li.h_count + 2 * i;
+        t.boxes = li.d_boxes + i * lidar::MAXB * 8; t.count = li.h_count + 2 * i;
         for (size_t p = 0; p < 2; ++p) {
             t.cnt[p] = tk.cnt + p * B + i; t.len[p] = tk.len + (p * B + i) * M; t.hist[p] = tk.hist + (p * B + i) * M * lidar::TRK_HIST * 2;
             t.tvel[p] = tk.tvel + (p * B + i) * M * 2;
         }
         t.vel = tk.vel + i * lidar::MAXB * 2; t.dt = F->egos[i]->d.c.dt;
     }
-    if (!mirror_differs(tk.tab, records(tv))) return RDA_OK;
-    HIPCHK(hipStreamSynchronize(F->stream));
-    HIPCHK(mirror_upload(tk.tab, records(tv), F->stream));
-    return RDA_OK;
+    return fleet_table(F, tk.tab, records(tv));
 }
 // one launch for the fleet, behind the scan kernel that wrote the counts; the caller switches tk.par once the tick goes through
-static void fleet_track_launch(rda_fleet *F, const TrackArgs &t)
+static void fleet_track_launch(rda_fleet *F, const FleetTracks &tk, const TrackArgs &t)
 {
-    hipLaunchKernelGGL(lidar::k_track_boxes_fleet, dim3((unsigned)F->B), dim3(lidar::TRK_NT), 0, F->stream, (const lidar::Track *)F->tk.tab.d, F->tk.par, t.gate,
+    hipLaunchKernelGGL(lidar::k_track_boxes_fleet, dim3((unsigned)F->B), dim3(lidar::TRK_NT), 0, F->stream, (const lidar::Track *)tk.tab.d, tk.par, t.gate,
                        t.window);
 }
 
-static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
-                          const double *range_max, const double *states, double eps, int min_samples, bool to_host, const TrackArgs *track = nullptr)
+// li (and track: tk): as for fleet_track_table
+static int fleet_scan_run(rda_fleet *F, FleetLidar &li, const int32_t *n_beams, const double *ranges, const double *angle_min, const double *angle_max,
+                          const double *range_max, const double *states, double eps, int min_samples, bool to_host, const TrackArgs *track = nullptr,
+                          const FleetTracks *tk = nullptr)
 {
     const size_t B = F->B;
-    FleetLidar &li = F->li;
     size_t off = 0;
     for (size_t i = 0; i < B; ++i) {
         lidar::Args &a = li.args.h[i];
@@ -3612,10 +3683,9 @@ static int fleet_scan_run(rda_fleet *F, const int32_t *n_beams, const double *ra
     memcpy(li.h_ranges, ranges, off * sizeof(double));                  // one pinned copy of all ranges (off <= B * MAXB)
     HIPCHK(li.args.push(F->stream));
     hipLaunchKernelGGL(lidar::k_scan_fleet, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d);
-    if (track) fleet_track_launch(F, *track);                           // (in front of the wait: the tick gains a launch, no wait)
+    if (track) fleet_track_launch(F, *tk, *track);                      // (in front of the wait: the tick gains a launch, no wait)
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));
     return RDA_OK;
 }
 
@@ -3626,9 +3696,10 @@ extern "C" int rda_fleet_scan_boxes(rda_fleet *F, const int32_t *n_beams, const 
     if (!n_boxes || cap < 0 || (cap > 0 && !boxes)) return RDA_ERR_ARG;
     int rc = fleet_scan_check(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples);
     if (rc != RDA_OK) return rc;
-    rc = fleet_lidar_reserve(F, true);
-    if (rc != RDA_OK) return rc;
-    rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, true);
+    FleetReserve rsv(F);
+    rsv.need_lidar(true);
+    rc = rsv.adopt();
+    if (rc == RDA_OK) rc = fleet_scan_run(F, F->li, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, true);
     if (rc != RDA_OK) return rc;
     size_t off = 0;
     for (size_t i = 0; i < (size_t)F->B; ++i) {
@@ -3697,23 +3768,24 @@ static int fleet_upload_scans(rda_fleet *F, const int32_t *n_beams, const double
     if (rc == RDA_OK && track) rc = track_check(*track);
     if (rc != RDA_OK) return rc;
     const size_t B = F->B;
-    for (rda_handle *H : F->egos) if (H->tick.pending) return RDA_ERR_ARG;                // a member inside a tick of its own
-    for (rda_handle *H : F->egos) if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member)
-    const bool fresh = !F->li.have(), fresh_tk = track && !F->tk.have();
-    if (fresh_tk) { FleetTracks t; if (t.alloc(B)) return RDA_ERR_HIP; rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; F->tk = std::move(t); }
-    else rc = fleet_lidar_reserve(F, false);
-    if (rc != RDA_OK) return rc;
-    rc = fleet_refresh(F);                              // behind whatever the members still have queued
-    if (rc == RDA_OK && track) rc = fleet_track_table(F);
-    if (rc == RDA_OK) rc = fleet_scan_run(F, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false, track);
+    if (!fleet_members_idle(F)) return RDA_ERR_ARG;
+    if (fleet_duals_follow(F)) return RDA_ERR_UNSUPPORTED;
+    // The scan runs on the blocks of the reservation where the fleet has none yet: how many boxes it finds decides what else the call allocates, so the
+    // call can still be refused behind it (the blocks then go with the call; the tracks: not switched)
+    FleetReserve rsv(F);
+    if (track) rsv.need(&FleetSets::tk, B);
+    rsv.need_lidar(false);
+    rc = rsv.bad();
+    FleetLidar &li = rsv.now(&FleetSets::li);
+    const FleetTracks &tk = rsv.now(&FleetSets::tk);
+    if (rc == RDA_OK) rc = fleet_refresh(F);            // behind whatever the members still have queued
+    if (rc == RDA_OK && track) rc = fleet_track_table(F, li, tk);
+    if (rc == RDA_OK) rc = fleet_scan_run(F, li, n_beams, ranges, angle_min, angle_max, range_max, states, eps, min_samples, false, track, &tk);
     // larger raw scenes where a member needs one: allocated for all members before anything of any member changes
     std::vector<SceneGrow> grow(B);
-    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (F->li.h_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], F->li.h_count[2 * i], grow[i]);
-    if (rc != RDA_OK) {                                 // a failed call leaves what the fleet and the members hold as it was (the tracks: not switched)
-        if (fresh) F->li = FleetLidar();
-        if (fresh_tk) F->tk = FleetTracks();
-        return rc;
-    }
+    for (size_t i = 0; i < B && rc == RDA_OK; ++i) if (li.h_count[2 * i] > 0) rc = scene_grow_alloc(F->egos[i], li.h_count[2 * i], grow[i]);
+    if (rc == RDA_OK) rc = rsv.adopt();                 // (first-use sets: no wait)
+    if (rc != RDA_OK) return rc;
     if (track) F->tk.par ^= 1;
     rc = fleet_scan_stage(F, grow, states, nullptr, order, track != nullptr);
     if (rc != RDA_OK) return rc;
@@ -3743,25 +3815,26 @@ extern "C" int rda_fleet_track_boxes(rda_fleet *F, const int32_t *n, const doubl
     const size_t B = F->B;
     for (size_t i = 0; i < B; ++i) if (n[i] < 0 || n[i] > cap) return RDA_ERR_ARG;
     for (size_t i = 0; i < B; ++i) if (n[i] > lidar::MAXB) return RDA_ERR_UNSUPPORTED;
-    int rc;
-    if (!F->tk.have()) { FleetTracks nt; if (nt.alloc(B)) return RDA_ERR_HIP; rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; F->tk = std::move(nt); }
-    else { rc = fleet_lidar_reserve(F, false); if (rc != RDA_OK) return rc; }
-    HIPCHK(hipStreamSynchronize(F->stream));            // (a staging that is still queued may be reading the boxes of the last scan)
-    rc = fleet_track_table(F);
+    FleetReserve rsv(F);
+    rsv.need(&FleetSets::tk, B);
+    rsv.need_lidar(false);
+    int rc = rsv.adopt();
+    if (rc != RDA_OK) return rc;
+    HIPCHK(fleet_wait(F));                              // (a staging that is still queued may be reading the boxes of the last scan)
+    rc = fleet_track_table(F, F->li, F->tk);
     if (rc != RDA_OK) return rc;
     for (size_t i = 0; i < B; ++i) {
         F->li.h_count[2 * i] = n[i]; F->li.h_count[2 * i + 1] = 0;
         if (n[i] > 0) HIPCHK(hipMemcpyAsync(F->li.d_boxes + i * lidar::MAXB * 8, boxes + i * (size_t)cap * 8, (size_t)n[i] * 8 * sizeof(double), hipMemcpyHostToDevice, F->stream));
     }
-    fleet_track_launch(F, t);
+    fleet_track_launch(F, F->tk, t);
     HIPCHK(hipGetLastError());
     std::vector<double> v;
     if (vel_out) {
         v.resize(B * lidar::MAXB * 2);
         HIPCHK(hipMemcpyAsync(v.data(), F->tk.vel, v.size() * sizeof(double), hipMemcpyDeviceToHost, F->stream));
     }
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));
     F->tk.par ^= 1;
     if (vel_out) for (size_t i = 0; i < B; ++i) memcpy(vel_out + i * (size_t)cap * 2, v.data() + i * lidar::MAXB * 2, (size_t)n[i] * 2 * sizeof(double));
     return RDA_OK;
@@ -3780,8 +3853,7 @@ extern "C" int rda_fleet_box_tracks(rda_fleet *F, int cap, int32_t *n, double *c
     HIPCHK(hipMemcpyAsync(tk.h_len, tk.len + p * B * M, B * M * sizeof(int), hipMemcpyDeviceToHost, F->stream));
     HIPCHK(hipMemcpyAsync(tk.h_hist, tk.hist + p * B * M * lidar::TRK_HIST * 2, B * M * lidar::TRK_HIST * 2 * sizeof(double), hipMemcpyDeviceToHost, F->stream));
     HIPCHK(hipMemcpyAsync(tk.h_tvel, tk.tvel + p * B * M * 2, B * M * 2 * sizeof(double), hipMemcpyDeviceToHost, F->stream));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));
     for (size_t i = 0; i < B; ++i) {
         int c = tk.h_cnt[i]; c = c < 0 ? 0 : (c > (int)M ? (int)M : c);
         n[i] = c;
@@ -3836,11 +3908,10 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
 {
     if (!F || !states || !ref_speed || !cur_index || !out_u || !out_s || ind_range < 1) return RDA_ERR_ARG;
     const size_t T = F->T, ns = traj_s(T), nin = step_doubles(T), B = F->B;
-    if (!F->trk.have()) {                               // first use: the tables (zeroed) take their place once all of them exist
-        FleetTrack t;
-        if (t.alloc(B)) return RDA_ERR_HIP;
-        F->trk = std::move(t);
-    }
+    FleetReserve rsv(F);
+    rsv.need(&FleetSets::trk, B);
+    int rc = rsv.adopt();
+    if (rc != RDA_OK) return rc;
     // the result of the tick is written where the host reads it (round 6): k_finish_fleet and k_track_fleet store straight into the pinned blocks (write-only,
     // fire-and-forget stores over the link, complete at the end of their kernels) instead of three device-to-host copies queued behind the last launch
     // (~10 us each on the tick's critical path).  rda_opts::zero_copy = 0 on any member keeps the copies.
@@ -3855,10 +3926,10 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
     }
     const auto io = [&](size_t i) { return fleet_member_io(F, i, nom_u ? nullptr : F->egos[i]->d.u, out_base, info_base); };
     const bool tables = mirror_differs(trk.io, io) || mirror_differs(trk.paths, member_paths(F)) || mirror_differs(trk.lens, member_lens(F));
-    int rc = fleet_refresh(F);
+    rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     if (tables) {
-        HIPCHK(hipStreamSynchronize(F->stream));
+        HIPCHK(fleet_wait(F));
         HIPCHK(mirror_upload(trk.io, io, F->stream));
         HIPCHK(mirror_upload(trk.paths, member_paths(F), F->stream));
         HIPCHK(mirror_upload(trk.lens, member_lens(F), F->stream));
@@ -3875,8 +3946,7 @@ extern "C" int rda_fleet_step_tracked(rda_fleet *F, const double *states, const 
         HIPCHK(trk.out.pull(F->stream, B));
     }
     if (ref_out) HIPCHK(F->in.pull(F->stream, F->in.n));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;  // their staged scenes have been consumed
+    HIPCHK(fleet_wait(F, true));
     for (size_t i = 0; i < B; ++i) {
         fleet_result_out(F, i, out_u, out_s, info);
         if (ref_out) memcpy(ref_out + i * ns, F->in.h + i * nin + step_ref(T), ns * sizeof(double));
@@ -3896,6 +3966,11 @@ struct RollArgs {
     bool peers = false; const double *controls0 = nullptr; double *peer_clearance_log = nullptr;     // rda_fleet_rollout_peers
     bool plan = false; const double *plans0 = nullptr; const int32_t *plan_valid0 = nullptr;          // rda_fleet_rollout_peers_plan (with peers)
     bool gears = false; const int32_t *piece0 = nullptr; int32_t *piece_log = nullptr;                // rda_fleet_rollout_gears: ref_speed unsigned, cur_index within piece0
+    // the head every entry fills (a constructor: an entry that leaves one of them out does not compile)
+    RollArgs(int K, const double *states, const double *ref_speed, const int32_t *cur_index, double threshold, int ind_range, int goal_margin, const double *nom_u,
+             double *states_log, double *u_log, int32_t *index_log, rda_info *info_log, int32_t *arrived_at, double *clearance_log)
+        : K(K), states(states), ref_speed(ref_speed), cur_index(cur_index), threshold(threshold), ind_range(ind_range), goal_margin(goal_margin), nom_u(nom_u),
+          states_log(states_log), u_log(u_log), index_log(index_log), info_log(info_log), arrived_at(arrived_at), clearance_log(clearance_log) {}
 };
 // the argument rules every entry has: of the arrays and counts, and (roll_check_members) of the members' paths
 static int roll_check_args(const rda_fleet *F, const RollArgs &a)
@@ -3973,16 +4048,6 @@ static void fleet_move_view(const rda_fleet *F, MoveView &v, bool own = false)
         v.nmax = a.n > v.nmax ? a.n : v.nmax; v.wmax = a.N * a.nt > v.wmax ? a.N * a.nt : v.wmax;
     }
 }
-// a polygon robot whose consecutive rows intersect: what the clearance kernel takes
-static bool member_clearance_ok(const rda_handle *H)
-{
-    if (H->d.c.robot_norm2) return false;
-    const int R = H->d.c.R;
-    const double *G = H->rob_G.data();
-    for (int k = 0; k < R; ++k) { const int j = (k + R - 1) % R; if (G[2 * j] * G[2 * k + 1] - G[2 * j + 1] * G[2 * k] == 0) return false; }
-    return true;
-}
-
 // The peer table as the members stand now: every member's footprint and kinematics, and its tail where its scene came from the peers upload
 static void fleet_peer_view(const rda_fleet *F, std::vector<scene::Peer> &v)
 {
@@ -4011,33 +4076,26 @@ static void fleet_peers_launch(rda_fleet *F, const double *states, const double 
                        states, controls, B);
 }
 static_assert(sizeof(((scene::Peer *)nullptr)->rv) == sizeof(((rollout::Clear *)nullptr)->rv), "the peer table takes the clearance record's robot vertices");
-
-// What every rollout reserves before its first tick - the tracker's tables, the rollout tables, a log block of K ticks and (clearance) a clearance log of
-// K * B.  alloc: whatever of it the fleet lacks, beside the fleet, so that a refusal changes nothing; the entry allocates its own sets next to it and, when
-// all of it exists, calls move_in and moves its own.  wait: the entry replaces or rewrites more than these (a block that is replaced waits by itself).
-struct RollReserve {
-    FleetTrack trk; FleetRollTables tab; FleetRollLog log; FleetDoubles clr;
-    int alloc(const rda_fleet *F, int K, bool clearance)
-    {
-        const size_t B = F->B;
-        int rc = 0;
-        if (!F->trk.have()) rc |= trk.alloc(B);
-        if (!F->ro.have()) rc |= tab.alloc(B);
-        if (K > F->ro_log.cap) rc |= log.alloc(K, B, (size_t)F->T);
-        if (clearance && (size_t)K * B > F->cl_log.v.n) rc |= clr.alloc((size_t)K * B);
-        return rc ? RDA_ERR_HIP : RDA_OK;
-    }
-    int move_in(rda_fleet *F, bool wait)
-    {
-        if (wait || log.have() || clr.have()) HIPCHK(hipStreamSynchronize(F->stream));       // (a shorter block is freed below)
-        if (trk.have()) F->trk = std::move(trk);
-        if (tab.have()) F->ro = std::move(tab);
-        if (log.have()) F->ro_log = std::move(log);
-        if (clr.have()) F->cl_log = std::move(clr);
-        F->roll_K = 0; F->gear_total = 0;                                       // (until this rollout's logs are on the host)
-        return RDA_OK;
-    }
-};
+// the peer table as the members stand now -> device, when it differs from what the device holds
+static int fleet_peer_table(rda_fleet *F)
+{
+    std::vector<scene::Peer> pv;
+    fleet_peer_view(F, pv);
+    return fleet_table(F, F->pe.tab, records(pv));
+}
+// the peers' inputs of a host-driven refresh or of a rollout's tick 0 -> device: states [B][3], controls [B][2] and (plans non-null) the plans with
+// their validity
+static int fleet_peers_inputs(rda_fleet *F, const double *states, const double *controls, const double *plans, const int32_t *plan_valid)
+{
+    HIPCHK(F->pe.st.upload(states, F->stream)); HIPCHK(F->pe.ctl.upload(controls, F->stream));
+    if (plans) { HIPCHK(F->pl.plan.upload(plans, F->stream)); HIPCHK(F->pl.valid.upload(plan_valid, F->stream)); }
+    return RDA_OK;
+}
+// every member's separation from the nearest other member at states [B][3] in device memory -> out [B]
+static void fleet_peer_clearance_launch(rda_fleet *F, const double *states, double *out)
+{
+    hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)F->B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d, states, out, F->B);
+}
 
 // What every rollout entry does around its ticks.
 // The advance kernel's member table and the io tables of tick 0 | of the later ticks as the members stand now; true: they, or the members' paths, differ
@@ -4123,9 +4181,7 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     }
     HIPCHK(hipMemcpyAsync(F->ro_log.log.d + lay.last, F->out.d, B * res_info(T) * sizeof(double), hipMemcpyDeviceToDevice, F->stream));      // the last tick's full controls and planned states, beside the logs
     HIPCHK(F->ro_log.log.pull(F->stream, lay.bytes));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
-    for (rda_handle *Hm : F->egos) Hm->tick.pending_scene = 0;                  // their staged scenes have been consumed
+    HIPCHK(fleet_wait(F, true));
     F->roll_K = a.K; F->gear_total = (int)gear_total;
     if (a.gears) memcpy(a.piece_log, F->gr_log.v.h, K * B * sizeof(int32_t));
     memcpy(a.states_log, a.states, B * 3 * sizeof(double));                     // row 0: the input
@@ -4140,6 +4196,14 @@ static int fleet_roll_fetch(rda_fleet *F, const RollLayout &lay, const RollArgs 
     return RDA_OK;
 }
 
+// scene::k_move_fleet's grid for members of at most gmax = n * E doubles of geometry and (mv: the move table, null: nothing moves) the snapshot over it -
+// `base`: the geometry as the call finds it
+static dim3 fleet_move_grid(rda_fleet *F, int gmax, const scene::Move *mv)
+{
+    const dim3 gmove((unsigned)((gmax + 255) / 256), (unsigned)F->B);
+    if (mv) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, mv);
+    return gmove;
+}
 // rda_fleet_rollout (moving = false: exactly the static entry), rda_fleet_rollout_moving and (a.peers: resort and moving set) rda_fleet_rollout_peers share
 // this body
 static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, bool moving)
@@ -4155,10 +4219,8 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         for (size_t i = 0; i < B; ++i) if (!member_peers_scene(F, i)) return RDA_ERR_ARG;      // the scenes of rda_fleet_upload_scenes_peers, nothing staged since
     }
     for (const rda_handle *H : F->egos) if (resort && (H->sc.n <= 0 || H->d.obstacle_num == 0)) return RDA_ERR_ARG;
-    for (const rda_handle *H : F->egos) {
-        if (H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;                   // (k_follow_* are per member)
-        if (!moving && H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
-    }
+    if (fleet_duals_follow(F)) return RDA_ERR_UNSUPPORTED;
+    for (const rda_handle *H : F->egos) if (!moving && H->d.obstacle_num != 0 && H->d.nt > 1) return RDA_ERR_UNSUPPORTED;  // a scene that moves has to be uploaded again every tick
     MoveView mvw;
     if (moving) {
         for (const rda_handle *H : F->egos) {
@@ -4169,30 +4231,17 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         fleet_move_view(F, mvw, a.peers);
     }
     const bool peer_log = a.peers && a.peer_clearance_log && B > 1;
-    // whatever is missing is allocated beside the fleet; nothing of the fleet changes before all of it exists
-    RollReserve rsv; FleetResort tres; FleetMove tmov; FleetSnapshot tsnap; FleetDoubles tpc; FleetPlan tpl; FleetGears tgr; FleetInts tgl; FleetDoubles tge;
-    {
-        int bad = rsv.alloc(F, a.K, a.clearance_log != nullptr);
-        if (a.gears && !F->gr.have()) bad |= tgr.alloc(B);
-        if (a.gears && (size_t)a.K * B > F->gr_log.v.n) bad |= tgl.alloc((size_t)a.K * B);
-        if (a.gears && gear_total > F->gr_endh.v.n) bad |= tge.alloc(gear_total);
-        if (peer_log && (size_t)a.K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)a.K * B);
-        if (a.plan && !F->pl.have()) bad |= tpl.alloc(B, T);
-        if (resort && !F->res.have()) bad |= tres.alloc(B);
-        if (moving && !F->mov.have()) bad |= tmov.alloc(B);
-        if (moving && mvw.mv_total > F->snap.cap) bad |= tsnap.alloc(mvw.mv_total);
-        if (bad) return RDA_ERR_HIP;
-    }
-    rc = rsv.move_in(F, tsnap.have() || tpc.have() || tgl.have() || tge.have());
+    const size_t KB = (size_t)a.K * B;
+    FleetReserve rsv(F);
+    rsv.need_rollout(a.K, a.clearance_log != nullptr);
+    if (a.gears) { rsv.need(&FleetSets::gr, B); rsv.grow(&FleetSets::gr_log, KB, KB); rsv.grow(&FleetSets::gr_endh, gear_total, gear_total); }
+    if (peer_log) rsv.grow(&FleetSets::pc_log, KB, KB);
+    if (a.plan) rsv.need(&FleetSets::pl, B, T);
+    if (resort) rsv.need(&FleetSets::res, B);
+    if (moving) { rsv.need(&FleetSets::mov, B); rsv.grow(&FleetSets::snap, mvw.mv_total, mvw.mv_total); }
+    rc = rsv.adopt();
     if (rc != RDA_OK) return rc;
-    if (tgr.have()) F->gr = std::move(tgr);
-    if (tgl.have()) F->gr_log = std::move(tgl);
-    if (tge.have()) F->gr_endh = std::move(tge);
-    if (tpc.have()) F->pc_log = std::move(tpc);
-    if (tpl.have()) F->pl = std::move(tpl);
-    if (tres.have()) F->res = std::move(tres);
-    if (tmov.have()) F->mov = std::move(tmov);
-    if (tsnap.have()) F->snap = std::move(tsnap);
+    F->roll_K = 0; F->gear_total = 0;                                           // (until this rollout's logs are on the host)
     rc = fleet_refresh(F);
     if (rc != RDA_OK) return rc;
     // one-time table refreshes (the only other waits of a rollout): the tables are compared with what the device holds and uploaded when they differ
@@ -4205,7 +4254,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     std::vector<scene::Peer> pv;
     if (a.peers) { fleet_peer_view(F, pv); if (mirror_differs(F->pe.tab, records(pv))) tables = true; }
     if (tables) {
-        HIPCHK(hipStreamSynchronize(F->stream));
+        HIPCHK(fleet_wait(F));
         if (a.peers) HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
         if (moving) {
             HIPCHK(mirror_upload(F->mov.mv, records(mvw.mv), F->stream));
@@ -4219,12 +4268,8 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
     int nmax = 0, wmax = 0;
     if (resort) { rc = fleet_resort_positions(F, a.states, 3, nmax, wmax); if (rc != RDA_OK) return rc; }
     if (a.peers) {                                                              // (behind fleet_resort_positions: no copy out of the pinned mirrors is queued)
-        memcpy(F->pe.st.h, a.states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, a.controls0, 2 * B * sizeof(double));
-        HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
-    }
-    if (a.plan) {
-        memcpy(F->pl.plan.h, a.plans0, B * traj_s(T) * sizeof(double)); memcpy(F->pl.valid.h, a.plan_valid0, B * sizeof(int));
-        HIPCHK(F->pl.plan.push(F->stream)); HIPCHK(F->pl.valid.push(F->stream));
+        rc = fleet_peers_inputs(F, a.states, a.controls0, a.plan ? a.plans0 : nullptr, a.plan_valid0);
+        if (rc != RDA_OK) return rc;
     }
     const RollLayout lay = roll_layout((size_t)a.K, B, T);
     rollout::Logs lg;
@@ -4245,8 +4290,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         gt = rollout::GearTab{ F->gr.rec.d, F->gr.piece.d, F->gr.paths.d, F->gr.lens.d, F->gr_log.v.d };
     }
     const bool moves = moving && mvw.gmax > 0;
-    const dim3 gmove((unsigned)((mvw.gmax + 255) / 256), (unsigned)B);
-    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)F->mov.mv.d);      // `base`: the geometry as the call finds it
+    const dim3 gmove = fleet_move_grid(F, mvw.gmax, moves ? F->mov.mv.d : nullptr);
     for (int k = 0; k < a.K; ++k) {
         // the peer rows of tick k: the members' states at its start and the controls applied one tick earlier (tick 0: the caller's, then the device logs)
         if (a.peers) fleet_peers_launch(F, k == 0 ? F->pe.st.d : lg.states + (size_t)k * B * 3, k == 0 ? F->pe.ctl.d : lg.u + (size_t)(k - 1) * B * 2);
@@ -4258,9 +4302,7 @@ static int fleet_rollout_scenes(rda_fleet *F, const RollArgs &a, int resort, boo
         rc = fleet_roll_tail(F, k, lg, a.goal_margin, resort ? F->res.rob.d : nullptr, moves ? F->mov.mv.d : nullptr, gmove,
                              a.clearance_log ? F->mov.cl.d : nullptr, a.gears ? &gt : nullptr);
         if (rc != RDA_OK) return rc;
-        if (peer_log)
-            hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
-                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->pc_log.v.d + (size_t)k * B, (int)B);
+        if (peer_log) fleet_peer_clearance_launch(F, lg.states + (size_t)(k + 1) * B * 3, F->pc_log.v.d + (size_t)k * B);
     }
     HIPCHK(hipGetLastError());
     return fleet_roll_fetch(F, lay, a);                                         // the rollout's one wait
@@ -4307,36 +4349,24 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
 {
     if (!F || !states || !clearance) return RDA_ERR_ARG;
     const size_t B = F->B;
-    for (const rda_handle *H : F->egos) {
-        if (H->tick.pending) return RDA_ERR_ARG;
-        if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
-    }
-    FleetMove tmov; FleetDoubles tclr;
-    {
-        int bad = 0;
-        if (!F->mov.have()) bad |= tmov.alloc(B);
-        if (B > F->cl_log.v.n) bad |= tclr.alloc(B);
-        if (bad) return RDA_ERR_HIP;
-    }
-    if (tclr.have()) HIPCHK(hipStreamSynchronize(F->stream));
-    if (tmov.have()) F->mov = std::move(tmov);
-    if (tclr.have()) F->cl_log = std::move(tclr);
-    int rc = fleet_refresh(F);                          // behind whatever the members still have queued
+    int rc = fleet_check_clearance_call(F);
+    if (rc != RDA_OK) return rc;
+    FleetReserve rsv(F);
+    rsv.need(&FleetSets::mov, B);
+    rsv.grow(&FleetSets::cl_log, B, B);
+    rc = rsv.adopt();
+    if (rc == RDA_OK) rc = fleet_refresh(F);            // behind whatever the members still have queued
     if (rc != RDA_OK) return rc;
     MoveView v;
     fleet_move_view(F, v);
-    if (mirror_differs(F->mov.cl, records(v.cl))) {
-        HIPCHK(hipStreamSynchronize(F->stream));
-        HIPCHK(mirror_upload(F->mov.cl, records(v.cl), F->stream));
-    }
-    memcpy(F->mov.st.h, states, 3 * B * sizeof(double));
-    HIPCHK(F->mov.st.push(F->stream));
+    rc = fleet_table(F, F->mov.cl, records(v.cl));
+    if (rc != RDA_OK) return rc;
+    HIPCHK(F->mov.st.upload(states, F->stream));
     hipLaunchKernelGGL(rollout::k_clearance_fleet, dim3((unsigned)B), dim3(rollout::CLEAR_NT), 0, F->stream, (const rollout::Clear *)F->mov.cl.d,
                        (const double *)F->mov.st.d, F->cl_log.v.d, (int)B);
     HIPCHK(hipGetLastError());
     HIPCHK(F->cl_log.v.pull(F->stream, B));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));
     memcpy(clearance, F->cl_log.v.h, B * sizeof(double));
     return RDA_OK;
 }
@@ -4345,18 +4375,12 @@ extern "C" int rda_fleet_clearance(rda_fleet *F, const double *states, double *c
 // plans (null: the constant-velocity mode): with plan_valid into the fleet's staging buffers, and scene::k_build_plan_fleet builds the slots
 static int fleet_peers_resort(rda_fleet *F, const double *states, const double *controls, const double *plans, const int32_t *plan_valid)
 {
-    const size_t B = F->B, T = F->T;
     int nmax = 0, wmax = 0;
     int rc = fleet_resort_positions(F, states, 3, nmax, wmax);                  // (waits for an earlier copy out of the pinned mirrors)
+    if (rc == RDA_OK) rc = fleet_peers_inputs(F, states, controls, plans, plan_valid);
     if (rc != RDA_OK) return rc;
-    memcpy(F->pe.st.h, states, 3 * B * sizeof(double)); memcpy(F->pe.ctl.h, controls, 2 * B * sizeof(double));
-    HIPCHK(F->pe.st.push(F->stream)); HIPCHK(F->pe.ctl.push(F->stream));
-    if (plans) {
-        memcpy(F->pl.plan.h, plans, B * traj_s(T) * sizeof(double)); memcpy(F->pl.valid.h, plan_valid, B * sizeof(int));
-        HIPCHK(F->pl.plan.push(F->stream)); HIPCHK(F->pl.valid.push(F->stream));
-    }
     fleet_peers_launch(F, F->pe.st.d, F->pe.ctl.d);
-    const scene::Plan pk{ F->pe.st.d, F->pl.plan.d, traj_s(T), F->pl.valid.d, nullptr };
+    const scene::Plan pk{ F->pe.st.d, F->pl.plan.d, traj_s((size_t)F->T), F->pl.valid.d, nullptr };
     fleet_resort_launch(F, F->res.sc.d, F->res.rob.d, nmax, wmax, plans ? &pk : nullptr);
     HIPCHK(hipGetLastError());
     return RDA_OK;
@@ -4373,30 +4397,23 @@ static int fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const 
     size_t total = 0;
     for (size_t i = 0; i < B; ++i) { if (counts[i] < 0) return RDA_ERR_ARG; total += (size_t)counts[i]; }
     if (total && (!kind || !nvert || !geom || !vel)) return RDA_ERR_ARG;
-    for (const rda_handle *H : F->egos) if (H->tick.pending) return RDA_ERR_ARG;                       // a member inside a tick of its own
-    for (const rda_handle *H : F->egos)
-        if (H->d.c.robot_norm2 || !member_clearance_ok(H) || R > E || H->opts.duals_follow) return RDA_ERR_UNSUPPORTED;      // (a footprint is a polygon row of R <= E vertices)
+    if (!fleet_members_idle(F)) return RDA_ERR_ARG;
+    if (!fleet_clearance_ok(F) || R > E || fleet_duals_follow(F)) return RDA_ERR_UNSUPPORTED;         // (a footprint is a polygon row of R <= E vertices)
     for (size_t e = 0; e < total; ++e) {                                        // scene_stage's rules
         if (kind[e] == 1) { if (E < 3) return RDA_ERR_UNSUPPORTED; }
         else if (kind[e] != 0 || nvert[e] < 0 || nvert[e] > E) return RDA_ERR_ARG;
     }
     if (B == 1 && counts[0] == 0) { F->egos[0]->d.obstacle_num = 0; return RDA_OK; }      // nothing written: stale A, b stay (rda_upload_scene with n = 0)
-    FleetPeers tpe; FleetResort tres; FleetPlan tpl; std::vector<SceneGrow> grow(B);
-    {
-        int bad = 0;
-        if (!F->pe.have()) bad |= tpe.alloc(B);
-        if (plan && !F->pl.have()) bad |= tpl.alloc(B, (size_t)T);
-        if (!F->res.have()) bad |= tres.alloc(B);
-        for (size_t i = 0; i < B; ++i) bad |= scene_grow_alloc(F->egos[i], counts[i] + (int)B - 1, grow[i]);
-        if (bad) return RDA_ERR_HIP;
-    }
-    int rc = fleet_refresh(F);                          // behind whatever the members still have queued ...
+    FleetReserve rsv(F);
+    std::vector<SceneGrow> grow(B);
+    rsv.need(&FleetSets::pe, B);
+    if (plan) rsv.need(&FleetSets::pl, B, (size_t)T);
+    rsv.need(&FleetSets::res, B);
+    for (size_t i = 0; i < B; ++i) rsv.refused |= scene_grow_alloc(F->egos[i], counts[i] + (int)B - 1, grow[i]);
+    int rc = rsv.bad();
+    if (rc == RDA_OK) rc = fleet_refresh(F);            // behind whatever the members still have queued ...
+    if (rc == RDA_OK) rc = rsv.adopt(true);             // ... and done: the members' pinned staging blocks are free
     if (rc != RDA_OK) return rc;
-    HIPCHK(hipStreamSynchronize(F->stream));            // ... and done: the members' pinned staging blocks are free
-    F->rob_pending = 0;
-    if (tpe.have()) F->pe = std::move(tpe);
-    if (tpl.have()) F->pl = std::move(tpl);
-    if (tres.have()) F->res = std::move(tres);
     F->n_own.assign(counts, counts + B);
     size_t off = 0;
     for (size_t i = 0; i < B; ++i) {
@@ -4429,8 +4446,7 @@ static int fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const 
     fleet_refresh_flags(F);
     rc = fleet_peers_resort(F, states, controls, plan ? plans : nullptr, plan_valid);
     if (rc != RDA_OK) return rc;
-    HIPCHK(hipStreamSynchronize(F->stream));            // the staging blocks are reused by the next call; the members' own calls see the scene
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));                              // the staging blocks are reused by the next call; the members' own calls see the scene
     return RDA_OK;
 }
 extern "C" int rda_fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const int32_t *kind, const int32_t *nvert, const double *geom,
@@ -4452,19 +4468,12 @@ static int fleet_scene_resort_peers(rda_fleet *F, const double *states, const do
         if (!member_peers_scene(F, i) || F->egos[i]->tick.pending) return RDA_ERR_ARG;
         if (F->egos[i]->opts.duals_follow) return RDA_ERR_UNSUPPORTED;
     }
-    if (plan && !F->pl.have()) {                        // first use: the staging buffers take their place once all of them exist
-        FleetPlan t;
-        if (t.alloc((size_t)F->B, (size_t)F->T)) return RDA_ERR_HIP;
-        F->pl = std::move(t);
-    }
-    int rc = fleet_refresh(F);
+    FleetReserve rsv(F);
+    if (plan) rsv.need(&FleetSets::pl, (size_t)F->B, (size_t)F->T);
+    int rc = rsv.adopt();
+    if (rc == RDA_OK) rc = fleet_refresh(F);
+    if (rc == RDA_OK) rc = fleet_peer_table(F);
     if (rc != RDA_OK) return rc;
-    std::vector<scene::Peer> pv;
-    fleet_peer_view(F, pv);
-    if (mirror_differs(F->pe.tab, records(pv))) {
-        HIPCHK(hipStreamSynchronize(F->stream));
-        HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
-    }
     return fleet_peers_resort(F, states, controls, plan ? plans : nullptr, plan_valid);
 }
 extern "C" int rda_fleet_scene_resort_peers(rda_fleet *F, const double *states, const double *controls)
@@ -4501,34 +4510,20 @@ extern "C" int rda_fleet_peer_clearance(rda_fleet *F, const double *states, doub
 {
     if (!F || !states || !out) return RDA_ERR_ARG;
     const size_t B = F->B;
-    for (const rda_handle *H : F->egos) {
-        if (H->tick.pending) return RDA_ERR_ARG;
-        if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
-    }
+    int rc = fleet_check_clearance_call(F);
+    if (rc != RDA_OK) return rc;
     if (B == 1) { out[0] = INFINITY; return RDA_OK; }  // no peer, no launch
-    FleetPeers tpe; FleetDoubles tpc;
-    {
-        int bad = 0;
-        if (!F->pe.have()) bad |= tpe.alloc(B);
-        if (B > F->pc_log.v.n) bad |= tpc.alloc(B);
-        if (bad) return RDA_ERR_HIP;
-    }
-    if (tpc.have() || F->rob_pending) { HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; }
-    if (tpe.have()) F->pe = std::move(tpe);
-    if (tpc.have()) F->pc_log = std::move(tpc);
-    std::vector<scene::Peer> pv;
-    fleet_peer_view(F, pv);
-    if (mirror_differs(F->pe.tab, records(pv))) {
-        HIPCHK(hipStreamSynchronize(F->stream));
-        HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
-    }
-    memcpy(F->pe.st.h, states, 3 * B * sizeof(double));
-    HIPCHK(F->pe.st.push(F->stream));
-    hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d, (const double *)F->pe.st.d,
-                       F->pc_log.v.d, (int)B);
+    FleetReserve rsv(F);
+    rsv.need(&FleetSets::pe, B);
+    rsv.grow(&FleetSets::pc_log, B, B);
+    rc = rsv.adopt(F->rob_pending != 0);                // (pe.st below: the states of a re-sort that is still queued)
+    if (rc == RDA_OK) rc = fleet_peer_table(F);
+    if (rc != RDA_OK) return rc;
+    HIPCHK(F->pe.st.upload(states, F->stream));
+    fleet_peer_clearance_launch(F, F->pe.st.d, F->pc_log.v.d);
     HIPCHK(hipGetLastError());
     HIPCHK(F->pc_log.v.pull(F->stream, B));
-    HIPCHK(hipStreamSynchronize(F->stream));
+    HIPCHK(fleet_wait(F));
     memcpy(out, F->pc_log.v.h, B * sizeof(double));
     return RDA_OK;
 }
@@ -4547,17 +4542,17 @@ extern "C" int rda_fleet_upload_worlds(rda_fleet *F, const int32_t *counts, int 
         if (kind[j] == 0) { if (nvert[j] < 3 || nvert[j] > we) return RDA_ERR_ARG; }
         else if (kind[j] != 1) return RDA_ERR_ARG;
     }
-    FleetWorld w;
-    if (w.alloc(B, counts, we)) return RDA_ERR_HIP;
+    FleetReserve rsv(F);
+    rsv.fresh(&FleetSets::world, B, counts, we);
+    if (rsv.bad()) return RDA_ERR_HIP;
+    FleetWorld &w = rsv.s.world;
     if (total > 0) {
         HIPCHK(hipMemcpy(w.geom, geom, total * we * 2 * sizeof(double), hipMemcpyHostToDevice));
         if (vel) HIPCHK(hipMemcpy(w.vel, vel, total * 2 * sizeof(double), hipMemcpyHostToDevice));   // (NULL: the zeros of the allocation - a standing world)
         HIPCHK(hipMemcpy(w.kind, kind, total * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(w.nvert, nvert, total * sizeof(int), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipStreamSynchronize(F->stream));              // a ray cast of the old world may still be queued
-    F->world = std::move(w);
-    return RDA_OK;
+    return rsv.adopt();                                   // (waits where there is an old world: a ray cast of it may still be queued)
 }
 
 // test hook: the resident worlds' geometry as it stands, member-major [total][we][2]
@@ -4568,7 +4563,7 @@ extern "C" int rda_debug_fleet_world(rda_fleet *F, double *geom, int32_t *n_tota
     *n_total = (int32_t)w.total;
     if (we) *we = w.e;
     if (w.total == 0 || !geom) return RDA_OK;
-    HIPCHK(hipStreamSynchronize(F->stream));
+    HIPCHK(fleet_wait(F));
     HIPCHK(hipMemcpy(geom, w.geom, w.total * w.e * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return RDA_OK;
 }
@@ -4615,16 +4610,6 @@ static void fleet_ray_launch(rda_fleet *F, const double *poses, int maxb, bool s
     else
         hipLaunchKernelGGL(lidar::k_raycast_fleet, grid, dim3(lidar::RAY_NT), 0, F->stream, (const lidar::Ray *)F->world.ray.d, poses);
 }
-// the peer table as the members stand now -> device, when it differs from what the device holds (the wait: an earlier copy out of the mirror may be queued)
-static int fleet_peer_table(rda_fleet *F)
-{
-    std::vector<scene::Peer> pv;
-    fleet_peer_view(F, pv);
-    if (!mirror_differs(F->pe.tab, records(pv))) return RDA_OK;
-    HIPCHK(hipStreamSynchronize(F->stream));
-    HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
-    return RDA_OK;
-}
 
 // the resident worlds as they stand (see: and the other members at `states`), ray-cast from states [B][3]: one launch, one wait
 static int fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *angle_min, const double *angle_max, const double *range_min,
@@ -4634,28 +4619,20 @@ static int fleet_raycast(rda_fleet *F, const int32_t *n_beams, const double *ang
     int rc = fleet_ray_check(F, n_beams, angle_min, angle_max, range_min, range_max, total);
     if (rc != RDA_OK) return rc;
     if (!states || (total > 0 && !ranges)) return RDA_ERR_ARG;
-    const size_t B = F->B;
-    if (see) for (const rda_handle *H : F->egos) if (!member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;      // (a footprint needs the vertices of a polygon robot)
-    FleetDoubles t; FleetPeers tpe;
-    {
-        int bad = 0;
-        if (total > F->rays.v.n) bad |= t.alloc(total);
-        if (see && !F->pe.have()) bad |= tpe.alloc(B);
-        if (bad) return RDA_ERR_HIP;
-    }
-    if (t.have()) { HIPCHK(hipStreamSynchronize(F->stream)); F->rays = std::move(t); }
-    if (tpe.have()) F->pe = std::move(tpe);
-    if (see) { rc = fleet_peer_table(F); if (rc != RDA_OK) return rc; }
+    if (see && !fleet_clearance_ok(F)) return RDA_ERR_UNSUPPORTED;               // (a footprint needs the vertices of a polygon robot)
+    FleetReserve rsv(F);
+    rsv.grow(&FleetSets::rays, total, total);
+    if (see) rsv.need(&FleetSets::pe, (size_t)F->B);
+    rc = rsv.adopt();
+    if (rc == RDA_OK && see) rc = fleet_peer_table(F);
     int maxb = 0;
-    rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
+    if (rc == RDA_OK) rc = fleet_ray_table(F, n_beams, angle_min, angle_max, range_min, range_max, maxb);
     if (rc != RDA_OK) return rc;
-    memcpy(F->world.st.h, states, 3 * B * sizeof(double));
-    HIPCHK(F->world.st.push(F->stream));
+    HIPCHK(F->world.st.upload(states, F->stream));
     fleet_ray_launch(F, F->world.st.d, maxb, see);
     HIPCHK(hipGetLastError());
     if (total > 0) HIPCHK(F->rays.v.pull(F->stream, total));
-    HIPCHK(hipStreamSynchronize(F->stream));
-    F->rob_pending = 0;
+    HIPCHK(fleet_wait(F));
     if (total > 0) memcpy(ranges, F->rays.v.h, total * sizeof(double));
     return RDA_OK;
 }
@@ -4695,34 +4672,26 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
     if (rc != RDA_OK) return rc;
     const size_t T = F->T, B = F->B;
     const int K = a.K;
-    for (const rda_handle *H : F->egos) {
-        if (H->opts.duals_follow || H->d.c.E < 4) return RDA_ERR_UNSUPPORTED;   // (k_follow_* are per member; a box has four vertices)
-        if ((a.clearance_log || see) && !member_clearance_ok(H)) return RDA_ERR_UNSUPPORTED;
-    }
+    if (fleet_duals_follow(F) || F->egos[0]->d.c.E < 4) return RDA_ERR_UNSUPPORTED;      // (a box has four vertices)
+    if ((a.clearance_log || see) && !fleet_clearance_ok(F)) return RDA_ERR_UNSUPPORTED;
     const bool peer_log = see && a.peer_clearance_log && B > 1;
-    // whatever is missing is allocated beside the fleet and the members; nothing of them changes before all of it exists
-    RollReserve rsv; FleetDoubles tray, tpc; FleetPeers tpe; FleetTracks ttk;
-    std::vector<SceneGrow> grow(B), none(B);                                    // a raw scene for the most boxes a member's beams can give | per tick: nothing to grow
-    {
-        int bad = rsv.alloc(F, K, a.clearance_log != nullptr);
-        if (track && !F->tk.have()) bad |= ttk.alloc(B);
-        if (total > F->rays.v.n) bad |= tray.alloc(total);
-        if (see && !F->pe.have()) bad |= tpe.alloc(B);
-        if (peer_log && (size_t)K * B > F->pc_log.v.n) bad |= tpc.alloc((size_t)K * B);
-        for (size_t i = 0; i < B && !bad; ++i) if (s.n_beams[i] > 0) bad |= scene_grow_alloc(F->egos[i], s.n_beams[i], grow[i]);
-        if (!bad) bad |= fleet_lidar_reserve(F, false);                         // (last: what it makes stays with the fleet)
-        if (bad) return RDA_ERR_HIP;
-    }
-    rc = fleet_refresh(F);                                                      // behind whatever the members still have queued
+    // a raw scene for the most boxes a member's beams can give, beside the members as the sets are beside the fleet | per tick: nothing to grow
+    FleetReserve rsv(F);
+    std::vector<SceneGrow> grow(B), none(B);
+    rsv.need_rollout(K, a.clearance_log != nullptr);
+    if (track) rsv.need(&FleetSets::tk, B);
+    rsv.grow(&FleetSets::rays, total, total);
+    if (see) rsv.need(&FleetSets::pe, B);
+    if (peer_log) rsv.grow(&FleetSets::pc_log, (size_t)K * B, (size_t)K * B);
+    for (size_t i = 0; i < B; ++i) if (s.n_beams[i] > 0) rsv.refused |= scene_grow_alloc(F->egos[i], s.n_beams[i], grow[i]);
+    rsv.need_lidar(false);
+    rc = rsv.bad();
+    if (rc == RDA_OK) rc = fleet_refresh(F);                                    // behind whatever the members still have queued
+    if (rc == RDA_OK) rc = rsv.adopt(true);                                     // (the lidar ticks rewrite the pinned tables whatever they hold)
     if (rc != RDA_OK) return rc;
-    rc = rsv.move_in(F, true);                                                  // (the wait: shorter blocks are freed; the pinned tables are rewritten)
-    if (rc != RDA_OK) return rc;
-    if (tray.have()) F->rays = std::move(tray);
-    if (tpe.have()) F->pe = std::move(tpe);
-    if (tpc.have()) F->pc_log = std::move(tpc);
-    if (ttk.have()) F->tk = std::move(ttk);
+    F->roll_K = 0; F->gear_total = 0;                                           // (until this rollout's logs are on the host)
     for (size_t i = 0; i < B; ++i) scene_grow_commit(F->egos[i], grow[i]);
-    if (track) { rc = fleet_track_table(F); if (rc != RDA_OK) return rc; }
+    if (track) { rc = fleet_track_table(F, F->li, F->tk); if (rc != RDA_OK) return rc; }
     RollView rv;
     if (fleet_roll_view(F, a.nom_u != nullptr, rv)) { rc = fleet_roll_upload(F, rv); if (rc != RDA_OK) return rc; }
     if (see) { rc = fleet_peer_table(F); if (rc != RDA_OK) return rc; }
@@ -4757,23 +4726,20 @@ static int fleet_rollout_lidar(rda_fleet *F, const RollArgs &a, const LidarArgs 
     HIPCHK(w.mv.push(F->stream));
     HIPCHK(w.cl.push(F->stream));
     const bool moves = s.moving && gmax > 0;
-    const dim3 gmove((unsigned)((gmax + 255) / 256), (unsigned)B);
-    if (moves) hipLaunchKernelGGL(scene::k_snapshot_fleet, gmove, dim3(256), 0, F->stream, (const scene::Move *)w.mv.d);       // `base`: the world as the call finds it
+    const dim3 gmove = fleet_move_grid(F, gmax, moves ? w.mv.d : nullptr);
     for (int k = 0; k < K; ++k) {
         const double *pose = lg.states + (size_t)k * B * 3;                     // where the advance kernel of tick k - 1 wrote the states
         for (size_t i = 0; i < B; ++i) { li.h_count[2 * i] = 0; li.h_count[2 * i + 1] = 0; }
         fleet_ray_launch(F, pose, maxb, see);
         hipLaunchKernelGGL(lidar::k_scan_fleet_at, dim3((unsigned)B), dim3(lidar::NT), lidar::LDS_BYTES, F->stream, (const lidar::Args *)li.args.d, pose);
-        if (track) { fleet_track_launch(F, *track); F->tk.par ^= 1; }
+        if (track) { fleet_track_launch(F, F->tk, *track); F->tk.par ^= 1; }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(F->stream));                                // the tick's one wait: the B box counts
+        HIPCHK(fleet_wait(F));                                                  // the tick's one wait: the B box counts
         if (s.nbox_log) for (size_t i = 0; i < B; ++i) s.nbox_log[(size_t)k * B + i] = li.h_count[2 * i];
         rc = fleet_scan_stage(F, none, nullptr, pose, s.order, track != nullptr);
         if (rc == RDA_OK) rc = fleet_roll_tail(F, k, lg, a.goal_margin, nullptr, moves ? w.mv.d : nullptr, gmove, a.clearance_log ? w.cl.d : nullptr);
         if (rc != RDA_OK) return rc;
-        if (peer_log)
-            hipLaunchKernelGGL(rollout::k_peer_clearance_fleet, dim3((unsigned)B), dim3(64), 0, F->stream, (const scene::Peer *)F->pe.tab.d,
-                               (const double *)(lg.states + (size_t)(k + 1) * B * 3), F->pc_log.v.d + (size_t)k * B, (int)B);
+        if (peer_log) fleet_peer_clearance_launch(F, lg.states + (size_t)(k + 1) * B * 3, F->pc_log.v.d + (size_t)k * B);
     }
     HIPCHK(hipGetLastError());
     return fleet_roll_fetch(F, lay, a);
@@ -4852,7 +4818,7 @@ extern "C" int rda_fleet_enqueue_range(rda_fleet *F, int k0, int k1)
     return RDA_OK;
 }
 
-extern "C" int rda_fleet_sync(rda_fleet *F) { if (!F) return RDA_ERR_ARG; HIPCHK(hipStreamSynchronize(F->stream)); F->rob_pending = 0; return RDA_OK; }
+extern "C" int rda_fleet_sync(rda_fleet *F) { if (!F) return RDA_ERR_ARG; HIPCHK(fleet_wait(F)); return RDA_OK; }
 extern "C" int rda_fleet_size(rda_fleet *F) { return F ? F->B : RDA_ERR_ARG; }
 
 // ---- pure-function hooks ------------------------------------------------------------------------

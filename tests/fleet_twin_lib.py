@@ -2,6 +2,7 @@
 obstacle motion, the comparison of a rollout's logs with host-driven ticks, and `FleetTwin`, the fleet of fresh handles every test file derives its own
 twin from.  T = 8, N = 4 slots, E = 4, iter_num = 2, dt = 0.1; B = 3 (Ackermann, differential, omni) on straight lanes 8 m apart with 7 obstacles each."""
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -73,6 +74,36 @@ def solver(hip, e, order=1, path=True, scene=True, robot=None, lane=lane, **kw):
     if scene:
         assert hip.upload_scene(sv._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(st), order, None) == 0
     return sv, st, len(pts), (kind, nvert, geom, vel)
+
+
+def bare_fleet(hip, cars, t=5):
+    """rda_fleet_create of fresh handles of `cars` (T = t, N = 4, E = 4): no path, no scene, none of the fleet's on-demand tables -> (solvers, fleet)"""
+    from rda_planner_amd.rda_solver import RDA_solver
+    svs = [RDA_solver(t, c, 4, 4, iter_num=ITER, step_time=DT, time_print=False) for c in cars]
+    F = C.c_void_p()
+    assert hip.fleet_create((C.c_void_p * len(svs))(*[s._be.handle for s in svs]), len(svs), C.byref(F)) == 0
+    return svs, F
+
+
+def refused_in_turn(hip, call, limit=40):
+    """call() -> rc with its allocation 0, 1, ... refused by the host-side hook, until it is not refused: every refusal is RDA_ERR_HIP and leaves the
+    live-allocation counters (rda_debug_alloc_stats) where they were -> (the last rc, the number of refusals)"""
+    def live():
+        n, by = C.c_longlong(0), C.c_longlong(0)
+        assert hip.debug_alloc_stats(C.byref(n), C.byref(by)) == 0
+        return n.value, by.value
+    gc.collect()                                                           # no handle of an earlier test is released while this one counts
+    for k in range(limit):
+        before = live()
+        hip.debug_alloc_fail(k)
+        try:
+            rc = call()
+        finally:
+            hip.debug_alloc_fail(-1)
+        if rc != RDA_ERR_HIP:
+            return rc, k
+        assert live() == before, (k, before, live())
+    return RDA_ERR_HIP, limit
 
 
 def info_tuple(i):

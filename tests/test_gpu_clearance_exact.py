@@ -23,6 +23,7 @@ import clear_grid as grid
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr, iptr
 
+from fleet_twin_lib import bare_fleet, refused_in_turn
 from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -283,3 +284,32 @@ def test_untouched_paths(hip):
     f.close()
     g = Fleet(hip, [sc.circle_robot(0.8, dynamics="diff")])
     assert g.rc == RDA_ERR_UNSUPPORTED
+
+
+# ---- 5 ----------------------------------------------------------------------------------------------------------------------------------------------
+def test_refused_allocations_of_a_first_clearance_call_change_nothing(hip):
+    """a fleet's first rda_fleet_clearance makes its move tables and the clearance log: refused at each of the 10 allocations in turn it returns
+    RDA_ERR_HIP and holds nothing more than before; the call that gets through returns the doubles of an undisturbed twin.  B = 2, T = 5, N = 4, E = 4,
+    three and two polygons."""
+    cars = [sc.rectangle_robot(dynamics="acker"), sc.rectangle_robot(dynamics="diff", wheelbase=0)]
+    states = np.array([[10.0, 20.0, 0.3], [14.0, 28.0, 1.4]])
+    scenes = [[sc.regular_polygon(13.0, 21.0, 4, 0.8, 0.2), sc.regular_polygon(8.0, 23.0, 3, 0.7, 1.0), sc.regular_polygon(10.5, 20.2, 4, 0.5, 0.4)],
+              [sc.regular_polygon(15.0, 31.0, 3, 0.9, 0.1), sc.regular_polygon(11.0, 27.0, 4, 0.6, 0.7)]]
+
+    def staged():
+        svs, F = bare_fleet(hip, cars)
+        flat = [sv.flatten_scene(list(s)) for sv, s in zip(svs, scenes)]
+        counts = np.array([f[0] for f in flat], np.int32)
+        kind, nvert = (np.ascontiguousarray(np.concatenate([f[j] for f in flat]), np.int32) for j in (1, 2))
+        geom, vel = (np.ascontiguousarray(np.concatenate([f[j] for f in flat]), float) for j in (3, 4))
+        assert hip.fleet_upload_scenes(F, iptr(counts), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(np.ascontiguousarray(states[:, 0:2])),
+                                       iptr(np.ones(2, np.int32))) == 0
+        return svs, F
+    (sa, fa), (sb, fb) = staged(), staged()
+    got, want = np.full(2, np.nan), np.full(2, np.nan)
+    rc, refused = refused_in_turn(hip, lambda: hip.fleet_clearance(fa, dptr(states), dptr(got)))
+    print("allocations of a fleet's first rda_fleet_clearance:", refused)
+    assert rc == 0 and refused == 10
+    assert hip.fleet_clearance(fb, dptr(states), dptr(want)) == 0
+    assert np.array_equal(got, want) and np.all(np.isfinite(want))
+    hip.fleet_destroy(fa); hip.fleet_destroy(fb)

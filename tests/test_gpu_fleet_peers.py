@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from fleet_twin_lib import DT, DYN, E, ITER, MARGIN, N, RDA_ERR_ARG, RDA_ERR_HIP, RDA_ERR_UNSUPPORTED, T, FleetTwin, advanced, compare_ticks, info_tuple, same_logs
+from fleet_twin_lib import bare_fleet, refused_in_turn
 from fleet_twin_lib import hip          # noqa: F401  (the fixture)
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr, iptr
@@ -340,6 +341,19 @@ def test_refused_allocation_leaves_the_resident_scenes(hip):
     assert rc == 0 and n - 1 >= 3
     assert small.scene(0)[0].shape[0] == 32 and np.array_equal(small.scene(2)[0][:30], big.base[60:90])
     small.close(); big.close()
+
+
+def test_refused_allocations_of_a_first_peer_clearance_call_change_nothing(hip):
+    """rda_fleet_peer_clearance on a fleet that has no peer table yet makes the table and the log: refused at each of the 8 allocations in turn it
+    returns RDA_ERR_HIP and holds nothing more than before; the call that gets through returns the doubles of an undisturbed twin.  B = 3, T = 5."""
+    (sa, fa), (sb, fb) = bare_fleet(hip, [car(e) for e in range(3)]), bare_fleet(hip, [car(e) for e in range(3)])
+    got, want = np.full(3, np.nan), np.full(3, np.nan)
+    rc, refused = refused_in_turn(hip, lambda: hip.fleet_peer_clearance(fa, dptr(START), dptr(got)))
+    print("allocations of a fleet's first rda_fleet_peer_clearance:", refused)
+    assert rc == 0 and refused == 8
+    assert hip.fleet_peer_clearance(fb, dptr(START), dptr(want)) == 0
+    assert np.array_equal(got, want) and np.all(np.isfinite(want))
+    hip.fleet_destroy(fa); hip.fleet_destroy(fb)
 
 
 # ---- 5 ----------------------------------------------------------------------------------------------------------------------------------------------

@@ -83,10 +83,10 @@ def agree(got, state, sensor, obstacles, what):
 
 class Sim:
     """a fleet of fresh handles of the given robots (nothing staged) and its worlds"""
-    def __init__(self, hip, cars):
+    def __init__(self, hip, cars, t=T):
         from rda_planner_amd.rda_solver import RDA_solver
         self.hip, self.B, self.cars = hip, len(cars), cars
-        self.svs = [RDA_solver(T, c, E, N, iter_num=ITER, step_time=DT, time_print=False) for c in cars]
+        self.svs = [RDA_solver(t, c, E, N, iter_num=ITER, step_time=DT, time_print=False) for c in cars]
         self.F = C.c_void_p()
         assert hip.fleet_create((C.c_void_p * self.B)(*[s._be.handle for s in self.svs]), self.B, C.byref(self.F)) == 0
 
@@ -256,6 +256,30 @@ def test_refusals(hip, sim):
     assert np.array_equal(sim.world(), w0) and w0.shape == (7, WE, 2)
     rc, after = sim.cast(poses, sensors, peers=True)
     assert rc == 0 and all(np.array_equal(x, y) for x, y in zip(before, after))
+
+
+def test_refused_allocations_of_a_first_seeing_cast_change_nothing(hip):
+    """rda_fleet_raycast_peers on a fleet that has worlds but no peer table and no ranges yet makes both: refused at each of the 8 allocations in turn
+    it returns RDA_ERR_HIP, holds nothing more than before and leaves the world as it was; the call that gets through returns the ranges of an
+    undisturbed twin.  B = 3, T = 5, worlds of 3, 2 and 3 obstacles, 8 beams."""
+    from fleet_twin_lib import refused_in_turn
+    eight = dict(number=8, angle_min=-np.pi, angle_max=np.pi, range_min=0.0, range_max=12.0)
+    worlds = [worlds3()[0][:3], worlds3()[2][:2], worlds3()[2]]
+    a, b = (Sim(hip, [car(e) for e in range(3)], t=5) for _ in range(2))
+    assert a.upload(worlds) == 0 and b.upload(worlds) == 0
+    w0, out = a.world(), {}
+
+    def first():
+        rc, out["ranges"] = a.cast(POSES[0], [eight] * 3, peers=True)
+        assert np.array_equal(a.world(), w0)
+        return rc
+    rc, refused = refused_in_turn(hip, first)
+    print("allocations of a fleet's first rda_fleet_raycast_peers:", refused)
+    assert rc == 0 and refused == 8
+    rc, want = b.cast(POSES[0], [eight] * 3, peers=True)
+    assert rc == 0 and all(np.array_equal(x, y) for x, y in zip(out["ranges"], want))
+    assert all(len(x) == 8 and np.all(np.isfinite(x)) for x in want)
+    a.close(); b.close()
 
 
 def test_python_raycast_peers(hip):

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import lidar_track_lib as L
-from fleet_twin_lib import DT, E, MARGIN, RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, T, advanced, info_tuple, same_logs
+from fleet_twin_lib import DT, E, MARGIN, RDA_ERR_ARG, RDA_ERR_UNSUPPORTED, T, advanced, bare_fleet, car, info_tuple, refused_in_turn, same_logs
 from lidar_world_lib import EPS
 from rda_planner_amd import lidar
 from rda_planner_amd._capi import dptr, iptr
@@ -400,3 +400,36 @@ def test_refused_allocations_change_nothing(hip):
     same_logs(la, lb, keys=("states", "controls", "index", "arrived_at", "boxes", "clearance", "peer_clearance"))
     assert all(same_table(x, y) for x, y in zip(a.tracks(), b.tracks()))
     a.close(); b.close()
+
+
+class Bare:
+    """a fleet of two fresh handles (T = 5) that has made none of its tables yet, with TTwin's tracker calls"""
+    track, tracks = TTwin.track, TTwin.tracks
+
+    def __init__(self, hip):
+        self.hip, self.B = hip, 2
+        self.svs, self.F = bare_fleet(hip, [car(0), car(1)])
+
+
+def test_refused_allocations_of_the_tracker_on_a_fresh_fleet_change_nothing(hip):
+    """rda_fleet_track_boxes as a fleet's first lidar call makes the tracker's table and the lidar block: refused at each of the 20 allocations in turn
+    it returns RDA_ERR_HIP, holds nothing more than before and has no tracks; the call that gets through, and a second tick behind it, give the
+    velocities and the table of an undisturbed twin.  B = 2, two and three boxes."""
+    a, b = Bare(hip), Bare(hip)
+    ticks = [[L.boxes_at(np.array([[0.0, 0.0], [3.0, 0.0]]) + k * np.array([0.05, 0.0])),
+              L.boxes_at(np.array([[1.0, 2.0], [4.0, 2.0], [7.0, 2.5]]) + k * np.array([0.0, -0.03]))] for k in range(2)]
+    out = {}
+
+    def first():
+        rc, out["vel"] = a.track(ticks[0], cap=4)
+        assert rc == 0 or all(len(t[0]) == 0 for t in a.tracks())
+        return rc
+    rc, refused = refused_in_turn(hip, first)
+    print("allocations of rda_fleet_track_boxes on a fresh fleet:", refused)
+    assert rc == 0 and refused == 20
+    rc, want = b.track(ticks[0], cap=4)
+    assert rc == 0 and all(np.array_equal(x, y) for x, y in zip(out["vel"], want))
+    (rca, va), (rcb, vb) = a.track(ticks[1], cap=4), b.track(ticks[1], cap=4)
+    assert rca == 0 and rcb == 0 and all(np.array_equal(x, y) for x, y in zip(va, vb)) and np.abs(vb[0]).max() > 0.4
+    assert all(same_table(x, y) for x, y in zip(a.tracks(cap=4), b.tracks(cap=4)))
+    hip.fleet_destroy(a.F); hip.fleet_destroy(b.F)
