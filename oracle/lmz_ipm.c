@@ -237,9 +237,7 @@ static int cqp_solve(const cqp *c, double tol, double mu_target, double *x, doub
     return status;
 }
 
-static double g_ipm_tol = 1e-8, g_ipm_mu = 1e-6;
-void orc_set_lmz_ipm_tol(double tol) { if (tol > 0) g_ipm_tol = tol; }
-void orc_set_lmz_ipm_mu(double mu) { g_ipm_mu = mu; }      /* > 0: return the central-path point at this barrier parameter; 0: stop by the gap test */
+const orc_switches *orc_switches_now(void);      /* rda_oracle.c: the oracle's one record of switches (lmz_ipm_tol, lmz_mu are read here); not exported */
 
 /* One (obstacle, stage) sub-problem by the interior-point method.  Arguments as orc_lammuz_one plus robot_norm2.
  * cmh = (optimal value, Im, H0, H1).  Returns 0 optimal, 1 inaccurate, 2 failed (outputs untouched), <0 bad argument. */
@@ -301,7 +299,8 @@ int orc_lammuz_ipm_one(int E, int R, const double *A, const double *b, int cone_
     if (robot_norm2) { c.G[r][itr] = -1; ++r; for (int j = 0; j < R - 1; ++j) { c.G[r][E + j] = 1; ++r; } c.qd[c.nq++] = R; }
     c.m = r;
     double x[NX], z[MX], s[MX];
-    int st = cqp_solve(&c, g_ipm_tol, g_ipm_mu, x, z, s, iters);
+    const orc_switches *sw = orc_switches_now();
+    int st = cqp_solve(&c, sw->lmz_ipm_tol, sw->lmz_mu, x, z, s, iters);
     if (st == 2) return 2;
     for (int i = 0; i < E; ++i) lam_out[i] = x[i];
     for (int j = 0; j < R; ++j) mu_out[j] = x[E + j];

@@ -31,46 +31,59 @@
 #define RMAX 16
 #define SIGN_TOL 1e-12
 
-static int g_threads = 1;
-static double g_su_warm_wfl = 1e-3, g_su_warm_mu0 = 1e-3; static int g_su_warm_cap = 30, g_su_warm_first = 1;   /* su warm start (orc_set_su_warm(0,0,0): cold) */
-void orc_set_su_warm(double wfl, double mu0, int cap) { g_su_warm_wfl = wfl; g_su_warm_mu0 = mu0; g_su_warm_cap = cap; }
-/* end game of a WARM-started su solve: floor of the fraction to the boundary and of the centering parameter (cold: 0.995, 1e-3) */
-static double g_su_warm_tau = 0.9999, g_su_warm_sig = 1e-5;
-void orc_set_su_warm_endgame(double tau, double sig) { g_su_warm_tau = tau; g_su_warm_sig = sig; }
-/* relative margin by which the start of a WARM attempt is pulled inside the control / distance boxes (cold: 0.01) */
-static double g_su_warm_clip = 0.01;
-void orc_set_su_warm_clip(double m) { g_su_warm_clip = m; }
-/* start used while the su-solves are easy (the last one took <= max iterations): wfl, mu0, clip, tau, sigma; max = 0 disables */
-static double g_su_easy[5] = {1e-12, 1e-12, 1e-12, 0.999999, 1e-7}; static int g_su_easy_max = 2;   /* = rda_opts_init (csrc/rda_hip.hip) */
+/* Every switch of the oracle: ONE record (orc_switches, rda_oracle.h), its defaults written in orc_switches_init and nowhere else.  The
+ * orc_set_* functions are one-line writes into it with their clamps; orc_put_switches stores a record as given (oracle_backend.switches
+ * snapshots, changes and puts back through it).  Not switches: the dump file below, the thread-local results t_su_*, g_pol_stat. */
+static orc_switches g_sw;
+void orc_switches_init(orc_switches *w)
+{
+    *w = (orc_switches){
+        .su_warm = {1e-3, 1e-3}, .su_warm_cap = 30, .su_warm_first = 1,       /* su warm start: slack floor, barrier parameter, iterations granted (0, 0, 0: cold) */
+        .su_warm_endgame = {0.9999, 1e-5},      /* end game of a WARM-started su solve: floor of the fraction to the boundary and of the centering parameter (cold: 0.995, 1e-3) */
+        .su_warm_clip = 0.01,                   /* relative margin by which the start of a WARM attempt is pulled inside the control / distance boxes (cold: 0.01) */
+        .su_easy = {1e-12, 1e-12, 1e-12, 0.999999, 1e-7}, .su_easy_max = 2,   /* start used while the su-solves are easy (the last one took <= max iterations): wfl, mu0, clip, tau, sigma; max = 0 disables */
+        .su_tol = {1e-9, 1e-10, 1e-11},         /* interior-point stop of the su-problem: rd, rp, mu */
+        .su_tol_early = {0, 0, 0},              /* the su-problems of the ADMM iterations BEFORE the last one of a step stop at these (0: same as su_tol) */
+        .su_hard_warm = {1.0, 1e-3},            /* start of the warm attempts of a step that follows an UNCONVERGED step (0 = off) */
+        .su_cold_from = 7, .su_cold_probe = 8,  /* a warm attempt that follows a solve with more than `from` interior-point iterations is skipped (the solve starts cold), except every `probe`-th such solve (0 = never) */
+        .su_first_attempt = 0,                  /* test switch: 1 = start with the last-resort attempt */
+        .su_accept = 1,                         /* su_solve_impl: the near-converged iterate kept as a safety net (see there); 2: test switch - ALWAYS return the remembered iterate (= csrc/su_device.h Args::accept) */
+        .su_land = 1, .su_land_tol = {1e-3, 1e-4, 1e-5},      /* first stop of a landed solve; a refused landing is tried again at 1e-2^k x while above su_tol, then the stop is SU_LAND_FALLBACK x su_tol */
+        .lmz_mode = 0,                          /* 0: support enumeration + tie-breaks T1-T3, 1: interior point (oracle/lmz_ipm.c) */
+        .tie_centre = 1,                        /* tie-break T1: central separating normal in the slack regime (0: max clearance) */
+        .lmz_mu = 1e-6, .lmz_ipm_tol = 1e-8,    /* lmz_ipm.c: > 0 return the central-path point at this barrier parameter, 0 stop by the gap test; its stop tolerance */
+        .su_trace = 0, .threads = 1,
+    };
+}
+__attribute__((constructor)) static void switches_boot(void) { orc_switches_init(&g_sw); }
+void orc_get_switches(orc_switches *w) { *w = g_sw; }
+void orc_put_switches(const orc_switches *w) { g_sw = *w; }
+__attribute__((visibility("hidden"))) const orc_switches *orc_switches_now(void) { return &g_sw; }     /* for lmz_ipm.c */
+void orc_set_su_warm(double wfl, double mu0, int cap) { g_sw.su_warm[0] = wfl; g_sw.su_warm[1] = mu0; g_sw.su_warm_cap = cap; }
+void orc_set_su_warm_endgame(double tau, double sig) { g_sw.su_warm_endgame[0] = tau; g_sw.su_warm_endgame[1] = sig; }
+void orc_set_su_warm_clip(double m) { g_sw.su_warm_clip = m; }
+void orc_set_su_easy(double wfl, double mu0, double clip, double tau, double sig, int max) { const double e[5] = {wfl, mu0, clip, tau, sig}; memcpy(g_sw.su_easy, e, sizeof e); g_sw.su_easy_max = max; }
+void orc_set_su_tol(double rd, double rp, double mu) { if (rd > 0 && rp > 0 && mu > 0) { g_sw.su_tol[0] = rd; g_sw.su_tol[1] = rp; g_sw.su_tol[2] = mu; } }
+void orc_set_su_tol_early(double rd, double rp, double mu) { g_sw.su_tol_early[0] = rd; g_sw.su_tol_early[1] = rp; g_sw.su_tol_early[2] = mu; }
+void orc_set_su_hard_warm(double wfl, double mu0) { g_sw.su_hard_warm[0] = wfl; g_sw.su_hard_warm[1] = mu0; }
+void orc_set_su_cold_from(int from, int probe) { g_sw.su_cold_from = from; g_sw.su_cold_probe = probe > 0 ? probe : 1; }
+void orc_set_su_first_attempt(int a) { g_sw.su_first_attempt = a ? 1 : 0; }
+void orc_set_su_accept(int on) { g_sw.su_accept = on; }
+void orc_set_su_land(int on) { g_sw.su_land = on; }
+void orc_set_su_land_tol(double rd, double rp, double mu) { if (rd > 0 && rp > 0 && mu > 0) { g_sw.su_land_tol[0] = rd; g_sw.su_land_tol[1] = rp; g_sw.su_land_tol[2] = mu; } }
+void orc_set_lmz_mode(int mode) { g_sw.lmz_mode = mode ? 1 : 0; }
+void orc_set_centre(int on) { g_sw.tie_centre = on; }
+void orc_set_lmz_ipm_tol(double tol) { if (tol > 0) g_sw.lmz_ipm_tol = tol; }
+void orc_set_lmz_ipm_mu(double mu) { g_sw.lmz_mu = mu; }
+void orc_set_su_trace(int on) { g_sw.su_trace = on; }
+void orc_set_threads(int n) { g_sw.threads = n > 0 ? n : 1; }
 static double cur_warm_tau = 0.9999, cur_warm_sig = 1e-5, cur_warm_clip = 0.01;     /* what the warm attempt of the solve in progress uses */
-void orc_set_su_easy(double wfl, double mu0, double clip, double tau, double sig, int max) { g_su_easy[0] = wfl; g_su_easy[1] = mu0; g_su_easy[2] = clip; g_su_easy[3] = tau; g_su_easy[4] = sig; g_su_easy_max = max; }
-static double g_su_tol[3] = {1e-9, 1e-10, 1e-11};   /* interior-point stop of the su-problem: rd, rp, mu */
-void orc_set_su_tol(double rd, double rp, double mu) { if (rd > 0 && rp > 0 && mu > 0) { g_su_tol[0] = rd; g_su_tol[1] = rp; g_su_tol[2] = mu; } }
-/* mirror of rda_opts::su_tol_early: the su-problems of the ADMM iterations BEFORE the last one of a step stop at these (0: same as su_tol) */
-static double g_su_tol_early[3] = {0, 0, 0};
-void orc_set_su_tol_early(double rd, double rp, double mu) { g_su_tol_early[0] = rd; g_su_tol_early[1] = rp; g_su_tol_early[2] = mu; }
-static int g_lmz_mode = 0;   /* 0: support enumeration + tie-breaks T1-T3, 1: interior point (oracle/lmz_ipm.c) */
-void orc_set_lmz_mode(int mode) { g_lmz_mode = mode ? 1 : 0; }
-static int g_centre = 1;     /* tie-break T1: central separating normal in the slack regime (orc_set_centre(0): max clearance) */
-void orc_set_centre(int on) { g_centre = on; }
 /* debug aids of the su interior point (not used by any test's comparison): orc_set_su_dump(path) records every su-problem orc_admm_su
- * solves (NULL / "": off), orc_set_su_trace(1) prints one line per interior-point iteration to stderr */
-static FILE *g_su_dump = NULL; static int g_su_trace = 0;
+ * solves (NULL / "": off), su_trace = 1 prints one line per interior-point iteration to stderr */
+static FILE *g_su_dump = NULL;
 void orc_set_su_dump(const char *path) { if (g_su_dump) fclose(g_su_dump); g_su_dump = (path && path[0]) ? fopen(path, "wb") : NULL; }
-void orc_set_su_trace(int on) { g_su_trace = on; }
-static double g_su_hard_wfl = 1.0, g_su_hard_mu0 = 1e-3;   /* mirror of rda_opts::su_hard_warm: start of the warm attempts of a step that follows an UNCONVERGED step (0 = off) */
-void orc_set_su_hard_warm(double wfl, double mu0) { g_su_hard_wfl = wfl; g_su_hard_mu0 = mu0; }
-/* mirror of rda_opts::su_cold_from / su_cold_probe: a warm attempt that follows a solve with more than `from` interior-point iterations is
- * skipped (the solve starts cold), except every `probe`-th such solve (0 = never) */
-static int g_su_cold_from = 7, g_su_cold_probe = 8;
-void orc_set_su_cold_from(int from, int probe) { g_su_cold_from = from; g_su_cold_probe = probe > 0 ? probe : 1; }
 #define SU_HARD_RD0 1e-2      /* = csrc/su_device.h */
 #define SU_HARD_DMU 1.0       /* = csrc/su_device.h */
-static int g_su_first_attempt = 0;               /* mirror of rda_opts::su_first_attempt (test switch): 1 = start with the last-resort attempt */
-void orc_set_su_first_attempt(int a) { g_su_first_attempt = a ? 1 : 0; }
-static int g_su_accept = 1;                      /* su_solve_impl: the near-converged iterate kept as a safety net (see there) */
-void orc_set_su_accept(int on) { g_su_accept = on; }      /* 2: test switch - ALWAYS return the remembered iterate (= csrc/su_device.h Args::accept) */
-void orc_set_threads(int n) { g_threads = n > 0 ? n : 1; }
 
 struct orc_handle {
     orc_cfg c;
@@ -499,7 +512,7 @@ int orc_lammuz_one(int E, int R, const double *A, const double *b, int cone_norm
     }
     }
     /* tie-break T1 (slack regime): central separating normal instead of the max-clearance one */
-    if (g_centre && best_m > 0 && best_H[0] * best_H[0] + best_H[1] * best_H[1] < 1e-8) {
+    if (g_sw.tie_centre && best_m > 0 && best_H[0] * best_H[0] + best_H[1] * best_H[1] < 1e-8) {
         double as[2] = {0, 0}, lc[EMAX], mc_[RMAX], mm;
         for (int i = 0; i < E; ++i) { as[0] += lam_out[i] * A[2 * i]; as[1] += lam_out[i] * A[2 * i + 1]; }
         if (as[0] * as[0] + as[1] * as[1] >= 1.0 - 1e-9 &&      /* a* on the unit circle: it has a direction */
@@ -695,12 +708,9 @@ static void chol_solve(const double *K, int n, double *rhs)
  * gradient at x+ (hinge terms re-evaluated) is stationary; otherwise move rows in / out of A by their signs (primal-dual active set) and try again, a few
  * rounds; no acceptance: the interior-point iterate is returned as before.  The model is solved by the method of multipliers on
  * K = H + rho C_A' C_A (one Cholesky factor, a few solves: converges like (|H| / rho)^k), so no row of C_A has to be independent of the others. */
-static int g_su_land = 1; static double g_su_land_tol[3] = {1e-3, 1e-4, 1e-5};   /* = rda_opts::su_land, su_land_tol (first stop; a refused landing is tried again at 1e-2^k x while above su_tol, then the stop is SU_LAND_FALLBACK x su_tol) */
 static __thread int t_su_landed = 0, t_su_land_rounds = 0;
 static long g_pol_stat[8];       /* calls, accepted, rounds summed, last verdict: chol failed, set still moving, not stationary; rows moved */
 void orc_get_su_land_stats(long *out8) { for (int i = 0; i < 8; ++i) { out8[i] = g_pol_stat[i]; g_pol_stat[i] = 0; } }
-void orc_set_su_land(int on) { g_su_land = on; }
-void orc_set_su_land_tol(double rd, double rp, double mu) { if (rd > 0 && rp > 0 && mu > 0) { g_su_land_tol[0] = rd; g_su_land_tol[1] = rp; g_su_land_tol[2] = mu; } }
 int orc_get_su_landed(void) { return t_su_landed; }
 static int su_land(const su_ctx *S, const lincon *con, int mc, int n, double *x, double *lm, double *w, double *s, double *grad, double *Hm, double *K, double tol_rd)
 {
@@ -827,7 +837,7 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
      * point (slack floor 0.1, mu0 = 10) and - since round 5 - as a plain long-step path-following iteration (`safe` below). */
     int status = 1, it = 0, used = 0;
     warm = warm && lam_keep != NULL;
-    for (int attempt = g_su_first_attempt ? 1 : (warm ? -1 : 0); attempt < 2 && status != 0; ++attempt) {
+    for (int attempt = g_sw.su_first_attempt ? 1 : (warm ? -1 : 0); attempt < 2 && status != 0; ++attempt) {
     const double wfl = attempt < 0 ? warm_wfl : (attempt ? 1e-1 : 1e-2), mu0 = attempt < 0 ? warm_mu0 : (attempt ? 10.0 : 1.0);
     /* (the cold attempt: 50 since round 5 - it was 100 while the last resort was a second Mehrotra attempt; every recorded solve that the cold
      * attempt finishes at all takes <= 37 iterations, a cycling one is better off in the last resort after 50 than after 100) */
@@ -901,16 +911,16 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
 #define SU_LAND_FALLBACK 1e-3
 #endif
 #define SU_CONV(tol) ((rdn <= (tol)[0] * sc && rpn <= (tol)[1] && mu <= (tol)[2] * sc) || (rdn <= 100 * (tol)[0] * sc && rpn <= (tol)[1] && mu <= 0.1 * (tol)[2] * sc))
-        if (g_su_land && land_failed < 99) {
+        if (g_sw.su_land && land_failed < 99) {
             /* Landing (round 6, see su_land): the interior point only has to get close enough for the active set to be read off - su_land_tol - and the
              * vertex is then computed exactly.  Refused (the active-set rounds can cycle while borderline rows are undecided): tried again at 1e-2 x
              * su_land_tol, 1e-4 x ... down to su_tol itself; once that one is refused the iteration stops at SU_LAND_FALLBACK x su_tol (below). */
             double lt[3], lsc = 1.0; int last = 1;
             for (int k = 0; k < land_failed && k < 8; ++k) lsc *= 1e-2;
-            for (int k = 0; k < 3; ++k) { lt[k] = lsc * g_su_land_tol[k]; if (lt[k] <= g_su_tol[k]) lt[k] = g_su_tol[k]; else last = 0; }
+            for (int k = 0; k < 3; ++k) { lt[k] = lsc * g_sw.su_land_tol[k]; if (lt[k] <= g_sw.su_tol[k]) lt[k] = g_sw.su_tol[k]; else last = 0; }
             if (SU_CONV(lt)) {
                 memcpy(x_sav, x, sizeof(double) * n); memcpy(lm_sav, lm, sizeof(double) * mc); memcpy(w_sav, w, sizeof(double) * mc);
-                if (su_land(&S, con, mc, n, x, lm, w, s, grad, Hm, K, g_su_tol[0])) { t_su_landed = 1; status = 0; break; }
+                if (su_land(&S, con, mc, n, x, lm, w, s, grad, Hm, K, g_sw.su_tol[0])) { t_su_landed = 1; status = 0; break; }
                 memcpy(x, x_sav, sizeof(double) * n); memcpy(lm, lm_sav, sizeof(double) * mc); memcpy(w, w_sav, sizeof(double) * mc);
                 land_failed = last ? 99 : land_failed + 1;
                 su_eval(&S, x, s, grad, Hm);
@@ -920,11 +930,11 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
          * singular (the steering of an Ackermann robot at v ~ 0) the point at su_tol is 1e-5 .. 1e-4 from the vertex, one or two iterations later 1e-7 .. 1e-8
          * (mirrors csrc/su_device.h).  Not reached within the cap: the safety net below has the iterate that met su_tol. */
         {
-            const double ft[3] = { SU_LAND_FALLBACK * g_su_tol[0], SU_LAND_FALLBACK * g_su_tol[1], SU_LAND_FALLBACK * g_su_tol[2] };
-            if ((!g_su_land && SU_CONV(g_su_tol)) || (g_su_land && land_failed >= 99 && SU_CONV(ft))) { status = 0; break; }
+            const double ft[3] = { SU_LAND_FALLBACK * g_sw.su_tol[0], SU_LAND_FALLBACK * g_sw.su_tol[1], SU_LAND_FALLBACK * g_sw.su_tol[2] };
+            if ((!g_sw.su_land && SU_CONV(g_sw.su_tol)) || (g_sw.su_land && land_failed >= 99 && SU_CONV(ft))) { status = 0; break; }
         }
-        if (g_su_accept && rpn <= g_su_tol[1] && rdn <= 10 * g_su_tol[0] * sc && mu <= 1e3 * g_su_tol[2] * sc) {
-            const double merit = fmax(rdn / (g_su_tol[0] * sc), mu / (g_su_tol[2] * sc));
+        if (g_sw.su_accept && rpn <= g_sw.su_tol[1] && rdn <= 10 * g_sw.su_tol[0] * sc && mu <= 1e3 * g_sw.su_tol[2] * sc) {
+            const double merit = fmax(rdn / (g_sw.su_tol[0] * sc), mu / (g_sw.su_tol[2] * sc));
             if (!have_acc || merit < acc_merit) { memcpy(x_acc, x, sizeof(double) * n); memcpy(lm_acc, lm, sizeof(double) * mc); have_acc = 1; acc_merit = merit; }
         }
         /* K = H + C' diag(lm/w) C */
@@ -979,11 +989,11 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
             if (dw[i] < 0 && -tau * w[i] / dw[i] < al) al = -tau * w[i] / dw[i];
             if (dl[i] < 0 && -tau * lm[i] / dl[i] < al) al = -tau * lm[i] / dl[i];
         }
-        if (g_su_trace == 2 && g_su_dump) {      /* (tools/experiments/scan_riccati.py) the iterate the factorisation of this iteration belongs to */
+        if (g_sw.su_trace == 2 && g_su_dump) {      /* (tools/experiments/scan_riccati.py) the iterate the factorisation of this iteration belongs to */
             double hd[3] = { (double)it, (double)mc, (double)n };
             fwrite(hd, sizeof(double), 3, g_su_dump); fwrite(x, sizeof(double), n, g_su_dump); fwrite(w, sizeof(double), mc, g_su_dump); fwrite(lm, sizeof(double), mc, g_su_dump);
         }
-        if (g_su_trace == 1) {       /* residuals of this iterate, the step taken from it, active hinge terms, the row that blocks the step */
+        if (g_sw.su_trace == 1) {       /* residuals of this iterate, the step taken from it, active hinge terms, the row that blocks the step */
             int nact = 0, blk = -1; double dxn = 0, bal = 2;
             for (int t = 0; t < T; ++t) for (int nn = 0; nn < N; ++nn) {
                 const double *aa = &a[(nn * T + t) * 2];
@@ -1017,7 +1027,7 @@ static int su_solve_impl(const orc_cfg *c, const double *nom_s, const double *no
     used += it;
     }
     /* every attempt failed: the safety net (see above) */
-    if ((status != 0 || g_su_accept == 2) && have_acc) { memcpy(x, x_acc, sizeof(double) * n); memcpy(lm, lm_acc, sizeof(double) * mc); status = 0; }
+    if ((status != 0 || g_sw.su_accept == 2) && have_acc) { memcpy(x, x_acc, sizeof(double) * n); memcpy(lm, lm_acc, sizeof(double) * mc); status = 0; }
     if (ipm_iters) *ipm_iters = used;
     if (status == 0 && lam_keep) memcpy(lam_keep, lm, sizeof(double) * mc);
     su_rollout(&S, x, s);
@@ -1039,7 +1049,7 @@ int orc_su_solve(const orc_cfg *c, const double *nom_s, const double *nom_u, con
 int orc_create(const orc_cfg *cfg, const double *G, const double *h, orc_handle **out)
 {
     if (cfg->E > EMAX || cfg->R > RMAX || cfg->N < 1 || cfg->T < 1) return -1;
-    if (cfg->robot_norm2 && !g_lmz_mode) return -2;      /* the enumeration has no norm2 robot candidates: interior-point mode only */
+    if (cfg->robot_norm2 && !g_sw.lmz_mode) return -2;      /* the enumeration has no norm2 robot candidates: interior-point mode only */
     orc_handle *H = calloc(1, sizeof(*H));
     H->c = *cfg;
     int T = cfg->T, N = cfg->N, E = cfg->E, R = cfg->R;
@@ -1220,26 +1230,26 @@ int orc_admm_su(orc_handle *H, int it, int *stopped)
     }
     /* ADMM iterations >= 1 start from the multipliers of the previous su-solve of this step, if that one converged */
     /* ... and the first one from those of the previous step, shifted by one stage */
-    const int warm = g_su_warm_mu0 > 0 && (it > 0 ? !((H->su_status >> (it - 1)) & 1) : g_su_warm_first);
+    const int warm = g_sw.su_warm[1] > 0 && (it > 0 ? !((H->su_status >> (it - 1)) & 1) : g_sw.su_warm_first);
     /* while the su-solves are easy (the last one took <= max iterations) the warm attempt starts 1e-6 from the previous solution's
      * active bounds and takes near-full steps - the same rule as csrc/rda_hip.hip su_body */
-    const int easy = warm && g_su_easy_max > 0 && H->su_last <= g_su_easy_max;
+    const int easy = warm && g_sw.su_easy_max > 0 && H->su_last <= g_sw.su_easy_max;
     /* after an unconverged step, and only while consecutive su-problems really are far apart: the last solve's FIRST iterate (the previous
      * solution with its multipliers) had a relative dual residual above SU_HARD_RD0.  (Round 4 keyed on the last solve's iteration count
      * > 3; a hard-started solve costs >= 3 iterations whatever the problem, so that key either locked the easy start out - iter_num = 1:
      * 1.0 -> 3.0 iterations per solve - or, set to > 3, left most of the gain: re-sorted north star 7.6 -> 6.2 against 5.3 with this key.) */
-    const int hard = warm && !easy && g_su_hard_mu0 > 0 && H->prev_unconv && H->su_hardlike && H->su_last < 99;
+    const int hard = warm && !easy && g_sw.su_hard_warm[1] > 0 && H->prev_unconv && H->su_hardlike && H->su_last < 99;
     /* hard regime without that rule (many moving obstacles): a warm attempt needs MORE iterations than a cold start - start cold, probe the warm start now and then */
-    const int go_cold = warm && !easy && !hard && g_su_cold_from > 0 && H->su_last > g_su_cold_from && H->su_last < 99 && H->su_probe % g_su_cold_probe != g_su_cold_probe - 1;
-    cur_warm_clip = easy ? g_su_easy[2] : g_su_warm_clip; cur_warm_tau = easy ? g_su_easy[3] : g_su_warm_tau; cur_warm_sig = easy ? g_su_easy[4] : g_su_warm_sig;
-    double tol_keep[3] = { g_su_tol[0], g_su_tol[1], g_su_tol[2] };
-    if (it < c->iter_num - 1 && g_su_tol_early[0] > 0 && g_su_tol_early[1] > 0 && g_su_tol_early[2] > 0) memcpy(g_su_tol, g_su_tol_early, sizeof g_su_tol);
+    const int go_cold = warm && !easy && !hard && g_sw.su_cold_from > 0 && H->su_last > g_sw.su_cold_from && H->su_last < 99 && H->su_probe % g_sw.su_cold_probe != g_sw.su_cold_probe - 1;
+    cur_warm_clip = easy ? g_sw.su_easy[2] : g_sw.su_warm_clip; cur_warm_tau = easy ? g_sw.su_easy[3] : g_sw.su_warm_endgame[0]; cur_warm_sig = easy ? g_sw.su_easy[4] : g_sw.su_warm_endgame[1];
+    double tol_keep[3] = { g_sw.su_tol[0], g_sw.su_tol[1], g_sw.su_tol[2] };
+    if (it < c->iter_num - 1 && g_sw.su_tol_early[0] > 0 && g_sw.su_tol_early[1] > 0 && g_sw.su_tol_early[2] > 0) memcpy(g_sw.su_tol, g_sw.su_tol_early, sizeof g_sw.su_tol);
     int st = su_solve_impl(c, H->s, H->u, H->ref, H->ref_speed, ca, cc, cg, H->dis, s_new, u_new, d_new, &ipm,
-                           H->su_lam_keep, warm && !go_cold, easy ? g_su_easy[0] : (hard ? g_su_hard_wfl : g_su_warm_wfl), easy ? g_su_easy[1] : (hard ? g_su_hard_mu0 : g_su_warm_mu0), g_su_warm_cap, it == 0, hard ? SU_HARD_DMU : 0.0);
-    memcpy(g_su_tol, tol_keep, sizeof g_su_tol);
+                           H->su_lam_keep, warm && !go_cold, easy ? g_sw.su_easy[0] : (hard ? g_sw.su_hard_warm[0] : g_sw.su_warm[0]), easy ? g_sw.su_easy[1] : (hard ? g_sw.su_hard_warm[1] : g_sw.su_warm[1]), g_sw.su_warm_cap, it == 0, hard ? SU_HARD_DMU : 0.0);
+    memcpy(g_sw.su_tol, tol_keep, sizeof g_sw.su_tol);
     H->su_last = st == 0 ? ipm : 99;
     H->su_hardlike = t_su_rd0 > SU_HARD_RD0;
-    H->su_probe = (g_su_cold_from > 0 && H->su_last > g_su_cold_from && H->su_last < 99) ? H->su_probe + 1 : 0;
+    H->su_probe = (g_sw.su_cold_from > 0 && H->su_last > g_sw.su_cold_from && H->su_last < 99) ? H->su_probe + 1 : 0;
     H->ipm_total += ipm; if (it < 32) H->ipm_hist[it] = ipm;
     if (st == 0) { memcpy(H->s, s_new, sizeof(double) * 3 * (T + 1)); memcpy(H->u, u_new, sizeof(double) * 2 * T); memcpy(H->dis, d_new, sizeof(double) * T); }
     else H->su_status |= 1 << it;                 /* 'No update of state and control vector' :699 */
@@ -1262,7 +1272,7 @@ int orc_admm_lammuz(orc_handle *H)
     /* ---- LamMuZ problems + dual updates of this rank's shard (rda_solver.py:628-635) ----------------- */
     const int n0 = H->rank * H->Nloc, n1 = n0 + H->Nloc < N ? n0 + H->Nloc : N;      /* the last shard may be short (N % P != 0) */
 #ifdef _OPENMP
-#pragma omp parallel for num_threads(g_threads) schedule(static)
+#pragma omp parallel for num_threads(g_sw.threads) schedule(static)
 #endif
     for (int n = n0; n < n1; ++n) {
         for (int t = 0; t < T; ++t) {
@@ -1275,7 +1285,7 @@ int orc_admm_lammuz(orc_handle *H)
                             && isfinite(H->zeta[n * T + t]) && isfinite(H->dis[t]);
             for (int i = 0; i < E; ++i) finite_in = finite_in && isfinite(At[2 * i]) && isfinite(At[2 * i + 1]) && isfinite(bt[i]);
             if (!finite_in) fail = 2;
-            else if (g_lmz_mode) {
+            else if (g_sw.lmz_mode) {
                 int st = orc_lammuz_ipm_one(E, R, At, bt, H->cone[n], c->robot_norm2, p, phi, H->G, H->h, &H->xi[o * 2], H->zeta[n * T + t],
                                             H->dis[t], c->ro2, c->accelerated, lam, mu, &z, NULL, NULL);
                 /* the reference accepts OPTIMAL only (rda_solver.py:781,816; Q8): anything else keeps the previous duals and the

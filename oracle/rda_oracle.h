@@ -47,6 +47,39 @@ typedef struct {
 
 typedef struct orc_handle orc_handle;
 
+/* Every switch of the oracle, process-wide: one record.  orc_switches_init writes the defaults (the only place that holds them),
+ * orc_get_switches reads the record in use, orc_put_switches stores one as given (no clamps).  The orc_set_* functions below write
+ * their fields of it with their clamps.  Tests change the oracle only inside oracle_backend.switches(...), which puts back what it found.
+ * The first block mirrors the rda_opts field of the same name (include/rda_hip.h, same defaults: tests/test_oracle_switches.py). */
+typedef struct {
+    double su_warm[2];          /* orc_set_su_warm: slack floor, barrier parameter of a warm start (0, 0: cold) */
+    int    su_warm_cap;         /* ... iterations granted to a warm attempt */
+    int    su_warm_first;       /* 1 (no setter): the first su-problem of a step starts from the previous step's multipliers */
+    double su_warm_endgame[2];  /* orc_set_su_warm_endgame */
+    double su_warm_clip;        /* orc_set_su_warm_clip */
+    double su_easy[5];          /* orc_set_su_easy: wfl, mu0, clip, tau, sigma */
+    int    su_easy_max;         /* ... 6th argument */
+    double su_tol[3];           /* orc_set_su_tol */
+    double su_tol_early[3];     /* orc_set_su_tol_early */
+    double su_hard_warm[2];     /* orc_set_su_hard_warm */
+    int    su_cold_from;        /* orc_set_su_cold_from */
+    int    su_cold_probe;       /* ... 2nd argument, >= 1 */
+    int    su_first_attempt;    /* orc_set_su_first_attempt */
+    int    su_accept;           /* orc_set_su_accept */
+    int    su_land;             /* orc_set_su_land */
+    double su_land_tol[3];      /* orc_set_su_land_tol */
+    int    lmz_mode;            /* orc_set_lmz_mode */
+    int    tie_centre;          /* orc_set_centre */
+    double lmz_mu;              /* orc_set_lmz_ipm_mu */
+    /* ---- the oracle's own ---- */
+    double lmz_ipm_tol;         /* orc_set_lmz_ipm_tol */
+    int    su_trace;            /* orc_set_su_trace */
+    int    threads;             /* orc_set_threads */
+} orc_switches;
+void orc_switches_init(orc_switches *w);
+void orc_get_switches(orc_switches *w);
+void orc_put_switches(const orc_switches *w);
+
 int  orc_create(const orc_cfg *cfg, const double *G /*R*2*/, const double *h /*R*/, orc_handle **out);
 void orc_destroy(orc_handle *h);
 int  orc_set_adjust(orc_handle *h, double slack_gain, double max_sd, double min_sd, double ro1, double ro2);

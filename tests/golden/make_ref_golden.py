@@ -35,7 +35,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 from helpers import random_polygon                        # noqa: E402
 from oracle import ref_harness as rh                      # noqa: E402
-from oracle.oracle_backend import api as orc_api          # noqa: E402
+from oracle.oracle_backend import switches                # noqa: E402
 from rda_planner_amd import scenarios as sc               # noqa: E402
 from rda_planner_amd.rda_solver import RDA_solver         # noqa: E402
 
@@ -278,13 +278,12 @@ if __name__ == "__main__":
                  + ("(cvxpy / ecos are not installed: oracle/refshim answers)" if backend == "refshim" else "(the real cvxpy is importable: pass --backend cvxpy)"))
     if backend == "cvxpy":
         SUFFIX, INJECT_ORACLE = "_cvxpy", False
-    orc = orc_api()
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    if args.only_na:
+    with switches(su_warm=(0.0, 0.0), su_warm_cap=0) as orc:
+        if args.only_na:
+            lammuz_problems_nonaccelerated(rs, mp)
+            sys.exit(0)
+        plumbing(rs, mp, orc)
+        problems(rs, mp)
         lammuz_problems_nonaccelerated(rs, mp)
-        sys.exit(0)
-    plumbing(rs, mp, orc)
-    problems(rs, mp)
-    lammuz_problems_nonaccelerated(rs, mp)
     for f in ("ref_plumbing", "ref_problems", "ref_problems_na"):
         print(f + SUFFIX + ".npz", os.path.getsize(os.path.join(HERE, f + SUFFIX + ".npz")) // 1024, "KiB")

@@ -36,6 +36,8 @@ TOL_U_FIXED = 1e-7
 TOL_U_IP = 5e-4
 TOL_U_FLIP = 5e-2          # steps on which the two sides stop one ADMM iteration apart (a residual within solver tolerance of iter_threshold)
 MAX_FLIPS_PER_1000 = 5
+# the COLD oracle, the independent checker (every su-problem of a step starts cold): `with switches(**hp.COLD_SU):`
+COLD_SU = dict(su_warm=(0.0, 0.0), su_warm_cap=0)
 
 ROBOT = sc.rectangle_robot()
 G = np.ascontiguousarray(ROBOT.G, float)

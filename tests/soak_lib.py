@@ -10,13 +10,14 @@ What is compared per step
     iters    ADMM iteration counts (early stop, rda_solver.py:594)
     status   su-solves that did not converge (either side)
 """
+import contextlib
 import os
 
 import numpy as np
 
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd.mpc import MPC
-from oracle.oracle_backend import oracle_backend, api as orc_api
+from oracle.oracle_backend import oracle_backend, su_dump as record_su, switches
 
 
 def body_rates(u, dyn, L):
@@ -93,25 +94,27 @@ def draw_scene(rng, seed, s, steps, large=False, exotic=False, circle_robot=Fals
 def run_soak(scenes=12, steps=100, seed=0, lmz_central=0.0, cold_oracle=False, only=-1, threads=None, dump_dir="", dump_tol=1e-5,
              su_dump="", so="", log=print, hip_kw=None, large=False, exotic=False, tight=False, robots=False, circles=False):
     """returns a dict of totals + the per-step outliers; `log` receives one line per remarkable step"""
-    lib = orc_api().lib
     if so:
         from rda_planner_amd import _lib
         _lib.SO_PATH = os.path.abspath(so)
-    if su_dump:
-        os.makedirs(os.path.dirname(os.path.abspath(su_dump)), exist_ok=True)
-        lib.orc_set_su_dump(os.path.abspath(su_dump).encode())
+    oracle = dict(threads=threads or min(16, os.cpu_count() or 1))      # more threads than that slow the oracle down (bench.py thread sweep)
     if lmz_central > 0:
-        lib.orc_set_lmz_mode(1); lib.orc_set_lmz_ipm_mu(lmz_central)
+        oracle.update(lmz_mode=1, lmz_mu=lmz_central)
     if cold_oracle:
-        lib.orc_set_su_warm(0.0, 0.0, 0)
-    lib.orc_set_threads(threads or min(16, os.cpu_count() or 1))      # more threads than that slow the oracle down (bench.py thread sweep)
+        oracle.update(su_warm=(0.0, 0.0), su_warm_cap=0)
     if dump_dir:
         os.makedirs(dump_dir, exist_ok=True)
     step_dump = os.path.join(dump_dir, "_step.bin") if dump_dir and not su_dump else ""
     rng = np.random.default_rng(seed)
     out = dict(steps=0, worst_raw=0.0, worst_body=0.0, worst_hor_body=0.0, iter_mismatch=0, failed=0, over_raw=0, outliers=[], flips=[],
                ipm_gpu=0, ipm_cpu=0)
-    try:
+    with contextlib.ExitStack() as undo:
+        undo.enter_context(switches(**oracle))
+        if su_dump:
+            os.makedirs(os.path.dirname(os.path.abspath(su_dump)), exist_ok=True)
+            undo.enter_context(record_su(os.path.abspath(su_dump)))
+        if step_dump:
+            undo.callback(lambda: os.path.exists(step_dump) and os.remove(step_dump))
         for s in range(scenes):
             d = draw_scene(rng, seed, s, steps, large, exotic, lmz_central > 0, tight, robots, circles)
             if only >= 0 and s != only:
@@ -132,11 +135,8 @@ def run_soak(scenes=12, steps=100, seed=0, lmz_central=0.0, cold_oracle=False, o
                 cur = [o if not np.any(o.velocity) else (o._replace(vertex=o.vertex + o.velocity * (0.1 * k)) if o.cone_type == "Rpositive"
                                                          else o._replace(center=o.center + o.velocity * (0.1 * k))) for o in d["scene"]]
                 ug, ig = gpu.control(st.copy(), d["speed"], list(cur))
-                if step_dump:
-                    lib.orc_set_su_dump(step_dump.encode())
-                uc, ic = cpu.control(st.copy(), d["speed"], list(cur))
-                if step_dump:
-                    lib.orc_set_su_dump(b"")
+                with record_su(step_dump) if step_dump else contextlib.nullcontext():
+                    uc, ic = cpu.control(st.copy(), d["speed"], list(cur))
                 out["steps"] += 1
                 out["ipm_gpu"] += int(ig["su_ipm_iters"]); out["ipm_cpu"] += int(ic["su_ipm_iters"])
                 du = float(np.abs(ug - uc).max())
@@ -173,13 +173,4 @@ def run_soak(scenes=12, steps=100, seed=0, lmz_central=0.0, cold_oracle=False, o
                 st = sc.kinematic_step(st, ug, d["car"], 0.1)
                 if ig["arrive"]:
                     break
-    finally:
-        lib.orc_set_su_dump(b"")
-        if cold_oracle:
-            lib.orc_set_su_warm(1e-3, 1e-3, 30)
-        if lmz_central > 0:
-            lib.orc_set_lmz_mode(0)
-        lib.orc_set_threads(1)
-        if step_dump and os.path.exists(step_dump):
-            os.remove(step_dump)
     return out

@@ -79,33 +79,37 @@ def test_integration_md_names_every_entry_point_of_the_header():
     assert [n for n in names if n not in doc] == []
 
 
-def _header_struct_fields(name):
-    """[(field, 'int' | 'double', length)] of `typedef struct <name> { ... } <name>;` in include/rda_hip.h, in declaration order"""
+def _header_struct_fields(name, header=os.path.join("include", "rda_hip.h")):
+    """[(field, 'int' | 'double', length)] of `typedef struct [<name>] { ... } <name>;` in the header, in declaration order"""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "rda_hip.h")).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, header)).read(), flags=re.S)
+    body = re.search(r"typedef struct(?: %s)? \{([^{}]*)\} %s;" % (name, name), text).group(1)
     out = []
     for decl in body.split(";"):
-        m = re.match(r"\s*(int32_t|double)\s+(.*)", decl.strip(), re.S)
+        m = re.match(r"\s*(int32_t|int|double)\s+(.*)", decl.strip(), re.S)
         if not m:
             continue
         for item in m.group(2).split(","):
             mm = re.match(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*$", item)
-            out.append((mm.group(1), "int" if m.group(1) == "int32_t" else "double", int(mm.group(2) or 1)))
+            out.append((mm.group(1), "double" if m.group(1) == "double" else "int", int(mm.group(2) or 1)))
     return out
 
 
-@pytest.mark.parametrize("cname,pyname", [("rda_opts", "Opts"), ("rda_cfg", "Cfg"), ("rda_info", "Info")])
+@pytest.mark.parametrize("cname,pyname", [("rda_opts", "Opts"), ("rda_cfg", "Cfg"), ("rda_info", "Info"), ("orc_switches", "Switches")])
 def test_ctypes_structs_mirror_the_header_field_by_field(cname, pyname):
-    """the ctypes mirrors of the C-ABI structs (rda_planner_amd/_capi.py) against include/rda_hip.h: names, order, types, array lengths -
-    a field added on one side only shifts everything behind it silently"""
+    """the ctypes mirrors of the C-ABI structs (rda_planner_amd/_capi.py) against include/rda_hip.h, and the oracle's record of switches
+    (oracle/oracle_backend.py) against oracle/rda_oracle.h: names, order, types, array lengths - a field added on one side only shifts
+    everything behind it silently"""
     import ctypes as C
     from rda_planner_amd import _capi
-    want = _header_struct_fields(cname)
+    if cname.startswith("orc_"):
+        want, mirror = _header_struct_fields(cname, os.path.join("oracle", "rda_oracle.h")), _oracle()
+    else:
+        want, mirror = _header_struct_fields(cname), _capi
+    assert len(want) >= 6
     got = []
-    for fname, ftype in getattr(_capi, pyname)._fields_:
+    for fname, ftype in getattr(mirror, pyname)._fields_:
         length = getattr(ftype, "_length_", 1)
         base = getattr(ftype, "_type_", ftype) if length > 1 else ftype
         got.append((fname, "int" if base is C.c_int else "double", length))
@@ -130,7 +134,9 @@ def _ctype_rule(prefix):
             f"{prefix}_cfg*": C.POINTER(k.Cfg), f"const {prefix}_cfg*": C.POINTER(k.Cfg),
             f"{prefix}_opts*": C.POINTER(k.Opts), f"const {prefix}_opts*": C.POINTER(k.Opts), f"{prefix}_info*": C.POINTER(k.Info)}
     if prefix == "orc":
-        rule.update({"const int*": k.c_int_p, "const orc_handle*": C.c_void_p, "const char*": C.c_char_p, "long*": C.POINTER(C.c_long)})
+        sw = C.POINTER(_oracle().Switches)
+        rule.update({"const int*": k.c_int_p, "const orc_handle*": C.c_void_p, "const char*": C.c_char_p, "long*": C.POINTER(C.c_long),
+                     "orc_switches*": sw, "const orc_switches*": sw})
     return rule
 
 
@@ -196,7 +202,7 @@ def test_oracle_tables_equal_the_oracle_header():
     _check_against(own, ob.ORC_PROTOTYPES, ob.ORC_CODES)
     nm = subprocess.run(["nm", "-D", "--defined-only", ob.oracle_lib.build()], check=True, capture_output=True, text=True).stdout
     exported = set(re.findall(r"\bT orc_(\w+)", nm))
-    assert len(exported) >= 42 and exported == set(header)
+    assert len(exported) >= 45 and exported == set(header)
 
 
 def test_prototypes_are_applied_to_the_library():

@@ -1,7 +1,7 @@
 """-m gpu : parity at the sizes BASELINE.json names, against the COLD oracle.
 
 The HIP path runs with its defaults (device-side obstacle pipeline and tracking, pipelined tick, interior-point warm
-starts of the su-problem within a step and across steps); the oracle runs with `orc_set_su_warm(0, 0, 0)`: every
+starts of the su-problem within a step and across steps); the oracle runs with `su_warm` = 0, 0 (helpers.COLD_SU): every
 su-problem starts cold, like ECOS in the reference (no warm start, rda_solver.py:693).  The two therefore reach the
 (unique) su solution along DIFFERENT iteration paths, which is what makes this an accuracy statement rather than a
 same-code-path identity (that identity is `tests/test_gpu_parity.py`, warm oracle, rounding level).
@@ -28,18 +28,16 @@ import pytest
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr
 
-from helpers import TOL_U, TOL_U_FIXED, TOL_U_FLIP
+from helpers import COLD_SU, TOL_U, TOL_U_FIXED, TOL_U_FLIP
+from oracle.oracle_backend import switches
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture()
 def cold_orc(orc):
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    orc.lib.orc_set_threads(16)
-    yield orc
-    orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
-    orc.lib.orc_set_threads(1)
+    with switches(threads=16, **COLD_SU):
+        yield orc
 
 
 def _workload(n_obs, T, n_steps, moving=False, seed_offset=0, iter_num=4, iter_threshold=0.2):

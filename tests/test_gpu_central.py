@@ -14,6 +14,7 @@ The tight check of the kernels is tests/test_gpu_central_rows.py: every row of e
 import numpy as np
 import pytest
 
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 
 pytestmark = pytest.mark.gpu
@@ -21,35 +22,33 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture()
 def central_orc(orc):
-    orc.lib.orc_set_lmz_mode(1)
-    yield orc
-    orc.lib.orc_set_lmz_mode(0)
-    orc.lib.orc_set_lmz_ipm_mu(1e-6)
+    with switches(lmz_mode=1):
+        yield orc
 
 
 def _closed_loop(car_t, path, obstacles, kw, steps, mu, orc, start=None):
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.mpc import MPC
-    orc.lib.orc_set_lmz_ipm_mu(mu)
     cpu = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, _backend=oracle_backend, **kw)
     gpu = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, lmz_central=mu, **kw)
     state = (path[0] if start is None else start).copy().reshape(3, 1)
     worst = dict(u=0.0, state=0.0, res=0.0)
     min_clear = np.inf
-    for i in range(steps):
-        uc, ic = cpu.control(state.copy(), 4.0, list(obstacles))
-        ug, ig = gpu.control(state.copy(), 4.0, list(obstacles))
-        assert ic["iters"] == ig["iters"] and ic["lmz_fail"] == ig["lmz_fail"], (i, ic["iters"], ig["iters"], ic["lmz_fail"], ig["lmz_fail"])
-        worst["u"] = max(worst["u"], float(np.abs(cpu.cur_vel_array - gpu.cur_vel_array).max()))
-        if np.isfinite(ic["resi_dual"]):
-            worst["res"] = max(worst["res"], abs(ic["resi_dual"] - ig["resi_dual"]) / (1 + ic["resi_dual"]), abs(ic["resi_pri"] - ig["resi_pri"]))
-        sc_, sg_ = cpu.rda.get_state(), gpu.rda.get_state()
-        for k in sc_:
-            worst["state"] = max(worst["state"], float(np.abs(sc_[k] - sg_[k]).max()))
-        gpu.rda.set_state(sc_)
-        gpu.cur_vel_array = cpu.cur_vel_array.copy()
-        state = sc.kinematic_step(state, uc, car_t, 0.1)
-        min_clear = min(min_clear, sc.clearance(car_t, state, obstacles))
+    with switches(lmz_mu=mu):
+        for i in range(steps):
+            uc, ic = cpu.control(state.copy(), 4.0, list(obstacles))
+            ug, ig = gpu.control(state.copy(), 4.0, list(obstacles))
+            assert ic["iters"] == ig["iters"] and ic["lmz_fail"] == ig["lmz_fail"], (i, ic["iters"], ig["iters"], ic["lmz_fail"], ig["lmz_fail"])
+            worst["u"] = max(worst["u"], float(np.abs(cpu.cur_vel_array - gpu.cur_vel_array).max()))
+            if np.isfinite(ic["resi_dual"]):
+                worst["res"] = max(worst["res"], abs(ic["resi_dual"] - ig["resi_dual"]) / (1 + ic["resi_dual"]), abs(ic["resi_pri"] - ig["resi_pri"]))
+            sc_, sg_ = cpu.rda.get_state(), gpu.rda.get_state()
+            for k in sc_:
+                worst["state"] = max(worst["state"], float(np.abs(sc_[k] - sg_[k]).max()))
+            gpu.rda.set_state(sc_)
+            gpu.cur_vel_array = cpu.cur_vel_array.copy()
+            state = sc.kinematic_step(state, uc, car_t, 0.1)
+            min_clear = min(min_clear, sc.clearance(car_t, state, obstacles))
     return worst, min_clear
 
 
@@ -91,12 +90,9 @@ def test_norm2_robot_is_not_rejected_any_more(hip):
 def test_central_path_at_the_north_star_size(central_orc):
     """T=20, N=200 (4000 sub-problems per launch: the size the kernel's launch time is quoted on), robust mode mu = 1e-3"""
     from test_gpu_baseline_sizes import _workload
-    central_orc.lib.orc_set_threads(16)
-    try:
+    with switches(threads=16):
         car_t, path, obstacles, kw = _workload(200, 20, 40)
         worst, _ = _closed_loop(car_t, path, obstacles, kw, 8, 1e-3, central_orc)
-    finally:
-        central_orc.lib.orc_set_threads(1)
     print(f"central path mu=1e-3, T=20 N=200: max |du| {worst['u']:.2e}, dual state {worst['state']:.2e}, residuals {worst['res']:.2e}")
     assert worst["u"] < 1e-4 and worst["state"] < 1e-4 and worst["res"] < 1e-6, worst
 

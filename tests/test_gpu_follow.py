@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import TOL_U
+from helpers import COLD_SU, TOL_U
 from follow_lib import PiecewiseOracle, follow
 from rda_planner_amd import scenarios as sc
 
@@ -73,42 +73,39 @@ def test_obstacles_entering_and_leaving_the_slots_match_the_oracle(n_obs, slots,
     state (the oracle continues from the GPU's state, as in the soak)"""
     from rda_planner_amd.mpc import MPC
     from rda_planner_amd.rda_solver import _Backend
-    from oracle.oracle_backend import api as orc_api
+    from oracle.oracle_backend import api as orc_api, switches
     car_t, path, obstacles = _scene(n_obs, moving, seed=9)
     kw = dict(sample_time=0.1, time_print=False, receding=15, iter_num=3, max_edge_num=4, max_obs_num=slots, ro1=200, obstacle_order=True)
     gpu = MPC(car_t, [p.copy() for p in path], duals_follow_obstacles=True, **kw)
     papi = PiecewiseOracle(orc_api(), kw["iter_num"])
     cpu = MPC(car_t, [p.copy() for p in path], _backend=lambda cfg, G, h: _Backend(papi, cfg, G, h), **kw)
-    orc_api().lib.orc_set_su_warm(0.0, 0.0, 0)                   # the cold oracle: the independent checker
-    try:
-        state = path[0].copy().reshape(3, 1)
-        prev, worst, changed, flips = None, 0.0, 0, 0
-        for k in range(36):
-            cur = _at(obstacles, k, moving)
-            ug, ig = gpu.control(state.copy(), 4.0, list(cur))
-            now = _slot_src(gpu)
-            assert len(now) == slots
+    state = path[0].copy().reshape(3, 1)
+    prev, worst, changed, flips = None, 0.0, 0, 0
+    for k in range(36):
+        cur = _at(obstacles, k, moving)
+        ug, ig = gpu.control(state.copy(), 4.0, list(cur))
+        now = _slot_src(gpu)
+        assert len(now) == slots
 
-            def hook(prev=prev, now=now):
-                if prev is not None:
-                    cpu.rda.set_state(follow(cpu.rda.get_state(), prev, now))
-            papi.hook = hook
-            uc, ic = cpu.control(state.copy(), 4.0, list(cur))
-            assert ig["status"] == 0 and ic["status"] == 0
+        def hook(prev=prev, now=now):
             if prev is not None:
-                changed += int(set(prev.tolist()) != set(now.tolist()))
-            if ig["iters"] == ic["iters"]:
-                worst = max(worst, float(np.abs(ug - uc).max()))
-            else:
-                flips += 1
-            prev = now
-            cpu.rda.set_state(gpu.rda.get_state())
-            cpu.cur_vel_array = gpu.cur_vel_array.copy(); cpu.cur_index = gpu.cur_index
-            state = sc.kinematic_step(state, ug, car_t, 0.1)
-        assert changed >= 5, changed                              # the slot SET did change (obstacles entered / left)
-        assert flips <= 1 and worst <= TOL_U, (flips, worst)
-    finally:
-        orc_api().lib.orc_set_su_warm(1e-3, 1e-3, 30)
+                cpu.rda.set_state(follow(cpu.rda.get_state(), prev, now))
+        papi.hook = hook
+        with switches(**COLD_SU):                                 # the cold oracle: the independent checker
+            uc, ic = cpu.control(state.copy(), 4.0, list(cur))
+        assert ig["status"] == 0 and ic["status"] == 0
+        if prev is not None:
+            changed += int(set(prev.tolist()) != set(now.tolist()))
+        if ig["iters"] == ic["iters"]:
+            worst = max(worst, float(np.abs(ug - uc).max()))
+        else:
+            flips += 1
+        prev = now
+        cpu.rda.set_state(gpu.rda.get_state())
+        cpu.cur_vel_array = gpu.cur_vel_array.copy(); cpu.cur_index = gpu.cur_index
+        state = sc.kinematic_step(state, ug, car_t, 0.1)
+    assert changed >= 5, changed                              # the slot SET did change (obstacles entered / left)
+    assert flips <= 1 and worst <= TOL_U, (flips, worst)
 
 
 def test_host_staged_slots_and_shards_are_refused():

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from tests.helpers import TOL_U_IP as TOL_U      # (this module runs with the landing off on both sides: the interior-point statement)
 
@@ -68,8 +69,8 @@ def test_hard_start_same_loop_fewer_iterations_no_lock_out(hip):
 
 def test_hard_start_equals_the_oracle_with_the_mirrored_rule(hip, orc):
     from oracle.oracle_backend import oracle_backend
-    orc.lib.orc_set_su_hard_warm(1.0, 1e-3)
-    uc, ipmc, itsc = _loop(True, None, backend=oracle_backend, steps=30)
+    with switches(su_hard_warm=(1.0, 1e-3)):
+        uc, ipmc, itsc = _loop(True, None, backend=oracle_backend, steps=30)
     per_c = list(_loop.per_step)
     ug, ipmg, itsg = _loop(True, (1.0, 1e-3), drive=uc, steps=30)
     print(f"interior-point iterations per step, oracle: {per_c}\n                                      gpu:    {_loop.per_step}")
@@ -104,11 +105,8 @@ def test_safety_net_hands_back_the_best_near_converged_iterate(hip, orc, T, N, d
     st2, s2, u2, d2, it2 = solve(2)
     assert st0 == st1 == st2 == 0 and it0 == it1 == it2
     assert np.array_equal(u0, u1) and np.array_equal(s0, s1)             # remembering changes nothing
-    try:
-        orc.lib.orc_set_su_accept(2)
+    with switches(su_accept=2):
         stc, sc_, uc, dc, _ = hp.su_solve(orc.lib.orc_su_solve, cfg, inp)
-    finally:
-        orc.lib.orc_set_su_accept(1)
     e_conv, e_orc = float(np.abs(u2 - u1).max()), float(np.abs(u2 - uc).max())
     print(f"T={T} N={N}: |u_remembered - u_converged| {e_conv:.2e}, |u_remembered - oracle's remembered| {e_orc:.2e}, {it2} iterations")
     assert stc == 0 and 0 < e_conv <= 2e-4 and e_orc <= 1e-8              # (an iterate 10 x / 1000 x short of the stop test: the reference solver's class; the two cold solves walk the same path)
@@ -123,7 +121,7 @@ SU_HARD = ["acker_T15_N27_weakly_active_c", "acker_T15_N45_rate_rows_cycle", "di
 @pytest.mark.parametrize("name", SU_HARD)
 def test_last_resort_attempt_converges_on_every_recorded_hard_instance_like_the_oracles(hip, orc, name):
     """round 5: the last-resort attempt of the su interior point is a plain long-step path-following iteration (csrc/su_device.h SU_SAFE_*,
-    oracle/rda_oracle.c `safe`).  Entered directly (rda_opts::su_first_attempt = 1 / orc_set_su_first_attempt) it converges on all eleven recorded
+    oracle/rda_oracle.c `safe`).  Entered directly (rda_opts::su_first_attempt = 1, the same field of orc_switches) it converges on all eleven recorded
     hard instances - 16 to 22 iterations in the oracle - incl. the one both Mehrotra attempts of the oracle cycled on for 100 iterations each
     (soak seed 32, scene 57, step 58: a rate row and a distance row trading places); kernel and oracle walk the same path."""
     import os
@@ -135,11 +133,8 @@ def test_last_resort_attempt_converges_on_every_recorded_hard_instance_like_the_
     s, u, d, it = np.zeros((3, T + 1)), np.zeros((2, T)), np.zeros(T), C.c_int(0)
     st = hip.lib.rda_su_solve_opts(C.byref(cfg), C.byref(o), dptr(inp["nom_s"]), dptr(inp["nom_u"]), dptr(inp["ref"]), inp["vref"], dptr(inp["a"]),
                                    dptr(inp["cc"]), dptr(inp["g"]), dptr(inp["d0"]), dptr(s), dptr(u), dptr(d), C.byref(it))
-    try:
-        orc.lib.orc_set_su_first_attempt(1)
+    with switches(su_first_attempt=1):
         so = hp.su_solve(orc.lib.orc_su_solve, cfg, inp)
-    finally:
-        orc.lib.orc_set_su_first_attempt(0)
     print(f"{name}: last-resort attempt alone: gpu {it.value} / oracle {so[4]} iterations, |du| {np.abs(u - so[2]).max():.1e}")
     # (the end-game-noise instance is the one where the oracle's dense Cholesky loses digits below mu = 1e-9: two iterations apart, weakly-active-row level)
     noisy = name == "omni_T25_N20_end_game_noise"

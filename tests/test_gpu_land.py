@@ -1,4 +1,4 @@
-"""-m gpu : the LANDING of the su interior point (rda_opts::su_land, round 6; oracle mirror orc_set_su_land).
+"""-m gpu : the LANDING of the su interior point (rda_opts::su_land, round 6; oracle mirror orc_switches::su_land).
 
 The interior point stops ON the central path: a row that is only just active (multiplier lam* ~ 1e-7) keeps the slack mu / lam*, so two iterations that stop
 at different mu - the kernel's warm Riccati iteration and the oracle's cold dense one - hand back controls up to 1e-4 apart; that, not rounding, is why the
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import helpers as hp
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import dptr
 
@@ -24,13 +25,8 @@ TOL_U_LANDED = 1e-9            # applied control and whole horizon, GPU (landed)
 
 @pytest.fixture()
 def landed_cold_orc(orc):
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    orc.lib.orc_set_su_land(1)
-    orc.lib.orc_set_threads(16)
-    yield orc
-    orc.lib.orc_set_su_land(1)                      # (the default since round 6)
-    orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
-    orc.lib.orc_set_threads(1)
+    with switches(su_land=1, threads=16, **hp.COLD_SU):        # (su_land = 1 is the default since round 6)
+        yield orc
 
 
 def _hip_landed(hip):

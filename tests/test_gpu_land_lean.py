@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import helpers as hp
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 
 pytestmark = pytest.mark.gpu
@@ -137,15 +138,12 @@ def _su_problem_in_a_handle(hip, cfg, si, **opts):
 @pytest.mark.parametrize("name", ["diff_T20_N24_just_active_hinges", "omni_T15_N40_hinge_flips"])      # (T = 20: time split; T = 15: one recursion)
 def test_refused_landing_goes_back_to_the_interior_point(orc, hip, name):
     from rda_planner_amd.rda_solver import hip_options
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0); orc.lib.orc_set_su_land(1)
-    try:
+    with switches(su_land=1, **hp.COLD_SU):
         cfg, si = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", name + ".npz"))
         st = (C.c_long * 8)()
         orc.lib.orc_get_su_land_stats(st)                       # (reading clears them)
         so = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
         orc.lib.orc_get_su_land_stats(st)
-    finally:
-        orc.lib.orc_set_su_land(1); orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
     lt = hip_options().su_land_tol
     (s, u, d), status, ipm, ls = _su_problem_in_a_handle(hip, cfg, si, su_land=1)
     _, status1, ipm1, ls1 = _su_problem_in_a_handle(hip, cfg, si, su_land=0, su_tol=(lt[0], lt[1], lt[2]))      # the same start, run to the first landing stop only

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import helpers as hp
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr
 
@@ -477,11 +478,8 @@ def test_su_weakly_active_instances_from_the_round4_soak(orc, hip, name):
     it ends on the vertex the tight oracle converges to (8e-9 .. 1e-9: what that interior point is still short of it)"""
     import ctypes as C
     cfg, inp = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", name + ".npz"))
-    try:
-        orc.lib.orc_set_su_tol(1e-12, 1e-12, 1e-15)
+    with switches(su_tol=(1e-12, 1e-12, 1e-15)):
         so = hp.su_solve(orc.lib.orc_su_solve, cfg, inp)
-    finally:
-        orc.lib.orc_set_su_tol(1e-9, 1e-10, 1e-11)
     sh = hp.su_solve(hip.lib.rda_su_solve, cfg, inp)
     assert so[0] == 0 and sh[0] == 0
     d = max(float(np.abs(so[k] - sh[k]).max()) for k in (1, 2, 3))
@@ -537,8 +535,7 @@ def test_closed_loop_dynamic_obs_example(orc):
     def car_of(env):
         ri = env.get_robot_info()
         return sc.car(ri.G, ri.h, ri.cone_type, ri.wheelbase, [10, 1], [10, 1.0], "acker")
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    try:
+    with switches(**hp.COLD_SU):
         env = irsim.make(yaml_path)
         car_t = car_of(env)
         cpu = MPC(car_t, [p.copy() for p in path], sample_time=0.1, _backend=oracle_backend, **kw)
@@ -563,8 +560,6 @@ def test_closed_loop_dynamic_obs_example(orc):
                 break
         print(f"dynamic_obs example vs cold oracle: {i + 1} steps, max |du| over the horizon {worst:.2e}, same ADMM iteration count on {same}")
         assert worst <= hp.TOL_U_FIXED and same >= 0.95 * (i + 1), (worst, same, i + 1)
-    finally:
-        orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
     env = irsim.make(yaml_path)
     solo = MPC(car_of(env), [p.copy() for p in path], sample_time=0.1, **kw)
     minc = np.inf

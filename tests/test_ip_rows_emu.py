@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers as hp
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import c_double_p, c_int_p, dptr
 
@@ -60,12 +61,11 @@ ROBOTS = {"rectangle": (hp.G, hp.H, 0),
 @pytest.mark.parametrize("mu", [1e-3, 1e-6])
 def test_row_parallel_kernel_arithmetic_equals_the_oracle_on_the_central_path(emu, orc, robot, accelerated, mu):
     L = _oracle(orc)
-    L.orc_set_lmz_ipm_mu(mu)
     G, h, rn2 = ROBOTS[robot]
     R = G.shape[0]
     rng = np.random.default_rng(7 + 13 * accelerated + (0 if robot == "rectangle" else 101))
     worst = 0.0
-    try:
+    with switches(lmz_mu=mu):
         for trial in range(60):
             circ = trial % 3 == 2
             E = 4
@@ -83,8 +83,6 @@ def test_row_parallel_kernel_arithmetic_equals_the_oracle_on_the_central_path(em
             scale = 1.0 + max(np.abs(lo).max(), np.abs(mo).max(), abs(zo.value))
             worst = max(worst, err / scale)
             assert err <= 2e-6 * scale, (trial, circ, err, lo, le, mo, me, zo.value, ze.value)
-    finally:
-        L.orc_set_lmz_ipm_mu(1e-6)
 
 
 @pytest.mark.parametrize("robot", ["rectangle", "circle"])

@@ -16,6 +16,7 @@ import pytest
 
 import helpers as hp
 import lmz_central_ref as ref
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, c_double_p, c_int_p, dptr, iptr, f64
 from test_ip_rows_emu import emu          # noqa: F401  (the fixture that builds tests/emu/rip_emu.cpp)
@@ -103,7 +104,7 @@ def grid(accelerated, mu, edges=(3, 4, 5, 6, 8)):
 
 
 def oracle_row(L, row):
-    """orc_lammuz_ipm_one on a row -> (status, lam, mu, z); the caller has set orc_set_lmz_ipm_mu(row.mu_star)"""
+    """orc_lammuz_ipm_one on a row -> (status, lam, mu, z); the caller runs it inside switches(lmz_mu=row.mu_star)"""
     lo, mo, zo, cmh, it = np.zeros(row.E), np.zeros(row.R), C.c_double(0), np.zeros(4), C.c_int(0)
     st = L.orc_lammuz_ipm_one(row.E, row.R, dptr(row.A), dptr(row.b), row.cone_norm2, row.robot_norm2, dptr(row.p), row.phi, dptr(row.G), dptr(row.h),
                               dptr(row.xi), row.zeta, row.dbar, row.ro2, row.accelerated, dptr(lo), dptr(mo), C.cast(C.byref(zo), c_double_p), dptr(cmh),
@@ -128,9 +129,8 @@ def _fits(emu, row):
 @pytest.mark.parametrize("accelerated,mu", CLASSES)
 def test_oracle_equals_the_reference_on_the_pinned_grid(orc, accelerated, mu):
     L = orc.lib
-    L.orc_set_lmz_ipm_mu(mu)
     worst, where, res, step = 0.0, None, 0.0, 0.0
-    try:
+    with switches(lmz_mu=mu):
         rows = grid(accelerated, mu)
         for label, row in rows:
             want = ref.solve_row(row)                 # (raises when it cannot certify the row)
@@ -140,8 +140,6 @@ def test_oracle_equals_the_reference_on_the_pinned_grid(orc, accelerated, mu):
             if dev > worst:
                 worst, where = dev, label
             res, step = max(res, want.grad_res), max(step, want.step)
-    finally:
-        L.orc_set_lmz_ipm_mu(1e-6)
     print(f"oracle vs reference, accelerated={accelerated} mu*={mu:g}: {len(rows)} rows, worst deviation {worst:.2e} at [{where}]; "
           f"reference certificate: gradient <= {res:.1e}, Newton step at the point / (1 + |x|) <= {step:.1e}")
     assert worst <= ref.ORACLE_WORST[(accelerated, mu)], (worst, where)
@@ -294,9 +292,8 @@ def test_rows_rebuilt_from_the_handle_state_are_what_the_oracle_solved(orc, name
     mu = 1e-3
     g = np.load(os.path.join(GOLD, "ref_plumbing.npz"))
     T, N, E, iter_num, ro1, dyn = (int(v) if i != 4 else float(v) for i, v in enumerate(g[f"{name}.cfg"]))
-    orc.lib.orc_set_lmz_mode(1); orc.lib.orc_set_lmz_ipm_mu(mu)
     worst = {}
-    try:
+    with switches(lmz_mode=1, lmz_mu=mu):
         s = RDA_solver(T, _car(dyn), E, N, iter_num=iter_num, time_print=False, ro1=ro1, _backend=oracle_backend)
         bound = ref.gpu_bound(s._cfg.accelerated, mu)
 
@@ -304,8 +301,6 @@ def test_rows_rebuilt_from_the_handle_state_are_what_the_oracle_solved(orc, name
             assert inf.lmz_fail == 0
             check_rows(rows, bound, f"{name} step {k} it {it}", worst)
         drive_rows(s, recorded_steps(name, 3), mu, on_call)
-    finally:
-        orc.lib.orc_set_lmz_mode(0); orc.lib.orc_set_lmz_ipm_mu(1e-6)
     print(f"{name}, oracle backend, rows rebuilt from the handle state: {figures(worst)} (bound on the deviation {bound:.1e})")
     assert not worst["bad"], worst["bad"][:5]
     assert worst["rows"] >= 100

@@ -13,6 +13,7 @@ import lmz_central_ref as ref
 import lmz_rows_cert as cert
 import test_gpu_lmz_rows_cert as gpu_cases
 from lmz_central_ref import LD
+from oracle.oracle_backend import switches
 from rda_planner_amd._capi import dptr, f64
 from test_lmz_central_ref import GOLD, drive_rows, grid, recorded_steps
 
@@ -185,11 +186,8 @@ def test_wrong_answers_are_rejected_with_a_margin(orc):
         if _moved(ans, wrong):
             kinds.setdefault(kind, []).append(cert.margin(row, *wrong))
 
-    L.orc_set_centre(0)
-    try:
+    with switches(tie_centre=0):
         uncentred = [c_oracle(L, row) for _, row in rows]
-    finally:
-        L.orc_set_centre(1)
     for k, ((label, row), ans) in enumerate(zip(rows, right)):
         tried("the optimum of the row with xi + 1e-8", row, ans, c_oracle(L, row._replace(xi=row.xi + 1e-8)))
         tried("the delta = 0 optimum", row, ans, c_oracle(L, row, delta=0.0))
@@ -269,12 +267,9 @@ def test_edge_scenes_of_the_gpu_cases_on_the_oracle_backend():
 
 
 def test_no_row_is_centred_with_the_tie_break_off(orc):
-    """orc_set_centre(0), the oracle's RDA_TIE_CENTRE=0: every row of the E = 4 scene meets criterion A"""
+    """tie_centre = 0, the oracle's RDA_TIE_CENTRE=0: every row of the E = 4 scene meets criterion A"""
     from oracle.oracle_backend import oracle_backend
-    orc.lib.orc_set_centre(0)
-    try:
+    with switches(tie_centre=0):
         s = gpu_cases.make_solver("E4-rectangle", _backend=oracle_backend)
         w = gpu_cases.certify_loop(s, gpu_cases.scenes_of("E4-rectangle"), None, gpu_cases.SHAPES["E4-rectangle"][4], "tie_centre = 0", tie_centre=0, classes=False)
-    finally:
-        orc.lib.orc_set_centre(1)
     assert w.get("B", 0) == 0 and w["A"] == w["rows"]

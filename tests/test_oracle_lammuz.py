@@ -13,6 +13,7 @@ import pytest
 
 import helpers as hp
 from oracle.lammuz_np import solve_lammuz
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "lammuz_golden.json")
@@ -68,11 +69,8 @@ def test_kkt_certificate_polygons(orc):
     """the enumeration (tie-break T1 = max clearance, i.e. the delta-perturbed problem) returns a KKT point"""
     rng = np.random.default_rng(3)
     inp = hp.lammuz_batch_inputs(rng, 400, circles=0.0)
-    orc.lib.orc_set_centre(0)
-    try:
+    with switches(tie_centre=0):
         lam, mu, z, cmh = hp.oracle_lammuz_batch(orc, inp)
-    finally:
-        orc.lib.orc_set_centre(1)
     worst = 0.0
     for i in range(400):
         worst = max(worst, _kkt_residual(inp["A"][i], inp["b"][i], inp["p"][i], inp["phi"][i], inp["xi"][i],
@@ -170,9 +168,8 @@ def test_central_normal_rule(orc):
     unit normal sits in the middle of the arc of separating directions - checked against a brute-force scan of that arc"""
     rng = np.random.default_rng(12)
     inp = hp.lammuz_batch_inputs(rng, 300, circles=0.3)
-    orc.lib.orc_set_centre(0)
-    lam0, mu0, z0, cmh0 = hp.oracle_lammuz_batch(orc, inp)
-    orc.lib.orc_set_centre(1)
+    with switches(tie_centre=0):
+        lam0, mu0, z0, cmh0 = hp.oracle_lammuz_batch(orc, inp)
     lam, mu, z, cmh = hp.oracle_lammuz_batch(orc, inp)
     n_central = 0
     for i in range(300):
@@ -251,11 +248,8 @@ def test_known_answer_distances(orc, kind, pose, dist):
         cone = 1
     inp = dict(A=A[None], b=b[None], cone=np.array([cone], np.int32), p=np.array([pose[:2]], float), phi=np.array([pose[2]]),
                xi=np.zeros((1, 2)), zeta=np.zeros(1), dbar=np.array([0.1]))
-    orc.lib.orc_set_centre(0)
-    try:
+    with switches(tie_centre=0):
         lam, mu, z, cmh = hp.oracle_lammuz_batch(orc, inp)
-    finally:
-        orc.lib.orc_set_centre(1)
     # max clearance is rewarded with delta = 1e-6, which buys delta*|x_R|^2/ro2 <= 1.6e-5 of extra m for H = -delta/ro2 * x_R
     assert abs(cmh[0, 1] + 0.1 - dist) < 3e-5
     assert abs(np.linalg.norm(A.T @ lam[0]) - 1) < 1e-9
@@ -290,6 +284,7 @@ def test_golden_vectors(orc):
     assert np.abs(mu - np.array(gold["mu"]))[ok].max() < 1e-8
 
 
+@switches(lmz_mu=0.0)          # stop by the gap test
 def test_ipm_norm2_robot_certifies_exactly_the_geometric_distance(orc):
     """Known-answer test of the cone conventions of the interior-point restatement (oracle/lmz_ipm.c) for a CIRCLE robot
     (car_tuple.cone_type == 'norm2', rda_solver.py:1034-1039): the sub-problem has optimal value 0 iff duals exist that certify
@@ -298,7 +293,6 @@ def test_ipm_norm2_robot_certifies_exactly_the_geometric_distance(orc):
     import ctypes as C
     from rda_planner_amd._capi import c_double_p, c_int_p, dptr
     L = orc.lib
-    L.orc_set_lmz_ipm_mu(0.0)
     r = 0.8
     G = np.ascontiguousarray([[1.0, 0.0], [0.0, 1.0], [0.0, 0.0]])
     h = np.ascontiguousarray([0.0, 0.0, -r])
@@ -328,4 +322,3 @@ def test_ipm_norm2_robot_certifies_exactly_the_geometric_distance(orc):
             assert np.hypot(mo[0], mo[1]) <= -mo[2] + 1e-7                      # mu in the robot's cone
             vals.append(cmh[0])
         assert vals[0] < 1e-9 and vals[1] > 2e-5, (trial, dist, vals)
-    L.orc_set_lmz_ipm_mu(1e-6)

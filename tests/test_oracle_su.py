@@ -5,6 +5,7 @@ import pytest
 
 import helpers as hp
 import su_kkt
+from oracle.oracle_backend import switches
 
 
 _lin, _objective = su_kkt.lin, su_kkt.objective          # the reference's linearisation and cost (restated in tests/su_kkt.py)
@@ -13,13 +14,12 @@ _lin, _objective = su_kkt.lin, su_kkt.objective          # the reference's linea
 @pytest.fixture(autouse=True)
 def _interior_point_only(request, orc):
     """this module is about the oracle's interior-point iteration (stop tolerances, cycling instances, start rules): the landing that is default since
-    round 6 (orc_set_su_land) is switched off - except in the tests of the landing itself"""
+    round 6 (su_land) is switched off - except in the tests of the landing itself"""
     if "landing" in request.node.name:
         yield
         return
-    orc.lib.orc_set_su_land(0)
-    yield
-    orc.lib.orc_set_su_land(1)
+    with switches(su_land=0):
+        yield
 
 
 @pytest.mark.parametrize("trial", range(6))
@@ -223,21 +223,15 @@ def test_stop_tolerance_vs_weakly_active_rows(orc, name):
     mode) sits between the two; the landed solve of round 6 is checked against the same three problems below."""
     import os
     cfg, si = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", name + ".npz"))
-    try:
-        orc.lib.orc_set_su_tol(1e-12, 1e-12, 1e-15)
+    with switches(su_tol=(1e-12, 1e-12, 1e-15)):
         st_t, _, u_t, _, it_t = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
-        orc.lib.orc_set_su_tol(1e-9, 1e-10, 1e-11)
-        st_d, _, u_d, _, it_d = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
-        orc.lib.orc_set_su_tol(1e-8, 1e-8, 1e-8)
+    st_d, _, u_d, _, it_d = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
+    with switches(su_tol=(1e-8, 1e-8, 1e-8)):
         st_e, _, u_e, _, it_e = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
-        # round 6: the LANDED solve (the default; this module switches it off) - the interior point stops at the 1e-3 class, the vertex is computed exactly
-        orc.lib.orc_set_su_tol(1e-9, 1e-10, 1e-11)
-        orc.lib.orc_set_su_land(1)
+    # round 6: the LANDED solve (the default; this module switches it off) - the interior point stops at the 1e-3 class, the vertex is computed exactly
+    with switches(su_land=1):
         st_l, _, u_l, _, it_l = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
         landed = orc.lib.orc_get_su_landed()
-    finally:
-        orc.lib.orc_set_su_tol(1e-9, 1e-10, 1e-11)
-        orc.lib.orc_set_su_land(0)
     assert st_t == 0 and st_d == 0 and st_e == 0 and it_e <= it_d <= it_t
     d_def, d_ecos = float(np.abs(u_d - u_t).max()), float(np.abs(u_e - u_t).max())
     d_land = float(np.abs(u_l - u_t).max())
@@ -255,40 +249,35 @@ def test_warm_started_su_reaches_the_cold_solution():
     from the same solver state must coincide to the solver tolerance, with the same ADMM iteration count.  What the warm start
     saves depends on the workload (one interior-point iteration per solve on the N=200 benchmark, nothing on this small scene);
     it must not cost more than a few per cent anywhere."""
-    from oracle.oracle_backend import api, oracle_backend
+    from oracle.oracle_backend import oracle_backend
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.mpc import MPC
-    lib = api().lib
-    try:
-        for dyn in ("acker", "diff", "omni"):
-            car_t = sc.rectangle_robot(dynamics=dyn, wheelbase=3.0 if dyn == "acker" else 0)
-            path = sc.line_path([4, 20, 0], [20, 20, 0], 0.1)
-            clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])
-            scene = sc.scene_polygons(8, lo=(6, 13), hi=(22, 27), seed=7, keep_clear=clear, clear_radius=2.6)
-            kw = dict(receding=10, iter_num=4, max_edge_num=4, max_obs_num=8, _backend=oracle_backend, time_print=False)
-            a, b = MPC(car_t, [p.copy() for p in path], **kw), MPC(car_t, [p.copy() for p in path], **kw)
-            st = path[0].copy().reshape(3, 1)
-            if dyn == "omni":
-                st[2, 0] = 0.0
-            ipm_w = ipm_c = 0
-            for k in range(25):
-                lib.orc_set_su_warm(1e-3, 1e-3, 30)
-                uw, iw = a.control(st.copy(), 4.0, list(scene))
-                lib.orc_set_su_warm(0.0, 0.0, 0)
+    for dyn in ("acker", "diff", "omni"):
+        car_t = sc.rectangle_robot(dynamics=dyn, wheelbase=3.0 if dyn == "acker" else 0)
+        path = sc.line_path([4, 20, 0], [20, 20, 0], 0.1)
+        clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])
+        scene = sc.scene_polygons(8, lo=(6, 13), hi=(22, 27), seed=7, keep_clear=clear, clear_radius=2.6)
+        kw = dict(receding=10, iter_num=4, max_edge_num=4, max_obs_num=8, _backend=oracle_backend, time_print=False)
+        a, b = MPC(car_t, [p.copy() for p in path], **kw), MPC(car_t, [p.copy() for p in path], **kw)
+        st = path[0].copy().reshape(3, 1)
+        if dyn == "omni":
+            st[2, 0] = 0.0
+        ipm_w = ipm_c = 0
+        for k in range(25):
+            uw, iw = a.control(st.copy(), 4.0, list(scene))
+            with switches(**hp.COLD_SU):
                 uc, ic = b.control(st.copy(), 4.0, list(scene))
-                assert iw["iters"] == ic["iters"], (dyn, k)
-                # the speed row is pinned by the wu term; the second control (steering / turn rate) enters the cost only through the
-                # predicted states, a direction in which the cost is nearly flat: two runs that stop at the same residual tolerance
-                # (1e-9 relative) along different iteration paths agree there to ~1e-4 only (3e-5 observed)
-                du = np.abs(uw - uc).max(axis=1)
-                assert du[0] < 1e-5 and du[1] < 2e-4, (dyn, k, du)
-                ipm_w += iw["su_ipm_iters"]; ipm_c += ic["su_ipm_iters"]
-                b.rda.set_state(a.rda.get_state())              # the cold run continues from the warm run's state
-                b.cur_vel_array, b.cur_index = a.cur_vel_array.copy(), a.cur_index
-                st = sc.kinematic_step(st, uw, car_t, 0.1)
-            assert ipm_w <= 1.05 * ipm_c, (dyn, ipm_w, ipm_c)
-    finally:
-        lib.orc_set_su_warm(1e-3, 1e-3, 30)
+            assert iw["iters"] == ic["iters"], (dyn, k)
+            # the speed row is pinned by the wu term; the second control (steering / turn rate) enters the cost only through the
+            # predicted states, a direction in which the cost is nearly flat: two runs that stop at the same residual tolerance
+            # (1e-9 relative) along different iteration paths agree there to ~1e-4 only (3e-5 observed)
+            du = np.abs(uw - uc).max(axis=1)
+            assert du[0] < 1e-5 and du[1] < 2e-4, (dyn, k, du)
+            ipm_w += iw["su_ipm_iters"]; ipm_c += ic["su_ipm_iters"]
+            b.rda.set_state(a.rda.get_state())              # the cold run continues from the warm run's state
+            b.cur_vel_array, b.cur_index = a.cur_vel_array.copy(), a.cur_index
+            st = sc.kinematic_step(st, uw, car_t, 0.1)
+        assert ipm_w <= 1.05 * ipm_c, (dyn, ipm_w, ipm_c)
 
 
 def test_su_replay_tool_records_and_replays(tmp_path, monkeypatch):
@@ -300,18 +289,14 @@ def test_su_replay_tool_records_and_replays(tmp_path, monkeypatch):
     monkeypatch.syspath_prepend(os.path.join(root, "tools"))
     sys.modules.pop("su_replay", None)
     su_replay = importlib.import_module("su_replay")
-    try:
-        su_replay.record("t", n_obs=12, T=8, steps=3, moving=True)
-        probs = su_replay.load("t")
-        assert 3 <= len(probs) <= 12 and probs[0]["T"] == 8 and probs[0]["N"] == 12 and probs[0]["it"] == 0
-        lib = su_replay._lib()
-        for pr in probs:
-            st, its, so, uo, do = su_replay.solve(lib, pr)
-            assert st == 0 and 1 <= its <= 40
-            assert np.all(np.isfinite(uo)) and np.all(do <= pr["cfg"].max_sd + 1e-9) and np.all(do >= pr["cfg"].min_sd - 1e-9)
-    finally:                                   # the recording run switched the oracle's su start rules and thread count: back to the defaults
-        lib = su_replay._lib()
-        lib.orc_set_su_warm(1e-3, 1e-3, 30); lib.orc_set_threads(1); lib.orc_set_su_dump(b""); lib.orc_set_su_trace(0)
+    su_replay.record("t", n_obs=12, T=8, steps=3, moving=True)
+    probs = su_replay.load("t")
+    assert 3 <= len(probs) <= 12 and probs[0]["T"] == 8 and probs[0]["N"] == 12 and probs[0]["it"] == 0
+    lib = su_replay._lib()
+    for pr in probs:
+        st, its, so, uo, do = su_replay.solve(lib, pr)
+        assert st == 0 and 1 <= its <= 40
+        assert np.all(np.isfinite(uo)) and np.all(do <= pr["cfg"].max_sd + 1e-9) and np.all(do >= pr["cfg"].min_sd - 1e-9)
 
 
 def test_end_game_lost_in_rounding_returns_the_near_converged_iterate(orc):
@@ -324,13 +309,10 @@ def test_end_game_lost_in_rounding_returns_the_near_converged_iterate(orc):
     own hand-over is exercised by its test switch (accept = 2: always hand the remembered iterate back).  Either way the point is a minimiser to 1e-6."""
     import os
     cfg, si = hp.load_su_case(os.path.join(os.path.dirname(__file__), "golden", "su_hard", "omni_T25_N20_end_game_noise.npz"))
-    try:
-        orc.lib.orc_set_su_accept(0)
+    with switches(su_accept=0):
         st0, _, u0, _, it0 = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
-        orc.lib.orc_set_su_accept(2)
+    with switches(su_accept=2):
         st2, _, u2, _, it2 = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
-    finally:
-        orc.lib.orc_set_su_accept(1)
     st, s, u, d, it = hp.su_solve(orc.lib.orc_su_solve, cfg, si)
     assert st0 == 0 and st == 0 and st2 == 0 and it == it0 == it2 and 20 < it <= 40, (st0, st, st2, it0, it, it2)        # (cold attempt 16, last resort 20)
     assert np.array_equal(u, u0) and 0 < np.abs(u2 - u).max() <= 2e-4           # the remembered iterate: of the looser class, next to the converged one
@@ -369,25 +351,22 @@ def test_warm_start_after_an_unconverged_step_saves_iterations_and_moves_nothing
     obstacles = sc.scene_polygons(200, lo=(8, 10), hi=(40, 40), seed=sc.SEED, keep_clear=clear, clear_radius=3.2)      # (the north-star scene)
 
     def loop(order, hard, iter_num=4, steps=40):
-        orc.lib.orc_set_su_hard_warm(*hard)
         m = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, receding=20, iter_num=iter_num, max_edge_num=4, max_obs_num=200,
                 ro1=200, obstacle_order=order, _backend=oracle_backend)
         st, us, ipm, its = path[0].copy().reshape(3, 1), [], 0, 0
-        for k in range(steps):
-            u, info = m.control(st, 4.0, list(obstacles))
-            assert info["status"] == 0
-            us.append(u.ravel().copy()); ipm += info["su_ipm_iters"]; its += info["iters"]
-            st = sc.kinematic_step(st, u, car_t, 0.1)
+        with switches(su_hard_warm=hard):
+            for k in range(steps):
+                u, info = m.control(st, 4.0, list(obstacles))
+                assert info["status"] == 0
+                us.append(u.ravel().copy()); ipm += info["su_ipm_iters"]; its += info["iters"]
+                st = sc.kinematic_step(st, u, car_t, 0.1)
         return np.array(us), ipm, its
-    try:
-        u0, ipm0, its0 = loop(True, (0.0, 0.0))
-        u1, ipm1, its1 = loop(True, (1.0, 1e-3))
-        f0, fi0, _ = loop(False, (0.0, 0.0))
-        f1, fi1, _ = loop(False, (1.0, 1e-3))
-        g0, gi0, _ = loop(False, (0.0, 0.0), iter_num=1, steps=25)          # every step 'unconverged' (one ADMM iteration), every su-problem easy
-        g1, gi1, _ = loop(False, (1.0, 1e-3), iter_num=1, steps=25)
-    finally:
-        orc.lib.orc_set_su_hard_warm(1.0, 1e-3)
+    u0, ipm0, its0 = loop(True, (0.0, 0.0))
+    u1, ipm1, its1 = loop(True, (1.0, 1e-3))
+    f0, fi0, _ = loop(False, (0.0, 0.0))
+    f1, fi1, _ = loop(False, (1.0, 1e-3))
+    g0, gi0, _ = loop(False, (0.0, 0.0), iter_num=1, steps=25)          # every step 'unconverged' (one ADMM iteration), every su-problem easy
+    g1, gi1, _ = loop(False, (1.0, 1e-3), iter_num=1, steps=25)
     print(f"re-sorted loop: {ipm0} -> {ipm1} interior-point iterations over 40 steps ({its0} / {its1} ADMM iterations), max |du| {np.abs(u0 - u1).max():.1e}")
     assert its0 == its1 and ipm1 <= 0.85 * ipm0, (ipm0, ipm1)
     assert np.abs(u0 - u1).max() <= 1e-4
@@ -404,31 +383,26 @@ def test_landing_makes_the_su_answer_independent_of_the_interior_point_path(orc,
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.mpc import MPC
     from rda_planner_amd import scenarios as sc
-    lib = orc.lib
     car_t = sc.rectangle_robot(dynamics="acker")
     path = sc.line_path([4, 25, 0], [40, 25, 0], 0.1)
     clear = np.array([[p[0, 0], p[1, 0]] for p in path[::10]])
     obstacles = sc.scene_polygons(24, lo=(8, 17), hi=(40, 33), seed=sc.SEED + 5, keep_clear=clear, clear_radius=2.2, moving=moving)
     kw = dict(receding=12, iter_num=3, max_edge_num=4, max_obs_num=24, ro1=200, obstacle_order=True, time_print=False)
     worst = {}
-    try:
-        for land in (0, 1):
-            lib.orc_set_su_land(land)
+    for land in (0, 1):
+        with switches(su_land=land):
             a = MPC(car_t, [p.copy() for p in path], sample_time=0.1, _backend=oracle_backend, **kw)
             b = MPC(car_t, [p.copy() for p in path], sample_time=0.1, _backend=oracle_backend, **kw)
             state, w = path[0].copy().reshape(3, 1), 0.0
             for k in range(16):
                 cur = obstacles if not moving else [o._replace(vertex=o.vertex + o.velocity * (0.1 * k)) for o in obstacles]
-                lib.orc_set_su_warm(1e-3, 1e-3, 30)
                 ua, ia = a.control(state.copy(), 4.0, list(cur))
-                lib.orc_set_su_warm(0.0, 0.0, 0)
-                ub, ib = b.control(state.copy(), 4.0, list(cur))
+                with switches(**hp.COLD_SU):
+                    ub, ib = b.control(state.copy(), 4.0, list(cur))
                 assert ia["iters"] == ib["iters"]
                 w = max(w, float(np.abs(a.cur_vel_array - b.cur_vel_array).max()))
                 b.rda.set_state(a.rda.get_state()); b.cur_vel_array = a.cur_vel_array.copy()
                 state = sc.kinematic_step(state, ua, car_t, 0.1)
             worst[land] = w
-    finally:
-        lib.orc_set_su_warm(1e-3, 1e-3, 30); lib.orc_set_su_land(1)
     print(f"moving={moving}: warm path vs cold path, max |du| over the horizon: {worst[0]:.2e} without the landing, {worst[1]:.2e} with it")
     assert worst[1] <= 1e-10 and worst[1] < worst[0]

@@ -20,6 +20,7 @@ import pytest
 
 import helpers as hp
 import su_kkt
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Info, dptr, iptr, f64
 
@@ -90,11 +91,8 @@ def _replay(make_solver, name, tol_state, tol_u, digest_tol):
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture()
 def cold_orc(orc):
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    orc.lib.orc_set_su_land(0)          # (the plumbing fixtures were recorded with the oracle's interior-point argmins injected: make_ref_golden.py, before the landing)
-    yield orc
-    orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
-    orc.lib.orc_set_su_land(1)
+    with switches(su_land=0, **hp.COLD_SU):      # (the plumbing fixtures were recorded with the oracle's interior-point argmins injected: make_ref_golden.py, before the landing)
+        yield orc
 
 
 @pytest.mark.parametrize("name", SCENES)

@@ -27,11 +27,12 @@ import pytest
 
 from oracle import ref_loader
 from oracle import ref_harness as rh
+from oracle.oracle_backend import switches
 from rda_planner_amd import scenarios as sc
 from rda_planner_amd._capi import Cfg, Info, dptr, f64
 from rda_planner_amd.rda_solver import RDA_solver
 
-from helpers import random_polygon, su_solve
+from helpers import COLD_SU, random_polygon, su_solve
 
 ADJ = ("ro1", "ro2", "slack_gain", "max_sd", "min_sd", "ws", "wu", "iter_threshold")
 PINNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_pinned")     # <first part of the key>.pkl.xz
@@ -121,9 +122,8 @@ def _shim_on_path():
 @pytest.fixture()
 def cold_orc(orc):
     """the oracle's pure hooks start cold; make `orc_admm_su` do the same so both sides call the same function"""
-    orc.lib.orc_set_su_warm(0.0, 0.0, 0)
-    yield orc
-    orc.lib.orc_set_su_warm(1e-3, 1e-3, 30)
+    with switches(**COLD_SU):
+        yield orc
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -570,6 +570,7 @@ def _ipm_api(orc):
 
 
 @pytest.mark.parametrize("robot", ["rectangle", "circle"])
+@switches(lmz_mu=0.0)                             # stop by the gap test, like the stand-in and like ECOS
 def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, robot):
     """`orc_lammuz_ipm_one` builds the cone program of ONE (obstacle, stage) by hand (canonical form in oracle/lmz_ipm.c); the
     reference builds the same program itself when constructed with receding = 1.  Both are solved by the same algorithm
@@ -577,7 +578,6 @@ def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, ro
     circle obstacles, rectangle AND circle (norm2, rda_solver.py:1034-1039) robots; the interior multipliers agree to a few
     per cent (the reference problem carries the free column 0 of lam, mu, which shares the step lengths - see DESIGN.md)."""
     L = _ipm_api(orc)
-    L.orc_set_lmz_ipm_mu(0.0)                     # stop by the gap test, like the stand-in and like ECOS
     if robot == "rectangle":
         car_t = sc.rectangle_robot(dynamics="acker")
         rn2 = 0
@@ -650,7 +650,6 @@ def test_interior_point_restatement_on_reference_one_stage_problems(ref, orc, ro
             assert np.linalg.norm(mo[:-1]) <= -mo[-1] + 1e-7
         else:
             assert mo.min() >= 0
-    L.orc_set_lmz_ipm_mu(1e-6)
     assert n_inacc <= 2
     # H and min(Im, 0) enter the cost squared: a 1e-8 optimality gap leaves them accurate to ~1e-4
     assert worst["cost"] < 2e-8 and worst["H"] < 2e-4 and worst["mneg"] < 2e-4 and worst["rel"] < 0.08, worst

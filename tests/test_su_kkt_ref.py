@@ -11,6 +11,7 @@ import pytest
 
 import helpers as hp
 import su_kkt
+from oracle.oracle_backend import su_dump
 from rda_planner_amd._capi import Info, dptr, iptr, f64
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -280,7 +281,7 @@ def _load_dump(path, T, N):
 @pytest.mark.parametrize("name", ["c1", "c4", "ns"])
 def test_rebuilt_su_problems_equal_what_the_oracle_solves(orc, tmp_path, name):
     """the harness of the GPU hot-path test: the su-problem of every ADMM iteration rebuilt from the handle's state (su_kkt.su_inputs_from_state)
-    is what orc_admm_su records (orc_set_su_dump) bit for bit; the oracle's in-loop answers are within TOL_U_FIXED of the certified optimum"""
+    is what orc_admm_su records (oracle_backend.su_dump) bit for bit; the oracle's in-loop answers are within TOL_U_FIXED of the certified optimum"""
     from oracle.oracle_backend import oracle_backend
     from rda_planner_amd.rda_solver import RDA_solver
     dump = tmp_path / "su.bin"
@@ -293,11 +294,8 @@ def test_rebuilt_su_problems_equal_what_the_oracle_solves(orc, tmp_path, name):
         rebuilt.append((it, si))
         c = su_kkt.certify(cfg, si, start=(s, u, dis))
         worst[0] = max(worst[0], check_against(c, s, u, dis, hp.TOL_U_FIXED, f"{name} step {k} it {it}"))
-    orc.lib.orc_set_su_dump(str(dump).encode())
-    try:
+    with su_dump(dump):
         drive_recorded_loop(make, name, on_su, steps=3 if name == "ns" else None)
-    finally:
-        orc.lib.orc_set_su_dump(b"")
     T, N = rebuilt[0][1]["nom_u"].shape[1], rebuilt[0][1]["a"].shape[0]
     rec = _load_dump(str(dump), T, N)
     assert len(rec) == len(rebuilt) > 0

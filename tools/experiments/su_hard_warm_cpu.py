@@ -12,11 +12,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from rda_planner_amd.mpc import MPC  # noqa: E402
 from rda_planner_amd import scenarios as sc  # noqa: E402
-from oracle.oracle_backend import oracle_backend, api as orc_api  # noqa: E402
-
-lib = orc_api().lib
-lib.orc_set_threads(min(16, os.cpu_count() or 1))
-
+from oracle.oracle_backend import oracle_backend, switches  # noqa: E402
 
 def run(order, iter_num=4, n_obs=200, T=20, moving=False, steps=60, thr=None):
     car_t, path, obstacles, kw = bench.build_workload(n_obs=n_obs, T=T, n_steps=steps + 20, moving=moving)
@@ -35,18 +31,18 @@ def run(order, iter_num=4, n_obs=200, T=20, moving=False, steps=60, thr=None):
     return ipm / sol
 
 
-try:
+with switches(threads=min(16, os.cpu_count() or 1)):
     if sys.argv[1:] == ["floors"]:
         for wfl, mu0 in [(0, 0), (1e-3, 1e-3), (1e-2, 1e-2), (0.1, 1e-2), (0.1, 1e-3), (0.3, 1e-3), (1.0, 1e-2), (1.0, 1e-3), (1.0, 1e-4), (3.0, 1e-2)]:
-            lib.orc_set_su_warm(wfl, mu0, 30)
-            print(f"warm attempts from (slack floor {wfl:g}, mu0 {mu0:g}): {run(True):.2f} interior-point iterations per su-solve", flush=True)
+            with switches(su_warm=(wfl, mu0)):
+                print(f"warm attempts from (slack floor {wfl:g}, mu0 {mu0:g}): {run(True):.2f} interior-point iterations per su-solve", flush=True)
     else:
         cases = [("north star, fixed binding", dict(order=False)), ("fixed, iter_num 1", dict(order=False, iter_num=1)), ("fixed, iter_num 2, iter_threshold 0.02", dict(order=False, iter_num=2, thr=0.02)),
                  ("north star, re-sorted", dict(order=True)), ("re-sorted, iter_num 2", dict(order=True, iter_num=2)), ("C4 fixed", dict(order=False, T=30, moving=True, steps=40)),
                  ("C4 re-sorted", dict(order=True, T=30, moving=True, steps=40)), ("N=20 re-sorted", dict(order=True, n_obs=20))]
         for name, kw in cases:
-            lib.orc_set_su_hard_warm(0.0, 0.0); a = run(**kw)
-            lib.orc_set_su_hard_warm(1.0, 1e-3); b = run(**kw)
+            with switches(su_hard_warm=(0.0, 0.0)):
+                a = run(**kw)
+            with switches(su_hard_warm=(1.0, 1e-3)):
+                b = run(**kw)
             print(f"{name}: {a:.2f} -> {b:.2f} interior-point iterations per su-solve with su_hard_warm = (1, 1e-3)", flush=True)
-finally:
-    lib.orc_set_su_warm(1e-3, 1e-3, 30); lib.orc_set_su_hard_warm(1.0, 1e-3)

@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tol", type=float, default=1e-5, help="steps whose raw |du| exceeds this are listed (and dumped with --dump-dir)")
     ap.add_argument("--only", type=int, default=-1, help="run this scene only (the random draws of the others are still made)")
-    ap.add_argument("--cold", action="store_true", help="cold oracle (orc_set_su_warm(0,0,0)): the independent checker; default = the warm oracle that mirrors the kernel's first start rules")
+    ap.add_argument("--cold", action="store_true", help="cold oracle (su_warm = 0, 0): the independent checker; default = the warm oracle that mirrors the kernel's first start rules")
     ap.add_argument("--lmz-central", type=float, default=0.0, help="interior-point LamMuZ mode on both sides (central-path point at this barrier parameter, e.g. 1e-3)")
     ap.add_argument("--dump", default="", help="record ALL the oracle's su-problems (same state as the GPU's: re-synchronised every step) for tools/su_replay.py")
     ap.add_argument("--dump-dir", default="", help="record the su-problems and both answers of the listed steps only (one .bin + .npz per step)")

@@ -39,10 +39,7 @@ def _path(name):
 def record(name, n_obs, T, steps, moving):
     from rda_planner_amd import scenarios as sc
     from rda_planner_amd.mpc import MPC
-    from oracle.oracle_backend import oracle_backend
-    l = _lib()
-    l.orc_set_su_warm(0.0, 0.0, 0); l.orc_set_threads(16)
-    l.orc_set_su_dump(_path(name).encode())
+    from oracle.oracle_backend import oracle_backend, su_dump, switches
     car_t = sc.rectangle_robot(dynamics="acker")
     length = max(40.0, 0.4 * steps + 12.0)
     path = sc.line_path([4, 25, 0], [4 + length, 25, 0], 0.1)
@@ -51,11 +48,11 @@ def record(name, n_obs, T, steps, moving):
     kw = dict(receding=T, iter_num=4, max_edge_num=4, max_obs_num=n_obs, ro1=200, obstacle_order=True, iter_threshold=0.2)
     cpu = MPC(car_t, [p.copy() for p in path], sample_time=0.1, time_print=False, _backend=oracle_backend, **kw)
     state = path[0].copy().reshape(3, 1)
-    for i in range(steps):
-        cur = obstacles if not moving else [o._replace(vertex=o.vertex + o.velocity * (0.1 * i)) for o in obstacles]
-        uc, ic = cpu.control(state.copy(), 4.0, list(cur))
-        state = sc.kinematic_step(state, uc, car_t, 0.1)
-    l.orc_set_su_dump(b"")
+    with switches(su_warm=(0.0, 0.0), su_warm_cap=0, threads=16), su_dump(_path(name)):
+        for i in range(steps):
+            cur = obstacles if not moving else [o._replace(vertex=o.vertex + o.velocity * (0.1 * i)) for o in obstacles]
+            uc, ic = cpu.control(state.copy(), 4.0, list(cur))
+            state = sc.kinematic_step(state, uc, car_t, 0.1)
     print("recorded", _path(name), os.path.getsize(_path(name)), "bytes")
 
 
@@ -111,11 +108,11 @@ def main():
         print(f"{len(its)} su-problems: {its.mean():.2f} interior-point iterations per cold solve (median {np.median(its):.0f}, max {its.max()}); by ADMM iteration " +
               " ".join(f"{np.mean([i for i, p in zip(its, probs) if p['it'] == k]):.1f}" for k in range(4)))
     elif a.cmd == "trace":
-        l.orc_set_su_trace(1)
-        for i in a.problems:
-            print(f"problem {i} (ADMM iteration {probs[i]['it']})", file=sys.stderr)
-            st, it = solve(l, probs[i])[:2]
-            print(f"  status {st}, {it} iterations", file=sys.stderr)
+        with oracle_backend.switches(su_trace=1):
+            for i in a.problems:
+                print(f"problem {i} (ADMM iteration {probs[i]['it']})", file=sys.stderr)
+                st, it = solve(l, probs[i])[:2]
+                print(f"  status {st}, {it} iterations", file=sys.stderr)
     else:
         sols, step = {}, -1
         for pr in probs:
