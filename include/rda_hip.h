@@ -553,8 +553,12 @@ int  rda_fleet_upload_worlds(rda_fleet *f, const int32_t *counts /*B*/, int we, 
  * it stands, from states [B][3], by ONE launch of lidar::k_raycast_fleet (the member in the grid, a thread per beam) and one wait.  Beam i of a member:
  * angle_min + i * (angle_max - angle_min) / (n_beams - 1), the last one exactly angle_max, a single beam angle_min; direction (cos, sin) of heading +
  * angle.  Circle: f = o - c, b = d.f, disc = b*b - (f.f - r*r), a hit needs disc >= 0 and t = -b - sqrt(disc) >= 0 (an origin inside a circle does not see
- * it).  Polygon edge p -> q: e = q - p, w = p - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, s = (w.x d.y - w.y d.x) / den, a hit needs
- * |den| > 1e-12, t >= 0, 0 <= s <= 1.  range = clip(min(range_max, all hits), range_min, range_max); an empty world: range_max everywhere.  `ranges` is
+ * it).  Polygon edge p -> q: e = q - p, w = p - o, u = q - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, the vertices' sides of the beam's line
+ * side_p = w.x d.y - w.y d.x and side_q = u.x d.y - u.y d.x; a hit needs (side_p >= 0) != (side_q >= 0), den^2 > 1e-20 e.e (|d| = 1), t >= 0.  A vertex's
+ * side depends on that vertex alone, so the edges that meet in it agree on it: a closed polygon has no gap at a vertex, at a repeated one, or between two
+ * 1e-13 m apart.  Only an edge that lies along the beam's line to within 1e-10 rad is skipped: there sides, den and t are rounding noise, and a beam that
+ * meets an edge that flat is a silhouette beam anyway (checked against exact rational ray casting, tests/ray_exact.py).  range = clip(min(range_max, all
+ * hits), range_min, range_max); an empty world: range_max everywhere.  `ranges` is
  * the concatenation of the members' scans (n_beams[i] = 0: no scan).  RDA_ERR_UNSUPPORTED: more than 4096 beams; RDA_ERR_ARG: no uploaded world, a negative
  * beam count, a missing array. */
 int  rda_fleet_raycast(rda_fleet *f, const int32_t *n_beams /*B*/, const double *angle_min, const double *angle_max,

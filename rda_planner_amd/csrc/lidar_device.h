@@ -534,8 +534,17 @@ __global__ __launch_bounds__(NT) void k_scan_fleet_at(const Args *as, const doub
 //   beam i     angle_min + i * (angle_max - angle_min) / (n_beams - 1), the last one exactly angle_max, a single beam angle_min (scan_body's rule =
 //              np.linspace); direction (cos, sin) of heading + angle, origin the pose's x, y
 //   circle     f = o - c, b = d.f, disc = b * b - (f.f - r * r); a hit: disc >= 0 and t = -b - sqrt(disc) >= 0 (an origin inside the circle: no hit)
-//   edge p->q  e = q - p, w = p - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, s = (w.x d.y - w.y d.x) / den;
-//              a hit: |den| > 1e-12, t >= 0, 0 <= s <= 1; only the polygon's nvert vertices
+//   edge p->q  e = q - p, w = p - o, u = q - o, den = d.x e.y - d.y e.x, t = (w.x e.y - w.y e.x) / den, and the side of the beam's line that each vertex
+//              lies on: side_p = w.x d.y - w.y d.x, side_q = u.x d.y - u.y d.x; a hit: (side_p >= 0) != (side_q >= 0), den^2 > 1e-20 e.e (|d| = 1),
+//              t >= 0; only the polygon's nvert vertices.  A vertex's side is computed from that vertex alone, so the two edges that meet in it read
+//              the SAME number and exactly one of them is crossed where the boundary passes through the line: no gap at a vertex, at a repeated
+//              vertex (a zero-length edge has den = 0) or between two vertices 1e-13 m apart.  (Before, each edge tested 0 <= s <= 1 with its own
+//              quotient s = side_p / den and skipped |den| <= 1e-12: both tests could fail at a shared vertex, and the beam went through the corner
+//              of a closed polygon.)  The guard on den is relative: it skips an edge that lies ALONG the beam's line, |sin| of the angle between them
+//              <= 1e-10.  There both sides and den are rounding noise (4e-16 relative) and t would be noise over noise - a return at 0 m on a beam
+//              that points away from the edge.  The edge's neighbours, which cross the line at an angle, carry its end points.  A beam that meets an
+//              edge that flat is a silhouette beam (its range moves by metres under 1e-9 rad), so the guard opens no gap for a conditioned beam.
+//              Held to exact rational ray casting by tests/ray_exact.py on the grid of tests/ray_grid.py
 //   range      clip(min(range_max, all hits), range_min, range_max); an empty world: range_max everywhere
 // One launch for the fleet: blockIdx.y = the member, a thread per beam, RAY_NT beams (one wave) per workgroup, so B * ceil(n_beams / 64) workgroups - 1088
 // at 64 members x 1080 beams.  The member's world goes through LDS in tiles of RAY_TILE obstacles; every lane reads the same obstacle at the same time
@@ -566,9 +575,12 @@ __device__ __forceinline__ void ray_edge(const double ox, const double oy, const
 #pragma clang fp contract(off)
     const double ex = qx - px, ey = qy - py;
     const double den = dx * ey - dy * ex;
-    const double wx = px - ox, wy = py - oy;
-    const double t = (wx * ey - wy * ex) / den, s = (wx * dy - wy * dx) / den;
-    if (fabs(den) > 1e-12 && t >= 0 && s >= 0 && s <= 1 && t < rng) rng = t;
+    const double wx = px - ox, wy = py - oy, ux = qx - ox, uy = qy - oy;
+    const double side_p = wx * dy - wy * dx, side_q = ux * dy - uy * dx;
+    if ((side_p >= 0) != (side_q >= 0) && den * den > 1e-20 * (ex * ex + ey * ey)) {
+        const double t = (wx * ey - wy * ex) / den;
+        if (t >= 0 && t < rng) rng = t;
+    }
 }
 // the member's direction of beam b (live beams only) and its world, tile by tile through tg / tk / tv: the part the two ray casters share.  Every barrier is
 // reached by the whole workgroup; returns min(range_max, world hits)
@@ -631,7 +643,7 @@ __global__ __launch_bounds__(RAY_NT) void k_raycast_fleet(const Ray *rs, const d
 // pair per peer and workgroup, never per beam.  A member does not see itself; a peer that contains the origin is hit from the inside like any polygon.  The
 // minimum over world and peers is exact, its order free.  The lane that owns a peer also drops it when it is out of reach - centre farther from the origin
 // than range_max plus the footprint's radius, so no hit of it can lower the minimum: the result is the same bit for bit, and a beam pays the edge tests
-// (two double divisions each, what this kernel's time is made of) only for the members its lidar can reach, not for all B - 1.
+// (two side values each and a double division where the edge is crossed) only for the members its lidar can reach, not for all B - 1.
 // LDS: the peer tile reuses the world tile's block (the world has been read when the first peer tile is written), so the launch costs what k_raycast_fleet's
 // does, 32 * 8 * 2 doubles + 2 * 32 ints = 4352 B per workgroup of one wave: 32 resident workgroups (the wave limit of a CU) hold 136 KiB of its 160 KiB, the
 // LDS does not bound the occupancy.  Workgroups: B * ceil(n_beams / 64), 1088 at 64 members x 1080 beams, as many as the blind caster; each tests

@@ -140,16 +140,25 @@ class World:
                 t = np.where(t >= 0, t, np.inf)
                 rng = np.minimum(rng, t)
             else:                                                            # ray / polygon edges
+                # An edge is crossed when its two vertices lie on different sides of the beam's line, `side >= 0` against `side < 0`.  A vertex's side
+                # value depends on that vertex alone, so the two edges that meet in it read the same number: the boundary has no gap at a vertex,
+                # at a repeated one or between two that nearly coincide (a zero-length edge is never crossed, a short one like any other).
+                # The one exception is an edge along the beam itself, see `cut` below.
                 V = ob.vertex
                 for k in range(V.shape[1]):
                     p, q = V[:, k], V[:, (k + 1) % V.shape[1]]
                     e = q - p
                     den = d[:, 0] * e[1] - d[:, 1] * e[0]
                     w = p - o
+                    u = q - o
+                    side_p = w[0] * d[:, 1] - w[1] * d[:, 0]
+                    side_q = u[0] * d[:, 1] - u[1] * d[:, 0]
                     with np.errstate(divide="ignore", invalid="ignore"):
                         t = (w[0] * e[1] - w[1] * e[0]) / den               # along the beam
-                        s_ = (w[0] * d[:, 1] - w[1] * d[:, 0]) / den         # along the edge
-                    ok = (np.abs(den) > 1e-12) & (t >= 0) & (s_ >= 0) & (s_ <= 1)
+                    # an edge that lies along the beam's line to within rounding (|sin| of the angle between them <= 1e-10) is skipped: there
+                    # both sides and den are rounding noise and t would be noise over noise.  A conditioned beam meets no edge that flat
+                    cut = den * den > 1e-20 * (e[0] * e[0] + e[1] * e[1])                  # (|d| = 1)
+                    ok = ((side_p >= 0) != (side_q >= 0)) & cut & (t >= 0)
                     rng = np.minimum(rng, np.where(ok, t, np.inf))
         rng = np.clip(rng, ld.range_min, ld.range_max)
         return {"ranges": rng, "angle_min": ld.angle_min, "angle_max": ld.angle_max, "range_min": ld.range_min,
