@@ -6,7 +6,7 @@ classes on top of oracle/librda_oracle.so instead of the HIP library.
 import contextlib
 import ctypes as C
 
-from rda_planner_amd._capi import CApi, CODES, declare
+from rda_planner_amd._capi import CApi, CODES, declare, set_fields
 from rda_planner_amd.rda_solver import _Backend
 from . import oracle_lib
 
@@ -76,22 +76,7 @@ def switches(**changes):
     orc = api()
     before = Switches()
     orc.get_switches(C.byref(before))
-    now = Switches.from_buffer_copy(before)
-    known = {f[0] for f in Switches._fields_}
-    for k, v in changes.items():
-        if k not in known:
-            raise TypeError(f"switches: unknown orc_switches field {k!r} (oracle/rda_oracle.h lists them)")
-        cur = getattr(now, k)
-        if hasattr(cur, "__len__"):
-            v = list(v)
-            if len(v) != len(cur):
-                raise ValueError(f"switches: {k} takes {len(cur)} values, got {len(v)}")
-            for i, x in enumerate(v):
-                cur[i] = x
-        else:
-            if isinstance(cur, int) and int(v) != v:
-                raise ValueError(f"switches: {k} is an integer switch, got {v!r}")
-            setattr(now, k, v)
+    now = set_fields(Switches.from_buffer_copy(before), changes, ("switches", "orc_switches", "oracle/rda_oracle.h"))
     orc.put_switches(C.byref(now))
     try:
         yield orc

@@ -183,12 +183,26 @@ def declare(lib, prefix, table, codes=CODES):
             fn.restype, fn.argtypes = signature(proto, codes)
 
 
+def _pointer(a, buffer_type, pointer_type):
+    """the data of the array `a` as a typed pointer that carries the array along as `_arr`, so the array lives as long as the pointer does.  Taken
+    through the array's buffer: half the time of `a.ctypes.data_as`, a dozen times per tick, which pays for the calls the shared step protocol of
+    rda_solver.py adds (profiles/solver_py_refactor.txt)"""
+    if a is None:
+        return None
+    try:
+        p = C.cast(buffer_type.from_buffer(a), pointer_type)
+    except (TypeError, ValueError):                                    # a read-only or non-contiguous array exports no such buffer
+        return a.ctypes.data_as(pointer_type)                          # (sets `_arr` itself)
+    p._arr = a
+    return p
+
+
 def dptr(a):
-    return a.ctypes.data_as(c_double_p) if a is not None else None
+    return _pointer(a, C.c_double * 0, c_double_p)
 
 
 def iptr(a):
-    return a.ctypes.data_as(c_int_p) if a is not None else None
+    return _pointer(a, C.c_int * 0, c_int_p)
 
 
 def f64(a, shape=None):
@@ -196,6 +210,36 @@ def f64(a, shape=None):
     if shape is not None:
         a = a.reshape(shape)
     return a
+
+
+def c_arg(v):
+    """a value as the C argument it is passed as: a float64 / int32 array as its pointer, a flag as 0 / 1, anything else (None, int, float, the
+    handle, the `Info` array) as it is"""
+    if isinstance(v, np.ndarray):
+        return {"float64": dptr, "int32": iptr}[v.dtype.name](v)       # an array of any other type is no argument of the library: KeyError
+    return int(v) if isinstance(v, (bool, np.bool_)) else v
+
+
+def set_fields(record, changes, who):
+    """`changes` (field=value) written into the ctypes `record`; an array field takes exactly as many values as it has entries, an int field an
+    integral value.  who = (the caller the messages start with, the C struct, the header that lists its fields)"""
+    caller, struct, header = who
+    known = {f[0] for f in record._fields_}
+    for k, v in changes.items():
+        if k not in known:
+            raise TypeError(f"{caller}: unknown {struct} field {k!r} ({header} lists them)")
+        cur = getattr(record, k)
+        if hasattr(cur, "__len__"):
+            v = list(v)
+            if len(v) != len(cur):
+                raise ValueError(f"{caller}: {k} takes {len(cur)} values, got {len(v)}")
+            for i, x in enumerate(v):
+                cur[i] = x
+        else:
+            if isinstance(cur, int) and int(v) != v:
+                raise ValueError(f"{caller}: {k} is an integer switch, got {v!r}")
+            setattr(record, k, v)
+    return record
 
 
 class CApi:

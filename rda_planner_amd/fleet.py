@@ -15,8 +15,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from ._capi import Info, dptr, iptr, f64
+from ._capi import Info, c_arg, dptr, iptr, f64
 from .mpc import scan_split_arg
+from .rda_solver import RDA_solver, scene_arrays, step_epilogue
 
 SENSOR_FIELDS = ("number", "angle_min", "angle_max", "range_min", "range_max")
 WORLD_EMAX = 8              # RDA_EMAX of include/rda_hip.h: the most vertices a world polygon may have
@@ -35,14 +36,6 @@ ROLLOUT_ARGS = {
     "fleet_rollout_lidar_peers":   _LIDAR + " peer_log",
     "fleet_rollout_lidar_tracked": _LIDAR + " peer_log see_peers track_gate track_window",
 }
-
-
-def c_arg(v):
-    """a value as the C argument it is passed as: a float64 / int32 array as its pointer, a flag as 0 / 1, anything else (None, int, float, the
-    handle, the `Info` array) as it is"""
-    if isinstance(v, np.ndarray):
-        return {"float64": dptr, "int32": iptr}[v.dtype.name](v)       # an array of any other type is no argument of the library: KeyError
-    return int(v) if isinstance(v, (bool, np.bool_)) else v
 
 
 def rollout_args(entry, values):
@@ -261,17 +254,8 @@ class Fleet:
             self._ref[i] = np.hstack(ref_list)[0:3, :]
             self._speed[i] = speed
             begun.append((cur_ref_path, ref_list))
-            if stage is not None:
-                continue
-            obstacles = obstacle_lists[i]
-            scene = None
-            if not m.rda_obstacle and m.device_obstacles and m.rda.has_scene:
-                scene = m.rda.flatten_scene(obstacles)
-            if scene is not None:
-                m.rda.upload_scene(scene, np.asarray(m.state, float)[0:2], m.obstacle_order)
-            else:
-                rda_obs = obstacles if m.rda_obstacle else m.convert_rda_obstacle(obstacles, m.state, m.obstacle_order)
-                m.rda.upload_obstacles(rda_obs)
+            if stage is None:
+                m._stage_obstacles(obstacle_lists[i])
         if stage is not None:
             stage(states_array([m.state for m in self.members], len(self.members)))
         self._call("fleet_step", self._handle, dptr(self._in_s), dptr(self._in_u), dptr(self._ref), dptr(self._speed),
@@ -279,12 +263,14 @@ class Fleet:
         out = []
         for i, m in enumerate(self.members):
             cur_ref_path, ref_list = begun[i]
-            if self._info[i].su_status and m.rda.time_print:
-                print("No update of state and control vector")        # reference rda_solver.py:699
-            info = m.rda.pack_info(ref_list, self._out_s[i].copy(), self._info[i], start)
-            out.append(m._end(cur_ref_path, self._out_u[i].copy(), info))
-            self._note_plan(i, self._out_s[i], info["arrive"])
+            out.append(m._end(cur_ref_path, *self._member_done(i, start, ref_list)))
+            self._note_plan(i, self._out_s[i], out[-1][1]["arrive"])
         return out
+
+    def _member_done(self, i, start, ref_list):
+        """member i's (u, info) out of the fleet's output blocks: the epilogue of a step of its own solver, without a timing printout"""
+        rda = self.members[i].rda
+        return step_epilogue(rda.time_print, rda.pack_info, self._info[i], start, self._out_u[i].copy(), self._out_s[i].copy(), ref_list)
 
     def _stage_all(self, obstacle_lists, st):
         """all members' raw scenes flattened in ONE pass over the obstacle objects and staged by one library call
@@ -309,9 +295,8 @@ class Fleet:
         scene = self.members[0].rda.flatten_scene(every)
         if scene is None or scene[0] != len(every):
             return None
-        _, kind, nvert, geom, vel = scene
         counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, len(self.members))
-        return counts, np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32), f64(geom), f64(vel)
+        return (counts, *scene_arrays(scene))
 
     def _check_peers(self, kwargs, plan=False):
         """what peers=True / peers="plan" needs of the library and of every member, checked before any library call"""
@@ -456,7 +441,6 @@ class Fleet:
         """every member's WORLD - the true obstacles its simulated lidar sees (`raycast`, `rollout(lidar=)`), apart from the obstacles the planner
         stages - resident on the device (rda_fleet_upload_worlds).  `obstacle_lists[i]`: the objects `control` takes (circles and polygons of up to 8
         vertices, with their velocities); an empty list is an empty world.  A new upload replaces the old worlds."""
-        from .rda_solver import RDA_solver
         if not self._has("has_fleet_rollout_lidar"):
             raise RuntimeError("the loaded solver library has no world entry points (rda_fleet_upload_worlds)")
         B = len(self.members)
@@ -471,10 +455,8 @@ class Fleet:
         scene = RDA_solver._flatten_scene_numpy(SimpleNamespace(max_edge_num=we), every)
         if scene is None or scene[0] != len(every):
             raise ValueError("Fleet.upload_worlds: an obstacle cannot be expressed as a circle or a polygon with a velocity")
-        _, kind, nvert, geom, vel = scene
         counts = np.fromiter((len(ol) for ol in obstacle_lists), np.int32, B)
-        kind, nvert = np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32)
-        self._call("fleet_upload_worlds", self._handle, iptr(counts), int(we), iptr(kind), iptr(nvert), dptr(f64(geom)), dptr(f64(vel)))
+        self._call("fleet_upload_worlds", self._handle, iptr(counts), int(we), *map(c_arg, scene_arrays(scene)))
 
     def raycast(self, states, sensors):
         """every member's lidar scan of its resident world (`upload_worlds`) from `states[i]`, ray-cast on the device by one launch
@@ -747,8 +729,7 @@ class Fleet:
         st, speed, cur, piece0 = np.zeros((B, 3)), np.zeros(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
         resident = True
         for i, m in enumerate(self.members):
-            state = states[i]
-            m.state = state[0:3] if np.shape(state)[0] > 3 else state
+            m._take_state(states[i])
             pieces = self._gear_pieces(m)
             piece0[i] = m.curve_index if m.enable_reverse else 0
             if piece0[i] >= len(pieces):
@@ -797,11 +778,8 @@ class Fleet:
                    dptr(nom_u), dptr(self._out_u), dptr(self._out_s), self._info, dptr(self._ref), iptr(mi), dptr(eh))
         out = []
         for i, m in enumerate(self.members):
-            if self._info[i].su_status and m.rda.time_print:
-                print("No update of state and control vector")        # reference rda_solver.py:699
             ref_own = self._ref[i].copy()
-            ref_list = [ref_own[:, j:j + 1] for j in range(T + 1)]
-            info = m.rda.pack_info(ref_list, self._out_s[i].copy(), self._info[i], start)
-            out.append(m._tracked_done(pieces[i], self._out_u[i].copy(), info, int(mi[i]), float(eh[i])))
+            u, info = self._member_done(i, start, [ref_own[:, j:j + 1] for j in range(T + 1)])
+            out.append(m._tracked_done(pieces[i], u, info, int(mi[i]), float(eh[i])))
             self._note_plan(i, self._out_s[i], info["arrive"])
         return out

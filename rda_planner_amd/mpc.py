@@ -68,18 +68,12 @@ class MPC:
         if self._tracks(kwargs):
             return self._control_tracked(state, ref_speed, obstacle_list, **kwargs)
         cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
-        scene = None
-        if not self.rda_obstacle and self.device_obstacles and self.rda.has_scene:
-            scene = self.rda.flatten_scene(obstacle_list)
+        scene, rda_obs_list = self._obstacle_form(obstacle_list)
         if scene is not None:
             u_opt_array, info = self.rda.iterative_solve_scene(
                 state_pre_array, self.cur_vel_array, ref_traj_list, speed, scene,
                 np.asarray(state, float)[0:2], self.obstacle_order, **kwargs)
         else:
-            if not self.rda_obstacle:
-                rda_obs_list = self.convert_rda_obstacle(obstacle_list, self.state, self.obstacle_order)
-            else:
-                rda_obs_list = obstacle_list
             u_opt_array, info = self.rda.iterative_solve(
                 state_pre_array, self.cur_vel_array, ref_traj_list, speed, rda_obs_list, **kwargs)
         return self._end(cur_ref_path, u_opt_array, info)
@@ -88,26 +82,34 @@ class MPC:
     def _tracks(self, kwargs):
         return self.device_track and self.rda.has_track and set(kwargs) <= {"threshold", "ind_range"}
 
+    def _take_state(self, state):
+        """`state` (a fourth row, the gear of a reverse path, is cut off) becomes the robot's state"""
+        self.state = state[0:3] if np.shape(state)[0] > 3 else state
+
     def _piece(self, state):
-        if np.shape(state)[0] > 3:
-            state = state[0:3]
-        self.state = state
+        self._take_state(state)
         if self.enable_reverse:
             cur_ref_path = self.curve_list[self.curve_index]
             return cur_ref_path, cur_ref_path[0][-1, 0]
         return self.ref_path, 1
 
-    def _stage_obstacles(self, obstacle_list, in_tick=False):
-        """obstacles into the solver's slots without solving: raw scene through the device pipeline, else host staging.
-        in_tick: a tick is open (`tracked_begin`), the scene goes behind the first su-problem without waiting."""
+    def _obstacle_form(self, obstacle_list):
+        """the form the obstacles reach the solver in: (flattened raw scene, None) for the device pipeline, else (None, the host's half-spaces)"""
         scene = None
         if not self.rda_obstacle and self.device_obstacles and self.rda.has_scene:
             scene = self.rda.flatten_scene(obstacle_list)
         if scene is not None:
+            return scene, None
+        return None, obstacle_list if self.rda_obstacle else self.convert_rda_obstacle(obstacle_list, self.state, self.obstacle_order)
+
+    def _stage_obstacles(self, obstacle_list, in_tick=False):
+        """obstacles into the solver's slots without solving: raw scene through the device pipeline, else host staging.
+        in_tick: a tick is open (`tracked_begin`), the scene goes behind the first su-problem without waiting."""
+        scene, rda_obs = self._obstacle_form(obstacle_list)
+        if scene is not None:
             upload = self.rda.upload_scene_async if in_tick else self.rda.upload_scene
             upload(scene, np.asarray(self.state, float)[0:2], self.obstacle_order)
         else:
-            rda_obs = obstacle_list if self.rda_obstacle else self.convert_rda_obstacle(obstacle_list, self.state, self.obstacle_order)
             self.rda.upload_obstacles(rda_obs)
 
     def _sync_path(self, cur_ref_path):
@@ -143,25 +145,29 @@ class MPC:
         self._dev_u = None if info["arrive"] else self.cur_vel_array
         return out
 
-    def _control_tracked(self, state, ref_speed, obstacle_list, **kwargs):
+    def _tracked_tick(self, state, ref_speed, stage, **kwargs):
+        """one tick with pre_process on the device; `stage(in_tick)` puts this tick's obstacles into the solver's slots"""
         cur_ref_path, gear_flag = self._piece(state)
         self._sync_path(cur_ref_path)
+        head = (self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u())
         if self.rda.has_pipeline:
             # pre_process and the first su-problem do not read this tick's obstacles (the first su-problem works with the
-            # products of the previous step, reference quirk Q4): they run on the device while the obstacle objects are
-            # flattened and staged here.  Same kernels, same order of dependent work, identical results.
-            self.rda.tracked_begin(self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
+            # products of the previous step, reference quirk Q4): they run on the device while the obstacles are
+            # staged here.  Same kernels, same order of dependent work, identical results.
+            self.rda.tracked_begin(*head, **kwargs)
             try:
-                self._stage_obstacles(obstacle_list, in_tick=True)
+                stage(True)
             except BaseException:
                 self.rda.tracked_finish(discard=True)           # close the tick before reporting the caller's error
                 raise
-            u_opt_array, info, min_index, end_heading = self.rda.tracked_finish()
+            out = self.rda.tracked_finish()
         else:
-            self._stage_obstacles(obstacle_list)
-            u_opt_array, info, min_index, end_heading = self.rda.iterative_solve_tracked(
-                self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
-        return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
+            stage(False)
+            out = self.rda.iterative_solve_tracked(*head, **kwargs)
+        return self._tracked_done(cur_ref_path, *out)
+
+    def _control_tracked(self, state, ref_speed, obstacle_list, **kwargs):
+        return self._tracked_tick(state, ref_speed, lambda in_tick: self._stage_obstacles(obstacle_list, in_tick), **kwargs)
 
     # ---- extension: the lidar front end on the device (rda_upload_scan) ---------------------------------------------------
     def _control_scan(self, state, ref_speed, obstacle_list, scan, eps, min_samples, split=0.0, **kwargs):
@@ -175,41 +181,20 @@ class MPC:
         if self.rda_obstacle or not self.rda.has_scan:
             raise RuntimeError("MPC.control(scan=...) needs the device-side lidar front end (rda_upload_scan); there is no host fallback")
         sk = {"split": split} if split else {}                # (an unsplit call is the call it always was)
+        stage = lambda in_tick=False: self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)      # noqa: E731
         if self._tracks(kwargs):
-            cur_ref_path, gear_flag = self._piece(state)
-            self._sync_path(cur_ref_path)
-            if self.rda.has_pipeline:
-                self.rda.tracked_begin(self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
-                try:
-                    self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
-                except BaseException:
-                    self.rda.tracked_finish(discard=True)           # close the tick before reporting the error
-                    raise
-                u_opt_array, info, min_index, end_heading = self.rda.tracked_finish()
-            else:
-                self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
-                u_opt_array, info, min_index, end_heading = self.rda.iterative_solve_tracked(
-                    self.state, gear_flag * ref_speed, self.cur_index, self._nominal_u(), **kwargs)
-            return self._tracked_done(cur_ref_path, u_opt_array, info, min_index, end_heading)
+            return self._tracked_tick(state, ref_speed, stage, **kwargs)
         cur_ref_path, speed, state_pre_array, ref_traj_list = self._begin(state, ref_speed, **kwargs)
-        self.rda.upload_scan(self.state, scan, eps, min_samples, self.obstacle_order, **sk)
+        stage()
         u_opt_array, info = self.rda.iterative_solve_staged(state_pre_array, self.cur_vel_array, ref_traj_list, speed)
         return self._end(cur_ref_path, u_opt_array, info)
 
     def _begin(self, state, ref_speed, **kwargs):
         """first half of `control` (mpc.py:127-147): the piece of the path in force, the signed reference speed, the
         nominal roll-out and the reference samples.  Shared with `Fleet.control`."""
-        if np.shape(state)[0] > 3:
-            state = state[0:3]
-        self.state = state
-        if self.enable_reverse:
-            cur_ref_path = self.curve_list[self.curve_index]
-            gear_flag = cur_ref_path[0][-1, 0]
-        else:
-            cur_ref_path = self.ref_path
-            gear_flag = 1
+        cur_ref_path, gear_flag = self._piece(state)
         state_pre_array, ref_traj_list, self.cur_index = self.pre_process(
-            state, cur_ref_path, self.cur_index, ref_speed, **kwargs)
+            self.state, cur_ref_path, self.cur_index, ref_speed, **kwargs)
         return cur_ref_path, gear_flag * ref_speed, state_pre_array, ref_traj_list
 
     def _end(self, cur_ref_path, u_opt_array, info):

@@ -16,7 +16,7 @@ from math import inf  # noqa: F401  (kept for API parity with the reference modu
 
 import numpy as np
 
-from ._capi import Cfg, Info, Opts, DYNAMICS, dptr, iptr, f64
+from ._capi import Cfg, Info, Opts, DYNAMICS, dptr, iptr, f64, set_fields
 import ctypes as C
 
 CONE_CODE = {"Rpositive": 0, "norm2": 1}
@@ -106,27 +106,40 @@ def hip_options(**changes):
     o = Opts()
     hip_api().opts_init(C.byref(o))
     _apply_env(o)
-    known = {f[0] for f in Opts._fields_}
-    for k, v in changes.items():
-        if k not in known:
-            raise TypeError(f"hip_options: unknown rda_opts field {k!r} (include/rda_hip.h lists them)")
-        cur = getattr(o, k)
-        if hasattr(cur, "__len__"):
-            v = list(v)
-            if len(v) != len(cur):
-                raise ValueError(f"hip_options: {k} takes {len(cur)} values, got {len(v)}")
-            for i, x in enumerate(v):
-                cur[i] = x
-        else:
-            if isinstance(cur, int) and int(v) != v:
-                raise ValueError(f"hip_options: {k} is an integer switch, got {v!r}")
-            setattr(o, k, v)
-    return o
+    return set_fields(o, changes, ("hip_options", "rda_opts", "include/rda_hip.h"))
 
 
 def _hip_backend(cfg, G, h, opts=None):
     from ._lib import hip_api          # raises loudly when librda_hip.so / the GPU is missing
     return _Backend(hip_api(), cfg, G, h, opts if opts is not None else hip_options())
+
+
+def scene_arrays(scene):
+    """(kind, nvert, geom, vel) of a flattened scene (`flatten_scene`) in the types the library reads"""
+    _, kind, nvert, geom, vel = scene
+    return np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(nvert, np.int32), f64(geom), f64(vel)
+
+
+def step_epilogue(time_print, pack_info, info_c, start, out_u, out_s, ref_states, report=None):
+    """what follows every step's library call: the reference's line when the su-problem made no update, the timing printout (`report`, a solver's
+    `_timing_report`; a `Fleet` has none for its members), then `pack_info`'s dict.  Returns (out_u, info)."""
+    if info_c.su_status and time_print:
+        print("No update of state and control vector")            # reference :699
+    if report is not None:
+        report(info_c, start)
+    return out_u, pack_info(ref_states, out_s, info_c, start)
+
+
+class _StepOut:
+    """the buffers a step hands its results back in: `u` (2, T), `s` (3, T+1), `info`; a tracked step also `ref` (3, T+1), the reference the
+    device sampled, `mi` the new path index and `eh` the heading of the last waypoint after the tick (quirk Q12)"""
+
+    def __init__(self, T, tracked=False):
+        self.u, self.s, self.info = np.zeros((2, T)), np.zeros((3, T + 1)), Info()
+        self.args = (dptr(self.u), dptr(self.s), C.byref(self.info))             # the tail of the library's argument list
+        if tracked:
+            self.ref, self.mi, self.eh = np.zeros((3, T + 1)), np.zeros(1, np.int32), np.zeros(1)
+            self.args += (None, dptr(self.ref), iptr(self.mi), dptr(self.eh))
 
 
 class RDA_solver:
@@ -203,6 +216,13 @@ class RDA_solver:
         self._be = make(cfg, G, h, opts) if make is _hip_backend else make(cfg, G, h)   # test backends select the mode themselves
         self._R = G.shape[0]
         self.pipeline = True        # MPC overlaps its per-tick obstacle staging with the first su-problem (set False to serialise)
+
+    def _call(self, name, *args):
+        """the library's `name(handle, *args)`; a negative return code raises what the binding makes of it"""
+        rc = getattr(self._be.api, name)(self._be.handle, *args)
+        if rc < 0:
+            raise self._be.api.failed(name, rc)
+        return rc
 
     # ---- runtime tunables (reference :426-434, :1055-1056) ------------------------------
     def assign_adjust_parameter(self, **kwargs):
@@ -337,45 +357,53 @@ class RDA_solver:
     def iterative_solve_scene(self, nom_s, nom_u, ref_states, ref_speed, scene, robot_xy, order, **kwargs):
         """`iterative_solve` fed with a flattened raw scene (see `flatten_scene`): conversion to half-spaces, the
         constant-velocity prediction, distance ordering, truncation and padding all run on the device."""
-        T = self.T
         start = time.time()
-        n, kind, nvert, geom, vel = scene
+        nominal = self._nominal_args(nom_s, nom_u, ref_states, ref_speed)
+        return self._step("step_scene", start, ref_states, *nominal, *self._scene_args(scene, robot_xy, order))
+
+    # ---- the step protocol: every step form is a head of its own, then `_step` or its two halves ---------------------------------------
+    def _nominal_args(self, nom_s, nom_u, ref_states, ref_speed):
+        """the host's nominal trajectory, reference and speed as the C arguments a step starts with (a pointer of `dptr` keeps its array alive)"""
+        T = self.T
         ref = f64(np.hstack(ref_states)[0:3, :], (3, T + 1))
-        nom_s = f64(nom_s, (3, T + 1))
-        nom_u = f64(nom_u, (2, T))
+        return dptr(f64(nom_s, (3, T + 1))), dptr(f64(nom_u, (2, T))), dptr(ref), float(ref_speed)
+
+    def _scene_args(self, scene, robot_xy, order):
+        """a flattened scene, the robot's position and the ordering flag as the run of C arguments that rda_step_scene, rda_upload_scene and
+        rda_upload_scene_async share"""
+        kind, nvert, geom, vel = scene_arrays(scene)
         rob = f64(np.asarray(robot_xy, float).ravel()[0:2])
-        out_u = np.zeros((2, T))
-        out_s = np.zeros((3, T + 1))
-        info_c = Info()
-        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
-        geom = f64(geom); vel = f64(vel)
+        return int(scene[0]), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob), int(bool(order))
+
+    def _step(self, name, start, ref_states, *args):
+        """one step through the library's `name`: timing on, the call with the output buffers behind `args`, the epilogue"""
+        out = _StepOut(self.T)
         self._timing_begin()
-        rc = self._be.api.step_scene(self._be.handle, dptr(nom_s), dptr(nom_u), dptr(ref), float(ref_speed), int(n),
-                                     iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob), int(bool(order)),
-                                     dptr(out_u), dptr(out_s), C.byref(info_c))
-        if rc < 0:
-            raise self._be.api.failed("step_scene", rc)
-        if info_c.su_status and self.time_print:
-            print("No update of state and control vector")        # reference :699
-        self._timing_report(info_c, start)
-        return out_u, self.pack_info(ref_states, out_s, info_c, start)
+        self._call(name, *args, *out.args)
+        return self._step_done(out.info, start, out.u, out.s, ref_states)
+
+    def _step_done(self, info_c, start, out_u, out_s, ref_states):
+        """the epilogue of all five step forms (`step_epilogue` with this solver's timing report)"""
+        return step_epilogue(self.time_print, self.pack_info, info_c, start, out_u, out_s, ref_states, self._timing_report)
+
+    def _tracked_head(self, state, ref_speed, cur_index, nom_u, threshold, ind_range):
+        """what rda_step_tracked and rda_tracked_begin take from the caller"""
+        st = f64(np.asarray(state, float).ravel()[0:3])
+        un = f64(nom_u, (2, self.T)) if nom_u is not None else None
+        return dptr(st), float(ref_speed), int(cur_index), float(threshold), int(ind_range), dptr(un)
+
+    def _tracked_done(self, out, start):
+        """the epilogue of a tracked step: (u, info, new cur_index, heading of the last waypoint after the tick - quirk Q12)"""
+        ref_states = [out.ref[:, i:i + 1] for i in range(self.T + 1)]
+        return (*self._step_done(out.info, start, out.u, out.s, ref_states), int(out.mi[0]), float(out.eh[0]))
 
     # ---- staging only (the solve is then issued by a Fleet for all of its members at once) -----------
     def upload_scene(self, scene, robot_xy, order):
-        n, kind, nvert, geom, vel = scene
-        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
-        geom = f64(geom); vel = f64(vel)
-        rob = f64(np.asarray(robot_xy, float).ravel()[0:2])
-        rc = self._be.api.upload_scene(self._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob),
-                                       int(bool(order)), None)
-        if rc < 0:
-            raise self._be.api.failed("upload_scene", rc)
+        self._call("upload_scene", *self._scene_args(scene, robot_xy, order), None)
 
     def upload_obstacles(self, obstacle_list):
         n_obs, A, b, cone, per_t = self._stage(obstacle_list)
-        rc = self._be.api.upload_obstacles(self._be.handle, n_obs, dptr(A), dptr(b), iptr(cone), per_t)
-        if rc < 0:
-            raise self._be.api.failed("upload_obstacles", rc)
+        self._call("upload_obstacles", n_obs, dptr(A), dptr(b), iptr(cone), per_t)
 
     def pack_info(self, ref_states, out_s, info_c, start):
         """the `info` dict of the reference (:603-608) plus the solver counters"""
@@ -400,9 +428,7 @@ class RDA_solver:
     def upload_path(self, ref_path):
         """the polyline of MPC.ref_path (list of (>=3)x1 waypoints) for `iterative_solve_tracked`"""
         P = np.ascontiguousarray(np.hstack(ref_path)[0:3, :].T, dtype=float)
-        rc = self._be.api.upload_path(self._be.handle, int(P.shape[0]), dptr(P))
-        if rc < 0:
-            raise self._be.api.failed("upload_path", rc)
+        self._call("upload_path", int(P.shape[0]), dptr(P))
 
     def upload_path_pieces(self, pieces):
         """all gear pieces of a path (MPC.curve_list: lists of 4x1 waypoints whose last row is the gear; a list of 3x1 waypoints is a piece with
@@ -410,30 +436,18 @@ class RDA_solver:
         lens = np.fromiter((len(p) for p in pieces), np.int32, len(pieces))
         gear = np.array([float(p[0][3, 0]) if np.shape(p[0])[0] > 3 else 1.0 for p in pieces])
         P = np.ascontiguousarray(np.hstack([w for p in pieces for w in p])[0:3, :].T, dtype=float)
-        rc = self._be.api.upload_path_pieces(self._be.handle, len(pieces), iptr(lens), dptr(gear), dptr(P))
-        if rc < 0:
-            raise self._be.api.failed("upload_path_pieces", rc)
+        self._call("upload_path_pieces", len(pieces), iptr(lens), dptr(gear), dptr(P))
 
     def iterative_solve_tracked(self, state, ref_speed, cur_index, nom_u=None, threshold=0.1, ind_range=10):
         """`iterative_solve` with MPC.pre_process (nominal roll-out, closest waypoint, arc-length reference sampling)
         done on the device from the robot state; obstacles are whatever is staged (upload_scene / upload_obstacles).
         Returns (u, info, new cur_index, heading of the last waypoint after the tick - quirk Q12)."""
-        T = self.T
         start = time.time()
-        st = f64(np.asarray(state, float).ravel()[0:3])
-        out_u, out_s, ref = np.zeros((2, T)), np.zeros((3, T + 1)), np.zeros((3, T + 1))
-        info_c, mi, eh = Info(), np.zeros(1, np.int32), np.zeros(1)
-        un = f64(nom_u, (2, T)) if nom_u is not None else None
+        head = self._tracked_head(state, ref_speed, cur_index, nom_u, threshold, ind_range)
+        out = _StepOut(self.T, tracked=True)
         self._timing_begin()
-        rc = self._be.api.step_tracked(self._be.handle, dptr(st), float(ref_speed), int(cur_index), float(threshold), int(ind_range),
-                                       dptr(un), dptr(out_u), dptr(out_s), C.byref(info_c), None, dptr(ref), iptr(mi), dptr(eh))
-        if rc < 0:
-            raise self._be.api.failed("step_tracked", rc)
-        if info_c.su_status and self.time_print:
-            print("No update of state and control vector")        # reference :699
-        self._timing_report(info_c, start)
-        ref_states = [ref[:, i:i + 1] for i in range(T + 1)]
-        return out_u, self.pack_info(ref_states, out_s, info_c, start), int(mi[0]), float(eh[0])
+        self._call("step_tracked", *head, *out.args)
+        return self._tracked_done(out, start)
 
     # ---- the tracked tick in two halves: the first su-problem runs while the caller stages this tick's obstacles ------
     @property
@@ -444,32 +458,19 @@ class RDA_solver:
         """queue pre_process + the first su-problem of the step (neither reads the obstacles of this tick: the first
         su-problem uses the products of the previous step, reference quirk Q4) and return without waiting"""
         self._tick_start = time.time()
-        st = f64(np.asarray(state, float).ravel()[0:3])
-        un = f64(nom_u, (2, self.T)) if nom_u is not None else None
+        head = self._tracked_head(state, ref_speed, cur_index, nom_u, threshold, ind_range)
         self._timing_begin()
-        rc = self._be.api.tracked_begin(self._be.handle, dptr(st), float(ref_speed), int(cur_index), float(threshold),
-                                        int(ind_range), dptr(un))
-        if rc < 0:
-            raise self._be.api.failed("tracked_begin", rc)
+        self._call("tracked_begin", *head)
 
     def upload_scene_async(self, scene, robot_xy, order):
         """`upload_scene` inside an open tick: staged on the stream behind the first su-problem, no wait"""
-        n, kind, nvert, geom, vel = scene
-        kind = np.ascontiguousarray(kind, np.int32); nvert = np.ascontiguousarray(nvert, np.int32)
-        geom = f64(geom); vel = f64(vel)
-        rob = f64(np.asarray(robot_xy, float).ravel()[0:2])
-        rc = self._be.api.upload_scene_async(self._be.handle, int(n), iptr(kind), iptr(nvert), dptr(geom), dptr(vel), dptr(rob),
-                                             int(bool(order)))
-        if rc < 0:
-            raise self._be.api.failed("upload_scene_async", rc)
+        self._call("upload_scene_async", *self._scene_args(scene, robot_xy, order))
 
     def scene_resort(self, robot_xy):
         """re-rank the RESIDENT raw scene by distance to `robot_xy` and rebuild the obstacle slots on the device (the reference's per-tick
         `obstacle_list.sort(key=rda_obs_distance)`, mpc.py:205-206) - no host-to-device copy; asynchronous like `upload_scene_async`"""
         rob = f64(np.asarray(robot_xy, float).ravel()[0:2])
-        rc = self._be.api.scene_resort(self._be.handle, dptr(rob))
-        if rc < 0:
-            raise self._be.api.failed("scene_resort", rc)
+        self._call("scene_resort", dptr(rob))
 
     # ---- lidar front end on the device (rda_scan_boxes / rda_upload_scan; host specification: lidar.py) ---------------------
     @property
@@ -479,7 +480,7 @@ class RDA_solver:
     def _scan_args(self, state, scan_data, eps, min_samples):
         ranges = f64(np.asarray(scan_data["ranges"], float).ravel())
         st = f64(np.asarray(state, float).ravel()[0:3])
-        head = (self._be.handle, int(ranges.size), dptr(ranges), float(scan_data["angle_min"]), float(scan_data["angle_max"]),
+        head = (int(ranges.size), dptr(ranges), float(scan_data["angle_min"]), float(scan_data["angle_max"]),
                 float(scan_data["range_max"]), dptr(st), float(eps), int(min_samples))
         return head, (ranges, st)                        # (the arrays stay referenced until the call has returned)
 
@@ -491,7 +492,7 @@ class RDA_solver:
             return
         if not getattr(self._be.api, "has_scan_split", False):
             raise RuntimeError("the loaded solver library cannot split scan clusters (rda_set_scan_split, rda_fleet_set_scan_split)")
-        rc = self._be.api.set_scan_split(self._be.handle, tol)
+        rc = self._be.api.set_scan_split(self._be.handle, tol)          # (not `_call`: a refused tolerance is the caller's ValueError)
         if rc < 0:
             raise ValueError("scan split: tol must be finite and greater than 0") if rc == -1 else self._be.api.failed("set_scan_split", rc)
         self._scan_split = tol
@@ -504,9 +505,7 @@ class RDA_solver:
         head, keep = self._scan_args(state, scan_data, eps, min_samples)
         cap = max(1, keep[0].size)
         boxes, n, labels = np.zeros((cap, 4, 2)), np.zeros(1, np.int32), np.zeros(cap, np.int32)
-        rc = self._be.api.scan_boxes(*head, iptr(n), dptr(boxes), cap, iptr(labels))
-        if rc < 0:
-            raise self._be.api.failed("scan_boxes", rc)
+        self._call("scan_boxes", *head, iptr(n), dptr(boxes), cap, iptr(labels))
         return (boxes[:n[0]], labels[:keep[0].size]) if with_labels else boxes[:n[0]]
 
     def upload_scan(self, state, scan_data, eps=2.0, min_samples=6, order=True, split=0.0):
@@ -515,46 +514,34 @@ class RDA_solver:
         self.set_scan_split(split)
         head, keep = self._scan_args(state, scan_data, eps, min_samples)
         n = np.zeros(1, np.int32)
-        rc = self._be.api.upload_scan(*head, int(bool(order)), iptr(n))
-        if rc < 0:
-            raise self._be.api.failed("upload_scan", rc)
+        self._call("upload_scan", *head, int(bool(order)), iptr(n))
         return int(n[0])
 
     def iterative_solve_staged(self, nom_s, nom_u, ref_states, ref_speed):
         """`iterative_solve` on the obstacles that are staged on the device already (`upload_scan`), with the host's nominal
         trajectory and reference: the device-resident step (a trace of one step: rda_upload_trace / rda_enqueue_step, which
         tests/test_gpu_parity.py pins to rda_step)"""
-        T, lib, h = self.T, self._be.api.lib, self._be.handle
+        lib, h = self._be.api.lib, self._be.handle
         start = time.time()
-        ref = f64(np.hstack(ref_states)[0:3, :], (3, T + 1))
-        nom_s, nom_u, speed = f64(nom_s, (3, T + 1)), f64(nom_u, (2, T)), f64([float(ref_speed)])
-        out_u, out_s, info_c = np.zeros((2, T)), np.zeros((3, T + 1)), Info()
+        nom_s, nom_u, ref, _ = self._nominal_args(nom_s, nom_u, ref_states, ref_speed)
+        speed, out = f64([float(ref_speed)]), _StepOut(self.T)
         self._timing_begin()
-        rc = lib.rda_upload_trace(h, 1, dptr(nom_s), dptr(nom_u), dptr(ref), dptr(speed))
+        # (not `_call`: whichever of the four calls refuses, the error is this form's own)
+        rc = lib.rda_upload_trace(h, 1, nom_s, nom_u, ref, dptr(speed))
         rc = rc or lib.rda_enqueue_step(h, 0) or lib.rda_sync(h)
-        rc = rc or lib.rda_fetch_result(h, 0, dptr(out_u), dptr(out_s), C.byref(info_c))
+        rc = rc or lib.rda_fetch_result(h, 0, *out.args)
         if rc < 0:
             raise RuntimeError(f"{self._be.api.prefix}: the step on the staged obstacles failed with code {rc}")
-        if info_c.su_status and self.time_print:
-            print("No update of state and control vector")        # reference :699
-        self._timing_report(info_c, start)
-        return out_u, self.pack_info(ref_states, out_s, info_c, start)
+        return self._step_done(out.info, start, out.u, out.s, ref_states)
 
     def tracked_finish(self, discard=False):
         """queue the rest of the ADMM loop, wait, return what `iterative_solve_tracked` returns"""
-        T = self.T
-        out_u, out_s, ref = np.zeros((2, T)), np.zeros((3, T + 1)), np.zeros((3, T + 1))
-        info_c, mi, eh = Info(), np.zeros(1, np.int32), np.zeros(1)
-        rc = self._be.api.tracked_finish(self._be.handle, dptr(out_u), dptr(out_s), C.byref(info_c), None, dptr(ref), iptr(mi), dptr(eh))
-        if discard:
+        out = _StepOut(self.T, tracked=True)
+        if discard:                                      # the tick is closed for a caller that is reporting an error of its own: whatever the library says
+            self._be.api.tracked_finish(self._be.handle, *out.args)
             return None
-        if rc < 0:
-            raise self._be.api.failed("tracked_finish", rc)
-        if info_c.su_status and self.time_print:
-            print("No update of state and control vector")        # reference :699
-        self._timing_report(info_c, self._tick_start)
-        ref_states = [ref[:, i:i + 1] for i in range(T + 1)]
-        return out_u, self.pack_info(ref_states, out_s, info_c, self._tick_start), int(mi[0]), float(eh[0])
+        self._call("tracked_finish", *out.args)
+        return self._tracked_done(out, self._tick_start)
 
     # ---- the reference's timing printout (rda_solver.py:587-601, `time_print`) ---------------------------------------------
     def _timing_begin(self):
@@ -589,25 +576,10 @@ class RDA_solver:
 
     # ---- one MPC step (reference iterative_solve :573-610) --------------------------------
     def iterative_solve(self, nom_s, nom_u, ref_states, ref_speed, obstacle_list, **kwargs):
-        T = self.T
         start = time.time()
-        ref = f64(np.hstack(ref_states)[0:3, :], (3, T + 1))
-        nom_s = f64(nom_s, (3, T + 1))
-        nom_u = f64(nom_u, (2, T))
+        nominal = self._nominal_args(nom_s, nom_u, ref_states, ref_speed)
         n_obs, A, b, cone, per_t = self._stage(obstacle_list)
-        out_u = np.zeros((2, T))
-        out_s = np.zeros((3, T + 1))
-        info_c = Info()
-        self._timing_begin()
-        rc = self._be.api.step(self._be.handle, dptr(nom_s), dptr(nom_u), dptr(ref), float(ref_speed),
-                               n_obs, dptr(A), dptr(b), iptr(cone), per_t, dptr(out_u), dptr(out_s),
-                               C.byref(info_c))
-        if rc < 0:
-            raise self._be.api.failed("step", rc)
-        if info_c.su_status and self.time_print:
-            print("No update of state and control vector")        # reference :699
-        self._timing_report(info_c, start)
-        return out_u, self.pack_info(ref_states, out_s, info_c, start)
+        return self._step("step", start, ref_states, *nominal, n_obs, dptr(A), dptr(b), iptr(cone), per_t)
 
     # ---- state access for tests -----------------------------------------------------------
     def get_state(self):

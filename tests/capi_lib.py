@@ -54,6 +54,83 @@ class Binding:
         raise AssertionError(f"library touched: {name}")
 
 
+# the arguments (the handle is argument 0) through which an entry hands results back
+OUTPUTS = {"step": (10, 11, 12), "step_scene": (12, 13, 14), "step_tracked": (7, 8, 9, 11, 12, 13), "tracked_finish": (1, 2, 3, 5, 6, 7),
+           "fetch_result": (2, 3, 4), "scan_boxes": (9, 10, 12), "upload_scan": (10,), "timing_launches": (2, 4)}
+TIMING = ("timing_reset", "timing_launches")
+
+
+def fixed_output(position, shape, dtype=float):
+    """what `Recorder` writes through the output pointer at argument `position`: an int32 array is all 2, a double array counts up in eighths from
+    `position`"""
+    import numpy as np
+    if np.dtype(dtype) == np.int32:
+        return np.full(shape, 2, np.int32)
+    return (position + np.arange(int(np.prod(shape))) / 8.0).reshape(shape)
+
+
+class Recorder:
+    """stands for a backend of `RDA_solver` (`_backend=lambda cfg, G, h: recorder`): it answers the capability flags it is given, records every call
+    of the binding as (entry name, arguments after the handle) with scalars as they are, numpy copies of the input arrays and "out" for an output,
+    writes `fixed_output` and `info` through the output pointers, and returns `fail[entry]` (default 0).  Calls through `.lib.rda_<entry>` are
+    recorded alike; the timing entries exist only with `timing`, and rda_last_nonconvex answers `nonconvex`."""
+    INFO = dict(resi_dual=0.125, resi_pri=0.0625, iters=2, su_status=0, su_ipm_iters=7, lmz_fail=0)
+
+    def __init__(self, fail=None, timing=True, nonconvex=0, info=None, **flags):
+        from rda_planner_amd._capi import CApi
+        self.calls, self.fail, self.timing, self.nonconvex, self.prefix = [], dict(fail or {}), timing, nonconvex, "rda"
+        self.info = dict(self.INFO, **(info or {}))
+        self.api, self.handle, self.lib = self, C.c_void_p(77), _RecorderLib(self)
+        self.failed = types.MethodType(CApi.failed, self)                 # the product's text
+        self.__dict__.update(flags)
+
+    def __getattr__(self, name):
+        if name.startswith(("has_", "_")):
+            raise AttributeError(name)
+        return lambda *args: self.entry(name, *args)
+
+    def names(self):
+        return [name for name, _ in self.calls]
+
+    def entry(self, name, *args):
+        import numpy as np
+        assert args and args[0] is self.handle, f"{name}: the handle comes first"
+        seen = []
+        for pos, a in enumerate(args[1:], 1):
+            out = pos in OUTPUTS.get(name, ())
+            if a is None or isinstance(a, (int, float)):
+                assert not isinstance(a, bool), f"{name}: argument {pos} is a bool"
+                seen.append(a)
+            elif isinstance(a, C._Pointer) and hasattr(a, "_arr"):        # dptr / iptr of a numpy array
+                arr = a._arr
+                assert arr.flags.c_contiguous and arr.dtype == {C.c_double: np.float64, C.c_int: np.int32}[a._type_], f"{name}: argument {pos}"
+                if out:
+                    arr[...] = fixed_output(pos, arr.shape, arr.dtype)
+                seen.append("out" if out else arr.copy())
+            elif isinstance(a, C._Pointer):                               # a cast pointer to a C int that is an output
+                assert out, f"{name}: argument {pos}"
+                a[0] = 2
+                seen.append("out")
+            else:                                                         # byref(Info)
+                assert out, f"{name}: argument {pos}"
+                for k, v in self.info.items():
+                    setattr(a._obj, k, v)
+                seen.append("out")
+        self.calls.append((name, seen))
+        return self.nonconvex if name == "last_nonconvex" else self.fail.get(name, 0)
+
+
+class _RecorderLib:
+    def __init__(self, rec):
+        self._rec = rec
+
+    def __getattr__(self, name):
+        entry = name[4:]
+        if not name.startswith("rda_") or (entry in TIMING and not self._rec.timing):
+            raise AttributeError(name)
+        return lambda *args: self._rec.entry(entry, *args)
+
+
 def member(tracks=True, reverse=False, **attrs):
     """stands for an `MPC` member: what every refusal of `Fleet.rollout` reads, and `attrs`; using its solver is an error"""
     def no_solver(*a, **k):
