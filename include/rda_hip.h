@@ -244,7 +244,8 @@ int  rda_timing_read(rda_handle *h, int which, double *total_ms, int *launches);
  * device flag, so launches queued behind it return at once; a caller that knows the executed ADMM iterations (rda_info.iters)
  * separates the two populations with this (bench.py: roofline per EXECUTED launch) */
 int  rda_timing_launches(rda_handle *h, int which, double *ms_out, int cap, int *launches);
-/* the form of the LamMuZ launch the library uses for this handle's shape and staged obstacles (kernel names joined by '+') */
+/* the LamMuZ launches of an ADMM iteration as the library plans them for this handle's shape and staged obstacles (kernel names joined by '+').
+ * The string lives in the handle: valid until the next call on the same handle ("" for a null handle) */
 const char *rda_lammuz_kernel(rda_handle *h);
 
 /* ---- caller-side nominal roll-out + reference sampling on the device ------------------------------
@@ -345,7 +346,8 @@ int  rda_fleet_size(rda_fleet *f);
 /* the fleet counterpart of rda_lammuz_kernel: the LamMuZ launches the next fleet tick issues per ADMM iteration as the members stand now
  * (kernel names joined by '+').  Enumeration fleets: "k_lammuz_fleet_rows_fast+k_lammuz_fleet_enum+k_lmz_finalize_fleet", "k_lammuz_fleet_rows" or
  * "k_lammuz_fleet+k_lmz_finalize_fleet".  Interior-point fleets: "k_lammuz_ip_fleet" when every member runs the row-parallel form,
- * "k_lammuz_cp_fleet_small|large+k_lmz_finalize_fleet" when none does, all three names when both forms have members. */
+ * "k_lammuz_cp_fleet_small|large+k_lmz_finalize_fleet" when none does, all three names when both forms have members.
+ * The string lives in the fleet: valid until the next call on the same fleet ("" for a null fleet). */
 const char *rda_fleet_lammuz_kernel(rda_fleet *f);
 /* one synchronous MPC step of every member with the obstacles each member has staged (rda_upload_obstacles /
  * rda_upload_scene): per-ego arrays of rda_step, concatenated ego-major */

@@ -28,6 +28,7 @@
 #include <dlfcn.h>
 #include "../../include/rda_hip.h"
 #include "host_buf.h"
+#include "lmz_plan.h"
 #include "lammuz_device.h"
 #include "lammuz_cp_device.h"
 #include "lammuz_ip_device.h"
@@ -72,6 +73,7 @@ constexpr int NCOEF = 9;      // per-(slot, stage) term arrays: NGATH of them tr
 constexpr int NGATH = 3;      // ax, ay, cb: what the su hinge reads per term
 constexpr int NBS = su::NBS;  // doubles per (stage, GS-slot block) partial; one more 8-byte word per block carries the near mask
 constexpr int GS = su::GS;    // slots per block partial = rows of a packed LamMuZ workgroup (2 waves x 4 rows of 16 lanes)
+static_assert(GS == lmzplan::GS, "lmz_plan.h sizes its grids for another block partial");
 struct Dev;
 __host__ __device__ inline double *coef_arr(const Dev &d, int r, int k);
 
@@ -107,8 +109,8 @@ struct Dev {
     double su_warm_wfl, su_warm_mu0;   // interior-point start of the su-problems of ADMM iterations >= 1 ("0,0" = cold)
     double su_hard_wfl, su_hard_mu0;   // ... of the steps that follow an UNCONVERGED step (rda_opts::su_hard_warm; mu0 = 0: the rule is off)
     int lmz_mode;            // 0: support enumeration + tie-breaks T1-T3 (default), 1: interior point, central path at lmz_mu (norm2 robots: always)
-    int ip_rows;             // mode 1 and the row-parallel kernel takes this shape (rda_handle::ip_rows): with staged obstacles the launch form is k_lammuz_ip, else the
-                             // per-thread kernel + k_lmz_finalize (lammuz_plan; the fleet kernels decide per member from this record)
+    int ip_rows;             // mode 1 and the row-parallel kernel takes this shape (and rda_opts::lmz_ip_rows): with staged obstacles the launch form is k_lammuz_ip, else the
+                             // per-thread kernel + k_lmz_finalize (lmzplan::member_ip_rows: the host's plans and the fleet kernels decide per member from this record)
     double lmz_mu;           // barrier parameter of the returned central-path point (mode 1)
     int centre;              // tie-break T1: central separating normal in the slack regime
     int obstacle_num;        // 0 or N
@@ -484,7 +486,6 @@ __device__ __forceinline__ void unit_of(const Dev &d, int w, int &t, int &nl) { 
 // blocks are numbered group-major (u = j T + t) and cut into 8 equal contiguous ranges, one per XCD - a group's stages land on one
 // XCD (two for the few groups a cut goes through), neighbouring groups (which share the 128-byte lines of the [T][N] arrays) too.
 //   b = 8 q + x ;  u = x per + q ,  per = ceil(T J / 8) ;  j = u / T ,  t = u % T
-__host__ __device__ inline int packed_grid(int T, int J) { return 8 * ((T * J + 7) / 8); }
 __device__ __forceinline__ void block_of(const Dev &d, int b, int &t, int &j)
 {
     const int T = d.c.T, W = T * d.J, per = (W + 7) / 8, x = b & 7, q = b >> 3, u = x * per + q;
@@ -1109,7 +1110,7 @@ __global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_enum(Dev d, int it) {
 // sub-problem per wave, the per-thread interior-point kernel), after the no-obstacle launch (quirk Q9 edits terms) and whenever the
 // host rewrites terms (rda_set_state, rda_reset, rda_shard_config).  One GS-slot block per GS threads, 256 / GS blocks per workgroup;
 // it < 0: no tail.
-constexpr int FPB = 256 / GS;          // block partials per workgroup of k_lmz_finalize
+constexpr int FPB = lmzplan::FPB;         // block partials per workgroup of k_lmz_finalize
 __device__ __forceinline__ void finalize_body(const Dev &d, const int block, const int nblocks, const int it, const Fin &fin)
 {
 #pragma clang fp contract(on)
@@ -1582,7 +1583,7 @@ struct rda_handle {
     Dev d;
     rda_opts opts;                        // sanitised (opts_sanitised): what the host code reads its switches from
     size_t su_lds = 0, su_trk_lds = 0; unsigned long long trk_seq = 0;
-    int ip_rows = 0;         // interior-point mode runs the row-parallel kernel (shape allows it and rda_opts::lmz_ip_rows)
+    char lmz_name[lmzplan::NAME_CAP] = "";      // what rda_lammuz_kernel last returned
     int admm_it = 0;         // host-driven ADMM pieces (rda_admm_*): the iteration rda_admm_su was last called with
     int stepped = 0;         // a step has been queued on this handle (sharded handles: rda_reset / rda_set_state are refused from then on)
     double scan_split = 0.0; // rda_set_scan_split: lidar::Args::split_tol of this handle's scans (0: one box per cluster)
@@ -1739,9 +1740,8 @@ extern "C" int rda_create_opts(const rda_cfg *cfg, const rda_opts *opts, const d
     rc |= m.pin(&H->stage.A, N * (T + 1) * E * 2); rc |= m.pin(&H->stage.b, N * (T + 1) * E); rc |= m.pin(&H->stage.cone, N);
     rc |= m.pin(&H->step.h, step_doubles(T)); rc |= m.pin(&H->res.blk.h, res_doubles(T));
     H->step.n = step_doubles(T); H->res.blk.n = res_doubles(T); H->res.T = T;      // (the two pairs filled in by hand: the allocations keep their order)
-    H->ip_rows = o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated);
-    d.ip_rows = (d.lmz_mode && H->ip_rows) ? 1 : 0;
-    if (H->d.lmz_mode && H->ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
+    d.ip_rows = (d.lmz_mode && o.lmz_ip_rows && rip::fits(cfg->E, cfg->R, cfg->E >= 3, cfg->robot_norm2, cfg->accelerated)) ? 1 : 0;
+    if (d.ip_rows && o.lmz_ip_warm) { rc |= m.dev(&d.ipw, N * T * 80); rc |= m.dev(&d.ipf, N * T); }
     if (rc) return RDA_ERR_HIP;
     { const int hard = 99; HIPCHK(hipMemcpy(&d.ctrl->su_last, &hard, sizeof(int), hipMemcpyHostToDevice)); }     // no su history yet
     HIPCHK(hipMemcpy(d.G, G, 2 * R * sizeof(double), hipMemcpyHostToDevice));
@@ -2139,59 +2139,40 @@ struct TimedLaunch {
     TimedLaunch &operator=(const TimedLaunch &) = delete;
 };
 
-// K1 launch of ADMM iteration `it`.  Packed rows when the shape allows: a small grid is ONE launch that also forms the block
-// partials; a dense grid is the common-path kernel + the work-list kernel, with k_lmz_finalize (partials) behind them.  One sub-problem per wave (big
-// shapes, the no-obstacle case of quirk Q9) and the per-thread interior-point kernel likewise end with k_lmz_finalize.
-constexpr int LMZ_NTH = 64 * GS / 4;             // threads of a packed workgroup (2 waves)
-// The LamMuZ launch form of a handle's shape and staged obstacles, with its grids: decided here only.  launch_lammuz executes the plan,
-// rda_lammuz_kernel names it (bench.py labels its per-launch times with the name).
-enum LmzForm { LMZ_CP_SMALL, LMZ_CP_LARGE, LMZ_IP, LMZ_ROWS_SPLIT, LMZ_ROWS_DENSE, LMZ_ROWS, LMZ_WAVE };
-struct LmzPlan { LmzForm form; int nb, ne; };        // workgroups of the form's first launch; of the work-list launch (split form)
-static LmzPlan lammuz_plan(const rda_handle *H, const Dev &d)
+// K1 launches of ADMM iteration `it`.  Which kernels, in which order and on what grid is lmzplan::solo's decision (lmz_plan.h) from the handle's shape
+// and staged obstacles: launch_lammuz executes that plan, rda_lammuz_kernel names it (bench.py labels its per-launch times with the name).
+static lmzplan::Member lmz_member(const rda_handle *H, const Dev &d)
 {
-    const int units = d.c.T * GS * d.J;          // rows of the grid (a stage is padded to whole GS-slot blocks)
-    if (d.lmz_mode && !(H->ip_rows && d.obstacle_num)) {
-        const int nth = d.Nlive * d.c.T;
-        return { (d.c.E <= 4 && d.c.R <= 4) ? LMZ_CP_SMALL : LMZ_CP_LARGE, d.obstacle_num ? (nth + 63) / 64 : (d.c.T + 63) / 64, 0 };
-    }
-    if (d.lmz_mode) return { LMZ_IP, packed_grid(d.c.T, d.J), 0 };
-    if (d.rows && d.obstacle_num) {
-        const int nb = packed_grid(d.c.T, d.J), cus = (units / GS * LMZ_NTH + 255) / 256;      // launch indices (XCD-aware order, a few fillers); CUs the grid asks for at one wave per SIMD
-        // Grid size (in compute units at one wave per SIMD) from which the dense forms are used.  Scenes with per-stage obstacle data
-        // (moving obstacles) lose the remembered support of more rows per launch, so the work list of the split form is longer and the
-        // single launch stays ahead up to a larger grid: measured cross-over ~280 CUs for static scenes (N = 300, T = 20: 35.7 vs 38.7 us),
-        // ~560 for moving ones (T = 30: N = 200 40.9 vs 47.1 us for the single launch, N = 300 52.2 vs 50.1, N = 400 60.7 vs 51.1).
-        if (cus <= (d.nt > 1 ? H->opts.lmz_dense_from * 7 / 4 : H->opts.lmz_dense_from)) return { LMZ_ROWS, nb, 0 };
-        if (!H->opts.lmz_split) return { LMZ_ROWS_DENSE, nb, 0 };
-        int ne = units / 32; if (ne < 64) ne = 64; if (ne > 2048) ne = 2048;
-        return { LMZ_ROWS_SPLIT, nb, ne };
-    }
-    return { LMZ_WAVE, d.obstacle_num ? (units + 3) / 4 : 1, 0 };
+    return { d.c.T, d.Nlive, d.J, d.c.E, d.c.R, d.nt, d.obstacle_num, d.rows, d.lmz_mode, d.ip_rows, H->opts.lmz_dense_from, H->opts.lmz_split };
 }
 extern "C" const char *rda_lammuz_kernel(rda_handle *H)
 {
-    static const char *const names[] = { "k_lammuz_cp_small+k_lmz_finalize", "k_lammuz_cp_large+k_lmz_finalize", "k_lammuz_ip",
-                                         "k_lammuz_rows_fast+k_lammuz_enum+k_lmz_finalize", "k_lammuz_rows_dense", "k_lammuz_rows", "k_lammuz+k_lmz_finalize" };
-    return H ? names[lammuz_plan(H, H->d).form] : "";
+    if (!H) return "";
+    lmzplan::name(lmzplan::solo(lmz_member(H, H->d)), false, H->lmz_name, sizeof H->lmz_name);
+    return H->lmz_name;
 }
 static void launch_lammuz(rda_handle *H, const Dev &d, int it, const Fin &fin)
 {
     if (d.Nlive == 0) return;                    // a shard without obstacles (N < P)
-    const LmzPlan p = lammuz_plan(H, d);
-    switch (p.form) {
-        case LMZ_CP_SMALL: hipLaunchKernelGGL(k_lammuz_cp_small, dim3(p.nb), dim3(64), 0, H->stream, d); break;
-        case LMZ_CP_LARGE: hipLaunchKernelGGL(k_lammuz_cp_large, dim3(p.nb), dim3(64), 0, H->stream, d); break;
-        case LMZ_IP: hipLaunchKernelGGL(k_lammuz_ip, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;      // (the row-parallel interior-point kernel)
-        case LMZ_ROWS: hipLaunchKernelGGL(k_lammuz_rows, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;
-        case LMZ_ROWS_DENSE: hipLaunchKernelGGL(k_lammuz_rows_dense, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it, fin); return;
-        case LMZ_ROWS_SPLIT:
-            // dense grid: common path with three waves per SIMD, then the deferred rows one per wave (see lammuz_body_rows)
-            hipLaunchKernelGGL(k_lammuz_rows_fast, dim3(p.nb), dim3(LMZ_NTH), 0, H->stream, d, it);
-            hipLaunchKernelGGL(k_lammuz_enum, dim3(p.ne), dim3(LMZ_NTH), 0, H->stream, d, it);
-            break;
-        case LMZ_WAVE: hipLaunchKernelGGL(k_lammuz, dim3(p.nb), dim3(256), 0, H->stream, d, it); break;
+    const lmzplan::Plan p = lmzplan::solo(lmz_member(H, d));
+    for (int i = 0; i < p.n; ++i) {
+        const dim3 grid(p.l[i].grid), block(p.l[i].block);
+        // one case per kernel id: the kernel of that name (checked against the table that rda_lammuz_kernel reports from) with its argument list
+#define LMZ_SOLO(ID, KERNEL, ...) case lmzplan::ID: static_assert(lmzplan::same(lmzplan::NAMES[lmzplan::ID].solo, #KERNEL), #KERNEL); \
+                                  hipLaunchKernelGGL(KERNEL, grid, block, 0, H->stream, __VA_ARGS__); break;
+        switch (p.l[i].kernel) {
+            LMZ_SOLO(ROWS, k_lammuz_rows, d, it, fin)
+            LMZ_SOLO(ROWS_DENSE, k_lammuz_rows_dense, d, it, fin)
+            LMZ_SOLO(ROWS_FAST, k_lammuz_rows_fast, d, it)
+            LMZ_SOLO(ENUM, k_lammuz_enum, d, it)
+            LMZ_SOLO(WAVE, k_lammuz, d, it)
+            LMZ_SOLO(IP, k_lammuz_ip, d, it, fin)               // (the row-parallel interior-point kernel)
+            LMZ_SOLO(CP_SMALL, k_lammuz_cp_small, d)
+            LMZ_SOLO(CP_LARGE, k_lammuz_cp_large, d)
+            LMZ_SOLO(FINALIZE, k_lmz_finalize, d, it, fin)
+        }
+#undef LMZ_SOLO
     }
-    hipLaunchKernelGGL(k_lmz_finalize, dim3((d.c.T * d.J + FPB - 1) / FPB), dim3(256), 0, H->stream, d, it, fin);      // block partials and the tail of the forms that do not make them
 }
 
 // The ADMM loop of one MPC step (rda_solver.py:588-596) is queued without host synchronisation, in two parts.  The HEAD (the first su-problem,
@@ -3036,8 +3017,8 @@ template <int TT> __global__ __launch_bounds__(su::NT) void k_su_fleet(const Dev
     su_body<TT>(d, it, e.s + k * ns, e.u + k * nu, e.ref + k * ns, e.speed + k);
 }
 
-// Enumeration mode: a member without obstacles (Q9) or of a shape the packed body does not take runs the one-per-wave body on the first quarter
-// of the (packed-size) grid... kept simple: the fleet uses the packed kernel only when every member can (its forms agree bit for bit)
+// Enumeration mode: the fleet uses the packed kernels only when every member can - a member without obstacles (Q9) or of a shape the packed body does
+// not take puts the whole fleet on the one-per-wave kernel (lmzplan::fleet; the forms agree bit for bit).  Member d's result locations of step k:
 __device__ __forceinline__ Fin fleet_fin(const Dev &d, const EgoIO &e, int k)
 {
     const size_t ns = 3 * (d.c.T + 1), nu = 2 * d.c.T;
@@ -3053,11 +3034,11 @@ __global__ __launch_bounds__(64 * GS / 4, 2) void k_lammuz_fleet_rows(const Dev 
 #endif
 __global__ __launch_bounds__(64 * GS / 4, LMZ_FLEET_FAST_OCC) void k_lammuz_fleet_rows_fast(const Dev *devs, int it) { lammuz_body_rows<1>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
 __global__ __launch_bounds__(64 * GS / 4, 1) void k_lammuz_fleet_enum(const Dev *devs, int it) { lammuz_body_rows<2>(devs[blockIdx.y], blockIdx.x, gridDim.x, it, Fin{}); }
-// Interior-point mode: the launch form is chosen PER MEMBER by lammuz_plan's rule - the row-parallel kernel for a member whose shape it takes
-// (Dev::ip_rows) and that has staged obstacles, else the per-thread kernel (with its quirk-Q9 branch) + k_lmz_finalize_fleet.  The two kernels agree only to
-// ~4e-6, so a fleet-wide choice would make a member's result depend on its neighbours.  A kernel of one form returns at once for the members of the other; the
-// host launches only the forms some member needs (fleet_refresh_flags).
-__device__ __forceinline__ bool member_ip_rows(const Dev &d) { return d.ip_rows && d.obstacle_num; }
+// Interior-point mode: the launch form is chosen PER MEMBER by the rule of a solo handle (lmzplan::member_ip_rows) - the row-parallel kernel for a member whose
+// shape it takes (Dev::ip_rows) and that has staged obstacles, else the per-thread kernel (with its quirk-Q9 branch) + k_lmz_finalize_fleet.  The two kernels agree
+// only to ~4e-6, so a fleet-wide choice would make a member's result depend on its neighbours.  A kernel of one form returns at once for the members of the other; the
+// host launches only the forms some member needs (lmzplan::fleet).
+using lmzplan::member_ip_rows;
 #ifndef LMZ_FLEET_IP_OCC
 #define LMZ_FLEET_IP_OCC 1
 #endif
@@ -3089,9 +3070,7 @@ __global__ __launch_bounds__(su::NT) void k_finish_fleet(const Dev *devs, const 
 {
     const Dev &d = devs[blockIdx.x];
     const EgoIO e = io[blockIdx.x];
-    const size_t ns = 3 * (d.c.T + 1), nu = 2 * d.c.T;
-    const Fin f = { e.out_u + k * nu, e.out_s + k * ns, e.info + k, nullptr, 0, 0 };
-    finish_body(d, f);
+    finish_body(d, fleet_fin(d, e, k));
 }
 
 // The table sets a fleet makes on first use.  Each owns its allocations (g: zeroed, counted) beside the views into them - a device array with its pinned
@@ -3255,8 +3234,8 @@ struct rda_fleet : FleetSets {            // (owns its buffers, event and stream
     hbuf::Pair<double> in;                // step path, per ego: a step block (step_doubles)
     hbuf::Pair<double> out;               // per ego: u | s, the head of a result block (res_info doubles)
     hbuf::Pair<rda_info> info;
-    int T, iter_num, J, rows, lmz_split;
-    int ip, ip_rows, ip_cp;               // interior-point fleet; some member runs the row-parallel kernel | the per-thread kernel this tick (fleet_refresh_flags)
+    int T, iter_num, J;
+    char lmz_name[lmzplan::NAME_CAP] = "";    // what rda_fleet_lammuz_kernel last returned
     size_t su_lds;
     int rob_pending;                      // a copy out of res.rob.h may be queued
     double scan_split = 0.0;              // rda_fleet_set_scan_split: lidar::Args::split_tol of every member's scan in the fleet's calls
@@ -3398,30 +3377,18 @@ extern "C" int rda_fleet_create(rda_handle *const *egos, int B, rda_fleet **out)
     return RDA_OK;
 }
 
-// which form of the LamMuZ launch the members allow together
-static void fleet_refresh_flags(rda_fleet *F)
+// the LamMuZ launches of an ADMM iteration that the members allow together, as they stand now (their host records: what the next upload of F->devs
+// carries, and what the last one carried wherever a step is enqueued)
+static lmzplan::Plan fleet_lmz_plan(const rda_fleet *F)
 {
-    F->rows = 1;
-    F->lmz_split = 1;
-    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->opts.lmz_split) F->lmz_split = 0;
-    for (int i = 0; i < F->B; ++i) if (!F->egos[i]->d.rows || !F->egos[i]->d.obstacle_num) F->rows = 0;
-    // interior-point mode (all members or none, rda_fleet_create): every member's own form, lammuz_plan's rule
-    F->ip = F->egos[0]->d.lmz_mode != 0; F->ip_rows = 0; F->ip_cp = 0;
-    if (F->ip) for (int i = 0; i < F->B; ++i) { const Dev &d = F->egos[i]->d; if (d.ip_rows && d.obstacle_num) F->ip_rows = 1; else F->ip_cp = 1; }
+    return lmzplan::fleet(F->B, [F](int i) { return lmz_member(F->egos[i], F->egos[i]->d); });
 }
 // the LamMuZ launches of the next tick as the members stand now (kernel names joined by '+')
 extern "C" const char *rda_fleet_lammuz_kernel(rda_fleet *F)
 {
     if (!F) return "";
-    fleet_refresh_flags(F);
-    if (F->ip) {
-        const bool small = F->egos[0]->d.c.E <= 4 && F->egos[0]->d.c.R <= 4;
-        if (!F->ip_cp) return "k_lammuz_ip_fleet";
-        if (!F->ip_rows) return small ? "k_lammuz_cp_fleet_small+k_lmz_finalize_fleet" : "k_lammuz_cp_fleet_large+k_lmz_finalize_fleet";
-        return small ? "k_lammuz_ip_fleet+k_lammuz_cp_fleet_small+k_lmz_finalize_fleet" : "k_lammuz_ip_fleet+k_lammuz_cp_fleet_large+k_lmz_finalize_fleet";
-    }
-    if (F->rows && F->lmz_split) return "k_lammuz_fleet_rows_fast+k_lammuz_fleet_enum+k_lmz_finalize_fleet";
-    return F->rows ? "k_lammuz_fleet_rows" : "k_lammuz_fleet+k_lmz_finalize_fleet";
+    lmzplan::name(fleet_lmz_plan(F), true, F->lmz_name, sizeof F->lmz_name);
+    return F->lmz_name;
 }
 
 // members' records (obstacle count, staged pointers, weights may have changed since the last call) -> device; the fleet
@@ -3439,7 +3406,6 @@ static int fleet_refresh(rda_fleet *F)
         HIPCHK(hipEventRecord(F->ev, F->egos[i]->stream));
         HIPCHK(hipStreamWaitEvent(F->stream, F->ev, 0));
     }
-    fleet_refresh_flags(F);
     return fleet_table(F, F->devs, member_devs(F));
 }
 
@@ -3447,29 +3413,26 @@ static int fleet_enqueue(rda_fleet *F, const EgoIO *io, int k)
 {
     const int B = F->B;
     const Dev *devs = F->devs.d;
+    const lmzplan::Plan p = fleet_lmz_plan(F);
     for (int it = 0; it < F->iter_num; ++it) {          // iteration 0 resets every member's control block (su_body)
         RDA_SU_DISPATCH(F->T, hipLaunchKernelGGL(k_su_fleet<TT>, dim3(B), dim3(su::NT), F->su_lds, F->stream, devs, io, it, k));
-        // (The fleet's own selection of the LamMuZ form, not lammuz_plan: no dense threshold, and other clamps of the work-list grid -
-        // a shared plan would branch on its caller.)
-        constexpr int NTH = LMZ_NTH;
-        const int nbr = F->T * F->J, nfin = (nbr + FPB - 1) / FPB, nbp = packed_grid(F->T, F->J);       // one workgroup per (stage, GS-slot block), XCD-aware order
-        if (F->ip) {                                    // interior point: only the forms some member needs this tick (a kernel returns at once for the others' members)
-            if (F->ip_rows) hipLaunchKernelGGL(k_lammuz_ip_fleet, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, it);
-            if (F->ip_cp) {
-                const int ncp = (F->egos[0]->d.c.N * F->T + 63) / 64;      // a thread per (slot, stage); the Q9 branch needs T threads
-                if (F->egos[0]->d.c.E <= 4 && F->egos[0]->d.c.R <= 4) hipLaunchKernelGGL(k_lammuz_cp_fleet_small, dim3(ncp, B), dim3(64), 0, F->stream, devs);
-                else hipLaunchKernelGGL(k_lammuz_cp_fleet_large, dim3(ncp, B), dim3(64), 0, F->stream, devs);
-                hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
+        for (int i = 0; i < p.n; ++i) {
+            const dim3 grid(p.l[i].grid, B), block(p.l[i].block);
+            // one case per kernel id, as in launch_lammuz: the fleet kernel of that name with its argument list
+#define LMZ_FLEET(ID, KERNEL, ...) case lmzplan::ID: static_assert(lmzplan::same(lmzplan::NAMES[lmzplan::ID].fleet, #KERNEL), #KERNEL); \
+                                   hipLaunchKernelGGL(KERNEL, grid, block, 0, F->stream, __VA_ARGS__); break;
+            switch (p.l[i].kernel) {
+                LMZ_FLEET(ROWS, k_lammuz_fleet_rows, devs, io, it, k)
+                LMZ_FLEET(ROWS_FAST, k_lammuz_fleet_rows_fast, devs, it)
+                LMZ_FLEET(ENUM, k_lammuz_fleet_enum, devs, it)
+                LMZ_FLEET(WAVE, k_lammuz_fleet, devs, it)
+                LMZ_FLEET(IP, k_lammuz_ip_fleet, devs, it)
+                LMZ_FLEET(CP_SMALL, k_lammuz_cp_fleet_small, devs)
+                LMZ_FLEET(CP_LARGE, k_lammuz_cp_fleet_large, devs)
+                LMZ_FLEET(FINALIZE, k_lmz_finalize_fleet, devs, io, it, k)
+                case lmzplan::ROWS_DENSE: break;                       // (no fleet kernel: lmzplan::fleet plans none)
             }
-        } else if (F->rows && F->lmz_split) {
-            hipLaunchKernelGGL(k_lammuz_fleet_rows_fast, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, it);
-            int ne = nbr / 8; if (ne < 8) ne = 8; if (ne > 128) ne = 128;
-            hipLaunchKernelGGL(k_lammuz_fleet_enum, dim3(ne, B), dim3(NTH), 0, F->stream, devs, it);
-            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
-        } else if (F->rows) hipLaunchKernelGGL(k_lammuz_fleet_rows, dim3(nbp, B), dim3(NTH), 0, F->stream, devs, io, it, k);
-        else {
-            hipLaunchKernelGGL(k_lammuz_fleet, dim3(nbr * GS / 4, B), dim3(256), 0, F->stream, devs, it);
-            hipLaunchKernelGGL(k_lmz_finalize_fleet, dim3(nfin, B), dim3(256), 0, F->stream, devs, io, it, k);
+#undef LMZ_FLEET
         }
     }
     hipLaunchKernelGGL(k_finish_fleet, dim3(B), dim3(su::NT), F->su_lds, F->stream, devs, io, k);
@@ -3746,7 +3709,6 @@ static int fleet_scan_stage(rda_fleet *F, std::vector<SceneGrow> &grow, const do
     }
     // the members' records as they are now (the stream is idle: nothing reads the pinned mirrors)
     HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
-    fleet_refresh_flags(F);
     if (nmax > 0) {
         HIPCHK(li.fill.push(F->stream));
         HIPCHK(li.sc.push(F->stream));
@@ -4443,7 +4405,6 @@ static int fleet_upload_scenes_peers(rda_fleet *F, const int32_t *counts, const 
     fleet_peer_view(F, pv);
     HIPCHK(mirror_upload(F->pe.tab, records(pv), F->stream));
     HIPCHK(mirror_upload(F->devs, member_devs(F), F->stream));
-    fleet_refresh_flags(F);
     rc = fleet_peers_resort(F, states, controls, plan ? plans : nullptr, plan_valid);
     if (rc != RDA_OK) return rc;
     HIPCHK(fleet_wait(F));                              // the staging blocks are reused by the next call; the members' own calls see the scene
